@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 512x512 grayscale images/sec of UNet predict (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N = 1 runs in this process.  N > 1 without a torch.distributed.run environment launches N fresh rank processes itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`, before this
@@ -62,12 +62,20 @@ def parse_args(argv=None):
     ap.add_argument("--no-train-step", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--no-trained-mae", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the (B,1,H,W) fp32 prediction of rank 0) as DIR/output.npy; "
+                         "above 60 MB only the first images that fit are written.  The inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--detail", default=None, help="write the full result (per-layer tables, notes) as JSON to this file; the printed line is the compact form (< 8 KB)")
     ap.add_argument("--train-batch", type=int, default=64)
     ap.add_argument("--rehearse", action="store_true",
                     help="launcher rehearsal without GPUs: the ranks form a gloo group, run the barrier / max-over-ranks timing code around an "
                          "empty step and rank 0 prints a line marked rehearsal (tests/test_host_logic.py; never a measurement)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -154,6 +162,21 @@ def timed_steps(model, x, steps, warmup, use_dist, timer=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     return dt, y
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6            # below 64 MB with the .npy header
+
+
+def dump_outputs(out_dir, y_host) -> dict:
+    """Writes the timed path's last output as float32 DIR/output.npy: the whole batch, or its first images up to DUMP_LIMIT_BYTES."""
+    import numpy as np
+    a = y_host.float().numpy()
+    per_image = a[0].nbytes if a.shape[0] else 1
+    keep = min(a.shape[0], max(1, DUMP_LIMIT_BYTES // per_image))
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "output.npy", np.ascontiguousarray(a[:keep]))
+    return {"dir": str(d), "files": {"output": list(a[:keep].shape)}, "images": f"{keep} of {a.shape[0]}"}
 
 
 def host_cpus():
@@ -619,6 +642,8 @@ def main():
         result["other_modes"] = other
 
     y_host = y.cpu() if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        result["dumped_outputs"] = dump_outputs(args.dump_outputs, y_host)
     del model, y
     torch.cuda.empty_cache()
 

@@ -174,7 +174,7 @@ def test_unet_forward_golden_small(golden, mode, ns):
 def test_unet_intermediates_golden(golden, mode):
     g = golden["unet_fwd_small"]
     model = gpu_model(2, "he", mode)
-    _, x = images01(1, 32, 32, seed=2)
+    _, x = images01(2, 32, 32, seed=2)
     keep = {}
     out = model.forward_features(x.to(DEV), keep=keep)
     np.testing.assert_allclose(out.cpu().numpy(), g["inter_y"], atol=OUT_ATOL[mode], rtol=0)

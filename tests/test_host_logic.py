@@ -490,6 +490,25 @@ def test_bench_self_launch_runs_two_ranks_on_cpu():
     assert "import torch" not in body and "visible_gpus" in body
 
 
+def test_bench_dump_outputs_and_steps(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's prediction as float32 DIR/output.npy (whole batch, or its first images
+    below the size cap); `--steps` below 1 is refused because ms_per_step divides by it."""
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / "d")])
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 2, str(tmp_path / "d"))
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    y = torch.rand(3, 1, 8, 8)
+    info = bench.dump_outputs(tmp_path / "d", y)
+    got = np.load(tmp_path / "d" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.numpy()) and info["images"] == "3 of 3"
+    per_image = 4 * 512 * 512
+    big = torch.zeros(bench.DUMP_LIMIT_BYTES // per_image + 5, 1, 512, 512)
+    bench.dump_outputs(tmp_path / "d", big)
+    got = np.load(tmp_path / "d" / "output.npy", mmap_mode="r")
+    assert got.shape[0] == bench.DUMP_LIMIT_BYTES // per_image and (tmp_path / "d" / "output.npy").stat().st_size < 64 * 10 ** 6
+
+
 def test_train_products_setting(monkeypatch):
     """`train_products` (include/wsu.h WSU_PRODUCTS_*): default 'f16', the environment overrides, an unknown name is refused when the model is
     built -- not at the first backward."""

@@ -1,5 +1,7 @@
 import sys, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+from pathlib import Path
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
 from gpu_util import DEV, gpu_model, images01
 for n, size in ((2, 1024), (1, 2048), (3, 516), (64, 512)):
     _, x = images01(min(n, 4), size, size, seed=3)
