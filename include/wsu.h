@@ -208,6 +208,34 @@ int wsu_conv3x3_up_pack(const float* w3_oihw, const float* wt, const float* bt, 
 int wsu_conv3x3_up_q_fwd(const void* x_low, const void* x_skip, const void* w_skip_packed, const void* w_low_packed, const float* bias, void* y,
                          int n, int h, int w, int cl, int c2, int cout, int relu, unsigned* range_flag, void* stream);
 
+/* ---- K1h: the opt-in inference mode 'f16p' -- ONE product per tap: f16(w) * f16(x) on the f16 matrix pipe, fp32 accumulation, no cross terms.
+ *      A planar H tensor ("F16P" storage) holds, per image and 16-channel chunk,
+ *          plane 0 = f16 ch 0-7, plane 1 = f16 ch 8-15   as [H][W][16 B] each (round to nearest even),
+ *      i.e. the first two planes of a planar Q tensor without the Q plane and the scale bytes: a chunk is 32 H W bytes (2 B per element;
+ *      wsu_planar_h_bytes).  The kernels are the K1q / K1u / K0p kernels instantiated for this format (csrc/conv3x3_q.hip, conv3x3_qu.hip,
+ *      planar.hip); range_flag is set only when a stored value is not a finite f16 (|v| > 65504, or NaN).
+ *      wsu_conv3x3_pack_h: w (cout, cin, 3, 3) OIHW fp32 -> per (64-co block, 16-channel input chunk) an 18 KB slice [tap 9][plane 2][64 co][16 B]
+ *        (wsu_conv3x3_packed_h_bytes); cin a multiple of 16, cout of 64.
+ *      wsu_conv3x3_h_fwd: arguments as wsu_conv3x3_q_fwd on planar H tensors (x1, x2, y, y_pool; a y beside the fused head is an H tensor too);
+ *        y_format must be WSU_PLANAR_H.
+ *      wsu_conv3x3_up_pack_h: as wsu_conv3x3_up_pack, the parity-class weights combined in fp32 and rounded to f16 once -> per (64-co block,
+ *        16-channel chunk of x_low, dy) a 16 KB slice [class 4][dx 2][plane 2][64 co][16 B] (wsu_conv3x3_up_packed_h_bytes).  The skip half
+ *        is wsu_conv3x3_pack_h of w3[:, cup:].
+ *      wsu_conv3x3_up_h_fwd: as wsu_conv3x3_up_q_fwd on planar H tensors (x_low, x_skip, y).
+ *      wsu_conv3x3_first_pl_fwd with y_format WSU_PLANAR_H writes the first layer as a planar H tensor. */
+#define WSU_PLANAR_H 2
+size_t wsu_planar_h_bytes(int n, int c, int h, int w);
+size_t wsu_conv3x3_packed_h_bytes(int cin, int cout);
+int wsu_conv3x3_pack_h(const float* w_oihw, void* w_packed, int cin, int cout, void* stream);
+int wsu_conv3x3_h_fwd(const void* x1, const void* x2, const void* w_packed_h, const float* bias, void* y, void* y_pool,
+                      const float* head_w, const float* head_b, float* head_out, float* head_logit, int head_cout,
+                      int n, int h, int w, int c1, int c2, int cout, int relu, int y_format, unsigned* range_flag, void* stream);
+size_t wsu_conv3x3_up_packed_h_bytes(int cl, int cout);
+int wsu_conv3x3_up_pack_h(const float* w3_oihw, const float* wt, const float* bt, const float* b3, void* w_low_packed, float* bias_out, float* wc_dense,
+                          int cl, int cup, int c2, int cout, void* stream);
+int wsu_conv3x3_up_h_fwd(const void* x_low, const void* x_skip, const void* w_skip_packed, const void* w_low_packed, const float* bias, void* y,
+                         int n, int h, int w, int cl, int c2, int cout, int relu, unsigned* range_flag, void* stream);
+
 /* ---- K1p + K0p fused: e11 -> e12 (-> pool) of the planar path in one launch for single-plane inputs (unet.py:141-144).  The loader waves of
  *      the persistent kernel compute e11's 64 channels from the image straight into the LDS stages (instead of fetching them); bitwise the
  *      result of wsu_conv3x3_first_pl_fwd followed by wsu_conv3x3_pl_fwd, and xe11 never reaches HBM.  img (N,1,H,W) fp32, w1 (64,1,3,3),
@@ -280,7 +308,8 @@ int wsu_conv3x3_first_pl_bwd_data(const void* g, const float* w_oihw, float* dx_
  *      wsu_convt2x2_pl_fwd: nn.ConvTranspose2d(k2, s2) + bias (unet.py:125,130,177,183), x: cin channels at (h, w) planar -> y: cout channels at
  *      (2h, 2w) planar; weights from wsu_convt2x2_pack(mode F16F8); cin a multiple of 32, cout of 64.
  *      wsu_conv3x3_first_pl_fwd: the first layer e11 (unet.py:82,141), x_nchw (N, cin <= 8, H, W) fp32 -> y: cout (multiple of 16) channels planar.
- *      y_format (round 4): WSU_PLANAR_A (the format above) or WSU_PLANAR_Q (K1q; the inputs of the transposed conv stay WSU_PLANAR_A). */
+ *      y_format (round 4): WSU_PLANAR_A (the format above) or WSU_PLANAR_Q (K1q; the inputs of the transposed conv stay WSU_PLANAR_A); WSU_PLANAR_H
+ *      (K1h, mode 'f16p': the two f16 planes; range_flag only beyond +-65504). */
 int wsu_convt2x2_pl_fwd(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin, int cout,
                         int y_format, unsigned* range_flag, void* stream);
 int wsu_conv3x3_first_pl_fwd(const float* x_nchw, const float* w_oihw, const float* bias, void* y, int n, int h, int w, int cin, int cout,

@@ -24,8 +24,9 @@ MODE_F32, MODE_BF16X3, MODE_BF16, MODE_BF16X3S, MODE_F16F8, MODE_F16F8X = 0, 1, 
 MODE_F16F8P = 6          # host-side names only: the planar inference path has its own entry points (wsu_*_pl_fwd), no `mode` argument
 MODE_F16F8Q = 7          # f16f8p with x_residual = 0 on the first conv of every decoder block
 MODE_F16F4P = 8          # planar Q storage; the 3x3 convs multiply their cross terms as block-scaled fp4 (wsu_conv3x3_q_fwd)
+MODE_F16P = 9            # planar H storage (two f16 planes); the 3x3 convs multiply f16(w) * f16(x) alone (wsu_conv3x3_h_fwd)
 MODES = {"f32": MODE_F32, "bf16x3": MODE_BF16X3, "bf16": MODE_BF16, "bf16x3s": MODE_BF16X3S, "f16f8": MODE_F16F8, "f16f8x": MODE_F16F8X, "f16f8p": MODE_F16F8P, "f16f8q": MODE_F16F8Q,
-         "f16f4p": MODE_F16F4P}
+         "f16f4p": MODE_F16F4P, "f16p": MODE_F16P}
 
 
 class WsuError(RuntimeError):
@@ -61,6 +62,13 @@ SIGNATURES = {
     "wsu_conv3x3_up_packed_bytes": (c_size_t, [c_int] * 2),
     "wsu_conv3x3_up_pack": (c_int, [_P] * 7 + [c_int] * 4 + [_P]),
     "wsu_conv3x3_up_q_fwd": (c_int, [_P] * 6 + [c_int] * 7 + [_P, _P]),
+    "wsu_planar_h_bytes": (c_size_t, [c_int] * 4),
+    "wsu_conv3x3_packed_h_bytes": (c_size_t, [c_int] * 2),
+    "wsu_conv3x3_pack_h": (c_int, [_P, _P, c_int, c_int, _P]),
+    "wsu_conv3x3_h_fwd": (c_int, [_P] * 10 + [c_int] * 9 + [_P, _P]),
+    "wsu_conv3x3_up_packed_h_bytes": (c_size_t, [c_int] * 2),
+    "wsu_conv3x3_up_pack_h": (c_int, [_P] * 7 + [c_int] * 4 + [_P]),
+    "wsu_conv3x3_up_h_fwd": (c_int, [_P] * 6 + [c_int] * 7 + [_P, _P]),
     "wsu_conv3x3_pl_bwd_data_workspace_bytes": (c_size_t, [c_int] * 5),
     "wsu_conv3x3_pack_ring": (c_int, [_P, _P, c_int, c_int, _P]),
     "wsu_conv3x3_pl_bwd_data": (c_int, [_P, _P, _P, _P, c_size_t, _P, _P, c_int, _P, _P, _P, _P] + [c_int] * 7 + [_P]),

@@ -18,6 +18,9 @@
 // max-pool, fused 1x1 head + sigmoid), the last step of a tile split by accumulator tile so that its second half overlaps the first half's stores.
 // Replaces nn.Conv2d(k=3, reflect) + F.relu (+ torch.cat, nn.MaxPool2d, outconv + sigmoid) of src/unet/model/unet.py:141-189.
 // Weights: wsu_conv3x3_pack_f4 (below).
+// Format H (mode 'f16p', include/wsu.h K1h): the same kernel instantiated with FMT = WSU_PLANAR_H -- the f16 products alone (9 instead of 14 matrix
+// units per chunk), two f16 planes in and out (2 B per element), 18 + 20 DMA pieces per step, an epilogue of bias, ReLU, f16 conversion and stores
+// (pool and head as above); weights: wsu_conv3x3_pack_h.
 #include "wsu_device.h"
 #include <cstdlib>
 
@@ -55,6 +58,20 @@ static_assert(LDS_TOTAL <= 160 * 1024 && W_SLOT % 1024 == 0, "LDS budget");
 constexpr int NLOAD = 4;
 constexpr int W_PIECES = W_SLOT / 1024;                   // 28
 constexpr unsigned OOB = 0xFFFFFFF0u;                     // beyond any descriptor: a store is dropped
+// Format H (mode 'f16p', WSU_PLANAR_H): an input slot holds the two f16 planes only, a weight slot [tap 9][plane 2][64 co][16 B] -- no Q plane,
+// no scale bytes, no fp4 weight plane.  QGeo<FMT>: the LDS geometry of the kernel instantiated for storage format FMT.
+constexpr int IN_SLOT_H = 2 * PLANE;                      // 19584
+constexpr int W_SLOT_H = 9 * 2 * WSU_COB * 16;            // 18432 = 18 DMA pieces: the packed slice of a (block, chunk) (wsu_conv3x3_pack_h)
+template <int FMT> struct QGeo {
+    static_assert(FMT == WSU_PLANAR_Q || FMT == WSU_PLANAR_H, "conv3x3_q_kernel formats: Q and H");
+    static constexpr bool H = FMT == WSU_PLANAR_H;
+    static constexpr int in_slot = H ? IN_SLOT_H : IN_SLOT, w_slot = H ? W_SLOT_H : W_SLOT;
+    static constexpr int w_planes = H ? 2 : 3;                                   // weight granule planes per tap
+    static constexpr int w_base = NIN * in_slot, lds_extra = w_base + NWS * w_slot;
+    static constexpr int lds_total = lds_extra + 1024 * 4 + 4 * 64 * 4 + 16;      // H: 100752
+    static constexpr int w_pieces = w_slot / 1024;
+};
+static_assert(QGeo<WSU_PLANAR_Q>::lds_total == LDS_TOTAL && QGeo<WSU_PLANAR_Q>::w_pieces == W_PIECES && W_SLOT_H % 1024 == 0, "LDS geometry");
 
 struct QArgs {
     const char* x1; const char* x2; const char* wp; const float* bias;
@@ -94,15 +111,18 @@ __device__ __forceinline__ float dpp_xor1(float v) {       // value of lane ^ 1 
 // 16 bytes per lane, S: one byte per lane into a dword slot); waves 0 / 1 (three segments = 12 pieces) take 5 weight pieces, waves 2 / 3 (8) take
 // 9: 17 DMA instructions per wave and step.  Issue order of a wave: W(0) IN(0) IN(1) | barrier 0 | W(1) IN(2) | barrier 1 | W(2) IN(3) | ...;
 // `s_waitcnt vmcnt(n)` = all but the n youngest have landed, so before barrier j + 1 the wave waits for everything but IN(j + 2).
-template <int LW>
+// Format H: two input pieces per segment (12 / 8 per wave) and 18 weight pieces (3 / 3 / 6 / 6): 9, 9, 10, 10 DMA instructions per wave and step.
+template <int FMT, int LW>
 __device__ __forceinline__ void q_loader(const QArgs& a, char* smem, int lane, int lw, int G, int J) {
+    using Gm = QGeo<FMT>;
     constexpr int NSEG = LW < 2 ? 3 : 2;
-    constexpr int NIN_OPS = 4 * NSEG;
-    constexpr int W0 = LW < 2 ? LW * 5 : 10 + (LW - 2) * 9, NWP = LW < 2 ? 5 : 9;
-    static_assert(2 * 5 + 2 * 9 == W_PIECES, "weight pieces over the loader waves");
+    constexpr int NIN_OPS = (Gm::H ? 2 : 4) * NSEG;
+    constexpr int W0 = Gm::H ? (LW < 2 ? LW * 3 : 6 + (LW - 2) * 6) : (LW < 2 ? LW * 5 : 10 + (LW - 2) * 9);
+    constexpr int NWP = Gm::H ? (LW < 2 ? 3 : 6) : (LW < 2 ? 5 : 9);
+    static_assert(2 * 5 + 2 * 9 == W_PIECES && 2 * 3 + 2 * 6 == QGeo<WSU_PLANAR_H>::w_pieces, "weight pieces over the loader waves");
     lds_char* smem3 = (lds_char*)smem;
     const unsigned hw16 = (unsigned)(a.h * a.w) * 16u;
-    const unsigned chunk_bytes = (unsigned)wsu_q_chunk_bytes(a.h, a.w);
+    const unsigned chunk_bytes = Gm::H ? (unsigned)wsu_h_chunk_bytes(a.h, a.w) : (unsigned)wsu_q_chunk_bytes(a.h, a.w);
     unsigned voff[NSEG], soff[NSEG];
     auto plan = [&](const Tile& t) __attribute__((always_inline)) {
         WSU_STATIC_FOR(NSEG, k, {
@@ -110,7 +130,7 @@ __device__ __forceinline__ void q_loader(const QArgs& a, char* smem, int lane, i
             const int r = idx / IW, c = idx - r * IW;
             const int yy = wsu_reflect(t.y0 - 1 + r, a.h), xx = wsu_reflect(t.x0 - 1 + c, a.w);
             voff[k] = (unsigned)(yy * a.w + xx) * 16u;
-            soff[k] = 3u * hw16 + wsu_q_soff(yy, xx, a.tiles_x);
+            if constexpr (!Gm::H) soff[k] = 3u * hw16 + wsu_q_soff(yy, xx, a.tiles_x);
         });
     };
     Tile ti = tile_of(a, lw); int ci = 0, kti = 0;                    // cursor of the input issue
@@ -118,23 +138,25 @@ __device__ __forceinline__ void q_loader(const QArgs& a, char* smem, int lane, i
     auto issue_in = [&](int s) __attribute__((always_inline)) {
         const char* in_src = ci < a.nch1 ? a.x1 + ((size_t)ti.n * a.nch1 + ci) * chunk_bytes : a.x2 + ((size_t)ti.n * (a.nch - a.nch1) + (ci - a.nch1)) * chunk_bytes;
         const auto rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(in_src), 0, (int)chunk_bytes, 0x00020000);
-        lds_char* slot = smem3 + (s % NIN) * IN_SLOT;
+        lds_char* slot = smem3 + (s % NIN) * Gm::in_slot;
         WSU_STATIC_FOR(NSEG, k, {
             constexpr int seg = LW + NLOAD * k;
             const bool live = seg < IN_SEG - 1 || lane < NPIX - (IN_SEG - 1) * 64;
             if (live) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(slot + seg * 1024), 16, voff[k], 0, 0, 0);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(slot + PLANE + seg * 1024), 16, voff[k], (int)hw16, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(slot + 2 * PLANE + seg * 1024), 16, voff[k], (int)(2u * hw16), 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(slot + 3 * PLANE + seg * 256), 1, soff[k], 0, 0, 0);
+                if constexpr (!Gm::H) {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(slot + 2 * PLANE + seg * 1024), 16, voff[k], (int)(2u * hw16), 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(slot + 3 * PLANE + seg * 256), 1, soff[k], 0, 0, 0);
+                }
             }
         });
         if (++ci == a.nch && s + 1 < J) { ci = 0; ++kti; ti = tile_of(a, lw + kti * G); plan(ti); }
     };
     auto issue_w = [&](int s) __attribute__((always_inline)) {
         const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.wp), 0, 0x7FFFFFF0, 0x00020000);
-        const int w_base = (cbw * a.nch + cw) * W_SLOT;
-        lds_char* slot = smem3 + W_BASE + (s % NWS) * W_SLOT;
+        const int w_base = (cbw * a.nch + cw) * Gm::w_slot;
+        lds_char* slot = smem3 + Gm::w_base + (s % NWS) * Gm::w_slot;
         WSU_STATIC_FOR(NWP, k, {
             constexpr int piece = W0 + k;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(slot + piece * 1024), 16, (unsigned)lane * 16u, w_base + piece * 1024, 0, 0);
@@ -274,9 +296,14 @@ __device__ __forceinline__ void q_loader_f1(const QArgs& a, char* smem, int lane
 // FQ: the stored outputs (y, y_pool) are planar Q tensors (else the e4m3-residual format of conv3x3_pl.hip: what the transposed convs read).
 // MSPLIT (small grids): a work item is HALF a tile's output channels (m-half = item & 1).
 // F1: the input channels (64 = e11's outputs) are computed from the image by the loader waves (q_loader_f1) instead of fetched.
-template <int RQ, int HC, bool POOL, bool FQ, bool MSPLIT, bool F1 = false>
+// FMT: storage format of the inputs and of the planar outputs -- WSU_PLANAR_Q (mode 'f16f4p': f16 products + fp4 cross terms) or WSU_PLANAR_H (mode
+// 'f16p': the f16 products alone, f16 planes in and out; FQ is then unused and set, F1 and RQ = 4 are not instantiated).
+template <int RQ, int HC, bool POOL, bool FQ, bool MSPLIT, bool F1 = false, int FMT = WSU_PLANAR_Q>
 __global__ __launch_bounds__((16 / RQ + NLOAD) * 64) __attribute__((amdgpu_waves_per_eu(RQ == 4 ? 2 : 3, RQ == 4 ? 2 : 3)))
 void conv3x3_q_kernel(const QArgs a) {
+    using Gm = QGeo<FMT>;
+    constexpr bool H = Gm::H;
+    static_assert(!(H && F1), "the fused first layer computes Q inputs");
     constexpr int NWAVE = 16 / RQ, NT = (NWAVE + NLOAD) * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -287,7 +314,7 @@ void conv3x3_q_kernel(const QArgs a) {
     const int K = a.ntiles > lw ? (a.ntiles - lw + G - 1) / G : 0;           // tiles walked by this workgroup
     const int J = K * a.nch;                                                  // chunk steps
 
-    float* s_bias = reinterpret_cast<float*>(smem + LDS_EXTRA);
+    float* s_bias = reinterpret_cast<float*>(smem + Gm::lds_extra);
     float* s_hw = s_bias + 1024;
     float* s_hb = s_hw + 4 * 64;
     for (int i = tid; i < a.cout; i += NT) s_bias[i] = a.bias ? a.bias[i] : 0.f;
@@ -302,10 +329,10 @@ void conv3x3_q_kernel(const QArgs a) {
     if (wv >= NWAVE) {
         if constexpr (F1) { q_loader_f1(a, smem, lane, lw, G, J, wv - NWAVE); return; }
         switch (wv - NWAVE) {
-            case 0: q_loader<0>(a, smem, lane, lw, G, J); break;
-            case 1: q_loader<1>(a, smem, lane, lw, G, J); break;
-            case 2: q_loader<2>(a, smem, lane, lw, G, J); break;
-            default: q_loader<3>(a, smem, lane, lw, G, J); break;
+            case 0: q_loader<FMT, 0>(a, smem, lane, lw, G, J); break;
+            case 1: q_loader<FMT, 1>(a, smem, lane, lw, G, J); break;
+            case 2: q_loader<FMT, 2>(a, smem, lane, lw, G, J); break;
+            default: q_loader<FMT, 3>(a, smem, lane, lw, G, J); break;
         }
         return;
     }
@@ -313,7 +340,7 @@ void conv3x3_q_kernel(const QArgs a) {
     // ================= matrix waves ===================================================================================================
     Tile cur = tile_of(a, lw);
     constexpr int MH = MSPLIT ? 1 : 2;                                        // accumulator tiles along the output channels
-    constexpr bool PIPE = RQ == 4 || WSU_Q_PIPE2;                             // explicit software pipeline of the fragment reads (below)
+    constexpr bool PIPE = (RQ == 4 || WSU_Q_PIPE2) && !H;                     // explicit software pipeline of the fragment reads (below)
     constexpr bool EPO = WSU_Q_EPO && !MSPLIT && HC == 0 && RQ != 4;
     f32x16 acc[2][4];                                                         // [MH][RQ] used (fixed bounds: a template-dependent bound made hipcc (ROCm 7.2) drop the host stubs)
     int kt = 0, j = 0;
@@ -324,7 +351,7 @@ void conv3x3_q_kernel(const QArgs a) {
     auto begin_step = [&]() __attribute__((always_inline)) {
         __builtin_amdgcn_s_barrier();                                         // the loaders' pieces landed; everyone left the slots that are refilled next
         asm volatile("" ::: "memory");
-        q_in_off = (unsigned)(j % NIN) * IN_SLOT; q_w_off = W_BASE + (unsigned)(j % NWS) * W_SLOT;
+        q_in_off = (unsigned)(j % NIN) * Gm::in_slot; q_w_off = Gm::w_base + (unsigned)(j % NWS) * Gm::w_slot;
         ldsA = smem + q_w_off + (cur.mh * 32 + l31) * 16;
         ldsB = smem + q_in_off + ((RQ * wv) * IW + l31) * 16;
         hh_q = hh;
@@ -343,7 +370,7 @@ void conv3x3_q_kernel(const QArgs a) {
         constexpr int ms = decltype(ms_c)::value, ML = ms < 0 ? 0 : ms, MU = ms < 0 ? MH : ms + 1;
         u32x4 ah[2], bh[4];
 _Pragma("unroll")
-        for (int m = ML; m < MU; ++m) ah[m] = *reinterpret_cast<const u32x4*>(ldsA + ((tap * 3 + hh) * 64 + m * 32) * 16);
+        for (int m = ML; m < MU; ++m) ah[m] = *reinterpret_cast<const u32x4*>(ldsA + ((tap * Gm::w_planes + hh) * 64 + m * 32) * 16);
 _Pragma("unroll")
         for (int q = 0; q < RQ; ++q) bh[q] = *reinterpret_cast<const u32x4*>(ldsB + hh * PLANE + ((q + dy) * IW + dx) * 16);
 _Pragma("unroll")
@@ -395,7 +422,7 @@ _Pragma("unroll")
         if constexpr (EPO) asm volatile("" : "+v"(hh_q));                     // (per call: the paths of a step must not share -- and hoist -- their lane offsets)
         WSU_STATIC_FOR(hi - lo, i, {
             constexpr int tp = lo + i;
-            if constexpr (!(WSU_Q_PROBE_NOX8 && tp == 4)) cross_q4(std::integral_constant<int, tp>{}, ms_c);
+            if constexpr (!H && !(WSU_Q_PROBE_NOX8 && tp == 4)) cross_q4(std::integral_constant<int, tp>{}, ms_c);
             main_term(std::integral_constant<int, 2 * tp>{}, ms_c);
             if constexpr (2 * tp + 1 < 9) main_term(std::integral_constant<int, 2 * tp + 1>{}, ms_c);
         });
@@ -521,6 +548,11 @@ _Pragma("unroll")
             __builtin_amdgcn_raw_buffer_store_b128(qg, rs, (int)((ok && !hh) ? off + 2u * plane_bytes : OOB), 0, 0);
             __builtin_amdgcn_raw_buffer_store_b8((unsigned char)sb, rs, (int)((ok && !hh) ? 3u * plane_bytes + soff : OOB), 0, 0);
         };
+        // format H: the f16 granules alone -- lanes 0-31 store plane 0 (ch 0-7), lanes 32-63 plane 1 (ch 8-15)
+        auto store_one_h = [&](const f32x4& X, const f32x4& Y, char* base, unsigned plane_bytes, unsigned off, bool ok, bool have) __attribute__((always_inline)) {
+            const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, have ? (int)(2u * plane_bytes) : 0, 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b128(wsu_h_granule(X, Y), rs, (int)(ok ? off + (hh ? plane_bytes : 0u) : OOB), 0, 0);
+        };
         // format A (the e4m3-residual format of conv3x3_pl.hip: f16 | f16 | e4m3((x - f16 x) * 2^12))
         auto store_one_a = [&](const f32x4& X, const f32x4& Y, char* base, unsigned plane_bytes, unsigned off, bool ok, bool have) __attribute__((always_inline)) {
             uint32_t xh0, xh1, xlo, yh0, yh1, ylo;
@@ -571,7 +603,12 @@ _Pragma("unroll")
                     }
                     const int r0 = RQ * wv + 2 * rp, row0 = cur.y0 + r0;
                     if (!HEAD || have_y) {
-                        if constexpr (FQ) {
+                        if constexpr (H) {
+                            char* base = a.y + ((size_t)cur.n * nco + oc) * (2u * hw16);
+                            WSU_STATIC_FOR(2, u, {
+                                store_one_h(vx[u], vy[u], base, hw16, (unsigned)((row0 + u) * a.w + col) * 16u, row0 + u < a.h && col < a.w, have_y);
+                            });
+                        } else if constexpr (FQ) {
                             const unsigned cb_ = (unsigned)wsu_q_chunk_bytes(a.h, a.w);
                             char* base = a.y + ((size_t)cur.n * nco + oc) * cb_;
                             const unsigned sblk = (unsigned)(((cur.y0 >> 4) * a.tiles_x + (cur.x0 >> 5)) * 512);
@@ -601,7 +638,12 @@ _Pragma("unroll")
                     const int gy0 = (cur.y0 >> 1) + (RQ / 2) * wv, gx = (cur.x0 >> 1) + (l31 >> 1);
                     const bool okx = !(l31 & 1) && gx < wp2;
                     const unsigned php16 = (unsigned)(hp * wp2) * 16u;
-                    if constexpr (FQ) {
+                    if constexpr (H) {
+                        char* base = a.ypool + ((size_t)cur.n * nco + oc) * (2u * php16);
+#pragma unroll
+                        for (int rp = 0; rp < RQ / 2; ++rp)
+                            store_one_h(px[rp], py[rp], base, php16, (unsigned)((gy0 + rp) * wp2 + gx) * 16u, okx && gy0 + rp < hp, true);
+                    } else if constexpr (FQ) {
                         const unsigned cbp = (unsigned)wsu_q_chunk_bytes(hp, wp2);
                         const int ptx = (wp2 + 31) >> 5;
                         char* base = a.ypool + ((size_t)cur.n * nco + oc) * cbp;
@@ -659,7 +701,8 @@ _Pragma("unroll")
             }
         }
         // beyond +-448 the e4m3 residual of format A saturates (plain f16 accuracy), beyond +-65504 the f16 part overflows: tell the caller once
-        if (a.range_flag && (a.y || POOL) && __builtin_amdgcn_ballot_w64(!(vmax <= WSU_F8_RANGE)) != 0 && lane == 0)
+        // (format H has no residual: only a value that is not a finite f16 counts)
+        if (a.range_flag && (a.y || POOL) && __builtin_amdgcn_ballot_w64(!(vmax <= (H ? WSU_F16_RANGE : WSU_F8_RANGE))) != 0 && lane == 0)
             atomicOr(a.range_flag, 1u);
         ++kt;
         if (j + 1 < J) cur = tile_of(a, lw + kt * G);
@@ -722,6 +765,28 @@ __global__ void pack_conv3x3_f4_kernel(const float* __restrict__ w, char* __rest
     }
 }
 
+// one thread per (block, chunk, tap, co): 16 weights -> the two f16 granules of format H (layout: wsu_conv3x3_pack_h below)
+__global__ void pack_conv3x3_h_kernel(const float* __restrict__ w, char* __restrict__ dst, int cin, int cout) {
+    const int nch = cin / 16;
+    const long long total = (long long)(cout / WSU_COB) * nch * 9 * WSU_COB;
+    for (long long d = (long long)blockIdx.x * blockDim.x + threadIdx.x; d < total; d += (long long)gridDim.x * blockDim.x) {
+        long long t = d;
+        const int co = (int)(t % WSU_COB); t /= WSU_COB;
+        const int tap = (int)(t % 9); t /= 9;
+        const int c = (int)(t % nch); const int cb = (int)(t / nch);
+        uint32_t h[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const size_t i0 = (((size_t)(cb * WSU_COB + co) * cin + c * 16 + 2 * e) * 3 + tap / 3) * 3 + tap % 3;
+            const _Float16 a = (_Float16)w[i0], b = (_Float16)w[i0 + 9];                      // channels 2e, 2e + 1: round to nearest even
+            h[e] = (uint32_t)__builtin_bit_cast(unsigned short, a) | ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
+        }
+        char* base = dst + ((size_t)cb * nch + c) * W_SLOT_H + (size_t)(tap * 2) * (WSU_COB * 16) + co * 16;
+        *reinterpret_cast<u32x4*>(base) = mk_u4(h[0], h[1], h[2], h[3]);
+        *reinterpret_cast<u32x4*>(base + WSU_COB * 16) = mk_u4(h[4], h[5], h[6], h[7]);
+    }
+}
+
 #define WSU_Q_INST(RQ) \
     template __global__ void conv3x3_q_kernel<RQ, 0, false, false, false>(const QArgs); \
     template __global__ void conv3x3_q_kernel<RQ, 0, false, true, false>(const QArgs);  \
@@ -734,6 +799,12 @@ __global__ void pack_conv3x3_f4_kernel(const float* __restrict__ w, char* __rest
 WSU_Q_INST(4)
 WSU_Q_INST(2)
 template __global__ void conv3x3_q_kernel<2, 0, true, true, false, true>(const QArgs);
+// format H (mode 'f16p'): plain, pool, head (1 / 4 planes) and the half-block variant of small grids, RQ = 2
+template __global__ void conv3x3_q_kernel<2, 0, false, true, false, false, WSU_PLANAR_H>(const QArgs);
+template __global__ void conv3x3_q_kernel<2, 0, true, true, false, false, WSU_PLANAR_H>(const QArgs);
+template __global__ void conv3x3_q_kernel<2, 1, false, true, false, false, WSU_PLANAR_H>(const QArgs);
+template __global__ void conv3x3_q_kernel<2, 4, false, true, false, false, WSU_PLANAR_H>(const QArgs);
+template __global__ void conv3x3_q_kernel<2, 0, false, true, true, false, WSU_PLANAR_H>(const QArgs);
 
 template <int RQ>
 int q_launch_rq(QArgs a, int yq, hipStream_t s, int ncu, bool msplit_on) {
@@ -765,6 +836,36 @@ int q_launch_rq(QArgs a, int yq, hipStream_t s, int ncu, bool msplit_on) {
     else if (yq) hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 0, false, true, false>), g, b, LDS_TOTAL, s, a);
     else hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 0, false, false, false>), g, b, LDS_TOTAL, s, a);
     return wsu_check_launch("conv3x3_q_kernel");
+}
+
+// format H: the launch choices of q_launch_rq<2> on the H instantiations
+int h_launch(QArgs a, hipStream_t s, int ncu, bool msplit_on) {
+    constexpr int HF = WSU_PLANAR_H, NT = (8 + NLOAD) * 64, LDS = QGeo<HF>::lds_total;
+    static bool attr_done = false;
+    if (!attr_done) {
+        const void* fns[5] = {reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 0, false, true, false, false, HF>),
+                              reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 0, true, true, false, false, HF>),
+                              reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 1, false, true, false, false, HF>),
+                              reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 4, false, true, false, false, HF>),
+                              reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 0, false, true, true, false, HF>)};
+        for (const void* fn : fns) {
+            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_q<H>): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        }
+        attr_done = true;
+    }
+    a.msplit = 0;
+    if (msplit_on && !a.head_w && !a.ypool && 2 * (long long)a.ntiles <= ncu) {       // small grids: half-block work items
+        a.msplit = 1; a.ncb *= 2; a.ntiles *= 2;
+        hipLaunchKernelGGL((conv3x3_q_kernel<2, 0, false, true, true, false, HF>), dim3(a.ntiles), dim3(NT), LDS, s, a);
+        return wsu_check_launch("conv3x3_q_kernel<H, msplit>");
+    }
+    const dim3 g(a.ntiles < ncu ? a.ntiles : ncu), b(NT);
+    if (a.head_w && a.head_cout == 1) hipLaunchKernelGGL((conv3x3_q_kernel<2, 1, false, true, false, false, HF>), g, b, LDS, s, a);
+    else if (a.head_w) hipLaunchKernelGGL((conv3x3_q_kernel<2, 4, false, true, false, false, HF>), g, b, LDS, s, a);
+    else if (a.ypool) hipLaunchKernelGGL((conv3x3_q_kernel<2, 0, true, true, false, false, HF>), g, b, LDS, s, a);
+    else hipLaunchKernelGGL((conv3x3_q_kernel<2, 0, false, true, false, false, HF>), g, b, LDS, s, a);
+    return wsu_check_launch("conv3x3_q_kernel<H>");
 }
 
 }  // namespace
@@ -877,6 +978,66 @@ int wsu_conv3x3_q_fwd(const void* x1, const void* x2, const void* w_packed_f4, c
     a.ablate = ablate;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return rq != 4 ? q_launch_rq<2>(a, y_format == WSU_PLANAR_Q, s, ncu, msplit_on != 0) : q_launch_rq<4>(a, y_format == WSU_PLANAR_Q, s, ncu, msplit_on != 0);
+}
+
+// ---- format H (mode 'f16p', include/wsu.h K1h) ----------------------------------------------------------------------------------------
+// Bytes of a planar H tensor: n * c/16 chunks of 32 h w bytes.
+size_t wsu_planar_h_bytes(int n, int c, int h, int w) {
+    if (n <= 0 || c <= 0 || c % 16 || h <= 0 || w <= 0) return 0;
+    return (size_t)n * (size_t)(c / 16) * wsu_h_chunk_bytes(h, w);
+}
+
+// Weights of the one-product conv: per (64-channel output block, 16-channel input chunk) one 18 KB slice [tap 9][plane 2][64 co][16 B], planes
+// f16 ci 0-7 | f16 ci 8-15 (round to nearest even).
+size_t wsu_conv3x3_packed_h_bytes(int cin, int cout) {
+    if (cin <= 0 || cout <= 0 || cin % 16 || cout % WSU_COB) return 0;
+    return (size_t)(cout / WSU_COB) * (cin / 16) * W_SLOT_H;
+}
+int wsu_conv3x3_pack_h(const float* w_oihw, void* w_packed, int cin, int cout, void* stream) {
+    WSU_REQUIRE(w_oihw && w_packed, "conv3x3_pack_h: null pointer");
+    WSU_REQUIRE(cin > 0 && cin % 16 == 0 && cout > 0 && cout % WSU_COB == 0, "conv3x3_pack_h: cin=%d must be a multiple of 16, cout=%d of %d", cin, cout, WSU_COB);
+    hipLaunchKernelGGL(pack_conv3x3_h_kernel, dim3(512), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, (char*)w_packed, cin, cout);
+    return wsu_check_launch("pack_conv3x3_h_kernel");
+}
+
+// Forward 3x3 reflect conv + bias + ReLU (+ pool, + head) in the one-product arithmetic on planar H tensors: the arguments of wsu_conv3x3_q_fwd,
+// weights of wsu_conv3x3_pack_h, y_format WSU_PLANAR_H (x1, x2, y, y_pool and a y beside the head are H tensors).
+int wsu_conv3x3_h_fwd(const void* x1, const void* x2, const void* w_packed_h, const float* bias, void* y, void* y_pool,
+                      const float* head_w, const float* head_b, float* head_out, float* head_logit, int head_cout,
+                      int n, int h, int w, int c1, int c2, int cout, int relu, int y_format, unsigned* range_flag, void* stream) {
+    WSU_REQUIRE(x1 && w_packed_h && (y || y_pool || head_w), "conv3x3_h: null pointer");
+    WSU_REQUIRE(y_format == WSU_PLANAR_H, "conv3x3_h: y_format must be WSU_PLANAR_H");
+    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2, "conv3x3_h: bad shape n=%d h=%d w=%d (reflect pad 1 needs h,w >= 2)", n, h, w);
+    WSU_REQUIRE(c1 > 0 && c1 % 16 == 0 && c2 >= 0 && c2 % 16 == 0 && (c2 == 0) == (x2 == nullptr), "conv3x3_h: c1=%d c2=%d must be multiples of 16", c1, c2);
+    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= 1024, "conv3x3_h: cout=%d must be a multiple of %d (<= 1024)", cout, WSU_COB);
+    WSU_REQUIRE(!head_w || (head_out && cout == WSU_COB && head_cout >= 1 && head_cout <= 4), "conv3x3_h: fused head needs cout == %d and 1..4 head planes", WSU_COB);
+    WSU_REQUIRE(!y_pool || (h % 2 == 0 && w % 2 == 0), "conv3x3_h: fused pool needs even h, w (got h=%d w=%d)", h, w);
+    WSU_REQUIRE(!(y_pool && head_w), "conv3x3_h: the fused pool and the fused head exclude each other");
+    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "conv3x3_h: h*w too large (a chunk must stay below 4 GiB)");
+    QArgs a;
+    a.x1 = (const char*)x1; a.x2 = (const char*)x2; a.wp = (const char*)w_packed_h; a.bias = bias;
+    a.y = (char*)y; a.ypool = (char*)y_pool;
+    a.head_w = head_w; a.head_b = head_b; a.head_out = head_out; a.head_logit = head_logit; a.head_cout = head_cout;
+    a.range_flag = range_flag;
+    a.n = n; a.h = h; a.w = w; a.c1 = c1; a.c2 = c2; a.cout = cout;
+    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ncb = cout / WSU_COB;
+    a.nch1 = c1 / 16; a.nch = (c1 + c2) / 16; a.relu = relu;
+    a.img = nullptr; a.w1 = nullptr; a.b1 = nullptr;
+    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
+    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_h: %lld tiles out of range", nt);
+    a.ntiles = (int)nt;
+    static int ncu = 0, msplit_on = 1, ablate = 0;
+    if (ncu == 0) {
+        int dev = 0; hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
+            wsu_set_error("conv3x3_h: cannot query the device"); return WSU_ERR_HIP;
+        }
+        const char* e = getenv("WSU_PL_MSPLIT"); msplit_on = e ? atoi(e) : 1;
+        e = getenv("WSU_PL_ABLATE"); ablate = e ? atoi(e) : 0;
+        ncu = prop.multiProcessorCount;
+    }
+    a.ablate = ablate;
+    return h_launch(a, static_cast<hipStream_t>(stream), ncu, msplit_on != 0);
 }
 
 }  // extern "C"

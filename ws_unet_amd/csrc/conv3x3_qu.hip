@@ -22,6 +22,9 @@
 //     their outstanding DMA instructions per allocation (`s_waitcnt vmcnt(n)`).
 // Accuracy: Wc is formed in fp32 and then split like any weight (f16 + fp4 residual terms); `xu` is never rounded to storage -- the fused
 // result is closer to the exact composition than the two-kernel path.  Replaces ops.convt2x2_pl + ops.conv3x3_q in UNet._forward_planar.
+// Format H (mode 'f16p', template argument FMT = WSU_PLANAR_H): planar H tensors in and out, the f16 products alone (no fp4 instruction, no Q /
+// scale pieces), Wc rounded to f16 once; the same ring of five slots, each step's allocations smaller (skip input 19.1 KB, weights 18 KB; low
+// input 10.3 KB, half a low chunk's weights 16 KB).
 #include "wsu_device.h"
 #include <cstdlib>
 
@@ -53,6 +56,10 @@ constexpr int LDS_TOTAL = LDS_BIAS + MAX_COUT * 4;        // 163328
 static_assert(SLOT >= IN_S && SLOT >= IN_L && SLOT >= W_L && SLOT >= W_S && SLOT % 16 == 0 && LDS_TOTAL <= 160 * 1024, "LDS budget");
 constexpr int NLOAD = 4, NWAVE = 8, NT = (NWAVE + NLOAD) * 64;
 constexpr unsigned OOB = 0xFFFFFFF0u;
+// format H: weight slices without the fp4 plane and the scale bytes
+constexpr int W_S_H = 9 * 2 * WSU_COB * 16;               // 18432: the (block, chunk) slice of wsu_conv3x3_pack_h
+constexpr int W_L_H = W_UNITS_L * 2 * WSU_COB * 16;       // 16384: [class 4][dx 2][plane 2][64 co][16 B]
+constexpr int PIECES_S_H = W_S_H / 1024, PIECES_L_H = W_L_H / 1024;   // 18, 16
 
 struct UArgs {
     const char* xl; const char* xs; const char* wps; const char* wpl; const float* bias;
@@ -97,17 +104,24 @@ __device__ __forceinline__ int step_allocs(const UArgs& a, int s) { return (s >=
 __device__ __forceinline__ bool step_is_l0(const UArgs& a, int s) { return s >= a.nchS && !((s - a.nchS) & 1); }
 
 // ================= loader wave LW: pure DMA, walks the allocation sequence ahead of the matrix waves ==========================================
-template <int LW>
+// Format H: two input pieces per segment; skip weights 3 / 3 / 6 / 6 pieces, low weights 3 / 3 / 5 / 5 (the low input: 4 / 4 / 2 / 2).
+template <int FMT, int LW>
 __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, int lw, int G, int K) {
+    constexpr bool H = FMT == WSU_PLANAR_H;
     constexpr int NSS = LW < 2 ? 3 : 2;                   // skip-input segments LW, LW + 4, LW + 8 (< 10)
     constexpr int NSL = LW < 2 ? 2 : 1;                   // low-input segments LW, LW + 4 (< 6)
-    constexpr int OPS_INS = 4 * NSS, OPS_INL = 4 * NSL;
-    constexpr int WS0 = LW < 2 ? LW * 5 : 10 + (LW - 2) * 9, NWS = LW < 2 ? 5 : 9;
-    constexpr int WL0 = LW < 2 ? LW * 5 : (LW == 2 ? 10 : 17), NWL = LW < 2 ? 5 : (LW == 2 ? 7 : 8);
+    constexpr int OPS_INS = (H ? 2 : 4) * NSS, OPS_INL = (H ? 2 : 4) * NSL;
+    constexpr int WS0 = H ? (LW < 2 ? LW * 3 : 6 + (LW - 2) * 6) : (LW < 2 ? LW * 5 : 10 + (LW - 2) * 9);
+    constexpr int NWS = H ? (LW < 2 ? 3 : 6) : (LW < 2 ? 5 : 9);
+    constexpr int WL0 = H ? (LW < 2 ? LW * 3 : 6 + (LW - 2) * 5) : (LW < 2 ? LW * 5 : (LW == 2 ? 10 : 17));
+    constexpr int NWL = H ? (LW < 2 ? 3 : 5) : (LW < 2 ? 5 : (LW == 2 ? 7 : 8));
+    constexpr int WSLICE_S = H ? W_S_H : W_S, WSLICE_L = H ? W_L_H : W_L;
     static_assert(2 * 5 + 2 * 9 == PIECES_S && 2 * 5 + 7 + 8 == PIECES_L, "weight pieces over the loader waves");
+    static_assert(2 * 3 + 2 * 6 == PIECES_S_H && 2 * 3 + 2 * 5 == PIECES_L_H, "weight pieces over the loader waves (format H)");
     lds_char* smem3 = (lds_char*)smem;
     const unsigned hw16 = (unsigned)(a.h * a.w) * 16u, hwl16 = (unsigned)(a.hl * a.wl) * 16u;
-    const unsigned cbytes_s = (unsigned)wsu_q_chunk_bytes(a.h, a.w), cbytes_l = (unsigned)wsu_q_chunk_bytes(a.hl, a.wl);
+    const unsigned cbytes_s = H ? (unsigned)wsu_h_chunk_bytes(a.h, a.w) : (unsigned)wsu_q_chunk_bytes(a.h, a.w);
+    const unsigned cbytes_l = H ? (unsigned)wsu_h_chunk_bytes(a.hl, a.wl) : (unsigned)wsu_q_chunk_bytes(a.hl, a.wl);
     const int T = a.nchS + 2 * a.nchL, A = 2 * a.nchS + 3 * a.nchL;
     const int J = K * T, total = K * A;
     if (J <= 0) return;
@@ -120,14 +134,14 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
             int yy = wsu_reflect(t.y0 - 1 + 2 * lr + (p >> 1), a.h), xx = wsu_reflect(t.x0 - 1 + 2 * lc + (p & 1), a.w);
             if (a.ablate & 32) { yy = wsu_reflect(t.y0 - 1 + idx / 34, a.h); xx = wsu_reflect(t.x0 - 1 + idx % 34, a.w); }      // (32: the natural row-major tile -- no gather; results wrong)
             voS[k] = (unsigned)(yy * a.w + xx) * 16u;
-            soS[k] = 3u * hw16 + wsu_q_soff(yy, xx, a.tiles_x);
+            if constexpr (!H) soS[k] = 3u * hw16 + wsu_q_soff(yy, xx, a.tiles_x);
         });
         WSU_STATIC_FOR(NSL, k, {
             const int idx = min((LW + NLOAD * k) * 64 + lane, NPIX_L - 1);
             const int r = idx / LP, c = min(idx - r * LP, LW_ - 1);                 // (columns 18..32 of a row are padding: any valid pixel)
             const int yy = min(max((t.y0 >> 1) - 1 + r, 0), a.hl - 1), xx = min(max((t.x0 >> 1) - 1 + c, 0), a.wl - 1);
             voL[k] = (unsigned)(yy * a.wl + xx) * 16u;
-            soL[k] = 3u * hwl16 + wsu_q_soff(yy, xx, a.ltiles_x);
+            if constexpr (!H) soL[k] = 3u * hwl16 + wsu_q_soff(yy, xx, a.ltiles_x);
         });
     };
     // ---- the allocation cursor
@@ -149,8 +163,10 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
                 if (seg < SEG_S - 1 || lane < NPIX_S - (SEG_S - 1) * 64) {
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + seg * 1024), 16, voS[k], 0, 0, 0);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + PLANE_S + seg * 1024), 16, voS[k], (int)hw16, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + 2 * PLANE_S + seg * 1024), 16, voS[k], (int)(2u * hw16), 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + 3 * PLANE_S + seg * 256), 1, soS[k], 0, 0, 0);
+                    if constexpr (!H) {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + 2 * PLANE_S + seg * 1024), 16, voS[k], (int)(2u * hw16), 0, 0);
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + 3 * PLANE_S + seg * 256), 1, soS[k], 0, 0, 0);
+                    }
                 }
             });
             nops = OPS_INS;
@@ -162,14 +178,16 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
                 if (seg < SEG_L - 1 || lane < NPIX_L - (SEG_L - 1) * 64) {
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + seg * 1024), 16, voL[k], 0, 0, 0);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + PLANE_L + seg * 1024), 16, voL[k], (int)hwl16, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + 2 * PLANE_L + seg * 1024), 16, voL[k], (int)(2u * hwl16), 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + 3 * PLANE_L + seg * 256), 1, soL[k], 0, 0, 0);
+                    if constexpr (!H) {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + 2 * PLANE_L + seg * 1024), 16, voL[k], (int)(2u * hwl16), 0, 0);
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + 3 * PLANE_L + seg * 256), 1, soL[k], 0, 0, 0);
+                    }
                 }
             });
             nops = OPS_INL;
         } else if (!a_low) {
             const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.wps), 0, 0x7FFFFFF0, 0x00020000);
-            const int base = (at.cb * a.nchS + a_c) * W_S;
+            const int base = (at.cb * a.nchS + a_c) * WSLICE_S;
             WSU_STATIC_FOR(NWS, k, {
                 constexpr int piece = WS0 + k;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + piece * 1024), 16, (unsigned)lane * 16u, base + piece * 1024, 0, 0);
@@ -177,7 +195,7 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
             nops = NWS;
         } else {
             const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.wpl), 0, 0x7FFFFFF0, 0x00020000);
-            const int base = ((at.cb * a.nchL + a_c) * 2 + (a_r == 2 ? 1 : 0)) * W_L;
+            const int base = ((at.cb * a.nchL + a_c) * 2 + (a_r == 2 ? 1 : 0)) * WSLICE_L;
             if (a.ablate & 16) {                                          // (16: half of the low weights' pieces)
                 WSU_STATIC_FOR((NWL + 1) / 2, k, {
                     constexpr int piece = WL0 + 2 * k;
@@ -232,8 +250,12 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
     }
 }
 
+// FMT: storage format of x_low, x_skip and y -- WSU_PLANAR_Q (mode 'f16f4p') or WSU_PLANAR_H (mode 'f16p': the f16 products alone)
+template <int FMT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void conv3x3_qu_kernel(const UArgs a) {
+    constexpr bool H = FMT == WSU_PLANAR_H;
+    constexpr int WPL = H ? 2 : 3;                                          // weight granule planes per tap / unit
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -246,10 +268,10 @@ void conv3x3_qu_kernel(const UArgs a) {
     if (wv >= NWAVE) {
         if (a.ablate & 4) __builtin_amdgcn_s_setprio(3);                       // experiment: the loaders' DMA instructions issue ahead of the matrix waves' streams
         switch (wv - NWAVE) {
-            case 0: u_loader<0>(a, smem, lane, lw, G, K); break;
-            case 1: u_loader<1>(a, smem, lane, lw, G, K); break;
-            case 2: u_loader<2>(a, smem, lane, lw, G, K); break;
-            default: u_loader<3>(a, smem, lane, lw, G, K); break;
+            case 0: u_loader<FMT, 0>(a, smem, lane, lw, G, K); break;
+            case 1: u_loader<FMT, 1>(a, smem, lane, lw, G, K); break;
+            case 2: u_loader<FMT, 2>(a, smem, lane, lw, G, K); break;
+            default: u_loader<FMT, 3>(a, smem, lane, lw, G, K); break;
         }
         return;
     }
@@ -284,7 +306,7 @@ void conv3x3_qu_kernel(const UArgs a) {
     auto skip_units = [&]() __attribute__((always_inline)) {
         WSU_STATIC_FOR(5, tp, {
             constexpr int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 2 * tp;
-            {
+            if constexpr (!H) {
                 const unsigned tapo = hh_q ? tap_s(t1 / 3, t1 % 3) : tap_s(t0 / 3, t0 % 3);
                 const int tap = hh_q ? t1 : t0;
                 u32x4 a4[2], b4[2]; int sa[2], sb[2];
@@ -309,7 +331,7 @@ _Pragma("unroll")
             WSU_STATIC_FOR((2 * tp + 1 < 9 ? 2 : 1), k, {
                 constexpr int tap = 2 * tp + k;
                 u32x4 ah[2], bh[2];
-                const unsigned wb = w_off + (unsigned)((tap * 3) * 64 + l31) * 16u + (unsigned)hh * 1024u;
+                const unsigned wb = w_off + (unsigned)((tap * WPL) * 64 + l31) * 16u + (unsigned)hh * 1024u;
                 const unsigned pb = in_off + (unsigned)hh * PLANE_S + tap_s(tap / 3, tap % 3) + laneS;
 _Pragma("unroll")
                 for (int m = 0; m < 2; ++m) ah[m] = *(lds_cu32x4*)(L + wb + m * 512);
@@ -325,7 +347,7 @@ _Pragma("unroll")
     // ---- half a low chunk: taps (dy, 0) and (dy, 1) of this wave's class -- units cls * 2 + dx of the slice [8][3 planes][64 co][16 B] + [8][64] scale bytes
     auto low_units = [&](int dy) __attribute__((always_inline)) {
         const unsigned rowo = (unsigned)(((py + dy) * LP + px) * 16);
-        {
+        if constexpr (!H) {
             const int u = cls * 2 + hh_q;                                   // lanes 32-63: dx = 1
             u32x4 a4[2], b4[2]; int sa[2], sb[2];
             const unsigned wb = w_off + (unsigned)((u * 3 + 2) * 64 + l31) * 16u, sab = w_off + W_GRAN_L + (unsigned)(u * 64 + l31);
@@ -344,7 +366,7 @@ _Pragma("unroll")
         }
         WSU_STATIC_FOR(2, dx, {
             u32x4 ah[2], bh[2];
-            const unsigned wb = w_off + (unsigned)(((cls * 2 + dx) * 3) * 64 + l31) * 16u + (unsigned)hh * 1024u;
+            const unsigned wb = w_off + (unsigned)(((cls * 2 + dx) * WPL) * 64 + l31) * 16u + (unsigned)hh * 1024u;
             const unsigned pb = in_off + (unsigned)hh * PLANE_L + rowo + dx * 16u + laneL;
 _Pragma("unroll")
             for (int m = 0; m < 2; ++m) ah[m] = *(lds_cu32x4*)(L + wb + m * 512);
@@ -386,6 +408,14 @@ _Pragma("unroll")
                         vx[q][e] = x; vy[q][e] = y;
                         vmax = fmaxf(vmax, fmaxf(fabsf(x), fabsf(y)));
                     }
+                if constexpr (H) {                                              // f16 granules only: lanes 0-31 plane 0, lanes 32-63 plane 1
+                    char* base = a.y + ((size_t)cur.n * nco + oc) * (2u * hw16);
+                    const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)(2u * hw16), 0x00020000);
+                    const unsigned hp = hho ? hw16 : 0u;
+                    __builtin_amdgcn_raw_buffer_store_b128(wsu_h_granule(vx[0], vy[0]), rs, (int)(ok0 ? off0 + hp : OOB), 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(wsu_h_granule(vx[1], vy[1]), rs, (int)(ok1 ? off1 + hp : OOB), 0, 0);
+                    return;                                                     // (this piece's lambda)
+                }
                 u32x4 g0, g1; uint32_t dh0, dr0, sb0, dh1, dr1, sb1;
                 wsu_q4_pre(vx[0], vy[0], g0, dh0, dr0, sb0);
                 wsu_q4_pre(vx[1], vy[1], g1, dh1, dr1, sb1);
@@ -400,7 +430,7 @@ _Pragma("unroll")
                 __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(hho ? sb1 : sb0), rs, (int)(okm ? 3u * hw16 + (hho ? so1 : so0) : OOB), 0, 0);
             });
         });
-        if (a.range_flag && __builtin_amdgcn_ballot_w64(!(vmax <= WSU_F8_RANGE)) != 0 && lane == 0) atomicOr(a.range_flag, 1u);
+        if (a.range_flag && __builtin_amdgcn_ballot_w64(!(vmax <= (H ? WSU_F16_RANGE : WSU_F8_RANGE))) != 0 && lane == 0) atomicOr(a.range_flag, 1u);
     };
 
     for (int t = 0; t < K; ++t) {
@@ -436,8 +466,9 @@ _Pragma("unroll")
 }
 
 // ---- packing of the low half: one thread per (block, low chunk, dy, class, dx, co) forms its 16 combined weights in fp32 (ci outer, then ky, kx,
-// fused multiply-adds) and encodes them like wsu_conv3x3_pack_f4 encodes a weight block.  wc_dense (optional): the fp32 values,
-// [cout][cl][py][px][dy][dx] -- what the tests emulate the arithmetic on.
+// fused multiply-adds) and encodes them like wsu_conv3x3_pack_f4 encodes a weight block (format H: rounds them to f16 once, like
+// wsu_conv3x3_pack_h).  wc_dense (optional): the fp32 values, [cout][cl][py][px][dy][dx] -- what the tests emulate the arithmetic on.
+template <int FMT>
 __global__ void pack_up_low_kernel(const float* __restrict__ w3, const float* __restrict__ wt, char* __restrict__ dst, float* __restrict__ wc_dense,
                                    int cup, int c2, int cl, int cout) {
     const int nchL = cl / 16, ctot = cup + c2;
@@ -475,6 +506,12 @@ __global__ void pack_up_low_kernel(const float* __restrict__ w3, const float* __
             r[2 * e] = (v[2 * e] - (float)x) * 2048.f; r[2 * e + 1] = (v[2 * e + 1] - (float)y) * 2048.f;
         }
         const u32x4 h0 = mk_u4(h[0], h[1], h[2], h[3]), h1 = mk_u4(h[4], h[5], h[6], h[7]);
+        if constexpr (FMT == WSU_PLANAR_H) {                               // slice [class 4][dx 2][plane 2][64 co][16 B]
+            char* base = dst + (((size_t)cb * nchL + c) * 2 + dy) * W_L_H + (size_t)(u * 2) * (WSU_COB * 16) + co * 16;
+            *reinterpret_cast<u32x4*>(base) = h0;
+            *reinterpret_cast<u32x4*>(base + WSU_COB * 16) = h1;
+            continue;
+        }
         const int E = wsu_q4_block_exp(wsu_f16x16_max_abs_bits(h0, h1));
         const float sc = wsu_pow2f(E);
         uint32_t q[4] = {0, 0, 0, 0};
@@ -525,7 +562,7 @@ int wsu_conv3x3_up_pack(const float* w3_oihw, const float* wt, const float* bt, 
     WSU_REQUIRE(cl > 0 && cl % 16 == 0 && cup > 0 && c2 >= 0 && cout > 0 && cout % WSU_COB == 0,
                 "conv3x3_up_pack: cl=%d must be a multiple of 16, cout=%d of %d, cup=%d > 0", cl, cout, WSU_COB, cup);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(pack_up_low_kernel, dim3(1024), dim3(128), 0, s, w3_oihw, wt, (char*)w_low_packed, wc_dense, cup, c2, cl, cout);
+    hipLaunchKernelGGL(pack_up_low_kernel<WSU_PLANAR_Q>, dim3(1024), dim3(128), 0, s, w3_oihw, wt, (char*)w_low_packed, wc_dense, cup, c2, cl, cout);
     int rc = wsu_check_launch("pack_up_low_kernel");
     if (rc != WSU_OK) return rc;
     hipLaunchKernelGGL(up_bias_kernel, dim3((cout + 63) / 64), dim3(64), 0, s, w3_oihw, bt, b3, bias_out, cup, c2, cout);
@@ -560,13 +597,69 @@ int wsu_conv3x3_up_q_fwd(const void* x_low, const void* x_skip, const void* w_sk
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
             wsu_set_error("conv3x3_up_q: cannot query the device"); return WSU_ERR_HIP;
         }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_qu_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_qu_kernel<WSU_PLANAR_Q>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
         if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_qu): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
         ncu = prop.multiProcessorCount;
     }
     a.ablate = ablate;
-    hipLaunchKernelGGL(conv3x3_qu_kernel, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3(NT), LDS_TOTAL, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(conv3x3_qu_kernel<WSU_PLANAR_Q>, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3(NT), LDS_TOTAL, static_cast<hipStream_t>(stream), a);
     return wsu_check_launch("conv3x3_qu_kernel");
+}
+
+// ---- format H (mode 'f16p', include/wsu.h K1h) ----------------------------------------------------------------------------------------
+// Bytes of the packed low half in format H: per (64-co block, 16-channel chunk of x_low, dy) one 16 KB slice [class 4][dx 2][plane 2][64 co][16 B].
+size_t wsu_conv3x3_up_packed_h_bytes(int cl, int cout) {
+    if (cl <= 0 || cout <= 0 || cl % 16 || cout % WSU_COB) return 0;
+    return (size_t)(cout / WSU_COB) * (cl / 16) * 2 * W_L_H;
+}
+
+// wsu_conv3x3_up_pack in format H: the combined weights rounded to f16 once (wc_dense and bias_out as there).  The skip half is
+// wsu_conv3x3_pack_h of w3[:, cup:].
+int wsu_conv3x3_up_pack_h(const float* w3_oihw, const float* wt, const float* bt, const float* b3, void* w_low_packed, float* bias_out, float* wc_dense,
+                          int cl, int cup, int c2, int cout, void* stream) {
+    WSU_REQUIRE(w3_oihw && wt && w_low_packed && bias_out, "conv3x3_up_pack_h: null pointer");
+    WSU_REQUIRE(cl > 0 && cl % 16 == 0 && cup > 0 && c2 >= 0 && cout > 0 && cout % WSU_COB == 0,
+                "conv3x3_up_pack_h: cl=%d must be a multiple of 16, cout=%d of %d, cup=%d > 0", cl, cout, WSU_COB, cup);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(pack_up_low_kernel<WSU_PLANAR_H>, dim3(1024), dim3(128), 0, s, w3_oihw, wt, (char*)w_low_packed, wc_dense, cup, c2, cl, cout);
+    int rc = wsu_check_launch("pack_up_low_kernel<H>");
+    if (rc != WSU_OK) return rc;
+    hipLaunchKernelGGL(up_bias_kernel, dim3((cout + 63) / 64), dim3(64), 0, s, w3_oihw, bt, b3, bias_out, cup, c2, cout);
+    return wsu_check_launch("up_bias_kernel");
+}
+
+// wsu_conv3x3_up_q_fwd on planar H tensors (x_low, x_skip, y): weights of wsu_conv3x3_pack_h (skip half) and wsu_conv3x3_up_pack_h.
+int wsu_conv3x3_up_h_fwd(const void* x_low, const void* x_skip, const void* w_skip_packed, const void* w_low_packed, const float* bias, void* y,
+                         int n, int h, int w, int cl, int c2, int cout, int relu, unsigned* range_flag, void* stream) {
+    WSU_REQUIRE(x_low && x_skip && w_skip_packed && w_low_packed && y, "conv3x3_up_h: null pointer");
+    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "conv3x3_up_h: bad shape n=%d h=%d w=%d (the output of a stride-2 transposed conv is even)", n, h, w);
+    WSU_REQUIRE(cl > 0 && cl % 16 == 0 && c2 > 0 && c2 % 16 == 0, "conv3x3_up_h: cl=%d c2=%d must be positive multiples of 16", cl, c2);
+    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= MAX_COUT, "conv3x3_up_h: cout=%d must be a multiple of %d (<= %d)", cout, WSU_COB, MAX_COUT);
+    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "conv3x3_up_h: h*w too large (a chunk must stay below 4 GiB)");
+    UArgs a;
+    a.xl = (const char*)x_low; a.xs = (const char*)x_skip; a.wps = (const char*)w_skip_packed; a.wpl = (const char*)w_low_packed; a.bias = bias;
+    a.y = (char*)y;
+    a.n = n; a.h = h; a.w = w; a.hl = h / 2; a.wl = w / 2; a.cl = cl; a.c2 = c2; a.cout = cout;
+    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ltiles_x = (a.wl + 31) / 32; a.ncb = cout / WSU_COB;
+    a.nchS = c2 / 16; a.nchL = cl / 16; a.relu = relu; a.range_flag = range_flag;
+    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
+    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_up_h: %lld tiles out of range", nt);
+    WSU_REQUIRE((long long)a.ncb * a.nchL * 2 * W_L_H < 0x7FFFFFF0LL && (long long)a.ncb * a.nchS * W_S_H < 0x7FFFFFF0LL, "conv3x3_up_h: packed weights beyond 2 GiB");
+    a.ntiles = (int)nt;
+    static int ncu = 0, ablate = 0;
+    if (ncu == 0) {
+        const char* ev = getenv("WSU_QU_ABLATE"); ablate = ev ? atoi(ev) : 0;
+        int dev = 0; hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
+            wsu_set_error("conv3x3_up_h: cannot query the device"); return WSU_ERR_HIP;
+        }
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_qu_kernel<WSU_PLANAR_H>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_qu<H>): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        ncu = prop.multiProcessorCount;
+    }
+    a.ablate = ablate;
+    hipLaunchKernelGGL(conv3x3_qu_kernel<WSU_PLANAR_H>, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3(NT), LDS_TOTAL, static_cast<hipStream_t>(stream), a);
+    return wsu_check_launch("conv3x3_qu_kernel<H>");
 }
 
 }  // extern "C"

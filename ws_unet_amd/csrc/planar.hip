@@ -548,8 +548,9 @@ __global__ void pack_convt_dgrad_pl_kernel(const float* __restrict__ w, char* __
 // =====================================================================================================================================
 struct FirstPlArgs { const float* x; const float* w; const float* b; char* y; unsigned* range_flag; int n, h, w_, cin, cout, relu; unsigned char* relu_mask_out; int yq; };
 
-template <bool YQ, int CINMAX>                                              // YQ: y is a planar Q tensor (compile-time, like convt2x2_pl_kernel); CINMAX: 1 (the
+template <int FMT, int CINMAX>                                              // FMT: y_format (compile-time, like convt2x2_pl_kernel): WSU_PLANAR_A / _Q / _H; CINMAX: 1 (the
 __global__ __launch_bounds__(256) void first_pl_kernel(const FirstPlArgs a) {   // published runs' single plane: 9 window registers instead of 72) or 8
+    constexpr bool YQ = FMT == WSU_PLANAR_Q;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* wl = reinterpret_cast<float*>(smem);                         // [ci][tap][cout]
     float* bl = wl + a.cin * 9 * a.cout;
@@ -630,6 +631,17 @@ __global__ __launch_bounds__(256) void first_pl_kernel(const FirstPlArgs a) {   
                 *reinterpret_cast<unsigned char*>(chunk + 3 * hw * 16 + wsu_q_soff(y, x, (a.w_ + 31) >> 5)) = (unsigned char)sb;
                 continue;
             }
+            if constexpr (FMT == WSU_PLANAR_H) {                         // planar H output: the two f16 planes (round to nearest even)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x2 p0 = {v[g][0], v[g][1]}, p1 = {v[g][2], v[g][3]};
+                    h[2 * g] = __builtin_bit_cast(uint32_t, __builtin_convertvector(p0, f16x2)); h[2 * g + 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(p1, f16x2));
+                }
+                char* dh = a.y + ((size_t)img * nco + oc) * wsu_h_chunk_bytes(a.h, a.w_) + ((size_t)y * a.w_ + x) * 16;
+                *reinterpret_cast<u32x4*>(dh) = mk_u4(h[0], h[1], h[2], h[3]);
+                *reinterpret_cast<u32x4*>(dh + hw * 16) = mk_u4(h[4], h[5], h[6], h[7]);
+                continue;
+            }
 #pragma unroll
             for (int g = 0; g < 4; ++g) wsu_split4_f16r8(v[g], WSU_F8_XLO_DIV, h[2 * g], h[2 * g + 1], lo[g]);
             char* dst = a.y + ((((size_t)img * nco + oc) * 3) * hw + (size_t)y * a.w_ + x) * 16;
@@ -643,7 +655,7 @@ __global__ __launch_bounds__(256) void first_pl_kernel(const FirstPlArgs a) {   
             }
         }
     }
-    if (a.range_flag && !(vmax <= WSU_F8_RANGE)) atomicOr(a.range_flag, 1u);      // rare: at most one atomic per lane
+    if (a.range_flag && !(vmax <= (FMT == WSU_PLANAR_H ? WSU_F16_RANGE : WSU_F8_RANGE))) atomicOr(a.range_flag, 1u);      // rare: at most one atomic per lane
 }
 
 }  // namespace
@@ -725,10 +737,11 @@ int wsu_convt2x2_pl_bwd_data(const void* dy, const void* w_packed_dgrad, void* d
 }
 
 // K0p: first layer into planar storage.  x_nchw: (N, cin, H, W) fp32, cin 1..8; w_oihw: (cout, cin, 3, 3); cout a multiple of 16 (<= 128).
+// y_format: WSU_PLANAR_A, WSU_PLANAR_Q or WSU_PLANAR_H (mode 'f16p').
 int wsu_conv3x3_first_pl_fwd(const float* x_nchw, const float* w_oihw, const float* bias, void* y, int n, int h, int w, int cin, int cout,
                              int relu, int y_format, unsigned* range_flag, unsigned char* relu_mask_out, void* stream) {
-    WSU_REQUIRE(y_format == WSU_PLANAR_A || y_format == WSU_PLANAR_Q, "conv3x3_first_pl: y_format must be WSU_PLANAR_A or WSU_PLANAR_Q");
-    WSU_REQUIRE(!(relu_mask_out && y_format == WSU_PLANAR_Q), "conv3x3_first_pl: relu_mask_out belongs to the training forward (format WSU_PLANAR_A)");
+    WSU_REQUIRE(y_format == WSU_PLANAR_A || y_format == WSU_PLANAR_Q || y_format == WSU_PLANAR_H, "conv3x3_first_pl: y_format must be WSU_PLANAR_A, WSU_PLANAR_Q or WSU_PLANAR_H");
+    WSU_REQUIRE(!(relu_mask_out && y_format != WSU_PLANAR_A), "conv3x3_first_pl: relu_mask_out belongs to the training forward (format WSU_PLANAR_A)");
     WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "conv3x3_first_pl: h*w too large");
     WSU_REQUIRE(x_nchw && w_oihw && y, "conv3x3_first_pl: null pointer");
     WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && cin >= 1 && cin <= 8 && cout > 0 && cout % 16 == 0 && cout <= 128, "conv3x3_first_pl: bad shape");
@@ -739,11 +752,13 @@ int wsu_conv3x3_first_pl_fwd(const float* x_nchw, const float* w_oihw, const flo
     const size_t lds = ((size_t)cin * 9 * cout + cout) * sizeof(float);
     hipStream_t s_ = static_cast<hipStream_t>(stream);
     if (cin == 1) {
-        if (a.yq) hipLaunchKernelGGL((first_pl_kernel<true, 1>), dim3(nblk), dim3(256), lds, s_, a);
-        else hipLaunchKernelGGL((first_pl_kernel<false, 1>), dim3(nblk), dim3(256), lds, s_, a);
+        if (y_format == WSU_PLANAR_H) hipLaunchKernelGGL((first_pl_kernel<WSU_PLANAR_H, 1>), dim3(nblk), dim3(256), lds, s_, a);
+        else if (a.yq) hipLaunchKernelGGL((first_pl_kernel<WSU_PLANAR_Q, 1>), dim3(nblk), dim3(256), lds, s_, a);
+        else hipLaunchKernelGGL((first_pl_kernel<WSU_PLANAR_A, 1>), dim3(nblk), dim3(256), lds, s_, a);
     } else {
-        if (a.yq) hipLaunchKernelGGL((first_pl_kernel<true, 8>), dim3(nblk), dim3(256), lds, s_, a);
-        else hipLaunchKernelGGL((first_pl_kernel<false, 8>), dim3(nblk), dim3(256), lds, s_, a);
+        if (y_format == WSU_PLANAR_H) hipLaunchKernelGGL((first_pl_kernel<WSU_PLANAR_H, 8>), dim3(nblk), dim3(256), lds, s_, a);
+        else if (a.yq) hipLaunchKernelGGL((first_pl_kernel<WSU_PLANAR_Q, 8>), dim3(nblk), dim3(256), lds, s_, a);
+        else hipLaunchKernelGGL((first_pl_kernel<WSU_PLANAR_A, 8>), dim3(nblk), dim3(256), lds, s_, a);
     }
     return wsu_check_launch("first_pl_kernel");
 }

@@ -288,6 +288,18 @@ __device__ __forceinline__ u32x4 wsu_q4_single(uint32_t dhi, uint32_t dres) {
     return mk_u4(__builtin_amdgcn_perm(ph, dhi, 0x05040100u), __builtin_amdgcn_perm(ph, dhi, 0x07060302u),
                  __builtin_amdgcn_perm(pr, dres, 0x05040100u), __builtin_amdgcn_perm(pr, dres, 0x07060302u));
 }
+// ---- planar H storage ("F16P" tensors of mode 'f16p'; layout: include/wsu.h): the two f16 planes of a Q chunk, nothing else ------------------
+#define WSU_F16_RANGE 65504.f          // |x| beyond this is not a finite f16: the range flag of the H epilogues
+__host__ __device__ inline size_t wsu_h_chunk_bytes(int h, int w) { return (size_t)32 * h * w; }
+// Accumulator-layout producer (the MFMA epilogues, lane layout of wsu_q4_pre): the f16 granule this lane stores to plane hh (lanes 0-31:
+// ch 0-7, lanes 32-63: ch 8-15), rounded to nearest even
+__device__ __forceinline__ u32x4 wsu_h_granule(const f32x4& X, const f32x4& Y) {
+    const f32x2 xa = {X[0], X[1]}, xb = {X[2], X[3]}, ya = {Y[0], Y[1]}, yb = {Y[2], Y[3]};
+    uint32_t xh0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(xa, f16x2)), xh1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(xb, f16x2));
+    uint32_t yh0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(ya, f16x2)), yh1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(yb, f16x2));
+    wsu_swap32(xh0, yh0); wsu_swap32(xh1, yh1);
+    return mk_u4(xh0, xh1, yh0, yh1);
+}
 // Pixel-per-thread producer (first layer): all 16 channels of a (pixel, chunk) in one thread -> the three granules and the scale byte
 __device__ __forceinline__ void wsu_q4_encode16(const f32x4 (&v)[4], u32x4& h0, u32x4& h1, u32x4& q, uint32_t& sb) {
     uint32_t h[8]; float r[16];

@@ -38,13 +38,17 @@ def _model_device(model) -> torch.device:
         return DEVICE
 
 
+PLANAR_MODES = ("f16f8p", "f16f8q", "f16f4p", "f16p")         # the modes whose forward sets UNet's range flag
+
+
 def range_fallback(model, collective: bool = False) -> bool:
     """One synchronising look at a planar model's range flag (UNet.range_exceeded: an activation beyond +-448 was stored since the last
-    look -- the format's e4m3 residual saturates there and that value keeps only f16 accuracy, MAE ~1e-4, AT the gate).  If set: warn,
+    look -- the format's e4m3 residual saturates there and that value keeps only f16 accuracy, MAE ~1e-4, AT the gate; mode 'f16p': beyond
+    +-65504, where the stored f16 value overflows).  If set: warn,
     switch the model to 'bf16x3s' (fp32-range storage) and return True -- the caller recomputes what it computed since the last look.
     The evaluate drivers call this once per data-set pass (one sync per pass), the per-image functions once per image (they synchronise
     on their result anyway).  `collective`: OR the flag over the ranks first (every rank of a sharded pass takes the same decision)."""
-    planar = getattr(model, "mode", None) in ("f16f8p", "f16f8q", "f16f4p") and hasattr(model, "range_exceeded")
+    planar = getattr(model, "mode", None) in PLANAR_MODES and hasattr(model, "range_exceeded")
     if collective:
         # EVERY rank enters the all-reduce, whatever its local state (a rank that skipped it while the others entered would hang the job
         # or pair with a later collective).  A rank whose model already left the planar modes by a look of its OWN that the other ranks
@@ -66,8 +70,12 @@ def range_fallback(model, collective: bool = False) -> bool:
             return False
         hit = model.range_exceeded()
     if hit:
-        logging.warning("ws_unet_amd.evaluate: activations beyond +-448 in mode '%s' (the planar format's e4m3 residual saturates there); "
-                        "switching this model to mode 'bf16x3s' and recomputing", model.mode)
+        if model.mode == "f16p":
+            logging.warning("ws_unet_amd.evaluate: activations beyond +-65504 in mode 'f16p' (not a finite f16: the planar H format overflows); "
+                            "switching this model to mode 'bf16x3s' and recomputing")
+        else:
+            logging.warning("ws_unet_amd.evaluate: activations beyond +-448 in mode '%s' (the planar format's e4m3 residual saturates there); "
+                            "switching this model to mode 'bf16x3s' and recomputing", model.mode)
         model.mode = "bf16x3s"
         model._range_switched = True
     return hit
@@ -299,7 +307,7 @@ def _submit_rows(rows, model):
         mark_uploaded([r[1] for r in rows])                  # one event behind the n uploads
     beta, l1 = predict_u8_batch(x_u8, model)
     rf = getattr(model, "_range_flag", None)
-    planar = rf is not None and getattr(model, "mode", None) in ("f16f8p", "f16f8q", "f16f4p")
+    planar = rf is not None and getattr(model, "mode", None) in PLANAR_MODES
     parts = [beta.reshape(-1), l1.reshape(-1)] + ([rf.reshape(-1).view(torch.float32)] if planar else [])
     dev_v = torch.cat(parts)
     host = torch.empty(dev_v.shape, dtype=torch.float32, pin_memory=dev_v.is_cuda)
@@ -409,7 +417,7 @@ def predict_u8_one_readback(x_u8: torch.Tensor, model: torch.nn.Module):
     beta, l1 = predict_u8_batch(x_u8, model)
     n = beta.numel()
     rf = getattr(model, "_range_flag", None)
-    planar = rf is not None and getattr(model, "mode", None) in ("f16f8p", "f16f8q", "f16f4p")
+    planar = rf is not None and getattr(model, "mode", None) in PLANAR_MODES
     parts = [beta.reshape(-1), l1.reshape(-1)] + ([rf.reshape(-1).view(torch.float32)] if planar else [])
     v = torch.cat(parts).cpu().numpy()
     return v[:n], v[n:2 * n], bool(planar and v[2 * n:].view(np.int32)[0] != 0)

@@ -21,6 +21,11 @@ Precision modes (``mode=`` or env ``WSU_MODE``):
             19 matrix units per chunk): MAE 2.1e-5 (the gate is 1e-4) instead of 4e-6.  Since round 4 on planar Q storage (ops.PlanarQ, include/wsu.h
             K1q): every producer's epilogue writes the fp4 granule + scale byte its consumer multiplies, the consumers' loader waves are pure DMA
             (csrc/conv3x3_q.hip); training forwards and the transposed convs keep the e4m3 arithmetic and format (profiles/r03/f16f4p.md, profiles/r04)
+  'f16p'    (opt-in) ONE product per tap: f16(w) * f16(x) on the f16 matrix pipe, fp32 accumulation, no cross terms (9 instead of 14 matrix
+            units per chunk), activations as two f16 planes (ops.PlanarH, include/wsu.h K1h: 2 bytes per element).  The K1q / K1u kernels
+            instantiated for that format; e11 -> 3x3 convs with fused pool and head -> the fused decoder entry for every decoder block (there is
+            no two-kernel decoder path: WSU_FUSE_UP and WSU_FUSE_FIRST_Q do not apply).  Its own MAE: meant for trained
+            checkpoints; range flag only beyond +-65504.  Trains in 'f16f8p' like 'f16f4p'
   'f16f8q'  'f16f8p' with ONE cross term (the weights' residual) on the first conv of every decoder block: MAE ~4e-5 instead of 4e-6
   'f16f8'   f16 products + fp8 cross terms      -- f16(w)*f16(x) exactly, the two residual cross terms on the block-scaled fp8
                                                    matrix pipe (0.70 of bf16x3's matrix cycles, ~2^-15 relative error per product, MAE
@@ -122,7 +127,7 @@ class UNet(nn.Module):
         # activations AND gradients (3 bytes per element, model/autograd.py; single-plane inputs, falls back to 'bf16x3' otherwise and when the
         # input gradient is asked for); else split-bf16 on fp32 tensors (~2^-16 relative per product -- finer than the TF32 convs PyTorch
         # trains with by default on the reference's GPUs)
-        self.train_mode = os.environ.get("WSU_TRAIN_MODE") or ("f32" if self.mode == "f32" else "f16f8p" if self.mode in ("f16f8p", "f16f8q", "f16f4p") else "bf16x3")
+        self.train_mode = os.environ.get("WSU_TRAIN_MODE") or ("f32" if self.mode == "f32" else "f16f8p" if self.mode in ("f16f8p", "f16f8q", "f16f4p", "f16p") else "bf16x3")
         # train_mode 'f16f8p': the terms the BACKWARD matrix kernels (3x3 data and weight gradients) multiply -- 'f16' (default: exact products of
         # the operands' f16 parts, fp32 accumulation; include/wsu.h WSU_PRODUCTS_*) or 'f16f8' (+ both residual cross terms, the forward's
         # arithmetic).  The forward -- loss, predictions, ReLU masks -- is the same.  Why 'f16' is enough (profiles/r03/
@@ -173,6 +178,8 @@ class UNet(nn.Module):
             return hit[1]
         if kind == "conv_f4":
             packed = ops.pack_conv3x3_f4(p)
+        elif kind == "conv_h":
+            packed = ops.pack_conv3x3_h(p)
         elif kind == "conv":
             packed = ops.pack_conv3x3(p, mode)
         elif kind == "dgrad":
@@ -190,16 +197,17 @@ class UNet(nn.Module):
         self._pack_cache[key] = (tag, packed)
         return packed
 
-    def _packed_up(self, up: str, c1: str):
-        """(w_skip_packed, w_low_packed, bias) of the fused decoder-block entry (ops.pack_conv3x3_up), cached on all four parameters' versions."""
+    def _packed_up(self, up: str, c1: str, fmt: str = "q"):
+        """(w_skip_packed, w_low_packed, bias) of the fused decoder-block entry (ops.pack_conv3x3_up; fmt 'h': ops.pack_conv3x3_up_h), cached on
+        all four parameters' versions."""
         lu, l1 = getattr(self, up), getattr(self, c1)
         ps = (lu.weight, lu.bias, l1.weight, l1.bias)
-        key = (up, c1, "up_q")
+        key = (up, c1, "up_" + fmt)
         tag = tuple((p._version, p.data_ptr(), p.device) for p in ps)
         hit = self._pack_cache.get(key)
         if hit is not None and hit[0] == tag:
             return hit[1]
-        packed = ops.pack_conv3x3_up(l1.weight, lu.weight, lu.bias, l1.bias)
+        packed = (ops.pack_conv3x3_up_h if fmt == "h" else ops.pack_conv3x3_up)(l1.weight, lu.weight, lu.bias, l1.bias)
         self._pack_cache[key] = (tag, packed)
         return packed
 
@@ -223,7 +231,7 @@ class UNet(nn.Module):
         t = keep if keep is not None else {}
         save = keep is not None
         e11 = self.e11
-        if m in (ops.MODE_F16F8P, ops.MODE_F16F8Q, ops.MODE_F16F4P):
+        if m in (ops.MODE_F16F8P, ops.MODE_F16F8Q, ops.MODE_F16F4P, ops.MODE_F16P):
             if save or not self._planar_ok():
                 m = ops.MODE_BF16X3             # intermediates are only kept in fp32 NHWC; odd channel counts take the general path
             else:
@@ -234,8 +242,12 @@ class UNet(nn.Module):
                     self._range_checked = True
                     if self.range_exceeded():
                         import logging
-                        logging.warning("ws_unet_amd.UNet: activations beyond +-448 in mode 'f16f8p' (the e4m3 residual saturates there); "
-                                        "switching this model to mode 'bf16x3s'")
+                        if self.mode == "f16p":
+                            logging.warning("ws_unet_amd.UNet: activations beyond +-65504 in mode 'f16p' (not a finite f16); "
+                                            "switching this model to mode 'bf16x3s'")
+                        else:
+                            logging.warning("ws_unet_amd.UNet: activations beyond +-448 in mode 'f16f8p' (the e4m3 residual saturates there); "
+                                            "switching this model to mode 'bf16x3s'")
                         self.mode = "bf16x3s"
                         self._range_switched = True                # (a sharded pass tells the other ranks: evaluate.range_fallback)
                         return self.forward_features(x, keep, want_logit)
@@ -326,7 +338,7 @@ class UNet(nn.Module):
 
     def range_exceeded(self, clear: bool = True) -> bool:
         """True if, since the last call, a planar ('f16f8p') forward stored an activation beyond +-448 -- where the format's e4m3 residual
-        saturates and that value keeps only f16 accuracy (NaN / Inf count too).  One device word OR-ed by the kernels' epilogues; reading
+        saturates and that value keeps only f16 accuracy (NaN / Inf count too); in mode 'f16p' only beyond +-65504 (not a finite f16).  One device word OR-ed by the kernels' epilogues; reading
         it synchronises.  A network that trips it should run in mode 'bf16x3s' (fp32-range storage)."""
         rf = getattr(self, "_range_flag", None)
         if rf is None:
@@ -342,7 +354,10 @@ class UNet(nn.Module):
 
     def _forward_planar(self, x: torch.Tensor, want_logit: bool = False):
         """unet.py:137-189 on planar F16F8P activations: e11 (VALU) -> 3x3 convs with fused pool / concat / head and transposed convs, all
-        persistent LDS-DMA kernels; no intermediate leaves the format."""
+        persistent LDS-DMA kernels; no intermediate leaves the format.  Mode 'f16p': planar H tensors throughout, every decoder block through
+        the fused entry ops.conv3x3_up_h (WSU_FUSE_UP and WSU_FUSE_FIRST_Q are ignored: the mode has no two-kernel decoder path)."""
+        if self.mode == "f16p":
+            return self._forward_planar_h(x, want_logit)
         W = ops.MODE_F16F8                                           # weights are packed as for 'f16f8'
         # 'f16f8q': the first conv of every decoder block (the two most expensive layers of unet_2) multiplies without the activations'
         # residual term: 15 instead of 19 matrix units there, MAE 4e-6 -> ~4e-5 on the gate's weights (still 2.5x inside 1e-4)
@@ -421,6 +436,46 @@ class UNet(nn.Module):
                 return conv(cur, None, c2, l2, want_y=False, head_w=self.outconv.weight.detach(), head_b=self.outconv.bias.detach(), want_logit=want_logit)
             tag(c2)
             cur = conv(cur, None, c2, l2, fmt=Q if fuse_up(depth - 1) else A, range_flag=rf)           # feeds the next transposed conv
+        raise AssertionError("unreachable")
+
+    def _forward_planar_h(self, x: torch.Tensor, want_logit: bool = False):
+        """The 'f16p' branch of _forward_planar: e11 -> planar H, 3x3 convs with fused pool and head (ops.conv3x3_h), the fused decoder entry
+        (ops.conv3x3_up_h) for every decoder block."""
+        tag = ops.set_layer
+        rf = self._range_flag_tensor(x.device)
+        e11 = self.e11
+        head = {"want_y": False, "head_w": self.outconv.weight.detach(), "head_b": self.outconv.bias.detach(), "want_logit": want_logit}
+
+        def conv(xa, name, **kw):
+            layer = getattr(self, name)
+            return ops.conv3x3_h(xa, None, self._packed(name, ops.MODE_F16P, "conv_h"), layer.bias.detach(), layer.out_channels, **kw)
+
+        tag("e11")
+        cur = ops.conv3x3_first_pl(x, e11.weight, e11.bias.detach(), range_flag=rf, y_format=ops.PLANAR_H)
+        skips: List = []
+        for lvl in range(self.nsteps + 1):
+            a, b = ENC[lvl]
+            if lvl >= 1:
+                tag(a)
+                cur = conv(cur, a, range_flag=rf)
+            if lvl == self.nsteps == 0:
+                tag(b + "+outconv")
+                return conv(cur, b, **head)
+            tag(b)
+            if lvl < self.nsteps:
+                full, cur = conv(cur, b, pool=True, range_flag=rf)
+                skips.append(full)
+            else:
+                cur = conv(cur, b, range_flag=rf)
+        for depth in range(self.nsteps, 0, -1):
+            up, c1, c2 = dec_names(depth)
+            tag(up + "+" + c1)
+            cur = ops.conv3x3_up_h(cur, skips[depth - 1], *self._packed_up(up, c1, "h"), getattr(self, c1).out_channels, range_flag=rf)
+            if depth == 1:
+                tag(c2 + "+outconv")
+                return conv(cur, c2, **head)
+            tag(c2)
+            cur = conv(cur, c2, range_flag=rf)
         raise AssertionError("unreachable")
 
     def forward(self, x_in: torch.Tensor) -> torch.Tensor:

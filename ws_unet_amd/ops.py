@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MODES, MODE_BF16, MODE_BF16X3, MODE_BF16X3S, MODE_F16F8, MODE_F16F8X, MODE_F16F8P, MODE_F16F8Q, MODE_F16F4P, check
+from ._lib import MODES, MODE_BF16, MODE_BF16X3, MODE_BF16X3S, MODE_F16F8, MODE_F16F8X, MODE_F16F8P, MODE_F16F8Q, MODE_F16F4P, MODE_F16P, check
 
 
 def _stream() -> int:
@@ -113,7 +113,7 @@ def _esz(mode: int) -> int:
 def weight_mode(mode: int) -> int:
     """The packed weights of 'bf16x3s' are the 'bf16x3' ones; 'f16f8' has its own packing, shared by 'f16f8x' (the same arithmetic on
     fp32 tensors: the training forward)."""
-    return MODE_BF16X3 if mode == MODE_BF16X3S else (MODE_F16F8 if mode in (MODE_F16F8X, MODE_F16F8P, MODE_F16F8Q, MODE_F16F4P) else mode)
+    return MODE_BF16X3 if mode == MODE_BF16X3S else (MODE_F16F8 if mode in (MODE_F16F8X, MODE_F16F8P, MODE_F16F8Q, MODE_F16F4P, MODE_F16P) else mode)
 
 
 def first_layer_weight_mode(mode: int) -> int:
@@ -272,7 +272,8 @@ def planar_shape(n: int, c: int, h: int, w: int):
     return (n, c // 16, PLANAR_PLANES, h, w, 4)
 
 
-PLANAR_A, PLANAR_Q = 0, 1     # include/wsu.h WSU_PLANAR_*: the e4m3-residual planar format / the planar Q format of mode 'f16f4p'
+PLANAR_A, PLANAR_Q, PLANAR_H = 0, 1, 2     # include/wsu.h WSU_PLANAR_*: the e4m3-residual planar format / the planar Q format of mode 'f16f4p' /
+                                           # the planar H format of mode 'f16p'
 
 
 class PlanarQ:
@@ -302,7 +303,27 @@ class PlanarQ:
         return self.data.data_ptr()
 
 
+class PlanarH:
+    """A planar H activation tensor ('F16P' storage of mode 'f16p', include/wsu.h K1h): per image and 16-channel chunk the planes f16 ch 0-7 |
+    f16 ch 8-15 as [H][W][16 B] -- the first two planes of a PlanarQ chunk, no Q plane and no scale bytes (2 bytes per element).  `data`: uint8
+    (N, C/16, 32 H W).  Written by conv3x3_h / conv3x3_up_h / conv3x3_first_pl(y_format=PLANAR_H), read by conv3x3_h and conv3x3_up_h."""
+    __slots__ = ("data", "n", "c", "h", "w")
+
+    def __init__(self, data: torch.Tensor, n: int, c: int, h: int, w: int):
+        self.data, self.n, self.c, self.h, self.w = data, n, c, h, w
+
+    @staticmethod
+    def chunk_bytes(h: int, w: int) -> int:
+        return 32 * h * w
+
+    empty = classmethod(PlanarQ.empty.__func__)
+    device = PlanarQ.device
+    data_ptr = PlanarQ.data_ptr
+
+
 def _planar_out(fmt: int, n: int, c: int, h: int, w: int, device):
+    if fmt == PLANAR_H:
+        return PlanarH.empty(n, c, h, w, device)
     return PlanarQ.empty(n, c, h, w, device) if fmt == PLANAR_Q else torch.empty(planar_shape(n, c, h, w), dtype=torch.float32, device=device)
 
 
@@ -425,6 +446,111 @@ def conv3x3_up_q(x_low: PlanarQ, x_skip: PlanarQ, w_skip_packed: torch.Tensor, w
     return y
 
 
+# ---- mode 'f16p': one product per tap, f16(w) * f16(x), on planar H tensors (include/wsu.h K1h) -------------------------------------------
+
+def pack_conv3x3_h(w: torch.Tensor) -> torch.Tensor:
+    """w: (Cout, Cin, 3, 3) fp32 OIHW on the device -> the packed weights of conv3x3_h: two f16 planes per tap, round to nearest even
+    (wsu_conv3x3_pack_h)."""
+    lib = _lib.load()
+    w = w.detach().contiguous()
+    _dev_check(w)
+    assert w.dtype == torch.float32 and w.dim() == 4 and w.shape[2:] == (3, 3)
+    cout, cin = w.shape[:2]
+    nbytes = lib.wsu_conv3x3_packed_h_bytes(cin, cout)
+    if nbytes == 0:
+        raise _lib.WsuError(f"f16 packing needs cin % 16 == 0 and cout % 64 == 0 (got {cin}, {cout})")
+    out = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    check(lib.wsu_conv3x3_pack_h(w.data_ptr(), out.data_ptr(), cin, cout, _stream()), "wsu_conv3x3_pack_h")
+    return out
+
+
+def conv3x3_h(x1: PlanarH, x2: Optional[PlanarH], w_packed_h: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
+              relu: bool = True, pool: bool = False, want_y: bool = True,
+              head_w: Optional[torch.Tensor] = None, head_b: Optional[torch.Tensor] = None, want_logit: bool = False,
+              range_flag: Optional[torch.Tensor] = None):
+    """3x3 reflect conv (+ReLU, +2x2 max-pool, +1x1 head and sigmoid) in the one-product arithmetic of mode 'f16p' on planar H activations
+    (wsu_conv3x3_h_fwd: the conv3x3_q kernel instantiated for format H).  x1 / x2: PlanarH; w_packed_h from pack_conv3x3_h; y / y_pool (and a y
+    beside the head): PlanarH.  Returns y [, y_pool] or, with head_w, out [, logit][, y]."""
+    lib = _lib.load()
+    hw2 = None if head_w is None else head_w.detach().reshape(head_w.shape[0], -1).contiguous()
+    assert isinstance(x1, PlanarH) and (x2 is None or isinstance(x2, PlanarH)), "conv3x3_h reads planar H tensors (ops.PlanarH)"
+    _dev_check(x1.data, None if x2 is None else x2.data, w_packed_h, bias, hw2, head_b)
+    n, h, w, c1 = x1.n, x1.h, x1.w, x1.c
+    c2 = 0
+    if x2 is not None:
+        assert (x2.n, x2.h, x2.w) == (n, h, w)
+        c2 = x2.c
+    assert w_packed_h.numel() * w_packed_h.element_size() == int(lib.wsu_conv3x3_packed_h_bytes(c1 + c2, cout)), "w_packed_h is not pack_conv3x3_h of (cin, cout)"
+    hc = 0 if hw2 is None else hw2.shape[0]
+    y = PlanarH.empty(n, cout, h, w, x1.device) if want_y else None
+    yp = PlanarH.empty(n, cout, h // 2, w // 2, x1.device) if pool else None
+    out = torch.empty((n, hc, h, w), dtype=torch.float32, device=x1.device) if hc else None
+    logit = torch.empty_like(out) if (hc and want_logit) else None
+    act = n * h * w * ((c1 + c2) + (cout if want_y else 0)) + (n * (h // 2) * (w // 2) * cout if pool else 0)     # planar elements read + written
+    meta = {"flops": 2.0 * 9 * (c1 + c2) * cout * n * h * w,
+            "bytes": float(act * 2 + n * h * w * hc * 4 + 9 * (c1 + c2) * cout * 2),
+            "bytes_2B": float(act * 2 + n * h * w * hc * 4 + 9 * (c1 + c2) * cout * 2),
+            "tiles": n * ((h + 15) // 16) * ((w + 31) // 32) * (cout // 64), "steps_per_tile": (c1 + c2) // 16}
+    check(_launch("conv3x3_h", meta, lambda: lib.wsu_conv3x3_h_fwd(
+        x1.data_ptr(), _ptr(x2), w_packed_h.data_ptr(), _ptr(bias), _ptr(y), _ptr(yp), _ptr(hw2), _ptr(head_b), _ptr(out), _ptr(logit), hc,
+        n, h, w, c1, c2, cout, int(relu), PLANAR_H, _ptr(range_flag), _stream())), "wsu_conv3x3_h_fwd")
+    if hc:
+        res = [out] + ([logit] if want_logit else []) + ([y] if want_y else [])
+        return res[0] if len(res) == 1 else tuple(res)
+    return (y, yp) if pool else y
+
+
+def pack_conv3x3_up_h(w3: torch.Tensor, wt: torch.Tensor, bt: Optional[torch.Tensor], b3: Optional[torch.Tensor], want_dense: bool = False):
+    """Weights of conv3x3_up_h (wsu_conv3x3_up_pack_h): as pack_conv3x3_up, the skip half packed by pack_conv3x3_h and the parity-class weights
+    combined in fp32 on the device and rounded to f16 once.  Returns (w_skip_packed, w_low_packed, bias[, wc_dense])."""
+    lib = _lib.load()
+    w3, wt = w3.detach().contiguous(), wt.detach().contiguous()
+    bt = None if bt is None else bt.detach().contiguous()
+    b3 = None if b3 is None else b3.detach().contiguous()
+    _dev_check(w3, wt, bt, b3)
+    assert w3.dtype == torch.float32 and w3.dim() == 4 and w3.shape[2:] == (3, 3) and wt.dtype == torch.float32 and wt.dim() == 4 and wt.shape[2:] == (2, 2)
+    cout, ctot = w3.shape[:2]
+    cl, cup = wt.shape[:2]
+    c2 = ctot - cup
+    nbytes = lib.wsu_conv3x3_up_packed_h_bytes(cl, cout)
+    if nbytes == 0 or c2 <= 0 or c2 % 16:
+        raise _lib.WsuError(f"fused upsample packing needs cl % 16 == 0, c2 % 16 == 0 (> 0) and cout % 64 == 0 (got cl={cl}, cup={cup}, c2={c2}, cout={cout})")
+    w_skip = pack_conv3x3_h(w3[:, cup:].contiguous())
+    w_low = torch.empty(nbytes, dtype=torch.uint8, device=w3.device)
+    bias = torch.empty(cout, dtype=torch.float32, device=w3.device)
+    dense = torch.empty((cout, cl, 2, 2, 2, 2), dtype=torch.float32, device=w3.device) if want_dense else None
+    check(lib.wsu_conv3x3_up_pack_h(w3.data_ptr(), wt.data_ptr(), _ptr(bt), _ptr(b3), w_low.data_ptr(), bias.data_ptr(), _ptr(dense),
+                                    cl, cup, c2, cout, _stream()), "wsu_conv3x3_up_pack_h")
+    return (w_skip, w_low, bias, dense) if want_dense else (w_skip, w_low, bias)
+
+
+def conv3x3_up_h(x_low: PlanarH, x_skip: PlanarH, w_skip_packed: torch.Tensor, w_low_packed: torch.Tensor, bias: torch.Tensor, cout: int,
+                 relu: bool = True, range_flag: Optional[torch.Tensor] = None) -> PlanarH:
+    """conv3x3_up_q in the one-product arithmetic of mode 'f16p' on planar H tensors (wsu_conv3x3_up_h_fwd): relu(conv3x3_reflect(cat[
+    conv_transpose2x2_s2(x_low), x_skip])) in one launch.  x_low: PlanarH at (h/2, w/2); x_skip: PlanarH at (h, w); weights from
+    pack_conv3x3_up_h.  Returns y: PlanarH."""
+    lib = _lib.load()
+    assert isinstance(x_low, PlanarH) and isinstance(x_skip, PlanarH), "conv3x3_up_h reads planar H tensors (ops.PlanarH)"
+    _dev_check(x_low.data, x_skip.data, w_skip_packed, w_low_packed, bias)
+    n, h, w, c2, cl = x_skip.n, x_skip.h, x_skip.w, x_skip.c, x_low.c
+    assert (x_low.n, 2 * x_low.h, 2 * x_low.w) == (n, h, w), "x_low must have half the skip tensor's height and width"
+    assert w_skip_packed.numel() == int(lib.wsu_conv3x3_packed_h_bytes(c2, cout)), "w_skip_packed is not pack_conv3x3_h of (c2, cout)"
+    assert w_low_packed.numel() == int(lib.wsu_conv3x3_up_packed_h_bytes(cl, cout)), "w_low_packed is not pack_conv3x3_up_h of (cl, cout)"
+    assert bias is not None and bias.numel() == cout
+    y = PlanarH.empty(n, cout, h, w, x_skip.device)
+    cup = cl // 2
+    act = n * h * w * (c2 + cout) + n * (h // 2) * (w // 2) * cl
+    # algorithmic work = the two reference ops it replaces (as conv3x3_up_q); bytes at 2 B per element and weight
+    meta = {"flops": 2.0 * 9 * (cup + c2) * cout * n * h * w + 2.0 * 4 * cl * cup * n * (h // 2) * (w // 2),
+            "flops_executed": 2.0 * (9 * c2 + 4 * cl) * cout * n * h * w,
+            "bytes": float(act * 2 + (9 * c2 + 16 * cl) * cout * 2), "bytes_2B": float(act * 2 + (9 * (cup + c2) * cout + 4 * cl * cup) * 2),
+            "tiles": n * ((h + 15) // 16) * ((w + 31) // 32) * (cout // 64), "steps_per_tile": c2 // 16 + 2 * (cl // 16)}
+    check(_launch("conv3x3_up_h", meta, lambda: lib.wsu_conv3x3_up_h_fwd(
+        x_low.data_ptr(), x_skip.data_ptr(), w_skip_packed.data_ptr(), w_low_packed.data_ptr(), bias.data_ptr(), y.data_ptr(),
+        n, h, w, cl, c2, cout, int(relu), _ptr(range_flag), _stream())), "wsu_conv3x3_up_h_fwd")
+    return y
+
+
 def conv3x3_pl(x1: torch.Tensor, x2: Optional[torch.Tensor], w_packed: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
                relu: bool = True, pool: bool = False, want_y: bool = True,
                head_w: Optional[torch.Tensor] = None, head_b: Optional[torch.Tensor] = None, want_logit: bool = False,
@@ -516,7 +642,7 @@ def relu_mask_alloc(n: int, c: int, h: int, w: int, device) -> torch.Tensor:
 def conv3x3_first_pl(x_nchw: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], relu: bool = True,
                      range_flag: Optional[torch.Tensor] = None, want_mask: bool = False, y_format: int = PLANAR_A):
     """First layer (N, cin <= 8, H, W) fp32 -> planar F16F8P tensor with w.shape[0] channels (wsu_conv3x3_first_pl_fwd) [, its relu_mask plane];
-    y_format=PLANAR_Q: a PlanarQ."""
+    y_format=PLANAR_Q: a PlanarQ; y_format=PLANAR_H: a PlanarH."""
     lib = _lib.load()
     w = w.detach().contiguous()
     _dev_check(x_nchw, w, bias)
@@ -525,7 +651,8 @@ def conv3x3_first_pl(x_nchw: torch.Tensor, w: torch.Tensor, bias: Optional[torch
     assert x_nchw.dtype == torch.float32 and x_nchw.is_contiguous() and w.shape[1] == cin
     y = _planar_out(y_format, n, cout, h, wd, x_nchw.device)
     mask = relu_mask_alloc(n, cout, h, wd, x_nchw.device) if want_mask else None
-    meta = {"flops": 2.0 * 9 * cin * cout * n * h * wd, "bytes": float(n * h * wd * (cin * 4 + cout * 3)), "bytes_2B": float(n * h * wd * (cin * 4 + cout * 2))}
+    meta = {"flops": 2.0 * 9 * cin * cout * n * h * wd, "bytes": float(n * h * wd * (cin * 4 + cout * (2 if y_format == PLANAR_H else 3))),
+            "bytes_2B": float(n * h * wd * (cin * 4 + cout * 2))}
     check(_launch("conv3x3_first_pl", meta, lambda: lib.wsu_conv3x3_first_pl_fwd(
         x_nchw.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), n, h, wd, cin, cout, int(relu), y_format, _ptr(range_flag), _ptr(mask), _stream())), "wsu_conv3x3_first_pl_fwd")
     return (y, mask) if want_mask else y
