@@ -16,15 +16,16 @@
 //     class planes of 9 x 17 pixels -- the loaders' DMA gathers every other pixel of a row (per-lane source address, contiguous LDS
 //     destination) -- and lanes 16-31 of a matrix tile hold their row's columns rotated by one, which makes the 16-byte fragment reads of two
 //     rows 272 B (528 B in the low tile) apart conflict free (lane groups of ds_read_b128, MI355X guide, LDS);
-//   * steps differ in size (a skip chunk: 9 taps, 28 KB of weights, 31 KB of input; half a low chunk: 2 taps x 4 classes, 25 KB of weights; a
-//     low chunk's input tile: 17 KB, shared by its two half-steps), so LDS is ONE ring of five 31.5 KB slots that inputs and weights are
-//     allocated from in step order; the loaders run as far ahead as the ring allows (2-3 allocations beyond the next step) and count
-//     their outstanding DMA instructions per allocation (`s_waitcnt vmcnt(n)`).
+//   * steps differ in kind: a skip chunk (9 taps, 28 KB of weights, 31 KB of input) or a whole low chunk (4 taps x 4 classes: two 25 KB weight
+//     slices, dy = 0 and dy = 1, and a 17 KB input tile), one s_barrier each.  LDS holds two 78.75 KB step regions; step j of a workgroup
+//     lives in region j & 1, so the loaders fetch step j + 1 while the matrix waves work on step j and wait for all of it (`s_waitcnt
+//     vmcnt(0)`) before the barrier that opens it.  (Until round 5 a low chunk was two half-steps L0 / L1 in a ring of five 31.5 KB slots:
+//     a barrier, a slice wait and an exposed first fragment read per 3 matrix units.)
 // Accuracy: Wc is formed in fp32 and then split like any weight (f16 + fp4 residual terms); `xu` is never rounded to storage -- the fused
 // result is closer to the exact composition than the two-kernel path.  Replaces ops.convt2x2_pl + ops.conv3x3_q in UNet._forward_planar.
 // Format H (mode 'f16p', template argument FMT = WSU_PLANAR_H): planar H tensors in and out, the f16 products alone (no fp4 instruction, no Q /
-// scale pieces), Wc rounded to f16 once; the same ring of five slots, each step's allocations smaller (skip input 19.1 KB, weights 18 KB; low
-// input 10.3 KB, half a low chunk's weights 16 KB).
+// scale pieces), Wc rounded to f16 once; the same two step regions, each step's allocations smaller (skip input 19.1 KB, weights 18 KB; low
+// input 10.3 KB, a dy slice of a low chunk's weights 16 KB).
 #include "wsu_device.h"
 #include <cstdlib>
 
@@ -49,11 +50,14 @@ constexpr int W_UNITS_L = 8;                              // (class, dx) units o
 constexpr int W_GRAN_L = W_UNITS_L * 3 * WSU_COB * 16;    // 24576
 constexpr int W_L = W_GRAN_L + 1024;                      // + [8][64] scale bytes, padded to a DMA piece
 constexpr int PIECES_S = W_S / 1024, PIECES_L = W_L / 1024;   // 28, 25
-constexpr int NSLOT = 5, SLOT = 32256;
-constexpr int LDS_BIAS = NSLOT * SLOT;                    // 161280
+// a step's region: S = input [0, IN_S) + weights [IN_S, IN_S + W_S);  L = weights dy 0 [0, W_L) + input [W_L, W_L + IN_L) + weights dy 1 after it
+constexpr int REGION = 80640;
+constexpr int OFF_SW = IN_S, OFF_LIN = W_L, OFF_LW1 = W_L + IN_L;
+constexpr int LDS_BIAS = 2 * REGION;                      // 161280
 constexpr int MAX_COUT = 512;
 constexpr int LDS_TOTAL = LDS_BIAS + MAX_COUT * 4;        // 163328
-static_assert(SLOT >= IN_S && SLOT >= IN_L && SLOT >= W_L && SLOT >= W_S && SLOT % 16 == 0 && LDS_TOTAL <= 160 * 1024, "LDS budget");
+static_assert(IN_S + W_S <= REGION && OFF_LW1 + W_L <= REGION && (REGION & 0xF) == 0 && LDS_TOTAL <= 160 * 1024, "LDS budget");
+static_assert((OFF_SW | OFF_LIN | OFF_LW1) % 16 == 0, "16-byte aligned allocations");
 constexpr int NLOAD = 4, NWAVE = 8, NT = (NWAVE + NLOAD) * 64;
 constexpr unsigned OOB = 0xFFFFFFF0u;
 // format H: weight slices without the fp4 plane and the scale bytes
@@ -92,19 +96,26 @@ __device__ __forceinline__ void wait_vm(int n) {
         WSU_VM_CASE(10) WSU_VM_CASE(11) WSU_VM_CASE(12) WSU_VM_CASE(13) WSU_VM_CASE(14) WSU_VM_CASE(15) WSU_VM_CASE(16) WSU_VM_CASE(17) WSU_VM_CASE(18) WSU_VM_CASE(19)
         WSU_VM_CASE(20) WSU_VM_CASE(21) WSU_VM_CASE(22) WSU_VM_CASE(23) WSU_VM_CASE(24) WSU_VM_CASE(25) WSU_VM_CASE(26) WSU_VM_CASE(27) WSU_VM_CASE(28) WSU_VM_CASE(29)
         WSU_VM_CASE(30) WSU_VM_CASE(31) WSU_VM_CASE(32) WSU_VM_CASE(33) WSU_VM_CASE(34) WSU_VM_CASE(35) WSU_VM_CASE(36) WSU_VM_CASE(37) WSU_VM_CASE(38) WSU_VM_CASE(39)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;       // (never: three allocations of a wave are at most 33 instructions)
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;       // (never: a step of a wave is at most 24 instructions)
     }
 #undef WSU_VM_CASE
 }
 
-// Steps of a tile: nchS skip chunks (kind S), then per low chunk the half-steps L0 (dy = 0) and L1 (dy = 1).  Allocations, in ring order:
-// S: input, weights;  L0: weights (dy 0), input;  L1: weights (dy 1).  Everything of a step dies with the step except a low chunk's input (dies
-// with L1): lifetimes end in allocation order, so "freed" is a prefix of the ring.
-__device__ __forceinline__ int step_allocs(const UArgs& a, int s) { return (s >= a.nchS && ((s - a.nchS) & 1)) ? 1 : 2; }
-__device__ __forceinline__ bool step_is_l0(const UArgs& a, int s) { return s >= a.nchS && !((s - a.nchS) & 1); }
+// Steps of a tile: nchS skip chunks (kind S), then one step per low chunk (kind L).  Everything of a step dies with the step, so the region
+// step j - 1 leaves at barrier j takes step j + 1.
+
+// Diagnostic stamps (only in the -DWSU_QU_STAMPS build, `make qustamp`; tools/stamp_qu.py): per workgroup < 256 the accumulated shader cycles
+// of matrix wave 0 and loader wave 0 per step kind, read back with wsu_debug_read_qu_stamps().  Values go to a buffer nothing else reads.
+#ifdef WSU_QU_STAMPS
+constexpr int QU_NST = 16;
+__device__ unsigned long long g_qu_stamps[256 * QU_NST];
+#define QU_STAMP(v) v = __builtin_amdgcn_s_memtime()
+#else
+#define QU_STAMP(v) do {} while (0)
+#endif
 
 // ================= loader wave LW: pure DMA, walks the allocation sequence ahead of the matrix waves ==========================================
-// Format H: two input pieces per segment; skip weights 3 / 3 / 6 / 6 pieces, low weights 3 / 3 / 5 / 5 (the low input: 4 / 4 / 2 / 2).
+// Format H: two input pieces per segment; skip weights 3 / 3 / 6 / 6 pieces, low weights 3 / 3 / 5 / 5 per dy slice (the low input: 4 / 4 / 2 / 2).
 template <int FMT, int LW>
 __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, int lw, int G, int K) {
     constexpr bool H = FMT == WSU_PLANAR_H;
@@ -122,8 +133,8 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
     const unsigned hw16 = (unsigned)(a.h * a.w) * 16u, hwl16 = (unsigned)(a.hl * a.wl) * 16u;
     const unsigned cbytes_s = H ? (unsigned)wsu_h_chunk_bytes(a.h, a.w) : (unsigned)wsu_q_chunk_bytes(a.h, a.w);
     const unsigned cbytes_l = H ? (unsigned)wsu_h_chunk_bytes(a.hl, a.wl) : (unsigned)wsu_q_chunk_bytes(a.hl, a.wl);
-    const int T = a.nchS + 2 * a.nchL, A = 2 * a.nchS + 3 * a.nchL;
-    const int J = K * T, total = K * A;
+    const int T = a.nchS + a.nchL;
+    const int J = K * T;
     if (J <= 0) return;
     unsigned voS[NSS], soS[NSS], voL[NSL], soL[NSL];
     auto plan = [&](const Tile& t) __attribute__((always_inline)) {
@@ -144,12 +155,12 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
             if constexpr (!H) soL[k] = 3u * hwl16 + wsu_q_soff(yy, xx, a.ltiles_x);
         });
     };
-    // ---- the allocation cursor
+    // ---- the step cursor: tile a_kt, chunk a_c of kind a_low; the allocation a_r of the step being issued (S: 0 input, 1 weights;
+    // L: 0 weights dy 0, 1 input, 2 weights dy 1)
     int a_kt = 0, a_c = 0, a_r = 0; bool a_low = false;
     Tile at = tile_of(a, lw);
-    int issued = 0, slot_off = 0, n1 = 0, n2 = 0, n3 = 0;
-    auto issue_next = [&]() __attribute__((always_inline)) {
-        lds_char* slot = smem3 + slot_off;
+    unsigned region = 0;                                                  // byte offset of the next step's region
+    auto issue_alloc = [&](lds_char* slot) __attribute__((always_inline)) {
         int nops;
         const bool is_in = a_low ? a_r == 1 : a_r == 0;
         const int skip_kind = a.ablate >> 8;                                 // 0x100 IN_S, 0x200 W_S, 0x400 IN_L, 0x800 W_L: that kind is not fetched (timing only)
@@ -210,44 +221,63 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
                 nops = NWL;
             }
         }
-        n3 = n2; n2 = n1; n1 = nops;
-        ++issued;
-        slot_off += SLOT; if (slot_off == NSLOT * SLOT) slot_off = 0;
-        // advance the cursor
-        ++a_r;
-        if (!a_low) {
-            if (a_r == 2) { a_r = 0; if (++a_c == a.nchS) { a_c = 0; a_low = true; } }
-        } else if (a_r == 3) { a_r = 0; ++a_c; }
-        if (a_low && a_c == a.nchL) {                                     // (nchL == 0 never happens: the entry point requires a low half)
-            a_low = false; a_c = 0; a_r = 0;
-            if (++a_kt < K) { at = tile_of(a, lw + a_kt * G); plan(at); }
-        }
+        return nops;
     };
-    auto wait_but = [&](int x) __attribute__((always_inline)) {          // everything has landed except the x youngest allocations
-        wait_vm(x <= 0 ? 0 : x == 1 ? n1 : x == 2 ? n1 + n2 : n1 + n2 + n3);
+    auto issue_step = [&]() __attribute__((always_inline)) {             // the DMA of the next step into its region; its instruction count
+        lds_char* base = smem3 + region;
+        int nops;
+        if (!a_low) {
+            a_r = 0; nops = issue_alloc(base);
+            a_r = 1; nops += issue_alloc(base + OFF_SW);
+            if (++a_c == a.nchS) { a_c = 0; a_low = true; }
+        } else {
+            a_r = 0; nops = issue_alloc(base);
+            a_r = 1; nops += issue_alloc(base + OFF_LIN);
+            a_r = 2; nops += issue_alloc(base + OFF_LW1);
+            if (++a_c == a.nchL) {                                        // (nchL == 0 never happens: the entry point requires a low half)
+                a_low = false; a_c = 0;
+                if (++a_kt < K) { at = tile_of(a, lw + a_kt * G); plan(at); }
+            }
+        }
+        region ^= (unsigned)REGION;
+        return nops;
     };
     plan(at);
+#ifdef WSU_QU_STAMPS
+    unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_rt0 = __builtin_amdgcn_s_memrealtime(), st_a, st_b, st_c;
+    unsigned long long st_wait[2] = {0, 0}, st_bar[2] = {0, 0}, st_issue = 0;
+    int st_kind = 0;                                                      // kind of the step the next barrier opens (0 S, 1 L)
+#endif
     {
-        const int lim = min(NSLOT, total);
-        while (issued < lim) issue_next();
-        wait_but(issued - step_allocs(a, 0));
+        issue_step();                                                     // steps 0 and 1: both regions are free
+        const int n1 = J > 1 ? issue_step() : 0;
+        wait_vm(n1);
     }
-    int s = 0, cb = 0;                                                    // step inside the tile; allocations begun at steps < j
     for (int j = 0; ; ++j) {
+        QU_STAMP(st_a);
         __builtin_amdgcn_s_barrier();                                     // barrier j: step j is complete in LDS; every matrix wave has left step j - 1
         asm volatile("" ::: "memory");
+        QU_STAMP(st_b);
+#ifdef WSU_QU_STAMPS
+        st_bar[st_kind] += st_b - st_a;
+#endif
         if (j + 1 >= J) break;
-        const int freed = cb - ((s > 0 && step_is_l0(a, s - 1)) ? 1 : 0);
-        const int lim = min(freed + NSLOT, total);
-        const int s1 = s + 1 == T ? 0 : s + 1;
-        if (!(a.ablate & 1)) {
-            while (issued < lim) issue_next();
-            const int need = cb + step_allocs(a, s) + step_allocs(a, s1);     // allocations of the steps <= j + 1
-            wait_but(issued - need);
-        }
-        cb += step_allocs(a, s);
-        s = s1;
+        if (j >= 1 && !(a.ablate & 1)) issue_step();                      // step j + 1 into the region step j - 1 has left
+        QU_STAMP(st_c);
+        wait_vm(0);                                                       // step j + 1 has landed
+#ifdef WSU_QU_STAMPS
+        st_kind = (j + 1) % T >= a.nchS;                                  // step j + 1 inside its tile
+        QU_STAMP(st_a);
+        st_issue += st_c - st_b; st_wait[st_kind] += st_a - st_c;
+#endif
     }
+#ifdef WSU_QU_STAMPS
+    if (lane == 0 && LW == 0 && blockIdx.x < 256) {
+        unsigned long long* d = g_qu_stamps + blockIdx.x * QU_NST;
+        d[8] = st_wait[0]; d[9] = st_wait[1]; d[10] = st_bar[0]; d[11] = st_bar[1]; d[12] = st_issue;
+        d[13] = __builtin_amdgcn_s_memrealtime() - st_rt0; d[14] = __builtin_amdgcn_s_memtime() - st_t0; d[15] = (unsigned long long)J;
+    }
+#endif
 }
 
 // FMT: storage format of x_low, x_skip and y -- WSU_PLANAR_Q (mode 'f16f4p') or WSU_PLANAR_H (mode 'f16p': the f16 products alone)
@@ -284,19 +314,33 @@ void conv3x3_qu_kernel(const UArgs a) {
     constexpr unsigned QS = 2 * CW * 16, QL = 2 * LP * 16;                   // second matrix tile: two low rows further
     Tile cur = tile_of(a, lw);
     f32x16 acc[2][2];                                                       // [32-channel half][matrix tile]
-    unsigned ring = 0;                                                       // byte offset of the next allocation's slot
+    unsigned region = 0;                                                     // byte offset of the next step's region
     unsigned in_off = 0, w_off = 0;
-    auto next_slot = [&]() __attribute__((always_inline)) { const unsigned r = ring; ring += SLOT; if (ring == NSLOT * SLOT) ring = 0; return r; };
+    auto next_region = [&]() __attribute__((always_inline)) { const unsigned r = region; region ^= (unsigned)REGION; return r; };
     int hh_q = hh;
     typedef __attribute__((address_space(3))) const unsigned char lds_cuchar;
     typedef __attribute__((address_space(3))) const int lds_cint;
     typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
     lds_char* L = (lds_char*)smem;
-    auto sync_step = [&]() __attribute__((always_inline)) {
+#ifdef WSU_QU_STAMPS
+    unsigned long long st_a, st_b, st_step[2] = {0, 0}, st_bar[2] = {0, 0}, st_epi = 0, st_t0 = __builtin_amdgcn_s_memtime();
+    int st_n[2] = {0, 0};
+#endif
+    auto sync_step = [&](int kind) __attribute__((always_inline)) {       // kind of the step the barrier opens: 0 S, 1 L (stamps only)
+        QU_STAMP(st_a);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
+        QU_STAMP(st_b);
+#ifdef WSU_QU_STAMPS
+        st_bar[kind] += st_b - st_a; ++st_n[kind];
+#endif
         hh_q = hh;
         asm volatile("" : "+v"(hh_q));
+    };
+    auto step_done = [&](int kind) __attribute__((always_inline)) {       // (stamps only) the step's matrix section, from its barrier on
+#ifdef WSU_QU_STAMPS
+        QU_STAMP(st_a); st_step[kind] += st_a - st_b;
+#endif
     };
     // byte offset of tap (ky, kx)'s source pixel relative to the lane's own class pixel, in the class planes of the skip tile
     auto tap_s = [&](int ky, int kx) __attribute__((always_inline)) {
@@ -344,7 +388,7 @@ _Pragma("unroll")
             });
         });
     };
-    // ---- half a low chunk: taps (dy, 0) and (dy, 1) of this wave's class -- units cls * 2 + dx of the slice [8][3 planes][64 co][16 B] + [8][64] scale bytes
+    // ---- a dy slice of a low chunk: taps (dy, 0) and (dy, 1) of this wave's class -- units cls * 2 + dx of the slice [8][3 planes][64 co][16 B] + [8][64] scale bytes
     auto low_units = [&](int dy) __attribute__((always_inline)) {
         const unsigned rowo = (unsigned)(((py + dy) * LP + px) * 16);
         if constexpr (!H) {
@@ -441,18 +485,23 @@ _Pragma("unroll")
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][q][r] = 0.f;
         for (int c = 0; c < a.nchS; ++c) {
-            sync_step();
-            in_off = next_slot(); w_off = next_slot();
+            sync_step(0);
+            const unsigned r = next_region();
+            in_off = r; w_off = r + OFF_SW;
             skip_units();
+            step_done(0);
         }
-        for (int c = 0; c < a.nchL; ++c) {
-            sync_step();
-            w_off = next_slot(); in_off = next_slot();
+        for (int c = 0; c < a.nchL; ++c) {                                    // one step: dy = 0 then dy = 1, the accumulation order of the two-kernel path
+            sync_step(1);
+            const unsigned r = next_region();
+            in_off = r + OFF_LIN;
+            w_off = r;
             low_units(0);
-            sync_step();
-            w_off = next_slot();
+            w_off = r + OFF_LW1;
             low_units(1);
+            step_done(1);
         }
+        QU_STAMP(st_a);
         if (a.ablate & 2) {
 #pragma unroll
             for (int m = 0; m < 2; ++m)
@@ -461,8 +510,18 @@ _Pragma("unroll")
         } else {
             finish_tile();
         }
+#ifdef WSU_QU_STAMPS
+        QU_STAMP(st_b); st_epi += st_b - st_a;
+#endif
         if (t + 1 < K) cur = tile_of(a, lw + (t + 1) * G);
     }
+#ifdef WSU_QU_STAMPS
+    if (lane == 0 && wv == 0 && blockIdx.x < 256) {
+        unsigned long long* d = g_qu_stamps + blockIdx.x * QU_NST;
+        d[0] = st_step[0]; d[1] = st_step[1]; d[2] = st_bar[0]; d[3] = st_bar[1]; d[4] = st_epi;
+        d[5] = (unsigned long long)st_n[0]; d[6] = (unsigned long long)st_n[1]; d[7] = __builtin_amdgcn_s_memtime() - st_t0;
+    }
+#endif
 }
 
 // ---- packing of the low half: one thread per (block, low chunk, dy, class, dx, co) forms its 16 combined weights in fp32 (ci outer, then ky, kx,
@@ -544,6 +603,14 @@ __global__ void up_bias_kernel(const float* __restrict__ w3, const float* __rest
 }  // namespace
 
 extern "C" {
+
+#ifdef WSU_QU_STAMPS
+// stamps of the last conv3x3_qu launch (-DWSU_QU_STAMPS build only): per workgroup < nblocks, QU_NST values (tools/stamp_qu.py names them)
+int wsu_debug_read_qu_stamps(unsigned long long* host_dst, int nblocks) {
+    if (nblocks > 256) nblocks = 256;
+    return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_qu_stamps), sizeof(unsigned long long) * QU_NST * nblocks, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
+}
+#endif
 
 // Bytes of the packed low half: per (64-co block, 16-channel chunk of x_low, dy) one 25 KB slice [class 4][dx 2][plane 3][64 co][16 B] + [8][64] scale bytes.
 size_t wsu_conv3x3_up_packed_bytes(int cl, int cout) {
