@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: 512x512 grayscale images/sec of UNet predict (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it sets up, warms up, times the K steps, writes the outputs if asked and
+prints the result line (with the roofline figures of the timed steps themselves).  `--full` adds the legs that take runs of
+their own -- the other precision modes, the batch-1 latency, the train step, the CPU baseline with `mae_vs_cpu_oracle` and
+the MAE on trained-like weights (each can be left out again with its --no-* option); they run after the timed steps, so
+they change neither the timing nor the dumped outputs.
 
 N = 1 runs in this process.  N > 1 without a torch.distributed.run environment launches N fresh rank processes itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`, before this
@@ -15,11 +21,11 @@ scaling), no data-path collective; a barrier brackets the timed region and the s
 
 Precision: default mode 'f16f4p' (exact f16 products on the f16 matrix pipe + the two residual cross terms of the 3x3 convs as one
 block-scaled fp4 operand pair per tap pair, fp32 accumulate; planar activation storage fed by LDS-DMA) -- the fastest mode that meets
-the 1e-4 MAE gate against the fp32 CPU oracle (2.1e-5; `mae_vs_cpu_oracle` is measured in every run); the other modes ('f16f8p' = the
-cross terms in e4m3: MAE 4e-6; 'f16f8' = that arithmetic on NHWC storage, 'bf16', 'f32', 'bf16x3', 'bf16x3s') are measured in the same run
-with fewer steps (`other_modes`).
+the 1e-4 MAE gate against the fp32 CPU oracle (2.1e-5; `mae_vs_cpu_oracle` is measured in every --full run); the other modes ('f16f8p' =
+the cross terms in e4m3: MAE 4e-6; 'f16f8' = that arithmetic on NHWC storage, 'bf16', 'f32', 'bf16x3', 'bf16x3s') are measured in a --full
+run with fewer steps (`other_modes`).
 
-Extra JSON objects on the one line rank 0 prints:
+Extra JSON objects on the one line rank 0 prints (all but `roofline` only with --full):
   roofline      dominant kernel = conv3x3 implicit GEMM: algorithmic FLOPs / HIP-event launch time vs the dense f16/bf16 MFMA
                 peak; `per_layer` = every launch of the forward with max(t_flop, t_byte) at the vendor peaks against its
                 measured time, their sum, and the HBM-bound transposed convs against 8 TB/s
@@ -57,6 +63,9 @@ def parse_args(argv=None):
     ap.add_argument("--mode", default=os.environ.get("WSU_BENCH_MODE", DEFAULT_MODE), choices=["bf16x3", "bf16x3s", "f16f8", "f16f8p", "f16f8q", "f16f4p", "bf16", "f32"])
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the other precision modes, the batch-1 latency, the train step, the CPU baseline "
+                         "(mae_vs_cpu_oracle) and the MAE on trained-like weights (N = 1 only); the --no-* options leave single legs out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-modes", action="store_true")
     ap.add_argument("--no-train-step", action="store_true")
@@ -630,8 +639,11 @@ def main():
             "kernel_ms_per_step": gpu_ms,
         }
 
-    # other precision modes, same run, fewer steps (rank 0 only, N = 1 only)
-    if rank == 0 and world == 1 and not args.no_other_modes:
+    # --full: the legs beyond the headline, each a run of its own after the timed steps (rank 0 only, N = 1 only)
+    full = rank == 0 and world == 1 and args.full
+
+    # other precision modes, same process, fewer steps
+    if full and not args.no_other_modes:
         other = {}
         for md in [m for m in ("bf16", "f32", "bf16x3", "bf16x3s", "f16f8", "f16f8p", "f16f8q", "f16f4p") if m != args.mode]:
             mm = build_model(md, dev)
@@ -647,13 +659,13 @@ def main():
     del model, y
     torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_latency:
+    if full and not args.no_latency:
         try:
             result["latency_b1"] = latency_b1_leg(dev, args.mode, args.size)
         except Exception as e:
             result["latency_b1"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and not args.no_train_step:
+    if full and not args.no_train_step:
         try:
             result["train_step"] = train_step_leg(dev, args.train_batch, args.size)
             # the same step with the forward's f16f8 arithmetic in the backward matrix kernels too (train_products='f16f8', the round-2 arithmetic)
@@ -662,7 +674,7 @@ def main():
         except Exception as e:                                       # the headline line must survive (e.g. a smaller card)
             result["train_step"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         nsample = 16
         cb = cpu_baseline(u8[:nsample])
         ref_y, n_done = cb["y"], cb["n_done"]
@@ -685,7 +697,7 @@ def main():
             for md, o in result["other_modes"].items():
                 k = min(4, n_done)
                 o["mae_vs_cpu_oracle"] = (o.pop("_y")[:k] - ref_y[:k]).abs().mean().item()
-    if rank == 0 and world == 1 and not args.no_trained_mae:
+    if full and not args.no_trained_mae:
         try:
             tm = trained_mae_leg(dev, [args.mode] + [m for m in ("f16f8p", "f32") if m != args.mode], args.size)
             result["trained_weights"] = tm

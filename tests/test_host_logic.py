@@ -509,6 +509,16 @@ def test_bench_dump_outputs_and_steps(tmp_path):
     assert got.shape[0] == bench.DUMP_LIMIT_BYTES // per_image and (tmp_path / "d" / "output.npy").stat().st_size < 64 * 10 ** 6
 
 
+def test_bench_full_is_opt_in():
+    """A plain `bench.py` run measures the headline only; the other modes, latency, train-step, CPU-baseline and MAE legs need `--full`,
+    and there the --no-* options still leave single legs out."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False
+    a = bench.parse_args(["--full", "--no-train-step"])
+    assert a.full and a.no_train_step and not a.no_cpu_baseline
+
+
 def test_train_products_setting(monkeypatch):
     """`train_products` (include/wsu.h WSU_PRODUCTS_*): default 'f16', the environment overrides, an unknown name is refused when the model is
     built -- not at the first backward."""

@@ -22,5 +22,5 @@ timeout -k 10 300 python tools/bench_ws_attack.py --correct-bias >> $O/ws_attack
 echo "ws attack done"
 WSU_TIME_TRAIN_LAUNCHES=1 timeout -k 10 300 python tools/time_train.py f16f8p 64 512 > $O/train_step.json 2> $O/train_step_launches.log
 echo "train launches done"
-timeout -k 10 500 python bench.py --detail $O/bench_n1_detail.json > $O/bench_n1.log 2>&1
+timeout -k 10 500 python bench.py --full --detail $O/bench_n1_detail.json > $O/bench_n1.log 2>&1
 tail -1 $O/bench_n1.log | cut -c1-150
