@@ -361,6 +361,36 @@ int wsu_ws_attack(const uint8_t* x_u8, const float* x_hat, const float* x_bias, 
                   int hat_full, float hat_scale, int weighted, int correct_bias, float* beta_hat, double* sums,
                   void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
 
+/* ---- K12-K14: HILL-cost weighted prediction error (wMAE) of src/filters/evaluate.py:79-115 `get_filter_residuals_cover` and
+ *      src/predictor_error.py:19-76 `attack`.  Both reference callers take HILL from a library (conseal.hill._costmap.compute_cost,
+ *      stegolab2.hill.compute_rho); here both are the textbook cost, the one pinned by results/prediction/filters.csv:
+ *        R = x (*) [[-1,2,-1],[2,-4,2],[-1,2,-1]];  rho0 = 1 / (box3x3(|R|)/9);  cost = box15x15(rho0)/225   ('same', boundary 'symm')
+ *        cost[isinf | isnan | cost > 1e10] = 1e10                                  (filters/evaluate.py:104, predictor_error.py:66)
+ *
+ * K12: x_u8 (N,H,W) DEVICE -> cost (N,H,W) DEVICE fp32 with cost[inf | nan | > clamp] = clamp (the reference's clamp is 1e10;
+ *      q and wMAE below need a positive finite clamp). */
+int wsu_hill_cost(const uint8_t* x_u8, float* cost, float clamp, int n, int h, int w, void* stream);
+
+/* K13: per-image threshold q = numpy.quantile(cost[1:-1,1:-1], quantile) ('linear', filters/evaluate.py:106) by an exact radix select.
+ *      (k, g) = floor / fraction of (count-1)*quantile with count = (H-2)(W-2) (host helper ws_unet_amd.hill.quantile_index);
+ *      q: (N) DEVICE fp64 = a + (b-a)*g  (b - (b-a)*(1-g) when g >= 0.5), a = c_(k), b = c_(min(k+1, count-1)).
+ *      The workspace (DEVICE, wsu_hill_threshold_workspace_bytes(n)) is zeroed on the stream by every call; deterministic. */
+size_t wsu_hill_threshold_workspace_bytes(int n);
+int wsu_hill_threshold(const float* cost, long long k, double g, double* q, void* workspace, size_t workspace_bytes,
+                       int n, int h, int w, void* stream);
+
+/* K14: per-image mae = mean|x - x_hat| and wmae = mean|x - x_hat| over cost <= q on the interior [1:-1,1:-1]
+ *      (filters/evaluate.py:101-107, predictor_error.py:60-67).  The prediction is either
+ *        x_hat (DEVICE fp32): hat_full=1 -> (N,H,W) read at [r][c] (a network output; hat_scale = 255), hat_full=0 -> (N,H-2,W-2);
+ *                             the residual is K10's float32 x - x_hat*hat_scale, or
+ *        pixel_filter (HOST, 9 doubles, weight of x[r-1+a][c-1+b] at [a*3+b]): get_filter_residuals' float64 y - x @ filter
+ *                             (filters/evaluate.py:53-76), evaluated inside the kernel.
+ *      mae, wmae: (N) DEVICE fp64 (fixed-order fp64 sums, deterministic); selected: optional (N) DEVICE int64 count of cost <= q. */
+size_t wsu_prediction_error_workspace_bytes(int n);
+int wsu_prediction_error(const uint8_t* x_u8, const float* x_hat, const double* pixel_filter, int hat_full, float hat_scale,
+                         const float* cost, const double* q, double* mae, double* wmae, long long* selected,
+                         void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
+
 /* Linear pixel predictor on its own (filters/evaluate.py:136-141): y (N,H-2,W-2) = convolve(x/255., K, 'valid')*255.
  * x: DEVICE (N,H,W) fp32; filter: HOST 9 floats K[a][b]. */
 int wsu_filter3x3_valid_f32(const float* x, const float* filter, float* y, int n, int h, int w, void* stream);

@@ -1,0 +1,201 @@
+"""GPU: HILL cost (K12), per-image quantile threshold (K13) and MAE / wMAE (K14) against the published filters.csv values and a
+numpy restatement of the definition (tests/hill_np.py)."""
+import json
+import shutil
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+from gpu_util import DEV, gpu_model
+import hill_np
+from ws_unet_amd import evaluate, filters, formula, hill, ops
+from ws_unet_amd.imread import imread4_u8
+
+pytestmark = pytest.mark.gpu
+
+COVERS = (6, 7, 8, 9, 10)
+AVG, KB = filters.NAMED_FILTERS["AVG"], filters.NAMED_FILTERS["KB"]
+
+
+def _covers_dataset(root):
+    (root / "images").mkdir()
+    for k in COVERS:
+        shutil.copy(GOLDEN / f"cover_{k}.png", root / "images" / f"{k}.png")
+    (root / "images" / "files.csv").write_text("name,height,width\n" + "".join(f"images/{k}.png,512,512\n" for k in COVERS))
+
+
+def _rel(a, b):
+    return 0.0 if a == b else abs(a - b) / abs(b)
+
+
+@pytest.mark.parametrize("iterator", ["python", "batched"])
+def test_filters_run_reproduces_published_table(tmp_path, iterator):
+    _covers_dataset(tmp_path)
+    kat = json.loads((GOLDEN / "prediction_kat.json").read_text())["values"]
+    df = filters.run(tmp_path, filter_names=["AVG", "KB"], channels=[[3], [3]], iterator=iterator)
+    assert list(df.columns) == ["fname", "mae_3_AVG", "wmae_3_AVG", "name", "height", "width", "mae_3_KB", "wmae_3_KB"]
+    assert df["name"].tolist() == [f"images/{k}.png" for k in (10, 6, 7, 8, 9)] * 2
+    checked = 0
+    for _, row in df.iterrows():
+        for col in ("mae_3_AVG", "wmae_3_AVG", "mae_3_KB", "wmae_3_KB"):
+            if not np.isnan(row[col]):
+                assert _rel(row[col], kat[row["name"]][col]) <= 1e-6, (row["name"], col, row[col])
+                checked += 1
+    assert checked == 20
+
+
+def _image_with_flats(h, w, seed):
+    rng = np.random.default_rng(seed)
+    x = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    for _ in range(max(1, h * w // 4000)):
+        r, c = rng.integers(0, max(1, h - 20)), rng.integers(0, max(1, w - 20))
+        x[r:r + 20, c:c + 20] = rng.integers(0, 256)
+    return x
+
+
+CASES = [
+    ("cover", lambda: imread4_u8(GOLDEN / "cover_8.png")[..., 3]),
+    ("random512", lambda: np.random.default_rng(1).integers(0, 256, (512, 512), dtype=np.uint8)),
+    ("flats2048x1536", lambda: _image_with_flats(2048, 1536, 2)),
+    ("flats37x53", lambda: _image_with_flats(37, 53, 3)),
+    ("smooth130x67", lambda: formula.synthetic_images(1, 130, 67, seed=4)[0]),
+    ("random5x6", lambda: np.random.default_rng(5).integers(0, 256, (5, 6), dtype=np.uint8)),
+    ("random3x3", lambda: np.random.default_rng(6).integers(0, 256, (3, 3), dtype=np.uint8)),
+    ("flat", lambda: np.full((64, 80), 77, dtype=np.uint8)),
+]
+
+
+@pytest.mark.parametrize("name,make", CASES, ids=[c[0] for c in CASES])
+def test_cost_map_matches_numpy(name, make):
+    x = make()
+    ref = hill_np.hill_cost(x)
+    got = hill.compute_cost(x)
+    assert isinstance(got, np.ndarray) and got.dtype == np.float32 and got.shape == x.shape
+    clamped = ref == 1e10
+    assert np.array_equal(got == np.float32(1e10), clamped)
+    if (~clamped).any():
+        rel = np.abs(got[~clamped] - ref[~clamped]) / ref[~clamped]
+        assert rel.max() <= 1e-5, rel.max()
+    if name == "flat":
+        assert clamped.all()
+    if name.startswith("flats"):
+        assert clamped.any() and not clamped.all()
+
+
+def test_cost_map_batch_and_tensor_forms():
+    x = formula.synthetic_images(3, 96, 160, seed=9)
+    t = torch.from_numpy(x).to(DEV)
+    batch = hill.compute_cost(t)
+    assert batch.is_cuda and batch.shape == (3, 96, 160)
+    for i in range(3):
+        assert torch.equal(batch[i].cpu(), torch.from_numpy(hill.compute_cost(x[i])))
+
+
+def _threshold_case(x, quantile, taps=AVG):
+    t = torch.from_numpy(x)[None].to(DEV)
+    cost = ops.hill_cost(t)
+    mae, wmae, q, sel = ops.prediction_error(t, pixel_filter=taps, quantile=quantile, cost=cost, return_threshold=True)
+    c = cost[0].cpu().numpy().astype(np.float64)[1:-1, 1:-1]
+    r = np.abs(x[1:-1, 1:-1].astype(np.float64) - hill_np.filter_hat(x, taps))
+    w_ref, q_ref, n_ref = hill_np.wmae(r, c, quantile)
+    assert int(sel[0]) == n_ref
+    if q_ref == 0:
+        assert float(q[0]) == 0
+    else:
+        assert _rel(float(q[0]), q_ref) <= 1e-6
+    assert _rel(float(wmae[0]), w_ref) <= 1e-6
+    assert _rel(float(mae[0]), r.mean()) <= 1e-12
+    return float(mae[0]), float(wmae[0]), int(sel[0])
+
+
+TIES = np.tile(np.random.default_rng(11).integers(0, 256, (8, 8), dtype=np.uint8), (40, 33))     # periodic: every cost repeats ~1 300 times
+
+
+@pytest.mark.parametrize("quantile", [0.0, 0.1, 0.5, 1.0, 0.37])
+def test_threshold_semantics(quantile):
+    _threshold_case(TIES, quantile)
+    _threshold_case(TIES[:-3, :-5], quantile, KB)
+    _threshold_case(_image_with_flats(75, 91, 12), quantile)
+    _threshold_case(imread4_u8(GOLDEN / "cover_6.png")[..., 3], quantile, KB)
+
+
+def test_threshold_edge_cases():
+    flat = np.full((40, 50), 200, dtype=np.uint8)
+    mae, wmae, sel = _threshold_case(flat, 0.1)
+    assert sel == 38 * 48 and wmae == mae                      # every cost is the clamp: every pixel selected
+    one = np.random.default_rng(13).integers(0, 256, (3, 3), dtype=np.uint8)
+    for qq in (0.0, 0.1, 1.0):
+        mae, wmae, sel = _threshold_case(one, qq)              # n = 1
+        assert sel == 1 and wmae == mae
+
+
+def test_unet_error_agrees_with_residual_stats_and_host():
+    model = gpu_model(2, "he", "f32", drop_rate=0.)
+    u8 = formula.synthetic_images(4, 64, 96, seed=21)
+    x_u8 = torch.from_numpy(u8).to(DEV)
+    mae, wmae = evaluate.predict_u8_error_batch(x_u8, model)
+    _, l1 = evaluate.predict_u8_batch(x_u8, model)
+    mae, wmae, l1 = mae.cpu().numpy(), wmae.cpu().numpy(), l1.cpu().numpy()
+    # both means sum the same float32 |x - y*255| terms in fp64, in different fixed orders (K10: 1024 strided threads and one tree;
+    # K14: 64 row blocks x 256 threads, two trees): the fp64 means agree to ~1e-15, so their float32 roundings agree unless the mean
+    # sits at an fp32 rounding boundary -- then they are one fp32 ulp apart
+    assert np.all(np.abs(mae.astype(np.float32) - l1) <= np.spacing(l1)), (mae, l1)
+    assert np.all(np.abs(mae - l1.astype(np.float64)) <= np.spacing(l1) * 0.5 + 1e-12 * l1)
+    # wmae against the host from the same GPU output
+    with torch.no_grad():
+        y = model(ops.u8_to_unit(x_u8)[:, None])[:, 0].contiguous()
+    cost = ops.hill_cost(x_u8).cpu().numpy().astype(np.float64)
+    yh = y.cpu().numpy()
+    for i in range(4):
+        d = u8[i][1:-1, 1:-1].astype(np.float32) - yh[i][1:-1, 1:-1] * np.float32(255.)
+        w_ref, _, _ = hill_np.wmae(np.abs(d).astype(np.float64), cost[i][1:-1, 1:-1])
+        assert _rel(wmae[i], w_ref) <= 1e-6
+
+
+def test_unet_error_rows(tmp_path):
+    _covers_dataset(tmp_path)
+    model = gpu_model(2, "he", "f32", drop_rate=0.)
+    df = evaluate.predict_unet_error_cover(tmp_path, model=model)
+    dfb = evaluate.predict_unet_error_cover_batched(tmp_path, model=model)
+    for d in (df, dfb):
+        assert list(d.columns) == ["name", "height", "width", "demosaic", "filter", "model", "inbayer", "information", "mae", "wmae", "channels"]
+        assert (d["filter"] == "UNet").all() and (d["channels"] == "3").all()
+    np.testing.assert_array_equal(df["mae"].to_numpy(), dfb["mae"].to_numpy())
+    np.testing.assert_array_equal(df["wmae"].to_numpy(), dfb["wmae"].to_numpy())
+
+
+def test_batch_invariance_and_determinism():
+    u8 = formula.synthetic_images(7, 128, 96, seed=31)
+    u8[3, 10:40, 20:60] = 9                                      # a flat patch: clamped costs in one image of the batch
+    x = torch.from_numpy(u8).to(DEV)
+    hat = torch.from_numpy(formula.synthetic_images(7, 128, 96, seed=32).astype(np.float32) / np.float32(255.)).to(DEV)
+    for kw in ({"pixel_filter": KB}, {"x_hat": hat}):
+        full = [t.cpu() for t in ops.prediction_error(x, **kw, return_threshold=True)]
+        again = [t.cpu() for t in ops.prediction_error(x, **kw, return_threshold=True)]
+        for a, b in zip(full, again):
+            assert torch.equal(a, b)
+        for i in (0, 6):
+            one_kw = {"pixel_filter": KB} if "pixel_filter" in kw else {"x_hat": hat[i:i + 1].contiguous()}
+            one = [t.cpu() for t in ops.prediction_error(x[i:i + 1].contiguous(), **one_kw, return_threshold=True)]
+            for a, b in zip(one, full):
+                assert torch.equal(a[0], b[i])
+        # the lone image at position 0 and at position 6 of a batch
+        for pos in (0, 6):
+            xb = x.clone()
+            xb[pos] = x[3]
+            kwb = kw if "pixel_filter" in kw else {"x_hat": torch.where(torch.arange(7, device=DEV)[:, None, None] == pos, hat[3], hat)}
+            res = [t.cpu() for t in ops.prediction_error(xb, **kwb, return_threshold=True)]
+            for a, b in zip(res, full):
+                assert torch.equal(a[pos], b[3])
+
+
+def test_interior_prediction_form():
+    u8 = formula.synthetic_images(2, 50, 70, seed=41)
+    x = torch.from_numpy(u8).to(DEV)
+    hat = torch.from_numpy(formula.synthetic_images(2, 50, 70, seed=42).astype(np.float32)).to(DEV)
+    full = ops.prediction_error(x, hat, hat_scale=1.)
+    inner = ops.prediction_error(x, hat[:, 1:-1, 1:-1].contiguous(), hat_scale=1.)
+    for a, b in zip(full, inner):
+        assert torch.equal(a, b)

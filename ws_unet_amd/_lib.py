@@ -14,7 +14,7 @@ import os
 # libamdhip64.so.7, so kernels, streams and device pointers live in ONE runtime.  Loaded second, the system
 # runtime from libwsu's RUNPATH would be a second, device-less runtime ("no ROCm-capable device").
 import torch  # noqa: F401
-from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint64, c_void_p
 from pathlib import Path
 
 _HERE = Path(__file__).resolve().parent
@@ -94,6 +94,11 @@ SIGNATURES = {
     "wsu_ws_attack": (c_int, [_P, _P, _P, _P, _P, c_int, c_float, c_int, c_int, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
     "wsu_lsb_delta_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     "wsu_filter3x3_valid_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "wsu_hill_cost": (c_int, [_P, _P, c_float, c_int, c_int, c_int, _P]),
+    "wsu_hill_threshold_workspace_bytes": (c_size_t, [c_int]),
+    "wsu_hill_threshold": (c_int, [_P, c_longlong, c_double, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_prediction_error_workspace_bytes": (c_size_t, [c_int]),
+    "wsu_prediction_error": (c_int, [_P, _P, _P, c_int, c_float, _P, _P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_u8_to_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     # ---- backward / train step

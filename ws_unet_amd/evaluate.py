@@ -666,6 +666,83 @@ predict_unet_stego_batched = _range_guarded(fabrika.stego_spatial(iterator="batc
     _drop_model_kw(predict_unet_batch)))
 
 
+# ---- prediction error with the HILL-cost weighted MAE (src/predictor_error.py:19-76 `attack`): mae and wmae per image ------------------------
+# A separate chain beside the WS statistics above: u8 -> /255 -> forward -> HILL cost (K12) -> 10 % quantile (K13) -> mae / wmae (K14).
+# predict_unet / predict_u8_batch and what they return are untouched.
+
+_ERROR_ROW = {"filter": "UNet", "model": "gray", "inbayer": "", "information": "Unconditional"}     # the constant fields of attack's row
+
+
+def predict_u8_error_batch(x_u8: torch.Tensor, model: torch.nn.Module, quantile: float = 0.1):
+    """x_u8: (N,H,W) uint8 on the model's device -> (mae[N], wmae[N]) fp64 device tensors.  mae is K10's l1 (same float32 residual
+    x - y*255, fp64 sums in another fixed order; see tests/test_gpu_prediction_error.py), wmae its mean over the interior pixels whose
+    HILL cost is at most the per-image `quantile` of the costs."""
+    x01 = ops.u8_to_unit(x_u8)[:, None]
+    with torch.no_grad():
+        y = model(x01)
+    return ops.prediction_error(x_u8, y[:, 0].contiguous(), hat_scale=255., quantile=quantile)
+
+
+def _u8_error_rows(x_u8: torch.Tensor, model: torch.nn.Module):
+    """predict_u8_error_batch + one look at the range flag (recompute in 'bf16x3s' if a planar forward left its range): numpy (mae, wmae)."""
+    mae, wmae = predict_u8_error_batch(x_u8, model)
+    if range_fallback(model):
+        mae, wmae = predict_u8_error_batch(x_u8, model)
+    return mae.cpu().numpy(), wmae.cpu().numpy()
+
+
+def _u8_plane(x: np.ndarray) -> np.ndarray:
+    if x.dtype != np.uint8:
+        u = x.astype(np.uint8)
+        if not np.array_equal(u, x):
+            raise ValueError("the HILL cost is defined on 8-bit pixel values")
+        x = u
+    return np.ascontiguousarray(x)
+
+
+def predict_unet_error(fname: str, model: torch.nn.Module, *, imread: typing.Callable = imread4_f32, channels=(3,), demosaic=None, **kw):
+    """Per-image row of src/predictor_error.py:19-76 `attack` for the UNet: mae and wmae (the MAE over the 10 % of interior pixels
+    with the lowest HILL cost; the reference takes HILL from stegolab2.hill.compute_rho, here the textbook cost of ws_unet_amd.hill,
+    the one filters.csv pins).  The row leads with the fabrika row fields (name, height, width)."""
+    x = _u8_plane(np.asarray(imread(fname))[..., channels[0]])
+    mae, wmae = _u8_error_rows(torch.from_numpy(x)[None].to(_model_device(model)), model)
+    return {**kw, "demosaic": demosaic, **_ERROR_ROW, "mae": float(mae[0]), "wmae": float(wmae[0]),
+            "channels": "".join(map(str, channels))}
+
+
+predict_unet_error_cover = fabrika.precovers(iterator="python", convert_to="pandas", ignore_missing=False)(predict_unet_error)
+predict_unet_error_stego = fabrika.stego_spatial(iterator="python", convert_to="pandas", ignore_missing=False)(predict_unet_error)
+
+
+def predict_unet_error_batch(fnames, kws, *, model: torch.nn.Module, imread: typing.Callable = imread4_u8, prefetched=None, **_ignored):
+    """Batched predict_unet_error for fabrika iterator='batched' (Y plane): the chunk's planes come from load_planes_u8 (pinned buffer,
+    decoded one chunk ahead when the iterator prefetches), go up as uint8 and run as one launch chain; ragged chunks go per image."""
+    planes = prefetched[0] if prefetched is not None else load_planes_u8(fnames, imread)
+    if planes is None:
+        return [predict_unet_error(f, model, **kw) for f, kw in zip(fnames, kws)]
+    x_u8 = planes.to(_model_device(model), non_blocking=True)
+    mark_uploaded(planes)
+    mae, wmae = predict_u8_error_batch(x_u8, model)
+    mae, wmae = mae.cpu().numpy(), wmae.cpu().numpy()
+    return [{**kw, "demosaic": None, **_ERROR_ROW, "mae": float(mae[i]), "wmae": float(wmae[i]), "channels": "3"} for i, kw in enumerate(kws)]
+
+
+def _error_batch_kw(fn):
+    def wrapped(fnames, kws, prefetched=None):
+        clean = [{k: v for k, v in kw.items() if k not in ("model", "imread", "device")} for kw in kws]
+        extra = {k: kws[0][k] for k in ("imread",) if k in kws[0]}
+        return fn(fnames, clean, model=kws[0]["model"], prefetched=prefetched, **extra)
+
+    wrapped.prefetch = lambda fnames, kws: (load_planes_u8(fnames, kws[0].get("imread", imread4_u8)),)
+    return wrapped
+
+
+predict_unet_error_cover_batched = _range_guarded(fabrika.precovers(iterator="batched", convert_to="pandas", ignore_missing=False)(
+    _error_batch_kw(predict_unet_error_batch)))
+predict_unet_error_stego_batched = _range_guarded(fabrika.stego_spatial(iterator="batched", convert_to="pandas", ignore_missing=False)(
+    _error_batch_kw(predict_unet_error_batch)))
+
+
 def get_model_config(model_dir: pathlib.Path, stego_method: str, model_name: str) -> typing.Dict[str, typing.Any]:
     with open(pathlib.Path(model_dir) / stego_method / model_name / "config.json") as f:
         return json.load(f)

@@ -3,13 +3,21 @@
 Mirrors the pieces of the reference that `src/ws/estimate.py:149-205 run` pulls in:
   NAMED_FILTERS_2D, get_coefficients, get_filter_estimator, infere_single   src/filters/evaluate.py:22-50,118-146
   get_processor_2d                                                          src/_defs/filters.py:72-83
-The rest of the reference's filter tooling (OLS fits, HILL-cost weighted MAE tables) is outside the UNet path.
+and the prediction-error table of the filters, results/prediction/filters.csv:
+  get_filter_residuals_cover, run                                           src/filters/evaluate.py:53-115,149-205
+(mae and wmae per image and filter; wmae is the MAE over the 10 % of interior pixels with the lowest HILL cost, ws_unet_amd.hill).
+The OLS fits of the reference's filter tooling stay outside the UNet path.
 `infere_single` runs on the GPU (wsu_filter3x3_valid_f32); inside `ws.estimate` a `FilterEstimator` is recognised and its
-taps are evaluated in the statistic kernel itself, so the prediction never exists in memory.
+taps are evaluated in the statistic kernel itself, so the prediction never exists in memory.  The same holds for the filter table:
+the flattened 8-tap coefficients are evaluated inside the error kernel (wsu_prediction_error) in float64, as `x @ filter` is.
 """
+import pathlib
 import typing
 
 import numpy as np
+
+from . import fabrika
+from .imread import imread4_u8
 
 NAMED_FILTERS = {
     "KB": np.array([[-1], [+2], [-1], [+2], [-1], [+2], [-1], [+2]], dtype="float64") / 4.,
@@ -68,3 +76,94 @@ def get_processor_2d(channels: typing.List[int]) -> typing.Callable:
 
     process_gray.plane_selector = tuple(channels)          # lets the batched WS path skip the host arrays for the Y plane
     return process_gray
+
+
+# ---- prediction-error table (src/filters/evaluate.py:53-115,149-179) ------------------------------------------------------------------------
+# The reference's get_processor (_defs/filters.py:39-69) turns a plane into the eight neighbours x00 x01 x02 x12 x22 x21 x20 x10 and the
+# centre x11, and `y - x @ filter` is the residual; here the 8 taps go to the kernel, which reads the neighbours itself
+# (ops._filter_taps64), and the HILL cost is computed on the device.  conseal.hill._costmap.compute_cost of the reference is the
+# textbook cost of ws_unet_amd.hill (the one that reproduces the published filters.csv).
+
+def _plane_u8(img: np.ndarray, channel: int) -> np.ndarray:
+    p = np.asarray(img)[..., channel]
+    if p.dtype != np.uint8:
+        u = p.astype(np.uint8)
+        if not np.array_equal(u, p):
+            raise ValueError("the HILL cost is defined on 8-bit pixel values")
+        p = u
+    return np.ascontiguousarray(p)
+
+
+def _device_error(x_u8_host, filter):
+    """(N,H,W) uint8 host planes -> numpy (mae[N], wmae[N]) of the in-kernel filter prediction."""
+    import torch
+    from . import ops
+    x = torch.as_tensor(x_u8_host).to("cuda", non_blocking=True)
+    mae, wmae = ops.prediction_error(x, pixel_filter=filter)
+    return mae.cpu().numpy(), wmae.cpu().numpy()
+
+
+def _row(fname, channels, filter_name, mae, wmae, kw) -> dict:
+    ch = "".join(map(str, channels))
+    return {"fname": fname, f"mae_{ch}_{filter_name}": float(mae), f"wmae_{ch}_{filter_name}": float(wmae), **kw}
+
+
+_ROW_KEYS = ("filter", "filter_name", "channels", "process_image", "imread")
+
+
+def _residuals_one(fname, filter: np.ndarray, filter_name: str, channels: typing.Tuple[int],
+                               process_image: typing.Callable = None, imread: typing.Callable = imread4_u8, **kw):
+    """Row {fname, mae_<ch>_<name>, wmae_<ch>_<name>, **kw} of one image (src/filters/evaluate.py:79-115).  `process_image` is
+    accepted for the reference's signature; the neighbour features are read by the kernel from plane channels[0]."""
+    x = _plane_u8(imread(fname), channels[0])
+    mae, wmae = _device_error(x[None], filter)
+    return _row(fname, channels, filter_name, mae[0], wmae[0], kw)
+
+
+get_filter_residuals_cover = fabrika.precovers(iterator="python", convert_to="pandas", ignore_missing=True)(_residuals_one)
+
+
+def _residuals_batch(fnames, kws, *, filter, filter_name, channels, imread=imread4_u8, prefetched=None, **_ignored):
+    """get_filter_residuals_cover for a chunk (fabrika iterator='batched'): one upload and one launch chain for the whole chunk."""
+    planes = prefetched[0] if prefetched is not None else _chunk_planes(fnames, channels, imread)
+    if planes is None:                                             # ragged chunk
+        return [_residuals_one(f, filter, filter_name, channels, imread=imread, **kw) for f, kw in zip(fnames, kws)]
+    mae, wmae = _device_error(planes, filter)
+    return [_row(f, channels, filter_name, mae[i], wmae[i], kw) for i, (f, kw) in enumerate(zip(fnames, kws))]
+
+
+def _chunk_planes(fnames, channels, imread):
+    from .evaluate import load_planes_u8
+    from .imread import imread4_f32
+    if tuple(channels) == (3,) and imread in (imread4_u8, imread4_f32):
+        return load_planes_u8(fnames, imread4_u8)                  # native batched decode of the Y plane into a pinned buffer
+    planes = [_plane_u8(imread(f), channels[0]) for f in fnames]
+    return np.stack(planes) if len({p.shape for p in planes}) == 1 else None
+
+
+def _split_kw(fn):
+    def wrapped(fnames, kws, prefetched=None):
+        shared = {k: kws[0][k] for k in _ROW_KEYS if k in kws[0]}
+        clean = [{k: v for k, v in kw.items() if k not in _ROW_KEYS} for kw in kws]
+        return fn(fnames, clean, prefetched=prefetched, **shared)
+
+    wrapped.prefetch = lambda fnames, kws: (_chunk_planes(fnames, kws[0]["channels"], kws[0].get("imread", imread4_u8)),)
+    return wrapped
+
+
+get_filter_residuals_cover_batched = fabrika.precovers(iterator="batched", convert_to="pandas", ignore_missing=True)(
+    _split_kw(_residuals_batch))
+
+
+def run(input_dir: pathlib.Path, filter_names: typing.Sequence[str] = ("AVG", "KB"), channels=((3,),),
+        imread: typing.Callable = imread4_u8, iterator: str = "python", **kw):
+    """The filters.csv table (src/filters/evaluate.py:149-179): one frame per zip(channels, filter_names) pair, concatenated.
+    With the default one-entry `channels` only the first filter (AVG) runs, as in the reference; its __main__ passes [[3], [3]].
+    iterator='batched' sends chunks of files through one launch chain (`batch_size` images)."""
+    import pandas as pd
+    fn = {"python": get_filter_residuals_cover, "batched": get_filter_residuals_cover_batched}[iterator]
+    res = []
+    for channel, filter_name in zip(channels, filter_names):
+        res.append(fn(input_dir, filter=get_coefficients(filter_name), filter_name=filter_name, channels=tuple(channel),
+                      imread=imread, **kw))
+    return pd.concat(res)

@@ -1010,6 +1010,89 @@ def ws_attack(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, x_bia
     return (beta, sums) if return_sums else beta
 
 
+def hill_cost(x_u8: torch.Tensor, clamp: float = 1e10) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,H,W) fp32 HILL cost with cost[inf | nan | > clamp] = clamp (wsu_hill_cost, K12)."""
+    lib = _lib.load()
+    _dev_check(x_u8)
+    assert x_u8.dtype == torch.uint8 and x_u8.dim() == 3
+    n, h, w = x_u8.shape
+    cost = torch.empty((n, h, w), dtype=torch.float32, device=x_u8.device)
+    check(_launch("hill_cost", {"bytes": float(n * h * w * 5)}, lambda: lib.wsu_hill_cost(
+        x_u8.data_ptr(), cost.data_ptr(), float(clamp), n, h, w, _stream())), "wsu_hill_cost")
+    return cost
+
+
+def hill_threshold(cost: torch.Tensor, quantile: float = 0.1) -> torch.Tensor:
+    """cost: (N,H,W) fp32 -> q[N] fp64 = numpy.quantile(cost[i, 1:-1, 1:-1], quantile) ('linear'), by an exact radix select (K13)."""
+    from .hill import quantile_index
+    lib = _lib.load()
+    _dev_check(cost)
+    assert cost.dtype == torch.float32 and cost.dim() == 3
+    n, h, w = cost.shape
+    k, g = quantile_index((h - 2) * (w - 2), quantile)
+    q = torch.empty(n, dtype=torch.float64, device=cost.device)
+    ws = torch.empty(lib.wsu_hill_threshold_workspace_bytes(n) // 4, dtype=torch.int32, device=cost.device)
+    check(_launch("hill_threshold", {"bytes": float(n * h * w * 16)}, lambda: lib.wsu_hill_threshold(
+        cost.data_ptr(), k, g, q.data_ptr(), ws.data_ptr(), ws.numel() * 4, n, h, w, _stream())), "wsu_hill_threshold")
+    return q
+
+
+def _filter_taps64(k) -> np.ndarray:
+    """Pixel filter -> 9 contiguous host doubles, the weight of x[r-1+a][c-1+b] at [a*3+b].  Accepts the reference's flattened
+    8-tap coefficients ((8,) / (8,1), NAMED_FILTERS, neighbour order x00 x01 x02 x12 x22 x21 x20 x10 of _defs/filters.py:57-67)
+    or a (3,3[,1]) kernel array in the convolution layout of NAMED_FILTERS_2D (the one ws_attack takes)."""
+    k = np.asarray(k, dtype=np.float64)
+    if k.size == 8:
+        f = k.reshape(8)
+        out = np.zeros((3, 3))
+        for t, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 2), (2, 2), (2, 1), (2, 0), (1, 0))):
+            out[a, b] = f[t]
+        return np.ascontiguousarray(out.reshape(9))
+    if k.ndim == 3 and k.shape[2] == 1:
+        k = k[..., 0]
+    if k.shape != (3, 3):
+        raise ValueError(f"8 flattened taps or a 3x3 single-channel kernel expected, got shape {k.shape}")
+    return np.ascontiguousarray(k[::-1, ::-1].reshape(9))         # true convolution -> weights of x[r-1+a][c-1+b]
+
+
+def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, hat_scale: float = 255.,
+                     quantile: float = 0.1, cost: Optional[torch.Tensor] = None, return_threshold: bool = False):
+    """Per-image MAE and HILL-cost weighted MAE of a pixel prediction on the interior [1:-1,1:-1] (K12-K14).
+    x_u8: (N,H,W) uint8.  x_hat: (N,H,W)/(N,1,H,W) full-frame prediction or (N,H-2,W-2) interior prediction, multiplied by
+    `hat_scale` (255 for a network output in [0,1]); or `pixel_filter` (8 flattened taps or a (3,3[,1]) kernel, see _filter_taps64)
+    evaluated in float64 inside the kernel.  `cost` reuses a hill_cost() map.  Returns (mae[N], wmae[N]) fp64 on the device,
+    plus (q[N] fp64, selected[N] int64) with return_threshold=True."""
+    lib = _lib.load()
+    _dev_check(x_u8, x_hat, cost)
+    assert x_u8.dtype == torch.uint8 and x_u8.dim() == 3
+    n, h, w = x_u8.shape
+    if (x_hat is None) == (pixel_filter is None):
+        raise ValueError("give exactly one of x_hat / pixel_filter")
+    hat_full = 1
+    if x_hat is not None:
+        assert x_hat.dtype == torch.float32
+        if x_hat.numel() == n * h * w:
+            hat_full = 1
+        elif x_hat.numel() == n * (h - 2) * (w - 2):
+            hat_full = 0
+        else:
+            raise ValueError(f"prediction of {tuple(x_hat.shape)} does not match pixels {tuple(x_u8.shape)}")
+    pt = _filter_taps64(pixel_filter) if pixel_filter is not None else None
+    if cost is None:
+        cost = hill_cost(x_u8)
+    assert cost.dtype == torch.float32 and cost.shape == x_u8.shape
+    q = hill_threshold(cost, quantile)
+    mae = torch.empty(n, dtype=torch.float64, device=x_u8.device)
+    wmae = torch.empty(n, dtype=torch.float64, device=x_u8.device)
+    sel = torch.empty(n, dtype=torch.int64, device=x_u8.device)
+    ws = torch.empty(lib.wsu_prediction_error_workspace_bytes(n) // 8, dtype=torch.float64, device=x_u8.device)
+    check(_launch("prediction_error", {"bytes": float(n * h * w * (9 if x_hat is not None else 5))}, lambda: lib.wsu_prediction_error(
+        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
+        hat_full, float(hat_scale), cost.data_ptr(), q.data_ptr(), mae.data_ptr(), wmae.data_ptr(), sel.data_ptr(),
+        ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())), "wsu_prediction_error")
+    return (mae, wmae, q, sel) if return_threshold else (mae, wmae)
+
+
 def filter3x3_valid(x: torch.Tensor, kernel) -> torch.Tensor:
     """x: (N,H,W) fp32 -> (N,H-2,W-2) fp32 = convolve(x/255., K, 'valid')*255. (wsu_filter3x3_valid_f32)."""
     lib = _lib.load()
