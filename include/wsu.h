@@ -391,6 +391,24 @@ int wsu_prediction_error(const uint8_t* x_u8, const float* x_hat, const double* 
                          const float* cost, const double* q, double* mae, double* wmae, long long* selected,
                          void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
 
+/* ---- K15: correlation of a predictor's cover estimate, made from the stego image, with the embedding change,
+ *      src/correlation.py:22-59 `run` (results/estimation/correlation.csv), per cover/stego pair on the interior [1:-1,1:-1]:
+ *        d = x_s - x_c;  dhat = xhat - x_c;  cor = (sum((dhat - mean dhat)(d - mean d)) / (n-1)) / std(xhat) / std(d)
+ *      with n = (H-2)(W-2) and both stds ddof 0 -- the reference's quirks, restated: std of xhat (not dhat), so the identity
+ *      filter gives ~0.013 and |cor| can exceed 1; IEEE division (x_s == x_c -> NaN, constant prediction -> +-inf or NaN).
+ *      xc_u8, xs_u8: (N,H,W) DEVICE cover / stego pixels.  The prediction xhat of the STEGO plane is either
+ *        x_hat (DEVICE fp32): hat_full=1 -> (N,H,W) read at [r][c], xhat = float32(x_hat*hat_scale) (a network output, hat_scale = 255),
+ *                             hat_full=0 -> (N,H-2,W-2) (what a host `predictor(x)` returns; hat_scale = 1), or
+ *        pixel_filter (HOST, 9 doubles K[a][b] of the reference's (3,3,1) kernel array, K11's layout): the 'valid' convolution
+ *                             sum_ab K[a][b] * x_s[r+1-a][c+1-b], evaluated inside the kernel in fp64.
+ *      Two passes (means, then centred fp64 sums), fixed-order and free of float atomics: deterministic and batch-independent.
+ *      cor: (N) DEVICE fp64; moments: optional (N,6) DEVICE fp64 {mean xhat, mean dhat, mean d, S_hd, S_hh, S_dd} (centred sums).
+ *      workspace: DEVICE, wsu_pair_correlation_workspace_bytes(n). */
+size_t wsu_pair_correlation_workspace_bytes(int n);
+int wsu_pair_correlation(const uint8_t* xc_u8, const uint8_t* xs_u8, const float* x_hat, const double* pixel_filter, int hat_full,
+                         float hat_scale, double* cor, double* moments, void* workspace, size_t workspace_bytes,
+                         int n, int h, int w, void* stream);
+
 /* Linear pixel predictor on its own (filters/evaluate.py:136-141): y (N,H-2,W-2) = convolve(x/255., K, 'valid')*255.
  * x: DEVICE (N,H,W) fp32; filter: HOST 9 floats K[a][b]. */
 int wsu_filter3x3_valid_f32(const float* x, const float* filter, float* y, int n, int h, int w, void* stream);

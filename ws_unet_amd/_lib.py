@@ -99,6 +99,8 @@ SIGNATURES = {
     "wsu_hill_threshold": (c_int, [_P, c_longlong, c_double, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
     "wsu_prediction_error_workspace_bytes": (c_size_t, [c_int]),
     "wsu_prediction_error": (c_int, [_P, _P, _P, c_int, c_float, _P, _P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_pair_correlation_workspace_bytes": (c_size_t, [c_int]),
+    "wsu_pair_correlation": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_u8_to_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     # ---- backward / train step

@@ -1093,6 +1093,45 @@ def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *
     return (mae, wmae, q, sel) if return_threshold else (mae, wmae)
 
 
+def pair_correlation(xc_u8: torch.Tensor, xs_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None,
+                     hat_full: bool = True, hat_scale: float = 255., moments: bool = False):
+    """Per-pair correlation of a cover estimate made from the stego plane with the embedding change (K15, src/correlation.py:22-59):
+    cor = (sum((dhat - mean dhat)(d - mean d)) / (n-1)) / std(xhat) / std(d) on the interior, d = x_s - x_c, dhat = xhat - x_c.
+    xc_u8, xs_u8: (N,H,W) uint8.  x_hat: (N,H,W) / (N,1,H,W) full-frame prediction (hat_full=True; a network output in [0,1], scaled by
+    `hat_scale` in float32) or (N,H-2,W-2) interior prediction in grey levels (hat_full=False, hat_scale=1.); or `pixel_filter`, a
+    (3,3[,1]) kernel array in K11's layout, evaluated on the stego plane in float64 inside the kernel.  Returns cor[N] fp64 on the
+    device, plus the (N,6) fp64 moments {mean xhat, mean dhat, mean d, S_hd, S_hh, S_dd} with moments=True."""
+    lib = _lib.load()
+    _dev_check(xc_u8, xs_u8, x_hat)
+    if xc_u8.dtype != torch.uint8 or xs_u8.dtype != torch.uint8 or xc_u8.dim() != 3 or xs_u8.shape != xc_u8.shape:
+        raise ValueError(f"cover / stego planes must be two (N,H,W) uint8 tensors of one shape, got {tuple(xc_u8.shape)} {xc_u8.dtype} "
+                         f"and {tuple(xs_u8.shape)} {xs_u8.dtype}")
+    n, h, w = xc_u8.shape
+    if (x_hat is None) == (pixel_filter is None):
+        raise ValueError("give exactly one of x_hat / pixel_filter")
+    if x_hat is not None:
+        if x_hat.dtype != torch.float32:
+            raise ValueError(f"x_hat must be float32, got {x_hat.dtype}")
+        want = n * h * w if hat_full else n * (h - 2) * (w - 2)
+        if x_hat.numel() != want:
+            raise ValueError(f"prediction of {tuple(x_hat.shape)} does not match pixels {tuple(xc_u8.shape)} (hat_full={bool(hat_full)})")
+    pt = None
+    if pixel_filter is not None:                                   # K11's layout K[a][b], kept in float64 (no float32 rounding of the taps)
+        pt = np.asarray(pixel_filter, dtype=np.float64)
+        pt = pt[..., 0] if pt.ndim == 3 and pt.shape[2] == 1 else pt
+        if pt.shape != (3, 3):
+            raise ValueError(f"3x3 single-channel kernel expected, got shape {np.shape(pixel_filter)}")
+        pt = np.ascontiguousarray(pt.reshape(9))
+    cor = torch.empty(n, dtype=torch.float64, device=xc_u8.device)
+    mom = torch.empty((n, 6), dtype=torch.float64, device=xc_u8.device) if moments else None
+    ws = torch.empty(lib.wsu_pair_correlation_workspace_bytes(n) // 8, dtype=torch.float64, device=xc_u8.device)
+    check(_launch("pair_correlation", {"bytes": float(n * h * w * (2 if x_hat is None else 6) * 2)}, lambda: lib.wsu_pair_correlation(
+        xc_u8.data_ptr(), xs_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
+        int(bool(hat_full)), float(hat_scale), cor.data_ptr(), mom.data_ptr() if mom is not None else None, ws.data_ptr(), ws.numel() * 8,
+        n, h, w, _stream())), "wsu_pair_correlation")
+    return (cor, mom) if moments else cor
+
+
 def filter3x3_valid(x: torch.Tensor, kernel) -> torch.Tensor:
     """x: (N,H,W) fp32 -> (N,H-2,W-2) fp32 = convolve(x/255., K, 'valid')*255. (wsu_filter3x3_valid_f32)."""
     lib = _lib.load()
