@@ -409,6 +409,38 @@ int wsu_pair_correlation(const uint8_t* xc_u8, const uint8_t* xs_u8, const float
                          float hat_scale, double* cor, double* moments, void* workspace, size_t workspace_bytes,
                          int n, int h, int w, void* stream);
 
+/* ---- K16-K18: the KB-stratified absolute-error box table, src/error_boxes.py `plot_error` (results/prediction/ae_boxes_3.csv):
+ *      per predictor the absolute error (AE) of every interior pixel [1:-1,1:-1] of the split, image-major; the pixels are cut into
+ *      slices by the anchor predictor's AE (the reference sorts by it and slices at argmin(sorted <= e_j) - 1, defs.py:77-92 for
+ *      the statistics), and each (predictor, slice) reports min, q25, q50, q75, max.
+ *
+ * K16 wsu_ae_values: the float32 AE of one predictor for N (N,H,W) DEVICE u8 planes, written to keys[key_offset + i*per + j]
+ *      (per = num_idx, or (H-2)(W-2) for all pixels, row-major); key_capacity bounds the write.  The predictor is either
+ *        pixel_filter (HOST, 9 doubles, the weight of x[r-1+a][c-1+b] at [a*3+b]: K14's layout): |y - x @ f| in fp64
+ *                     (filters/evaluate.py:53-76), exact in float32 for the dyadic taps the Python layer admits, or
+ *        x_hat (DEVICE fp32 (N,H,W) network output): |x - float32(x_hat*hat_scale)|, K10's float32 residual.
+ *      idx: optional DEVICE int64 (N,num_idx) interior indices (`subset_residual`'s draws, with replacement, in draw order).
+ *      flag: DEVICE u32, OR-ed with 1 on a NaN / infinite AE and with 2 on an index outside the interior (that key is not written).
+ * K17 wsu_ae_slices: over `count` anchor keys (DEVICE fp32, non-negative) and HOST edges e_j (1..5 of them), writes DEVICE u64
+ *      out[num_edges + 1][3]: row j < num_edges {#(a <= e_j), bits of max{a <= e_j}, largest index holding it + 1} -- the key at
+ *      rank c_j - 1 of the stable sort by (a, index) -- and row num_edges {-, bits of max a, largest index holding it + 1}, the
+ *      key at rank N - 1 (0 = no such key).  The host turns them into the slices' boundary keys.
+ * K18 wsu_ae_select: exact order statistics per (predictor, slice) by a radix select over the float32 bit patterns (11/11/10-bit
+ *      digits, one pass over all predictors' keys per level, then one for c_(k+1)).  keys: DEVICE fp32 [num_pred][stride], the first
+ *      `count` of each row used; anchor: the row that defines the slices.  slices: HOST int64 [num_slices][10] = {size, has_lo,
+ *      lo_bits, lo_idx, has_hi, hi_bits, hi_idx, k0, k1, k2}: a pixel at index i with anchor bits a is in the slice iff
+ *      (lo_bits, lo_idx) <= (a, i) < (hi_bits, hi_idx) lexicographically (an absent bound always holds); size = its pixel count
+ *      (0 = empty); k_t < size are the ranks to select.  out: DEVICE u32 [num_pred][num_slices][8] float32 bits {min, max,
+ *      c_(k0), c_(k0+1), c_(k1), c_(k1+1), c_(k2), c_(k2+1)} (c_(k+1) clamped to the last rank; NaN for an empty slice).
+ *      flags: DEVICE u32 [num_pred], 1 where a key is negative, NaN or infinite.  Integer atomics only: deterministic.
+ *      workspace: DEVICE, wsu_ae_select_workspace_bytes(num_pred); num_pred <= 16, num_slices <= 6. */
+int wsu_ae_values(const uint8_t* x_u8, const float* x_hat, const double* pixel_filter, float hat_scale, const long long* idx, int num_idx,
+                  float* keys, size_t key_offset, size_t key_capacity, uint32_t* flag, int n, int h, int w, void* stream);
+int wsu_ae_slices(const float* anchor_keys, long long count, const double* edges, int num_edges, unsigned long long* out, void* stream);
+size_t wsu_ae_select_workspace_bytes(int num_pred);
+int wsu_ae_select(const float* keys, size_t stride, int num_pred, int anchor, long long count, const long long* slices, int num_slices,
+                  uint32_t* out, uint32_t* flags, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Linear pixel predictor on its own (filters/evaluate.py:136-141): y (N,H-2,W-2) = convolve(x/255., K, 'valid')*255.
  * x: DEVICE (N,H,W) fp32; filter: HOST 9 floats K[a][b]. */
 int wsu_filter3x3_valid_f32(const float* x, const float* filter, float* y, int n, int h, int w, void* stream);

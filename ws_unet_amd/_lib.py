@@ -101,6 +101,10 @@ SIGNATURES = {
     "wsu_prediction_error": (c_int, [_P, _P, _P, c_int, c_float, _P, _P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
     "wsu_pair_correlation_workspace_bytes": (c_size_t, [c_int]),
     "wsu_pair_correlation": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_ae_values": (c_int, [_P, _P, _P, c_float, _P, c_int, _P, c_size_t, c_size_t, _P, c_int, c_int, c_int, _P]),
+    "wsu_ae_slices": (c_int, [_P, c_longlong, _P, c_int, _P, _P]),
+    "wsu_ae_select_workspace_bytes": (c_size_t, [c_int]),
+    "wsu_ae_select": (c_int, [_P, c_size_t, c_int, c_int, c_longlong, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_u8_to_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     # ---- backward / train step

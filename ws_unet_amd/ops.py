@@ -1132,6 +1132,78 @@ def pair_correlation(xc_u8: torch.Tensor, xs_u8: torch.Tensor, x_hat: Optional[t
     return (cor, mom) if moments else cor
 
 
+def ae_values(x_u8: torch.Tensor, keys: torch.Tensor, offset: int, flag: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *,
+              pixel_filter=None, hat_scale: float = 255., idx: Optional[torch.Tensor] = None) -> None:
+    """K16: the float32 absolute error of one predictor on the interior of (N,H,W) uint8 planes, written into the 1-D float32 `keys`
+    at `offset` + i*per + j (per = idx.shape[1], or (H-2)(W-2)).  The predictor is a full-frame `x_hat` ((N,H,W) / (N,1,H,W) fp32,
+    times `hat_scale`: |x - x_hat*255| in float32) or `pixel_filter` (9 taps in the kernel's layout, or anything
+    _filter_taps64 takes; |y - x @ f| in float64).  idx: optional
+    (N,m) int64 interior indices.  flag: a 1-element int32 device tensor, OR-ed with 1 on NaN / inf, 2 on a bad index."""
+    lib = _lib.load()
+    _dev_check(x_u8, keys, flag, x_hat, idx)
+    if x_u8.dtype != torch.uint8 or x_u8.dim() != 3 or keys.dtype != torch.float32 or keys.dim() != 1 or not keys.is_contiguous():
+        raise ValueError(f"(N,H,W) uint8 planes and a contiguous 1-D float32 key array expected, got {tuple(x_u8.shape)} {x_u8.dtype}, "
+                         f"{tuple(keys.shape)} {keys.dtype}")
+    n, h, w = x_u8.shape
+    if (x_hat is None) == (pixel_filter is None):
+        raise ValueError("give exactly one of x_hat / pixel_filter")
+    if x_hat is not None and (x_hat.dtype != torch.float32 or x_hat.numel() != n * h * w or not x_hat.is_contiguous()):
+        raise ValueError(f"x_hat must be a contiguous float32 full-frame prediction of {n * h * w} values, got {tuple(x_hat.shape)}")
+    m = 0
+    if idx is not None:
+        if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != n or not idx.is_contiguous():
+            raise ValueError(f"idx must be a contiguous (N,m) int64 tensor, got {tuple(idx.shape)} {idx.dtype}")
+        m = int(idx.shape[1])
+    pt = None
+    if pixel_filter is not None:                                   # 9 taps already in the kernel's layout, or what _filter_taps64 takes
+        pf = np.asarray(pixel_filter, dtype=np.float64)
+        pt = np.ascontiguousarray(pf) if pf.shape == (9,) else _filter_taps64(pf)
+    per = m if m else (h - 2) * (w - 2)
+    check(_launch("ae_values", {"bytes": float(n * (h * w * (5 if x_hat is not None else 1) + per * 4))}, lambda: lib.wsu_ae_values(
+        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None, float(hat_scale),
+        idx.data_ptr() if idx is not None else None, m, keys.data_ptr(), int(offset), keys.numel(), flag.data_ptr(), n, h, w,
+        _stream())), "wsu_ae_values")
+
+
+def ae_slices(anchor_keys: torch.Tensor, edges, count: Optional[int] = None) -> torch.Tensor:
+    """K17 over the first `count` (default: all) anchor keys: a (len(edges)+1, 3) uint64-valued int64 device tensor, row j
+    {#(a <= e_j), float32 bits of max{a <= e_j}, largest index holding it + 1}, last row {0, bits of max a, its largest index + 1}."""
+    lib = _lib.load()
+    _dev_check(anchor_keys)
+    if anchor_keys.dtype != torch.float32 or anchor_keys.dim() != 1 or not anchor_keys.is_contiguous():
+        raise ValueError(f"a contiguous 1-D float32 key array expected, got {tuple(anchor_keys.shape)} {anchor_keys.dtype}")
+    count = anchor_keys.numel() if count is None else int(count)
+    if not 0 < count <= anchor_keys.numel():
+        raise ValueError(f"count={count} outside (0, {anchor_keys.numel()}] of the anchor keys")
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+    out = torch.empty((len(e) + 1, 3), dtype=torch.int64, device=anchor_keys.device)
+    check(_launch("ae_slices", {"bytes": float(count * 8)}, lambda: lib.wsu_ae_slices(
+        anchor_keys.data_ptr(), count, e.ctypes.data, len(e), out.data_ptr(), _stream())), "wsu_ae_slices")
+    return out
+
+
+def ae_select(keys: torch.Tensor, anchor: int, slices, count: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """K18: exact order statistics per (predictor, slice).  keys: (P, stride) float32 device tensor (the first `count` of each row);
+    slices: host int64 (S, 10) descriptors (include/wsu.h).  Returns (out (P,S,8) int32 device tensor of float32 bit patterns
+    {min, max, c_(k0), c_(k0+1), c_(k1), c_(k1+1), c_(k2), c_(k2+1)}, flags (P,) int32: 1 where a key is negative or not finite)."""
+    lib = _lib.load()
+    _dev_check(keys)
+    if keys.dtype != torch.float32 or keys.dim() != 2 or not keys.is_contiguous():
+        raise ValueError(f"a contiguous (P, N) float32 key array expected, got {tuple(keys.shape)} {keys.dtype}")
+    p, stride = keys.shape
+    count = stride if count is None else int(count)
+    sl = np.ascontiguousarray(np.asarray(slices, dtype=np.int64))
+    if sl.ndim != 2 or sl.shape[1] != 10:
+        raise ValueError(f"(S, 10) slice descriptors expected, got {sl.shape}")
+    out = torch.empty((p, sl.shape[0], 8), dtype=torch.int32, device=keys.device)
+    flags = torch.empty(p, dtype=torch.int32, device=keys.device)
+    ws = torch.empty(lib.wsu_ae_select_workspace_bytes(p) // 8, dtype=torch.int64, device=keys.device)
+    check(_launch("ae_select", {"bytes": float(p * count * 8 * 8)}, lambda: lib.wsu_ae_select(
+        keys.data_ptr(), stride, p, int(anchor), count, sl.ctypes.data, sl.shape[0], out.data_ptr(), flags.data_ptr(), ws.data_ptr(),
+        ws.numel() * 8, _stream())), "wsu_ae_select")
+    return out, flags
+
+
 def filter3x3_valid(x: torch.Tensor, kernel) -> torch.Tensor:
     """x: (N,H,W) fp32 -> (N,H-2,W-2) fp32 = convolve(x/255., K, 'valid')*255. (wsu_filter3x3_valid_f32)."""
     lib = _lib.load()
