@@ -441,6 +441,24 @@ size_t wsu_ae_select_workspace_bytes(int num_pred);
 int wsu_ae_select(const float* keys, size_t stride, int num_pred, int anchor, long long count, const long long* slices, int num_slices,
                   uint32_t* out, uint32_t* flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K19: exact confusion counts of a threshold sweep, src/ws/roc.py `produce_roc` (results/detection/auc_*.csv, roc_*.csv),
+ *      for `groups` groups of scores in one call.  numpy's semantics, as the reference computes (y_hat > tau) & (y > 0.):
+ *        TP_j = #{pos: s > tau_j}   FP_j = #{neg: s > tau_j}   TN_j = #{neg: s <= tau_j}   FN_j = #{pos: s <= tau_j}
+ *      compared in float64 (a float32 score widened exactly: NumPy 2 / NEP 50 compares a float32 array with an np.float64 tau in
+ *      float64; numpy 1.x rounded tau to float32 first).  A NaN score or a label other than 0 / 1 is in none of the four counts;
+ *      +-inf are ordinary scores.
+ *      scores: DEVICE fp64 [offsets[groups]]; labels: DEVICE int8, one per score: 1 = positive (y > 0), 0 = negative (y <= 0),
+ *      -1 = neither (y is NaN); offsets: HOST int64 [groups + 1], offsets[0] = 0, non-decreasing -- group g is
+ *      [offsets[g], offsets[g+1]) (empty groups allowed; scores / labels may be NULL when every group is); taus: HOST fp64 [t],
+ *      finite, strictly ascending, 1 <= t <= 4096; groups <= 65535.  taus and offsets are copied into the workspace on `stream`.
+ *      counts: DEVICE int64 [groups][t][4] = {TP, FP, TN, FN} at taus[j].  Two passes: a (label, bin) histogram per group with
+ *      bin = #{tau_j < s} (LDS, 64-bit global integer atomics), then a fixed-order prefix scan -- deterministic and independent of
+ *      how the scores are split into calls.  workspace: DEVICE, wsu_roc_counts_workspace_bytes(groups, t) (0 for bad arguments),
+ *      zeroed on the stream by every call. */
+size_t wsu_roc_counts_workspace_bytes(int groups, int t);
+int wsu_roc_counts(const double* scores, const signed char* labels, const long long* offsets, int groups, const double* taus, int t,
+                   long long* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Linear pixel predictor on its own (filters/evaluate.py:136-141): y (N,H-2,W-2) = convolve(x/255., K, 'valid')*255.
  * x: DEVICE (N,H,W) fp32; filter: HOST 9 floats K[a][b]. */
 int wsu_filter3x3_valid_f32(const float* x, const float* filter, float* y, int n, int h, int w, void* stream);

@@ -1204,6 +1204,36 @@ def ae_select(keys: torch.Tensor, anchor: int, slices, count: Optional[int] = No
     return out, flags
 
 
+def roc_counts(scores: torch.Tensor, labels: torch.Tensor, offsets, taus) -> torch.Tensor:
+    """K19: exact confusion counts of a threshold sweep over G groups of scores (include/wsu.h).  scores: contiguous 1-D float64 device
+    tensor; labels: contiguous 1-D int8 device tensor of the same length (1 positive, 0 negative, -1 neither); offsets: host int64 (G+1,)
+    group bounds (offsets[0] = 0, non-decreasing, offsets[-1] = len(scores)); taus: host float64 (T,), finite, strictly ascending,
+    T <= 4096.  Returns a (G, T, 4) int64 device tensor {TP, FP, TN, FN}: a score counts as above tau_j iff s > tau_j in float64, a NaN
+    score or a -1 label in none of the four."""
+    lib = _lib.load()
+    for name, t, dt in (("scores", scores, torch.float64), ("labels", labels, torch.int8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D {dt} tensor, got {getattr(t, 'dtype', type(t))} of shape {tuple(getattr(t, 'shape', ()))}")
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be on the GPU (no CPU fallback exists)")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if labels.numel() != scores.numel() or labels.device != scores.device:
+        raise ValueError(f"labels ({labels.numel()} on {labels.device}) must match scores ({scores.numel()} on {scores.device})")
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    tau = np.ascontiguousarray(np.asarray(taus, dtype=np.float64).reshape(-1))
+    if off.size < 2 or off[-1] != scores.numel():
+        raise ValueError(f"offsets must hold G+1 >= 2 bounds ending at len(scores)={scores.numel()}, got {off.tolist()[:8]}")
+    groups = off.size - 1
+    counts = torch.empty((groups, tau.size, 4), dtype=torch.int64, device=scores.device)
+    nbytes = lib.wsu_roc_counts_workspace_bytes(groups, tau.size)
+    ws = torch.empty(max(1, nbytes // 8), dtype=torch.int64, device=scores.device)
+    check(_launch("roc_counts", {"bytes": float(scores.numel() * 9)}, lambda: lib.wsu_roc_counts(
+        scores.data_ptr() or None, labels.data_ptr() or None, off.ctypes.data, groups, tau.ctypes.data, tau.size, counts.data_ptr(),
+        ws.data_ptr(), nbytes, _stream())), "wsu_roc_counts")
+    return counts
+
+
 def filter3x3_valid(x: torch.Tensor, kernel) -> torch.Tensor:
     """x: (N,H,W) fp32 -> (N,H-2,W-2) fp32 = convolve(x/255., K, 'valid')*255. (wsu_filter3x3_valid_f32)."""
     lib = _lib.load()
