@@ -138,9 +138,10 @@ def test_unet_error_agrees_with_residual_stats_and_host():
     mae, wmae = evaluate.predict_u8_error_batch(x_u8, model)
     _, l1 = evaluate.predict_u8_batch(x_u8, model)
     mae, wmae, l1 = mae.cpu().numpy(), wmae.cpu().numpy(), l1.cpu().numpy()
-    # both means sum the same float32 |x - y*255| terms in fp64, in different fixed orders (K10: 1024 strided threads and one tree;
-    # K14: 64 row blocks x 256 threads, two trees): the fp64 means agree to ~1e-15, so their float32 roundings agree unless the mean
-    # sits at an fp32 rounding boundary -- then they are one fp32 ulp apart
+    # both means sum the same float32 |x - fl32(y*255)| terms (wsu_metric.h residual_f32: the product is rounded before the subtraction
+    # in K10 and in K14 alike) in fp64, in different fixed orders (K10: 1024 strided threads and one tree; K14: 64 row blocks x 256
+    # threads, two trees): the fp64 means agree to ~1e-15, so their float32 roundings agree unless the mean sits at an fp32 rounding
+    # boundary -- then they are one fp32 ulp apart
     assert np.all(np.abs(mae.astype(np.float32) - l1) <= np.spacing(l1)), (mae, l1)
     assert np.all(np.abs(mae - l1.astype(np.float64)) <= np.spacing(l1) * 0.5 + 1e-12 * l1)
     # wmae against the host from the same GPU output
@@ -148,10 +149,17 @@ def test_unet_error_agrees_with_residual_stats_and_host():
         y = model(ops.u8_to_unit(x_u8)[:, None])[:, 0].contiguous()
     cost = ops.hill_cost(x_u8).cpu().numpy().astype(np.float64)
     yh = y.cpu().numpy()
+    mae_y = ops.prediction_error(x_u8, y)[0].cpu().numpy()      # K14 on this very y
     for i in range(4):
         d = u8[i][1:-1, 1:-1].astype(np.float32) - yh[i][1:-1, 1:-1] * np.float32(255.)
         w_ref, _, _ = hill_np.wmae(np.abs(d).astype(np.float64), cost[i][1:-1, 1:-1])
         assert _rel(wmae[i], w_ref) <= 1e-6
+        # K14's fp64 mae is the mean of exactly these float32 terms: only the fp64 summation order differs (the filter path's bound
+        # above).  A residual fused into one FMA (x - y*255 rounded once) misses this by ~1e-8.
+        m_ref = np.abs(d).astype(np.float64).mean()
+        print(f"image {i}: mae {mae_y[i]!r} host {m_ref!r} rel {_rel(mae_y[i], m_ref):.3e}; batch mae rel {_rel(mae[i], m_ref):.3e}")
+        assert _rel(mae_y[i], m_ref) <= 1e-12
+        assert _rel(mae[i], m_ref) <= 1e-12
 
 
 def test_unet_error_rows(tmp_path):

@@ -2,6 +2,7 @@
 read-after-write sites that made the fused head of conv3x3_pl return wrong logits on ~25 % of the launches must not come back with a
 future schedule.  `make -C ws_unet_amd/csrc isa` emits the gfx950 assembly with each TU's own flags (hipcc cross-compiles without a GPU);
 tools/pk_hazard.py defines the pattern.  Cause and hardware evidence: profiles/r03/pk_hazard.md."""
+import re
 import subprocess
 import sys
 from pathlib import Path
@@ -62,3 +63,70 @@ kern_a:
     found = pk_hazard.find_sites(adj)
     assert len(found) == 1 and found[0][3] == [] and not pk_hazard.compiler_pads(found[0][2])
     assert pk_hazard.patch(adj, "waitcnt")[1] == 0 and pk_hazard.patch(adj, "adjacent")[1] == 1
+
+
+# ---- float32 sequences of the metric kernels: no contraction (ws_unet_amd/csrc/wsu_metric.h) ------------------------------------------
+# Kernels that restate numpy's float32 operation sequence.  The conv kernels that share pointwise.hip fuse on purpose and are not listed.
+UNFUSED_KERNELS = {
+    "pointwise.s": ["ws_stats_kernel", "ws_meter_kernel"],                                                    # K10, the WS meter
+    "ws_attack.s": ["ws_attack_partial_kernel", "ws_attack_finish_kernel", "filter3x3_valid_kernel", "lsb_delta_unit_kernel"],   # K11
+    "hill.s": ["hill_cost_kernel", "pred_err_partial_kernel", "pred_err_finish_kernel"],                      # K12, K14
+    "correlation.s": ["pair_corr_mean_kernel", "pair_corr_centred_kernel", "pair_corr_finish_kernel"],        # K15
+    "error_boxes.s": ["ae_values_kernel"],                                                                    # K16
+}
+# f32 FMAs of an expansion other than division, by kernel: (count, what they are).  ws_meter_kernel converts rintf(xi) to int64; the
+# float -> int64 expansion is `v_trunc_f32; v_mul_f32 |t|, 2^-32; v_floor_f32; v_fma_f32 lo, hi, -2^32, |t|; v_cvt_u32_f32 x 2`, and
+# inside the pixel loop the two literals sit in scalar registers (`s_mov_b32 sN, 0xcf800000` before the loop), so the FMA carries no
+# literal of its own.
+OTHER_EXPANSION_FMAS = {"ws_meter_kernel": (1, re.compile(r"v_fma_f32 v\d+, v\d+, (s\d+), \|v\d+\|"))}
+_FMA = re.compile(r"\s*(v_fma_f32|v_fmac_f32|v_fmamk_f32|v_fmaak_f32|v_pk_fma_f32)(_e32|_e64|_dpp|_sdwa)?\s")
+_POW32 = re.compile(r"0x[4c]f800000\b", re.I)                      # +-2^32: the 64-bit integer division's two FMAs per division
+
+
+def kernel_bodies(text):
+    """{kernel name as in the source: its instruction lines}, a body running from the kernel's label to its .amdhsa_kernel line"""
+    lines, out = text.splitlines(), {}
+    for end, ln in enumerate(lines):
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln)
+        if not m:
+            continue
+        start = next(i for i, l in enumerate(lines) if l.startswith(m.group(1) + ":"))
+        short = re.search(r"(?:^_Z|_GLOBAL__N_1)(\d+)(?=\D)", m.group(1))          # the length-prefixed source name of the mangled symbol
+        out[m.group(1)[short.end():short.end() + int(short.group(1))] if short else m.group(1)] = lines[start + 1:end]
+    return out
+
+
+def f32_fmas_and_divisions(body):
+    fmas = [ln.strip() for ln in body if _FMA.match(ln) and not _POW32.search(ln)]
+    return fmas, sum(1 for ln in body if re.match(r"\s*v_div_fixup_f32", ln))
+
+
+def test_no_rn_intrinsic_in_the_sources():
+    """`#pragma clang fp contract(off)` does not reach the round-to-nearest header intrinsics: they carry the default contraction and
+    fuse with a neighbouring add.  Float32 sequences are written with plain operators (wsu_metric.h)."""
+    csrc = ROOT / "ws_unet_amd" / "csrc"
+    bad = [f"{f.name}:{i + 1}" for f in sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.h"))
+           for i, ln in enumerate(f.read_text().splitlines()) if re.search(r"__f(add|sub|mul|div)_rn", ln)]
+    assert not bad, bad
+
+
+def test_metric_kernels_have_no_fused_multiply_add_outside_a_division(isa_files):
+    """In every listed kernel the f32 FMAs are exactly those of its IEEE divisions: #FMA == k * #v_div_fixup_f32, with k read from
+    lsb_delta_unit_kernel of the same build (one division, nothing else that could fuse)."""
+    by_name = {f.name: kernel_bodies(f.read_text()) for f in isa_files if f.name in UNFUSED_KERNELS}
+    fmas, divs = f32_fmas_and_divisions(by_name["ws_attack.s"]["lsb_delta_unit_kernel"])
+    assert divs == 1 and len(fmas) >= 1, (fmas, divs)
+    k = len(fmas)
+    bad = []
+    for fname, kernels in UNFUSED_KERNELS.items():
+        for kern in kernels:
+            body = by_name[fname][kern]
+            fmas, divs = f32_fmas_and_divisions(body)
+            extra, form = OTHER_EXPANSION_FMAS.get(kern, (0, None))
+            if form is not None:                                   # the named expansion: the FMA's scalar operand holds -2^32
+                named = [m for m in map(form.fullmatch, fmas) if m and any(
+                    re.match(rf"\s*s_mov_b32 {m.group(1)}, 0xcf800000\b", ln, re.I) for ln in body)]
+                assert len(named) == extra, (kern, fmas)
+            if len(fmas) != k * divs + extra:
+                bad.append(f"{fname} {kern}: {len(fmas)} f32 FMAs, {divs} divisions x {k} + {extra}: " + " ; ".join(fmas[:6]))
+    assert not bad, "\n".join(bad)

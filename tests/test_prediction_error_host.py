@@ -76,15 +76,31 @@ def test_argument_errors_without_gpu(lib):
 
 
 def test_filter_taps_layout():
-    from ws_unet_amd.ops import _filter_taps64
+    from ws_unet_amd.ops import filter_taps
+
+    def weights(k):
+        return filter_taps(k, np.float64, "weights", "2d 8")
     flat = np.arange(1, 9, dtype=np.float64)                 # x00 x01 x02 x12 x22 x21 x20 x10
-    np.testing.assert_array_equal(_filter_taps64(flat).reshape(3, 3), [[1, 2, 3], [8, 0, 4], [7, 6, 5]])
-    np.testing.assert_array_equal(_filter_taps64(flat[:, None]), _filter_taps64(flat))
+    np.testing.assert_array_equal(weights(flat).reshape(3, 3), [[1, 2, 3], [8, 0, 4], [7, 6, 5]])
+    np.testing.assert_array_equal(weights(flat[:, None]), weights(flat))
     # the (3,3,1) convolution layout of NAMED_FILTERS_2D gives the same weights as the flattened taps
     for name in ("AVG", "KB"):
-        np.testing.assert_array_equal(_filter_taps64(filters.NAMED_FILTERS_2D[name]), _filter_taps64(filters.NAMED_FILTERS[name]))
+        np.testing.assert_array_equal(weights(filters.NAMED_FILTERS_2D[name]), weights(filters.NAMED_FILTERS[name]))
     with pytest.raises(ValueError):
-        _filter_taps64(np.ones((2, 2)))
+        weights(np.ones((2, 2)))
+    # one layout, two directions: the kernel layout is the weights reversed, in the dtype asked for, and a (3,3[,1]) array passes through
+    for name, k2d in filters.NAMED_FILTERS_2D.items():
+        kern = filter_taps(k2d, np.float32, "kernel")
+        assert kern.dtype == np.float32 and kern.flags.c_contiguous
+        np.testing.assert_array_equal(kern, np.asarray(k2d, dtype=np.float32).reshape(9))
+        np.testing.assert_array_equal(filter_taps(k2d, np.float64, "kernel")[::-1], weights(k2d))
+    np.testing.assert_array_equal(filter_taps(flat, np.float64, "kernel", "2d 8")[::-1], weights(flat))
+    nine = np.arange(9, dtype=np.float64)
+    np.testing.assert_array_equal(filter_taps(nine, np.float64, "weights", "2d 8 9"), nine)       # already in the layout
+    for bad, allow in ((flat, "2d"), (nine, "2d 8")):        # 8 or 9 flat values only where the wrapper takes them
+        with pytest.raises(ValueError):
+            filter_taps(bad, np.float64, "weights", allow)
+    assert filter_taps(None, np.float32, "kernel") is None
 
 
 def _fake_dataset(root, names):

@@ -1,0 +1,165 @@
+"""Bit-level record of the metric kernels (K10-K19, filter3x3_valid, lsb_delta_unit, the WS meter) on fixed synthetic inputs.
+
+  python tools/metric_bits.py OUT.json          run every op once and write, per output tensor, the SHA-256 of its bytes; rows whose
+                                                float32 sequence has an inexact product (`may_move`) also keep their values and their
+                                                largest error against a float32 numpy restatement summed in float64 (`oracle_err`)
+  python tools/metric_bits.py --compare A B     rows of A.json and B.json side by side: equal hashes, or the largest relative change and
+                                                which of the two is closer to the oracle; exit status 1 if a row that is not
+                                                `may_move` differs or B is further from the oracle than A
+
+Two builds of libwsu are compared by running the first form twice in fresh processes, once with the environment variable WSU_LIB
+pointing at the other build (the C ABI decides what is compared, the Python package is the same).  profiles/r11 has such a pair."""
+import hashlib
+import json
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+import numpy as np  # noqa: E402
+
+F32 = np.float32
+
+
+def compare(path_a, path_b) -> int:
+    a, b = json.loads(Path(path_a).read_text()), json.loads(Path(path_b).read_text())
+    assert list(a) == list(b), "the two files hold different rows"
+    bad = 0
+    for row in a:
+        ra, rb = a[row], b[row]
+        if ra["sha256"] == rb["sha256"]:
+            print(f"{row:44s} equal")
+            continue
+        note = ""
+        if "values" in ra:
+            va, vb = np.array(ra["values"]), np.array(rb["values"])
+            nz = (va != 0) | (vb != 0)
+            rel = float(np.max(np.abs(va - vb)[nz] / np.maximum(np.abs(va), np.abs(vb))[nz]))
+            note = f"max rel change {rel:.3e}, max abs {float(np.max(np.abs(va - vb))):.3e}; oracle_err {ra['oracle_err']:.3e} -> {rb['oracle_err']:.3e}"
+        ok = ra["may_move"] and rb["oracle_err"] <= ra["oracle_err"]       # (a float32 output is at best half an ulp from the oracle)
+        bad += not ok
+        print(f"{row:44s} DIFFERENT{'' if ok else ' (NOT ALLOWED)'} {note}")
+    return 1 if bad else 0
+
+
+def main(out_path) -> None:
+    import torch
+    from oracle import ws_ref
+    from ws_unet_amd import error_boxes, filters, formula, ops
+    from ws_unet_amd.ws import roc
+    dev = torch.device("cuda")
+    rows = {}
+
+    def put(name, t, may_move=False, oracle=None):
+        v = t.detach().cpu().contiguous().numpy()
+        rows[name] = {"sha256": hashlib.sha256(v.tobytes()).hexdigest(), "shape": list(v.shape), "dtype": str(v.dtype), "may_move": may_move}
+        if may_move:
+            o = np.asarray(oracle, dtype=np.float64)
+            rows[name]["values"] = v.astype(np.float64).reshape(-1).tolist()
+            rows[name]["oracle_err"] = float(np.max(np.abs(v.astype(np.float64) - o) / np.maximum(np.abs(o), 1e-300)))
+
+    n, h, w = 3, 64, 96
+    cov = formula.synthetic_images(n, h, w, seed=111)
+    u8 = np.stack([cov[0], formula.lsbr_embed(cov[1], 0.4, seed=3), formula.lsbr_embed(cov[2], 1.0, seed=4)])
+    rng = np.random.default_rng(112)
+    y01 = ((formula.synthetic_images(n, h, w, seed=113).astype(np.float64) + rng.random((n, h, w))) / 256.).astype(F32)    # a "network output"
+    yb01 = ((rng.random((n, h, w)) - 0.5) / 64.).astype(F32)                                                              # and its bias plane
+    x, xc = torch.from_numpy(u8).to(dev), torch.from_numpy(cov).to(dev)
+    y, yb = torch.from_numpy(y01).to(dev), torch.from_numpy(yb01).to(dev)
+    K = filters.NAMED_FILTERS_2D
+    xf = u8.astype(F32)
+    inner = (slice(None), slice(1, -1), slice(1, -1))
+    res_y = xf[inner] - y01[inner] * F32(255.)                   # K10's float32 residual, two roundings
+
+    # K10 and the WS meter
+    beta, l1 = ops.ws_residual_stats(x, y)
+    put("K10 ws_residual_stats beta", beta)
+    put("K10 ws_residual_stats l1", l1)
+    x01 = (xf / F32(255.)).astype(F32)
+    xi = x01 * F32(255.)
+    xbar = np.round(xi).astype(np.int64) ^ 1
+    meter = ((xi.astype(np.float64) - xbar)[inner] * (xi[inner] - y01[inner] * F32(255.)).astype(np.float64) / ((h - 2) * (w - 2))).sum((1, 2))
+    put("ws_meter_beta", ops.ws_meter_beta(torch.from_numpy(x01).to(dev), y), True, meter)
+
+    # K11: the three sums against the float32 terms of oracle/ws_ref.py summed in float64
+    def k11_sums(hat, bias, mean_k):
+        out = []
+        for i in range(n):
+            k = mean_k[..., ::-1][..., 0]
+            mu, mu2 = ws_ref.conv3x3_valid(xf[i], k), ws_ref.conv3x3_valid(xf[i] ** 2, k)
+            wgt = 1 / (5 + (mu2 - mu ** 2))
+            ws = wgt * (xf[i] - (u8[i] ^ 1).astype(F32))[1:-1, 1:-1]
+            out.append([np.sum(t, dtype=np.float64) for t in (wgt, ws * (xf[i][1:-1, 1:-1] - hat[i]), ws * bias[i])])
+        return np.array(out)
+
+    def k11_beta(sums):                                          # the finish kernel's arithmetic, correct_bias=True
+        beta = np.maximum(sums[:, 1] / sums[:, 0], 0.0)
+        return beta - beta * (sums[:, 2] / sums[:, 0])
+
+    for pix in ("KB", "AVG", "AVG9"):
+        for mean in ("AVG", "AVG9"):
+            hat = [ws_ref.filter_infere_single(xf[i][..., None], K[pix])[..., 0] for i in range(n)]
+            bias = [ws_ref.filter_infere_single(((u8[i] ^ 1).astype(F32) - xf[i])[..., None], K[pix])[..., 0] for i in range(n)]
+            b, s = ops.ws_attack(x, None, pixel_filter=K[pix], mean_filter=K[mean], weighted=1, correct_bias=True, return_sums=True)
+            moves, ref = "AVG9" in (pix, mean), k11_sums(hat, bias, K[mean])
+            put(f"K11 ws_attack pixel={pix} mean={mean} beta", b, moves, k11_beta(ref))
+            put(f"K11 ws_attack pixel={pix} mean={mean} sums", s, moves, ref)
+    b, s = ops.ws_attack(x, y, x_bias=yb, mean_filter=K["AVG"], hat_scale=255., weighted=1, correct_bias=True, return_sums=True)
+    ref = k11_sums((y01 * F32(255.))[inner], (yb01 * F32(255.))[inner], K["AVG"])
+    put("K11 ws_attack x_hat mean=AVG beta", b, True, k11_beta(ref))
+    put("K11 ws_attack x_hat mean=AVG sums", s, True, ref)
+    small = np.ascontiguousarray(xf[:1, :40, :48])               # small enough to keep the values of the row that may move
+    for name in ("KB", "AVG", "AVG9", "1"):
+        ref = ws_ref.filter_infere_single(small[0][..., None], K[name])[None, ..., 0]
+        put(f"filter3x3_valid {name}", ops.filter3x3_valid(torch.from_numpy(small).to(dev), K[name]), name == "AVG9", ref)
+    put("lsb_delta_unit", ops.lsb_delta_unit(x))
+
+    # K12-K14
+    cost = ops.hill_cost(x)
+    put("K12 hill_cost", cost)
+    put("K13 hill_threshold", ops.hill_threshold(cost, 0.1))
+    for name in ("KB", "AVG", "AVG9"):
+        for label, t in zip(("mae", "wmae", "q", "selected"), ops.prediction_error(x, pixel_filter=K[name], cost=cost, return_threshold=True)):
+            put(f"K14 prediction_error filter={name} {label}", t)
+    mae, wmae, _, sel = ops.prediction_error(x, y, cost=cost, return_threshold=True)
+    put("K14 prediction_error x_hat mae", mae, True, np.abs(res_y).astype(np.float64).mean((1, 2)))
+    put("K14 prediction_error x_hat selected", sel)
+
+    # K15
+    for name in ("KB", "AVG", "AVG9"):
+        cor, mom = ops.pair_correlation(xc, x, pixel_filter=K[name], moments=True)
+        put(f"K15 pair_correlation filter={name} cor", cor)
+        put(f"K15 pair_correlation filter={name} moments", mom)
+    cor, mom = ops.pair_correlation(xc, x, y, hat_full=True, hat_scale=255., moments=True)
+    put("K15 pair_correlation x_hat cor", cor)
+    put("K15 pair_correlation x_hat moments", mom)
+
+    # K16-K18
+    per = (h - 2) * (w - 2)
+    keys = torch.zeros((3, n * per), dtype=torch.float32, device=dev)
+    flags = torch.zeros(3, dtype=torch.int32, device=dev)
+    for p, kw in enumerate(({"pixel_filter": error_boxes.filter_taps(K["KB"])}, {"pixel_filter": filters.NAMED_FILTERS["AVG"]},
+                            {"x_hat": y, "hat_scale": 255.})):
+        ops.ae_values(x, keys[p], 0, flags[p:p + 1], **kw)
+    put("K16 ae_values KB / AVG / x_hat keys", keys)
+    put("K16 ae_values flags", flags)
+    put("K17 ae_slices", ops.ae_slices(keys[0], [float(e) for e in error_boxes.EDGE_VALUES]))
+    table = error_boxes.box_table({"KB": keys[0], "AVG": keys[1], "UNet": keys[2]}, "KB")
+    put("K17 + K18 box_table", torch.from_numpy(np.ascontiguousarray(table[list(error_boxes.STATS)].to_numpy(dtype=np.float64))))
+
+    # K19
+    scores = torch.from_numpy(np.concatenate([rng.random(5000), rng.random(3000) * 0.1, [np.nan, 0.0, 1.0]])).to(dev)
+    labels = torch.from_numpy(rng.integers(-1, 2, scores.numel()).astype(np.int8)).to(dev)
+    put("K19 roc_counts", ops.roc_counts(scores, labels, [0, 5000, 8000, scores.numel()], roc.TAUS))
+
+    torch.cuda.synchronize()
+    Path(out_path).write_text("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in rows.items()) + "\n}\n")
+    print(f"{len(rows)} rows -> {out_path}")
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) != 2:
+        sys.exit(__doc__)
+    main(sys.argv[1])

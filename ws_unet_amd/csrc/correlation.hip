@@ -11,16 +11,16 @@
 // tree, 64 row blocks per image, then a sequential sum over the blocks), with no float atomics, so a pair's result does not
 // depend on the batch it is in.  Division by zero follows IEEE: x_s == x_c gives 0/0 = NaN, a constant prediction +-inf.
 // Memory-bound: 2 B (+ 4 B with x_hat) per pixel and pass; the second pass re-reads what the first one just brought to L2.
-#include "wsu_device.h"
-// numpy's float64 operation sequence: separately rounded products and sums (no fused multiply-adds)
+// numpy's float64 operation sequence: separately rounded products and sums, plain operators (wsu_metric.h)
 #pragma clang fp contract(off)
+#include "wsu_metric.h"
 
 namespace {
 
 constexpr int PC_PARTS = 64;            // row blocks (workgroups) per image
 constexpr int PC_THREADS = 256;
 
-struct CTaps { double k[9]; };          // K[a][b] of the reference's (3,3,1) kernel array (K11's layout), a = row tap, b = column tap
+using CTaps = Taps3x3<double>;
 
 // pass-1 partials per (image, block): {sum d, sum x_c} as int64, {sum xhat} as fp64; pass-2 partials: {S_hd, S_hh, S_dd} fp64
 struct PcWs {
@@ -38,19 +38,11 @@ __device__ __forceinline__ PcWs pc_ws(void* ws, int n) {
 }
 
 // the prediction at interior pixel (r, c), r in 1..h-2, c in 1..w-2, widened to fp64
-__device__ __forceinline__ double pc_hat(const uint8_t* __restrict__ s, const float* __restrict__ xhat, size_t hat_base, int use_filter,
+__device__ __forceinline__ double pc_hat(const uint8_t* __restrict__ s, const float* __restrict__ xhat, size_t hbase, int use_filter,
                                          const CTaps& t, int hat_full, float hat_scale, int r, int c, int w) {
-    if (use_filter) {
-        // scipy.signal.convolve(x, K, 'valid'): a true convolution, sum_ab K[a][b] * x[r+1-a][c+1-b], taps in the order K00 .. K22
-        double acc = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) acc += t.k[a * 3 + b] * (double)s[(size_t)(r + 1 - a) * w + (c + 1 - b)];
-        return acc;
-    }
-    const size_t o = hat_full ? hat_base + (size_t)r * w + c : hat_base + (size_t)(r - 1) * (w - 2) + (c - 1);
-    return (double)__fmul_rn(xhat[o], hat_scale);         // K10's float32 xhat = y * 255, then widened
+    // scipy.signal.convolve(x, K, 'valid'): a true convolution, sum_ab K[a][b] * x[r+1-a][c+1-b], taps in the order K00 .. K22
+    if (use_filter) return filter_hat64<true>(t, s, r, c, w);
+    return (double)(xhat[hat_index(hat_full, hbase, r, c, w)] * hat_scale);         // K10's float32 xhat = y * 255, then widened
 }
 
 // The three means of image nn from its pass-1 partials.  Called by a whole workgroup of >= PC_PARTS threads: the partials are loaded
@@ -83,7 +75,7 @@ __global__ __launch_bounds__(PC_THREADS) void pair_corr_mean_kernel(
     const int nn = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
     const uint8_t* c_img = xc + (size_t)nn * h * w;
     const uint8_t* s_img = xs + (size_t)nn * h * w;
-    const size_t hat_base = hat_full ? (size_t)nn * h * w : (size_t)nn * (h - 2) * (w - 2);
+    const size_t hbase = hat_base(hat_full, nn, h, w);
     long long sd = 0, sc = 0;
     double sh = 0.0;
     for (int r = 1 + part; r <= h - 2; r += PC_PARTS) {
@@ -91,15 +83,11 @@ __global__ __launch_bounds__(PC_THREADS) void pair_corr_mean_kernel(
             const int vc = c_img[(size_t)r * w + c], vs = s_img[(size_t)r * w + c];
             sd += vs - vc;
             sc += vc;
-            sh += pc_hat(s_img, xhat, hat_base, use_filter, taps, hat_full, hat_scale, r, c, w);
+            sh += pc_hat(s_img, xhat, hbase, use_filter, taps, hat_full, hat_scale, r, c, w);
         }
     }
     ired[0][tid] = sd; ired[1][tid] = sc; hred[tid] = sh;
-    __syncthreads();
-    for (int st = PC_THREADS / 2; st > 0; st >>= 1) {
-        if (tid < st) { ired[0][tid] += ired[0][tid + st]; ired[1][tid] += ired[1][tid + st]; hred[tid] += hred[tid + st]; }
-        __syncthreads();
-    }
+    block_sum<PC_THREADS>(tid, ired[0], ired[1], hred);
     if (tid == 0) {
         const PcWs p = pc_ws(workspace, n);
         p.isum[((size_t)nn * PC_PARTS + part) * 2 + 0] = ired[0][0];
@@ -120,12 +108,12 @@ __global__ __launch_bounds__(PC_THREADS) void pair_corr_centred_kernel(
     const double m_d = means[0], m_h = means[2], m_dh = means[2] - means[1];      // mean d, mean xhat, mean dhat
     const uint8_t* c_img = xc + (size_t)nn * h * w;
     const uint8_t* s_img = xs + (size_t)nn * h * w;
-    const size_t hat_base = hat_full ? (size_t)nn * h * w : (size_t)nn * (h - 2) * (w - 2);
+    const size_t hbase = hat_base(hat_full, nn, h, w);
     double s_hd = 0.0, s_hh = 0.0, s_dd = 0.0;
     for (int r = 1 + part; r <= h - 2; r += PC_PARTS) {
         for (int c = 1 + tid; c <= w - 2; c += PC_THREADS) {
             const int vc = c_img[(size_t)r * w + c], vs = s_img[(size_t)r * w + c];
-            const double hat = pc_hat(s_img, xhat, hat_base, use_filter, taps, hat_full, hat_scale, r, c, w);
+            const double hat = pc_hat(s_img, xhat, hbase, use_filter, taps, hat_full, hat_scale, r, c, w);
             const double dd = (double)(vs - vc) - m_d;
             const double hh = hat - m_h;
             const double dh = (hat - (double)vc) - m_dh;
@@ -135,11 +123,7 @@ __global__ __launch_bounds__(PC_THREADS) void pair_corr_centred_kernel(
         }
     }
     red[0][tid] = s_hd; red[1][tid] = s_hh; red[2][tid] = s_dd;
-    __syncthreads();
-    for (int st = PC_THREADS / 2; st > 0; st >>= 1) {
-        if (tid < st) { red[0][tid] += red[0][tid + st]; red[1][tid] += red[1][tid + st]; red[2][tid] += red[2][tid + st]; }
-        __syncthreads();
-    }
+    block_sum<PC_THREADS>(tid, red[0], red[1], red[2]);
     if (tid < 3) p.csum[((size_t)nn * PC_PARTS + part) * 3 + tid] = red[tid][0];
 }
 
@@ -182,8 +166,7 @@ int wsu_pair_correlation(const uint8_t* xc_u8, const uint8_t* xs_u8, const float
     WSU_REQUIRE((long long)h * w <= (1LL << 40), "pair_correlation: %d x %d pixels exceed the exact integer sums", h, w);
     WSU_REQUIRE(workspace_bytes >= wsu_pair_correlation_workspace_bytes(n), "pair_correlation: workspace too small (%zu < %zu bytes)",
                 workspace_bytes, wsu_pair_correlation_workspace_bytes(n));
-    CTaps t{};
-    for (int i = 0; i < 9; ++i) t.k[i] = pixel_filter ? pixel_filter[i] : 0.0;
+    const CTaps t = taps_from_kernel(pixel_filter);
     const int use_filter = pixel_filter ? 1 : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(pair_corr_mean_kernel, dim3(PC_PARTS, n), dim3(PC_THREADS), 0, s, xc_u8, xs_u8, x_hat, use_filter, t, hat_full,

@@ -12,14 +12,14 @@
 // keys to c_j, the key at rank c_j - 1 (the lexicographic maximum of (a, index) over a <= e_j) and the key at rank N - 1 (the global
 // maximum), from which the host forms every slice as a pair of boundary keys: a pixel belongs to a slice iff its (a, index) lies
 // between them, which also covers the reference's overlapping slices.  K18 is an exact multi-rank radix select over the float32 bit
-// patterns (non-negative, so monotone as uint32), K13's 11/11/10-bit digits for every predictor x slice x rank at once: one pass over the
+// patterns (non-negative, so monotone as uint32), wsu_metric.h's 11/11/10-bit digits for every predictor x slice x rank at once: one pass over the
 // keys per digit level (the rank's own prefix decides which keys count), then one pass for count(c <= a) and min(c > a), which gives
 // c_(k+1) next to a = c_(k).  min and max are reductions of the first pass.  Counts are 32-bit inside a workgroup and 64-bit across
 // workgroups, every cross-workgroup combination is an integer atomic (add / max), and results pass between kernels only at kernel
 // boundaries: deterministic, and independent of how the keys were batched.
-#include "wsu_device.h"
-// numpy's float64 operation sequence for the filter residual (no fused multiply-adds), like hill.hip
+// numpy's float64 operation sequence for the filter residual: plain operators, no fused multiply-adds (wsu_metric.h)
 #pragma clang fp contract(off)
+#include "wsu_metric.h"
 
 namespace {
 
@@ -32,7 +32,7 @@ constexpr int AE_BINS = 2048;
 constexpr int AE_MAX_PRED = 16;
 constexpr int AE_STATE = 4;                     // u64 per (predictor, slice, rank): prefix bits, remaining rank, count(<= a), ~min(> a)
 
-struct DTaps { double k[9]; };                  // weights of x[r-1+a][c-1+b], a,b = 0..2 (K14's layout)
+using DTaps = Taps3x3<double>;
 
 // ---- K16 ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(AE_THREADS) void ae_values_kernel(const uint8_t* __restrict__ x, const float* __restrict__ xhat, float hat_scale,
@@ -56,17 +56,10 @@ __global__ __launch_bounds__(AE_THREADS) void ae_values_kernel(const uint8_t* __
     float ae;
     if (use_filter) {
         // get_filter_residuals: y - x @ filter in float64 (filters/evaluate.py:53-76); exact for the dyadic taps the host admits
-        double hat = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) hat += taps.k[a * 3 + b] * (double)img[(size_t)(r - 1 + a) * w + (c - 1 + b)];
-        ae = (float)fabs((double)img[(size_t)r * w + c] - hat);
+        ae = (float)fabs((double)img[(size_t)r * w + c] - filter_hat64<false>(taps, img, r, c, w));
     } else {
-        // K10's float32 residual x - float32(y*255): plain operators under this file's contract(off), so the product is rounded
-        // before the subtraction (the __fmul_rn / __fsub_rn header functions carry the default contraction and fuse to an FMA)
-        const float yh = xhat[(size_t)nn * h * w + (size_t)r * w + c] * hat_scale;
-        ae = fabsf((float)img[(size_t)r * w + c] - yh);
+        // K10's float32 residual x - float32(y*255), the product rounded before the subtraction; x_hat is full-frame here
+        ae = fabsf(residual_f32((float)img[(size_t)r * w + c], xhat[hat_index(1, hat_base(1, nn, h, w), r, c, w)], hat_scale));
     }
     if (!(ae <= 3.402823466e38f)) atomicOr(flag, 1u); // NaN or +inf
     keys[(size_t)nn * per + j] = ae;
@@ -180,11 +173,6 @@ __device__ __forceinline__ AeWs ae_ws(void* ws, int np) {
     return p;
 }
 
-struct Digit { int shift, bins; uint32_t mask; };
-__device__ __forceinline__ Digit ae_digit(int level) {
-    return level == 0 ? Digit{21, 2048, 0u} : level == 1 ? Digit{10, 2048, 0xFFE00000u} : Digit{0, 1024, 0xFFFFFC00u};
-}
-
 __device__ __forceinline__ unsigned long long* ae_hist_row(const AeWs& p, int np, int level, int pred, int j, int t) {
     return p.hist + ((((size_t)level * np + pred) * AE_MAX_SLICES + j) * AE_RANKS + t) * AE_BINS;
 }
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(AE_HIST_THREADS) void ae_select_hist_kernel(const f
     __shared__ uint32_t lmin[AE_MAX_SLICES], lmax[AE_MAX_SLICES], lbad;
     const int tid = threadIdx.x, pred = blockIdx.y;
     const AeWs p = ae_ws(workspace, np);
-    const Digit dg = ae_digit(level);
+    const RadixDigit dg = radix_digit(level);
     const int nr = level == 0 ? 1 : AE_RANKS;                // histograms per slice
     const int nb = sl.ns * nr * dg.bins;
     uint32_t prefix[AE_MAX_SLICES][AE_RANKS];
@@ -269,29 +257,9 @@ __global__ __launch_bounds__(AE_THREADS) void ae_select_pick_kernel(int np, Slic
     const int t = blockIdx.x % AE_RANKS, j = (blockIdx.x / AE_RANKS) % AE_MAX_SLICES, pred = blockIdx.x / (AE_RANKS * AE_MAX_SLICES);
     if (j >= sl.ns || sl.size[j] == 0) return;
     const AeWs p = ae_ws(workspace, np);
-    const Digit dg = ae_digit(level);
-    const unsigned long long* hist = ae_hist_row(p, np, level, pred, j, level == 0 ? 0 : t);
     unsigned long long* st = ae_state(p, pred, j, t);
-    const unsigned long long kk = level == 0 ? (unsigned long long)sl.rank[j][t] : st[1];
-    const int per = dg.bins / AE_THREADS;
-    unsigned long long mine = 0;
-    for (int q = 0; q < per; ++q) mine += hist[tid * per + q];
-    part[tid] = mine;
-    __syncthreads();
-    unsigned long long before = 0;
-    for (int q = 0; q < tid; ++q) before += part[q];
-    if (kk >= before && kk < before + mine) {
-        for (int q = 0; q < per; ++q) {
-            const unsigned long long cnt = hist[tid * per + q];
-            if (kk < before + cnt) {
-                const uint32_t prefix = level == 0 ? 0u : (uint32_t)st[0];
-                st[0] = prefix | ((uint32_t)(tid * per + q) << dg.shift);
-                st[1] = kk - before;
-                break;
-            }
-            before += cnt;
-        }
-    }
+    radix_pick<unsigned long long>(ae_hist_row(p, np, level, pred, j, level == 0 ? 0 : t), st,
+                                   level == 0 ? (unsigned long long)sl.rank[j][t] : st[1], level, part, tid);
 }
 
 // count(c <= a) and max(~c) over c > a within each slice, for every rank's a = c_(k): grid (parts, P)
@@ -356,12 +324,8 @@ __global__ __launch_bounds__(64) void ae_select_finish_kernel(int np, Slices sl,
     o[1] = (uint32_t)p.minmax[((size_t)pred * AE_MAX_SLICES + j) * 2 + 1];
     for (int t = 0; t < AE_RANKS; ++t) {
         const unsigned long long* st = ae_state(p, pred, j, t);
-        const uint32_t a = (uint32_t)st[0];
-        const long long k = sl.rank[j][t];
-        uint32_t b = a;
-        if (k + 1 < sl.size[j] && (long long)st[2] < k + 2) b = ~(uint32_t)st[3];
-        o[2 + 2 * t] = a;
-        o[3 + 2 * t] = b;
+        o[2 + 2 * t] = (uint32_t)st[0];
+        o[3 + 2 * t] = radix_next_bits((uint32_t)st[0], sl.rank[j][t], sl.size[j], (long long)st[2], (uint32_t)st[3]);
     }
 }
 
@@ -386,8 +350,7 @@ int wsu_ae_values(const uint8_t* x_u8, const float* x_hat, const double* pixel_f
                 "ae_values: %d x %lld keys at offset %zu exceed the key array of %zu", n, per, key_offset, key_capacity);
     const long long blocks = (per + AE_THREADS - 1) / AE_THREADS;
     WSU_REQUIRE(blocks <= 0x7FFFFFFFLL, "ae_values: %lld keys per image", per);
-    DTaps t{};
-    for (int i = 0; i < 9; ++i) t.k[i] = pixel_filter ? pixel_filter[i] : 0.0;
+    const DTaps t = taps_from_weights(pixel_filter);
     hipLaunchKernelGGL(ae_values_kernel, dim3((unsigned)blocks, n), dim3(AE_THREADS), 0, static_cast<hipStream_t>(stream), x_u8, x_hat,
                        hat_scale, pixel_filter ? 1 : 0, t, idx, num_idx, keys + key_offset, flag, h, w);
     return wsu_check_launch("ae_values_kernel");

@@ -14,9 +14,9 @@
 // three histogram passes of 11/11/10 bits give a = c_(k); one more pass gives count(c <= a) and min(c > a), hence b = c_(k+1).
 // All cross-workgroup traffic is integer atomics, and results pass between kernels only at kernel boundaries: deterministic.
 // K14 sums |x - x_hat| in fp64 in a fixed order (per-thread strided, LDS tree, 64 partial blocks per image, second tree).
-#include "wsu_device.h"
-// numpy's float32 / float64 operation sequences (no fused multiply-adds), like ws_attack.hip
+// numpy's float32 / float64 operation sequences: plain operators, no fused multiply-adds (wsu_metric.h)
 #pragma clang fp contract(off)
+#include "wsu_metric.h"
 
 namespace {
 
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void hill_cost_kernel(const uint8_t* __restric
         for (int u = 0; u < 3; ++u)
 #pragma unroll
             for (int v = 0; v < 3; ++v) s += ar[(a + u) * HR + b + v];
-        rho[i] = s > 0 ? __fdiv_rn(9.0f, (float)s) : __builtin_inff();
+        rho[i] = s > 0 ? 9.0f / (float)s : __builtin_inff();
     }
     __syncthreads();
     // ---- horizontal 15-tap direct sums (rows of rho, HT output columns)
@@ -121,16 +121,11 @@ __global__ __launch_bounds__(256) void hill_cost_kernel(const uint8_t* __restric
 
 // ---- K13 ------------------------------------------------------------------------------------------------------------------
 // Workspace (uint32): hist[3][n][RS_BINS], then state[n][4] = {prefix bits, remaining rank, count(c <= a), ~min(c > a) bits}.
-struct RsPass { int shift, bins; uint32_t mask; };
-__device__ __forceinline__ RsPass rs_pass(int p) {
-    return p == 0 ? RsPass{21, 2048, 0u} : p == 1 ? RsPass{10, 2048, 0xFFE00000u} : RsPass{0, 1024, 0xFFFFFC00u};
-}
-
 __global__ __launch_bounds__(256) void hill_select_hist_kernel(const float* __restrict__ cost, uint32_t* __restrict__ ws, int pass,
                                                                int n, int h, int w) {
     __shared__ uint32_t lh[RS_BINS];
     const int nn = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
-    const RsPass ps = rs_pass(pass);
+    const RadixDigit ps = radix_digit(pass);
     uint32_t* hist = ws + ((size_t)pass * n + nn) * RS_BINS;
     const uint32_t prefix = pass == 0 ? 0u : ws[(size_t)3 * n * RS_BINS + nn * 4 + 0];
     for (int b = tid; b < RS_BINS; b += 256) lh[b] = 0u;
@@ -150,29 +145,8 @@ __global__ __launch_bounds__(256) void hill_select_hist_kernel(const float* __re
 __global__ __launch_bounds__(256) void hill_select_pick_kernel(uint32_t* __restrict__ ws, int pass, long long k, int n) {
     __shared__ uint32_t part[256];
     const int nn = blockIdx.x, tid = threadIdx.x;
-    const RsPass ps = rs_pass(pass);
-    const uint32_t* hist = ws + ((size_t)pass * n + nn) * RS_BINS;
     uint32_t* st = ws + (size_t)3 * n * RS_BINS + nn * 4;
-    const uint32_t kk = pass == 0 ? (uint32_t)k : st[1];
-    const int per = ps.bins / 256;
-    uint32_t mine = 0;
-    for (int j = 0; j < per; ++j) mine += hist[tid * per + j];
-    part[tid] = mine;
-    __syncthreads();
-    uint32_t before = 0;                                     // exclusive prefix of this thread's bin range (256 adds: negligible)
-    for (int t = 0; t < tid; ++t) before += part[t];
-    if (kk >= before && kk < before + mine) {
-        for (int j = 0; j < per; ++j) {
-            const uint32_t cnt = hist[tid * per + j];
-            if (kk < before + cnt) {
-                const uint32_t prefix = pass == 0 ? 0u : st[0];
-                st[0] = prefix | ((uint32_t)(tid * per + j) << ps.shift);
-                st[1] = kk - before;
-                break;
-            }
-            before += cnt;
-        }
-    }
+    radix_pick<uint32_t>(ws + ((size_t)pass * n + nn) * RS_BINS, st, pass == 0 ? (uint32_t)k : st[1], pass, part, tid);
 }
 
 // count(c <= a) and min(c > a) for a = c_(k) (stored as the maximum of the complemented bit pattern, so zero is the identity)
@@ -208,14 +182,13 @@ __global__ __launch_bounds__(64) void hill_select_finish_kernel(const uint32_t* 
     if (nn >= n) return;
     const uint32_t* st = ws + (size_t)3 * n * RS_BINS + nn * 4;
     const double a = (double)__uint_as_float(st[0]);
-    double b = a;
-    if (k + 1 < count && (long long)st[2] < k + 2) b = (double)__uint_as_float(~st[3]);
+    const double b = (double)__uint_as_float(radix_next_bits(st[0], k, count, (long long)st[2], st[3]));
     const double d = b - a;
     q[nn] = g >= 0.5 ? b - d * (1.0 - g) : a + d * g;
 }
 
 // ---- K14 ------------------------------------------------------------------------------------------------------------------
-struct DTaps { double k[9]; };                          // weights of x[r-1+a][c-1+b], a,b = 0..2 (correlation layout)
+using DTaps = Taps3x3<double>;
 
 __global__ __launch_bounds__(256) void pred_err_partial_kernel(
     const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, int hat_full, float hat_scale, int use_filter, DTaps taps,
@@ -224,8 +197,7 @@ __global__ __launch_bounds__(256) void pred_err_partial_kernel(
     const int nn = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
     const uint8_t* img = xu8 + (size_t)nn * h * w;
     const float* cimg = cost + (size_t)nn * h * w;
-    const int ih = h - 2, iw = w - 2;
-    const size_t hat_base = hat_full ? (size_t)nn * h * w : (size_t)nn * ih * iw;
+    const size_t hbase = hat_base(hat_full, nn, h, w);
     const double qq = q[nn];
     double sa = 0.0, ss = 0.0, sn = 0.0;
     for (int r = 1 + part; r <= h - 2; r += PE_PARTS) {
@@ -233,29 +205,17 @@ __global__ __launch_bounds__(256) void pred_err_partial_kernel(
             double ad;
             if (use_filter) {
                 // get_filter_residuals: y - x @ filter, float64 (filters/evaluate.py:53-76), taps in the fixed order x00 .. x22
-                double hat = 0.0;
-#pragma unroll
-                for (int a = 0; a < 3; ++a)
-#pragma unroll
-                    for (int b = 0; b < 3; ++b) hat += taps.k[a * 3 + b] * (double)img[(size_t)(r - 1 + a) * w + (c - 1 + b)];
-                ad = fabs((double)img[(size_t)r * w + c] - hat);
+                ad = fabs((double)img[(size_t)r * w + c] - filter_hat64<false>(taps, img, r, c, w));
             } else {
-                const size_t o = hat_full ? hat_base + (size_t)r * w + c : hat_base + (size_t)(r - 1) * iw + (c - 1);
-                const float d = __fsub_rn((float)img[(size_t)r * w + c], __fmul_rn(xhat[o], hat_scale));   // K10's float32 residual
-                ad = (double)fabsf(d);
+                // K10's float32 residual: the same two roundings per pixel, so K14 and K10 sum the same float32 terms
+                ad = (double)fabsf(residual_f32((float)img[(size_t)r * w + c], xhat[hat_index(hat_full, hbase, r, c, w)], hat_scale));
             }
             sa += ad;
             if ((double)cimg[(size_t)r * w + c] <= qq) { ss += ad; sn += 1.0; }
         }
     }
     red[0][tid] = sa; red[1][tid] = ss; red[2][tid] = sn;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-            red[0][tid] += red[0][tid + st]; red[1][tid] += red[1][tid + st]; red[2][tid] += red[2][tid + st];
-        }
-        __syncthreads();
-    }
+    block_sum<256>(tid, red[0], red[1], red[2]);
     if (tid < 3) partial[((size_t)nn * PE_PARTS + part) * 3 + tid] = red[tid][0];
 }
 
@@ -264,11 +224,7 @@ __global__ __launch_bounds__(64) void pred_err_finish_kernel(const double* __res
     __shared__ double red[3][PE_PARTS];
     const int nn = blockIdx.x, tid = threadIdx.x;
     for (int k = 0; k < 3; ++k) red[k][tid] = partial[((size_t)nn * PE_PARTS + tid) * 3 + k];
-    __syncthreads();
-    for (int st = PE_PARTS / 2; st > 0; st >>= 1) {
-        if (tid < st) for (int k = 0; k < 3; ++k) red[k][tid] += red[k][tid + st];
-        __syncthreads();
-    }
+    block_sum<PE_PARTS>(tid, red[0], red[1], red[2]);
     if (tid == 0) {
         mae[nn] = red[0][0] / count;
         wmae[nn] = red[1][0] / red[2][0];
@@ -329,8 +285,7 @@ int wsu_prediction_error(const uint8_t* x_u8, const float* x_hat, const double* 
     WSU_REQUIRE((x_hat != nullptr) != (pixel_filter != nullptr), "prediction_error: give exactly one of x_hat / pixel_filter");
     WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, "prediction_error: bad shape n=%d h=%d w=%d", n, h, w);
     WSU_REQUIRE(workspace_bytes >= wsu_prediction_error_workspace_bytes(n), "prediction_error: workspace too small");
-    DTaps t{};
-    for (int i = 0; i < 9; ++i) t.k[i] = pixel_filter ? pixel_filter[i] : 0.0;
+    const DTaps t = taps_from_weights(pixel_filter);
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* partial = static_cast<double*>(workspace);
     hipLaunchKernelGGL(pred_err_partial_kernel, dim3(PE_PARTS, n), dim3(256), 0, s, x_u8, x_hat, hat_full ? 1 : 0, hat_scale,

@@ -1,10 +1,11 @@
 // Bandwidth-bound kernels of the forward path: first layer (few input planes), 1x1 head + sigmoid,
 // stand-alone max-pool, UniformDropout, u8 -> unit float, WS residual statistics.
 #include "wsu_device.h"
-// No fused multiply-adds in this file: the residual statistics follow numpy's float32 operation sequence (src/unet/evaluate.py:125-132).
-// (Until round 3 the SLP vectorizer happened to pack these products into v_pk_mul_f32 / v_pk_add_f32, which cannot fuse; built without it
-// (Makefile) hipcc's default -ffp-contract=fast would fuse them.)
+// No contraction in this file: the residual statistics follow numpy's float32 operation sequence (src/unet/evaluate.py:125-132) with plain
+// operators (hipcc's default -ffp-contract=fast would fuse them; wsu_metric.h has the policy).  The conv kernels below fuse on purpose,
+// with explicit fmaf.
 #pragma clang fp contract(off)
+#include "wsu_metric.h"
 
 namespace {
 
@@ -211,8 +212,7 @@ __global__ __launch_bounds__(256) void u8_to_unit_kernel(const uint8_t* __restri
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void ws_stats_kernel(const uint8_t* __restrict__ xu8, const float* __restrict__ y01,
                                                         float* __restrict__ beta_hat, float* __restrict__ l1, int h, int w) {
-    __shared__ double sb[1024];
-    __shared__ double sl[1024];
+    __shared__ double red[2][1024];                          // {beta terms, |d|}
     const int nn = blockIdx.x, tid = threadIdx.x;
     const int ih = h - 2, iw = w - 2;
     const long long cnt = (long long)ih * iw;
@@ -223,20 +223,15 @@ __global__ __launch_bounds__(1024) void ws_stats_kernel(const uint8_t* __restric
         const uint8_t u = xu8[o];
         const float xf = (float)u;
         const float xbar = (float)(uint8_t)(u ^ 1);
-        const float xhat = y01[o] * 255.0f;                  // evaluate.py:51
-        const float d = xf - xhat;                           // float32 like numpy
+        const float d = residual_f32(xf, y01[o], 255.0f);    // x - y*255 (evaluate.py:51), float32 like numpy
         ab += (double)((xf - xbar) * d);
         al += (double)fabsf(d);
     }
-    sb[tid] = ab; sl[tid] = al;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (tid < s) { sb[tid] += sb[tid + s]; sl[tid] += sl[tid + s]; }
-        __syncthreads();
-    }
+    red[0][tid] = ab; red[1][tid] = al;
+    block_sum<1024>(tid, red[0], red[1]);
     if (tid == 0) {
-        beta_hat[nn] = (float)(sb[0] / (double)cnt);
-        l1[nn] = (float)(sl[0] / (double)cnt);
+        beta_hat[nn] = (float)(red[0][0] / (double)cnt);
+        l1[nn] = (float)(red[1][0] / (double)cnt);
     }
 }
 
@@ -244,7 +239,7 @@ __global__ __launch_bounds__(1024) void ws_stats_kernel(const uint8_t* __restric
 // the float inputs (xi = x*255 in float32, x_bar = int(round(xi)) ^ 1, the product in float64 like numpy's float32 - int64 promotion).
 __global__ __launch_bounds__(1024) void ws_meter_kernel(const float* __restrict__ x01, const float* __restrict__ y01,
                                                         double* __restrict__ beta_hat, int h, int w) {
-    __shared__ double sb[1024];
+    __shared__ double red[1024];
     const int nn = blockIdx.x, tid = threadIdx.x;
     const int ih = h - 2, iw = w - 2;
     const long long cnt = (long long)ih * iw;
@@ -252,17 +247,13 @@ __global__ __launch_bounds__(1024) void ws_meter_kernel(const float* __restrict_
     for (long long i = tid; i < cnt; i += 1024) {
         const int r = (int)(i / iw) + 1, c = (int)(i % iw) + 1;
         const size_t o = ((size_t)nn * h + r) * w + c;
-        const float xi = __fmul_rn(x01[o], 255.0f), xh = __fmul_rn(y01[o], 255.0f);
+        const float xi = x01[o] * 255.0f;
         const long long xbar = (long long)rintf(xi) ^ 1LL;                       // np.round = half-to-even = rintf
-        ab += ((double)xi - (double)xbar) * (double)__fsub_rn(xi, xh) / (double)cnt;
+        ab += ((double)xi - (double)xbar) * (double)residual_f32(xi, y01[o], 255.0f) / (double)cnt;
     }
-    sb[tid] = ab;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (tid < s) sb[tid] += sb[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) beta_hat[nn] = sb[0];
+    red[tid] = ab;
+    block_sum<1024>(tid, red);
+    if (tid == 0) beta_hat[nn] = red[0];
 }
 
 }  // namespace

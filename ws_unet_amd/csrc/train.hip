@@ -10,8 +10,9 @@
 #include "wsu_device.h"
 // No fused multiply-adds in this file: the loss follows the reference's float32 operation sequence (out * 255 rounded, then subtracted: src/_defs/losses.py:55-63) -- a fused multiply-add
 // rounds once and moves the WS term by ~1e-4 relative through its cancellation.
-// (Until round 3 the SLP vectorizer happened to pack these products into v_pk_mul_f32 / v_pk_add_f32, which cannot fuse; built without it
-// (Makefile) hipcc's default -ffp-contract=fast would fuse them.)
+// Plain operators only: hipcc's default -ffp-contract=fast would fuse them, the pragma below stops that, and it does not reach the
+// __f*_rn header intrinsics, which fuse regardless (wsu_metric.h has the policy; this file's ISA has no f32 FMA outside the division and
+// sqrtf expansions, profiles/r11/README.md).
 #pragma clang fp contract(off)
 #include <cmath>
 

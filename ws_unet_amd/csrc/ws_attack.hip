@@ -8,41 +8,37 @@
 //   beta   = clip( sum(weights * (x - x_bar) * (x - x_hat)), 0, None )                                       (:118-121)
 //   if correct_bias:  beta -= beta * sum(weights * (x - x_bar) * pixel_estimator(x_bar - x))                 (:126-128)
 //
-// Everything per pixel is float32 like the numpy original (separately rounded mul / sub, no contraction); the three sums
+// Everything per pixel is float32 like the numpy original (separately rounded mul / sub, no contraction: wsu_metric.h); the three sums
 // are fp64 in a fixed order (per-thread strided, LDS tree, 64 partial blocks per image, second tree), so a result is
 // bitwise reproducible.  With the reference's default mean estimator (AVG, 8 taps of 1/8) mu, mu2 and var are exact in
 // float32 for uint8 pixels, whatever the order of the nine products.
-// HBM-bound: 1 B (pixel, neighbours hit L1/L2) + 4 B (prediction) [+ 4 B bias prediction] per pixel.
-#include "wsu_device.h"
-// No fused multiply-adds in this file: the WS estimator follows numpy's float32 operation sequence (src/ws/estimate.py:90-121).
-// (Until round 3 the SLP vectorizer happened to pack these products into v_pk_mul_f32 / v_pk_add_f32, which cannot fuse; built without it
-// (Makefile) hipcc's default -ffp-contract=fast would fuse them.)
+// HBM-bound: 1 B (pixel, neighbours hit L1/L2) + 4 B (prediction) [+ 4 B bias prediction] per pixel.  With an in-kernel filter the
+// quotients x / 255. come from a 256-entry LDS table (one IEEE division per thread and workgroup; the same bits as dividing per pixel).
+// No fused multiply-adds in this file: the WS estimator follows numpy's float32 operation sequence (src/ws/estimate.py:90-121), written
+// with plain operators under contract(off) (hipcc's default -ffp-contract=fast would fuse them; see wsu_metric.h for the policy).
 #pragma clang fp contract(off)
+#include "wsu_metric.h"
 
 namespace {
 
 constexpr int WSA_PARTS = 64;                           // partial blocks per image
-struct Taps { float k[9]; };                            // K[a][b] of the (3,3,1) numpy kernel, a = row tap, b = column tap
-
-// true convolution, 'valid': out(r,c) = sum_{a,b} K[a][b] * v(r+1-a, c+1-b); v[i][j] holds the 3x3 neighbourhood, i,j = 0..2
-__device__ __forceinline__ float conv9(const Taps& t, const float v[3][3]) {
-    float acc = 0.f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) acc = __fadd_rn(acc, __fmul_rn(t.k[a * 3 + b], v[2 - a][2 - b]));
-    return acc;
-}
+using Taps = Taps3x3<float>;
+// true convolution, 'valid': out(r,c) = sum_{a,b} K[a][b] * v(r+1-a, c+1-b), summed in the order K00 .. K22
+__device__ __forceinline__ float conv9(const Taps& t, const float v[3][3]) { return conv9_f32<true>(t, v); }
 
 __global__ __launch_bounds__(256) void ws_attack_partial_kernel(
     const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, const float* __restrict__ xbias,
     Taps mean_taps, Taps pixel_taps, int use_pixel_filter, int hat_full, float hat_scale, int weighted, int correct_bias,
     double* __restrict__ partial, int h, int w) {
     __shared__ double red[3][256];
+    __shared__ float unit[256];                          // u / 255.f of every uint8 value: one IEEE division per thread, not nine per pixel
     const int nn = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
     const uint8_t* img = xu8 + (size_t)nn * h * w;
-    const int ih = h - 2, iw = w - 2;
-    const size_t hat_base = hat_full ? (size_t)nn * h * w : (size_t)nn * ih * iw;
+    if (use_pixel_filter) {                              // (uniform over the workgroup)
+        unit[tid] = (float)tid / 255.0f;
+        __syncthreads();
+    }
+    const size_t hbase = hat_base(hat_full, nn, h, w);
     double sw = 0.0, sb = 0.0, sc = 0.0;
     for (int r = 1 + part; r <= h - 2; r += WSA_PARTS) {
         for (int c = 1 + tid; c <= w - 2; c += 256) {
@@ -54,49 +50,44 @@ __global__ __launch_bounds__(256) void ws_attack_partial_kernel(
                 for (int j = 0; j < 3; ++j) {
                     u[i][j] = img[(size_t)(r - 1 + i) * w + (c - 1 + j)];
                     v[i][j] = (float)u[i][j];
-                    v2[i][j] = __fmul_rn(v[i][j], v[i][j]);
+                    v2[i][j] = v[i][j] * v[i][j];
                 }
             float wgt = 1.0f;
             if (weighted != 0) {
                 const float mu = conv9(mean_taps, v);
                 const float mu2 = conv9(mean_taps, v2);
-                const float var = __fsub_rn(mu2, __fmul_rn(mu, mu));
-                const float t = __fadd_rn(5.0f, var);
-                wgt = weighted > 0 ? __fdiv_rn(1.0f, t) : t;
+                const float mu_sq = mu * mu;
+                const float var = mu2 - mu_sq;
+                const float t = 5.0f + var;
+                wgt = weighted > 0 ? 1.0f / t : t;
             }
             const float x = v[1][1];
-            const float s = __fsub_rn(x, (float)(uint8_t)(u[1][1] ^ 1));             // x - x_bar = +-1
-            float hat, bias = 0.f;
+            const float s = x - (float)(uint8_t)(u[1][1] ^ 1);                       // x - x_bar = +-1
+            float res, bias = 0.f;                                                    // res = x - x_hat
             if (use_pixel_filter) {
                 float q[3][3], qb[3][3];
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
 #pragma unroll
                     for (int j = 0; j < 3; ++j) {
-                        q[i][j] = __fdiv_rn(v[i][j], 255.0f);                           // filters/evaluate.py:136-141
-                        qb[i][j] = __fdiv_rn(__fsub_rn((float)(uint8_t)(u[i][j] ^ 1), v[i][j]), 255.0f);
+                        q[i][j] = unit[u[i][j]];                                        // x / 255. (filters/evaluate.py:136-141)
+                        qb[i][j] = (u[i][j] & 1) ? -unit[1] : unit[1];                  // (x_bar - x) / 255. = -+1 / 255.
                     }
-                hat = __fmul_rn(conv9(pixel_taps, q), 255.0f);
-                if (correct_bias) bias = __fmul_rn(conv9(pixel_taps, qb), 255.0f);
+                res = residual_f32(x, conv9(pixel_taps, q), 255.0f);
+                if (correct_bias) bias = conv9(pixel_taps, qb) * 255.0f;
             } else {
-                const size_t o = hat_full ? hat_base + (size_t)r * w + c : hat_base + (size_t)(r - 1) * iw + (c - 1);
-                hat = __fmul_rn(xhat[o], hat_scale);
-                if (correct_bias) bias = __fmul_rn(xbias[o], hat_scale);
+                const size_t o = hat_index(hat_full, hbase, r, c, w);
+                res = residual_f32(x, xhat[o], hat_scale);
+                if (correct_bias) bias = xbias[o] * hat_scale;
             }
-            const float ws = __fmul_rn(wgt, s);
+            const float ws = wgt * s;
             sw += (double)wgt;
-            sb += (double)__fmul_rn(ws, __fsub_rn(x, hat));
-            sc += (double)__fmul_rn(ws, bias);
+            sb += (double)(ws * res);
+            sc += (double)(ws * bias);
         }
     }
     red[0][tid] = sw; red[1][tid] = sb; red[2][tid] = sc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-            red[0][tid] += red[0][tid + st]; red[1][tid] += red[1][tid + st]; red[2][tid] += red[2][tid + st];
-        }
-        __syncthreads();
-    }
+    block_sum<256>(tid, red[0], red[1], red[2]);
     if (tid < 3) partial[((size_t)nn * WSA_PARTS + part) * 3 + tid] = red[tid][0];
 }
 
@@ -105,11 +96,7 @@ __global__ __launch_bounds__(64) void ws_attack_finish_kernel(const double* __re
     __shared__ double red[3][WSA_PARTS];
     const int nn = blockIdx.x, tid = threadIdx.x;
     for (int k = 0; k < 3; ++k) red[k][tid] = partial[((size_t)nn * WSA_PARTS + tid) * 3 + k];
-    __syncthreads();
-    for (int st = WSA_PARTS / 2; st > 0; st >>= 1) {
-        if (tid < st) for (int k = 0; k < 3; ++k) red[k][tid] += red[k][tid + st];
-        __syncthreads();
-    }
+    block_sum<WSA_PARTS>(tid, red[0], red[1], red[2]);
     if (tid == 0) {
         const double sw = red[0][0], sb = red[1][0], sc = red[2][0];
         double beta = sb / sw;
@@ -123,7 +110,7 @@ __global__ __launch_bounds__(64) void ws_attack_finish_kernel(const double* __re
 __global__ __launch_bounds__(256) void lsb_delta_unit_kernel(const uint8_t* __restrict__ x, float* __restrict__ y, size_t count) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
         const uint8_t u = x[i];
-        y[i] = __fdiv_rn(__fsub_rn((float)(uint8_t)(u ^ 1), (float)u), 255.0f);        // (x_bar - x) / 255.
+        y[i] = ((float)(uint8_t)(u ^ 1) - (float)u) / 255.0f;                          // (x_bar - x) / 255.
     }
 }
 
@@ -139,8 +126,8 @@ __global__ __launch_bounds__(256) void filter3x3_valid_kernel(const float* __res
 #pragma unroll
         for (int a = 0; a < 3; ++a)
 #pragma unroll
-            for (int b = 0; b < 3; ++b) q[a][b] = __fdiv_rn(p[(size_t)a * w + b], 255.0f);
-        y[i] = __fmul_rn(conv9(taps, q), 255.0f);
+            for (int b = 0; b < 3; ++b) q[a][b] = p[(size_t)a * w + b] / 255.0f;
+        y[i] = conv9(taps, q) * 255.0f;
     }
 }
 
@@ -160,8 +147,7 @@ int wsu_ws_attack(const uint8_t* x_u8, const float* x_hat, const float* x_bias, 
     WSU_REQUIRE(!correct_bias || pixel_filter || x_bias, "ws_attack: correct_bias needs x_bias = pixel_estimator(x_bar - x)");
     WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, "ws_attack: bad shape n=%d h=%d w=%d", n, h, w);
     WSU_REQUIRE(workspace_bytes >= wsu_ws_attack_workspace_bytes(n), "ws_attack: workspace too small");
-    Taps mt{}, pt{};
-    for (int i = 0; i < 9; ++i) { mt.k[i] = mean_filter ? mean_filter[i] : 0.f; pt.k[i] = pixel_filter ? pixel_filter[i] : 0.f; }
+    const Taps mt = taps_from_kernel(mean_filter), pt = taps_from_kernel(pixel_filter);
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* partial = static_cast<double*>(workspace);
     hipLaunchKernelGGL(ws_attack_partial_kernel, dim3(WSA_PARTS, n), dim3(256), 0, s, x_u8, x_hat, x_bias, mt, pt,
@@ -175,8 +161,7 @@ int wsu_ws_attack(const uint8_t* x_u8, const float* x_hat, const float* x_bias, 
 int wsu_filter3x3_valid_f32(const float* x, const float* filter, float* y, int n, int h, int w, void* stream) {
     WSU_REQUIRE(x && filter && y, "filter3x3_valid: null pointer");
     WSU_REQUIRE(n > 0 && h >= 3 && w >= 3, "filter3x3_valid: bad shape n=%d h=%d w=%d", n, h, w);
-    Taps t{};
-    for (int i = 0; i < 9; ++i) t.k[i] = filter[i];
+    const Taps t = taps_from_kernel(filter);
     const long long total = (long long)n * (h - 2) * (w - 2);
     const long long nblk = (total + 255) / 256;
     hipLaunchKernelGGL(filter3x3_valid_kernel, dim3((unsigned)(nblk < 65536 ? nblk : 65536)), dim3(256), 0,

@@ -1,0 +1,111 @@
+// Device helpers shared by the metric kernels K10-K18 (pointwise.hip K10 + WS meter, ws_attack.hip, hill.hip, correlation.hip,
+// error_boxes.hip): the one definition each of a 3x3 predictor's taps, the prediction at a pixel, the float32 residual, the fixed-order
+// block sum and the radix-select steps.
+//
+// Rounding policy: these functions restate numpy's float32 / float64 operation sequences with PLAIN operators, one rounding each.  That
+// holds only under `#pragma clang fp contract(off)`, which is per translation unit: every including .hip file sets it BEFORE this
+// include.  The __f*_rn header intrinsics are no substitute: the pragma does not reach them, they carry hipcc's default contraction and
+// fuse with a neighbouring add (tests/test_isa_lint.py counts the f32 FMAs of every kernel that uses this header).
+#pragma once
+#include "wsu_device.h"
+
+// ---- a 3x3 linear predictor --------------------------------------------------------------------------------------------------------
+// k[a*3+b] is the weight of x[r-1+a][c-1+b] (correlation layout).  The reference's kernel arrays K[a][b] (NAMED_FILTERS_2D, applied as a
+// true convolution to x[r+1-a][c+1-b]) are the same nine numbers reversed.
+template <typename T> struct Taps3x3 { T k[9]; };
+template <typename T> inline Taps3x3<T> taps_from_weights(const T* wgt) {         // host; null -> zeros
+    Taps3x3<T> t{};
+    for (int i = 0; i < 9; ++i) t.k[i] = wgt ? wgt[i] : T(0);
+    return t;
+}
+template <typename T> inline Taps3x3<T> taps_from_kernel(const T* kern) {         // host; K[a][b] of a true convolution; null -> zeros
+    Taps3x3<T> t{};
+    for (int i = 0; i < 9; ++i) t.k[8 - i] = kern ? kern[i] : T(0);
+    return t;
+}
+
+// The sum order is part of a result's bits: REVERSE = false visits x[r-1][c-1] first (x @ filter, K14 / K16), REVERSE = true visits
+// x[r+1][c+1] first, i.e. K00 .. K22 of scipy's convolve (K11 / K15).  v[i][j] = x[r-1+i][c-1+j].
+template <bool REVERSE> __device__ __forceinline__ float conv9_f32(const Taps3x3<float>& t, const float v[3][3]) {
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const int j = REVERSE ? 8 - i : i;
+        acc = acc + t.k[j] * v[j / 3][j % 3];
+    }
+    return acc;
+}
+// float64 taps on the uint8 plane `img` (row stride w) at interior pixel (r, c)
+template <bool REVERSE> __device__ __forceinline__ double filter_hat64(const Taps3x3<double>& t, const uint8_t* __restrict__ img,
+                                                                       int r, int c, int w) {
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const int j = REVERSE ? 8 - i : i;
+        acc += t.k[j] * (double)img[(size_t)(r - 1 + j / 3) * w + (c - 1 + j % 3)];
+    }
+    return acc;
+}
+
+// where the prediction at interior pixel (r, c) of image nn lives: (N,H,W) full frames (hat_full) or (N,H-2,W-2) interiors.  The image's
+// base is a separate function so that a kernel computes it once, outside its pixel loops.
+__device__ __forceinline__ size_t hat_base(int hat_full, int nn, int h, int w) {
+    return hat_full ? (size_t)nn * h * w : (size_t)nn * (h - 2) * (w - 2);
+}
+__device__ __forceinline__ size_t hat_index(int hat_full, size_t base, int r, int c, int w) {
+    return hat_full ? base + (size_t)r * w + c : base + (size_t)(r - 1) * (w - 2) + (c - 1);
+}
+
+// "K10's float32 residual": x - fl32(y * scale), two roundings (src/unet/evaluate.py:51,125-132)
+__device__ __forceinline__ float residual_f32(float x, float y, float scale) {
+    const float xhat = y * scale;
+    return x - xhat;
+}
+
+// ---- fixed-order block sum -----------------------------------------------------------------------------------------------------------
+// Every thread has stored its terms in rows[k][tid] (each row THREADS long, double or long long); afterwards rows[k][0] holds row k's sum,
+// paired (tid, tid + st) with st halving from THREADS/2, so a sum's bits depend on neither the schedule nor the launch.  One barrier per
+// level serves all rows.
+template <int THREADS, typename... T> __device__ __forceinline__ void block_sum(int tid, T*... rows) {
+    __syncthreads();
+    for (int st = THREADS / 2; st > 0; st >>= 1) {
+        if (tid < st) ((rows[tid] += rows[tid + st]), ...);
+        __syncthreads();
+    }
+}
+
+// ---- exact radix select over float32 bit patterns (K13, K18) -----------------------------------------------------------------------
+// Three digit levels of 11 / 11 / 10 bits; `mask` selects the bits the earlier levels fixed.
+struct RadixDigit { int shift, bins; uint32_t mask; };
+__device__ __forceinline__ RadixDigit radix_digit(int level) {
+    return level == 0 ? RadixDigit{21, 2048, 0u} : level == 1 ? RadixDigit{10, 2048, 0xFFE00000u} : RadixDigit{0, 1024, 0xFFFFFC00u};
+}
+// One 256-thread workgroup: the bin of `hist` (this level's counts of the keys under the prefix st[0]) that holds rank kk, by a
+// fixed-order scan; st[0] gains the bin's digit, st[1] becomes the rank within the bin.  C = uint32_t or unsigned long long counts.
+template <typename C> __device__ __forceinline__ void radix_pick(const C* __restrict__ hist, C* __restrict__ st, C kk, int level,
+                                                                 C* part, int tid) {
+    const RadixDigit dg = radix_digit(level);
+    const int per = dg.bins / 256;
+    C mine = 0;
+    for (int j = 0; j < per; ++j) mine += hist[tid * per + j];
+    part[tid] = mine;
+    __syncthreads();
+    C before = 0;                                            // exclusive prefix of this thread's bin range (256 adds: negligible)
+    for (int t = 0; t < tid; ++t) before += part[t];
+    if (kk < before || kk >= before + mine) return;
+    for (int j = 0; j < per; ++j) {
+        const C cnt = hist[tid * per + j];
+        if (kk < before + cnt) {
+            const uint32_t prefix = level == 0 ? 0u : (uint32_t)st[0];
+            st[0] = prefix | ((uint32_t)(tid * per + j) << dg.shift);
+            st[1] = kk - before;
+            return;
+        }
+        before += cnt;
+    }
+}
+// b = c_(k+1) beside a = c_(k) among `size` keys: a again when k is the last rank or count(c <= a) already covers rank k+1, else
+// min(c > a), which the "next" passes keep as the maximum of the complemented bits
+__device__ __forceinline__ uint32_t radix_next_bits(uint32_t a, long long k, long long size, long long count_le, uint32_t not_min_gt) {
+    return (k + 1 < size && count_le < k + 2) ? ~not_min_gt : a;
+}

@@ -60,11 +60,11 @@ def subset_indices(fname: str, count: int, size: int) -> np.ndarray:
 
 
 def filter_taps(f) -> np.ndarray:
-    """A filter (8 flattened taps or a (3,3[,1]) kernel, see ops._filter_taps64) -> its 9 float64 taps in K14's layout, if its AE is
-    exact in float32 (taps multiples of 2^-12 and 255 * (1 + sum |f|) < 2^12: the residual is then a multiple of 2^-12 below 2^12,
+    """A filter (8 flattened taps or a (3,3[,1]) kernel, see ops.filter_taps) -> its 9 float64 weights of x[r-1+a][c-1+b], if its AE
+    is exact in float32 (taps multiples of 2^-12 and 255 * (1 + sum |f|) < 2^12: the residual is then a multiple of 2^-12 below 2^12,
     24 significant bits).  ValueError otherwise."""
-    from .ops import _filter_taps64
-    t = _filter_taps64(f)
+    from . import ops
+    t = ops.filter_taps(f, np.float64, "weights", "2d 8")
     scaled = t * 4096.0
     if not (np.all(np.isfinite(t)) and np.array_equal(scaled, np.round(scaled)) and 255.0 * (1.0 + np.abs(t).sum()) < 4096.0):
         raise ValueError(f"filter {np.asarray(f).reshape(-1).tolist()}: its AE is not exact in float32 (taps must be multiples of "

@@ -81,7 +81,7 @@ def get_processor_2d(channels: typing.List[int]) -> typing.Callable:
 # ---- prediction-error table (src/filters/evaluate.py:53-115,149-179) ------------------------------------------------------------------------
 # The reference's get_processor (_defs/filters.py:39-69) turns a plane into the eight neighbours x00 x01 x02 x12 x22 x21 x20 x10 and the
 # centre x11, and `y - x @ filter` is the residual; here the 8 taps go to the kernel, which reads the neighbours itself
-# (ops._filter_taps64), and the HILL cost is computed on the device.  conseal.hill._costmap.compute_cost of the reference is the
+# (ops.filter_taps), and the HILL cost is computed on the device.  conseal.hill._costmap.compute_cost of the reference is the
 # textbook cost of ws_unet_amd.hill (the one that reproduces the published filters.csv).
 
 def _plane_u8(img: np.ndarray, channel: int) -> np.ndarray:

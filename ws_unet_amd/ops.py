@@ -965,16 +965,49 @@ def ws_residual_stats(x_u8: torch.Tensor, y01: torch.Tensor) -> Tuple[torch.Tens
     return beta, l1
 
 
-def _taps(k) -> Optional[np.ndarray]:
-    """(3,3) / (3,3,1) kernel array -> 9 contiguous host floats K[a][b] (layout of the reference's NAMED_FILTERS)."""
+_RING = ((0, 0), (0, 1), (0, 2), (1, 2), (2, 2), (2, 1), (2, 0), (1, 0))     # neighbour order of the flattened 8-tap filters
+
+
+def filter_taps(k, dtype, layout: str, allow: str = "2d") -> Optional[np.ndarray]:
+    """A 3x3 linear predictor -> the 9 contiguous host values a C entry point wants, or None for None.  layout "kernel": K[a][b] of
+    the reference's (3,3[,1]) NAMED_FILTERS_2D arrays, applied as a true convolution to x[r+1-a][c+1-b] (wsu_ws_attack,
+    wsu_filter3x3_valid_f32, wsu_pair_correlation); layout "weights": the weight of x[r-1+a][c-1+b] at [a*3+b], the same numbers
+    reversed (wsu_prediction_error, wsu_ae_values).  Always accepted: a (3,3) / (3,3,1) kernel array.  With "8" in `allow` also the
+    reference's flattened 8-tap coefficients ((8,) / (8,1), NAMED_FILTERS, neighbour order x00 x01 x02 x12 x22 x21 x20 x10 of
+    _defs/filters.py:57-67); with "9" also a (9,) array that is already in `layout`."""
     if k is None:
         return None
-    k = np.asarray(k, dtype=np.float32)
-    if k.ndim == 3 and k.shape[2] == 1:
-        k = k[..., 0]
-    if k.shape != (3, 3):
-        raise ValueError(f"3x3 single-channel kernel expected, got shape {k.shape}")
-    return np.ascontiguousarray(k)
+    k = np.asarray(k, dtype=dtype)
+    if "9" in allow and k.shape == (9,):
+        return np.ascontiguousarray(k)
+    if "8" in allow and k.size == 8:
+        wgt = np.zeros((3, 3), dtype=dtype)
+        for tap, (a, b) in zip(k.reshape(8), _RING):
+            wgt[a, b] = tap
+    else:
+        if k.ndim == 3 and k.shape[2] == 1:
+            k = k[..., 0]
+        if k.shape != (3, 3):
+            raise ValueError(f"{'8 flattened taps or a ' if '8' in allow else ''}3x3 single-channel kernel expected, got shape {k.shape}")
+        wgt = k[::-1, ::-1]
+    return np.ascontiguousarray((wgt if layout == "weights" else wgt[::-1, ::-1]).reshape(9))
+
+
+def _hat_full(x_hat: torch.Tensor, n: int, h: int, w: int, hat_full: Optional[bool] = None, *others: Optional[torch.Tensor]) -> int:
+    """Validate a prediction (and tensors that must match it, such as x_bias): contiguous float32 of N*H*W values (full frames,
+    returns 1) or N*(H-2)*(W-2) (interiors, returns 0).  `hat_full` says which one the caller requires; None infers it."""
+    for t in (x_hat,) + tuple(o for o in others if o is not None):
+        if t.dtype != torch.float32:
+            raise ValueError(f"x_hat must be float32, got {t.dtype}")
+        if not t.is_contiguous() or t.numel() != x_hat.numel():
+            raise ValueError(f"x_hat must be contiguous and x_bias must match it, got {tuple(t.shape)} for {tuple(x_hat.shape)}")
+    full, inner = n * h * w, n * (h - 2) * (w - 2)
+    if hat_full is None and x_hat.numel() in (full, inner):
+        return int(x_hat.numel() == full)
+    if hat_full is not None and x_hat.numel() == (full if hat_full else inner):
+        return int(bool(hat_full))
+    raise ValueError(f"prediction of {tuple(x_hat.shape)} does not match pixels {(n, h, w)}"
+                     + ("" if hat_full is None else f" (hat_full={bool(hat_full)})"))
 
 
 def ws_attack(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, x_bias: Optional[torch.Tensor] = None,
@@ -987,18 +1020,8 @@ def ws_attack(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, x_bia
     _dev_check(x_u8, *[t for t in (x_hat, x_bias) if t is not None])
     n, h, w = x_u8.shape
     assert x_u8.dtype == torch.uint8
-    hat_full = 1
-    if x_hat is not None:
-        assert x_hat.dtype == torch.float32 and x_hat.is_contiguous()
-        if x_hat.numel() == n * h * w:
-            hat_full = 1
-        elif x_hat.numel() == n * (h - 2) * (w - 2):
-            hat_full = 0
-        else:
-            raise ValueError(f"prediction of {tuple(x_hat.shape)} does not match pixels {tuple(x_u8.shape)}")
-        if x_bias is not None:
-            assert x_bias.dtype == torch.float32 and x_bias.is_contiguous() and x_bias.numel() == x_hat.numel()
-    pt, mt = _taps(pixel_filter), _taps(mean_filter)
+    hat_full = _hat_full(x_hat, n, h, w, None, x_bias) if x_hat is not None else 1
+    pt, mt = filter_taps(pixel_filter, np.float32, "kernel"), filter_taps(mean_filter, np.float32, "kernel")
     beta = torch.empty(n, dtype=torch.float32, device=x_u8.device)
     sums = torch.empty((n, 3), dtype=torch.float64, device=x_u8.device) if return_sums else None
     ws = torch.empty(lib.wsu_ws_attack_workspace_bytes(n) // 8, dtype=torch.float64, device=x_u8.device)
@@ -1037,29 +1060,11 @@ def hill_threshold(cost: torch.Tensor, quantile: float = 0.1) -> torch.Tensor:
     return q
 
 
-def _filter_taps64(k) -> np.ndarray:
-    """Pixel filter -> 9 contiguous host doubles, the weight of x[r-1+a][c-1+b] at [a*3+b].  Accepts the reference's flattened
-    8-tap coefficients ((8,) / (8,1), NAMED_FILTERS, neighbour order x00 x01 x02 x12 x22 x21 x20 x10 of _defs/filters.py:57-67)
-    or a (3,3[,1]) kernel array in the convolution layout of NAMED_FILTERS_2D (the one ws_attack takes)."""
-    k = np.asarray(k, dtype=np.float64)
-    if k.size == 8:
-        f = k.reshape(8)
-        out = np.zeros((3, 3))
-        for t, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 2), (2, 2), (2, 1), (2, 0), (1, 0))):
-            out[a, b] = f[t]
-        return np.ascontiguousarray(out.reshape(9))
-    if k.ndim == 3 and k.shape[2] == 1:
-        k = k[..., 0]
-    if k.shape != (3, 3):
-        raise ValueError(f"8 flattened taps or a 3x3 single-channel kernel expected, got shape {k.shape}")
-    return np.ascontiguousarray(k[::-1, ::-1].reshape(9))         # true convolution -> weights of x[r-1+a][c-1+b]
-
-
 def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, hat_scale: float = 255.,
                      quantile: float = 0.1, cost: Optional[torch.Tensor] = None, return_threshold: bool = False):
     """Per-image MAE and HILL-cost weighted MAE of a pixel prediction on the interior [1:-1,1:-1] (K12-K14).
     x_u8: (N,H,W) uint8.  x_hat: (N,H,W)/(N,1,H,W) full-frame prediction or (N,H-2,W-2) interior prediction, multiplied by
-    `hat_scale` (255 for a network output in [0,1]); or `pixel_filter` (8 flattened taps or a (3,3[,1]) kernel, see _filter_taps64)
+    `hat_scale` (255 for a network output in [0,1]); or `pixel_filter` (8 flattened taps or a (3,3[,1]) kernel, see filter_taps)
     evaluated in float64 inside the kernel.  `cost` reuses a hill_cost() map.  Returns (mae[N], wmae[N]) fp64 on the device,
     plus (q[N] fp64, selected[N] int64) with return_threshold=True."""
     lib = _lib.load()
@@ -1068,16 +1073,8 @@ def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *
     n, h, w = x_u8.shape
     if (x_hat is None) == (pixel_filter is None):
         raise ValueError("give exactly one of x_hat / pixel_filter")
-    hat_full = 1
-    if x_hat is not None:
-        assert x_hat.dtype == torch.float32
-        if x_hat.numel() == n * h * w:
-            hat_full = 1
-        elif x_hat.numel() == n * (h - 2) * (w - 2):
-            hat_full = 0
-        else:
-            raise ValueError(f"prediction of {tuple(x_hat.shape)} does not match pixels {tuple(x_u8.shape)}")
-    pt = _filter_taps64(pixel_filter) if pixel_filter is not None else None
+    hat_full = _hat_full(x_hat, n, h, w) if x_hat is not None else 1
+    pt = filter_taps(pixel_filter, np.float64, "weights", "2d 8")
     if cost is None:
         cost = hill_cost(x_u8)
     assert cost.dtype == torch.float32 and cost.shape == x_u8.shape
@@ -1110,18 +1107,8 @@ def pair_correlation(xc_u8: torch.Tensor, xs_u8: torch.Tensor, x_hat: Optional[t
     if (x_hat is None) == (pixel_filter is None):
         raise ValueError("give exactly one of x_hat / pixel_filter")
     if x_hat is not None:
-        if x_hat.dtype != torch.float32:
-            raise ValueError(f"x_hat must be float32, got {x_hat.dtype}")
-        want = n * h * w if hat_full else n * (h - 2) * (w - 2)
-        if x_hat.numel() != want:
-            raise ValueError(f"prediction of {tuple(x_hat.shape)} does not match pixels {tuple(xc_u8.shape)} (hat_full={bool(hat_full)})")
-    pt = None
-    if pixel_filter is not None:                                   # K11's layout K[a][b], kept in float64 (no float32 rounding of the taps)
-        pt = np.asarray(pixel_filter, dtype=np.float64)
-        pt = pt[..., 0] if pt.ndim == 3 and pt.shape[2] == 1 else pt
-        if pt.shape != (3, 3):
-            raise ValueError(f"3x3 single-channel kernel expected, got shape {np.shape(pixel_filter)}")
-        pt = np.ascontiguousarray(pt.reshape(9))
+        _hat_full(x_hat, n, h, w, bool(hat_full))
+    pt = filter_taps(pixel_filter, np.float64, "kernel")           # K11's layout, kept in float64 (no float32 rounding of the taps)
     cor = torch.empty(n, dtype=torch.float64, device=xc_u8.device)
     mom = torch.empty((n, 6), dtype=torch.float64, device=xc_u8.device) if moments else None
     ws = torch.empty(lib.wsu_pair_correlation_workspace_bytes(n) // 8, dtype=torch.float64, device=xc_u8.device)
@@ -1136,8 +1123,8 @@ def ae_values(x_u8: torch.Tensor, keys: torch.Tensor, offset: int, flag: torch.T
               pixel_filter=None, hat_scale: float = 255., idx: Optional[torch.Tensor] = None) -> None:
     """K16: the float32 absolute error of one predictor on the interior of (N,H,W) uint8 planes, written into the 1-D float32 `keys`
     at `offset` + i*per + j (per = idx.shape[1], or (H-2)(W-2)).  The predictor is a full-frame `x_hat` ((N,H,W) / (N,1,H,W) fp32,
-    times `hat_scale`: |x - x_hat*255| in float32) or `pixel_filter` (9 taps in the kernel's layout, or anything
-    _filter_taps64 takes; |y - x @ f| in float64).  idx: optional
+    times `hat_scale`: |x - x_hat*255| in float32) or `pixel_filter` (9 weights of x[r-1+a][c-1+b], 8 flattened taps or a
+    (3,3[,1]) kernel, see filter_taps; |y - x @ f| in float64).  idx: optional
     (N,m) int64 interior indices.  flag: a 1-element int32 device tensor, OR-ed with 1 on NaN / inf, 2 on a bad index."""
     lib = _lib.load()
     _dev_check(x_u8, keys, flag, x_hat, idx)
@@ -1147,17 +1134,14 @@ def ae_values(x_u8: torch.Tensor, keys: torch.Tensor, offset: int, flag: torch.T
     n, h, w = x_u8.shape
     if (x_hat is None) == (pixel_filter is None):
         raise ValueError("give exactly one of x_hat / pixel_filter")
-    if x_hat is not None and (x_hat.dtype != torch.float32 or x_hat.numel() != n * h * w or not x_hat.is_contiguous()):
-        raise ValueError(f"x_hat must be a contiguous float32 full-frame prediction of {n * h * w} values, got {tuple(x_hat.shape)}")
+    if x_hat is not None:
+        _hat_full(x_hat, n, h, w, True)
     m = 0
     if idx is not None:
         if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != n or not idx.is_contiguous():
             raise ValueError(f"idx must be a contiguous (N,m) int64 tensor, got {tuple(idx.shape)} {idx.dtype}")
         m = int(idx.shape[1])
-    pt = None
-    if pixel_filter is not None:                                   # 9 taps already in the kernel's layout, or what _filter_taps64 takes
-        pf = np.asarray(pixel_filter, dtype=np.float64)
-        pt = np.ascontiguousarray(pf) if pf.shape == (9,) else _filter_taps64(pf)
+    pt = filter_taps(pixel_filter, np.float64, "weights", "2d 8 9")
     per = m if m else (h - 2) * (w - 2)
     check(_launch("ae_values", {"bytes": float(n * (h * w * (5 if x_hat is not None else 1) + per * 4))}, lambda: lib.wsu_ae_values(
         x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None, float(hat_scale),
@@ -1240,7 +1224,7 @@ def filter3x3_valid(x: torch.Tensor, kernel) -> torch.Tensor:
     _dev_check(x)
     assert x.dtype == torch.float32 and x.dim() == 3
     n, h, w = x.shape
-    k = _taps(kernel)
+    k = filter_taps(kernel, np.float32, "kernel")
     y = torch.empty((n, h - 2, w - 2), dtype=torch.float32, device=x.device)
     check(lib.wsu_filter3x3_valid_f32(x.data_ptr(), k.ctypes.data, y.data_ptr(), n, h, w, _stream()), "wsu_filter3x3_valid_f32")
     return y
