@@ -373,6 +373,62 @@ def test_batched_iterator_submits_the_next_chunk_before_collecting(tmp_path):
                    ("collect", "staged:3.png"), ("collect", "staged:6.png")]
 
 
+def test_pipeline_stages_one_chunk_ahead_with_one_in_flight():
+    """fabrika.pipeline itself, driven as the iterator drives a fn that has `prefetch` but no `submit` (submit = fn, collect = identity): the
+    event order of the two-stage test above; with a split fn the order of the three-stage one; without prefetch no helper thread, same order."""
+    import threading
+    log, chunks = [], [[0, 1, 2], [3, 4, 5], [6]]
+    main, staged_next = threading.get_ident(), {3: threading.Event(), 6: threading.Event()}
+
+    def prefetch(ch):
+        log.append(("pre", ch[0], threading.get_ident() == main))
+        if ch[0] in staged_next:
+            staged_next[ch[0]].set()
+        return f"staged:{ch[0]}"
+
+    def run(ch, staged):
+        if ch[0] + 3 in staged_next:                          # chunk k+1 is being staged while chunk k runs (not after it)
+            assert staged_next[ch[0] + 3].wait(timeout=30)
+        log.append(("run", ch[0], staged))
+        return [(i, staged) for i in ch]
+    out = list(fabrika.pipeline(chunks, prefetch, run, lambda h: h))
+    assert out == [[(i, f"staged:{ch[0]}") for i in ch] for ch in chunks]
+    assert [e for e in log if e[0] == "pre"] == [("pre", 0, False), ("pre", 3, False), ("pre", 6, False)]      # each once, on the helper thread
+    assert [e for e in log if e[0] == "run"] == [("run", 0, "staged:0"), ("run", 3, "staged:3"), ("run", 6, "staged:6")]
+    # split form: submit(k+1) before collect(k), at most one chunk in flight
+    log.clear()
+    out = list(fabrika.pipeline(chunks, lambda ch: None, lambda ch, st: log.append(("submit", ch[0])) or ch,
+                                lambda h: log.append(("collect", h[0])) or h))
+    assert out == chunks
+    assert log == [("submit", 0), ("submit", 3), ("collect", 0), ("submit", 6), ("collect", 3), ("collect", 6)]
+    # no prefetch: nothing staged, no thread, same order; no chunks: nothing happens
+    log.clear()
+    before = threading.active_count()
+    out = list(fabrika.pipeline(chunks, None, lambda ch, st: log.append(("submit", ch[0], st, threading.active_count() - before)) or ch, lambda h: h))
+    assert out == chunks and log == [("submit", 0, None, 0), ("submit", 3, None, 0), ("submit", 6, None, 0)]
+    assert list(fabrika.pipeline([], prefetch, run, lambda h: h)) == []
+
+
+def test_shared_kwargs_strips_the_rows_and_keeps_the_split():
+    seen = []
+
+    def fn(fnames, kws, prefetched=None, **shared):
+        seen.append(("fn", kws, prefetched, shared))
+        return kws
+    plain = fabrika.shared_kwargs(fn, ("model", "imread"))
+    rows = [{"name": "a", "model": 1, "imread": 2}, {"name": "b", "model": 1, "imread": 2}]
+    assert plain(["a", "b"], rows, prefetched="p") == [{"name": "a"}, {"name": "b"}]
+    assert seen == [("fn", [{"name": "a"}, {"name": "b"}], "p", {"model": 1, "imread": 2})]
+    assert not hasattr(plain, "prefetch") and not hasattr(plain, "submit")
+    assert plain(["a"], [{"name": "a", "model": 1}]) == [{"name": "a"}] and seen[-1][3] == {"model": 1}     # an absent key is not invented
+    fn.submit = lambda fnames, kws, prefetched=None, **shared: ("handle", kws, prefetched, shared)
+    fn.collect = lambda handle: handle[1]
+    pre = lambda fnames, kws: kws[0]["imread"]                # the prefetch stage sees the unstripped rows
+    split = fabrika.shared_kwargs(fn, ("model", "imread"), pre)
+    assert split.prefetch is pre and split.collect is fn.collect
+    assert split.submit(["a", "b"], rows, prefetched="p") == ("handle", [{"name": "a"}, {"name": "b"}], "p", {"model": 1, "imread": 2})
+
+
 def _pair_dataset(root, n=10, size=16):
     from PIL import Image
     from ws_unet_amd import formula

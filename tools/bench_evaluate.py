@@ -27,7 +27,7 @@ m = get_model("unet_2", in_channels=1, out_channels=1, channel=[0], drop_rate=0.
 m.load_state_dict({k: torch.from_numpy(v) for k, v in formula.formula_state_dict(2, "he").items()})
 m = m.to("cuda")
 batched = fabrika.precovers(iterator="batched", convert_to="pandas", ignore_missing=False, batch_size=a.batch)(
-    evaluate._drop_model_kw(evaluate.predict_unet_batch))
+    fabrika.shared_kwargs(evaluate.predict_unet_batch, ("model", "imread", "device"), evaluate._prefetch_planes))
 batched(root, model=m, take_num_images=a.batch)                 # warm-up
 torch.cuda.synchronize()
 t0 = time.perf_counter(); dfb = batched(root, model=m); torch.cuda.synchronize(); t_b = time.perf_counter() - t0

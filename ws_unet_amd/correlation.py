@@ -124,29 +124,6 @@ def p_value(cor, n):
 
 # ---- GPU correlation of a batch of pairs ------------------------------------------------------------------------------------------
 
-def _unet_model(predictor):
-    import torch
-    from .ws.estimate import UNetEstimator
-    if isinstance(predictor, UNetEstimator):
-        return predictor.model
-    return predictor if isinstance(predictor, torch.nn.Module) else None
-
-
-def _device_of(predictor):
-    import torch
-    from .evaluate import _model_device
-    model = _unet_model(predictor)
-    return _model_device(model) if model is not None else torch.device("cuda")
-
-
-def _unet_cor(xc_u8, xs_u8, model):
-    import torch
-    from . import ops
-    with torch.no_grad():
-        y = model(ops.u8_to_unit(xs_u8)[:, None])[:, 0].contiguous()
-    return ops.pair_correlation(xc_u8, xs_u8, y, hat_full=True, hat_scale=255.)
-
-
 def correlation_u8_batch(xc_u8, xs_u8, predictor) -> typing.Tuple[np.ndarray, np.ndarray]:
     """(cor[N], p[N]) float64 numpy arrays for a batch of cover / stego planes, (N,H,W) uint8 device tensors.  The predictor is
       * a `filters.FilterEstimator`: its taps are evaluated on the stego planes inside K15 (no host convolution);
@@ -155,18 +132,17 @@ def correlation_u8_batch(xc_u8, xs_u8, predictor) -> typing.Tuple[np.ndarray, np
       * any other callable: the reference's call pattern, `predictor(x_s)` per image on the host with x_s (H,W,1) float32 in
         0..255, returning (H-2,W-2[,1]); the predictions are uploaded as float32."""
     from . import evaluate, ops
+    from .ws.estimate import unet_model_of
     if xc_u8.dim() != 3 or xc_u8.shape != xs_u8.shape:
         raise ValueError(f"cover and stego batches differ in shape: {tuple(xc_u8.shape)} and {tuple(xs_u8.shape)}")
     n, h, w = xc_u8.shape
-    model = _unet_model(predictor)
+    model = unet_model_of(predictor)
     if isinstance(predictor, filters.FilterEstimator):
         cor = ops.pair_correlation(xc_u8, xs_u8, pixel_filter=np.asarray(predictor.kernel)[..., ::-1])
     elif model is not None:
-        if (h, w) != (512, 512):
-            raise ValueError(f"the UNet predictor works on 512x512 planes, got {h}x{w} (CenterCrop(512) would change the geometry)")
-        cor = _unet_cor(xc_u8, xs_u8, model)
-        if evaluate.range_fallback(model):
-            cor = _unet_cor(xc_u8, xs_u8, model)
+        evaluate.check_unet_geometry((h, w), "the UNet predictor")
+        cor = evaluate.range_retry(model, lambda: ops.pair_correlation(xc_u8, xs_u8, evaluate.unet_plane(model, xs_u8), hat_full=True,
+                                                                      hat_scale=255.))
     else:
         import torch
         hats = []
@@ -210,11 +186,13 @@ def _row(name_c, name_s, cor, p) -> dict:
 
 def _pair_one(fname, name_c, name_s, predictor, **_kw) -> dict:
     import torch
+    from .evaluate import _model_device
+    from .ws.estimate import unet_model_of
     path_c, path_s = _pair_paths(fname, name_c, name_s)
     x_c, x_s = _read_gray(path_c), _read_gray(path_s)
     if x_c.shape != x_s.shape:
         raise ValueError(f"cover {path_c} is {x_c.shape}, stego {path_s} is {x_s.shape}")
-    dev = _device_of(predictor)
+    dev = _model_device(unet_model_of(predictor))
     cor, p = correlation_u8_batch(torch.from_numpy(x_c)[None].to(dev), torch.from_numpy(x_s)[None].to(dev), predictor)
     return _row(name_c, name_s, cor[0], p[0])
 
@@ -239,14 +217,13 @@ def _chunk_planes(fnames, kws):
 
 def _pair_chunk(fnames, kws, prefetched=None) -> typing.List[dict]:
     """_pair_one for a chunk of pairs (fabrika iterator='batched'): one upload and one K15 launch chain for the whole chunk."""
-    from .evaluate import mark_uploaded
+    from .evaluate import _model_device, upload_planes
+    from .ws.estimate import unet_model_of
     planes = prefetched if prefetched is not None else _chunk_planes(fnames, kws)
     if planes is None:                                              # ragged chunk
         return [_pair_one(f, **kw) for f, kw in zip(fnames, kws)]
     predictor = kws[0]["predictor"]
-    dev = _device_of(predictor)
-    xc, xs = planes[0].to(dev, non_blocking=True), planes[1].to(dev, non_blocking=True)
-    mark_uploaded(planes)
+    xc, xs = upload_planes(planes, _model_device(unet_model_of(predictor)))
     cor, p = correlation_u8_batch(xc, xs, predictor)
     return [_row(kw["name_c"], kw["name_s"], cor[i], p[i]) for i, kw in enumerate(kws)]
 
@@ -309,13 +286,10 @@ def main(argv=None) -> None:
     for name in a.filters:
         add(name, filters.get_filter_estimator(filter_name=name, flatten=False))
     if a.model_dir:
-        from . import get_unet_estimator
-        from .evaluate import get_model_config, get_model_name
-        model_dir = pathlib.Path(a.model_dir)
-        for method in a.unet_stego_methods:
-            model_name = get_model_name(stego_method=method, model_dir=model_dir)
-            config = get_model_config(model_dir=model_dir, stego_method=method, model_name=model_name)
-            predictor = get_unet_estimator(model_path=model_dir / method, model_name=model_name, channels=(3,), mode=a.mode)
+        from .evaluate import trained_runs
+        from .ws.estimate import as_unet_estimator
+        for method, model_name, config in trained_runs(a.model_dir, a.unet_stego_methods):
+            predictor = as_unet_estimator((pathlib.Path(a.model_dir) / method, model_name), a.mode)
             add(f"UNet_{method}_{config['loss']}", predictor)
     out = pathlib.Path(a.out)
     out.parent.mkdir(parents=True, exist_ok=True)

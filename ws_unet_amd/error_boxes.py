@@ -195,34 +195,24 @@ def _resolve(name: str, spec, mode) -> _Pred:
     """A predictor spec: a filter name of filters.NAMED_FILTERS, filter taps, a UNet model / UNetEstimator, or (model_path,
     model_name) of a trained run (loaded in inference `mode`)."""
     import torch
-    from .ws.estimate import UNetEstimator
+    from .ws.estimate import UNetEstimator, as_unet_estimator
     if isinstance(spec, str):
         if spec not in filters.NAMED_FILTERS:
             raise ValueError(f"predictor {name}: unknown filter {spec!r}")
         return _Pred(name, taps=filter_taps(filters.get_coefficients(spec)))
-    if isinstance(spec, UNetEstimator):
-        return _Pred(name, model=spec.model)
-    if isinstance(spec, torch.nn.Module):
-        return _Pred(name, model=spec)
-    if isinstance(spec, tuple) and len(spec) == 2 and not isinstance(spec[0], (int, float)):
-        from .evaluate import get_pretrained
-        return _Pred(name, model=get_pretrained(spec[0], (3,), model_name=spec[1], mode=mode))
+    if isinstance(spec, (UNetEstimator, torch.nn.Module)) or (isinstance(spec, tuple) and len(spec) == 2 and not isinstance(spec[0], (int, float))):
+        return _Pred(name, model=as_unet_estimator(spec, mode).model)
     return _Pred(name, taps=filter_taps(spec))
 
 
 def _keys_of(x, pred: _Pred, keys_row, offset: int, flag, idx) -> None:
     """K16 for one predictor over (N,H,W) device planes."""
-    import torch
-    from . import ops
+    from . import evaluate, ops
     if pred.taps is not None:
         ops.ae_values(x, keys_row, offset, flag, pixel_filter=pred.taps, idx=idx)
         return
-    if tuple(x.shape[1:]) != (512, 512):
-        raise ValueError(f"predictor {pred.name}: the UNet works on 512x512 planes, got {tuple(x.shape[1:])} "
-                         "(the reference's CenterCrop(512) would change the geometry)")
-    with torch.no_grad():
-        y = pred.model(ops.u8_to_unit(x)[:, None])[:, 0].contiguous()
-    ops.ae_values(x, keys_row, offset, flag, x_hat=y, hat_scale=255., idx=idx)
+    evaluate.check_unet_geometry(x.shape[1:], f"predictor {pred.name}: the UNet")
+    ops.ae_values(x, keys_row, offset, flag, x_hat=evaluate.unet_plane(pred.model, x), hat_scale=255., idx=idx)
 
 
 def _indices(fnames, count: int, num_pixels, device):
@@ -256,26 +246,23 @@ def _fill(fnames, hw, per, preds, rows, keys, flags, num_pixels, batch_size, pro
     """Stream the files through the batched u8 reader (decode of chunk k+1 beside the GPU work on chunk k) and write the keys of
     `preds` into keys[rows[p]] at each image's offset."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
-    from tqdm import tqdm
-    from .evaluate import mark_uploaded
-    chunks = [list(range(k, min(k + batch_size, len(fnames)))) for k in range(0, len(fnames), batch_size)]
+    from .evaluate import upload_planes
+    chunks = [range(k, min(k + batch_size, len(fnames))) for k in range(0, len(fnames), batch_size)]
     offsets = np.concatenate([[0], np.cumsum(per)])
-    with ThreadPoolExecutor(max_workers=1) as ex:
-        fut = ex.submit(_groups, [fnames[i] for i in chunks[0]], [hw[i] for i in chunks[0]]) if chunks else None
-        for k, chunk in enumerate(tqdm(chunks, disable=not progress_on)):
-            groups = fut.result()
-            if k + 1 < len(chunks):
-                fut = ex.submit(_groups, [fnames[i] for i in chunks[k + 1]], [hw[i] for i in chunks[k + 1]])
-            i0 = chunk[0]
-            for planes, fs in groups:
-                x = planes.to("cuda", non_blocking=True)
-                mark_uploaded(planes)
-                idx = _indices(fs, (x.shape[1] - 2) * (x.shape[2] - 2), num_pixels, x.device)
-                for p, pred in enumerate(preds):
-                    r = rows[p]
-                    _keys_of(x, pred, keys[r], int(offsets[i0]), flags[r:r + 1], idx)
-                i0 += len(fs)
+
+    def submit(chunk, groups):                                      # upload and queue K16 for every predictor; nothing is read back
+        i0 = chunk[0]
+        for planes, fs in groups:
+            x = upload_planes(planes, "cuda")
+            idx = _indices(fs, (x.shape[1] - 2) * (x.shape[2] - 2), num_pixels, x.device)
+            for p, pred in enumerate(preds):
+                r = rows[p]
+                _keys_of(x, pred, keys[r], int(offsets[i0]), flags[r:r + 1], idx)
+            i0 += len(fs)
+
+    stage = lambda chunk: _groups([fnames[i] for i in chunk], [hw[i] for i in chunk])
+    for _ in fabrika.tqdm(fabrika.pipeline(chunks, stage, submit, lambda handle: None), total=len(chunks), disable=not progress_on):
+        pass
     torch.cuda.current_stream().synchronize()
 
 
@@ -334,8 +321,8 @@ def _filter_residuals(fname, filter, num_pixels=None, **kw) -> np.ndarray:
 
 
 def _unet_residuals(fname, model, channels=(3,), num_pixels=None, **kw) -> np.ndarray:
-    from .ws.estimate import UNetEstimator
-    return _ae_one(fname, _Pred("UNet", model=model.model if isinstance(model, UNetEstimator) else model), num_pixels)
+    from .ws.estimate import unet_model_of
+    return _ae_one(fname, _Pred("UNet", model=unet_model_of(model)), num_pixels)
 
 
 # src/error_boxes.py filter_residuals / unet_residuals: one flat array per image (all interior pixels, or `num_pixels` draws).  They
@@ -385,12 +372,9 @@ def main(argv=None) -> None:
     logging.basicConfig(level=logging.INFO)
     predictors = {"KB": "KB", "AVG": "AVG"}
     if a.model_dir:
-        from .evaluate import get_model_config, get_model_name
-        model_dir = pathlib.Path(a.model_dir)
-        for method in UNET_RUNS:
-            model_name = get_model_name(stego_method=method, model_dir=model_dir)
-            config = get_model_config(model_dir=model_dir, stego_method=method, model_name=model_name)
-            predictors[f"UNet_{config['loss']}"] = (model_dir / method, model_name)
+        from .evaluate import trained_runs
+        for method, model_name, config in trained_runs(a.model_dir, UNET_RUNS):
+            predictors[f"UNet_{config['loss']}"] = (pathlib.Path(a.model_dir) / method, model_name)
     res = run(a.data, predictors, anchor="KB", split=a.split, take_num_images=a.take_num_images, num_pixels=a.num_pixels, mode=a.mode,
               progress_on=a.progress)
     out = pathlib.Path(a.out)

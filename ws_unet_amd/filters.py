@@ -17,7 +17,7 @@ import typing
 import numpy as np
 
 from . import fabrika
-from .imread import imread4_u8
+from .imread import imread4_u8, u8_plane
 
 NAMED_FILTERS = {
     "KB": np.array([[-1], [+2], [-1], [+2], [-1], [+2], [-1], [+2]], dtype="float64") / 4.,
@@ -85,21 +85,14 @@ def get_processor_2d(channels: typing.List[int]) -> typing.Callable:
 # textbook cost of ws_unet_amd.hill (the one that reproduces the published filters.csv).
 
 def _plane_u8(img: np.ndarray, channel: int) -> np.ndarray:
-    p = np.asarray(img)[..., channel]
-    if p.dtype != np.uint8:
-        u = p.astype(np.uint8)
-        if not np.array_equal(u, p):
-            raise ValueError("the HILL cost is defined on 8-bit pixel values")
-        p = u
-    return np.ascontiguousarray(p)
+    return u8_plane(np.asarray(img)[..., channel], "the HILL cost is defined on 8-bit pixel values")
 
 
 def _device_error(x_u8_host, filter):
     """(N,H,W) uint8 host planes -> numpy (mae[N], wmae[N]) of the in-kernel filter prediction."""
     import torch
-    from . import ops
-    x = torch.as_tensor(x_u8_host).to("cuda", non_blocking=True)
-    mae, wmae = ops.prediction_error(x, pixel_filter=filter)
+    from . import evaluate, ops
+    mae, wmae = ops.prediction_error(evaluate.upload_planes(torch.as_tensor(x_u8_host), "cuda"), pixel_filter=filter)
     return mae.cpu().numpy(), wmae.cpu().numpy()
 
 
@@ -141,18 +134,8 @@ def _chunk_planes(fnames, channels, imread):
     return np.stack(planes) if len({p.shape for p in planes}) == 1 else None
 
 
-def _split_kw(fn):
-    def wrapped(fnames, kws, prefetched=None):
-        shared = {k: kws[0][k] for k in _ROW_KEYS if k in kws[0]}
-        clean = [{k: v for k, v in kw.items() if k not in _ROW_KEYS} for kw in kws]
-        return fn(fnames, clean, prefetched=prefetched, **shared)
-
-    wrapped.prefetch = lambda fnames, kws: (_chunk_planes(fnames, kws[0]["channels"], kws[0].get("imread", imread4_u8)),)
-    return wrapped
-
-
-get_filter_residuals_cover_batched = fabrika.precovers(iterator="batched", convert_to="pandas", ignore_missing=True)(
-    _split_kw(_residuals_batch))
+get_filter_residuals_cover_batched = fabrika.precovers(iterator="batched", convert_to="pandas", ignore_missing=True)(fabrika.shared_kwargs(
+    _residuals_batch, _ROW_KEYS, lambda fnames, kws: (_chunk_planes(fnames, kws[0]["channels"], kws[0].get("imread", imread4_u8)),)))
 
 
 def run(input_dir: pathlib.Path, filter_names: typing.Sequence[str] = ("AVG", "KB"), channels=((3,),),

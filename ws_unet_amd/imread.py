@@ -38,6 +38,17 @@ def imread4_f32(fname) -> np.ndarray:
     return imread4_u8(fname).astype("float32")
 
 
+def u8_plane(p, what: str) -> np.ndarray:
+    """A plane of integer values 0..255, of any dtype, as contiguous uint8; ValueError(what) for any other values."""
+    p = np.asarray(p)
+    if p.dtype != np.uint8:
+        u = p.astype(np.uint8)
+        if not np.array_equal(u, p):
+            raise ValueError(what)
+        p = u
+    return np.ascontiguousarray(p)
+
+
 def png_shape(fname):
     """(H, W) of a PNG without decoding pixels (wsu_png_shape); None if libwsu_io cannot parse the file."""
     import ctypes

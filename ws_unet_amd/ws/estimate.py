@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from .. import fabrika, filters, ops
-from ..evaluate import _decode_pool, _model_device
-from ..imread import imread4_u8
+from ..evaluate import _decode_pool, _model_device, check_unet_geometry, unet_plane, upload_planes
+from ..imread import imread4_u8, u8_plane
 
 NAMED_FILTERS = filters.NAMED_FILTERS_2D
 
@@ -48,25 +48,38 @@ class UNetEstimator:
                         "use the fabrika iterators 'python' or 'batched' (ws.estimate.attack_cover / attack_cover_batched)")
 
 
+# ---- what a predictor is: a filters.FilterEstimator, a UNet (a UNetEstimator, or for some drivers a bare model or the (model_path,
+# model_name) of a trained run), or any other callable, run on the host like the reference's ----------------------------------------
+
+def unet_model_of(predictor):
+    """The UNet whose forward a driver runs on the device for this predictor (a UNetEstimator's, or a bare model), or None.
+    (Where a predictor's planes go is evaluate._model_device of it: the UNet's device, the default GPU for None.)"""
+    if isinstance(predictor, UNetEstimator):
+        return predictor.model
+    return predictor if isinstance(predictor, torch.nn.Module) else None
+
+
+def as_unet_estimator(unet, mode: str = None):
+    """None | UNetEstimator | model | (model_path, model_name) of a trained run (loaded in inference `mode`) -> UNetEstimator (None: None)."""
+    if unet is None or isinstance(unet, UNetEstimator):
+        return unet
+    if isinstance(unet, torch.nn.Module):
+        return UNetEstimator(unet)
+    if isinstance(unet, tuple) and len(unet) == 2:
+        from .. import get_unet_estimator
+        return get_unet_estimator(model_path=unet[0], model_name=unet[1], channels=(3,), mode=mode)
+    raise ValueError(f"unet: a UNetEstimator, a model or (model_path, model_name), got {type(unet).__name__}")
+
+
 def _as_u8_plane(x: np.ndarray) -> np.ndarray:
     """First channel of the processed image as uint8; the LSB flip is only defined for integer pixel values."""
-    p = np.asarray(x)[..., 0]
-    u = p.astype(np.uint8)
-    if not np.array_equal(u.astype(p.dtype), p):
-        raise ValueError("WS attack needs integer pixel values in 0..255")
-    return np.ascontiguousarray(u)
-
-
-def _device_of(pixel_estimator) -> torch.device:
-    if isinstance(pixel_estimator, UNetEstimator):
-        return _model_device(pixel_estimator.model)
-    return torch.device("cuda")
+    return u8_plane(np.asarray(x)[..., 0], "WS attack needs integer pixel values in 0..255")
 
 
 def _unet_planes(model, x_u8: torch.Tensor, correct_bias: bool):
     """Full-frame network outputs in [0,1] for x and (if needed) for x_bar - x (estimate.py:89,127)."""
+    y = unet_plane(model, x_u8)
     with torch.no_grad():
-        y = model(ops.u8_to_unit(x_u8)[:, None])[:, 0].contiguous()
         yb = model(ops.lsb_delta_unit(x_u8)[:, None])[:, 0].contiguous() if correct_bias else None
     return y, yb
 
@@ -76,8 +89,7 @@ def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct
     kw = dict(mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted) if abs(int(weighted)) == 1 else 0,
               correct_bias=correct_bias)
     if isinstance(pixel_estimator, UNetEstimator):
-        if x_u8.shape[1:] != (512, 512):
-            raise ValueError("the UNet estimator works on 512x512 planes (CenterCrop(512) would change the geometry)")
+        check_unet_geometry(x_u8.shape[1:], "the UNet estimator")
         y, yb = _unet_planes(pixel_estimator.model, x_u8, correct_bias)
         return ops.ws_attack(x_u8, y, x_bias=yb, hat_scale=255.0, **kw)
     if isinstance(pixel_estimator, filters.FilterEstimator):
@@ -111,7 +123,7 @@ def attack(
     """WS estimate of one image (estimate.py:55-136): returns kw | {beta_hat, channels, weighted, correct_bias}."""
     x = process_image(imread(fname))                         # x_bar = process(x ^ 1) is formed on the device
     try:
-        x_u8 = torch.from_numpy(_as_u8_plane(x))[None].to(_device_of(pixel_estimator))
+        x_u8 = torch.from_numpy(_as_u8_plane(x))[None].to(_model_device(unet_model_of(pixel_estimator)))
         beta_hat = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=[x])[0].item()
         beta_hat = np.float32(beta_hat)
     except ValueError:                                      # estimate.py:122-123
@@ -163,7 +175,7 @@ def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED
     try:
         if u8 is None:
             u8 = torch.from_numpy(np.stack([_as_u8_plane(p) for p in planes]))
-        x_u8 = u8.to(_device_of(pixel_estimator), non_blocking=True)
+        x_u8 = upload_planes(u8, _model_device(unet_model_of(pixel_estimator)))
         beta = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=planes).cpu().numpy()
     except ValueError:
         beta = [None] * len(fnames)
@@ -174,25 +186,16 @@ def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED
 _ATTACK_KEYS = ("channels", "pixel_estimator", "mean_estimator", "correct_bias", "weighted", "imread", "process_image")
 
 
-def _split_attack_kw(fn):
-    def wrapped(fnames, kws, prefetched=None):
-        shared = {k: kws[0][k] for k in _ATTACK_KEYS if k in kws[0]}
-        clean = [{k: v for k, v in kw.items() if k not in _ATTACK_KEYS} for kw in kws]
-        return fn(fnames, clean, prefetched=prefetched, **shared)
-
-    def prefetch(fnames, kws):
-        k0 = kws[0]
-        if not _native_planes_ok(k0["channels"], k0["pixel_estimator"], k0.get("imread", imread4_u8), k0.get("process_image")):
-            return None
-        from ..evaluate import load_planes_u8
-        return (load_planes_u8(fnames, imread4_u8),)
-
-    wrapped.prefetch = prefetch
-    return wrapped
+def _prefetch_native(fnames, kws):
+    k0 = kws[0]
+    if not _native_planes_ok(k0["channels"], k0["pixel_estimator"], k0.get("imread", imread4_u8), k0.get("process_image")):
+        return None
+    from ..evaluate import load_planes_u8
+    return (load_planes_u8(fnames, imread4_u8),)
 
 
-attack_cover_batched = fabrika.precovers(iterator="batched", ignore_missing=True)(_split_attack_kw(attack_batch))
-attack_stego_batched = fabrika.stego_spatial(iterator="batched", ignore_missing=True)(_split_attack_kw(attack_batch))
+attack_cover_batched = fabrika.precovers(iterator="batched", ignore_missing=True)(fabrika.shared_kwargs(attack_batch, _ATTACK_KEYS, _prefetch_native))
+attack_stego_batched = fabrika.stego_spatial(iterator="batched", ignore_missing=True)(fabrika.shared_kwargs(attack_batch, _ATTACK_KEYS, _prefetch_native))
 
 
 def run(

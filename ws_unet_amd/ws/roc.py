@@ -149,35 +149,29 @@ def roc_table(df_roc):
 
 # ---- WS scores of every predictor from one decode ------------------------------------------------------------------------------
 
-_TAIL_KEYS = ("predictors",)
-
-
 def _prefetch(fnames, kws):
     from ..evaluate import load_planes_u8
     return (load_planes_u8(fnames),)
 
 
-def _submit(fnames, kws, prefetched=None):
+def _submit(fnames, clean, *, predictors, prefetched=None):
     """Upload the chunk once and queue every predictor's statistic (ws.estimate._stat) on it; nothing waits for the GPU.  A ragged
     chunk goes through ws.estimate.attack image by image, as ws.estimate.attack_batch does."""
-    from ..evaluate import load_planes_u8, mark_uploaded
+    from ..evaluate import load_planes_u8, upload_planes
     from . import estimate
-    preds = kws[0]["predictors"]
-    clean = [{k: v for k, v in kw.items() if k not in _TAIL_KEYS} for kw in kws]
     planes = prefetched[0] if prefetched is not None else load_planes_u8(fnames)
     if planes is None:
         proc = filters_lib.get_processor_2d((3,))
         return "host", [[estimate.attack(f, (3,), est, estimate.NAMED_FILTERS["AVG"], False, 0, imread4_u8, proc, **{**kw, "model_name": name})
-                         for name, est in preds] for f, kw in zip(fnames, clean)]
-    x = planes.to(estimate._device_of(preds[-1][1]), non_blocking=True)
-    mark_uploaded(planes)
+                         for name, est in predictors] for f, kw in zip(fnames, clean)]
+    x = upload_planes(planes, estimate._model_device(estimate.unet_model_of(predictors[-1][1])))
     betas = []
-    for _, est in preds:
+    for _, est in predictors:
         try:
             betas.append(estimate._stat(x, est, estimate.NAMED_FILTERS["AVG"], 0, False))
         except ValueError:                                   # ws.estimate.attack_batch: no estimate for this chunk
             betas.append(None)
-    return "device", (clean, [name for name, _ in preds], betas)
+    return "device", (clean, [name for name, _ in predictors], betas)
 
 
 def _collect(handle):
@@ -191,26 +185,14 @@ def _collect(handle):
     return [[{**kw, "model_name": name, "beta_hat": betas[p][i], **tail} for p, name in enumerate(names)] for i, kw in enumerate(clean)]
 
 
-def _score_chunk(fnames, kws, prefetched=None):
-    return _collect(_submit(fnames, kws, prefetched=prefetched))
+def _score_chunk(fnames, kws, prefetched=None, **shared):
+    return _collect(_submit(fnames, kws, prefetched=prefetched, **shared))
 
 
-_score_chunk.prefetch, _score_chunk.submit, _score_chunk.collect = _prefetch, _submit, _collect
+_score_chunk.submit, _score_chunk.collect = _submit, _collect
+_score_chunk = fabrika.shared_kwargs(_score_chunk, ("predictors",), _prefetch)
 _score_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(_score_chunk)
 _score_stegos = fabrika.stego_spatial(iterator="batched", convert_to=None, ignore_missing=True)(_score_chunk)
-
-
-def _unet_estimator(unet, mode):
-    import torch
-    from .estimate import UNetEstimator
-    if unet is None or isinstance(unet, UNetEstimator):
-        return unet
-    if isinstance(unet, torch.nn.Module):
-        return UNetEstimator(unet)
-    if isinstance(unet, tuple) and len(unet) == 2:
-        from .. import get_unet_estimator
-        return get_unet_estimator(model_path=unet[0], model_name=unet[1], channels=(3,), mode=mode)
-    raise ValueError(f"unet: a UNetEstimator, a model or (model_path, model_name), got {type(unet).__name__}")
 
 
 def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_METHODS, alphas: typing.Sequence[float] = ALPHAS,
@@ -228,7 +210,7 @@ def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_MET
         if name not in estimate.NAMED_FILTERS:
             raise ValueError(f"unknown filter {name!r}; choose from {sorted(estimate.NAMED_FILTERS)}")
     preds = [(name, filters_lib.get_filter_estimator(filter_name=name, flatten=False)) for name in names]
-    est = _unet_estimator(unet, mode)
+    est = estimate.as_unet_estimator(unet, mode)
     if est is not None:
         preds.append(("UNet", est))
     if not preds:
@@ -302,9 +284,9 @@ def main(argv=None) -> None:
     detectors = [load_scores(path, name, a.stego_methods, a.alphas) for path, name in a.scores]      # input errors before GPU work
     unet = None
     if a.model_dir:
-        from ..evaluate import get_model_name
-        model_dir = pathlib.Path(a.model_dir)
-        unet = (model_dir / a.train_method, get_model_name(stego_method=a.train_method, model_dir=model_dir))
+        from ..evaluate import trained_runs
+        (method, model_name, _), = trained_runs(a.model_dir, [a.train_method])
+        unet = (pathlib.Path(a.model_dir) / method, model_name)
     res = collect_ws_scores(a.data, a.stego_methods, a.alphas, a.filters, unet=unet, mode=a.mode, progress_on=a.progress)
     res = pd.concat([res] + detectors).reset_index(drop=True)
     res["stego_method"] = res["stego_method"].fillna("Cover")
