@@ -35,6 +35,14 @@ def test_header_symbols_are_exported_and_bound(lib):
     assert sorted(_lib.SIGNATURES) == syms, "ctypes signatures and header drifted apart"
 
 
+def test_library_exports_nothing_the_header_does_not_declare(lib):
+    """Diagnostic read-backs and helpers shared between translation units stay out of the export table: include/wsu.h is the whole ABI."""
+    r = subprocess.run(["nm", "-D", "--defined-only", str(ROOT / "ws_unet_amd" / "libwsu.so")], capture_output=True, text=True, check=True)
+    exported = {ln.split()[-1] for ln in r.stdout.splitlines() if ln.split() and ln.split()[-1].startswith("wsu_")}
+    assert len(exported) >= 15, r.stdout[-500:]
+    assert not sorted(exported - set(declared_symbols())), "exported by libwsu.so but not declared in wsu.h"
+
+
 def test_version_and_argument_errors_without_gpu(lib):
     assert lib.wsu_version() == 100
     assert lib.wsu_act_elem_size(0) == 4 and lib.wsu_act_elem_size(1) == 4 and lib.wsu_act_elem_size(2) == 2

@@ -110,6 +110,19 @@ def test_no_rn_intrinsic_in_the_sources():
     assert not bad, bad
 
 
+def test_the_library_reads_two_environment_variables_and_carries_no_timing_probe():
+    """A variable in someone's shell must not change what the product computes: the library reads the two organisation switches the GPU
+    suite pins (bitwise-equal results) and nothing else, and no timing-only switch, probe build or stamp buffer is left in its sources."""
+    csrc = ROOT / "ws_unet_amd" / "csrc"
+    sources = sorted(p for p in csrc.iterdir() if p.is_file() and (p.suffix in (".hip", ".h", ".cpp") or p.name == "Makefile"))
+    assert len(sources) >= 20, sources
+    names = {m for f in sources for m in re.findall(r'getenv\(\s*"?([^")]*)"?\s*\)', f.read_text())}
+    assert names == {"WSU_Q_ROWS", "WSU_PL_MSPLIT"}, names
+    bad = [f"{f.name}:{i + 1}" for f in sources for i, ln in enumerate(f.read_text().splitlines())
+           if re.search(r"ablate|WSU_PROBE|_STAMPS", ln)]
+    assert not bad, bad
+
+
 def test_metric_kernels_have_no_fused_multiply_add_outside_a_division(isa_files):
     """In every listed kernel the f32 FMAs are exactly those of its IEEE divisions: #FMA == k * #v_div_fixup_f32, with k read from
     lsb_delta_unit_kernel of the same build (one division, nothing else that could fuse)."""

@@ -1,5 +1,5 @@
 """Timing of single conv3x3_q layers (planar Q tensors, the default inference mode's 3x3 conv) on random and on all-zero operands, optionally with
-an alternative build of libwsu (WSU_LIB=...): the power-management measurement of profiles/r03 (tools/probe_units_pl.py) for the round-4 kernel.
+an alternative build of libwsu (WSU_LIB=...): the power-management measurement of profiles/r03 for the round-4 kernel.
 python tools/probe_q_layer.py [--zeros]"""
 import sys, time
 from pathlib import Path

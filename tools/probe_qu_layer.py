@@ -1,5 +1,5 @@
 """Timing of the fused decoder-block entry (ops.conv3x3_up_q, csrc/conv3x3_qu.hip) at unet_2's two shapes (batch 32 @ 512x512), beside the two-kernel
-path it replaces (convt2x2_pl -> conv3x3_q).  Environment: WSU_QU_ABLATE (timing-only ablations, results wrong), WSU_LIB.
+path it replaces (convt2x2_pl -> conv3x3_q).  Environment: WSU_LIB.
 python tools/probe_qu_layer.py [--zeros] [--no-two]"""
 import sys
 from pathlib import Path
@@ -36,8 +36,7 @@ for (name, n, sl, cl, c2, cout) in [("upconv3+d31", 32, 128, 256, 128, 128), ("u
     w_skip, w_low, bias = ops.pack_conv3x3_up(w3, wt, bt, b3)
     us = timed(lambda: ops.conv3x3_up_q(ql, qs, w_skip, w_low, bias, cout))
     fl = 2.0 * 9 * (cup + c2) * cout * n * (2 * sl) ** 2 + 2.0 * 4 * cl * cup * n * sl * sl
-    tag = f"ablate={os.environ.get('WSU_QU_ABLATE', '0')}{' zeros' if ZEROS else ''}"
-    line = f"{name} [{tag}]: fused {us:8.1f} us = {fl / us / 1e6:6.1f} TFLOP/s of the two reference ops"
+    line = f"{name}{' [zeros]' if ZEROS else ''}: fused {us:8.1f} us = {fl / us / 1e6:6.1f} TFLOP/s of the two reference ops"
     if "--no-two" not in sys.argv:
         al = planar_encode(xl)
         wpt, wp3 = ops.pack_convt2x2(wt, ops.mode_id("f16f8")), ops.pack_conv3x3_f4(w3)

@@ -1,4 +1,4 @@
-"""Transposed-conv layers of unet_2 at batch 32 in mode f16f8 (WSU_CONVT_TILE=2 selects the 2x32 tile): python tools/time_convt.py"""
+"""Transposed-conv layers of unet_2 at batch 32 in mode f16f8: python tools/time_convt.py"""
 import os, sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -19,4 +19,4 @@ for cin, cout, hw in ((256, 128, 128), (128, 64, 256)):
     for _ in range(10):
         ops.convt2x2(x, wp, b, cout, m)
     e.record(); torch.cuda.synchronize()
-    print(f"convT {cin}->{cout} @{hw} tile={os.environ.get('WSU_CONVT_TILE', '4')}: {s.elapsed_time(e) * 100:.0f} us", flush=True)
+    print(f"convT {cin}->{cout} @{hw}: {s.elapsed_time(e) * 100:.0f} us", flush=True)

@@ -1,5 +1,4 @@
-"""Per-layer timing of the planar weight-gradient kernel at the production shapes: python tools/time_wgrad.py  (WSU_WGRAD_ABLATE=1|2 for the
-timing-only variants: no matrix section / no staging after the first tile)."""
+"""Per-layer timing of the planar weight-gradient kernel at the production shapes: python tools/time_wgrad.py"""
 import os
 import sys
 

@@ -8,13 +8,13 @@
 // torch.autograd).  Everything is deterministic: fixed-order two-stage reductions, no float atomics.
 #include "wsu_device.h"
 
-extern "C" int wsu_conv3x3_launch_ex(const void* x1, const void* x2, const void* w_packed, const float* bias,
+WSU_INTERNAL int wsu_conv3x3_launch_ex(const void* x1, const void* x2, const void* w_packed, const float* bias,
                                      void* y, void* y2, int csplit, void* y_pool, uint8_t* pool_idx,
                                      const void* relu_mask, const void* relu_mask2,
                                      int n, int h, int w, int c1, int c2, int cout,
                                      int mode, int relu, int pad_zero, void* stream);
 
-extern "C" int wsu_conv3x3_pack_dgrad_swapped(const float* w_oihw, void* w_packed, int cin, int cout, int mode, void* stream);
+WSU_INTERNAL int wsu_conv3x3_pack_dgrad_swapped(const float* w_oihw, void* w_packed, int cin, int cout, int mode, void* stream);
 
 namespace {
 

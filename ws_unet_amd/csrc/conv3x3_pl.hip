@@ -64,8 +64,6 @@ struct PlArgs {
     const float* img; const float* w1; const float* b1;   // fused first layer (kernel variant F1): the 64 input channels are computed by the loaders
     int xres;                                             // 0: the inputs' residual plane (plane 2) is not used (kernel variant XRES = false)
     unsigned* range_flag;                                 // optional: bit 0 is set when a stored activation exceeds the encodable range (|x| > 448)
-    int ablate;                                           // timing-only experiments (WSU_PL_ABLATE, bits; results wrong when != 0): 1 = no DMA after step 0,
-                                                          // 2 = no epilogue (accumulators dropped), 8 = the loaders do not derive LDS plane 3
     // data-gradient variant (GRAD): zero padding, gradient encodings, no bias / ReLU; output chunks < nco1 go to y, the others to y2 (fused
     // concat: one gradient per source); mask / mask2 (optional, planar activations shaped like y / y2): the ReLU mask (x > 0) of the layer
     // that produced this conv's input, applied to the result; images n >= k * imgs_per_wset take weight set k (ring strips)
@@ -81,10 +79,6 @@ struct PlArgs {
 };
 
 struct Tile { int n, y0, x0, cb, mh; };                   // mh: the 32-channel half of block cb this item computes (kernel variant MSPLIT), else 0
-
-// Diagnostic stamps (only in the -DWSU_PL_STAMPS build): per workgroup the accumulated shader cycles of each phase of the chunk loop and
-// the s_memrealtime span, read back with wsu_debug_read_pl_stamps().  Values go to a buffer nothing else reads.
-__device__ unsigned long long g_pl_stamps[256 * 8];
 
 __device__ __forceinline__ Tile tile_of(const PlArgs& a, int t) {
     Tile r;
@@ -196,13 +190,6 @@ __device__ __forceinline__ void swap32(uint32_t& upper_of, uint32_t& lower_of) {
     upper_of = r[0]; lower_of = r[1];
 }
 
-// Stamps are compiled in only with -DWSU_PL_STAMPS (make probes -> libwsu_plstamp.so): in the product build STAMP() is empty.
-#ifdef WSU_PL_STAMPS
-#define STAMP(var) var = __builtin_amdgcn_s_memtime()
-#else
-#define STAMP(var) do {} while (0)
-#endif
-
 // ================= loader wave LW: the whole DMA of step j+1 right after the barrier that opens step j ====================================
 template <int LW, bool XRES, bool F1, bool GRAD, bool HONLY = false>
 __device__ __forceinline__ void pl_loader(const PlArgs& a, char* smem, int lane, int lw, int G, int J, int lw_rt = LW) {
@@ -212,11 +199,6 @@ __device__ __forceinline__ void pl_loader(const PlArgs& a, char* smem, int lane,
     float* s_w1 = reinterpret_cast<float*>(smem + LDS_F1);
     float* s_b1 = s_w1 + 9 * 64;
     unsigned char* s_mask = reinterpret_cast<unsigned char*>(smem + LDS_EXTRA);   // GRAD: [4 output chunks][2 f16 planes][512 px] bytes of 8 mask bits (the bias slot)
-    [[maybe_unused]] unsigned long long t_wait = 0, t_bar = 0, t_dma = 0, s0 = 0, s1 = 0, s2 = 0, s3 = 0, t0 = 0, rt0 = 0;     // stamps build only
-    STAMP(t0);
-#ifdef WSU_PL_STAMPS
-    rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
     unsigned voff[IN_PER_WAVE];
     Tile t = tile_of(a, lw);
     // ---- fused first layer (F1): the loaders COMPUTE the input planes of a step instead of fetching them -- relu(b1 + w1 * 3x3 window of
@@ -403,22 +385,19 @@ __device__ __forceinline__ void pl_loader(const PlArgs& a, char* smem, int lane,
     }
     int c = 0, kt = 0;
     for (int j = 0; j < J; ++j) {
-        STAMP(s0);
         static_assert(W_PER_WAVE == 9, "the vmcnt immediate below");
         if constexpr (!HONLY) {                                           // (f16 products only: LDS plane 3 is not used, nothing to derive)
         asm volatile("s_waitcnt vmcnt(9)" ::: "memory");                  // this wave's INPUT pieces of step j have landed (everything older than its
-        if (!(a.ablate & 8)) derive_x8(smem + (j & 1) * STAGE);           // 9 youngest operations: the weight pieces, or mask loads issued after them)
+        derive_x8(smem + (j & 1) * STAGE);                                // 9 youngest operations: the weight pieces, or mask loads issued after them)
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // ... its weight pieces (and the mask granules) too
         if (mask_pending) { mask_commit(); mask_pending = false; }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // ... and its derived / computed planes are written
-        STAMP(s1);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        STAMP(s2);
         const bool first_chunk = c == 0;
         const Tile tj = t;
-        if (j + 1 < J && !(a.ablate & 1)) {
+        if (j + 1 < J) {
             if (++c == a.nch) {
                 c = 0; ++kt;
                 t = tile_of(a, lw + kt * G);
@@ -428,19 +407,10 @@ __device__ __forceinline__ void pl_loader(const PlArgs& a, char* smem, int lane,
             f1_chunk(c, smem + ((j + 1) & 1) * STAGE);
         }
         if (GRAD && first_chunk) mask_issue(tj);
-        STAMP(s3);
-        t_wait += s1 - s0; t_bar += s2 - s1; t_dma += s3 - s2;
     }
     if constexpr (F1) {
         if (a.range_flag && __builtin_amdgcn_ballot_w64(!(f1_max <= WSU_F8_RANGE)) != 0 && lane == 0) atomicOr(a.range_flag, 1u);
     }
-#ifdef WSU_PL_STAMPS
-    if (lane == 0 && LW == 0 && blockIdx.x < 32) {
-        unsigned long long* d = g_pl_stamps + (blockIdx.x * 2 + 1) * 8;
-        d[0] = __builtin_amdgcn_s_memtime() - t0; d[1] = __builtin_amdgcn_s_memrealtime() - rt0;
-        d[2] = t_wait; d[3] = t_bar; d[4] = t_dma; d[5] = 0; d[6] = 0; d[7] = (unsigned long long)J;
-    }
-#endif
 }
 
 
@@ -498,13 +468,6 @@ void conv3x3_pl_kernel(const PlArgs a) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
-    [[maybe_unused]] unsigned long long t_wait = 0, t_bar = 0, t_dma = 0, t_mma = 0, t_epi = 0, t0 = 0, rt0 = 0;               // stamps build only
-    [[maybe_unused]] unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
-    STAMP(t0);
-#ifdef WSU_PL_STAMPS
-    rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-
     if (wv >= NWAVE) {
         // ================= loader waves (pl_loader<LW, ...>: the slot geometry of a wave is compile-time) ===========================
         if constexpr (F1) {
@@ -521,9 +484,6 @@ void conv3x3_pl_kernel(const PlArgs a) {
     }
 
     // ================= matrix waves ===================================================================================================
-#ifdef WSU_PL_MATRIX_PRIO
-    __builtin_amdgcn_s_setprio(WSU_PL_MATRIX_PRIO);                           // experiment: matrix waves above the loader wave of their SIMD
-#endif
     Tile cur = tile_of(a, lw);
     constexpr int MH = MSPLIT ? 1 : 2;                                        // accumulator tiles along the output channels
     f32x16 acc[2][2];                                                         // [MH][2] used (declared with the template-dependent bound, hipcc (ROCm 7.2)
@@ -536,18 +496,11 @@ void conv3x3_pl_kernel(const PlArgs a) {
     const char* ldsA = smem;                                                  // + ((tap*4 + g)*64 + m*32)*16   (HONLY: tap*2 + g)
     const char* ldsB = smem;                                                  // + g*PLANE + ((q+dy)*IW + dx)*16
     const int hh_q = hh;
-#if WSU_PROBE == 5
-    u32x4 sa0[2], sa1[2], sb0[2], sb1[2], sah[2], sbh[2];
-#endif
     auto begin_step = [&]() __attribute__((always_inline)) {
         // ---- step j: its DMA (issued by the loaders one step ago) has had a whole matrix section to land -----------------------
-        STAMP(s0);
-        STAMP(s1);
         __builtin_amdgcn_s_barrier();                                         // the loaders' pieces landed; everyone left the other stage
         asm volatile("" ::: "memory");
-        STAMP(s2);
         st = HONLY ? smem + (j % NSTAGE_H) * STAGE_H : smem + (j & 1) * STAGE;
-        STAMP(s3);
         ldsA = st + (HONLY ? LDS_IN_H : LDS_IN) + (cur.mh * 32 + l31) * 16;
         ldsB = st + ((2 * wv) * IW + l31) * 16;
     };
@@ -568,11 +521,6 @@ void conv3x3_pl_kernel(const PlArgs a) {
             const int aoff = ((hh_q ? t1 : t0) * 4 + 2) * 64 * 16;
             const int boff = 2 * PLANE + (hh_q ? ((t1 / 3) * IW + t1 % 3) : ((t0 / 3) * IW + t0 % 3)) * 16;
             u32x4 a0[2], a1[2], b0[2], b1[2];
-#if WSU_PROBE == 5                                                      // timing probe 5 (make probes): LDS fragments are read for the first group of a step only
-            if (tp == 0) {
-#else
-            {
-#endif
 _Pragma("unroll")
             for (int m = 0; m < MH; ++m) {
                 a0[m] = *reinterpret_cast<const u32x4*>(ldsA + aoff + m * 32 * 16);
@@ -583,12 +531,6 @@ _Pragma("unroll")
                 b0[q] = *reinterpret_cast<const u32x4*>(ldsB + boff + q * IW * 16);
                 b1[q] = *reinterpret_cast<const u32x4*>(ldsB + boff + PLANE + q * IW * 16);
             }
-#if WSU_PROBE == 5
-            for (int m = 0; m < 2; ++m) { sa0[m] = a0[m]; sa1[m] = a1[m]; sb0[m] = b0[m]; sb1[m] = b1[m]; }
-            } else { for (int m = 0; m < 2; ++m) { a0[m] = sa0[m]; a1[m] = sa1[m]; b0[m] = sb0[m]; b1[m] = sb1[m]; } }
-#else
-            }
-#endif
             if (single && hh) {
                 const u32x4 z = mk_u4(0, 0, 0, 0);
 _Pragma("unroll")
@@ -604,21 +546,10 @@ _Pragma("unroll")
             constexpr int tap = decltype(tap_c)::value, dy = tap / 3, dx = tap % 3;
             constexpr int ms = decltype(ms_c)::value, ML = ms < 0 ? 0 : ms, MU = ms < 0 ? MH : ms + 1;
             u32x4 ah[2], bh[2];
-#if WSU_PROBE == 5
-            if (tap == 0) {
-#else
-            {
-#endif
 _Pragma("unroll")
             for (int m = ML; m < MU; ++m) ah[m] = *reinterpret_cast<const u32x4*>(ldsA + ((tap * (HONLY ? 2 : 4) + hh) * 64 + m * 32) * 16);
 _Pragma("unroll")
             for (int q = 0; q < 2; ++q) bh[q] = *reinterpret_cast<const u32x4*>(ldsB + hh * PLANE + ((q + dy) * IW + dx) * 16);
-#if WSU_PROBE == 5
-            for (int m = 0; m < 2; ++m) { sah[m] = ah[m]; sbh[m] = bh[m]; }
-            } else { for (int m = 0; m < 2; ++m) { ah[m] = sah[m]; bh[m] = sbh[m]; } }
-#else
-            }
-#endif
 _Pragma("unroll")
             for (int m = ML; m < MU; ++m)
 _Pragma("unroll")
@@ -634,9 +565,7 @@ _Pragma("unroll")
             WSU_STATIC_FOR(9, tap, { main_term(std::integral_constant<int, tap>{}, all_m); });
         } else if constexpr (XRES) {
             WSU_STATIC_FOR(5, tp, {
-#if WSU_PROBE != 3                                                      // timing probe 3 (make probes): no cross terms at all = plain f16, 9 units
                 cross(std::integral_constant<int, tp>{});
-#endif
                 main_term(std::integral_constant<int, 2 * tp>{}, all_m);
                 if constexpr (2 * tp + 1 < 9) main_term(std::integral_constant<int, 2 * tp + 1>{}, all_m);
             });
@@ -824,48 +753,18 @@ _Pragma("unroll")
             ++kt;
             c = 0;
             if (j + 1 < J) cur = tile_of(a, lw + kt * G);
-#ifdef WSU_PL_STAMPS
-            t_epi += __builtin_amdgcn_s_memtime() - s4;
-#endif
         };
-        {
-            for (; j < J; ++j) {
-                begin_step();
-                if (c == 0) zero_acc();
-                units_all();
-                STAMP(s4);
-                t_wait += s1 - s0; t_bar += s2 - s1; t_dma += s3 - s2; t_mma += s4 - s3;
-                if (c + 1 == a.nch && (a.ablate & 2)) {                        // timing only: the tile's results are dropped (kept alive for the compiler)
-#pragma unroll
-                    for (int m = 0; m < MH; ++m)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) asm volatile("" :: "v"(acc[m][q]));
-                    ++kt; c = 0;
-                    if (j + 1 < J) cur = tile_of(a, lw + kt * G);
-                } else if (c + 1 == a.nch) {
-                    finish_tile();
-                } else {
-                    ++c;
-                }
-            }
+        for (; j < J; ++j) {
+            begin_step();
+            if (c == 0) zero_acc();
+            units_all();
+            if (c + 1 == a.nch) finish_tile(); else ++c;
         }
     }
-#ifdef WSU_PL_STAMPS
-    if (lane == 0 && blockIdx.x >= 64 && blockIdx.x < 128) g_pl_stamps[(blockIdx.x * 2) * 8 + wv] = t_bar;          // per-wave barrier waits / section times
-    if (lane == 0 && blockIdx.x >= 32 && blockIdx.x < 64) g_pl_stamps[(blockIdx.x * 2) * 8 + wv] = t_mma;
-    if (tid == 64 && blockIdx.x < 32) {                                        // matrix wave 1's view
-        unsigned long long* d = g_pl_stamps + (blockIdx.x * 2) * 8;
-        d[0] = __builtin_amdgcn_s_memtime() - t0; d[1] = __builtin_amdgcn_s_memrealtime() - rt0;
-        d[2] = t_wait; d[3] = t_bar; d[4] = t_dma; d[5] = t_mma; d[6] = t_epi; d[7] = (unsigned long long)J;
-    }
-#endif
 }
 
 // one place that knows the instantiations: attributes once, then the variant the arguments select
 int pl_launch(PlArgs a, bool first, hipStream_t s, bool grad = false) {
-    static int ablate = -1;
-    if (ablate < 0) { const char* e = getenv("WSU_PL_ABLATE"); ablate = e ? atoi(e) : 0; }
-    a.ablate = ablate;
     static int ncu = 0;
     if (ncu == 0) {
         int dev = 0; hipDeviceProp_t prop;
@@ -911,12 +810,6 @@ int pl_launch(PlArgs a, bool first, hipStream_t s, bool grad = false) {
 }  // namespace
 
 extern "C" {
-
-// diagnostic only (rows alternate: matrix wave 1, loader wave 8 of workgroups 0..127) (not part of include/wsu.h): phase stamps of the last conv3x3_pl launch with WSU_PL_STAMP=1
-int wsu_debug_read_pl_stamps(unsigned long long* host_dst, int nblocks) {
-    if (nblocks > 256) nblocks = 256;
-    return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_pl_stamps), (size_t)nblocks * 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : -2;
-}
 
 size_t wsu_relu_mask_bytes(int n, int c, int h, int w) {
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return 0;
@@ -1001,8 +894,8 @@ size_t wsu_conv3x3_pl_bwd_data_workspace_bytes(int n, int h, int w, int cin, int
     return (size_t)4 * n * (L + 2) * 3 * (size_t)(cin + cout);
 }
 
-int wsu_ring_gather_pl(const void* g, void* strips, int n, int h, int w, int c, int L, void* stream);
-int wsu_ring_fold_pl(const void* strips_out, void* dx1, void* dx2, const void* mask1, const void* mask2,
+WSU_INTERNAL int wsu_ring_gather_pl(const void* g, void* strips, int n, int h, int w, int c, int L, void* stream);
+WSU_INTERNAL int wsu_ring_fold_pl(const void* strips_out, void* dx1, void* dx2, const void* mask1, const void* mask2,
                      int n, int h, int w, int cin, int csplit, int L, int gres, void* stream);
 
 int wsu_conv3x3_pl_bwd_data(const void* g, const void* w_packed_dgrad, const void* w_packed_ring, void* workspace, size_t workspace_bytes,

@@ -24,22 +24,6 @@
 #include "wsu_device.h"
 #include <cstdlib>
 
-#ifndef WSU_Q_EPO
-#define WSU_Q_EPO 1             // 1 = the last step of a tile is split by accumulator tile and its second half shares a basic block with the first half of the epilogue
-#endif
-#ifndef WSU_Q_PIPE2
-#define WSU_Q_PIPE2 0           // experiment: 1 = the eight-wave organisation (RQ = 2) also issues the fragment reads of unit u + 1 before the matrix instructions of unit u
-#endif
-#ifndef WSU_Q_PIPE_DEPTH
-#define WSU_Q_PIPE_DEPTH 1      // units of fragment reads in flight in front of the matrix instructions that use them (explicit pipeline)
-#endif
-#ifndef WSU_Q_PROBE_NOX8
-#define WSU_Q_PROBE_NOX8 0      // timing-only probe (results wrong; make qnox8): 1 = the half-empty fp4 instruction of the unpaired ninth tap is skipped
-#endif                          // (profiles/r04/ab_forward_organisations.md, third A/B: the time follows the ENERGY of the useful products)
-#ifndef WSU_Q_EPO_FENCE
-#define WSU_Q_EPO_FENCE 1       // 1 = one scheduling region per hook of that block (RQ = 4: without the fences the scheduler hoists the fragment reads of all five tap
-#endif                          //     pairs above the epilogue and spills 60-70 registers)
-
 namespace {
 
 constexpr int TW = 32, TH = 16, IW = TW + 2, IH = TH + 2;
@@ -83,7 +67,6 @@ struct QArgs {
     int ntiles;                                           // n * tiles_y * tiles_x * ncb
     unsigned* range_flag;
     int msplit;                                           // 1: work items are half-blocks of 32 output channels (kernel variant MSPLIT); ncb = 2 * cout / 64
-    int ablate;                                           // timing-only experiments (WSU_PL_ABLATE bits; results wrong when != 0): 1 = no DMA after step 0, 2 = no epilogue
     const float* img; const float* w1; const float* b1;   // fused first layer (kernel variant F1): the 64 input channels are computed by the loader waves; w1 = tap-major [9][64]
 };
 
@@ -173,12 +156,10 @@ __device__ __forceinline__ void q_loader(const QArgs& a, char* smem, int lane, i
         __builtin_amdgcn_s_barrier();                                 // barrier j: step j is complete in LDS; every matrix wave has left step j - 1
         asm volatile("" ::: "memory");
         if (j + 1 >= J) break;
-        if (!(a.ablate & 1)) {
-            issue_w(j + 1);                                           // its slot held step j - 1
-            const bool more = j + 2 < J;
-            if (more) issue_in(j + 2);                                // its slot held step j - 1
-            if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NIN_OPS) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        issue_w(j + 1);                                               // its slot held step j - 1
+        const bool more = j + 2 < J;
+        if (more) issue_in(j + 2);                                    // its slot held step j - 1
+        if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NIN_OPS) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
 }
 
@@ -191,7 +172,6 @@ __device__ __forceinline__ void q_loader(const QArgs& a, char* smem, int lane, i
 // index (four inlined copies beside the matrix waves' code cost the e4m3 kernel of round 2 ~160 spilled registers).
 __device__ __forceinline__ void q_loader_f1(const QArgs& a, char* smem, int lane, int lw, int G, int J, int lw8) {
     if (J <= 0) return;
-    if (a.ablate & 16) __builtin_amdgcn_s_setprio(3);                 // experiment (WSU_Q_F1_PRIO=1): the computing loaders' instructions ahead of the matrix waves'
     lds_char* smem3 = (lds_char*)smem;
     constexpr int F1_PX = 3;                                          // segments lw8, lw8 + 4, lw8 + 8 (< 10)
     float pimg[F1_PX][9];
@@ -340,8 +320,8 @@ void conv3x3_q_kernel(const QArgs a) {
     // ================= matrix waves ===================================================================================================
     Tile cur = tile_of(a, lw);
     constexpr int MH = MSPLIT ? 1 : 2;                                        // accumulator tiles along the output channels
-    constexpr bool PIPE = (RQ == 4 || WSU_Q_PIPE2) && !H;                     // explicit software pipeline of the fragment reads (below)
-    constexpr bool EPO = WSU_Q_EPO && !MSPLIT && HC == 0 && RQ != 4;
+    constexpr bool PIPE = RQ == 4 && !H;                                        // explicit software pipeline of the fragment reads (below)
+    constexpr bool EPO = !MSPLIT && HC == 0 && RQ != 4;                       // the last step of a tile is split by accumulator tile: its second half shares a basic block with the first half of the epilogue
     f32x16 acc[2][4];                                                         // [MH][RQ] used (fixed bounds: a template-dependent bound made hipcc (ROCm 7.2) drop the host stubs)
     int kt = 0, j = 0;
     unsigned q_in_off = 0, q_w_off = 0;                                       // this step's input / weight slot
@@ -422,7 +402,7 @@ _Pragma("unroll")
         if constexpr (EPO) asm volatile("" : "+v"(hh_q));                     // (per call: the paths of a step must not share -- and hoist -- their lane offsets)
         WSU_STATIC_FOR(hi - lo, i, {
             constexpr int tp = lo + i;
-            if constexpr (!H && !(WSU_Q_PROBE_NOX8 && tp == 4)) cross_q4(std::integral_constant<int, tp>{}, ms_c);
+            if constexpr (!H) cross_q4(std::integral_constant<int, tp>{}, ms_c);
             main_term(std::integral_constant<int, 2 * tp>{}, ms_c);
             if constexpr (2 * tp + 1 < 9) main_term(std::integral_constant<int, 2 * tp + 1>{}, ms_c);
         });
@@ -490,13 +470,13 @@ _Pragma("unroll")
         }
     };
     auto units_pipelined = [&]() __attribute__((always_inline)) {
-        constexpr int NU = 14, D = WSU_Q_PIPE_DEPTH, NS = D + 1;              // D units of reads in flight, NS fragment sets
-        Frag fr[NS];
-        WSU_STATIC_FOR(D, u, { load_unit(u_c, fr[u % NS]); });
+        constexpr int NU = 14;                                                // one unit of reads in flight, two fragment sets
+        Frag fr[2];
+        load_unit(std::integral_constant<int, 0>{}, fr[0]);
         WSU_STATIC_FOR(NU, u, {
-            if constexpr (u + D < NU) load_unit(std::integral_constant<int, u + D>{}, fr[(u + D) % NS]);
+            if constexpr (u + 1 < NU) load_unit(std::integral_constant<int, u + 1>{}, fr[(u + 1) % 2]);
             __builtin_amdgcn_sched_barrier(0);                                // (the reads FIRST: left to itself the scheduler sinks them behind most of the unit's matrix instructions)
-            mma_unit(u_c, fr[u % NS]);
+            mma_unit(u_c, fr[u % 2]);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
@@ -671,10 +651,8 @@ _Pragma("unroll")
             epi_m(std::integral_constant<int, 0>{}, [&](auto h_c) __attribute__((always_inline)) {
                 constexpr int h = decltype(h_c)::value;
                 constexpr int lo = 5 * h / NHT, hi = 5 * (h + 1) / NHT;
-                if constexpr (WSU_Q_EPO_FENCE && RQ == 4) __builtin_amdgcn_sched_barrier(0);
                 if constexpr (hi > lo) units_range(std::integral_constant<int, 1>{}, std::integral_constant<int, lo>{}, std::integral_constant<int, hi>{});
             });
-            if constexpr (WSU_Q_EPO_FENCE && RQ == 4) __builtin_amdgcn_sched_barrier(0);
             epi_m(std::integral_constant<int, 1>{}, nothing);
         } else {
             WSU_STATIC_FOR(MH, m, { (void)m; epi_m(m_c, nothing); });
@@ -714,17 +692,10 @@ _Pragma("unroll")
         begin_step();
         if constexpr (EPO) units_all(std::integral_constant<int, 0>{});       // the last step: m = 0 first; m = 1 follows inside the epilogue
         else units_all(all_m);
-        if (a.ablate & 2) {                                                   // timing only: the tile's results are dropped (kept alive for the compiler)
-            if constexpr (EPO) units_all(std::integral_constant<int, 1>{});
-#pragma unroll
-            for (int m = 0; m < MH; ++m)
-#pragma unroll
-                for (int q = 0; q < RQ; ++q) asm volatile("" :: "v"(acc[m][q]));
-            ++kt;
-            if (j + 1 < J) cur = tile_of(a, lw + kt * G);
-        } else {
-            finish_tile();
-        }
+        // scheduling fence between the tile's last step and its epilogue: scheduled as one region the eight-wave instantiations <2, 0, *, *, false, ...>
+        // take 168 registers and spill 1-3 of them; with the fence 133-147 and none (a timing-only branch stood here and ended the block: 162-164)
+        __builtin_amdgcn_sched_barrier(0);
+        finish_tile();
         ++j;
     }
 }
@@ -906,9 +877,7 @@ int wsu_conv3x3_q_fused_first_fwd(const float* img, const float* w1_taps, const 
     a.range_flag = range_flag;
     a.n = n; a.h = h; a.w = w; a.c1 = 64; a.c2 = 0; a.cout = cout;
     a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ncb = cout / WSU_COB;
-    static int prio = -1;
-    if (prio < 0) { const char* e = getenv("WSU_Q_F1_PRIO"); prio = (e && atoi(e)) ? 1 : 0; }
-    a.nch1 = 4; a.nch = 4; a.relu = relu; a.msplit = 0; a.ablate = prio ? 16 : 0;
+    a.nch1 = 4; a.nch = 4; a.relu = relu; a.msplit = 0;
     a.img = img; a.w1 = w1; a.b1 = b1;
     const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
     WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_q_fused_first: %lld tiles out of range", nt);
@@ -964,7 +933,7 @@ int wsu_conv3x3_q_fwd(const void* x1, const void* x2, const void* w_packed_f4, c
     const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
     WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_q: %lld tiles out of range", nt);
     a.ntiles = (int)nt;
-    static int ncu = 0, rq = 0, msplit_on = 1, ablate = 0;
+    static int ncu = 0, rq = 0, msplit_on = 1;
     if (ncu == 0) {
         int dev = 0; hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
@@ -972,10 +941,8 @@ int wsu_conv3x3_q_fwd(const void* x1, const void* x2, const void* w_packed_f4, c
         }
         const char* e = getenv("WSU_Q_ROWS"); rq = (e && atoi(e) == 4) ? 4 : 2;       // experiment switch: 4 = four matrix waves (one per SIMD) x four rows
         e = getenv("WSU_PL_MSPLIT"); msplit_on = e ? atoi(e) : 1;
-        e = getenv("WSU_PL_ABLATE"); ablate = e ? atoi(e) : 0;
         ncu = prop.multiProcessorCount;
     }
-    a.ablate = ablate;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return rq != 4 ? q_launch_rq<2>(a, y_format == WSU_PLANAR_Q, s, ncu, msplit_on != 0) : q_launch_rq<4>(a, y_format == WSU_PLANAR_Q, s, ncu, msplit_on != 0);
 }
@@ -1026,17 +993,15 @@ int wsu_conv3x3_h_fwd(const void* x1, const void* x2, const void* w_packed_h, co
     const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
     WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_h: %lld tiles out of range", nt);
     a.ntiles = (int)nt;
-    static int ncu = 0, msplit_on = 1, ablate = 0;
+    static int ncu = 0, msplit_on = 1;
     if (ncu == 0) {
         int dev = 0; hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
             wsu_set_error("conv3x3_h: cannot query the device"); return WSU_ERR_HIP;
         }
         const char* e = getenv("WSU_PL_MSPLIT"); msplit_on = e ? atoi(e) : 1;
-        e = getenv("WSU_PL_ABLATE"); ablate = e ? atoi(e) : 0;
         ncu = prop.multiProcessorCount;
     }
-    a.ablate = ablate;
     return h_launch(a, static_cast<hipStream_t>(stream), ncu, msplit_on != 0);
 }
 

@@ -27,7 +27,6 @@
 // scale pieces), Wc rounded to f16 once; the same two step regions, each step's allocations smaller (skip input 19.1 KB, weights 18 KB; low
 // input 10.3 KB, a dy slice of a low chunk's weights 16 KB).
 #include "wsu_device.h"
-#include <cstdlib>
 
 namespace {
 
@@ -72,7 +71,6 @@ struct UArgs {
     int tiles_x, tiles_y, ltiles_x, ncb, nchS, nchL;
     int relu, ntiles;
     unsigned* range_flag;
-    int ablate;                                           // timing-only experiments (WSU_QU_ABLATE bits; results wrong when != 0): 1 = no DMA after the first allocations, 2 = no epilogue; 4 = loader waves at priority 3 (results right), 8 = low inputs from one cached tile, 16 = half of the low weights' pieces
 };
 
 struct Tile { int n, y0, x0, cb; };
@@ -104,16 +102,6 @@ __device__ __forceinline__ void wait_vm(int n) {
 // Steps of a tile: nchS skip chunks (kind S), then one step per low chunk (kind L).  Everything of a step dies with the step, so the region
 // step j - 1 leaves at barrier j takes step j + 1.
 
-// Diagnostic stamps (only in the -DWSU_QU_STAMPS build, `make qustamp`; tools/stamp_qu.py): per workgroup < 256 the accumulated shader cycles
-// of matrix wave 0 and loader wave 0 per step kind, read back with wsu_debug_read_qu_stamps().  Values go to a buffer nothing else reads.
-#ifdef WSU_QU_STAMPS
-constexpr int QU_NST = 16;
-__device__ unsigned long long g_qu_stamps[256 * QU_NST];
-#define QU_STAMP(v) v = __builtin_amdgcn_s_memtime()
-#else
-#define QU_STAMP(v) do {} while (0)
-#endif
-
 // ================= loader wave LW: pure DMA, walks the allocation sequence ahead of the matrix waves ==========================================
 // Format H: two input pieces per segment; skip weights 3 / 3 / 6 / 6 pieces, low weights 3 / 3 / 5 / 5 per dy slice (the low input: 4 / 4 / 2 / 2).
 template <int FMT, int LW>
@@ -142,8 +130,7 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
             const int idx = min((LW + NLOAD * k) * 64 + lane, NPIX_S - 1);
             const int p = idx / CPIX, rem = idx - p * CPIX;
             const int lr = rem / CW, lc = rem - lr * CW;
-            int yy = wsu_reflect(t.y0 - 1 + 2 * lr + (p >> 1), a.h), xx = wsu_reflect(t.x0 - 1 + 2 * lc + (p & 1), a.w);
-            if (a.ablate & 32) { yy = wsu_reflect(t.y0 - 1 + idx / 34, a.h); xx = wsu_reflect(t.x0 - 1 + idx % 34, a.w); }      // (32: the natural row-major tile -- no gather; results wrong)
+            const int yy = wsu_reflect(t.y0 - 1 + 2 * lr + (p >> 1), a.h), xx = wsu_reflect(t.x0 - 1 + 2 * lc + (p & 1), a.w);
             voS[k] = (unsigned)(yy * a.w + xx) * 16u;
             if constexpr (!H) soS[k] = 3u * hw16 + wsu_q_soff(yy, xx, a.tiles_x);
         });
@@ -163,10 +150,7 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
     auto issue_alloc = [&](lds_char* slot) __attribute__((always_inline)) {
         int nops;
         const bool is_in = a_low ? a_r == 1 : a_r == 0;
-        const int skip_kind = a.ablate >> 8;                                 // 0x100 IN_S, 0x200 W_S, 0x400 IN_L, 0x800 W_L: that kind is not fetched (timing only)
-        if (skip_kind & (is_in ? (a_low ? 4 : 1) : (a_low ? 8 : 2))) {
-            nops = 0;
-        } else if (is_in && !a_low) {
+        if (is_in && !a_low) {
             const char* src = a.xs + ((size_t)at.n * a.nchS + a_c) * cbytes_s;
             const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(src), 0, (int)cbytes_s, 0x00020000);
             WSU_STATIC_FOR(NSS, k, {
@@ -182,7 +166,7 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
             });
             nops = OPS_INS;
         } else if (is_in) {
-            const char* src = (a.ablate & 8) ? a.xl : a.xl + ((size_t)at.n * a.nchL + a_c) * cbytes_l;      // (8: every low input from image 0, chunk 0 -- cache hits)
+            const char* src = a.xl + ((size_t)at.n * a.nchL + a_c) * cbytes_l;
             const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(src), 0, (int)cbytes_l, 0x00020000);
             WSU_STATIC_FOR(NSL, k, {
                 constexpr int seg = LW + NLOAD * k;
@@ -207,19 +191,11 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
         } else {
             const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.wpl), 0, 0x7FFFFFF0, 0x00020000);
             const int base = ((at.cb * a.nchL + a_c) * 2 + (a_r == 2 ? 1 : 0)) * WSLICE_L;
-            if (a.ablate & 16) {                                          // (16: half of the low weights' pieces)
-                WSU_STATIC_FOR((NWL + 1) / 2, k, {
-                    constexpr int piece = WL0 + 2 * k;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + piece * 1024), 16, (unsigned)lane * 16u, base + piece * 1024, 0, 0);
-                });
-                nops = (NWL + 1) / 2;
-            } else {
-                WSU_STATIC_FOR(NWL, k, {
-                    constexpr int piece = WL0 + k;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + piece * 1024), 16, (unsigned)lane * 16u, base + piece * 1024, 0, 0);
-                });
-                nops = NWL;
-            }
+            WSU_STATIC_FOR(NWL, k, {
+                constexpr int piece = WL0 + k;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(slot + piece * 1024), 16, (unsigned)lane * 16u, base + piece * 1024, 0, 0);
+            });
+            nops = NWL;
         }
         return nops;
     };
@@ -243,41 +219,18 @@ __device__ __forceinline__ void u_loader(const UArgs& a, char* smem, int lane, i
         return nops;
     };
     plan(at);
-#ifdef WSU_QU_STAMPS
-    unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_rt0 = __builtin_amdgcn_s_memrealtime(), st_a, st_b, st_c;
-    unsigned long long st_wait[2] = {0, 0}, st_bar[2] = {0, 0}, st_issue = 0;
-    int st_kind = 0;                                                      // kind of the step the next barrier opens (0 S, 1 L)
-#endif
     {
         issue_step();                                                     // steps 0 and 1: both regions are free
         const int n1 = J > 1 ? issue_step() : 0;
         wait_vm(n1);
     }
     for (int j = 0; ; ++j) {
-        QU_STAMP(st_a);
         __builtin_amdgcn_s_barrier();                                     // barrier j: step j is complete in LDS; every matrix wave has left step j - 1
         asm volatile("" ::: "memory");
-        QU_STAMP(st_b);
-#ifdef WSU_QU_STAMPS
-        st_bar[st_kind] += st_b - st_a;
-#endif
         if (j + 1 >= J) break;
-        if (j >= 1 && !(a.ablate & 1)) issue_step();                      // step j + 1 into the region step j - 1 has left
-        QU_STAMP(st_c);
+        if (j >= 1) issue_step();                                         // step j + 1 into the region step j - 1 has left
         wait_vm(0);                                                       // step j + 1 has landed
-#ifdef WSU_QU_STAMPS
-        st_kind = (j + 1) % T >= a.nchS;                                  // step j + 1 inside its tile
-        QU_STAMP(st_a);
-        st_issue += st_c - st_b; st_wait[st_kind] += st_a - st_c;
-#endif
     }
-#ifdef WSU_QU_STAMPS
-    if (lane == 0 && LW == 0 && blockIdx.x < 256) {
-        unsigned long long* d = g_qu_stamps + blockIdx.x * QU_NST;
-        d[8] = st_wait[0]; d[9] = st_wait[1]; d[10] = st_bar[0]; d[11] = st_bar[1]; d[12] = st_issue;
-        d[13] = __builtin_amdgcn_s_memrealtime() - st_rt0; d[14] = __builtin_amdgcn_s_memtime() - st_t0; d[15] = (unsigned long long)J;
-    }
-#endif
 }
 
 // FMT: storage format of x_low, x_skip and y -- WSU_PLANAR_Q (mode 'f16f4p') or WSU_PLANAR_H (mode 'f16p': the f16 products alone)
@@ -296,7 +249,6 @@ void conv3x3_qu_kernel(const UArgs a) {
     for (int i = tid; i < a.cout; i += NT) s_bias[i] = a.bias ? a.bias[i] : 0.f;
 
     if (wv >= NWAVE) {
-        if (a.ablate & 4) __builtin_amdgcn_s_setprio(3);                       // experiment: the loaders' DMA instructions issue ahead of the matrix waves' streams
         switch (wv - NWAVE) {
             case 0: u_loader<FMT, 0>(a, smem, lane, lw, G, K); break;
             case 1: u_loader<FMT, 1>(a, smem, lane, lw, G, K); break;
@@ -322,25 +274,11 @@ void conv3x3_qu_kernel(const UArgs a) {
     typedef __attribute__((address_space(3))) const int lds_cint;
     typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
     lds_char* L = (lds_char*)smem;
-#ifdef WSU_QU_STAMPS
-    unsigned long long st_a, st_b, st_step[2] = {0, 0}, st_bar[2] = {0, 0}, st_epi = 0, st_t0 = __builtin_amdgcn_s_memtime();
-    int st_n[2] = {0, 0};
-#endif
-    auto sync_step = [&](int kind) __attribute__((always_inline)) {       // kind of the step the barrier opens: 0 S, 1 L (stamps only)
-        QU_STAMP(st_a);
+    auto sync_step = [&]() __attribute__((always_inline)) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        QU_STAMP(st_b);
-#ifdef WSU_QU_STAMPS
-        st_bar[kind] += st_b - st_a; ++st_n[kind];
-#endif
         hh_q = hh;
         asm volatile("" : "+v"(hh_q));
-    };
-    auto step_done = [&](int kind) __attribute__((always_inline)) {       // (stamps only) the step's matrix section, from its barrier on
-#ifdef WSU_QU_STAMPS
-        QU_STAMP(st_a); st_step[kind] += st_a - st_b;
-#endif
     };
     // byte offset of tap (ky, kx)'s source pixel relative to the lane's own class pixel, in the class planes of the skip tile
     auto tap_s = [&](int ky, int kx) __attribute__((always_inline)) {
@@ -485,43 +423,23 @@ _Pragma("unroll")
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][q][r] = 0.f;
         for (int c = 0; c < a.nchS; ++c) {
-            sync_step(0);
+            sync_step();
             const unsigned r = next_region();
             in_off = r; w_off = r + OFF_SW;
             skip_units();
-            step_done(0);
         }
         for (int c = 0; c < a.nchL; ++c) {                                    // one step: dy = 0 then dy = 1, the accumulation order of the two-kernel path
-            sync_step(1);
+            sync_step();
             const unsigned r = next_region();
             in_off = r + OFF_LIN;
             w_off = r;
             low_units(0);
             w_off = r + OFF_LW1;
             low_units(1);
-            step_done(1);
         }
-        QU_STAMP(st_a);
-        if (a.ablate & 2) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) asm volatile("" :: "v"(acc[m][q]));
-        } else {
-            finish_tile();
-        }
-#ifdef WSU_QU_STAMPS
-        QU_STAMP(st_b); st_epi += st_b - st_a;
-#endif
+        finish_tile();
         if (t + 1 < K) cur = tile_of(a, lw + (t + 1) * G);
     }
-#ifdef WSU_QU_STAMPS
-    if (lane == 0 && wv == 0 && blockIdx.x < 256) {
-        unsigned long long* d = g_qu_stamps + blockIdx.x * QU_NST;
-        d[0] = st_step[0]; d[1] = st_step[1]; d[2] = st_bar[0]; d[3] = st_bar[1]; d[4] = st_epi;
-        d[5] = (unsigned long long)st_n[0]; d[6] = (unsigned long long)st_n[1]; d[7] = __builtin_amdgcn_s_memtime() - st_t0;
-    }
-#endif
 }
 
 // ---- packing of the low half: one thread per (block, low chunk, dy, class, dx, co) forms its 16 combined weights in fp32 (ci outer, then ky, kx,
@@ -604,14 +522,6 @@ __global__ void up_bias_kernel(const float* __restrict__ w3, const float* __rest
 
 extern "C" {
 
-#ifdef WSU_QU_STAMPS
-// stamps of the last conv3x3_qu launch (-DWSU_QU_STAMPS build only): per workgroup < nblocks, QU_NST values (tools/stamp_qu.py names them)
-int wsu_debug_read_qu_stamps(unsigned long long* host_dst, int nblocks) {
-    if (nblocks > 256) nblocks = 256;
-    return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_qu_stamps), sizeof(unsigned long long) * QU_NST * nblocks, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
-}
-#endif
-
 // Bytes of the packed low half: per (64-co block, 16-channel chunk of x_low, dy) one 25 KB slice [class 4][dx 2][plane 3][64 co][16 B] + [8][64] scale bytes.
 size_t wsu_conv3x3_up_packed_bytes(int cl, int cout) {
     if (cl <= 0 || cout <= 0 || cl % 16 || cout % WSU_COB) return 0;
@@ -657,9 +567,8 @@ int wsu_conv3x3_up_q_fwd(const void* x_low, const void* x_skip, const void* w_sk
     WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_up_q: %lld tiles out of range", nt);
     WSU_REQUIRE((long long)a.ncb * a.nchL * 2 * W_L < 0x7FFFFFF0LL && (long long)a.ncb * a.nchS * W_S < 0x7FFFFFF0LL, "conv3x3_up_q: packed weights beyond 2 GiB");
     a.ntiles = (int)nt;
-    static int ncu = 0, ablate = 0;
+    static int ncu = 0;
     if (ncu == 0) {
-        const char* ev = getenv("WSU_QU_ABLATE"); ablate = ev ? atoi(ev) : 0;
         int dev = 0; hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
             wsu_set_error("conv3x3_up_q: cannot query the device"); return WSU_ERR_HIP;
@@ -668,7 +577,6 @@ int wsu_conv3x3_up_q_fwd(const void* x_low, const void* x_skip, const void* w_sk
         if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_qu): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
         ncu = prop.multiProcessorCount;
     }
-    a.ablate = ablate;
     hipLaunchKernelGGL(conv3x3_qu_kernel<WSU_PLANAR_Q>, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3(NT), LDS_TOTAL, static_cast<hipStream_t>(stream), a);
     return wsu_check_launch("conv3x3_qu_kernel");
 }
@@ -713,9 +621,8 @@ int wsu_conv3x3_up_h_fwd(const void* x_low, const void* x_skip, const void* w_sk
     WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_up_h: %lld tiles out of range", nt);
     WSU_REQUIRE((long long)a.ncb * a.nchL * 2 * W_L_H < 0x7FFFFFF0LL && (long long)a.ncb * a.nchS * W_S_H < 0x7FFFFFF0LL, "conv3x3_up_h: packed weights beyond 2 GiB");
     a.ntiles = (int)nt;
-    static int ncu = 0, ablate = 0;
+    static int ncu = 0;
     if (ncu == 0) {
-        const char* ev = getenv("WSU_QU_ABLATE"); ablate = ev ? atoi(ev) : 0;
         int dev = 0; hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
             wsu_set_error("conv3x3_up_h: cannot query the device"); return WSU_ERR_HIP;
@@ -724,7 +631,6 @@ int wsu_conv3x3_up_h_fwd(const void* x_low, const void* x_skip, const void* w_sk
         if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_qu<H>): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
         ncu = prop.multiProcessorCount;
     }
-    a.ablate = ablate;
     hipLaunchKernelGGL(conv3x3_qu_kernel<WSU_PLANAR_H>, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3(NT), LDS_TOTAL, static_cast<hipStream_t>(stream), a);
     return wsu_check_launch("conv3x3_qu_kernel<H>");
 }

@@ -8,7 +8,6 @@
 // interleaves the 4 sub-position tiles into a [4 x 64 output pixels][64 co] LDS tile so that the NHWC
 // stores are whole 16-byte pieces of contiguous output rows.
 #include "wsu_device.h"
-#include <cstdlib>
 
 namespace {
 
@@ -549,11 +548,7 @@ int wsu_convt2x2_fwd(const void* x, const void* w_packed, const float* bias, voi
     if (mode == WSU_MODE_F32) return launch_ct<WSU_MODE_F32>(a, s);
     if (presplit) return launch_ct<WSU_MODE_BF16X3, true>(a, s);
     if (f16f8x) return launch_ct<WSU_MODE_F16F8, false>(a, s);
-    if (mode == WSU_MODE_F16F8) {
-        static int small = -1;                                    // WSU_CONVT_TILE=2: the 2 x 32 tile of the generic kernel (A/B runs)
-        if (small < 0) { const char* e = getenv("WSU_CONVT_TILE"); small = (e && e[0] == '2') ? 1 : 0; }
-        return small ? launch_ct<WSU_MODE_F16F8, true>(a, s) : launch_ct_f16f8(a, s);
-    }
+    if (mode == WSU_MODE_F16F8) return launch_ct_f16f8(a, s);
     if (mode == WSU_MODE_BF16X3) return launch_ct<WSU_MODE_BF16X3>(a, s);
     return launch_ct<WSU_MODE_BF16>(a, s);
 }

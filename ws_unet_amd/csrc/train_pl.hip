@@ -430,12 +430,12 @@ inline unsigned grid_for(long long total) { return (unsigned)((total + 255) / 25
 }  // namespace
 
 // internal (conv3x3_pl.hip): the two thin kernels around the strips' conv
-extern "C" int wsu_ring_gather_pl(const void* g, void* strips, int n, int h, int w, int c, int L, void* stream) {
+WSU_INTERNAL int wsu_ring_gather_pl(const void* g, void* strips, int n, int h, int w, int c, int L, void* stream) {
     const long long total = (long long)4 * (c / 16) * 3 * n * (L + 2);
     hipLaunchKernelGGL(ring_gather_pl_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), (const char*)g, (char*)strips, n, h, w, c / 16, L);
     return wsu_check_launch("ring_gather_pl_kernel");
 }
-extern "C" int wsu_ring_fold_pl(const void* strips_out, void* dx1, void* dx2, const void* mask1, const void* mask2,
+WSU_INTERNAL int wsu_ring_fold_pl(const void* strips_out, void* dx1, void* dx2, const void* mask1, const void* mask2,
                                 int n, int h, int w, int cin, int csplit, int L, int gres, void* stream) {
     const int nrows = (h - 2 != 1) ? 2 : 1, ncols = (w - 2 != 1) ? 2 : 1;
     const long long total = (long long)n * (nrows * w + ncols * (h - nrows)) * (cin / 16);

@@ -15,7 +15,6 @@
 // slab; wgrad_reduce sums the slabs in a fixed order into the OIHW / IOHW gradient (bitwise reproducible --
 // no float atomics).
 #include "wsu_device.h"
-#include <cstdlib>
 
 namespace {
 
@@ -443,7 +442,6 @@ struct WgPlArgs {
     int n, hu, wu, cu, cv1, cv2;
     int tiles_x, tiles_y, ntiles, nsplit, nmb, nnb, tiles_per_split;
     int honly;                      // 1: f16 products only (wsu.h WSU_PRODUCTS_F16; ring kernel variant HONLY)
-    int ablate;                     // timing-only experiments (WSU_WGRAD_ABLATE; results wrong when != 0): 1 = no matrix section, 2 = staging of the first tile only, 4 = no derived copies (the ring kernel's variant HONLY = products F16 is the product form of "no cross terms")
 };
 
 // HONLY (products = WSU_PRODUCTS_F16): the residual halves are not loaded, no e4m3 images are written or multiplied; bias sums of the f16 parts.
@@ -564,9 +562,6 @@ __global__ __launch_bounds__(NT, 2) void wgrad_pl_kernel(const WgPlArgs a) {
         int n, y0, x0;
         decode(tile, n, y0, x0);
         __syncthreads();
-        if ((a.ablate & 2) && tile > t0) {
-            // timing experiment: no staging after the first tile
-        } else
         if (!have_pref) {
             rot = 0;
 #pragma unroll
@@ -605,7 +600,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_pl_kernel(const WgPlArgs a) {
         }
         __syncthreads();
         {
-            have_pref = tile + 1 < t1 && (!ROLL || (tile + 1) % a.tiles_y != 0) && !(a.ablate & 2);
+            have_pref = tile + 1 < t1 && (!ROLL || (tile + 1) % a.tiles_y != 0);
             if (have_pref) {
                 int n2, y2, x2;
                 decode(tile + 1, n2, y2, x2);
@@ -618,7 +613,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_pl_kernel(const WgPlArgs a) {
                 }
             }
         }
-        if (!(a.ablate & 1)) {
+        {
             const int colA8 = wm * 32 + ((lane >> 4) & 1) * 16, colB8 = wn * 32 + ((lane >> 4) & 1) * 16;
             constexpr int SU8 = UGRAD ? WSU_F8_SCALE_G : WSU_F8_SCALE_X, SUL = UGRAD ? WSU_F8_SCALE_GLO : WSU_F8_SCALE_XLO;
             constexpr int SV8 = UGRAD ? WSU_F8_SCALE_X : WSU_F8_SCALE_G, SVL = UGRAD ? WSU_F8_SCALE_XLO : WSU_F8_SCALE_GLO;
@@ -916,12 +911,12 @@ __device__ __forceinline__ void wgr_loader(const WgPlArgs& a, char* smem, int la
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // this wave's derived copies of step k are written
         __builtin_amdgcn_s_barrier();                                   // barrier k: the matrix waves start step k; all of step k is visible
         asm volatile("" ::: "memory");
-        if (wi.t < t1) { if (!(a.ablate & 2)) issue(wi, issued); wgr_advance(a, t1, wi); ++issued; }     // step k + DEPTH: its slots held steps k-1 (U) / k-2 (V)
+        if (wi.t < t1) { issue(wi, issued); wgr_advance(a, t1, wi); ++issued; }     // step k + DEPTH: its slots held steps k-1 (U) / k-2 (V)
         if (bias_on && !wb.pro) bias(k);
         wgr_advance(a, t1, wb);
         if (!(wb.t < t1)) break;                                        // no step k+1
-        wait_all_but((a.ablate & 2) ? 0 : issued - (k + 2));             // step k+1 landed
-        if (!(a.ablate & 4)) derive(k + 1);
+        wait_all_but(issued - (k + 2));                                 // step k+1 landed
+        derive(k + 1);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                                       // closing barrier 1: the matrix waves have left the last step
@@ -983,7 +978,7 @@ __global__ __launch_bounds__(wgr::NTD) void wgrad_ring_kernel(const WgPlArgs a) 
     for (int k = 0; w.t < t1; ++k) {
         __builtin_amdgcn_s_barrier();                                   // step k is in LDS
         asm volatile("" ::: "memory");
-        if (!w.pro && !(a.ablate & 1)) {
+        if (!w.pro) {
             const char* us = smem + (k % NU) * U_SLOT;
             const char* u_hi = us + U_HI + wm * U_HH; const char* u_c8 = us + U_C8 + wm * U_BH; const char* u_l8 = us + U_L8 + wm * U_BH;
 #pragma unroll
@@ -1165,12 +1160,7 @@ int run_wgrad_pl(WgPlArgs a, float* dw, float* db, float* workspace, size_t work
     a.tiles_per_split = (a.ntiles + nsplit - 1) / nsplit;
     a.part = workspace;
     a.bpart = db ? workspace + (size_t)nsplit * slab / sizeof(float) : nullptr;
-    static int ablate = -1;
-    if (ablate < 0) { const char* e = getenv("WSU_WGRAD_ABLATE"); ablate = e ? atoi(e) : 0; }
-    a.ablate = ablate;
-    static int impl = -1;                                              // WSU_WGRAD_IMPL=reg: the register-staged kernel (A/B runs)
-    if (impl < 0) { const char* e = getenv("WSU_WGRAD_IMPL"); impl = (e && e[0] == 'r') ? 0 : 1; }
-    if (KIND == 0 && impl == 1) {
+    if constexpr (KIND == 0) {                                         // conv: the ring kernel (the register-staged kernel below serves the transposed conv)
         // one persistent-style workgroup per CU: the splits cover the tiles, fewer and longer than the register-staged kernel's
         static int ncu = 0;
         if (ncu == 0) {
@@ -1192,23 +1182,24 @@ int run_wgrad_pl(WgPlArgs a, float* dw, float* db, float* workspace, size_t work
         if (rc) return rc;
         hipLaunchKernelGGL(wgrad_reduce_kernel<KIND>, dim3(512), dim3(256), 0, s, a.part, (const float*)a.bpart, dw, a.bpart ? db : (float*)nullptr, ns, a.nmb, a.nnb, nbias);
         return wsu_check_launch("wgrad_reduce_kernel");
+    } else {
+        constexpr int THP = KIND == 1 ? CT_TH_F16 : G::TH;                 // the f16-products instantiation: tile rows, LDS (no e4m3 images)
+        using GP = GeoX3<KIND, THP>;
+        constexpr int LDS_H = GP::U_BYTES + GP::V_BYTES;
+        static bool attr = false;
+        if (!attr) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pl_kernel<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, GeoX3<KIND>::LDS_F8);
+            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pl_kernel<KIND, true, THP>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H);
+            if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(wgrad_pl): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+            attr = true;
+        }
+        if (a.honly) hipLaunchKernelGGL((wgrad_pl_kernel<KIND, true, THP>), dim3(nsplit * a.nmb * a.nnb), dim3(NT), LDS_H, s, a);
+        else hipLaunchKernelGGL(wgrad_pl_kernel<KIND>, dim3(nsplit * a.nmb * a.nnb), dim3(NT), GeoX3<KIND>::LDS_F8, s, a);
+        int rc = wsu_check_launch("wgrad_pl_kernel");
+        if (rc) return rc;
+        hipLaunchKernelGGL(wgrad_reduce_kernel<KIND>, dim3(512), dim3(256), 0, s, a.part, (const float*)a.bpart, dw, a.bpart ? db : (float*)nullptr, nsplit, a.nmb, a.nnb, nbias);
+        return wsu_check_launch("wgrad_reduce_kernel");
     }
-    constexpr int THP = KIND == 1 ? CT_TH_F16 : G::TH;                 // the f16-products instantiation: tile rows, LDS (no e4m3 images)
-    using GP = GeoX3<KIND, THP>;
-    constexpr int LDS_H = GP::U_BYTES + GP::V_BYTES;
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pl_kernel<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, GeoX3<KIND>::LDS_F8);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pl_kernel<KIND, true, THP>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(wgrad_pl): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-        attr = true;
-    }
-    if (a.honly) hipLaunchKernelGGL((wgrad_pl_kernel<KIND, true, THP>), dim3(nsplit * a.nmb * a.nnb), dim3(NT), LDS_H, s, a);
-    else hipLaunchKernelGGL(wgrad_pl_kernel<KIND>, dim3(nsplit * a.nmb * a.nnb), dim3(NT), GeoX3<KIND>::LDS_F8, s, a);
-    int rc = wsu_check_launch("wgrad_pl_kernel");
-    if (rc) return rc;
-    hipLaunchKernelGGL(wgrad_reduce_kernel<KIND>, dim3(512), dim3(256), 0, s, a.part, (const float*)a.bpart, dw, a.bpart ? db : (float*)nullptr, nsplit, a.nmb, a.nnb, nbias);
-    return wsu_check_launch("wgrad_reduce_kernel");
 }
 
 }  // namespace

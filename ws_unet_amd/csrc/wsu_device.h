@@ -1,8 +1,5 @@
 // Shared device-side helpers for the gfx950 kernels of libwsu.
 #pragma once
-#ifndef WSU_PROBE
-#define WSU_PROBE 0             // timing-only build variants of the f16f8 matrix section (make probes; results are wrong when != 0)
-#endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -29,6 +26,8 @@ int wsu_check_launch(const char* what);
             return WSU_ERR_ARG;           \
         }                                 \
     } while (0)
+// a C-linkage helper called across translation units that is no part of include/wsu.h: not exported by libwsu.so
+#define WSU_INTERNAL extern "C" __attribute__((visibility("hidden")))
 
 // ---- tiling constants shared by packers and kernels ----------------------------------------------
 // A "chunk" is 64 bytes of channel data per pixel, staged in LDS as 4 granule planes of 16 bytes:
@@ -322,19 +321,9 @@ __device__ __forceinline__ void wsu_q4_encode16(const f32x4 (&v)[4], u32x4& h0, 
     q = mk_u4(wsu_f16x8_to_fp4(h0, sc), wsu_f16x8_to_fp4(h1, sc), q2, q3);
 }
 // fp4 cross-term MFMA: one granule per operand, per-lane E8M0 scale bytes
-#ifndef WSU_PROBE16
-#define WSU_PROBE16 0           // timing-only build (make qprobe16; results are wrong): every 32x32 matrix instruction of conv3x3_q.hip as TWO 16x16 instructions
-#endif                          // of the same cycles and products on the same operand registers -- what the 16x16x32 / 16x16x128 shapes would buy at no padding
 __device__ __forceinline__ void wsu_mfma_q4(const u32x4& a, const u32x4& b, int scale_a, int scale_b, f32x16& acc) {
     const i32x8 av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w, 0, 0, 0, 0}, bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w, 0, 0, 0, 0};
-#if WSU_PROBE16
-    f32x4 c0 = {acc[0], acc[1], acc[2], acc[3]}, c1 = {acc[8], acc[9], acc[10], acc[11]};
-    c0 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, c0, 4, 4, 0, scale_a, 0, scale_b);
-    c1 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, c1, 4, 4, 0, scale_a, 0, scale_b);
-    acc[0] = c0[0]; acc[1] = c0[1]; acc[2] = c0[2]; acc[3] = c0[3]; acc[8] = c1[0]; acc[9] = c1[1]; acc[10] = c1[2]; acc[11] = c1[3];
-#else
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 4, 4, 0, scale_a, 0, scale_b);
-#endif
 }
 
 // the same for a stored GRADIENT granule: e4m3(g * 4)
@@ -354,26 +343,13 @@ __device__ __forceinline__ u32x2 wsu_f16x8_to_fp8_grad(const u32x4& h) {
 // 4-7 block 1; inside a block lanes 0-31 hold k = 0..15 and lanes 32-63 k = 16..31; block b is scaled by byte 0 of the scale registers of
 // lanes 32b .. 32b+31 -> a lane passes (hh ? block-1 scale : block-0 scale).
 __device__ __forceinline__ void wsu_mfma_f16(const u32x4& a, const u32x4& b, f32x16& acc) {
-#if WSU_PROBE16
-    f32x4 c0 = {acc[4], acc[5], acc[6], acc[7]}, c1 = {acc[12], acc[13], acc[14], acc[15]};
-    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c1, 0, 0, 0);
-    acc[4] = c0[0]; acc[5] = c0[1]; acc[6] = c0[2]; acc[7] = c0[3]; acc[12] = c1[0]; acc[13] = c1[1]; acc[14] = c1[2]; acc[15] = c1[3];
-#else
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-#endif
 }
 __device__ __forceinline__ void wsu_mfma_f8x2(const u32x4& a_blk0, const u32x4& a_blk1, const u32x4& b_blk0, const u32x4& b_blk1,
                                               int scale_a, int scale_b, f32x16& acc) {
     i32x8 a = {(int)a_blk0.x, (int)a_blk0.y, (int)a_blk0.z, (int)a_blk0.w, (int)a_blk1.x, (int)a_blk1.y, (int)a_blk1.z, (int)a_blk1.w};
     i32x8 b = {(int)b_blk0.x, (int)b_blk0.y, (int)b_blk0.z, (int)b_blk0.w, (int)b_blk1.x, (int)b_blk1.y, (int)b_blk1.z, (int)b_blk1.w};
-#if WSU_PROBE == 2                                                  // timing probe: the same registers read as fp4 operands (4x the bf16 rate)
-    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 4, 4, 0, scale_a, 0, scale_b);
-#elif WSU_PROBE == 4                                                // timing probe: fp6 (e2m3) operands
-    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 2, 2, 0, scale_a, 0, scale_b);
-#else
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 0, 0, 0, scale_a, 0, scale_b);
-#endif
 }
 
 __device__ __forceinline__ float wsu_bf16_to_f32(uint16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
