@@ -459,6 +459,41 @@ size_t wsu_roc_counts_workspace_bytes(int groups, int t);
 int wsu_roc_counts(const double* scores, const signed char* labels, const long long* offsets, int groups, const double* taus, int t,
                    long long* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K20-K23: the stego simulators HILLR and LSBR.  The reference's stego twins were made by a library outside its tree; HILLR is
+ *      pinned to them bit for bit (tests/golden/stego_HILLR_*), LSBR's realisation is defined here.  Every plane is DEVICE (N,H,W) and
+ *      contiguous; H, W >= 1, H*W < 2^32, N <= 65535.  stego may alias cover.  Deterministic: integer atomics only, two calls give the
+ *      same bits, and an image's result does not depend on its position in the batch or on the batch size.
+ *
+ * K20: the HILL cost of K12 in float64 with the operation order of numpy's float64 restatement (exact integer S, 1.0 / (S / 9.0) as
+ *      two divisions, +inf where S == 0, 15 horizontal then 15 vertical taps each added in order from 0, / 225.0, then
+ *      inf | nan | > clamp -> clamp): bit-identical to it.  This is the ranking key of HILLR; the float32 cost of K12 cannot be (two
+ *      keys of a reference cover are 9.4e-8 apart, relatively).  0 < clamp < inf. */
+int wsu_hill_cost_f64(const uint8_t* x_u8, double* key, double clamp, int n, int h, int w, void* stream);
+/* K21: bits[i] = the uint64 pattern of the key of rank k[i] (0-based, ascending) among the H*W keys of image i, by an exact radix
+ *      select.  Keys must be positive and finite (K20's are, after the clamp), so their patterns order as the values do.  k: DEVICE
+ *      int64 [N]; a negative rank gives the pattern 0, which is below every key (K22 then changes nothing); a rank >= H*W is taken as
+ *      H*W - 1.  workspace: DEVICE, 8-byte aligned, wsu_rank_select_f64_workspace_bytes(n) (0 for n <= 0), zeroed on the stream by
+ *      every call. */
+size_t wsu_rank_select_f64_workspace_bytes(int n);
+int wsu_rank_select_f64(const double* key, const long long* k, uint64_t* bits, void* workspace, size_t workspace_bytes,
+                        int n, int h, int w, void* stream);
+/* K22: stego = cover ^ (key <= c) with c = the key whose pattern is bits[i]; changes[i] (DEVICE int64 [N], zeroed on the stream) =
+ *      the number of flipped pixels.  With bits from K21 at k = floor((H*W - 1) * alpha / 2) this is HILLR: the k + 1 cheapest pixels
+ *      change.  TIES at the threshold are ALL flipped, so changes[i] can exceed k + 1; a flat image, whose keys all equal the clamp, is
+ *      flipped entirely.  The reference does not pin that case (its 25 files have a single pixel at the threshold); flipping every tie
+ *      is the choice that does not depend on any order among equal keys.  Loads and stores of the planes are 16 bytes wide where cover
+ *      and stego share their alignment, single bytes at an image's unaligned ends. */
+int wsu_embed_threshold(const uint8_t* cover, const double* key, const uint64_t* bits, uint8_t* stego, long long* changes,
+                        int n, int h, int w, void* stream);
+/* K23: LSB replacement at change rate alpha / 2 with a counter-based generator: pixel i (linear index in its image) flips iff
+ *      word < thresholds[image], word = output word i % 4 of Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments
+ *      0x9E3779B9 / 0xBB67AE85) on the counter (i / 4, 0, 0, 0) under the key (low, high word of seeds[image]).  seeds: DEVICE uint64
+ *      [N]; thresholds: DEVICE uint32 [N], each from wsu_lsbr_threshold (HOST: *threshold = floor(alpha / 2 * 2^32) in float64, alpha in
+ *      [0, 1]; 0 copies the cover); changes as in K22. */
+int wsu_lsbr_threshold(double alpha, uint32_t* threshold);
+int wsu_embed_lsbr(const uint8_t* cover, const uint64_t* seeds, const uint32_t* thresholds, uint8_t* stego, long long* changes,
+                   int n, int h, int w, void* stream);
+
 /* Linear pixel predictor on its own (filters/evaluate.py:136-141): y (N,H-2,W-2) = convolve(x/255., K, 'valid')*255.
  * x: DEVICE (N,H,W) fp32; filter: HOST 9 floats K[a][b]. */
 int wsu_filter3x3_valid_f32(const float* x, const float* filter, float* y, int n, int h, int w, void* stream);

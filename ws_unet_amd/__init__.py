@@ -9,7 +9,7 @@ Everything heavy (torch, the HIP library) is imported lazily on first attribute 
 import importlib
 
 __all__ = ["get_model", "load_model", "infere_single", "get_model_name", "get_model_config",
-           "get_pretrained", "get_unet_estimator", "data"]
+           "get_pretrained", "get_unet_estimator", "data", "simulate", "image_seed", "write_dataset"]
 
 _LAZY = {
     "get_model": ("ws_unet_amd.model", "get_model"),
@@ -18,6 +18,9 @@ _LAZY = {
     "get_model_name": ("ws_unet_amd.evaluate", "get_model_name"),
     "get_model_config": ("ws_unet_amd.evaluate", "get_model_config"),
     "get_pretrained": ("ws_unet_amd.evaluate", "get_pretrained"),
+    "simulate": ("ws_unet_amd.embed", "simulate"),
+    "image_seed": ("ws_unet_amd.embed", "image_seed"),
+    "write_dataset": ("ws_unet_amd.embed", "write_dataset"),
 }
 
 
@@ -25,7 +28,7 @@ def __getattr__(name):
     if name in _LAZY:
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(mod), attr)
-    if name in ("data", "evaluate", "model", "fabrika", "ops", "formula", "losses", "metrics", "imread", "parallel", "trainer", "filters", "ws"):
+    if name in ("data", "evaluate", "model", "fabrika", "ops", "formula", "losses", "metrics", "imread", "parallel", "trainer", "filters", "ws", "embed"):
         return importlib.import_module(f"ws_unet_amd.{name}")
     raise AttributeError(name)
 

@@ -107,6 +107,12 @@ SIGNATURES = {
     "wsu_ae_select": (c_int, [_P, c_size_t, c_int, c_int, c_longlong, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "wsu_roc_counts_workspace_bytes": (c_size_t, [c_int, c_int]),
     "wsu_roc_counts": (c_int, [_P, _P, _P, c_int, _P, c_int, _P, _P, c_size_t, _P]),
+    "wsu_hill_cost_f64": (c_int, [_P, _P, c_double, c_int, c_int, c_int, _P]),
+    "wsu_rank_select_f64_workspace_bytes": (c_size_t, [c_int]),
+    "wsu_rank_select_f64": (c_int, [_P, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_embed_threshold": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "wsu_lsbr_threshold": (c_int, [c_double, _P]),
+    "wsu_embed_lsbr": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_u8_to_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     # ---- backward / train step

@@ -1,0 +1,368 @@
+// K20-K23: the stego simulators HILLR and LSBR (the reference ships ready-made twins of its five covers, made by a library outside its
+// tree; tests/golden/stego_HILLR_* pins HILLR to those files bit for bit, LSBR's realisation is this package's own):
+//
+//   HILLR   key = HILL cost in float64 (the operation order of tests/hill_np.hill_cost), full frame
+//           k   = floor((H*W - 1) * alpha / 2)             c_(k) = the key of rank k (0-based, ascending)
+//           stego = cover ^ (key <= c_(k))                 (k + 1 changes when c_(k) is held by one pixel; ties are all flipped)
+//   LSBR    stego = cover ^ (word < T),  T = floor(alpha / 2 * 2^32),  word = Philox4x32-10 word (i % 4) of counter (i / 4, 0, 0, 0)
+//           under the image's 64-bit seed as key (low, high), i = the pixel's linear index in its image
+//
+// K20 is K12 in float64 on a 32 x 32 tile (the float64 arrays of a 64 x 64 tile would need 97 KB of LDS; a 32 x 32 tile needs 36 KB
+// and stays static): every sum is a direct sum in numpy's order, the two divisions are IEEE divisions, nothing is contracted.  K21 is an
+// exact radix select over the keys' uint64 patterns (positive and finite after the clamp, so monotone): six histogram passes of
+// 11/11/11/11/11/9 bits.  All cross-workgroup traffic is integer atomics, results pass between kernels only at kernel boundaries, the
+// workspace and the change counters are zeroed on the stream: two calls give the same bits.
+#pragma clang fp contract(off)
+#include "wsu_metric.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(2))) double f64x2;
+
+constexpr int ET = 32;                 // K20 output tile (ET x ET pixels per workgroup, 256 threads)
+constexpr int EX = ET + 18;            // staged u8 window (pad 9 on each side)
+constexpr int EXS = ET + 32;           // its LDS row stride (hill_stage_window)
+constexpr int ER = ET + 16;            // |R| extent
+constexpr int ES = ET + 14;            // S / rho0 extent
+
+constexpr int SEL_LEVELS = 6;          // K21 radix: 11 / 11 / 11 / 11 / 11 / 9 bits
+constexpr int SEL_BINS = 2048;
+constexpr int SEL_PARTS = 64;          // K21 workgroups per image
+constexpr int EMB_MAX_BLOCKS = 64;     // K22 / K23 workgroups per image, at most
+
+// ---- K20 ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hill_cost_f64_kernel(const uint8_t* __restrict__ x, double* __restrict__ cost, int h, int w,
+                                                            int vec_in, int vec_out, double clamp) {
+    __shared__ __attribute__((aligned(16))) uint8_t xs[EX * EXS];
+    __shared__ short ar[ER * ER];
+    __shared__ double rho[ES * ES];
+    __shared__ __attribute__((aligned(16))) double hbuf[ES * ET];
+    const int tid = threadIdx.x;
+    const int c0 = blockIdx.x * ET, r0 = blockIdx.y * ET, nn = blockIdx.z;
+    const uint8_t* img = x + (size_t)nn * h * w;
+
+    hill_stage_window<ET>(img, xs, r0, c0, h, w, vec_in, tid);
+    __syncthreads();
+    // ---- |R| (exact integers, |R| <= 16 * 255)
+    for (int i = tid; i < ER * ER; i += 256) {
+        const int a = i / ER, b = i % ER;
+        const uint8_t* p = xs + a * EXS + b + 7;
+        const int r = -(int)p[0] + 2 * (int)p[1] - (int)p[2]
+                    + 2 * (int)p[EXS] - 4 * (int)p[EXS + 1] + 2 * (int)p[EXS + 2]
+                    - (int)p[2 * EXS] + 2 * (int)p[2 * EXS + 1] - (int)p[2 * EXS + 2];
+        ar[i] = (short)(r < 0 ? -r : r);
+    }
+    __syncthreads();
+    // ---- S = box3x3(|R|) (exact), rho0 = 1 / (S / 9): two IEEE divisions, as numpy's `1.0 / (s / 9.0)`
+    for (int i = tid; i < ES * ES; i += 256) {
+        const int a = i / ES, b = i % ES;
+        int s = 0;
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+            for (int v = 0; v < 3; ++v) s += ar[(a + u) * ER + b + v];
+        const double m = (double)s / 9.0;
+        rho[i] = s > 0 ? 1.0 / m : __builtin_inf();
+    }
+    __syncthreads();
+    // ---- horizontal 15-tap direct sums, left to right from 0
+    for (int i = tid; i < ES * ET; i += 256) {
+        const int a = i / ET, b = i % ET;
+        const double* p = rho + a * ES + b;
+        double s = 0.0;
+#pragma unroll
+        for (int t = 0; t < 15; ++t) s += p[t];
+        hbuf[i] = s;
+    }
+    __syncthreads();
+    // ---- vertical 15-tap direct sums, top to bottom from 0, / 225, clamp; two consecutive columns per thread -> one 16-byte store
+    for (int i = tid; i < ET * (ET / 2); i += 256) {
+        const int a = i / (ET / 2), b = (i % (ET / 2)) * 2;
+        f64x2 s = {0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < 15; ++t) s += *reinterpret_cast<const f64x2*>(hbuf + (a + t) * ET + b);
+        s.x = s.x / 225.0;
+        s.y = s.y / 225.0;
+        s.x = s.x <= clamp ? s.x : clamp;          // inf / nan / > clamp -> clamp
+        s.y = s.y <= clamp ? s.y : clamp;
+        const int r = r0 + a, c = c0 + b;
+        if (r >= h) continue;
+        double* o = cost + ((size_t)nn * h + r) * w + c;
+        if (vec_out && c + 2 <= w) {
+            *reinterpret_cast<f64x2*>(o) = s;
+        } else {
+            if (c < w) o[0] = s.x;
+            if (c + 1 < w) o[1] = s.y;
+        }
+    }
+}
+
+// ---- K21 ------------------------------------------------------------------------------------------------------------------
+// Level l fixes the bits from sel_shift(l) upwards; the bits above sel_shift(l - 1) are the prefix the earlier levels found.
+__device__ __forceinline__ int sel_shift(int level) { return level < SEL_LEVELS - 1 ? 53 - 11 * level : 0; }
+__device__ __forceinline__ int sel_bins(int level) { return level < SEL_LEVELS - 1 ? SEL_BINS : 512; }
+__device__ __forceinline__ uint64_t sel_mask(int level) { return level == 0 ? 0ull : ~0ull << sel_shift(level - 1); }
+
+// Workspace: state[n][2] (uint64) = {prefix bits, remaining rank}, then hist[SEL_LEVELS][n][SEL_BINS] (uint32).
+__device__ __forceinline__ uint32_t* sel_hist(void* ws, int level, int n, int nn) {
+    return reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(ws) + (size_t)2 * n) + ((size_t)level * n + nn) * SEL_BINS;
+}
+
+__global__ __launch_bounds__(256) void rank_select_hist_kernel(const uint64_t* __restrict__ keys, void* __restrict__ ws, int level,
+                                                               int n, long long hw) {
+    __shared__ uint32_t lh[SEL_BINS];
+    const int nn = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
+    const int shift = sel_shift(level), bins = sel_bins(level);
+    const uint64_t mask = sel_mask(level);
+    const uint64_t prefix = level == 0 ? 0ull : static_cast<const uint64_t*>(ws)[(size_t)2 * nn];
+    for (int b = tid; b < SEL_BINS; b += 256) lh[b] = 0u;
+    __syncthreads();
+    const uint64_t* img = keys + (size_t)nn * hw;
+    for (long long i = (long long)part * 256 + tid; i < hw; i += (long long)SEL_PARTS * 256) {
+        const uint64_t u = img[i];
+        if ((u & mask) == prefix) atomicAdd(&lh[(uint32_t)(u >> shift) & (uint32_t)(bins - 1)], 1u);
+    }
+    __syncthreads();
+    uint32_t* hist = sel_hist(ws, level, n, nn);
+    for (int b = tid; b < bins; b += 256)
+        if (lh[b]) atomicAdd(&hist[b], lh[b]);
+}
+
+// one workgroup per image: the bin that holds the remaining rank, by a fixed-order scan of the histogram; the last level writes the
+// whole pattern.  A negative rank selects nothing: pattern 0, below every key.  A rank past the last is the last.
+__global__ __launch_bounds__(256) void rank_select_pick_kernel(void* __restrict__ ws, const long long* __restrict__ k, int level,
+                                                               uint64_t* __restrict__ bits, int n, long long hw) {
+    __shared__ uint64_t part[256];
+    const int nn = blockIdx.x, tid = threadIdx.x;
+    const bool last = level == SEL_LEVELS - 1;
+    const long long k0 = k[nn];
+    if (k0 < 0) {                                            // (uniform over the workgroup)
+        if (last && tid == 0) bits[nn] = 0ull;
+        return;
+    }
+    uint64_t* st = static_cast<uint64_t*>(ws) + (size_t)2 * nn;
+    const uint64_t prefix = level == 0 ? 0ull : st[0];
+    const uint64_t kk = level == 0 ? (uint64_t)(k0 < hw ? k0 : hw - 1) : st[1];
+    const uint32_t* hist = sel_hist(ws, level, n, nn);
+    const int per = sel_bins(level) / 256;
+    uint64_t mine = 0;
+    for (int j = 0; j < per; ++j) mine += hist[tid * per + j];
+    part[tid] = mine;
+    __syncthreads();                                         // (also: every thread has read st[] before the finder writes it)
+    uint64_t before = 0;
+    for (int t = 0; t < tid; ++t) before += part[t];
+    if (kk < before || kk >= before + mine) return;
+    for (int j = 0; j < per; ++j) {
+        const uint64_t cnt = hist[tid * per + j];
+        if (kk < before + cnt) {
+            const uint64_t found = prefix | ((uint64_t)(tid * per + j) << sel_shift(level));
+            st[0] = found;
+            st[1] = kk - before;
+            if (last) bits[nn] = found;
+            return;
+        }
+        before += cnt;
+    }
+}
+
+// ---- K22 / K23: the pixel loops -----------------------------------------------------------------------------------------------
+// An image's pixels as `head` leading bytes, `groups` 16-byte groups whose loads and stores are aligned, and trailing bytes; `bytes` =
+// head + tail.  Input and output must share their alignment, else every pixel is a byte; quad: a group must start at a multiple of 4
+// pixels (K23: one generator call serves pixels 4g .. 4g+3).
+struct Span { long long head, groups, bytes; };
+__device__ __forceinline__ Span image_span(const uint8_t* in, const uint8_t* out, long long hw, bool quad) {
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+    long long head = hw;
+    if (((a ^ b) & 15) == 0) {
+        const long long hd = (long long)((16 - (a & 15)) & 15);
+        if (hd <= hw && (!quad || hd % 4 == 0)) head = hd;
+    }
+    const long long groups = (hw - head) / 16;
+    return Span{head, groups, hw - 16 * groups};
+}
+__device__ __forceinline__ long long span_byte_index(const Span& sp, long long j) { return j < sp.head ? j : j + 16 * sp.groups; }
+
+// this thread's count -> one integer atomic per workgroup (wave reduction, then the four wave sums)
+__device__ __forceinline__ void add_changes(int cnt, long long* __restrict__ dst, int tid) {
+    __shared__ int wsum[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+    if ((tid & 63) == 0) wsum[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (total) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)total);
+    }
+}
+
+// K22.  A wave takes 1024 consecutive pixels at a time: lane l owns pixels 16 l .. 16 l + 15 (one 16-byte load and store), the keys are
+// read 64 consecutive ones per step (lane l: key 64 j + l) and a ballot hands every lane the 16 decisions of its pixels.
+__global__ __launch_bounds__(256) void embed_threshold_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ keys,
+                                                              const uint64_t* __restrict__ bits, uint8_t* __restrict__ stego,
+                                                              long long* __restrict__ changes, long long hw) {
+    const int nn = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const uint8_t* cin = cover + (size_t)nn * hw;
+    uint8_t* cout = stego + (size_t)nn * hw;
+    const uint64_t* kin = keys + (size_t)nn * hw;
+    const uint64_t thr = bits[nn];
+    const Span sp = image_span(cin, cout, hw, false);
+    int cnt = 0;
+    const long long nwaves = (long long)gridDim.x * 4;
+    for (long long ch = (long long)blockIdx.x * 4 + (tid >> 6); ch * 64 < sp.groups; ch += nwaves) {       // (uniform over the wave)
+        const long long base = sp.head + ch * 1024, end = sp.head + 16 * sp.groups;
+        uint32_t my = 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const long long i = base + j * 64 + lane;
+            const bool flip = i < end && kin[i] <= thr;
+            const unsigned long long m = __ballot(flip);
+            if ((lane >> 2) == j) my = (uint32_t)(m >> (16 * (lane & 3))) & 0xFFFFu;
+        }
+        const long long g = ch * 64 + lane;
+        if (g < sp.groups) {
+            u32x4 v = *reinterpret_cast<const u32x4*>(cin + sp.head + 16 * g);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) v[e >> 2] ^= ((my >> e) & 1u) << (8 * (e & 3));
+            *reinterpret_cast<u32x4*>(cout + sp.head + 16 * g) = v;
+            cnt += __popc(my);
+        }
+    }
+    for (long long j = (long long)blockIdx.x * 256 + tid; j < sp.bytes; j += (long long)gridDim.x * 256) {
+        const long long i = span_byte_index(sp, j);
+        const uint8_t flip = kin[i] <= thr ? 1 : 0;
+        cout[i] = cin[i] ^ flip;
+        cnt += flip;
+    }
+    add_changes(cnt, changes + nn, tid);
+}
+
+// K23.  Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32 x 32 -> 64 bit products, the key bumped between rounds.
+struct Words4 { uint32_t v[4]; };
+__device__ __forceinline__ Words4 philox4x32_10(uint32_t c0, uint32_t k0, uint32_t k1) {
+    uint32_t c[4] = {c0, 0u, 0u, 0u};
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return Words4{{c[0], c[1], c[2], c[3]}};
+}
+
+__global__ __launch_bounds__(256) void embed_lsbr_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ seeds,
+                                                         const uint32_t* __restrict__ thresholds, uint8_t* __restrict__ stego,
+                                                         long long* __restrict__ changes, long long hw) {
+    const int nn = blockIdx.y, tid = threadIdx.x;
+    const uint8_t* cin = cover + (size_t)nn * hw;
+    uint8_t* cout = stego + (size_t)nn * hw;
+    const uint32_t k0 = (uint32_t)seeds[nn], k1 = (uint32_t)(seeds[nn] >> 32), thr = thresholds[nn];
+    const Span sp = image_span(cin, cout, hw, true);
+    int cnt = 0;
+    for (long long g = (long long)blockIdx.x * 256 + tid; g < sp.groups; g += (long long)gridDim.x * 256) {
+        const long long p = sp.head + 16 * g;                               // a multiple of 4
+        u32x4 v = *reinterpret_cast<const u32x4*>(cin + p);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const Words4 wd = philox4x32_10((uint32_t)(p / 4 + q), k0, k1);
+            uint32_t flips = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) flips |= (wd.v[e] < thr ? 1u : 0u) << (8 * e);
+            v[q] ^= flips;
+            cnt += __popc(flips);
+        }
+        *reinterpret_cast<u32x4*>(cout + p) = v;
+    }
+    for (long long j = (long long)blockIdx.x * 256 + tid; j < sp.bytes; j += (long long)gridDim.x * 256) {
+        const long long i = span_byte_index(sp, j);
+        const Words4 wd = philox4x32_10((uint32_t)(i / 4), k0, k1);
+        const int e = (int)(i & 3);                                          // (selects: a dynamic index would put the words in LDS)
+        const uint32_t word = e == 0 ? wd.v[0] : e == 1 ? wd.v[1] : e == 2 ? wd.v[2] : wd.v[3];
+        const uint8_t flip = word < thr ? 1 : 0;
+        cout[i] = cin[i] ^ flip;
+        cnt += flip;
+    }
+    add_changes(cnt, changes + nn, tid);
+}
+
+int embed_blocks(long long hw) {
+    const long long b = (hw / 16 + 255) / 256;
+    return (int)(b < 1 ? 1 : b > EMB_MAX_BLOCKS ? EMB_MAX_BLOCKS : b);
+}
+
+}  // namespace
+
+// a frame's pixel count must fit the 32-bit histogram counters and Philox's 32-bit counter word (4 pixels each)
+#define EMBED_REQUIRE_SHAPE(what)                                                                                     \
+    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, what ": bad shape n=%d h=%d w=%d", n, h, w);                 \
+    WSU_REQUIRE((long long)h * w < (1LL << 32), what ": %lld pixels per image exceed the 32-bit counters", (long long)h * w)
+
+extern "C" {
+
+int wsu_hill_cost_f64(const uint8_t* x_u8, double* key, double clamp, int n, int h, int w, void* stream) {
+    WSU_REQUIRE(x_u8 && key, "hill_cost_f64: null pointer");
+    EMBED_REQUIRE_SHAPE("hill_cost_f64");
+    WSU_REQUIRE(clamp > 0.0 && clamp < __builtin_inf(), "hill_cost_f64: clamp=%g must be positive and finite", clamp);
+    const int vec_in = (w % 16 == 0) && ((uintptr_t)x_u8 % 16 == 0);
+    const int vec_out = (w % 2 == 0) && ((uintptr_t)key % 16 == 0);
+    hipLaunchKernelGGL(hill_cost_f64_kernel, dim3((w + ET - 1) / ET, (h + ET - 1) / ET, n), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_u8, key, h, w, vec_in, vec_out, clamp);
+    return wsu_check_launch("hill_cost_f64_kernel");
+}
+
+size_t wsu_rank_select_f64_workspace_bytes(int n) {
+    return n > 0 ? (size_t)n * (2 * sizeof(uint64_t) + (size_t)SEL_LEVELS * SEL_BINS * sizeof(uint32_t)) : 0;
+}
+
+int wsu_rank_select_f64(const double* key, const long long* k, uint64_t* bits, void* workspace, size_t workspace_bytes,
+                        int n, int h, int w, void* stream) {
+    WSU_REQUIRE(key && k && bits && workspace, "rank_select_f64: null pointer");
+    EMBED_REQUIRE_SHAPE("rank_select_f64");
+    WSU_REQUIRE(workspace_bytes >= wsu_rank_select_f64_workspace_bytes(n), "rank_select_f64: workspace too small");
+    WSU_REQUIRE((uintptr_t)workspace % 8 == 0, "rank_select_f64: workspace must be 8-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long hw = (long long)h * w;
+    if (hipMemsetAsync(workspace, 0, wsu_rank_select_f64_workspace_bytes(n), s) != hipSuccess) return wsu_check_launch("rank_select_f64 memset");
+    for (int level = 0; level < SEL_LEVELS; ++level) {
+        hipLaunchKernelGGL(rank_select_hist_kernel, dim3(SEL_PARTS, n), dim3(256), 0, s, reinterpret_cast<const uint64_t*>(key), workspace,
+                           level, n, hw);
+        int rc = wsu_check_launch("rank_select_hist_kernel");
+        if (rc) return rc;
+        hipLaunchKernelGGL(rank_select_pick_kernel, dim3(n), dim3(256), 0, s, workspace, k, level, bits, n, hw);
+        rc = wsu_check_launch("rank_select_pick_kernel");
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int wsu_embed_threshold(const uint8_t* cover, const double* key, const uint64_t* bits, uint8_t* stego, long long* changes,
+                        int n, int h, int w, void* stream) {
+    WSU_REQUIRE(cover && key && bits && stego && changes, "embed_threshold: null pointer");
+    EMBED_REQUIRE_SHAPE("embed_threshold");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long hw = (long long)h * w;
+    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_threshold memset");
+    hipLaunchKernelGGL(embed_threshold_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, reinterpret_cast<const uint64_t*>(key),
+                       bits, stego, changes, hw);
+    return wsu_check_launch("embed_threshold_kernel");
+}
+
+int wsu_lsbr_threshold(double alpha, uint32_t* threshold) {
+    WSU_REQUIRE(threshold, "lsbr_threshold: null pointer");
+    WSU_REQUIRE(alpha >= 0.0 && alpha <= 1.0, "lsbr_threshold: alpha=%g outside [0, 1]", alpha);
+    *threshold = (uint32_t)(alpha / 2.0 * 4294967296.0);               // floor: the product is not negative
+    return 0;
+}
+
+int wsu_embed_lsbr(const uint8_t* cover, const uint64_t* seeds, const uint32_t* thresholds, uint8_t* stego, long long* changes,
+                   int n, int h, int w, void* stream) {
+    WSU_REQUIRE(cover && seeds && thresholds && stego && changes, "embed_lsbr: null pointer");
+    EMBED_REQUIRE_SHAPE("embed_lsbr");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long hw = (long long)h * w;
+    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbr memset");
+    hipLaunchKernelGGL(embed_lsbr_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, thresholds, stego, changes, hw);
+    return wsu_check_launch("embed_lsbr_kernel");
+}
+
+}  // extern "C"

@@ -22,21 +22,13 @@ namespace {
 
 constexpr int HT = 64;                 // K12 output tile (HT x HT pixels per workgroup, 256 threads)
 constexpr int HX = HT + 18;            // staged u8 window (pad 9 on each side)
-constexpr int HXS = 96;                // LDS row stride of the window; window column wc lives at wc + 7 (16-byte aligned row loads)
+constexpr int HXS = HT + 32;           // LDS row stride of the window; window column wc lives at wc + 7 (hill_stage_window)
 constexpr int HR = HT + 16;            // |R| extent
 constexpr int HS = HT + 14;            // S / rho0 extent
 
 constexpr int RS_BINS = 2048;          // K13 radix: 11 / 11 / 10 bits
 constexpr int RS_PARTS = 64;           // K13 / K14 workgroups per image
 constexpr int PE_PARTS = 64;
-
-// numpy.pad(mode='symmetric') index, repeated reflection (period 2n): -1 -> 0, -2 -> 1, n -> n-1, ...
-__device__ __forceinline__ int sym_fold(int j, int n) {
-    const int p = 2 * n;
-    int m = j % p;
-    m = m < 0 ? m + p : m;
-    return m < n ? m : p - 1 - m;
-}
 
 __global__ __launch_bounds__(256) void hill_cost_kernel(const uint8_t* __restrict__ x, float* __restrict__ cost, int h, int w,
                                                         int vec_in, int vec_out, float clamp) {
@@ -49,18 +41,7 @@ __global__ __launch_bounds__(256) void hill_cost_kernel(const uint8_t* __restric
     const uint8_t* img = x + (size_t)nn * h * w;
 
     // ---- stage the (HT+18)^2 window: 16-byte row segments where the tile is well inside the image, else through the fold
-    if (vec_in && r0 - 9 >= 0 && r0 + HT + 9 <= h && c0 - 16 >= 0 && c0 + HT + 16 <= w) {
-        for (int i = tid; i < HX * 6; i += 256) {
-            const int wr = i / 6, seg = i % 6;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(img + (size_t)(r0 - 9 + wr) * w + (c0 - 16 + seg * 16));
-            *reinterpret_cast<u32x4*>(xs + wr * HXS + seg * 16) = v;
-        }
-    } else {
-        for (int i = tid; i < HX * HX; i += 256) {
-            const int wr = i / HX, wc = i % HX;
-            xs[wr * HXS + wc + 7] = img[(size_t)sym_fold(r0 - 9 + wr, h) * w + sym_fold(c0 - 9 + wc, w)];
-        }
-    }
+    hill_stage_window<HT>(img, xs, r0, c0, h, w, vec_in, tid);
     __syncthreads();
     // ---- |R| (exact integers, |R| <= 16 * 255)
     for (int i = tid; i < HR * HR; i += 256) {

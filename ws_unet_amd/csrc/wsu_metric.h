@@ -1,6 +1,6 @@
-// Device helpers shared by the metric kernels K10-K18 (pointwise.hip K10 + WS meter, ws_attack.hip, hill.hip, correlation.hip,
-// error_boxes.hip): the one definition each of a 3x3 predictor's taps, the prediction at a pixel, the float32 residual, the fixed-order
-// block sum and the radix-select steps.
+// Device helpers shared by the metric kernels K10-K18 and the simulators K20-K23 (pointwise.hip K10 + WS meter, ws_attack.hip, hill.hip,
+// correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's taps, the prediction at a pixel, the float32
+// residual, the HILL cost's input window, the fixed-order block sum and the radix-select steps.
 //
 // Rounding policy: these functions restate numpy's float32 / float64 operation sequences with PLAIN operators, one rounding each.  That
 // holds only under `#pragma clang fp contract(off)`, which is per translation unit: every including .hip file sets it BEFORE this
@@ -60,6 +60,34 @@ __device__ __forceinline__ size_t hat_index(int hat_full, size_t base, int r, in
 __device__ __forceinline__ float residual_f32(float x, float y, float scale) {
     const float xhat = y * scale;
     return x - xhat;
+}
+
+// ---- the HILL cost's input window (K12 fp32, K20 fp64) -----------------------------------------------------------------------------
+// numpy.pad(mode='symmetric') index, repeated reflection (period 2n): -1 -> 0, -2 -> 1, n -> n-1, ...
+__device__ __forceinline__ int sym_fold(int j, int n) {
+    const int p = 2 * n;
+    int m = j % p;
+    m = m < 0 ? m + p : m;
+    return m < n ? m : p - 1 - m;
+}
+// One 256-thread workgroup stages the (TILE+18)^2 uint8 window of the tile at (r0, c0) -- x padded by 9, 'symmetric' -- into `xs`: LDS row
+// stride TILE + 32, window column wc at wc + 7, so that a tile well inside the image is copied as 16-byte row segments (vec_in: rows and
+// base 16-byte aligned); every other tile reads through the fold.  The caller's barrier follows.
+template <int TILE> __device__ __forceinline__ void hill_stage_window(const uint8_t* __restrict__ img, uint8_t* xs, int r0, int c0,
+                                                                      int h, int w, int vec_in, int tid) {
+    constexpr int X = TILE + 18, XS = TILE + 32, SEGS = XS / 16;
+    if (vec_in && r0 - 9 >= 0 && r0 + TILE + 9 <= h && c0 - 16 >= 0 && c0 + TILE + 16 <= w) {
+        for (int i = tid; i < X * SEGS; i += 256) {
+            const int wr = i / SEGS, seg = i % SEGS;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(img + (size_t)(r0 - 9 + wr) * w + (c0 - 16 + seg * 16));
+            *reinterpret_cast<u32x4*>(xs + wr * XS + seg * 16) = v;
+        }
+    } else {
+        for (int i = tid; i < X * X; i += 256) {
+            const int wr = i / X, wc = i % X;
+            xs[wr * XS + wc + 7] = img[(size_t)sym_fold(r0 - 9 + wr, h) * w + sym_fold(c0 - 9 + wc, w)];
+        }
+    }
 }
 
 // ---- fixed-order block sum -----------------------------------------------------------------------------------------------------------

@@ -1,0 +1,156 @@
+"""Stego simulators on the device: HILLR and LSBR twins of cover images (wsu_hill_cost_f64, wsu_rank_select_f64,
+wsu_embed_threshold, wsu_embed_lsbr; include/wsu.h K20-K23).
+
+The reference ships its five covers with ready-made `stego_*` folders from a library outside its tree.  Here a covers-only data
+set gets its twins from the package itself:
+
+  * `simulate(cover_u8, stego_method, alpha, seeds)` on resident (N,H,W) uint8 planes;
+  * `write_dataset(data_dir, stego_method, alpha)` / `python -m ws_unet_amd.embed --data DIR --stego-method HILLR --alphas .4 .2`
+    writes `stego_<METHOD>_alpha_<a>_independent_images/<stem>.png` and its files.csv, which fabrika.stego_spatial and
+    fabrika.cover_stego_spatial then list like the reference's folders;
+  * `data.pairs.PairLoader(..., simulate=True)` makes the twin of every uploaded cover instead of decoding a second file.
+
+HILLR is deterministic and reproduces the reference's files bit for bit: the LSB flips on the k + 1 pixels of lowest float64 HILL
+cost, k = floor((H*W - 1) * alpha / 2); every pixel that ties with the threshold flips too (a flat image flips entirely).  LSBR
+flips each LSB independently with probability alpha / 2 from Philox4x32-10 keyed by the image's seed: the realisation is a function
+of (seed, alpha, pixel index) alone -- `image_seed(filename, stream)` makes it a function of the file stem and a stream number.
+"""
+from __future__ import annotations
+
+import argparse
+import pathlib
+import typing
+
+import numpy as np
+import torch
+
+from . import fabrika
+
+METHODS = ("LSBR", "HILLR")
+
+
+def method_name(stego_method: str) -> str:
+    """'LSBR' / 'HILLR', matched case-insensitively (the reference spells both 'LSBr' and 'LSBR')."""
+    m = str(stego_method).upper()
+    if m not in METHODS:
+        raise NotImplementedError(f"stego method {stego_method!r} is not simulated here: choose one of {' / '.join(METHODS)}")
+    return m
+
+
+def image_seed(filename, stream: int = 0) -> int:
+    """The 64-bit LSBR seed of an image: fabrika.filename_to_image_seed (file stem only, < 2^31) in the low word, `stream` above."""
+    stream = int(stream)
+    if not 0 <= stream < 2 ** 32:
+        raise ValueError(f"stream {stream} outside [0, 2^32)")
+    return fabrika.filename_to_image_seed(str(filename)) | (stream << 32)
+
+
+def hillr_rank(alpha: float, h: int, w: int) -> int:
+    """k = floor((H*W - 1) * alpha / 2) in float64: the k + 1 cheapest pixels change.  alpha == 0 -> -1 (no pixel changes)."""
+    return int(np.floor((h * w - 1) * (float(alpha) / 2))) if alpha > 0 else -1
+
+
+def _alphas(alpha, n: int) -> np.ndarray:
+    a = np.asarray(alpha, dtype=np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+        raise ValueError(f"alpha must be a scalar or one value per image ({n}), got shape {a.shape}")
+    a = np.broadcast_to(a, (n,))
+    if not np.all((a >= 0) & (a <= 1)):
+        raise ValueError(f"alpha outside [0, 1]: {alpha!r}")
+    return a
+
+
+def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, key: typing.Optional[torch.Tensor] = None):
+    """cover_u8: (N,H,W) uint8 on the device; alpha: a scalar or one value per image -> (stego (N,H,W) uint8, changes (N) int64), both
+    on the device.  'LSBR' needs `seeds`, one 64-bit integer per image (image_seed); 'HILLR' ignores them and takes an optional
+    `key` = ops.hill_cost_f64(cover_u8) made earlier (several alphas of the same covers)."""
+    from . import ops
+    method = method_name(stego_method)
+    if not (isinstance(cover_u8, torch.Tensor) and cover_u8.dim() == 3 and cover_u8.dtype == torch.uint8):
+        raise ValueError("simulate: cover_u8 must be an (N,H,W) uint8 tensor")
+    n, h, w = cover_u8.shape
+    a = _alphas(alpha, n)
+    dev = cover_u8.device
+    if method == "HILLR":
+        if key is None:
+            key = ops.hill_cost_f64(cover_u8)
+        k = torch.tensor([hillr_rank(v, h, w) for v in a], dtype=torch.int64).to(dev)
+        return ops.embed_threshold(cover_u8, key, ops.rank_select_f64(key, k))
+    if seeds is None:
+        raise ValueError("simulate: 'LSBR' needs one seed per image (embed.image_seed)")
+    s = np.array([int(v) % 2 ** 64 for v in (seeds.tolist() if isinstance(seeds, (torch.Tensor, np.ndarray)) else seeds)], dtype=np.uint64)
+    if s.shape != (n,):
+        raise ValueError(f"simulate: {s.shape[0] if s.ndim else 1} seeds for {n} images")
+    t = np.array([ops.lsbr_threshold(v) for v in a], dtype=np.uint32)
+    return ops.embed_lsbr(cover_u8, torch.from_numpy(s.view(np.int64)).to(dev), torch.from_numpy(t.view(np.int32)).to(dev))
+
+
+# ---- whole data sets --------------------------------------------------------------------------------------------------------
+
+def folder_name(stego_method: str, alpha: float) -> str:
+    """`stego_<METHOD>_alpha_<a>_independent_images`: the reference's folder scheme with the method in upper case, as its files.csv
+    spells it (the reference's own folders say 'HILLr' / 'LSBr' beside 'HILLR' / 'LSBR' in the name column; that mismatch is not copied)."""
+    return f"stego_{method_name(stego_method)}_alpha_{float(alpha)}_independent_images"
+
+
+def _prefetch(fnames, kws):
+    from .imread import read_luma_batch
+    return (read_luma_batch(fnames),)
+
+
+def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, prefetched=None):
+    """One chunk of covers -> their twins at every alpha, written as 8-bit gray PNGs; one list of files.csv rows per cover."""
+    from PIL import Image
+    from . import ops
+    planes = prefetched[0] if prefetched is not None else _prefetch(fnames, kws)[0]
+    cover = torch.from_numpy(np.ascontiguousarray(planes)).to("cuda")
+    method = method_name(stego_method)
+    key = ops.hill_cost_f64(cover) if method == "HILLR" else None
+    seeds = [image_seed(f, stream) for f in fnames] if method == "LSBR" else None
+    rows = [[] for _ in fnames]
+    for a in alphas:
+        stego = simulate(cover, method, a, seeds, key=key)[0].cpu().numpy()
+        folder = folder_name(method, a)
+        (pathlib.Path(out_dir) / folder).mkdir(parents=True, exist_ok=True)
+        for i, f in enumerate(fnames):
+            name = f"{folder}/{pathlib.Path(f).stem}.png"
+            Image.fromarray(stego[i]).save(pathlib.Path(out_dir) / name)
+            rows[i].append({"name": name, "height": stego.shape[1], "width": stego.shape[2], "stego_method": method, "alpha": float(a)})
+    return rows
+
+
+_write_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(
+    fabrika.shared_kwargs(_write_chunk, ("stego_method", "alphas", "stream", "out_dir"), _prefetch))
+
+
+def write_dataset(data_dir, stego_method: str, alpha, *, split: typing.Optional[str] = None, stream: int = 0) -> typing.List[pathlib.Path]:
+    """Twins of every cover of `data_dir` (images*/files.csv, or the rows of `split`) at `alpha` (one value or several), written
+    beside the covers; returns the folders.  A folder's files.csv lists exactly the files of this call."""
+    import pandas as pd
+    data_dir = pathlib.Path(data_dir)
+    method = method_name(stego_method)
+    alphas = [float(a) for a in np.atleast_1d(np.asarray(alpha, dtype=np.float64))]
+    _alphas(alphas, len(alphas))
+    rows = _write_covers(data_dir, split=split, stego_method=method, alphas=alphas, stream=int(stream), out_dir=str(data_dir))
+    folders = []
+    for j, a in enumerate(alphas):
+        folder = data_dir / folder_name(method, a)
+        pd.DataFrame([r[j] for r in rows], columns=["name", "height", "width", "stego_method", "alpha"]).to_csv(folder / "files.csv", index=False)
+        folders.append(folder)
+    return folders
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser(description="Write simulated stego twins of a data set's covers (HILLR / LSBR, made on the GPU).")
+    ap.add_argument("--data", required=True, help="data set directory (images*/files.csv)")
+    ap.add_argument("--stego-method", required=True, help=" / ".join(METHODS))
+    ap.add_argument("--alphas", type=float, nargs="+", required=True, help="embedding rates in [0, 1]")
+    ap.add_argument("--split", default=None, help="a split CSV of the data set: only its covers")
+    ap.add_argument("--stream", type=int, default=0, help="LSBR realisation number (image_seed)")
+    ns = ap.parse_args(argv)
+    for folder in write_dataset(ns.data, ns.stego_method, ns.alphas, split=ns.split, stream=ns.stream):
+        print(folder)
+
+
+if __name__ == "__main__":
+    main()

@@ -1060,6 +1060,73 @@ def hill_threshold(cost: torch.Tensor, quantile: float = 0.1) -> torch.Tensor:
     return q
 
 
+def _u8_planes(x_u8: torch.Tensor) -> Tuple[int, int, int]:
+    _dev_check(x_u8)
+    if x_u8.dtype != torch.uint8 or x_u8.dim() != 3:
+        raise ValueError(f"expected an (N,H,W) uint8 tensor, got {tuple(x_u8.shape)} {x_u8.dtype}")
+    return tuple(x_u8.shape)
+
+
+def hill_cost_f64(x_u8: torch.Tensor, clamp: float = 1e10) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,H,W) fp64 HILL cost, bit-identical to numpy's float64 restatement (wsu_hill_cost_f64, K20): the
+    ranking key of the HILLR simulator."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(x_u8)
+    key = torch.empty((n, h, w), dtype=torch.float64, device=x_u8.device)
+    check(_launch("hill_cost_f64", {"bytes": float(n * h * w * 9)}, lambda: lib.wsu_hill_cost_f64(
+        x_u8.data_ptr(), key.data_ptr(), float(clamp), n, h, w, _stream())), "wsu_hill_cost_f64")
+    return key
+
+
+def rank_select_f64(key: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
+    """key: (N,H,W) fp64, positive and finite; k: (N) int64 ranks on the device -> (N) int64 holding the uint64 pattern of each
+    image's key of rank k (0-based, ascending; negative: the pattern 0, below every key), by an exact radix select (K21)."""
+    lib = _lib.load()
+    _dev_check(key, k)
+    assert key.dtype == torch.float64 and key.dim() == 3 and k.dtype == torch.int64 and k.shape == (key.shape[0],)
+    n, h, w = key.shape
+    bits = torch.empty(n, dtype=torch.int64, device=key.device)
+    ws = torch.empty(lib.wsu_rank_select_f64_workspace_bytes(n) // 8, dtype=torch.int64, device=key.device)
+    check(_launch("rank_select_f64", {"bytes": float(n * h * w * 48)}, lambda: lib.wsu_rank_select_f64(
+        key.data_ptr(), k.data_ptr(), bits.data_ptr(), ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())), "wsu_rank_select_f64")
+    return bits
+
+
+def embed_threshold(cover_u8: torch.Tensor, key: torch.Tensor, bits: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """stego = cover ^ (key <= the key whose pattern is bits[i]), every tie flipped (K22) -> (stego (N,H,W) uint8, changes (N) int64)."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(cover_u8)
+    _dev_check(key, bits)
+    assert key.dtype == torch.float64 and key.shape == cover_u8.shape and bits.dtype == torch.int64 and bits.shape == (n,)
+    stego = torch.empty_like(cover_u8)
+    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
+    check(_launch("embed_threshold", {"bytes": float(n * h * w * 10)}, lambda: lib.wsu_embed_threshold(
+        cover_u8.data_ptr(), key.data_ptr(), bits.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_threshold")
+    return stego, changes
+
+
+def lsbr_threshold(alpha: float) -> int:
+    """T = floor(alpha / 2 * 2^32) of wsu_embed_lsbr (a pixel flips iff its generator word < T); alpha outside [0, 1] raises."""
+    import ctypes
+    t = ctypes.c_uint32(0)
+    check(_lib.load().wsu_lsbr_threshold(float(alpha), ctypes.byref(t)), "wsu_lsbr_threshold")
+    return t.value
+
+
+def embed_lsbr(cover_u8: torch.Tensor, seeds: torch.Tensor, thresholds: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """LSB replacement with Philox4x32-10 (K23).  seeds: (N) int64 holding the images' 64-bit seeds; thresholds: (N) int32 holding
+    the uint32 lsbr_threshold of each image's alpha -> (stego (N,H,W) uint8, changes (N) int64)."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(cover_u8)
+    _dev_check(seeds, thresholds)
+    assert seeds.dtype == torch.int64 and seeds.shape == (n,) and thresholds.dtype == torch.int32 and thresholds.shape == (n,)
+    stego = torch.empty_like(cover_u8)
+    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
+    check(_launch("embed_lsbr", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbr(
+        cover_u8.data_ptr(), seeds.data_ptr(), thresholds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_lsbr")
+    return stego, changes
+
+
 def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, hat_scale: float = 255.,
                      quantile: float = 0.1, cost: Optional[torch.Tensor] = None, return_threshold: bool = False):
     """Per-image MAE and HILL-cost weighted MAE of a pixel prediction on the interior [1:-1,1:-1] (K12-K14).

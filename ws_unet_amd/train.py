@@ -31,6 +31,7 @@ DEFAULTS: typing.Dict[str, typing.Any] = {
     "learning_rate": 1e-4, "loss": "l1ws", "loss_lambda": 0.25, "network": "unet_2", "num_epochs": 300, "output_dir": "runs",
     "patience": 10, "resume": None, "resume_dir": None, "seed": None, "stego_method": None, "tr_csv": "split_tr.csv",
     "va_csv": "split_va.csv", "take_num_images": None, "mode": None, "train_mode": None,
+    "simulate_stego": False,         # make the stego samples on the device from the covers (data/pairs.py simulate=True): no stego_* folders needed
 }
 
 
@@ -71,12 +72,14 @@ def train(args: typing.Dict[str, typing.Any]) -> float:
 
     stego = None if args["covers_only"] else args["stego_method"]
     alpha = None if args["covers_only"] or args["alpha"] is None else float(args["alpha"])
-    kw = dict(covers_only=bool(args["covers_only"]), rank=rank, world=world, device=dev, take_num_images=args["take_num_images"])
+    kw = dict(covers_only=bool(args["covers_only"]), rank=rank, world=world, device=dev, take_num_images=args["take_num_images"],
+              simulate=bool(args["simulate_stego"]))
     per_rank = args["batch_size"] // world
     tr_loader = PairLoader(args["dataset"], args["tr_csv"], stego, alpha, per_rank, shuffle=True, seed=int(args["seed"] or 0), **kw)
     va_loader = PairLoader(args["dataset"], args["va_csv"], stego, alpha, per_rank, shuffle=False, **kw)
 
-    cfg = {k: v for k, v in args.items() if k not in ("mode", "train_mode", "take_num_images")}
+    # (simulate_stego: written only when set, so that the config.json of every other run is what it was)
+    cfg = {k: v for k, v in args.items() if k not in ("mode", "train_mode", "take_num_images") and (k != "simulate_stego" or v)}
     trainer = Trainer(model, loss=args["loss"], lr=args["learning_rate"], out_dir=out_dir, config=cfg, patience=args["patience"])
     best = trainer.fit(tr_loader, va_loader, args["num_epochs"])
     if rank == 0:
