@@ -324,19 +324,47 @@ void conv3x3_q_kernel(const QArgs a) {
     constexpr bool EPO = !MSPLIT && HC == 0 && RQ != 4;                       // the last step of a tile is split by accumulator tile: its second half shares a basic block with the first half of the epilogue
     f32x16 acc[2][4];                                                         // [MH][RQ] used (fixed bounds: a template-dependent bound made hipcc (ROCm 7.2) drop the host stubs)
     int kt = 0, j = 0;
-    unsigned q_in_off = 0, q_w_off = 0;                                       // this step's input / weight slot
-    const char* ldsA = smem;                                                  // + ((tap * 3 + g) * 64 + m * 32) * 16
-    const char* ldsB = smem;                                                  // + g * PLANE + ((q + dy) * IW + dx) * 16
+    // the slots of this step and of the next one as running offsets (step j lives in input slot j % NIN and weight slot j % NWS, as the loaders count them)
+    unsigned q_in_off = 0, q_w_off = Gm::w_base;
+    unsigned nx_in = 0, nx_w = Gm::w_base;
+    // lane bases of a step's fragment reads, formed BEFORE the step's barrier (begin_step): a_off / b_off of the f16 products
+    // (+ ((tap * planes) * 64 + m * 32) * 16 and + ((q + dy) * IW + dx) * 16), hd_* of the first fp4 unit (tap pair 0), whose reads open the step
+    unsigned a_off = 0, b_off = 0, hd_w = 0, hd_sa = 0, hd_b = 0, hd_sb = 0;
     int hh_q = hh;                                                            // an opaque copy of the lane half per step: keeps the tap-pair offsets of the cross terms from being hoisted out of the tile loop (and spilled)
+    typedef __attribute__((address_space(3))) const unsigned char lds_cuchar;
+    typedef __attribute__((address_space(3))) const int lds_cint;
+    typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
+    lds_char* const L = (lds_char*)smem;
+    const unsigned Lb = (unsigned)(size_t)L;                                  // the pinned bases are absolute LDS addresses (at()): no add behind the barrier
+    auto at = [](unsigned addr) __attribute__((always_inline)) { return (lds_char*)(size_t)addr; };
     auto begin_step = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_s_barrier();                                         // the loaders' pieces landed; everyone left the slots that are refilled next
-        asm volatile("" ::: "memory");
-        q_in_off = (unsigned)(j % NIN) * Gm::in_slot; q_w_off = Gm::w_base + (unsigned)(j % NWS) * Gm::w_slot;
-        ldsA = smem + q_w_off + (cur.mh * 32 + l31) * 16;
-        ldsB = smem + q_in_off + ((RQ * wv) * IW + l31) * 16;
+        // everything the first reads of the step need depends on the step count, the tile and the lane only: it is formed here, where a wave waits
+        // for the others anyway, and pinned in front of the barrier (the empty asm statements and the barrier keep their order) -- behind the
+        // barrier the step opens with its LDS reads.  The pinned values are opaque, so nothing of them is hoisted out of the tile loop either.
+        q_in_off = nx_in; q_w_off = nx_w;
+        nx_in = nx_in + (unsigned)Gm::in_slot == (unsigned)(NIN * Gm::in_slot) ? 0u : nx_in + (unsigned)Gm::in_slot;
+        static_assert(NWS == 2, "nx_w toggles between the two weight slots the loaders fill as s % NWS");
+        nx_w = (unsigned)(2 * Gm::w_base + Gm::w_slot) - nx_w;
         hh_q = hh;
         asm volatile("" : "+v"(hh_q));
+        a_off = Lb + q_w_off + (unsigned)((cur.mh * 32 + l31) * 16) + (unsigned)(hh * 64 * 16);
+        b_off = Lb + q_in_off + (unsigned)(((RQ * wv) * IW + l31) * 16) + (unsigned)(hh * PLANE);
+        if constexpr (!H) {
+            const int tap = hh_q ? 1 : 0;                                     // tap pair 0: lanes 0-31 tap 0, lanes 32-63 tap 1 (pixel offset = tap)
+            const unsigned pix = (unsigned)((RQ * wv) * IW + l31 + tap);
+            hd_w = Lb + q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u + (unsigned)((tap * 3 + 2) * 64) * 16u;
+            hd_sa = Lb + q_w_off + W_GRAN + (unsigned)(tap * 64 + cur.mh * 32 + l31);
+            hd_b = Lb + q_in_off + 2 * PLANE + pix * 16u;
+            hd_sb = Lb + q_in_off + 3 * PLANE + pix * 4u;
+            asm volatile("" : "+v"(a_off), "+v"(b_off), "+v"(hd_w), "+v"(hd_sa), "+v"(hd_b), "+v"(hd_sb));
+        } else {
+            asm volatile("" : "+v"(a_off), "+v"(b_off));
+        }
+        __builtin_amdgcn_s_barrier();                                         // the loaders' pieces landed; everyone left the slots that are refilled next
+        asm volatile("" ::: "memory");
     };
+    // the accumulators are cleared only where a tile has a single step (nch == 1: its first step is the split last step); everywhere else the
+    // first unit of the tile's first step takes a literal zero as its C operand (FIRST below) -- the same sums, no 64 moves per wave and tile
     auto zero_acc = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int m = 0; m < MH; ++m)
@@ -345,45 +373,50 @@ void conv3x3_q_kernel(const QArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][q][r] = 0.f;
     };
-    auto main_term = [&](auto tap_c, auto ms_c) __attribute__((always_inline)) {
+    // FIRST (here and below): the unit opens a tile -- its matrix instructions take the literal zero for C and define the accumulators
+    auto main_term = [&](auto tap_c, auto ms_c, auto first_c) __attribute__((always_inline)) {
         constexpr int tap = decltype(tap_c)::value, dy = tap / 3, dx = tap % 3;
         constexpr int ms = decltype(ms_c)::value, ML = ms < 0 ? 0 : ms, MU = ms < 0 ? MH : ms + 1;
+        constexpr bool FIRST = decltype(first_c)::value;
         u32x4 ah[2], bh[4];
 _Pragma("unroll")
-        for (int m = ML; m < MU; ++m) ah[m] = *reinterpret_cast<const u32x4*>(ldsA + ((tap * Gm::w_planes + hh) * 64 + m * 32) * 16);
+        for (int m = ML; m < MU; ++m) ah[m] = *(lds_cu32x4*)(at(a_off) + ((tap * Gm::w_planes) * 64 + m * 32) * 16);
 _Pragma("unroll")
-        for (int q = 0; q < RQ; ++q) bh[q] = *reinterpret_cast<const u32x4*>(ldsB + hh * PLANE + ((q + dy) * IW + dx) * 16);
+        for (int q = 0; q < RQ; ++q) bh[q] = *(lds_cu32x4*)(at(b_off) + ((q + dy) * IW + dx) * 16);
 _Pragma("unroll")
         for (int m = ML; m < MU; ++m)
 _Pragma("unroll")
-            for (int q = 0; q < RQ; ++q) wsu_mfma_f16(ah[m], bh[q], acc[m][q]);
+            for (int q = 0; q < RQ; ++q) {
+                if constexpr (FIRST) acc[m][q] = wsu_mfma_f16_z(ah[m], bh[q]);
+                else wsu_mfma_f16(ah[m], bh[q], acc[m][q]);
+            }
     };
     // both cross terms of a tap pair in one fp4 instruction -- lane half hh carries tap 2 tp + hh: weight granule plane 2 and the pixel's Q granule,
     // each with its E8M0 scale byte (per (tap, co) / per pixel)
-    auto cross_q4 = [&](auto tp_c, auto ms_c) __attribute__((always_inline)) {
+    auto cross_q4 = [&](auto tp_c, auto ms_c, auto first_c) __attribute__((always_inline)) {
         constexpr int tp = decltype(tp_c)::value;
         constexpr int ms = decltype(ms_c)::value, ML = ms < 0 ? 0 : ms, MU = ms < 0 ? MH : ms + 1;
+        constexpr bool FIRST = decltype(first_c)::value;
         constexpr int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 2 * tp;
         constexpr bool single = 2 * tp + 1 >= 9;
+        constexpr bool HEAD_UNIT = tp == 0 && ms <= 0;                        // the unit that opens a step: its lane bases come from begin_step
         const int tap = hh_q ? t1 : t0;
         const int pixoff = (tap / 3) * IW + tap % 3;
         u32x4 a4[2], b4[4]; int sa[2], sb[4];
-        typedef __attribute__((address_space(3))) const unsigned char lds_cuchar;
-        typedef __attribute__((address_space(3))) const int lds_cint;
-        typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
-        lds_char* L = (lds_char*)smem;
-        const unsigned wbase = q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u + (unsigned)((tap * 3 + 2) * 64) * 16u;
-        const unsigned sabase = q_w_off + W_GRAN + (unsigned)(tap * 64 + cur.mh * 32 + l31);
         const unsigned pix = (unsigned)((RQ * wv) * IW + l31 + pixoff);
+        const unsigned wbase = HEAD_UNIT ? hd_w : Lb + q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u + (unsigned)((tap * 3 + 2) * 64) * 16u;
+        const unsigned sabase = HEAD_UNIT ? hd_sa : Lb + q_w_off + W_GRAN + (unsigned)(tap * 64 + cur.mh * 32 + l31);
+        const unsigned bbase = HEAD_UNIT ? hd_b : Lb + q_in_off + 2 * PLANE + pix * 16u;
+        const unsigned sbbase = HEAD_UNIT ? hd_sb : Lb + q_in_off + 3 * PLANE + pix * 4u;
 _Pragma("unroll")
         for (int m = ML; m < MU; ++m) {
-            a4[m] = *(lds_cu32x4*)(L + wbase + m * 32 * 16);
-            sa[m] = *(lds_cuchar*)(L + sabase + m * 32);
+            a4[m] = *(lds_cu32x4*)(at(wbase) + m * 32 * 16);
+            sa[m] = *(lds_cuchar*)(at(sabase) + m * 32);
         }
 _Pragma("unroll")
         for (int q = 0; q < RQ; ++q) {
-            b4[q] = *(lds_cu32x4*)(L + q_in_off + 2 * PLANE + (pix + q * IW) * 16u);
-            sb[q] = *(lds_cint*)(L + q_in_off + 3 * PLANE + (pix + q * IW) * 4u);      // the pixel's dword slot: byte 0 = its scale byte
+            b4[q] = *(lds_cu32x4*)(at(bbase) + (q * IW) * 16u);
+            sb[q] = *(lds_cint*)(at(sbbase) + (q * IW) * 4u);                  // the pixel's dword slot: byte 0 = its scale byte
         }
         if (single && hh_q) {
             const u32x4 z = mk_u4(0, 0, 0, 0);
@@ -395,16 +428,25 @@ _Pragma("unroll")
 _Pragma("unroll")
         for (int m = ML; m < MU; ++m)
 _Pragma("unroll")
-            for (int q = 0; q < RQ; ++q) wsu_mfma_q4(a4[m], b4[q], sa[m], sb[q], acc[m][q]);
+            for (int q = 0; q < RQ; ++q) {
+                if constexpr (FIRST) acc[m][q] = wsu_mfma_q4_z(a4[m], b4[q], sa[m], sb[q]);
+                else wsu_mfma_q4(a4[m], b4[q], sa[m], sb[q], acc[m][q]);
+            }
     };
-    auto units_range = [&](auto ms_c, auto lo_c, auto hi_c) __attribute__((always_inline)) {     // tap pairs [lo, hi)
+    constexpr std::false_type not_first{};
+    constexpr std::true_type tile_first{};
+    auto units_range = [&](auto ms_c, auto lo_c, auto hi_c, auto first_c) __attribute__((always_inline)) {     // tap pairs [lo, hi)
         constexpr int lo = decltype(lo_c)::value, hi = decltype(hi_c)::value;
-        if constexpr (EPO) asm volatile("" : "+v"(hh_q));                     // (per call: the paths of a step must not share -- and hoist -- their lane offsets)
+        constexpr bool FIRST = decltype(first_c)::value;
+        static_assert(!FIRST || lo == 0, "a tile opens with tap pair 0");
+        // (per call: the paths of a step must not share -- and hoist -- their lane offsets.  Not in front of the unit that opens a step: its
+        // offsets were formed before the barrier)
+        if constexpr (EPO && !(lo == 0 && decltype(ms_c)::value <= 0)) asm volatile("" : "+v"(hh_q));
         WSU_STATIC_FOR(hi - lo, i, {
             constexpr int tp = lo + i;
-            if constexpr (!H) cross_q4(std::integral_constant<int, tp>{}, ms_c);
-            main_term(std::integral_constant<int, 2 * tp>{}, ms_c);
-            if constexpr (2 * tp + 1 < 9) main_term(std::integral_constant<int, 2 * tp + 1>{}, ms_c);
+            if constexpr (!H) cross_q4(std::integral_constant<int, tp>{}, ms_c, std::integral_constant<bool, FIRST && tp == 0>{});
+            main_term(std::integral_constant<int, 2 * tp>{}, ms_c, std::integral_constant<bool, FIRST && H && tp == 0>{});
+            if constexpr (2 * tp + 1 < 9) main_term(std::integral_constant<int, 2 * tp + 1>{}, ms_c, not_first);
         });
     };
     constexpr std::integral_constant<int, -1> all_m{};
@@ -417,26 +459,24 @@ _Pragma("unroll")
     struct Frag { u32x4 a[2]; u32x4 b[4]; int sa[2]; int sb[4]; };
     auto load_unit = [&](auto u_c, Frag& f) __attribute__((always_inline)) {
         constexpr int u = decltype(u_c)::value, tp = u / 3, k = u % 3;
-        typedef __attribute__((address_space(3))) const unsigned char lds_cuchar;
-        typedef __attribute__((address_space(3))) const int lds_cint;
-        typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
-        lds_char* L = (lds_char*)smem;
         if constexpr (k == 0) {
             constexpr int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 2 * tp;
             const int tap = hh_q ? t1 : t0;
             const int pixoff = (tap / 3) * IW + tap % 3;
-            const unsigned wbase = q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u + (unsigned)((tap * 3 + 2) * 64) * 16u;
-            const unsigned sabase = q_w_off + W_GRAN + (unsigned)(tap * 64 + cur.mh * 32 + l31);
             const unsigned pix = (unsigned)((RQ * wv) * IW + l31 + pixoff);
+            const unsigned wbase = u == 0 ? hd_w : Lb + q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u + (unsigned)((tap * 3 + 2) * 64) * 16u;
+            const unsigned sabase = u == 0 ? hd_sa : Lb + q_w_off + W_GRAN + (unsigned)(tap * 64 + cur.mh * 32 + l31);
+            const unsigned bbase = u == 0 ? hd_b : Lb + q_in_off + 2 * PLANE + pix * 16u;
+            const unsigned sbbase = u == 0 ? hd_sb : Lb + q_in_off + 3 * PLANE + pix * 4u;
 _Pragma("unroll")
             for (int m = 0; m < MH; ++m) {
-                f.a[m] = *(lds_cu32x4*)(L + wbase + m * 32 * 16);
-                f.sa[m] = *(lds_cuchar*)(L + sabase + m * 32);
+                f.a[m] = *(lds_cu32x4*)(at(wbase) + m * 32 * 16);
+                f.sa[m] = *(lds_cuchar*)(at(sabase) + m * 32);
             }
 _Pragma("unroll")
             for (int q = 0; q < RQ; ++q) {
-                f.b[q] = *(lds_cu32x4*)(L + q_in_off + 2 * PLANE + (pix + q * IW) * 16u);
-                f.sb[q] = *(lds_cint*)(L + q_in_off + 3 * PLANE + (pix + q * IW) * 4u);
+                f.b[q] = *(lds_cu32x4*)(at(bbase) + (q * IW) * 16u);
+                f.sb[q] = *(lds_cint*)(at(sbbase) + (q * IW) * 4u);
             }
         } else {
             constexpr int tap = 2 * tp + k - 1, dy = tap / 3, dx = tap % 3;
@@ -448,8 +488,9 @@ _Pragma("unroll")
             for (int q = 0; q < RQ; ++q) f.b[q] = *(lds_cu32x4*)(L + bbase + ((q + dy) * IW + dx) * 16);
         }
     };
-    auto mma_unit = [&](auto u_c, Frag& f) __attribute__((always_inline)) {
+    auto mma_unit = [&](auto u_c, Frag& f, auto first_c) __attribute__((always_inline)) {
         constexpr int u = decltype(u_c)::value, tp = u / 3, k = u % 3;
+        constexpr bool FIRST = decltype(first_c)::value && u == 0;
         if constexpr (k == 0) {
             if (2 * tp + 1 >= 9 && hh_q) {                                    // the ninth tap has no partner: lanes 32-63 multiply zeros
                 const u32x4 z = mk_u4(0, 0, 0, 0);
@@ -461,7 +502,10 @@ _Pragma("unroll")
 _Pragma("unroll")
             for (int m = 0; m < MH; ++m)
 _Pragma("unroll")
-                for (int q = 0; q < RQ; ++q) wsu_mfma_q4(f.a[m], f.b[q], f.sa[m], f.sb[q], acc[m][q]);
+                for (int q = 0; q < RQ; ++q) {
+                    if constexpr (FIRST) acc[m][q] = wsu_mfma_q4_z(f.a[m], f.b[q], f.sa[m], f.sb[q]);
+                    else wsu_mfma_q4(f.a[m], f.b[q], f.sa[m], f.sb[q], acc[m][q]);
+                }
         } else {
 _Pragma("unroll")
             for (int m = 0; m < MH; ++m)
@@ -469,20 +513,20 @@ _Pragma("unroll")
                 for (int q = 0; q < RQ; ++q) wsu_mfma_f16(f.a[m], f.b[q], acc[m][q]);
         }
     };
-    auto units_pipelined = [&]() __attribute__((always_inline)) {
+    auto units_pipelined = [&](auto first_c) __attribute__((always_inline)) {
         constexpr int NU = 14;                                                // one unit of reads in flight, two fragment sets
         Frag fr[2];
         load_unit(std::integral_constant<int, 0>{}, fr[0]);
         WSU_STATIC_FOR(NU, u, {
             if constexpr (u + 1 < NU) load_unit(std::integral_constant<int, u + 1>{}, fr[(u + 1) % 2]);
             __builtin_amdgcn_sched_barrier(0);                                // (the reads FIRST: left to itself the scheduler sinks them behind most of the unit's matrix instructions)
-            mma_unit(u_c, fr[u % 2]);
+            mma_unit(u_c, fr[u % 2], first_c);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
-    auto units_all = [&](auto ms_c) __attribute__((always_inline)) {
-        if constexpr (PIPE && decltype(ms_c)::value < 0) { units_pipelined(); return; }      // (the split last step of EPO keeps the unpipelined units of its half)
-        units_range(ms_c, std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{});
+    auto units_all = [&](auto ms_c, auto first_c) __attribute__((always_inline)) {
+        if constexpr (PIPE && decltype(ms_c)::value < 0) { units_pipelined(first_c); return; }      // (the split last step of EPO keeps the unpipelined units of its half)
+        units_range(ms_c, std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{}, first_c);
     };
 
     // ---- epilogue of the tile: accumulators -> planar global memory ---------------------------------------------------------------------
@@ -548,6 +592,7 @@ _Pragma("unroll")
         auto epi_m = [&](auto m_c, auto&& hook) __attribute__((always_inline)) {   // one accumulator tile along the output channels: 32 channels x this wave's RQ x 32 pixels
             constexpr int m = decltype(m_c)::value;
             constexpr int NH = RQ / 2;                                         // hooks per piece: one before each row pair
+            f32x4 spx, spy;                                                    // POOL, planar Q, RQ = 2: piece 0's pooled row, kept for the encode it shares with piece 1's
             auto piece = [&](auto cp_c) __attribute__((always_inline)) {       // 16 output channels = accumulator groups g4 = 2cp, 2cp+1
                 constexpr int cp = decltype(cp_c)::value;
                 const int oc = cur.cb * 4 + (m + cur.mh) * 2 + cp;
@@ -630,8 +675,21 @@ _Pragma("unroll")
                         if constexpr (RQ == 4) {
                             store_pair_q(px[0], py[0], px[1], py[1], base, cbp, php16, (unsigned)(gy0 * wp2 + gx) * 16u, (unsigned)((gy0 + 1) * wp2 + gx) * 16u,
                                          wsu_q_soff(gy0, gx, ptx), wsu_q_soff(gy0 + 1, gx, ptx), okx && gy0 < hp, okx && gy0 + 1 < hp, true);
+                        } else if constexpr (cp == 0) {
+                            spx = px[0]; spy = py[0];
                         } else {
-                            store_one_q(px[0], py[0], base, cbp, php16, (unsigned)(gy0 * wp2 + gx) * 16u, wsu_q_soff(gy0, gx, ptx), okx && gy0 < hp, true);
+                            // ONE encode per accumulator tile: both lanes of a pair (l, l ^ 1) hold the pooled pixel, so the even lane keeps piece 0's
+                            // 16 channels of it and the odd lane takes piece 1's (the exchanges of the encoding pair lane l with l + 32: same parity);
+                            // the odd lanes store one chunk further, under a descriptor that spans both chunks.  Relies on the layout of a planar
+                            // tensor: the chunks oc - 1 (piece 0) and oc (piece 1) of an image lie cbp bytes apart ([n][C / 16] chunks of cbp bytes),
+                            // and on 2 * cbp fitting the descriptor's 32-bit extent (a pooled chunk is a quarter of a chunk the entry points keep below 4 GiB)
+                            static_assert(cp == 1, "piece 1 closes the pair: its chunk follows piece 0's");
+                            const bool odd = (l31 & 1) != 0;
+                            f32x4 sx, sy;
+_Pragma("unroll")
+                            for (int e = 0; e < 4; ++e) { sx[e] = odd ? px[0][e] : spx[e]; sy[e] = odd ? py[0][e] : spy[e]; }
+                            const unsigned coff = odd ? cbp : 0u;
+                            store_one_q(sx, sy, base - cbp, 2u * cbp, php16, (unsigned)(gy0 * wp2 + gx) * 16u + coff, wsu_q_soff(gy0, gx, ptx) + coff, gx < wp2 && gy0 < hp, true);
                         }
                     } else {
                         char* base = a.ypool + (((size_t)cur.n * nco + oc) * 3) * php16;
@@ -651,7 +709,7 @@ _Pragma("unroll")
             epi_m(std::integral_constant<int, 0>{}, [&](auto h_c) __attribute__((always_inline)) {
                 constexpr int h = decltype(h_c)::value;
                 constexpr int lo = 5 * h / NHT, hi = 5 * (h + 1) / NHT;
-                if constexpr (hi > lo) units_range(std::integral_constant<int, 1>{}, std::integral_constant<int, lo>{}, std::integral_constant<int, hi>{});
+                if constexpr (hi > lo) units_range(std::integral_constant<int, 1>{}, std::integral_constant<int, lo>{}, std::integral_constant<int, hi>{}, not_first);
             });
             epi_m(std::integral_constant<int, 1>{}, nothing);
         } else {
@@ -687,11 +745,15 @@ _Pragma("unroll")
     };
     // one loop nest per tile, the last step spelled out after the inner loop
     for (int t = 0; t < K; ++t) {
-        zero_acc();
-        for (int cc = 1; cc < a.nch; ++cc) { begin_step(); units_all(all_m); ++j; }
+        if (a.nch == 1) {
+            zero_acc();
+        } else {
+            begin_step(); units_all(all_m, tile_first); ++j;                  // the tile's first step defines the accumulators
+            for (int cc = 2; cc < a.nch; ++cc) { begin_step(); units_all(all_m, not_first); ++j; }
+        }
         begin_step();
-        if constexpr (EPO) units_all(std::integral_constant<int, 0>{});       // the last step: m = 0 first; m = 1 follows inside the epilogue
-        else units_all(all_m);
+        if constexpr (EPO) units_all(std::integral_constant<int, 0>{}, not_first);       // the last step: m = 0 first; m = 1 follows inside the epilogue
+        else units_all(all_m, not_first);
         // scheduling fence between the tile's last step and its epilogue: scheduled as one region the eight-wave instantiations <2, 0, *, *, false, ...>
         // take 168 registers and spill 1-3 of them; with the fence 133-147 and none (a timing-only branch stood here and ended the block: 162-164)
         __builtin_amdgcn_sched_barrier(0);

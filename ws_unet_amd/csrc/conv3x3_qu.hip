@@ -274,32 +274,64 @@ void conv3x3_qu_kernel(const UArgs a) {
     typedef __attribute__((address_space(3))) const int lds_cint;
     typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
     lds_char* L = (lds_char*)smem;
-    auto sync_step = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        hh_q = hh;
-        asm volatile("" : "+v"(hh_q));
-    };
+    const unsigned Lb = (unsigned)(size_t)L;                                 // the pinned bases are absolute LDS addresses (at())
+    auto at = [](unsigned addr) __attribute__((always_inline)) { return (lds_char*)(size_t)addr; };
     // byte offset of tap (ky, kx)'s source pixel relative to the lane's own class pixel, in the class planes of the skip tile
     auto tap_s = [&](int ky, int kx) __attribute__((always_inline)) {
         return (unsigned)(((((py + ky) & 1) * 2 + ((px + kx) & 1)) * CPIX + ((py + ky) >> 1) * CW + ((px + kx) >> 1)) * 16);
     };
+    // lane bases of a step's fragment reads, formed BEFORE the step's barrier (sync_step): a_off / b_off of the f16 products (weights: + the
+    // unit's planes and the 32-channel half; input: + the tap's pixel offset and the matrix tile), hd_* of the fp4 unit that opens the step
+    unsigned a_off = 0, b_off = 0, hd_w = 0, hd_sa = 0, hd_b = 0, hd_sb = 0;
+    // a step of kind S (LOW = false) or L: takes the next region and forms everything the step's first reads need -- it depends on the step
+    // count, the wave and the lane only -- in front of the barrier, where a wave waits for the others anyway.  The empty asm statements pin the
+    // values there (they and the barrier keep their order) and make them opaque per step, like hh_q: nothing is hoisted out of the tile loop.
+    // Behind the barrier the step opens with its LDS reads.
+    auto sync_step = [&](auto low_c) __attribute__((always_inline)) {
+        constexpr bool LOW = decltype(low_c)::value;
+        const unsigned r = next_region();
+        in_off = LOW ? r + OFF_LIN : r;
+        w_off = LOW ? r : r + OFF_SW;
+        hh_q = hh;
+        asm volatile("" : "+v"(hh_q));
+        a_off = Lb + w_off + (unsigned)l31 * 16u + (unsigned)hh * 1024u;
+        b_off = Lb + in_off + (unsigned)hh * (LOW ? PLANE_L : PLANE_S) + (LOW ? laneL : laneS);
+        if constexpr (!H) {
+            // S: tap pair 0 = taps (0, 0) | (0, 1) by lane half; L: dy = 0, unit cls * 2 + dx with dx = the lane half
+            const int u = LOW ? cls * 2 + hh_q : hh_q;
+            const unsigned pb = LOW ? (unsigned)((py * LP + px) * 16) + (unsigned)hh_q * 16u + laneL : (hh_q ? tap_s(0, 1) : tap_s(0, 0)) + laneS;
+            hd_w = Lb + w_off + (unsigned)((u * 3 + 2) * 64 + l31) * 16u;
+            hd_sa = Lb + w_off + (LOW ? W_GRAN_L : W_GRAN_S) + (unsigned)(u * 64 + l31);
+            hd_b = Lb + in_off + 2 * (LOW ? PLANE_L : PLANE_S) + pb;
+            hd_sb = Lb + in_off + 3 * (LOW ? PLANE_L : PLANE_S) + (pb >> 2);
+            asm volatile("" : "+v"(a_off), "+v"(b_off), "+v"(hd_w), "+v"(hd_sa), "+v"(hd_b), "+v"(hd_sb));
+        } else {
+            asm volatile("" : "+v"(a_off), "+v"(b_off));
+        }
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
     // ---- a skip chunk: the nine taps of the ordinary conv, operands of conv3x3_q.hip (f16 products per tap, both cross terms of a tap pair as one fp4 instruction)
-    auto skip_units = [&]() __attribute__((always_inline)) {
+    // FIRST: the step opens a tile -- the matrix instructions of its first unit take the literal zero for C and define the accumulators
+    auto skip_units = [&](auto first_c) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_c)::value;
         WSU_STATIC_FOR(5, tp, {
             constexpr int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 2 * tp;
             if constexpr (!H) {
                 const unsigned tapo = hh_q ? tap_s(t1 / 3, t1 % 3) : tap_s(t0 / 3, t0 % 3);
                 const int tap = hh_q ? t1 : t0;
                 u32x4 a4[2], b4[2]; int sa[2], sb[2];
-                const unsigned wb = w_off + (unsigned)((tap * 3 + 2) * 64 + l31) * 16u, sab = w_off + W_GRAN_S + (unsigned)(tap * 64 + l31);
                 const unsigned pb = tapo + laneS;
+                const unsigned wb = tp == 0 ? hd_w : Lb + w_off + (unsigned)((tap * 3 + 2) * 64 + l31) * 16u;
+                const unsigned sab = tp == 0 ? hd_sa : Lb + w_off + W_GRAN_S + (unsigned)(tap * 64 + l31);
+                const unsigned bb = tp == 0 ? hd_b : Lb + in_off + 2 * PLANE_S + pb;
+                const unsigned sbb = tp == 0 ? hd_sb : Lb + in_off + 3 * PLANE_S + (pb >> 2);
 _Pragma("unroll")
-                for (int m = 0; m < 2; ++m) { a4[m] = *(lds_cu32x4*)(L + wb + m * 512); sa[m] = *(lds_cuchar*)(L + sab + m * 32); }
+                for (int m = 0; m < 2; ++m) { a4[m] = *(lds_cu32x4*)(at(wb) + m * 512); sa[m] = *(lds_cuchar*)(at(sab) + m * 32); }
 _Pragma("unroll")
                 for (int q = 0; q < 2; ++q) {
-                    b4[q] = *(lds_cu32x4*)(L + in_off + 2 * PLANE_S + pb + q * QS);
-                    sb[q] = *(lds_cint*)(L + in_off + 3 * PLANE_S + ((pb + q * QS) >> 2));
+                    b4[q] = *(lds_cu32x4*)(at(bb) + q * QS);
+                    sb[q] = *(lds_cint*)(at(sbb) + q * (QS >> 2));
                 }
                 if (2 * tp + 1 >= 9 && hh_q) {                            // the ninth tap has no partner: lanes 32-63 multiply zeros
                     const u32x4 z = mk_u4(0, 0, 0, 0);
@@ -308,38 +340,48 @@ _Pragma("unroll")
 _Pragma("unroll")
                 for (int m = 0; m < 2; ++m)
 _Pragma("unroll")
-                    for (int q = 0; q < 2; ++q) wsu_mfma_q4(a4[m], b4[q], sa[m], sb[q], acc[m][q]);
+                    for (int q = 0; q < 2; ++q) {
+                        if constexpr (FIRST && tp == 0) acc[m][q] = wsu_mfma_q4_z(a4[m], b4[q], sa[m], sb[q]);
+                        else wsu_mfma_q4(a4[m], b4[q], sa[m], sb[q], acc[m][q]);
+                    }
             }
             WSU_STATIC_FOR((2 * tp + 1 < 9 ? 2 : 1), k, {
                 constexpr int tap = 2 * tp + k;
                 u32x4 ah[2], bh[2];
-                const unsigned wb = w_off + (unsigned)((tap * WPL) * 64 + l31) * 16u + (unsigned)hh * 1024u;
-                const unsigned pb = in_off + (unsigned)hh * PLANE_S + tap_s(tap / 3, tap % 3) + laneS;
+                const unsigned pb = b_off + tap_s(tap / 3, tap % 3);
 _Pragma("unroll")
-                for (int m = 0; m < 2; ++m) ah[m] = *(lds_cu32x4*)(L + wb + m * 512);
+                for (int m = 0; m < 2; ++m) ah[m] = *(lds_cu32x4*)(at(a_off) + ((tap * WPL) * 64) * 16 + m * 512);
 _Pragma("unroll")
-                for (int q = 0; q < 2; ++q) bh[q] = *(lds_cu32x4*)(L + pb + q * QS);
+                for (int q = 0; q < 2; ++q) bh[q] = *(lds_cu32x4*)(at(pb) + q * QS);
 _Pragma("unroll")
                 for (int m = 0; m < 2; ++m)
 _Pragma("unroll")
-                    for (int q = 0; q < 2; ++q) wsu_mfma_f16(ah[m], bh[q], acc[m][q]);
+                    for (int q = 0; q < 2; ++q) {
+                        if constexpr (FIRST && H && tap == 0) acc[m][q] = wsu_mfma_f16_z(ah[m], bh[q]);
+                        else wsu_mfma_f16(ah[m], bh[q], acc[m][q]);
+                    }
             });
         });
     };
     // ---- a dy slice of a low chunk: taps (dy, 0) and (dy, 1) of this wave's class -- units cls * 2 + dx of the slice [8][3 planes][64 co][16 B] + [8][64] scale bytes
-    auto low_units = [&](int dy) __attribute__((always_inline)) {
+    auto low_units = [&](auto dy_c) __attribute__((always_inline)) {
+        constexpr int dy = decltype(dy_c)::value;
+        constexpr unsigned WDY = dy ? (unsigned)(OFF_LW1) : 0u;               // the dy = 1 slice of the step's weights, relative to the dy = 0 slice
         const unsigned rowo = (unsigned)(((py + dy) * LP + px) * 16);
         if constexpr (!H) {
             const int u = cls * 2 + hh_q;                                   // lanes 32-63: dx = 1
             u32x4 a4[2], b4[2]; int sa[2], sb[2];
-            const unsigned wb = w_off + (unsigned)((u * 3 + 2) * 64 + l31) * 16u, sab = w_off + W_GRAN_L + (unsigned)(u * 64 + l31);
             const unsigned pb = rowo + (unsigned)hh_q * 16u + laneL;
+            const unsigned wb = dy == 0 ? hd_w : Lb + w_off + WDY + (unsigned)((u * 3 + 2) * 64 + l31) * 16u;
+            const unsigned sab = dy == 0 ? hd_sa : Lb + w_off + WDY + W_GRAN_L + (unsigned)(u * 64 + l31);
+            const unsigned bb = dy == 0 ? hd_b : Lb + in_off + 2 * PLANE_L + pb;
+            const unsigned sbb = dy == 0 ? hd_sb : Lb + in_off + 3 * PLANE_L + (pb >> 2);
 _Pragma("unroll")
-            for (int m = 0; m < 2; ++m) { a4[m] = *(lds_cu32x4*)(L + wb + m * 512); sa[m] = *(lds_cuchar*)(L + sab + m * 32); }
+            for (int m = 0; m < 2; ++m) { a4[m] = *(lds_cu32x4*)(at(wb) + m * 512); sa[m] = *(lds_cuchar*)(at(sab) + m * 32); }
 _Pragma("unroll")
             for (int q = 0; q < 2; ++q) {
-                b4[q] = *(lds_cu32x4*)(L + in_off + 2 * PLANE_L + pb + q * QL);
-                sb[q] = *(lds_cint*)(L + in_off + 3 * PLANE_L + ((pb + q * QL) >> 2));
+                b4[q] = *(lds_cu32x4*)(at(bb) + q * QL);
+                sb[q] = *(lds_cint*)(at(sbb) + q * (QL >> 2));
             }
 _Pragma("unroll")
             for (int m = 0; m < 2; ++m)
@@ -348,12 +390,12 @@ _Pragma("unroll")
         }
         WSU_STATIC_FOR(2, dx, {
             u32x4 ah[2], bh[2];
-            const unsigned wb = w_off + (unsigned)(((cls * 2 + dx) * WPL) * 64 + l31) * 16u + (unsigned)hh * 1024u;
-            const unsigned pb = in_off + (unsigned)hh * PLANE_L + rowo + dx * 16u + laneL;
+            const unsigned wb = a_off + WDY + (unsigned)(((cls * 2 + dx) * WPL) * 64) * 16u;
+            const unsigned pb = b_off + rowo + dx * 16u;
 _Pragma("unroll")
-            for (int m = 0; m < 2; ++m) ah[m] = *(lds_cu32x4*)(L + wb + m * 512);
+            for (int m = 0; m < 2; ++m) ah[m] = *(lds_cu32x4*)(at(wb) + m * 512);
 _Pragma("unroll")
-            for (int q = 0; q < 2; ++q) bh[q] = *(lds_cu32x4*)(L + pb + q * QL);
+            for (int q = 0; q < 2; ++q) bh[q] = *(lds_cu32x4*)(at(pb) + q * QL);
 _Pragma("unroll")
             for (int m = 0; m < 2; ++m)
 _Pragma("unroll")
@@ -416,26 +458,18 @@ _Pragma("unroll")
     };
 
     for (int t = 0; t < K; ++t) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[m][q][r] = 0.f;
-        for (int c = 0; c < a.nchS; ++c) {
-            sync_step();
-            const unsigned r = next_region();
-            in_off = r; w_off = r + OFF_SW;
-            skip_units();
+        // a tile opens with a skip chunk: no accumulator clear, its first unit writes C = 0 + products.  nchS >= 1 is what the loaders count on too
+        // (one barrier per step on both sides): wsu_conv3x3_up_q_fwd / _h_fwd refuse c2 == 0 (WSU_REQUIRE) before anything is launched
+        sync_step(std::false_type{});
+        skip_units(std::true_type{});
+        for (int c = 1; c < a.nchS; ++c) {
+            sync_step(std::false_type{});
+            skip_units(std::false_type{});
         }
         for (int c = 0; c < a.nchL; ++c) {                                    // one step: dy = 0 then dy = 1, the accumulation order of the two-kernel path
-            sync_step();
-            const unsigned r = next_region();
-            in_off = r + OFF_LIN;
-            w_off = r;
-            low_units(0);
-            w_off = r + OFF_LW1;
-            low_units(1);
+            sync_step(std::true_type{});
+            low_units(std::integral_constant<int, 0>{});
+            low_units(std::integral_constant<int, 1>{});
         }
         finish_tile();
         if (t + 1 < K) cur = tile_of(a, lw + (t + 1) * G);

@@ -326,6 +326,13 @@ __device__ __forceinline__ void wsu_mfma_q4(const u32x4& a, const u32x4& b, int 
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 4, 4, 0, scale_a, 0, scale_b);
 }
 
+// ... with a literal zero for C: the unit that opens an accumulation (`v_mfma ..., 0`: the sums of wsu_mfma_q4 on cleared accumulators, no clear)
+__device__ __forceinline__ f32x16 wsu_mfma_q4_z(const u32x4& a, const u32x4& b, int scale_a, int scale_b) {
+    const i32x8 av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w, 0, 0, 0, 0}, bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w, 0, 0, 0, 0};
+    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, z, 4, 4, 0, scale_a, 0, scale_b);
+}
+
 // the same for a stored GRADIENT granule: e4m3(g * 4)
 __device__ __forceinline__ u32x2 wsu_f16x8_to_fp8_grad(const u32x4& h) {
     const _Float16 m = (_Float16)112.f;
@@ -344,6 +351,10 @@ __device__ __forceinline__ u32x2 wsu_f16x8_to_fp8_grad(const u32x4& h) {
 // lanes 32b .. 32b+31 -> a lane passes (hh ? block-1 scale : block-0 scale).
 __device__ __forceinline__ void wsu_mfma_f16(const u32x4& a, const u32x4& b, f32x16& acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 wsu_mfma_f16_z(const u32x4& a, const u32x4& b) {          // C = literal zero (see wsu_mfma_q4_z)
+    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), z, 0, 0, 0);
 }
 __device__ __forceinline__ void wsu_mfma_f8x2(const u32x4& a_blk0, const u32x4& a_blk1, const u32x4& b_blk0, const u32x4& b_blk1,
                                               int scale_a, int scale_b, f32x16& acc) {
