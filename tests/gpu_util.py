@@ -197,3 +197,16 @@ def planar_q_decode(t, parts: bool = False):
     val = hi.float() + fp4_values(codes[..., 16:]) * torch.exp2(e - 11)[..., None]
     val = val.permute(0, 1, 4, 2, 3).reshape(n, c, h, w).cpu()
     return (val, hi, codes[..., :16], codes[..., 16:], e) if parts else val
+
+
+def planar_h_encode(x: torch.Tensor) -> ops.PlanarH:
+    """NCHW fp32 (CPU) -> PlanarH on the device: per 16-channel chunk plane 0 = f16 ch 0-7, plane 1 = f16 ch 8-15 as [H][W][8 x f16]."""
+    n, c, h, w = x.shape
+    t = x.half().reshape(n, c // 16, 2, 8, h, w).permute(0, 1, 2, 4, 5, 3).contiguous()
+    return ops.PlanarH(t.view(torch.uint8).reshape(n, c // 16, 32 * h * w).to(DEV), n, c, h, w)
+
+
+def planar_h_decode(t: ops.PlanarH) -> torch.Tensor:
+    """PlanarH -> NCHW fp32 (CPU): the stored f16 values."""
+    d = t.data.cpu().view(torch.float16).reshape(t.n, t.c // 16, 2, t.h, t.w, 8)
+    return d.permute(0, 1, 2, 5, 3, 4).reshape(t.n, t.c, t.h, t.w).float()

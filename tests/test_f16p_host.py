@@ -41,19 +41,28 @@ def _rejects(rc, lib, *words):
         assert w in msg, (w, msg)
 
 
-def test_conv3x3_h_fwd_rejects_bad_arguments(lib):
-    f = lib.wsu_conv3x3_h_fwd
+PLANAR_Q = 1
+BOTH = pytest.mark.parametrize("fmt", ["q", "h"])
+
+
+@BOTH
+def test_conv3x3_h_fwd_rejects_bad_arguments(lib, fmt):
+    f, own = (lib.wsu_conv3x3_h_fwd, PLANAR_H) if fmt == "h" else (lib.wsu_conv3x3_q_fwd, PLANAR_Q)
     # (x1, x2, w, bias, y, y_pool, head_w, head_b, head_out, head_logit, head_cout, n, h, w, c1, c2, cout, relu, y_format, range_flag, stream)
-    _rejects(f(None, None, None, None, None, None, None, None, None, None, 0, 1, 8, 8, 64, 0, 64, 1, PLANAR_H, None, None), lib, b"null")
-    _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 8, 8, 64, 0, 64, 1, 1, None, None), lib, b"y_format", b"WSU_PLANAR_H")
-    _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 8, 8, 64, 0, 96, 1, PLANAR_H, None, None), lib, b"cout=96")
-    _rejects(f(1, None, 1, None, None, 1, None, None, None, None, 0, 1, 7, 8, 64, 0, 64, 1, PLANAR_H, None, None), lib, b"even h, w", b"h=7")
-    _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 8, 8, 40, 0, 64, 1, PLANAR_H, None, None), lib, b"c1=40")
-    _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 1, 8, 64, 0, 64, 1, PLANAR_H, None, None), lib, b"reflect")
+    _rejects(f(None, None, None, None, None, None, None, None, None, None, 0, 1, 8, 8, 64, 0, 64, 1, own, None, None), lib, b"null")
+    if fmt == "h":
+        _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 8, 8, 64, 0, 64, 1, 1, None, None), lib, b"y_format", b"WSU_PLANAR_H")
+    else:
+        _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 8, 8, 64, 0, 64, 1, PLANAR_H, None, None), lib, b"y_format")
+    _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 8, 8, 64, 0, 96, 1, own, None, None), lib, b"cout=96")
+    _rejects(f(1, None, 1, None, None, 1, None, None, None, None, 0, 1, 7, 8, 64, 0, 64, 1, own, None, None), lib, b"even h, w", b"h=7")
+    _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 8, 8, 40, 0, 64, 1, own, None, None), lib, b"c1=40")
+    _rejects(f(1, None, 1, None, 1, None, None, None, None, None, 0, 1, 1, 8, 64, 0, 64, 1, own, None, None), lib, b"reflect")
 
 
-def test_conv3x3_up_h_fwd_rejects_bad_arguments(lib):
-    f = lib.wsu_conv3x3_up_h_fwd
+@BOTH
+def test_conv3x3_up_h_fwd_rejects_bad_arguments(lib, fmt):
+    f = lib.wsu_conv3x3_up_h_fwd if fmt == "h" else lib.wsu_conv3x3_up_q_fwd
     # (x_low, x_skip, w_skip, w_low, bias, y, n, h, w, cl, c2, cout, relu, range_flag, stream)
     _rejects(f(1, None, 1, 1, 1, 1, 1, 16, 16, 128, 64, 64, 1, None, None), lib, b"null")
     _rejects(f(1, 1, 1, 1, 1, 1, 1, 16, 16, 128, 64, 80, 1, None, None), lib, b"cout=80")
@@ -62,16 +71,29 @@ def test_conv3x3_up_h_fwd_rejects_bad_arguments(lib):
     _rejects(f(1, 1, 1, 1, 1, 1, 1, 16, 16, 120, 64, 64, 1, None, None), lib, b"cl=120")
 
 
+@BOTH
+def test_packers_reject_bad_arguments(lib, fmt):
+    pack, up_pack = (lib.wsu_conv3x3_pack_h, lib.wsu_conv3x3_up_pack_h) if fmt == "h" else (lib.wsu_conv3x3_pack_f4, lib.wsu_conv3x3_up_pack)
+    _rejects(pack(None, 1, 64, 64, None), lib, b"null")
+    _rejects(pack(1, 1, 64, 48, None), lib, b"cout=48")
+    _rejects(up_pack(1, 1, None, None, None, 1, None, 128, 64, 64, 64, None), lib, b"null")
+    _rejects(up_pack(1, 1, None, None, 1, 1, None, 128, 64, 64, 72, None), lib, b"cout=72")
+
+
 def test_packers_and_first_layer_reject_bad_arguments(lib):
-    _rejects(lib.wsu_conv3x3_pack_h(None, 1, 64, 64, None), lib, b"null")
-    _rejects(lib.wsu_conv3x3_pack_h(1, 1, 64, 48, None), lib, b"cout=48")
-    _rejects(lib.wsu_conv3x3_up_pack_h(1, 1, None, None, None, 1, None, 128, 64, 64, 64, None), lib, b"null")
-    _rejects(lib.wsu_conv3x3_up_pack_h(1, 1, None, None, 1, 1, None, 128, 64, 64, 72, None), lib, b"cout=72")
     # (x, w, bias, y, n, h, w, cin, cout, relu, y_format, range_flag, relu_mask_out, stream): format H accepted, other values still rejected,
     # and the training forward's ReLU mask still belongs to format A only
     _rejects(lib.wsu_conv3x3_first_pl_fwd(1, 1, None, 1, 1, 8, 8, 1, 64, 1, 3, None, None, None), lib, b"WSU_PLANAR_H")
     _rejects(lib.wsu_conv3x3_first_pl_fwd(1, 1, None, 1, 1, 8, 8, 1, 64, 1, PLANAR_H, None, 1, None), lib, b"relu_mask_out")
     _rejects(lib.wsu_conv3x3_first_pl_fwd(None, 1, None, 1, 1, 8, 8, 1, 64, 1, PLANAR_H, None, None, None), lib, b"null")
+
+
+def test_wrong_format_tensors_are_refused_before_any_launch():
+    with pytest.raises(AssertionError, match="planar Q tensors"):
+        ops.conv3x3_q(ops.PlanarH.empty(1, 16, 4, 4, "cpu"), None, None, None, 64)
+    q = ops.PlanarQ.empty(1, 16, 4, 4, "cpu")
+    with pytest.raises(AssertionError, match="planar H tensors"):
+        ops.conv3x3_up_h(q, q, None, None, None, 64)
 
 
 def test_mode_name_resolves():

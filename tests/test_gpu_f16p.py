@@ -9,28 +9,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV, gpu_model, images01, oracle_forward
+from gpu_util import DEV, gpu_model, images01, oracle_forward, planar_h_decode, planar_h_encode
 from ws_unet_amd import evaluate, formula, ops
 from ws_unet_amd.model import get_model
 from ws_unet_amd.model.unet import ENC, dec_names
 from oracle import unet_ref
 
 pytestmark = pytest.mark.gpu
-
-
-# ---- planar H tensors <-> NCHW ---------------------------------------------------------------------------------------------------------------
-
-def h_encode(x: torch.Tensor) -> ops.PlanarH:
-    """NCHW fp32 (CPU) -> PlanarH on the device: per 16-channel chunk plane 0 = f16 ch 0-7, plane 1 = f16 ch 8-15 as [H][W][8 x f16]."""
-    n, c, h, w = x.shape
-    t = x.half().reshape(n, c // 16, 2, 8, h, w).permute(0, 1, 2, 4, 5, 3).contiguous()
-    return ops.PlanarH(t.view(torch.uint8).reshape(n, c // 16, 32 * h * w).to(DEV), n, c, h, w)
-
-
-def h_decode(t: ops.PlanarH) -> torch.Tensor:
-    """PlanarH -> NCHW fp32 (CPU): the stored f16 values."""
-    d = t.data.cpu().view(torch.float16).reshape(t.n, t.c // 16, 2, t.h, t.w, 8)
-    return d.permute(0, 1, 2, 5, 3, 4).reshape(t.n, t.c, t.h, t.w).float()
 
 
 def r16(t: torch.Tensor) -> torch.Tensor:
@@ -75,13 +60,13 @@ def test_conv3x3_h_against_emulation(n, h, w, c1, c2, cout, kind):
         hb = torch.randn(hc, generator=g) * 0.1
         kw = {"head_w": hw_.to(DEV), "head_b": hb.to(DEV), "want_logit": True}
     rf = torch.zeros(1, dtype=torch.int32, device=DEV)
-    res = ops.conv3x3_h(h_encode(x1), None if x2 is None else h_encode(x2), wp, b.to(DEV), cout, pool=kind == "pool", range_flag=rf, **kw)
+    res = ops.conv3x3_h(planar_h_encode(x1), None if x2 is None else planar_h_encode(x2), wp, b.to(DEV), cout, pool=kind == "pool", range_flag=rf, **kw)
     torch.cuda.synchronize()
     assert int(rf.item()) == 0
     if kind == "pool":
         y, yp = res
         ref_p = F.max_pool2d(act, 2)
-        d = (h_decode(yp).double() - r16(ref_p.float()).double()).abs()
+        d = (planar_h_decode(yp).double() - r16(ref_p.float()).double()).abs()
         assert float(d.max()) <= float(ref_p.abs().max()) * 2 ** -10, float(d.max())     # at most one f16 rounding step apart
     elif kind.startswith("head"):
         out, logit, y = res
@@ -91,7 +76,7 @@ def test_conv3x3_h_against_emulation(n, h, w, c1, c2, cout, kind):
         assert (out.cpu().double() - torch.sigmoid(z)).abs().max().item() <= 1e-5
     else:
         y = res
-    got = h_decode(y).double()
+    got = planar_h_decode(y).double()
     ref = r16(act.float()).double()
     d = (got - ref).abs()
     # stored values: the f16 rounding of the fp32 sum -- equal to the rounding of the exact sum except where the summation order straddles a
@@ -136,8 +121,8 @@ def test_conv3x3_up_h(n, hl, wl, cl, cup, c2, cout):
     b3 = torch.randn(cout, generator=g) * 0.1
     wsk, wlo, bias, dense = ops.pack_conv3x3_up_h(w3.to(DEV), wt.to(DEV), bt.to(DEV), b3.to(DEV), want_dense=True)
     rf = torch.zeros(1, dtype=torch.int32, device=DEV)
-    y = ops.conv3x3_up_h(h_encode(xl), h_encode(xs), wsk, wlo, bias, cout, range_flag=rf)
-    got = h_decode(y).double()
+    y = ops.conv3x3_up_h(planar_h_encode(xl), planar_h_encode(xs), wsk, wlo, bias, cout, range_flag=rf)
+    got = planar_h_decode(y).double()
     assert int(rf.item()) == 0
     # (a) the exact composition of the reference's two ops on the same stored inputs, fp64
     xu = F.conv_transpose2d(xl.double(), wt.double(), bt.double(), stride=2)

@@ -11,7 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV, fp4_codes, fp4_values, planar_decode, planar_q_decode, planar_q_encode, planar_q_parts, q_block_exp
+from gpu_util import (DEV, fp4_codes, fp4_values, planar_decode, planar_h_decode, planar_h_encode, planar_q_decode, planar_q_encode,
+                      planar_q_parts, q_block_exp)
 
 pytestmark = pytest.mark.gpu
 
@@ -89,19 +90,6 @@ def _up_case(n, hl, wl, cl, cup, c2, cout, seed):
     w3 = torch.randn((cout, cup + c2, 3, 3), generator=g) * (2.0 / (9 * (cup + c2))) ** 0.5
     b3 = torch.randn(cout, generator=g) * 0.1
     return xl, xs, wt, bt, w3, b3
-
-
-def h_encode(x):
-    """NCHW fp32 (CPU) -> ops.PlanarH on the device: per 16-channel chunk plane 0 = f16 ch 0-7, plane 1 = f16 ch 8-15 as [H][W][8 x f16]"""
-    from ws_unet_amd import ops
-    n, c, h, w = x.shape
-    t = x.half().reshape(n, c // 16, 2, 8, h, w).permute(0, 1, 2, 4, 5, 3).contiguous()
-    return ops.PlanarH(t.view(torch.uint8).reshape(n, c // 16, 32 * h * w).to(DEV), n, c, h, w)
-
-
-def h_decode(t):
-    d = t.data.cpu().view(torch.float16).reshape(t.n, t.c // 16, 2, t.h, t.w, 8)
-    return d.permute(0, 1, 2, 5, 3, 4).reshape(t.n, t.c, t.h, t.w).float()
 
 
 def r16(t):
@@ -216,17 +204,17 @@ def _check_h_conv(x, wgt, b, act, pool):
     from ws_unet_amd import ops
     cout = wgt.shape[0]
     rf = torch.zeros(1, dtype=torch.int32, device=DEV)
-    res = ops.conv3x3_h(h_encode(x), None, ops.pack_conv3x3_h(wgt.to(DEV)), b.to(DEV), cout, pool=pool, range_flag=rf)
+    res = ops.conv3x3_h(planar_h_encode(x), None, ops.pack_conv3x3_h(wgt.to(DEV)), b.to(DEV), cout, pool=pool, range_flag=rf)
     torch.cuda.synchronize()
     assert int(rf.item()) == 0
     y = res[0] if pool else res
-    got, ref = h_decode(y).double(), r16(act.float()).double()
+    got, ref = planar_h_decode(y).double(), r16(act.float()).double()
     d = (got - ref).abs()
     print(f"[fixed costs h {tuple(x.shape)} -> {cout} pool={pool}] differing stored values {float((d > 0).double().mean()):.2e}, max {float(d.max()):.2e}")
     assert float((d > 0).double().mean()) <= 2e-3
     assert float(d.max()) <= float(ref.abs().max()) * 2 ** -10
     if pool:
-        assert float((h_decode(res[1]) - F.max_pool2d(h_decode(y), 2)).abs().max()) == 0.0
+        assert float((planar_h_decode(res[1]) - F.max_pool2d(planar_h_decode(y), 2)).abs().max()) == 0.0
 
 
 @pytest.mark.parametrize("pool", [False, True])

@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV, planar_encode, planar_q_decode, planar_q_encode
+from gpu_util import DEV, planar_encode, planar_h_decode, planar_h_encode, planar_q_decode, planar_q_encode
 from test_gpu_qu import _case, _q_roundtrip, _up_q_ref
 
 pytestmark = pytest.mark.gpu
@@ -57,14 +57,14 @@ def test_fused_entry_against_the_two_kernel_path_and_itself(n, hl, wl, cl, cup, 
 def test_fused_entry_format_h_repeatable(n, hl, wl, cl, cup, c2, cout):
     """format H (mode 'f16p') shares the step plan: the same result on every launch, and as close to the exact composition as test_gpu_f16p asks"""
     from ws_unet_amd import ops
-    from test_gpu_f16p import h_decode, h_encode, r16
+    from test_gpu_f16p import r16
     xl, xs, wt, bt, w3, b3 = _case(n, hl, wl, cl, cup, c2, cout, seed=9)
     xl, xs = r16(xl), r16(xs)
     wsk, wlo, bias = ops.pack_conv3x3_up_h(w3.to(DEV), wt.to(DEV), bt.to(DEV), b3.to(DEV))
-    hl_, hs_ = h_encode(xl), h_encode(xs)
-    got = h_decode(ops.conv3x3_up_h(hl_, hs_, wsk, wlo, bias, cout))
+    hl_, hs_ = planar_h_encode(xl), planar_h_encode(xs)
+    got = planar_h_decode(ops.conv3x3_up_h(hl_, hs_, wsk, wlo, bias, cout))
     for _ in range(3):
-        assert torch.equal(h_decode(ops.conv3x3_up_h(hl_, hs_, wsk, wlo, bias, cout)), got)
+        assert torch.equal(planar_h_decode(ops.conv3x3_up_h(hl_, hs_, wsk, wlo, bias, cout)), got)
     exact = _exact(xl, xs, wt, bt, w3, b3).double()
     rel = float((got.double() - exact).norm() / exact.norm())
     assert rel <= 6e-4, rel

@@ -653,8 +653,7 @@ int wsu_conv3x3_first_bwd_weight(const float* g, const float* x_nchw, float* dw,
     hipStream_t s = static_cast<hipStream_t>(stream);
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&first_wgrad_partial_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FW_LDS);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(first_wgrad): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        if (int rc = wsu_raise_lds(first_wgrad_partial_kernel, FW_LDS, "first_wgrad")) return rc;
         attr_done = true;
     }
     hipLaunchKernelGGL(first_wgrad_partial_kernel, dim3(nchunks, cout / 64), dim3(256), FW_LDS, s, g, x_nchw, workspace, n, h, w, cin, cout, chunk);

@@ -1021,9 +1021,7 @@ int launch_conv_nw(const ConvArgs& a_in, hipStream_t s) {
     a.tiles_y = (a.h + Shape<NW>::TH - 1) / Shape<NW>::TH;
     static bool attr_done = false;     // benign race: idempotent
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<MODE, NW, S16, F1, PS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        if (int rc = wsu_raise_lds(conv3x3_kernel<MODE, NW, S16, F1, PS>, lds, "conv3x3")) return rc;
         attr_done = true;
     }
     const long long nblk = (long long)a.n * a.tiles_x * a.tiles_y * a.ncb;
@@ -1267,8 +1265,7 @@ int wsu_conv3x3_wino_fwd(const void* x1, const void* x2, const void* w_packed, c
     constexpr int LDS = EPI_BYTES > WN_LDS_V + WN_LDS_W ? EPI_BYTES : WN_LDS_V + WN_LDS_W;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_wino): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        if (int rc = wsu_raise_lds(conv3x3_wino_kernel, LDS, "conv3x3_wino")) return rc;
         attr_done = true;
     }
     const long long nblk = (long long)n * a.tiles_x * a.tiles_y * a.ncb;

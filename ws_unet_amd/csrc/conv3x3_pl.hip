@@ -765,23 +765,17 @@ _Pragma("unroll")
 
 // one place that knows the instantiations: attributes once, then the variant the arguments select
 int pl_launch(PlArgs a, bool first, hipStream_t s, bool grad = false) {
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            wsu_set_error("conv3x3_pl: cannot query the device"); return WSU_ERR_HIP;
-        }
-        const void* fns[9] = {reinterpret_cast<const void*>(&conv3x3_pl_kernel<0, false, false, false, true, false, true>), reinterpret_cast<const void*>(&conv3x3_pl_kernel<0, false, true, false, true>),reinterpret_cast<const void*>(&conv3x3_pl_kernel<0, false>), reinterpret_cast<const void*>(&conv3x3_pl_kernel<0, true>),
-                              reinterpret_cast<const void*>(&conv3x3_pl_kernel<1, false>), reinterpret_cast<const void*>(&conv3x3_pl_kernel<4, false>),
-                              reinterpret_cast<const void*>(&conv3x3_pl_kernel<0, false, false>),
-                              reinterpret_cast<const void*>(&conv3x3_pl_kernel<0, false, true, true>), reinterpret_cast<const void*>(&conv3x3_pl_kernel<0, true, true, true>)};
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pl_kernel<0, false, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-        if (e0 != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_pl): %s", hipGetErrorString(e0)); return WSU_ERR_HIP; }
-        for (const void* fn : fns) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-            if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_pl): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-        }
-        ncu = prop.multiProcessorCount;
+    const int ncu = wsu_cu_count("conv3x3_pl");
+    if (!ncu) return WSU_ERR_HIP;
+    static bool attr_done = false;
+    if (!attr_done) {
+        void (*const fns[10])(const PlArgs) = {conv3x3_pl_kernel<0, false, false, false, true, false, true>, conv3x3_pl_kernel<0, false, true, false, true>,
+                                               conv3x3_pl_kernel<0, false>, conv3x3_pl_kernel<0, true>, conv3x3_pl_kernel<1, false>, conv3x3_pl_kernel<4, false>,
+                                               conv3x3_pl_kernel<0, false, false>, conv3x3_pl_kernel<0, false, true, true>, conv3x3_pl_kernel<0, true, true, true>,
+                                               conv3x3_pl_kernel<0, false, true, false, false, true>};
+        for (auto fn : fns)
+            if (int rc = wsu_raise_lds(fn, LDS_TOTAL, "conv3x3_pl")) return rc;
+        attr_done = true;
     }
     // small grids: the plain variant splits every tile's 64 output channels over two work items when that still fits the CUs
     static int msplit_on = -1;

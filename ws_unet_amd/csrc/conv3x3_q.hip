@@ -820,85 +820,109 @@ __global__ void pack_conv3x3_h_kernel(const float* __restrict__ w, char* __restr
     }
 }
 
-#define WSU_Q_INST(RQ) \
-    template __global__ void conv3x3_q_kernel<RQ, 0, false, false, false>(const QArgs); \
-    template __global__ void conv3x3_q_kernel<RQ, 0, false, true, false>(const QArgs);  \
-    template __global__ void conv3x3_q_kernel<RQ, 0, true, false, false>(const QArgs);  \
-    template __global__ void conv3x3_q_kernel<RQ, 0, true, true, false>(const QArgs);   \
-    template __global__ void conv3x3_q_kernel<RQ, 1, false, false, false>(const QArgs); \
-    template __global__ void conv3x3_q_kernel<RQ, 4, false, false, false>(const QArgs); \
-    template __global__ void conv3x3_q_kernel<RQ, 0, false, false, true>(const QArgs);  \
-    template __global__ void conv3x3_q_kernel<RQ, 0, false, true, true>(const QArgs);
-WSU_Q_INST(4)
-WSU_Q_INST(2)
-template __global__ void conv3x3_q_kernel<2, 0, true, true, false, true>(const QArgs);
-// format H (mode 'f16p'): plain, pool, head (1 / 4 planes) and the half-block variant of small grids, RQ = 2
-template __global__ void conv3x3_q_kernel<2, 0, false, true, false, false, WSU_PLANAR_H>(const QArgs);
-template __global__ void conv3x3_q_kernel<2, 0, true, true, false, false, WSU_PLANAR_H>(const QArgs);
-template __global__ void conv3x3_q_kernel<2, 1, false, true, false, false, WSU_PLANAR_H>(const QArgs);
-template __global__ void conv3x3_q_kernel<2, 4, false, true, false, false, WSU_PLANAR_H>(const QArgs);
-template __global__ void conv3x3_q_kernel<2, 0, false, true, true, false, WSU_PLANAR_H>(const QArgs);
+// ---- the instantiated variants, written once: X(RQ, head planes, POOL, FQ, MSPLIT, F1, FMT).  Format Q, both RQ: plain / pool with a format-A or a
+// format-Q y, the head (1 / 4 planes; a y beside it is format A) and the half-block variant of small grids; RQ = 2 also the fused first layer.
+// Format H (mode 'f16p', RQ = 2, FQ always set): plain, pool, head and the half-block variant.
+#define WSU_Q_VARIANTS_RQ(X, RQ)                    \
+    X(RQ, 0, false, false, false, false, WSU_PLANAR_Q) \
+    X(RQ, 0, false, true, false, false, WSU_PLANAR_Q)  \
+    X(RQ, 0, true, false, false, false, WSU_PLANAR_Q)  \
+    X(RQ, 0, true, true, false, false, WSU_PLANAR_Q)   \
+    X(RQ, 1, false, false, false, false, WSU_PLANAR_Q) \
+    X(RQ, 4, false, false, false, false, WSU_PLANAR_Q) \
+    X(RQ, 0, false, false, true, false, WSU_PLANAR_Q)  \
+    X(RQ, 0, false, true, true, false, WSU_PLANAR_Q)
+#define WSU_Q_VARIANTS(X)                            \
+    WSU_Q_VARIANTS_RQ(X, 4)                          \
+    WSU_Q_VARIANTS_RQ(X, 2)                          \
+    X(2, 0, true, true, false, true, WSU_PLANAR_Q)   \
+    X(2, 0, false, true, false, false, WSU_PLANAR_H) \
+    X(2, 0, true, true, false, false, WSU_PLANAR_H)  \
+    X(2, 1, false, true, false, false, WSU_PLANAR_H) \
+    X(2, 4, false, true, false, false, WSU_PLANAR_H) \
+    X(2, 0, false, true, true, false, WSU_PLANAR_H)
+#define WSU_Q_INST(RQ, HC, POOL, FQ, MSPLIT, F1, FMT) template __global__ void conv3x3_q_kernel<RQ, HC, POOL, FQ, MSPLIT, F1, FMT>(const QArgs);
+WSU_Q_VARIANTS(WSU_Q_INST)
 
-template <int RQ>
-int q_launch_rq(QArgs a, int yq, hipStream_t s, int ncu, bool msplit_on) {
-    constexpr int NT = (16 / RQ + NLOAD) * 64;
-    static bool attr_done = false;
-    if (!attr_done) {
-        const void* fns[8] = {reinterpret_cast<const void*>(&conv3x3_q_kernel<RQ, 0, false, false, false>), reinterpret_cast<const void*>(&conv3x3_q_kernel<RQ, 0, false, true, false>),
-                              reinterpret_cast<const void*>(&conv3x3_q_kernel<RQ, 0, true, false, false>), reinterpret_cast<const void*>(&conv3x3_q_kernel<RQ, 0, true, true, false>),
-                              reinterpret_cast<const void*>(&conv3x3_q_kernel<RQ, 1, false, false, false>), reinterpret_cast<const void*>(&conv3x3_q_kernel<RQ, 4, false, false, false>),
-                              reinterpret_cast<const void*>(&conv3x3_q_kernel<RQ, 0, false, false, true>), reinterpret_cast<const void*>(&conv3x3_q_kernel<RQ, 0, false, true, true>)};
-        for (const void* fn : fns) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-            if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_q): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+struct QVariant {
+    int rq, hc; bool pool, fq, msplit, f1; int fmt;
+    void (*kernel)(const QArgs);
+    bool raised;                                          // its dynamic-LDS limit has been raised
+};
+#define WSU_Q_ROW(RQ, HC, POOL, FQ, MSPLIT, F1, FMT) {RQ, HC, POOL, FQ, MSPLIT, F1, FMT, conv3x3_q_kernel<RQ, HC, POOL, FQ, MSPLIT, F1, FMT>, false},
+QVariant q_variants[] = {WSU_Q_VARIANTS(WSU_Q_ROW)};
+
+// Picks the variant for `a` (built by q_args) and launches it: the half-block variant on grids of at most half the CUs, else one persistent
+// workgroup per CU.  yq: y / y_pool are format-Q tensors (format H: always the storage format).
+int q_launch(QArgs a, const char* who, int fmt, int rq, bool yq, bool msplit_on, hipStream_t s) {
+    const bool h = fmt == WSU_PLANAR_H, f1 = a.img != nullptr;
+    const int ncu = wsu_cu_count(who);
+    if (!ncu) return WSU_ERR_HIP;
+    const int hc = !a.head_w ? 0 : (a.head_cout == 1 ? 1 : 4);
+    const bool pool = a.ypool != nullptr, fq = h || (yq && !hc);
+    a.msplit = !f1 && msplit_on && !hc && !pool && 2 * (long long)a.ntiles <= ncu;       // small grids: half-block work items
+    if (a.msplit) { a.ncb *= 2; a.ntiles *= 2; }
+    for (QVariant& v : q_variants) {
+        if (v.rq != rq || v.hc != hc || v.pool != pool || v.fq != fq || v.msplit != (a.msplit != 0) || v.f1 != f1 || v.fmt != fmt) continue;
+        const int lds = h ? QGeo<WSU_PLANAR_H>::lds_total : LDS_TOTAL;
+        if (!v.raised) {
+            if (int rc = wsu_raise_lds(v.kernel, lds, f1 ? "conv3x3_q<F1>" : (h ? "conv3x3_q<H>" : "conv3x3_q"))) return rc;
+            v.raised = true;
         }
-        attr_done = true;
+        hipLaunchKernelGGL(v.kernel, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3((16 / rq + NLOAD) * 64), lds, s, a);
+        return wsu_check_launch(f1 ? "conv3x3_q_kernel<F1>" : (h ? (a.msplit ? "conv3x3_q_kernel<H, msplit>" : "conv3x3_q_kernel<H>")
+                                                                 : (a.msplit ? "conv3x3_q_kernel<msplit>" : "conv3x3_q_kernel")));
     }
-    a.msplit = 0;
-    if (msplit_on && !a.head_w && !a.ypool && 2 * (long long)a.ntiles <= ncu) {       // small grids: half-block work items
-        a.msplit = 1; a.ncb *= 2; a.ntiles *= 2;
-        if (yq) hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 0, false, true, true>), dim3(a.ntiles), dim3(NT), LDS_TOTAL, s, a);
-        else hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 0, false, false, true>), dim3(a.ntiles), dim3(NT), LDS_TOTAL, s, a);
-        return wsu_check_launch("conv3x3_q_kernel<msplit>");
-    }
-    const dim3 g(a.ntiles < ncu ? a.ntiles : ncu), b(NT);
-    if (a.head_w && a.head_cout == 1) hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 1, false, false, false>), g, b, LDS_TOTAL, s, a);
-    else if (a.head_w) hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 4, false, false, false>), g, b, LDS_TOTAL, s, a);
-    else if (a.ypool && yq) hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 0, true, true, false>), g, b, LDS_TOTAL, s, a);
-    else if (a.ypool) hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 0, true, false, false>), g, b, LDS_TOTAL, s, a);
-    else if (yq) hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 0, false, true, false>), g, b, LDS_TOTAL, s, a);
-    else hipLaunchKernelGGL((conv3x3_q_kernel<RQ, 0, false, false, false>), g, b, LDS_TOTAL, s, a);
-    return wsu_check_launch("conv3x3_q_kernel");
+    wsu_set_error("%s: no kernel variant for this combination of outputs", who);        // (never: q_args admits the instantiated combinations only)
+    return WSU_ERR_UNSUPPORTED;
 }
 
-// format H: the launch choices of q_launch_rq<2> on the H instantiations
-int h_launch(QArgs a, hipStream_t s, int ncu, bool msplit_on) {
-    constexpr int HF = WSU_PLANAR_H, NT = (8 + NLOAD) * 64, LDS = QGeo<HF>::lds_total;
-    static bool attr_done = false;
-    if (!attr_done) {
-        const void* fns[5] = {reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 0, false, true, false, false, HF>),
-                              reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 0, true, true, false, false, HF>),
-                              reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 1, false, true, false, false, HF>),
-                              reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 4, false, true, false, false, HF>),
-                              reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 0, false, true, true, false, HF>)};
-        for (const void* fn : fns) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_q<H>): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-        }
-        attr_done = true;
-    }
-    a.msplit = 0;
-    if (msplit_on && !a.head_w && !a.ypool && 2 * (long long)a.ntiles <= ncu) {       // small grids: half-block work items
-        a.msplit = 1; a.ncb *= 2; a.ntiles *= 2;
-        hipLaunchKernelGGL((conv3x3_q_kernel<2, 0, false, true, true, false, HF>), dim3(a.ntiles), dim3(NT), LDS, s, a);
-        return wsu_check_launch("conv3x3_q_kernel<H, msplit>");
-    }
-    const dim3 g(a.ntiles < ncu ? a.ntiles : ncu), b(NT);
-    if (a.head_w && a.head_cout == 1) hipLaunchKernelGGL((conv3x3_q_kernel<2, 1, false, true, false, false, HF>), g, b, LDS, s, a);
-    else if (a.head_w) hipLaunchKernelGGL((conv3x3_q_kernel<2, 4, false, true, false, false, HF>), g, b, LDS, s, a);
-    else if (a.ypool) hipLaunchKernelGGL((conv3x3_q_kernel<2, 0, true, true, false, false, HF>), g, b, LDS, s, a);
-    else hipLaunchKernelGGL((conv3x3_q_kernel<2, 0, false, true, false, false, HF>), g, b, LDS, s, a);
-    return wsu_check_launch("conv3x3_q_kernel<H>");
+// Checks the arguments of a forward entry point and fills QArgs.  formats: bit f set = y_format f is allowed (formats_msg names the set).
+// img / w1 / b1 non-null: the fused first layer (64 computed input channels instead of x1 / x2; y and y_pool both written).
+int q_args(QArgs& a, const char* who, const void* x1, const void* x2, const float* img, const float* w1, const float* b1, const void* wp, const float* bias,
+           void* y, void* y_pool, const float* head_w, const float* head_b, float* head_out, float* head_logit, int head_cout,
+           int n, int h, int w, int c1, int c2, int cout, int relu, int y_format, unsigned formats, const char* formats_msg, unsigned* range_flag) {
+    const bool f1 = img || w1 || b1;
+    WSU_REQUIRE(wp && (f1 ? img && w1 && b1 && y && y_pool : x1 && (y || y_pool || head_w)), "%s: null pointer", who);
+    WSU_REQUIRE(!f1 || (((uintptr_t)w1 & 63) == 0 && ((uintptr_t)b1 & 63) == 0), "%s: w1_taps and b1 must be 64-byte aligned (scalar 16-dword loads)", who);
+    WSU_REQUIRE(y_format >= 0 && y_format < 32 && ((formats >> y_format) & 1u), "%s: y_format must be %s", who, formats_msg);
+    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2, "%s: bad shape n=%d h=%d w=%d (reflect pad 1 needs h,w >= 2)", who, n, h, w);
+    WSU_REQUIRE(c1 > 0 && c1 % 16 == 0 && c2 >= 0 && c2 % 16 == 0 && (c2 == 0) == (x2 == nullptr), "%s: c1=%d c2=%d must be multiples of 16", who, c1, c2);
+    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= 1024, "%s: cout=%d must be a multiple of %d (<= 1024)", who, cout, WSU_COB);
+    WSU_REQUIRE(!head_w || (head_out && cout == WSU_COB && head_cout >= 1 && head_cout <= 4), "%s: fused head needs cout == %d and 1..4 head planes", who, WSU_COB);
+    WSU_REQUIRE(!y_pool || (h % 2 == 0 && w % 2 == 0), "%s: fused pool needs even h, w (got h=%d w=%d)", who, h, w);
+    WSU_REQUIRE(!(y_pool && head_w), "%s: the fused pool and the fused head exclude each other", who);
+    WSU_REQUIRE(!(head_w && y && y_format == WSU_PLANAR_Q), "%s: a y beside the fused head is written in format WSU_PLANAR_A", who);
+    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "%s: h*w too large (a chunk must stay below 4 GiB)", who);
+    a.x1 = (const char*)x1; a.x2 = (const char*)x2; a.wp = (const char*)wp; a.bias = bias;
+    a.y = (char*)y; a.ypool = (char*)y_pool;
+    a.head_w = head_w; a.head_b = head_b; a.head_out = head_out; a.head_logit = head_logit; a.head_cout = head_cout;
+    a.range_flag = range_flag;
+    a.n = n; a.h = h; a.w = w; a.c1 = c1; a.c2 = c2; a.cout = cout;
+    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ncb = cout / WSU_COB;
+    a.nch1 = c1 / 16; a.nch = (c1 + c2) / 16; a.relu = relu; a.msplit = 0;
+    a.img = img; a.w1 = w1; a.b1 = b1;
+    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
+    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "%s: %lld tiles out of range", who, nt);
+    a.ntiles = (int)nt;
+    return WSU_OK;
+}
+
+// WSU_PL_MSPLIT (default 1): 0 switches the half-block variant of small grids off.  Read once per process.
+bool q_msplit_on() {
+    static const int on = [] { const char* e = getenv("WSU_PL_MSPLIT"); return e ? atoi(e) : 1; }();
+    return on != 0;
+}
+
+size_t packed_bytes(int cin, int cout, int slot) {
+    if (cin <= 0 || cout <= 0 || cin % 16 || cout % WSU_COB) return 0;
+    return (size_t)(cout / WSU_COB) * (cin / 16) * slot;
+}
+int pack(void (*kernel)(const float*, char*, int, int), const char* who, const char* kernel_name, const float* w_oihw, void* w_packed, int cin, int cout, void* stream) {
+    WSU_REQUIRE(w_oihw && w_packed, "%s: null pointer", who);
+    WSU_REQUIRE(cin > 0 && cin % 16 == 0 && cout > 0 && cout % WSU_COB == 0, "%s: cin=%d must be a multiple of 16, cout=%d of %d", who, cin, cout, WSU_COB);
+    hipLaunchKernelGGL(kernel, dim3(512), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, (char*)w_packed, cin, cout);
+    return wsu_check_launch(kernel_name);
 }
 
 }  // namespace
@@ -908,15 +932,9 @@ extern "C" {
 // Weights of the fp4-cross-term conv: per (64-channel output block, 16-channel input chunk) one 28 KB slice =
 // [tap 9][plane 3][64 co][16 B] with planes f16 ci 0-7 | f16 ci 8-15 | fp4(residual * 2^11 / 2^E) ci 0-15, fp4(f16 part / 2^E) ci 0-15 (nibble i =
 // channel i), then [tap 9][64 co] scale bytes E + 127 - 11 (the 2^-11 of the residual's pre-scaling rides in the weight's scale), zero padded to 1 KB.
-size_t wsu_conv3x3_packed_f4_bytes(int cin, int cout) {
-    if (cin <= 0 || cout <= 0 || cin % 16 || cout % WSU_COB) return 0;
-    return (size_t)(cout / WSU_COB) * (cin / 16) * W_SLOT;
-}
+size_t wsu_conv3x3_packed_f4_bytes(int cin, int cout) { return packed_bytes(cin, cout, W_SLOT); }
 int wsu_conv3x3_pack_f4(const float* w_oihw, void* w_packed, int cin, int cout, void* stream) {
-    WSU_REQUIRE(w_oihw && w_packed, "conv3x3_pack_f4: null pointer");
-    WSU_REQUIRE(cin > 0 && cin % 16 == 0 && cout > 0 && cout % WSU_COB == 0, "conv3x3_pack_f4: cin=%d must be a multiple of 16, cout=%d of %d", cin, cout, WSU_COB);
-    hipLaunchKernelGGL(pack_conv3x3_f4_kernel, dim3(512), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, (char*)w_packed, cin, cout);
-    return wsu_check_launch("pack_conv3x3_f4_kernel");
+    return pack(pack_conv3x3_f4_kernel, "conv3x3_pack_f4", "pack_conv3x3_f4_kernel", w_oihw, w_packed, cin, cout, stream);
 }
 
 // e11 + e12 (+ pool) of the default inference mode in ONE launch for single-plane inputs (unet.py:141-144; kernel variant F1 above): img (N,1,H,W)
@@ -926,37 +944,12 @@ int wsu_conv3x3_pack_f4(const float* w_oihw, void* w_packed, int cin, int cout, 
 // HBM.  h, w even; cout a multiple of 64.  range_flag as in wsu_conv3x3_q_fwd (it also covers the computed xe11 values).
 int wsu_conv3x3_q_fused_first_fwd(const float* img, const float* w1_taps, const float* b1, const void* w_packed_f4, const float* bias, void* y, void* y_pool,
                                   int n, int h, int w, int cout, int relu, unsigned* range_flag, void* stream) {
-    const float* w1 = w1_taps;
-    WSU_REQUIRE(img && w1 && b1 && w_packed_f4 && y && y_pool, "conv3x3_q_fused_first: null pointer");
-    WSU_REQUIRE(((uintptr_t)w1 & 63) == 0 && ((uintptr_t)b1 & 63) == 0, "conv3x3_q_fused_first: w1_taps and b1 must be 64-byte aligned (scalar 16-dword loads)");
-    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "conv3x3_q_fused_first: bad shape n=%d h=%d w=%d (even h, w: the pooled output)", n, h, w);
-    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= 1024, "conv3x3_q_fused_first: cout=%d must be a multiple of %d (<= 1024)", cout, WSU_COB);
-    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "conv3x3_q_fused_first: h*w too large (a chunk must stay below 4 GiB)");
+    const char* who = "conv3x3_q_fused_first";
+    WSU_REQUIRE(img && w1_taps && b1, "%s: null pointer", who);
     QArgs a;
-    a.x1 = nullptr; a.x2 = nullptr; a.wp = (const char*)w_packed_f4; a.bias = bias;
-    a.y = (char*)y; a.ypool = (char*)y_pool;
-    a.head_w = nullptr; a.head_b = nullptr; a.head_out = nullptr; a.head_logit = nullptr; a.head_cout = 0;
-    a.range_flag = range_flag;
-    a.n = n; a.h = h; a.w = w; a.c1 = 64; a.c2 = 0; a.cout = cout;
-    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ncb = cout / WSU_COB;
-    a.nch1 = 4; a.nch = 4; a.relu = relu; a.msplit = 0;
-    a.img = img; a.w1 = w1; a.b1 = b1;
-    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
-    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_q_fused_first: %lld tiles out of range", nt);
-    a.ntiles = (int)nt;
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            wsu_set_error("conv3x3_q_fused_first: cannot query the device"); return WSU_ERR_HIP;
-        }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_q_kernel<2, 0, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_q<F1>): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-        ncu = prop.multiProcessorCount;
-    }
-    hipLaunchKernelGGL((conv3x3_q_kernel<2, 0, true, true, false, true>), dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3((8 + NLOAD) * 64), LDS_TOTAL,
-                       static_cast<hipStream_t>(stream), a);
-    return wsu_check_launch("conv3x3_q_kernel<F1>");
+    if (int rc = q_args(a, who, nullptr, nullptr, img, w1_taps, b1, w_packed_f4, bias, y, y_pool, nullptr, nullptr, nullptr, nullptr, 0,
+                        n, h, w, 64, 0, cout, relu, WSU_PLANAR_Q, 1u << WSU_PLANAR_Q, "WSU_PLANAR_Q", range_flag)) return rc;
+    return q_launch(a, who, WSU_PLANAR_Q, 2, true, false, static_cast<hipStream_t>(stream));
 }
 
 // Bytes of a planar Q tensor (n images, c channels -- a multiple of 16 -- at h x w): n * c/16 chunks of 48 h w + 512 ceil(h/16) ceil(w/32) bytes.
@@ -973,40 +966,12 @@ size_t wsu_planar_q_bytes(int n, int c, int h, int w) {
 int wsu_conv3x3_q_fwd(const void* x1, const void* x2, const void* w_packed_f4, const float* bias, void* y, void* y_pool,
                       const float* head_w, const float* head_b, float* head_out, float* head_logit, int head_cout,
                       int n, int h, int w, int c1, int c2, int cout, int relu, int y_format, unsigned* range_flag, void* stream) {
-    WSU_REQUIRE(x1 && w_packed_f4 && (y || y_pool || head_w), "conv3x3_q: null pointer");
-    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2, "conv3x3_q: bad shape n=%d h=%d w=%d (reflect pad 1 needs h,w >= 2)", n, h, w);
-    WSU_REQUIRE(c1 > 0 && c1 % 16 == 0 && c2 >= 0 && c2 % 16 == 0 && (c2 == 0) == (x2 == nullptr), "conv3x3_q: c1=%d c2=%d must be multiples of 16", c1, c2);
-    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= 1024, "conv3x3_q: cout=%d must be a multiple of %d (<= 1024)", cout, WSU_COB);
-    WSU_REQUIRE(!head_w || (head_out && cout == WSU_COB && head_cout >= 1 && head_cout <= 4), "conv3x3_q: fused head needs cout == %d and 1..4 head planes", WSU_COB);
-    WSU_REQUIRE(!y_pool || (h % 2 == 0 && w % 2 == 0), "conv3x3_q: fused pool needs even h, w");
-    WSU_REQUIRE(!(y_pool && head_w), "conv3x3_q: the fused pool and the fused head exclude each other");
-    WSU_REQUIRE(y_format == WSU_PLANAR_A || y_format == WSU_PLANAR_Q, "conv3x3_q: y_format must be WSU_PLANAR_A or WSU_PLANAR_Q");
-    WSU_REQUIRE(!(head_w && y && y_format != WSU_PLANAR_A), "conv3x3_q: a y beside the fused head is written in format WSU_PLANAR_A");
-    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "conv3x3_q: h*w too large (a chunk must stay below 4 GiB)");
     QArgs a;
-    a.x1 = (const char*)x1; a.x2 = (const char*)x2; a.wp = (const char*)w_packed_f4; a.bias = bias;
-    a.y = (char*)y; a.ypool = (char*)y_pool;
-    a.head_w = head_w; a.head_b = head_b; a.head_out = head_out; a.head_logit = head_logit; a.head_cout = head_cout;
-    a.range_flag = range_flag;
-    a.n = n; a.h = h; a.w = w; a.c1 = c1; a.c2 = c2; a.cout = cout;
-    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ncb = cout / WSU_COB;
-    a.nch1 = c1 / 16; a.nch = (c1 + c2) / 16; a.relu = relu;
-    a.img = nullptr; a.w1 = nullptr; a.b1 = nullptr;
-    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
-    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_q: %lld tiles out of range", nt);
-    a.ntiles = (int)nt;
-    static int ncu = 0, rq = 0, msplit_on = 1;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            wsu_set_error("conv3x3_q: cannot query the device"); return WSU_ERR_HIP;
-        }
-        const char* e = getenv("WSU_Q_ROWS"); rq = (e && atoi(e) == 4) ? 4 : 2;       // experiment switch: 4 = four matrix waves (one per SIMD) x four rows
-        e = getenv("WSU_PL_MSPLIT"); msplit_on = e ? atoi(e) : 1;
-        ncu = prop.multiProcessorCount;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return rq != 4 ? q_launch_rq<2>(a, y_format == WSU_PLANAR_Q, s, ncu, msplit_on != 0) : q_launch_rq<4>(a, y_format == WSU_PLANAR_Q, s, ncu, msplit_on != 0);
+    if (int rc = q_args(a, "conv3x3_q", x1, x2, nullptr, nullptr, nullptr, w_packed_f4, bias, y, y_pool, head_w, head_b, head_out, head_logit, head_cout,
+                        n, h, w, c1, c2, cout, relu, y_format, 1u << WSU_PLANAR_A | 1u << WSU_PLANAR_Q, "WSU_PLANAR_A or WSU_PLANAR_Q", range_flag)) return rc;
+    // WSU_Q_ROWS: experiment switch, 4 = four matrix waves (one per SIMD) x four rows
+    static const int rq = [] { const char* e = getenv("WSU_Q_ROWS"); return (e && atoi(e) == 4) ? 4 : 2; }();
+    return q_launch(a, "conv3x3_q", WSU_PLANAR_Q, rq, y_format == WSU_PLANAR_Q, q_msplit_on(), static_cast<hipStream_t>(stream));
 }
 
 // ---- format H (mode 'f16p', include/wsu.h K1h) ----------------------------------------------------------------------------------------
@@ -1018,15 +983,9 @@ size_t wsu_planar_h_bytes(int n, int c, int h, int w) {
 
 // Weights of the one-product conv: per (64-channel output block, 16-channel input chunk) one 18 KB slice [tap 9][plane 2][64 co][16 B], planes
 // f16 ci 0-7 | f16 ci 8-15 (round to nearest even).
-size_t wsu_conv3x3_packed_h_bytes(int cin, int cout) {
-    if (cin <= 0 || cout <= 0 || cin % 16 || cout % WSU_COB) return 0;
-    return (size_t)(cout / WSU_COB) * (cin / 16) * W_SLOT_H;
-}
+size_t wsu_conv3x3_packed_h_bytes(int cin, int cout) { return packed_bytes(cin, cout, W_SLOT_H); }
 int wsu_conv3x3_pack_h(const float* w_oihw, void* w_packed, int cin, int cout, void* stream) {
-    WSU_REQUIRE(w_oihw && w_packed, "conv3x3_pack_h: null pointer");
-    WSU_REQUIRE(cin > 0 && cin % 16 == 0 && cout > 0 && cout % WSU_COB == 0, "conv3x3_pack_h: cin=%d must be a multiple of 16, cout=%d of %d", cin, cout, WSU_COB);
-    hipLaunchKernelGGL(pack_conv3x3_h_kernel, dim3(512), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, (char*)w_packed, cin, cout);
-    return wsu_check_launch("pack_conv3x3_h_kernel");
+    return pack(pack_conv3x3_h_kernel, "conv3x3_pack_h", "pack_conv3x3_h_kernel", w_oihw, w_packed, cin, cout, stream);
 }
 
 // Forward 3x3 reflect conv + bias + ReLU (+ pool, + head) in the one-product arithmetic on planar H tensors: the arguments of wsu_conv3x3_q_fwd,
@@ -1034,37 +993,10 @@ int wsu_conv3x3_pack_h(const float* w_oihw, void* w_packed, int cin, int cout, v
 int wsu_conv3x3_h_fwd(const void* x1, const void* x2, const void* w_packed_h, const float* bias, void* y, void* y_pool,
                       const float* head_w, const float* head_b, float* head_out, float* head_logit, int head_cout,
                       int n, int h, int w, int c1, int c2, int cout, int relu, int y_format, unsigned* range_flag, void* stream) {
-    WSU_REQUIRE(x1 && w_packed_h && (y || y_pool || head_w), "conv3x3_h: null pointer");
-    WSU_REQUIRE(y_format == WSU_PLANAR_H, "conv3x3_h: y_format must be WSU_PLANAR_H");
-    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2, "conv3x3_h: bad shape n=%d h=%d w=%d (reflect pad 1 needs h,w >= 2)", n, h, w);
-    WSU_REQUIRE(c1 > 0 && c1 % 16 == 0 && c2 >= 0 && c2 % 16 == 0 && (c2 == 0) == (x2 == nullptr), "conv3x3_h: c1=%d c2=%d must be multiples of 16", c1, c2);
-    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= 1024, "conv3x3_h: cout=%d must be a multiple of %d (<= 1024)", cout, WSU_COB);
-    WSU_REQUIRE(!head_w || (head_out && cout == WSU_COB && head_cout >= 1 && head_cout <= 4), "conv3x3_h: fused head needs cout == %d and 1..4 head planes", WSU_COB);
-    WSU_REQUIRE(!y_pool || (h % 2 == 0 && w % 2 == 0), "conv3x3_h: fused pool needs even h, w (got h=%d w=%d)", h, w);
-    WSU_REQUIRE(!(y_pool && head_w), "conv3x3_h: the fused pool and the fused head exclude each other");
-    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "conv3x3_h: h*w too large (a chunk must stay below 4 GiB)");
     QArgs a;
-    a.x1 = (const char*)x1; a.x2 = (const char*)x2; a.wp = (const char*)w_packed_h; a.bias = bias;
-    a.y = (char*)y; a.ypool = (char*)y_pool;
-    a.head_w = head_w; a.head_b = head_b; a.head_out = head_out; a.head_logit = head_logit; a.head_cout = head_cout;
-    a.range_flag = range_flag;
-    a.n = n; a.h = h; a.w = w; a.c1 = c1; a.c2 = c2; a.cout = cout;
-    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ncb = cout / WSU_COB;
-    a.nch1 = c1 / 16; a.nch = (c1 + c2) / 16; a.relu = relu;
-    a.img = nullptr; a.w1 = nullptr; a.b1 = nullptr;
-    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
-    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_h: %lld tiles out of range", nt);
-    a.ntiles = (int)nt;
-    static int ncu = 0, msplit_on = 1;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            wsu_set_error("conv3x3_h: cannot query the device"); return WSU_ERR_HIP;
-        }
-        const char* e = getenv("WSU_PL_MSPLIT"); msplit_on = e ? atoi(e) : 1;
-        ncu = prop.multiProcessorCount;
-    }
-    return h_launch(a, static_cast<hipStream_t>(stream), ncu, msplit_on != 0);
+    if (int rc = q_args(a, "conv3x3_h", x1, x2, nullptr, nullptr, nullptr, w_packed_h, bias, y, y_pool, head_w, head_b, head_out, head_logit, head_cout,
+                        n, h, w, c1, c2, cout, relu, y_format, 1u << WSU_PLANAR_H, "WSU_PLANAR_H", range_flag)) return rc;
+    return q_launch(a, "conv3x3_h", WSU_PLANAR_H, 2, true, q_msplit_on(), static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

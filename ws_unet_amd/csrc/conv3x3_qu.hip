@@ -552,15 +552,78 @@ __global__ void up_bias_kernel(const float* __restrict__ w3, const float* __rest
     out[co] = s;
 }
 
+// ---- the host side, once for both formats: what differs between Q (mode 'f16f4p') and H (mode 'f16p') is this row (the kernels are instantiated
+// here, in the order the rows name them)
+struct UFormat {
+    const char* pack; const char* fwd;                                      // message prefixes
+    void (*pack_kernel)(const float*, const float*, char*, float*, int, int, int, int); const char* pack_kernel_name;
+    void (*kernel)(const UArgs); const char* kernel_name; const char* lds_name;
+    int w_s, w_l;                                                           // bytes of a skip slice and of a dy slice of the low half
+};
+const UFormat& u_format(int fmt) {
+    static const UFormat q = {"conv3x3_up_pack", "conv3x3_up_q", pack_up_low_kernel<WSU_PLANAR_Q>, "pack_up_low_kernel",
+                              conv3x3_qu_kernel<WSU_PLANAR_Q>, "conv3x3_qu_kernel", "conv3x3_qu", W_S, W_L};
+    static const UFormat h = {"conv3x3_up_pack_h", "conv3x3_up_h", pack_up_low_kernel<WSU_PLANAR_H>, "pack_up_low_kernel<H>",
+                              conv3x3_qu_kernel<WSU_PLANAR_H>, "conv3x3_qu_kernel<H>", "conv3x3_qu<H>", W_S_H, W_L_H};
+    return fmt == WSU_PLANAR_H ? h : q;
+}
+
+size_t up_packed_bytes(int fmt, int cl, int cout) {
+    if (cl <= 0 || cout <= 0 || cl % 16 || cout % WSU_COB) return 0;
+    return (size_t)(cout / WSU_COB) * (cl / 16) * 2 * u_format(fmt).w_l;
+}
+
+int up_pack(int fmt, const float* w3_oihw, const float* wt, const float* bt, const float* b3, void* w_low_packed, float* bias_out, float* wc_dense,
+            int cl, int cup, int c2, int cout, void* stream) {
+    const UFormat& f = u_format(fmt);
+    WSU_REQUIRE(w3_oihw && wt && w_low_packed && bias_out, "%s: null pointer", f.pack);
+    WSU_REQUIRE(cl > 0 && cl % 16 == 0 && cup > 0 && c2 >= 0 && cout > 0 && cout % WSU_COB == 0,
+                "%s: cl=%d must be a multiple of 16, cout=%d of %d, cup=%d > 0", f.pack, cl, cout, WSU_COB, cup);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(f.pack_kernel, dim3(1024), dim3(128), 0, s, w3_oihw, wt, (char*)w_low_packed, wc_dense, cup, c2, cl, cout);
+    int rc = wsu_check_launch(f.pack_kernel_name);
+    if (rc != WSU_OK) return rc;
+    hipLaunchKernelGGL(up_bias_kernel, dim3((cout + 63) / 64), dim3(64), 0, s, w3_oihw, bt, b3, bias_out, cup, c2, cout);
+    return wsu_check_launch("up_bias_kernel");
+}
+
+int up_fwd(int fmt, const void* x_low, const void* x_skip, const void* w_skip_packed, const void* w_low_packed, const float* bias, void* y,
+           int n, int h, int w, int cl, int c2, int cout, int relu, unsigned* range_flag, void* stream) {
+    const UFormat& f = u_format(fmt);
+    const char* who = f.fwd;
+    WSU_REQUIRE(x_low && x_skip && w_skip_packed && w_low_packed && y, "%s: null pointer", who);
+    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "%s: bad shape n=%d h=%d w=%d (the output of a stride-2 transposed conv is even)", who, n, h, w);
+    WSU_REQUIRE(cl > 0 && cl % 16 == 0 && c2 > 0 && c2 % 16 == 0, "%s: cl=%d c2=%d must be positive multiples of 16", who, cl, c2);
+    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= MAX_COUT, "%s: cout=%d must be a multiple of %d (<= %d)", who, cout, WSU_COB, MAX_COUT);
+    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "%s: h*w too large (a chunk must stay below 4 GiB)", who);
+    UArgs a;
+    a.xl = (const char*)x_low; a.xs = (const char*)x_skip; a.wps = (const char*)w_skip_packed; a.wpl = (const char*)w_low_packed; a.bias = bias;
+    a.y = (char*)y;
+    a.n = n; a.h = h; a.w = w; a.hl = h / 2; a.wl = w / 2; a.cl = cl; a.c2 = c2; a.cout = cout;
+    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ltiles_x = (a.wl + 31) / 32; a.ncb = cout / WSU_COB;
+    a.nchS = c2 / 16; a.nchL = cl / 16; a.relu = relu; a.range_flag = range_flag;
+    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
+    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "%s: %lld tiles out of range", who, nt);
+    WSU_REQUIRE((long long)a.ncb * a.nchL * 2 * f.w_l < 0x7FFFFFF0LL && (long long)a.ncb * a.nchS * f.w_s < 0x7FFFFFF0LL, "%s: packed weights beyond 2 GiB", who);
+    a.ntiles = (int)nt;
+    const int ncu = wsu_cu_count(who);
+    if (!ncu) return WSU_ERR_HIP;
+    static bool raised[2] = {false, false};
+    bool& done = raised[fmt == WSU_PLANAR_H];
+    if (!done) {
+        if (int rc = wsu_raise_lds(f.kernel, LDS_TOTAL, f.lds_name)) return rc;
+        done = true;
+    }
+    hipLaunchKernelGGL(f.kernel, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3(NT), LDS_TOTAL, static_cast<hipStream_t>(stream), a);
+    return wsu_check_launch(f.kernel_name);
+}
+
 }  // namespace
 
 extern "C" {
 
 // Bytes of the packed low half: per (64-co block, 16-channel chunk of x_low, dy) one 25 KB slice [class 4][dx 2][plane 3][64 co][16 B] + [8][64] scale bytes.
-size_t wsu_conv3x3_up_packed_bytes(int cl, int cout) {
-    if (cl <= 0 || cout <= 0 || cl % 16 || cout % WSU_COB) return 0;
-    return (size_t)(cout / WSU_COB) * (cl / 16) * 2 * W_L;
-}
+size_t wsu_conv3x3_up_packed_bytes(int cl, int cout) { return up_packed_bytes(WSU_PLANAR_Q, cl, cout); }
 
 // Packs the upsampled half of a decoder block's first conv.  w3: (cout, cup + c2, 3, 3) OIHW fp32, the conv's weights (input channels
 // [0, cup) = the transposed conv's output, as torch.cat([xu, skip]) orders them, unet.py:172,178,184); wt: (cl, cup, 2, 2) fp32, the
@@ -569,15 +632,7 @@ size_t wsu_conv3x3_up_packed_bytes(int cl, int cout) {
 // The skip half is wsu_conv3x3_pack_f4 of w3[:, cup:].
 int wsu_conv3x3_up_pack(const float* w3_oihw, const float* wt, const float* bt, const float* b3, void* w_low_packed, float* bias_out, float* wc_dense,
                         int cl, int cup, int c2, int cout, void* stream) {
-    WSU_REQUIRE(w3_oihw && wt && w_low_packed && bias_out, "conv3x3_up_pack: null pointer");
-    WSU_REQUIRE(cl > 0 && cl % 16 == 0 && cup > 0 && c2 >= 0 && cout > 0 && cout % WSU_COB == 0,
-                "conv3x3_up_pack: cl=%d must be a multiple of 16, cout=%d of %d, cup=%d > 0", cl, cout, WSU_COB, cup);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(pack_up_low_kernel<WSU_PLANAR_Q>, dim3(1024), dim3(128), 0, s, w3_oihw, wt, (char*)w_low_packed, wc_dense, cup, c2, cl, cout);
-    int rc = wsu_check_launch("pack_up_low_kernel");
-    if (rc != WSU_OK) return rc;
-    hipLaunchKernelGGL(up_bias_kernel, dim3((cout + 63) / 64), dim3(64), 0, s, w3_oihw, bt, b3, bias_out, cup, c2, cout);
-    return wsu_check_launch("up_bias_kernel");
+    return up_pack(WSU_PLANAR_Q, w3_oihw, wt, bt, b3, w_low_packed, bias_out, wc_dense, cl, cup, c2, cout, stream);
 }
 
 // Forward of relu(conv3x3_reflect(cat[convT2x2_s2(x_low), x_skip])) in one launch (K1u above).  x_low: planar Q tensor, cl channels at (h/2) x
@@ -586,87 +641,24 @@ int wsu_conv3x3_up_pack(const float* w3_oihw, const float* wt, const float* bt, 
 // range_flag as in wsu_conv3x3_q_fwd.  Asynchronous on `stream`; allocates nothing.
 int wsu_conv3x3_up_q_fwd(const void* x_low, const void* x_skip, const void* w_skip_packed, const void* w_low_packed, const float* bias, void* y,
                          int n, int h, int w, int cl, int c2, int cout, int relu, unsigned* range_flag, void* stream) {
-    WSU_REQUIRE(x_low && x_skip && w_skip_packed && w_low_packed && y, "conv3x3_up_q: null pointer");
-    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "conv3x3_up_q: bad shape n=%d h=%d w=%d (the output of a stride-2 transposed conv is even)", n, h, w);
-    WSU_REQUIRE(cl > 0 && cl % 16 == 0 && c2 > 0 && c2 % 16 == 0, "conv3x3_up_q: cl=%d c2=%d must be positive multiples of 16", cl, c2);
-    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= MAX_COUT, "conv3x3_up_q: cout=%d must be a multiple of %d (<= %d)", cout, WSU_COB, MAX_COUT);
-    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "conv3x3_up_q: h*w too large (a chunk must stay below 4 GiB)");
-    UArgs a;
-    a.xl = (const char*)x_low; a.xs = (const char*)x_skip; a.wps = (const char*)w_skip_packed; a.wpl = (const char*)w_low_packed; a.bias = bias;
-    a.y = (char*)y;
-    a.n = n; a.h = h; a.w = w; a.hl = h / 2; a.wl = w / 2; a.cl = cl; a.c2 = c2; a.cout = cout;
-    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ltiles_x = (a.wl + 31) / 32; a.ncb = cout / WSU_COB;
-    a.nchS = c2 / 16; a.nchL = cl / 16; a.relu = relu; a.range_flag = range_flag;
-    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
-    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_up_q: %lld tiles out of range", nt);
-    WSU_REQUIRE((long long)a.ncb * a.nchL * 2 * W_L < 0x7FFFFFF0LL && (long long)a.ncb * a.nchS * W_S < 0x7FFFFFF0LL, "conv3x3_up_q: packed weights beyond 2 GiB");
-    a.ntiles = (int)nt;
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            wsu_set_error("conv3x3_up_q: cannot query the device"); return WSU_ERR_HIP;
-        }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_qu_kernel<WSU_PLANAR_Q>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_qu): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-        ncu = prop.multiProcessorCount;
-    }
-    hipLaunchKernelGGL(conv3x3_qu_kernel<WSU_PLANAR_Q>, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3(NT), LDS_TOTAL, static_cast<hipStream_t>(stream), a);
-    return wsu_check_launch("conv3x3_qu_kernel");
+    return up_fwd(WSU_PLANAR_Q, x_low, x_skip, w_skip_packed, w_low_packed, bias, y, n, h, w, cl, c2, cout, relu, range_flag, stream);
 }
 
 // ---- format H (mode 'f16p', include/wsu.h K1h) ----------------------------------------------------------------------------------------
 // Bytes of the packed low half in format H: per (64-co block, 16-channel chunk of x_low, dy) one 16 KB slice [class 4][dx 2][plane 2][64 co][16 B].
-size_t wsu_conv3x3_up_packed_h_bytes(int cl, int cout) {
-    if (cl <= 0 || cout <= 0 || cl % 16 || cout % WSU_COB) return 0;
-    return (size_t)(cout / WSU_COB) * (cl / 16) * 2 * W_L_H;
-}
+size_t wsu_conv3x3_up_packed_h_bytes(int cl, int cout) { return up_packed_bytes(WSU_PLANAR_H, cl, cout); }
 
 // wsu_conv3x3_up_pack in format H: the combined weights rounded to f16 once (wc_dense and bias_out as there).  The skip half is
 // wsu_conv3x3_pack_h of w3[:, cup:].
 int wsu_conv3x3_up_pack_h(const float* w3_oihw, const float* wt, const float* bt, const float* b3, void* w_low_packed, float* bias_out, float* wc_dense,
                           int cl, int cup, int c2, int cout, void* stream) {
-    WSU_REQUIRE(w3_oihw && wt && w_low_packed && bias_out, "conv3x3_up_pack_h: null pointer");
-    WSU_REQUIRE(cl > 0 && cl % 16 == 0 && cup > 0 && c2 >= 0 && cout > 0 && cout % WSU_COB == 0,
-                "conv3x3_up_pack_h: cl=%d must be a multiple of 16, cout=%d of %d, cup=%d > 0", cl, cout, WSU_COB, cup);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(pack_up_low_kernel<WSU_PLANAR_H>, dim3(1024), dim3(128), 0, s, w3_oihw, wt, (char*)w_low_packed, wc_dense, cup, c2, cl, cout);
-    int rc = wsu_check_launch("pack_up_low_kernel<H>");
-    if (rc != WSU_OK) return rc;
-    hipLaunchKernelGGL(up_bias_kernel, dim3((cout + 63) / 64), dim3(64), 0, s, w3_oihw, bt, b3, bias_out, cup, c2, cout);
-    return wsu_check_launch("up_bias_kernel");
+    return up_pack(WSU_PLANAR_H, w3_oihw, wt, bt, b3, w_low_packed, bias_out, wc_dense, cl, cup, c2, cout, stream);
 }
 
 // wsu_conv3x3_up_q_fwd on planar H tensors (x_low, x_skip, y): weights of wsu_conv3x3_pack_h (skip half) and wsu_conv3x3_up_pack_h.
 int wsu_conv3x3_up_h_fwd(const void* x_low, const void* x_skip, const void* w_skip_packed, const void* w_low_packed, const float* bias, void* y,
                          int n, int h, int w, int cl, int c2, int cout, int relu, unsigned* range_flag, void* stream) {
-    WSU_REQUIRE(x_low && x_skip && w_skip_packed && w_low_packed && y, "conv3x3_up_h: null pointer");
-    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "conv3x3_up_h: bad shape n=%d h=%d w=%d (the output of a stride-2 transposed conv is even)", n, h, w);
-    WSU_REQUIRE(cl > 0 && cl % 16 == 0 && c2 > 0 && c2 % 16 == 0, "conv3x3_up_h: cl=%d c2=%d must be positive multiples of 16", cl, c2);
-    WSU_REQUIRE(cout > 0 && cout % WSU_COB == 0 && cout <= MAX_COUT, "conv3x3_up_h: cout=%d must be a multiple of %d (<= %d)", cout, WSU_COB, MAX_COUT);
-    WSU_REQUIRE((long long)h * w * 50 < 0xFFFFFFF0LL, "conv3x3_up_h: h*w too large (a chunk must stay below 4 GiB)");
-    UArgs a;
-    a.xl = (const char*)x_low; a.xs = (const char*)x_skip; a.wps = (const char*)w_skip_packed; a.wpl = (const char*)w_low_packed; a.bias = bias;
-    a.y = (char*)y;
-    a.n = n; a.h = h; a.w = w; a.hl = h / 2; a.wl = w / 2; a.cl = cl; a.c2 = c2; a.cout = cout;
-    a.tiles_x = (w + TW - 1) / TW; a.tiles_y = (h + TH - 1) / TH; a.ltiles_x = (a.wl + 31) / 32; a.ncb = cout / WSU_COB;
-    a.nchS = c2 / 16; a.nchL = cl / 16; a.relu = relu; a.range_flag = range_flag;
-    const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
-    WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "conv3x3_up_h: %lld tiles out of range", nt);
-    WSU_REQUIRE((long long)a.ncb * a.nchL * 2 * W_L_H < 0x7FFFFFF0LL && (long long)a.ncb * a.nchS * W_S_H < 0x7FFFFFF0LL, "conv3x3_up_h: packed weights beyond 2 GiB");
-    a.ntiles = (int)nt;
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            wsu_set_error("conv3x3_up_h: cannot query the device"); return WSU_ERR_HIP;
-        }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_qu_kernel<WSU_PLANAR_H>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(conv3x3_qu<H>): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-        ncu = prop.multiProcessorCount;
-    }
-    hipLaunchKernelGGL(conv3x3_qu_kernel<WSU_PLANAR_H>, dim3(a.ntiles < ncu ? a.ntiles : ncu), dim3(NT), LDS_TOTAL, static_cast<hipStream_t>(stream), a);
-    return wsu_check_launch("conv3x3_qu_kernel<H>");
+    return up_fwd(WSU_PLANAR_H, x_low, x_skip, w_skip_packed, w_low_packed, bias, y, n, h, w, cl, c2, cout, relu, range_flag, stream);
 }
 
 }  // extern "C"

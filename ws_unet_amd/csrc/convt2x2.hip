@@ -422,8 +422,7 @@ int launch_ct_f16f8(const CtArgs& a_in, hipStream_t s) {
     const int lds = f8t::EPI4 > f8t::LDS_MAIN4 ? f8t::EPI4 : f8t::LDS_MAIN4;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2x2_f16f8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(convt2x2_f16f8): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        if (int rc = wsu_raise_lds(convt2x2_f16f8_kernel, lds, "convt2x2_f16f8")) return rc;
         attr_done = true;
     }
     const long long nblk = (long long)a.n * a.tiles_x * a.tiles_y * a.ncb;
@@ -439,9 +438,7 @@ int launch_ct(const CtArgs& a, hipStream_t s) {
     const int lds = EPI > LDS_MAIN ? EPI : LDS_MAIN;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2x2_kernel<MODE, PS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(convt2x2): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        if (int rc = wsu_raise_lds(convt2x2_kernel<MODE, PS>, lds, "convt2x2")) return rc;
         attr_done = true;
     }
     const long long nblk = (long long)a.n * a.tiles_x * a.tiles_y * a.ncb;

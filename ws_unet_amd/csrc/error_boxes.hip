@@ -410,9 +410,7 @@ int wsu_ae_select(const float* keys, size_t stride, int num_pred, int anchor, lo
     if (hipMemsetAsync(flags, 0, (size_t)num_pred * sizeof(uint32_t), s) != hipSuccess) return wsu_check_launch("ae_select memset");
     static bool attr_done = false;     // benign race: idempotent
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ae_select_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           AE_MAX_SLICES * AE_RANKS * AE_BINS * (int)sizeof(uint32_t));
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(ae_select_hist): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        if (int rc = wsu_raise_lds(ae_select_hist_kernel, AE_MAX_SLICES * AE_RANKS * AE_BINS * (int)sizeof(uint32_t), "ae_select_hist")) return rc;
         attr_done = true;
     }
     const int parts = ae_parts(count);

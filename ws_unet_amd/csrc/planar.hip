@@ -679,16 +679,13 @@ int wsu_convt2x2_pl_fwd(const void* x, const void* w_packed, const float* bias, 
     const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
     WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "convt2x2_pl: %lld tiles out of range", nt);
     a.ntiles = (int)nt;
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            wsu_set_error("convt2x2_pl: cannot query the device"); return WSU_ERR_HIP;
-        }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2x2_pl_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, ct::LDS_TOTAL);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2x2_pl_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, ct::LDS_TOTAL);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(convt2x2_pl): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-        ncu = prop.multiProcessorCount;
+    const int ncu = wsu_cu_count("convt2x2_pl");
+    if (!ncu) return WSU_ERR_HIP;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (int rc = wsu_raise_lds(convt2x2_pl_kernel<false>, ct::LDS_TOTAL, "convt2x2_pl")) return rc;
+        if (int rc = wsu_raise_lds(convt2x2_pl_kernel<true>, ct::LDS_TOTAL, "convt2x2_pl")) return rc;
+        attr_done = true;
     }
     const int grid = (int)(nt < ncu ? nt : ncu);
     if (a.yq) hipLaunchKernelGGL(convt2x2_pl_kernel<true>, dim3(grid), dim3(ct::NT), ct::LDS_TOTAL, static_cast<hipStream_t>(stream), a);
@@ -719,16 +716,13 @@ int wsu_convt2x2_pl_bwd_data(const void* dy, const void* w_packed_dgrad, void* d
     const long long nt = (long long)n * a.tiles_x * a.tiles_y * a.ncb;
     WSU_REQUIRE(nt > 0 && nt < 0x3FFFFFFFLL, "convt2x2_pl_bwd_data: %lld tiles out of range", nt);
     a.ntiles = (int)nt;
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-            wsu_set_error("convt2x2_pl_bwd_data: cannot query the device"); return WSU_ERR_HIP;
-        }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2x2_bwd_pl_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, CtbGeo<false>::LDS_TOTAL);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2x2_bwd_pl_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, CtbGeo<true>::LDS_TOTAL);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(convt2x2_bwd_pl): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-        ncu = prop.multiProcessorCount;
+    const int ncu = wsu_cu_count("convt2x2_pl_bwd_data");
+    if (!ncu) return WSU_ERR_HIP;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (int rc = wsu_raise_lds(convt2x2_bwd_pl_kernel<false>, CtbGeo<false>::LDS_TOTAL, "convt2x2_bwd_pl")) return rc;
+        if (int rc = wsu_raise_lds(convt2x2_bwd_pl_kernel<true>, CtbGeo<true>::LDS_TOTAL, "convt2x2_bwd_pl")) return rc;
+        attr_done = true;
     }
     const int grid = (int)(nt < ncu ? nt : ncu);
     if (products == WSU_PRODUCTS_F16) hipLaunchKernelGGL(convt2x2_bwd_pl_kernel<true>, dim3(grid), dim3(ctb::NT), CtbGeo<true>::LDS_TOTAL, static_cast<hipStream_t>(stream), a);

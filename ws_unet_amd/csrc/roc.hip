@@ -170,9 +170,7 @@ int wsu_roc_counts(const double* scores, const signed char* labels, const long l
     if (hipMemsetAsync(p.hist, 0, roc_hist_words(groups, t) * 8, s) != hipSuccess) return wsu_check_launch("roc_counts memset");
     static bool attr_done = false;     // benign race: idempotent
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&roc_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)roc_lds_bytes(ROC_MAX_T));
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(roc_hist): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        if (int rc = wsu_raise_lds(roc_hist_kernel, (int)roc_lds_bytes(ROC_MAX_T), "roc_hist")) return rc;
         attr_done = true;
     }
     if (longest > 0) {

@@ -1105,15 +1105,13 @@ int run_wgrad(WgArgs a, float* dw, float* db, float* workspace, size_t workspace
     if (x3) {
         static bool attr_x3 = false;
         if (!attr_x3) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_x3_kernel<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, GeoX3<KIND>::LDS);
-            if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(wgrad_x3): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+            if (int rc = wsu_raise_lds(wgrad_x3_kernel<KIND>, GeoX3<KIND>::LDS, "wgrad_x3")) return rc;
             attr_x3 = true;
         }
         if (f8) {
             static bool attr_f8 = false;
             if (!attr_f8) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_x3_kernel<KIND, true>), hipFuncAttributeMaxDynamicSharedMemorySize, GeoX3<KIND>::LDS_F8);
-                if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(wgrad_f8): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+                if (int rc = wsu_raise_lds(wgrad_x3_kernel<KIND, true>, GeoX3<KIND>::LDS_F8, "wgrad_f8")) return rc;
                 attr_f8 = true;
             }
             hipLaunchKernelGGL((wgrad_x3_kernel<KIND, true>), dim3(nsplit * a.nmb * a.nnb), dim3(NT), GeoX3<KIND>::LDS_F8, s, a);
@@ -1126,8 +1124,7 @@ int run_wgrad(WgArgs a, float* dw, float* db, float* workspace, size_t workspace
     }
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(wgrad): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+        if (int rc = wsu_raise_lds(wgrad_kernel<KIND>, G::LDS, "wgrad")) return rc;
         attr_done = true;
     }
     hipLaunchKernelGGL(wgrad_kernel<KIND>, dim3(nsplit * a.nmb * a.nnb), dim3(NT), G::LDS, s, a);
@@ -1162,14 +1159,13 @@ int run_wgrad_pl(WgPlArgs a, float* dw, float* db, float* workspace, size_t work
     a.bpart = db ? workspace + (size_t)nsplit * slab / sizeof(float) : nullptr;
     if constexpr (KIND == 0) {                                         // conv: the ring kernel (the register-staged kernel below serves the transposed conv)
         // one persistent-style workgroup per CU: the splits cover the tiles, fewer and longer than the register-staged kernel's
-        static int ncu = 0;
-        if (ncu == 0) {
-            int dev = 0; hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { wsu_set_error("wgrad_ring: cannot query the device"); return WSU_ERR_HIP; }
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ring_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, wgr::LDS_TOTAL);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ring_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, wgr::LDS_TOTAL);
-            if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(wgrad_ring): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
-            ncu = prop.multiProcessorCount;
+        const int ncu = wsu_cu_count("wgrad_ring");
+        if (!ncu) return WSU_ERR_HIP;
+        static bool attr = false;
+        if (!attr) {
+            if (int rc = wsu_raise_lds(wgrad_ring_kernel<false>, wgr::LDS_TOTAL, "wgrad_ring")) return rc;
+            if (int rc = wsu_raise_lds(wgrad_ring_kernel<true>, wgr::LDS_TOTAL, "wgrad_ring")) return rc;
+            attr = true;
         }
         int ns = (ncu + a.nmb * a.nnb - 1) / (a.nmb * a.nnb);
         ns = max(1, min(ns, min(nsplit, a.ntiles)));
@@ -1188,9 +1184,8 @@ int run_wgrad_pl(WgPlArgs a, float* dw, float* db, float* workspace, size_t work
         constexpr int LDS_H = GP::U_BYTES + GP::V_BYTES;
         static bool attr = false;
         if (!attr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pl_kernel<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, GeoX3<KIND>::LDS_F8);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pl_kernel<KIND, true, THP>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H);
-            if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(wgrad_pl): %s", hipGetErrorString(e)); return WSU_ERR_HIP; }
+            if (int rc = wsu_raise_lds(wgrad_pl_kernel<KIND>, GeoX3<KIND>::LDS_F8, "wgrad_pl")) return rc;
+            if (int rc = wsu_raise_lds(wgrad_pl_kernel<KIND, true, THP>, LDS_H, "wgrad_pl")) return rc;
             attr = true;
         }
         if (a.honly) hipLaunchKernelGGL((wgrad_pl_kernel<KIND, true, THP>), dim3(nsplit * a.nmb * a.nnb), dim3(NT), LDS_H, s, a);

@@ -23,6 +23,24 @@ int wsu_check_launch(const char* what) {
     return WSU_OK;
 }
 
+int wsu_cu_count(const char* who) {
+    static int ncu = 0;
+    if (ncu == 0) {
+        int dev = 0; hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
+            wsu_set_error("%s: cannot query the device", who); return 0;
+        }
+        ncu = prop.multiProcessorCount;
+    }
+    return ncu;
+}
+
+int wsu_raise_lds_ptr(const void* kernel, int bytes, const char* who) {
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) { wsu_set_error("hipFuncSetAttribute(%s): %s", who, hipGetErrorString(e)); return WSU_ERR_HIP; }
+    return WSU_OK;
+}
+
 extern "C" {
 int wsu_version(void) { return WSU_VERSION; }
 const char* wsu_last_error(void) { return g_err; }

@@ -28,6 +28,13 @@ int wsu_check_launch(const char* what);
     } while (0)
 // a C-linkage helper called across translation units that is no part of include/wsu.h: not exported by libwsu.so
 #define WSU_INTERNAL extern "C" __attribute__((visibility("hidden")))
+// CU count of the current device, queried once per process; 0 after "<who>: cannot query the device" has been set (the caller returns WSU_ERR_HIP)
+WSU_INTERNAL int wsu_cu_count(const char* who);
+// raises a kernel's dynamic-LDS limit to `bytes`; WSU_ERR_HIP after "hipFuncSetAttribute(<who>): <hip error string>" has been set
+WSU_INTERNAL int wsu_raise_lds_ptr(const void* kernel, int bytes, const char* who);
+template <class... A> inline int wsu_raise_lds(void (*kernel)(A...), int bytes, const char* who) {
+    return wsu_raise_lds_ptr(reinterpret_cast<const void*>(kernel), bytes, who);
+}
 
 // ---- tiling constants shared by packers and kernels ----------------------------------------------
 // A "chunk" is 64 bytes of channel data per pixel, staged in LDS as 4 granule planes of 16 bytes:

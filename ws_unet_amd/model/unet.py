@@ -169,6 +169,20 @@ class UNet(nn.Module):
         self._pack_cache: Dict[tuple, tuple] = {}
 
     # ---- packed-weight cache (re-packed only when a parameter was modified) -------------------------
+    _PACKERS = {
+        "conv_f4": lambda p, mode: ops.pack_conv3x3_f4(p),
+        "conv_h": lambda p, mode: ops.pack_conv3x3_h(p),
+        "conv": ops.pack_conv3x3,
+        "dgrad": lambda p, mode: ops.pack_conv3x3(p, mode, dgrad=True),
+        "ring": lambda p, mode: ops.pack_conv3x3_ring(p),
+        # e11's weights tap-major (9, 64): the scalar loads of ops.conv3x3_q_fused_first
+        "taps": lambda p, mode: p.detach().reshape(p.shape[0], 9).t().contiguous(),
+        "convt_dgrad_pl": lambda p, mode: ops.pack_convt2x2_pl_dgrad(p),
+        "convt_dgrad": ops.pack_convt2x2_dgrad,
+        "convt": ops.pack_convt2x2,
+    }
+    _UP_PACKERS = {ops.PLANAR_Q: ops.pack_conv3x3_up, ops.PLANAR_H: ops.pack_conv3x3_up_h}
+
     def _packed(self, name: str, mode: int, kind: str) -> torch.Tensor:
         p = getattr(self, name).weight
         key = (name, mode, kind)
@@ -176,38 +190,21 @@ class UNet(nn.Module):
         hit = self._pack_cache.get(key)
         if hit is not None and hit[0] == tag:
             return hit[1]
-        if kind == "conv_f4":
-            packed = ops.pack_conv3x3_f4(p)
-        elif kind == "conv_h":
-            packed = ops.pack_conv3x3_h(p)
-        elif kind == "conv":
-            packed = ops.pack_conv3x3(p, mode)
-        elif kind == "dgrad":
-            packed = ops.pack_conv3x3(p, mode, dgrad=True)
-        elif kind == "ring":
-            packed = ops.pack_conv3x3_ring(p)
-        elif kind == "taps":                                         # e11's weights tap-major (9, 64): the scalar loads of ops.conv3x3_q_fused_first
-            packed = p.detach().reshape(p.shape[0], 9).t().contiguous()
-        elif kind == "convt_dgrad_pl":
-            packed = ops.pack_convt2x2_pl_dgrad(p)
-        elif kind == "convt_dgrad":
-            packed = ops.pack_convt2x2_dgrad(p, mode)
-        else:
-            packed = ops.pack_convt2x2(p, mode)
+        packed = self._PACKERS[kind](p, mode)
         self._pack_cache[key] = (tag, packed)
         return packed
 
-    def _packed_up(self, up: str, c1: str, fmt: str = "q"):
-        """(w_skip_packed, w_low_packed, bias) of the fused decoder-block entry (ops.pack_conv3x3_up; fmt 'h': ops.pack_conv3x3_up_h), cached on
-        all four parameters' versions."""
+    def _packed_up(self, up: str, c1: str, fmt: int = ops.PLANAR_Q):
+        """(w_skip_packed, w_low_packed, bias) of the fused decoder-block entry (ops.pack_conv3x3_up; fmt PLANAR_H: ops.pack_conv3x3_up_h), cached
+        on all four parameters' versions."""
         lu, l1 = getattr(self, up), getattr(self, c1)
         ps = (lu.weight, lu.bias, l1.weight, l1.bias)
-        key = (up, c1, "up_" + fmt)
+        key = (up, c1, "up", fmt)
         tag = tuple((p._version, p.data_ptr(), p.device) for p in ps)
         hit = self._pack_cache.get(key)
         if hit is not None and hit[0] == tag:
             return hit[1]
-        packed = (ops.pack_conv3x3_up_h if fmt == "h" else ops.pack_conv3x3_up)(l1.weight, lu.weight, lu.bias, l1.bias)
+        packed = self._UP_PACKERS[fmt](l1.weight, lu.weight, lu.bias, l1.bias)
         self._pack_cache[key] = (tag, packed)
         return packed
 
@@ -356,8 +353,6 @@ class UNet(nn.Module):
         """unet.py:137-189 on planar F16F8P activations: e11 (VALU) -> 3x3 convs with fused pool / concat / head and transposed convs, all
         persistent LDS-DMA kernels; no intermediate leaves the format.  Mode 'f16p': planar H tensors throughout, every decoder block through
         the fused entry ops.conv3x3_up_h (WSU_FUSE_UP and WSU_FUSE_FIRST_Q are ignored: the mode has no two-kernel decoder path)."""
-        if self.mode == "f16p":
-            return self._forward_planar_h(x, want_logit)
         W = ops.MODE_F16F8                                           # weights are packed as for 'f16f8'
         # 'f16f8q': the first conv of every decoder block (the two most expensive layers of unet_2) multiplies without the activations'
         # residual term: 15 instead of 19 matrix units there, MAE 4e-6 -> ~4e-5 on the gate's weights (still 2.5x inside 1e-4)
@@ -365,29 +360,34 @@ class UNet(nn.Module):
         # 'f16f4p' (default): block-scaled fp4 cross terms on planar Q tensors (ops.PlanarQ; csrc/conv3x3_q.hip): every producer's epilogue writes
         # the fp4 granule and scale byte its consumer multiplies; only the two tensors the transposed convs read stay in the e4m3-residual format
         q4 = self.mode == "f16f4p"
-        CK = "conv_f4" if q4 else "conv"
-        Q, A = ops.PLANAR_Q, ops.PLANAR_A
+        # 'f16p': the walk of 'f16f4p' on planar H tensors (ops.PlanarH), the fused entry for every decoder block, no format-A tensor anywhere
+        h16 = self.mode == "f16p"
+        CK = "conv_h" if h16 else "conv_f4" if q4 else "conv"
+        A = ops.PLANAR_A
+        S = ops.PLANAR_H if h16 else ops.PLANAR_Q                    # the storage format between the layers of the 'f16f4p' / 'f16p' walk
         tag = ops.set_layer
         e11 = self.e11
         rf = self._range_flag_tensor(x.device)
 
-        def conv(xa, xb, name, layer, fmt=Q, xres=True, **kw):       # one 3x3 conv of the planar path in this mode's arithmetic
+        def conv(xa, xb, name, layer, fmt=S, xres=True, **kw):       # one 3x3 conv of the planar path in this mode's arithmetic
+            if h16:
+                return ops.conv3x3_h(xa, xb, self._packed(name, W, CK), layer.bias.detach(), layer.out_channels, **kw)
             if q4:
                 return ops.conv3x3_q(xa, xb, self._packed(name, W, CK), layer.bias.detach(), layer.out_channels, y_format=fmt, **kw)
             return ops.conv3x3_pl(xa, xb, self._packed(name, W, CK), layer.bias.detach(), layer.out_channels, x_residual=xres, **kw)
 
         def fuse_up(depth):                                          # decoder block `depth` runs upconv + concat + first conv as one launch
             l1 = getattr(self, dec_names(depth)[1])
-            return q4 and self.fuse_up_planar and l1.out_channels <= 512 and l1.out_channels % 64 == 0
+            return h16 or (q4 and self.fuse_up_planar and l1.out_channels <= 512 and l1.out_channels % 64 == 0)
 
         # e11 is folded into e12 (its 64 channels are computed by the loader waves of the persistent kernel) for single-plane inputs -- an
         # experiment switch of the e4m3 modes (the fused kernel multiplies e4m3 cross terms and writes the e4m3-residual format)
-        fuse_first = self.fuse_first_planar and not q4 and e11.in_channels == 1 and e11.out_channels == 64 and self.nsteps >= 1
+        fuse_first = self.fuse_first_planar and not (q4 or h16) and e11.in_channels == 1 and e11.out_channels == 64 and self.nsteps >= 1
         fuse_first_q = q4 and self.fuse_first_q and e11.in_channels == 1 and e11.out_channels == 64 and self.nsteps >= 1 and self.e12.in_channels == 64
         cur = None
         if not fuse_first and not fuse_first_q:
             tag("e11")
-            cur = ops.conv3x3_first_pl(x, e11.weight, e11.bias.detach(), range_flag=rf, y_format=Q if q4 else A)
+            cur = ops.conv3x3_first_pl(x, e11.weight, e11.bias.detach(), range_flag=rf, y_format=S if (q4 or h16) else A)
         skips: List = []
         for lvl in range(self.nsteps + 1):
             a, b = ENC[lvl]
@@ -419,63 +419,23 @@ class UNet(nn.Module):
                 full, cur = conv(cur, None, b, lb, pool=True, range_flag=rf)
                 skips.append(full)
             else:
-                cur = conv(cur, None, b, lb, fmt=Q if fuse_up(self.nsteps) else A, range_flag=rf)        # feeds the transposed conv
+                cur = conv(cur, None, b, lb, fmt=S if fuse_up(self.nsteps) else A, range_flag=rf)        # feeds the transposed conv
         for depth in range(self.nsteps, 0, -1):
             up, c1, c2 = dec_names(depth)
             lu, l1, l2 = getattr(self, up), getattr(self, c1), getattr(self, c2)
             if fuse_up(depth):
                 tag(up + "+" + c1)
-                cur = ops.conv3x3_up_q(cur, skips[depth - 1], *self._packed_up(up, c1), l1.out_channels, range_flag=rf)
+                cur = (ops.conv3x3_up_h if h16 else ops.conv3x3_up_q)(cur, skips[depth - 1], *self._packed_up(up, c1, S), l1.out_channels, range_flag=rf)
             else:
                 tag(up)
-                xu = ops.convt2x2_pl(cur, self._packed(up, W, "convt"), lu.bias.detach(), lu.out_channels, range_flag=rf, y_format=Q if q4 else A)
+                xu = ops.convt2x2_pl(cur, self._packed(up, W, "convt"), lu.bias.detach(), lu.out_channels, range_flag=rf, y_format=S if q4 else A)
                 tag(c1)
                 cur = conv(xu, skips[depth - 1], c1, l1, xres=not quick, range_flag=rf)
             if depth == 1:
                 tag(c2 + "+outconv")
                 return conv(cur, None, c2, l2, want_y=False, head_w=self.outconv.weight.detach(), head_b=self.outconv.bias.detach(), want_logit=want_logit)
             tag(c2)
-            cur = conv(cur, None, c2, l2, fmt=Q if fuse_up(depth - 1) else A, range_flag=rf)           # feeds the next transposed conv
-        raise AssertionError("unreachable")
-
-    def _forward_planar_h(self, x: torch.Tensor, want_logit: bool = False):
-        """The 'f16p' branch of _forward_planar: e11 -> planar H, 3x3 convs with fused pool and head (ops.conv3x3_h), the fused decoder entry
-        (ops.conv3x3_up_h) for every decoder block."""
-        tag = ops.set_layer
-        rf = self._range_flag_tensor(x.device)
-        e11 = self.e11
-        head = {"want_y": False, "head_w": self.outconv.weight.detach(), "head_b": self.outconv.bias.detach(), "want_logit": want_logit}
-
-        def conv(xa, name, **kw):
-            layer = getattr(self, name)
-            return ops.conv3x3_h(xa, None, self._packed(name, ops.MODE_F16P, "conv_h"), layer.bias.detach(), layer.out_channels, **kw)
-
-        tag("e11")
-        cur = ops.conv3x3_first_pl(x, e11.weight, e11.bias.detach(), range_flag=rf, y_format=ops.PLANAR_H)
-        skips: List = []
-        for lvl in range(self.nsteps + 1):
-            a, b = ENC[lvl]
-            if lvl >= 1:
-                tag(a)
-                cur = conv(cur, a, range_flag=rf)
-            if lvl == self.nsteps == 0:
-                tag(b + "+outconv")
-                return conv(cur, b, **head)
-            tag(b)
-            if lvl < self.nsteps:
-                full, cur = conv(cur, b, pool=True, range_flag=rf)
-                skips.append(full)
-            else:
-                cur = conv(cur, b, range_flag=rf)
-        for depth in range(self.nsteps, 0, -1):
-            up, c1, c2 = dec_names(depth)
-            tag(up + "+" + c1)
-            cur = ops.conv3x3_up_h(cur, skips[depth - 1], *self._packed_up(up, c1, "h"), getattr(self, c1).out_channels, range_flag=rf)
-            if depth == 1:
-                tag(c2 + "+outconv")
-                return conv(cur, c2, **head)
-            tag(c2)
-            cur = conv(cur, c2, range_flag=rf)
+            cur = conv(cur, None, c2, l2, fmt=S if fuse_up(depth - 1) else A, range_flag=rf)           # feeds the next transposed conv
         raise AssertionError("unreachable")
 
     def forward(self, x_in: torch.Tensor) -> torch.Tensor:

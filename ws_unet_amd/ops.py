@@ -6,6 +6,7 @@ shape (N, H, W, C), fp32 for modes 'f32' / 'bf16x3', bf16 for mode 'bf16'.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import numpy as np
@@ -158,17 +159,7 @@ def pack_conv3x3(w: torch.Tensor, mode: int, dgrad: bool = False) -> torch.Tenso
 def pack_conv3x3_f4(w: torch.Tensor) -> torch.Tensor:
     """w: (Cout, Cin, 3, 3) fp32 OIHW on the device -> the packed weights of conv3x3_q: f16 planes + block-scaled fp4 cross-term
     granules + scale bytes (wsu_conv3x3_pack_f4)."""
-    lib = _lib.load()
-    w = w.detach()
-    _dev_check(w)
-    assert w.dtype == torch.float32 and w.dim() == 4 and w.shape[2:] == (3, 3)
-    cout, cin = w.shape[:2]
-    nbytes = lib.wsu_conv3x3_packed_f4_bytes(cin, cout)
-    if nbytes == 0:
-        raise _lib.WsuError(f"fp4 packing needs cin % 16 == 0 and cout % 64 == 0 (got {cin}, {cout})")
-    out = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    check(lib.wsu_conv3x3_pack_f4(w.data_ptr(), out.data_ptr(), cin, cout, _stream()), "wsu_conv3x3_pack_f4")
-    return out
+    return _pack_conv3x3_planar(PLANAR_Q, w)
 
 
 def pack_convt2x2(w: torch.Tensor, mode: int) -> torch.Tensor:
@@ -276,22 +267,16 @@ PLANAR_A, PLANAR_Q, PLANAR_H = 0, 1, 2     # include/wsu.h WSU_PLANAR_*: the e4m
                                            # the planar H format of mode 'f16p'
 
 
-class PlanarQ:
-    """A planar Q activation tensor ('F16F4P' storage, include/wsu.h, round 4): per image and 16-channel chunk the planes f16 ch 0-7 | f16 ch
-    8-15 | Q (32 fp4 nibbles per pixel: the f16 parts and the residuals * 2^11, both over the block's power-of-two scale) as [H][W][16 B], then
-    one E8M0 scale byte per pixel in 16 x 32-pixel tile blocks.  `data`: uint8 (N, C/16, chunk_bytes).  Written by the producing kernel's
-    epilogue (conv3x3_q / convt2x2_pl / conv3x3_first_pl with y_format=PLANAR_Q), read by conv3x3_q; opaque to everything else."""
+class _Planar:
+    """A planar activation tensor of the Q / H inference paths: `data` uint8 (N, C/16, chunk_bytes(h, w)), opaque to everything but the kernels
+    of its format `fmt` (PLANAR_Q / PLANAR_H)."""
     __slots__ = ("data", "n", "c", "h", "w")
 
     def __init__(self, data: torch.Tensor, n: int, c: int, h: int, w: int):
         self.data, self.n, self.c, self.h, self.w = data, n, c, h, w
 
-    @staticmethod
-    def chunk_bytes(h: int, w: int) -> int:
-        return 48 * h * w + 512 * ((h + 15) // 16) * ((w + 31) // 32)
-
     @classmethod
-    def empty(cls, n: int, c: int, h: int, w: int, device) -> "PlanarQ":
+    def empty(cls, n: int, c: int, h: int, w: int, device):
         assert c % 16 == 0
         return cls(torch.empty((n, c // 16, cls.chunk_bytes(h, w)), dtype=torch.uint8, device=device), n, c, h, w)
 
@@ -303,28 +288,147 @@ class PlanarQ:
         return self.data.data_ptr()
 
 
-class PlanarH:
+class PlanarQ(_Planar):
+    """A planar Q activation tensor ('F16F4P' storage, include/wsu.h, round 4): per image and 16-channel chunk the planes f16 ch 0-7 | f16 ch
+    8-15 | Q (32 fp4 nibbles per pixel: the f16 parts and the residuals * 2^11, both over the block's power-of-two scale) as [H][W][16 B], then
+    one E8M0 scale byte per pixel in 16 x 32-pixel tile blocks.  `data`: uint8 (N, C/16, chunk_bytes).  Written by the producing kernel's
+    epilogue (conv3x3_q / convt2x2_pl / conv3x3_first_pl with y_format=PLANAR_Q), read by conv3x3_q; opaque to everything else."""
+    __slots__ = ()
+    fmt = PLANAR_Q
+
+    @staticmethod
+    def chunk_bytes(h: int, w: int) -> int:
+        return 48 * h * w + 512 * ((h + 15) // 16) * ((w + 31) // 32)
+
+
+class PlanarH(_Planar):
     """A planar H activation tensor ('F16P' storage of mode 'f16p', include/wsu.h K1h): per image and 16-channel chunk the planes f16 ch 0-7 |
     f16 ch 8-15 as [H][W][16 B] -- the first two planes of a PlanarQ chunk, no Q plane and no scale bytes (2 bytes per element).  `data`: uint8
     (N, C/16, 32 H W).  Written by conv3x3_h / conv3x3_up_h / conv3x3_first_pl(y_format=PLANAR_H), read by conv3x3_h and conv3x3_up_h."""
-    __slots__ = ("data", "n", "c", "h", "w")
-
-    def __init__(self, data: torch.Tensor, n: int, c: int, h: int, w: int):
-        self.data, self.n, self.c, self.h, self.w = data, n, c, h, w
+    __slots__ = ()
+    fmt = PLANAR_H
 
     @staticmethod
     def chunk_bytes(h: int, w: int) -> int:
         return 32 * h * w
 
-    empty = classmethod(PlanarQ.empty.__func__)
-    device = PlanarQ.device
-    data_ptr = PlanarQ.data_ptr
+
+# What the Q path (mode 'f16f4p') and the H path (mode 'f16p': one product per tap, f16(w) * f16(x), include/wsu.h K1h) differ in on the host: the
+# tensor class, the names (a public function = its KernelTimer key, then its lib functions) and the stored bytes per activation element and per
+# weight, each as (numerator, denominator).
+_PlanarFormat = namedtuple("_PlanarFormat", "cls letter conv conv_fwd packer pack packed_bytes up up_fwd up_packer up_pack up_packed_bytes "
+                                            "act_bytes weight_bytes")
+_PLANAR = {
+    PLANAR_Q: _PlanarFormat(PlanarQ, "Q", "conv3x3_q", "wsu_conv3x3_q_fwd", "pack_conv3x3_f4", "wsu_conv3x3_pack_f4", "wsu_conv3x3_packed_f4_bytes",
+                            "conv3x3_up_q", "wsu_conv3x3_up_q_fwd", "pack_conv3x3_up", "wsu_conv3x3_up_pack", "wsu_conv3x3_up_packed_bytes",
+                            (49, 16), (28, 9)),
+    PLANAR_H: _PlanarFormat(PlanarH, "H", "conv3x3_h", "wsu_conv3x3_h_fwd", "pack_conv3x3_h", "wsu_conv3x3_pack_h", "wsu_conv3x3_packed_h_bytes",
+                            "conv3x3_up_h", "wsu_conv3x3_up_h_fwd", "pack_conv3x3_up_h", "wsu_conv3x3_up_pack_h", "wsu_conv3x3_up_packed_h_bytes",
+                            (2, 1), (2, 1)),
+}
 
 
 def _planar_out(fmt: int, n: int, c: int, h: int, w: int, device):
-    if fmt == PLANAR_H:
-        return PlanarH.empty(n, c, h, w, device)
-    return PlanarQ.empty(n, c, h, w, device) if fmt == PLANAR_Q else torch.empty(planar_shape(n, c, h, w), dtype=torch.float32, device=device)
+    if fmt in _PLANAR:
+        return _PLANAR[fmt].cls.empty(n, c, h, w, device)
+    return torch.empty(planar_shape(n, c, h, w), dtype=torch.float32, device=device)
+
+
+def _pack_conv3x3_planar(fmt: int, w: torch.Tensor) -> torch.Tensor:
+    f = _PLANAR[fmt]
+    lib = _lib.load()
+    w = w.detach().contiguous()
+    _dev_check(w)
+    assert w.dtype == torch.float32 and w.dim() == 4 and w.shape[2:] == (3, 3)
+    cout, cin = w.shape[:2]
+    nbytes = getattr(lib, f.packed_bytes)(cin, cout)
+    if nbytes == 0:
+        raise _lib.WsuError(f"{'fp4' if fmt == PLANAR_Q else 'f16'} packing needs cin % 16 == 0 and cout % 64 == 0 (got {cin}, {cout})")
+    out = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    check(getattr(lib, f.pack)(w.data_ptr(), out.data_ptr(), cin, cout, _stream()), f.pack)
+    return out
+
+
+def _conv3x3_planar(fmt: int, x1, x2, w_packed, bias, cout, relu, pool, want_y, head_w, head_b, want_logit, range_flag, y_format):
+    f = _PLANAR[fmt]
+    lib = _lib.load()
+    hw2 = None if head_w is None else head_w.detach().reshape(head_w.shape[0], -1).contiguous()
+    assert isinstance(x1, f.cls) and (x2 is None or isinstance(x2, f.cls)), f"{f.conv} reads planar {f.letter} tensors (ops.Planar{f.letter})"
+    _dev_check(x1.data, None if x2 is None else x2.data, w_packed, bias, hw2, head_b)
+    n, h, w, c1 = x1.n, x1.h, x1.w, x1.c
+    c2 = 0
+    if x2 is not None:
+        assert (x2.n, x2.h, x2.w) == (n, h, w)
+        c2 = x2.c
+    assert w_packed.numel() * w_packed.element_size() == int(getattr(lib, f.packed_bytes)(c1 + c2, cout)), \
+        f"w_packed_{f.packer.rsplit('_', 1)[1]} is not {f.packer} of (cin, cout)"
+    hc = 0 if hw2 is None else hw2.shape[0]
+    yf = PLANAR_A if (hc and fmt == PLANAR_Q) else y_format           # format Q: a y beside the head is written for convt2x2_pl
+    y = _planar_out(yf, n, cout, h, w, x1.device) if want_y else None
+    yp = _planar_out(yf, n, cout, h // 2, w // 2, x1.device) if pool else None
+    out = torch.empty((n, hc, h, w), dtype=torch.float32, device=x1.device) if hc else None
+    logit = torch.empty_like(out) if (hc and want_logit) else None
+    act = n * h * w * ((c1 + c2) + (cout if want_y else 0)) + (n * (h // 2) * (w // 2) * cout if pool else 0)     # planar elements read + written
+    (an, ad), (wn, wd) = f.act_bytes, f.weight_bytes
+    meta = {"flops": 2.0 * 9 * (c1 + c2) * cout * n * h * w,
+            "bytes": float(act * an / ad + n * h * w * hc * 4 + 9 * (c1 + c2) * cout * wn / wd),
+            "bytes_2B": float(act * 2 + n * h * w * hc * 4 + 9 * (c1 + c2) * cout * 2),
+            "tiles": n * ((h + 15) // 16) * ((w + 31) // 32) * (cout // 64), "steps_per_tile": (c1 + c2) // 16}
+    check(_launch(f.conv, meta, lambda: getattr(lib, f.conv_fwd)(
+        x1.data_ptr(), _ptr(x2), w_packed.data_ptr(), _ptr(bias), _ptr(y), _ptr(yp), _ptr(hw2), _ptr(head_b), _ptr(out), _ptr(logit), hc,
+        n, h, w, c1, c2, cout, int(relu), yf, _ptr(range_flag), _stream())), f.conv_fwd)
+    if hc:
+        res = [out] + ([logit] if want_logit else []) + ([y] if want_y else [])
+        return res[0] if len(res) == 1 else tuple(res)
+    return (y, yp) if pool else y
+
+
+def _pack_conv3x3_up_planar(fmt: int, w3, wt, bt, b3, want_dense):
+    f = _PLANAR[fmt]
+    lib = _lib.load()
+    w3, wt = w3.detach().contiguous(), wt.detach().contiguous()
+    bt = None if bt is None else bt.detach().contiguous()
+    b3 = None if b3 is None else b3.detach().contiguous()
+    _dev_check(w3, wt, bt, b3)
+    assert w3.dtype == torch.float32 and w3.dim() == 4 and w3.shape[2:] == (3, 3) and wt.dtype == torch.float32 and wt.dim() == 4 and wt.shape[2:] == (2, 2)
+    cout, ctot = w3.shape[:2]
+    cl, cup = wt.shape[:2]
+    c2 = ctot - cup
+    nbytes = getattr(lib, f.up_packed_bytes)(cl, cout)
+    if nbytes == 0 or c2 <= 0 or c2 % 16:
+        raise _lib.WsuError(f"fused upsample packing needs cl % 16 == 0, c2 % 16 == 0 (> 0) and cout % 64 == 0 (got cl={cl}, cup={cup}, c2={c2}, cout={cout})")
+    w_skip = _pack_conv3x3_planar(fmt, w3[:, cup:])
+    w_low = torch.empty(nbytes, dtype=torch.uint8, device=w3.device)
+    bias = torch.empty(cout, dtype=torch.float32, device=w3.device)
+    dense = torch.empty((cout, cl, 2, 2, 2, 2), dtype=torch.float32, device=w3.device) if want_dense else None
+    check(getattr(lib, f.up_pack)(w3.data_ptr(), wt.data_ptr(), _ptr(bt), _ptr(b3), w_low.data_ptr(), bias.data_ptr(), _ptr(dense),
+                                  cl, cup, c2, cout, _stream()), f.up_pack)
+    return (w_skip, w_low, bias, dense) if want_dense else (w_skip, w_low, bias)
+
+
+def _conv3x3_up_planar(fmt: int, x_low, x_skip, w_skip_packed, w_low_packed, bias, cout, relu, range_flag):
+    f = _PLANAR[fmt]
+    lib = _lib.load()
+    assert isinstance(x_low, f.cls) and isinstance(x_skip, f.cls), f"{f.up} reads planar {f.letter} tensors (ops.Planar{f.letter})"
+    _dev_check(x_low.data, x_skip.data, w_skip_packed, w_low_packed, bias)
+    n, h, w, c2, cl = x_skip.n, x_skip.h, x_skip.w, x_skip.c, x_low.c
+    assert (x_low.n, 2 * x_low.h, 2 * x_low.w) == (n, h, w), "x_low must have half the skip tensor's height and width"
+    assert w_skip_packed.numel() == int(getattr(lib, f.packed_bytes)(c2, cout)), f"w_skip_packed is not {f.packer} of (c2, cout)"
+    assert w_low_packed.numel() == int(getattr(lib, f.up_packed_bytes)(cl, cout)), f"w_low_packed is not {f.up_packer} of (cl, cout)"
+    assert bias is not None and bias.numel() == cout
+    y = f.cls.empty(n, cout, h, w, x_skip.device)
+    cup = cl // 2
+    act = n * h * w * (c2 + cout) + n * (h // 2) * (w // 2) * cl
+    (an, ad), (wn, wd) = f.act_bytes, f.weight_bytes
+    # algorithmic work = the two reference ops it replaces: ConvTranspose2d (2 * 4 * cl * cup MACs per low pixel) + the 3x3 conv over cup + c2 channels
+    meta = {"flops": 2.0 * 9 * (cup + c2) * cout * n * h * w + 2.0 * 4 * cl * cup * n * (h // 2) * (w // 2),
+            "flops_executed": 2.0 * (9 * c2 + 4 * cl) * cout * n * h * w,
+            "bytes": float(act * an / ad + (9 * c2 + 16 * cl) * cout * wn / wd), "bytes_2B": float(act * 2 + (9 * (cup + c2) * cout + 4 * cl * cup) * 2),
+            "tiles": n * ((h + 15) // 16) * ((w + 31) // 32) * (cout // 64), "steps_per_tile": c2 // 16 + 2 * (cl // 16)}
+    check(_launch(f.up, meta, lambda: getattr(lib, f.up_fwd)(
+        x_low.data_ptr(), x_skip.data_ptr(), w_skip_packed.data_ptr(), w_low_packed.data_ptr(), bias.data_ptr(), y.data_ptr(),
+        n, h, w, cl, c2, cout, int(relu), _ptr(range_flag), _stream())), f.up_fwd)
+    return y
 
 
 def conv3x3_q(x1: PlanarQ, x2: Optional[PlanarQ], w_packed_f4: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
@@ -335,34 +439,7 @@ def conv3x3_q(x1: PlanarQ, x2: Optional[PlanarQ], w_packed_f4: torch.Tensor, bia
     (wsu_conv3x3_q_fwd, csrc/conv3x3_q.hip; the default inference mode 'f16f4p').  x1 / x2: PlanarQ; w_packed_f4 from pack_conv3x3_f4;
     y / y_pool: PlanarQ (y_format=PLANAR_Q) or e4m3-residual planar tensors (PLANAR_A: what convt2x2_pl reads; always for a y beside the head).
     Returns y [, y_pool] or, with head_w, out [, logit][, y]."""
-    lib = _lib.load()
-    hw2 = None if head_w is None else head_w.detach().reshape(head_w.shape[0], -1).contiguous()
-    assert isinstance(x1, PlanarQ) and (x2 is None or isinstance(x2, PlanarQ)), "conv3x3_q reads planar Q tensors (ops.PlanarQ)"
-    _dev_check(x1.data, None if x2 is None else x2.data, w_packed_f4, bias, hw2, head_b)
-    n, h, w, c1 = x1.n, x1.h, x1.w, x1.c
-    c2 = 0
-    if x2 is not None:
-        assert (x2.n, x2.h, x2.w) == (n, h, w)
-        c2 = x2.c
-    assert w_packed_f4.numel() * w_packed_f4.element_size() == int(lib.wsu_conv3x3_packed_f4_bytes(c1 + c2, cout)), "w_packed_f4 is not pack_conv3x3_f4 of (cin, cout)"
-    hc = 0 if hw2 is None else hw2.shape[0]
-    yf = PLANAR_A if hc else y_format
-    y = _planar_out(yf, n, cout, h, w, x1.device) if want_y else None
-    yp = _planar_out(yf, n, cout, h // 2, w // 2, x1.device) if pool else None
-    out = torch.empty((n, hc, h, w), dtype=torch.float32, device=x1.device) if hc else None
-    logit = torch.empty_like(out) if (hc and want_logit) else None
-    act = n * h * w * ((c1 + c2) + (cout if want_y else 0)) + (n * (h // 2) * (w // 2) * cout if pool else 0)     # planar elements read + written
-    meta = {"flops": 2.0 * 9 * (c1 + c2) * cout * n * h * w,
-            "bytes": float(act * 49 / 16 + n * h * w * hc * 4 + 9 * (c1 + c2) * cout * 28 / 9),
-            "bytes_2B": float(act * 2 + n * h * w * hc * 4 + 9 * (c1 + c2) * cout * 2),
-            "tiles": n * ((h + 15) // 16) * ((w + 31) // 32) * (cout // 64), "steps_per_tile": (c1 + c2) // 16}
-    check(_launch("conv3x3_q", meta, lambda: lib.wsu_conv3x3_q_fwd(
-        x1.data_ptr(), _ptr(x2), w_packed_f4.data_ptr(), _ptr(bias), _ptr(y), _ptr(yp), _ptr(hw2), _ptr(head_b), _ptr(out), _ptr(logit), hc,
-        n, h, w, c1, c2, cout, int(relu), yf, _ptr(range_flag), _stream())), "wsu_conv3x3_q_fwd")
-    if hc:
-        res = [out] + ([logit] if want_logit else []) + ([y] if want_y else [])
-        return res[0] if len(res) == 1 else tuple(res)
-    return (y, yp) if pool else y
+    return _conv3x3_planar(PLANAR_Q, x1, x2, w_packed_f4, bias, cout, relu, pool, want_y, head_w, head_b, want_logit, range_flag, y_format)
 
 
 def conv3x3_q_fused_first(x_nchw: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w_packed_f4: torch.Tensor,
@@ -397,25 +474,7 @@ def pack_conv3x3_up(w3: torch.Tensor, wt: torch.Tensor, bt: Optional[torch.Tenso
     fp32, the nn.ConvTranspose2d weights; bt / b3: their biases.  Returns (w_skip_packed, w_low_packed, bias[, wc_dense]): the skip half packed
     like any conv3x3_q weight, the upsampled half as parity-class 2x2-tap weights combined in fp32 on the device, the combined bias, and on
     request the combined weights (Cout, Cl, 2, 2, 2, 2) [py][px][dy][dx]."""
-    lib = _lib.load()
-    w3, wt = w3.detach().contiguous(), wt.detach().contiguous()
-    bt = None if bt is None else bt.detach().contiguous()
-    b3 = None if b3 is None else b3.detach().contiguous()
-    _dev_check(w3, wt, bt, b3)
-    assert w3.dtype == torch.float32 and w3.dim() == 4 and w3.shape[2:] == (3, 3) and wt.dtype == torch.float32 and wt.dim() == 4 and wt.shape[2:] == (2, 2)
-    cout, ctot = w3.shape[:2]
-    cl, cup = wt.shape[:2]
-    c2 = ctot - cup
-    nbytes = lib.wsu_conv3x3_up_packed_bytes(cl, cout)
-    if nbytes == 0 or c2 <= 0 or c2 % 16:
-        raise _lib.WsuError(f"fused upsample packing needs cl % 16 == 0, c2 % 16 == 0 (> 0) and cout % 64 == 0 (got cl={cl}, cup={cup}, c2={c2}, cout={cout})")
-    w_skip = pack_conv3x3_f4(w3[:, cup:].contiguous())
-    w_low = torch.empty(nbytes, dtype=torch.uint8, device=w3.device)
-    bias = torch.empty(cout, dtype=torch.float32, device=w3.device)
-    dense = torch.empty((cout, cl, 2, 2, 2, 2), dtype=torch.float32, device=w3.device) if want_dense else None
-    check(lib.wsu_conv3x3_up_pack(w3.data_ptr(), wt.data_ptr(), _ptr(bt), _ptr(b3), w_low.data_ptr(), bias.data_ptr(), _ptr(dense),
-                                  cl, cup, c2, cout, _stream()), "wsu_conv3x3_up_pack")
-    return (w_skip, w_low, bias, dense) if want_dense else (w_skip, w_low, bias)
+    return _pack_conv3x3_up_planar(PLANAR_Q, w3, wt, bt, b3, want_dense)
 
 
 def conv3x3_up_q(x_low: PlanarQ, x_skip: PlanarQ, w_skip_packed: torch.Tensor, w_low_packed: torch.Tensor, bias: torch.Tensor, cout: int,
@@ -424,26 +483,7 @@ def conv3x3_up_q(x_low: PlanarQ, x_skip: PlanarQ, w_skip_packed: torch.Tensor, w
     arithmetic of the default inference mode (wsu_conv3x3_up_q_fwd, csrc/conv3x3_qu.hip): the upsampled half runs as a 2x2-tap conv on x_low with
     weights combined per output-pixel parity class -- the upsampled tensor never exists.  x_low: PlanarQ at (h/2, w/2); x_skip: PlanarQ at (h, w);
     weights from pack_conv3x3_up.  Returns y: PlanarQ."""
-    lib = _lib.load()
-    assert isinstance(x_low, PlanarQ) and isinstance(x_skip, PlanarQ), "conv3x3_up_q reads planar Q tensors (ops.PlanarQ)"
-    _dev_check(x_low.data, x_skip.data, w_skip_packed, w_low_packed, bias)
-    n, h, w, c2, cl = x_skip.n, x_skip.h, x_skip.w, x_skip.c, x_low.c
-    assert (x_low.n, 2 * x_low.h, 2 * x_low.w) == (n, h, w), "x_low must have half the skip tensor's height and width"
-    assert w_skip_packed.numel() == int(lib.wsu_conv3x3_packed_f4_bytes(c2, cout)), "w_skip_packed is not pack_conv3x3_f4 of (c2, cout)"
-    assert w_low_packed.numel() == int(lib.wsu_conv3x3_up_packed_bytes(cl, cout)), "w_low_packed is not pack_conv3x3_up of (cl, cout)"
-    assert bias is not None and bias.numel() == cout
-    y = PlanarQ.empty(n, cout, h, w, x_skip.device)
-    cup = cl // 2
-    act = n * h * w * (c2 + cout) + n * (h // 2) * (w // 2) * cl
-    # algorithmic work = the two reference ops it replaces: ConvTranspose2d (2 * 4 * cl * cup MACs per low pixel) + the 3x3 conv over cup + c2 channels
-    meta = {"flops": 2.0 * 9 * (cup + c2) * cout * n * h * w + 2.0 * 4 * cl * cup * n * (h // 2) * (w // 2),
-            "flops_executed": 2.0 * (9 * c2 + 4 * cl) * cout * n * h * w,
-            "bytes": float(act * 49 / 16 + (9 * c2 + 16 * cl) * cout * 28 / 9), "bytes_2B": float(act * 2 + (9 * (cup + c2) * cout + 4 * cl * cup) * 2),
-            "tiles": n * ((h + 15) // 16) * ((w + 31) // 32) * (cout // 64), "steps_per_tile": c2 // 16 + 2 * (cl // 16)}
-    check(_launch("conv3x3_up_q", meta, lambda: lib.wsu_conv3x3_up_q_fwd(
-        x_low.data_ptr(), x_skip.data_ptr(), w_skip_packed.data_ptr(), w_low_packed.data_ptr(), bias.data_ptr(), y.data_ptr(),
-        n, h, w, cl, c2, cout, int(relu), _ptr(range_flag), _stream())), "wsu_conv3x3_up_q_fwd")
-    return y
+    return _conv3x3_up_planar(PLANAR_Q, x_low, x_skip, w_skip_packed, w_low_packed, bias, cout, relu, range_flag)
 
 
 # ---- mode 'f16p': one product per tap, f16(w) * f16(x), on planar H tensors (include/wsu.h K1h) -------------------------------------------
@@ -451,17 +491,7 @@ def conv3x3_up_q(x_low: PlanarQ, x_skip: PlanarQ, w_skip_packed: torch.Tensor, w
 def pack_conv3x3_h(w: torch.Tensor) -> torch.Tensor:
     """w: (Cout, Cin, 3, 3) fp32 OIHW on the device -> the packed weights of conv3x3_h: two f16 planes per tap, round to nearest even
     (wsu_conv3x3_pack_h)."""
-    lib = _lib.load()
-    w = w.detach().contiguous()
-    _dev_check(w)
-    assert w.dtype == torch.float32 and w.dim() == 4 and w.shape[2:] == (3, 3)
-    cout, cin = w.shape[:2]
-    nbytes = lib.wsu_conv3x3_packed_h_bytes(cin, cout)
-    if nbytes == 0:
-        raise _lib.WsuError(f"f16 packing needs cin % 16 == 0 and cout % 64 == 0 (got {cin}, {cout})")
-    out = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    check(lib.wsu_conv3x3_pack_h(w.data_ptr(), out.data_ptr(), cin, cout, _stream()), "wsu_conv3x3_pack_h")
-    return out
+    return _pack_conv3x3_planar(PLANAR_H, w)
 
 
 def conv3x3_h(x1: PlanarH, x2: Optional[PlanarH], w_packed_h: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
@@ -471,57 +501,13 @@ def conv3x3_h(x1: PlanarH, x2: Optional[PlanarH], w_packed_h: torch.Tensor, bias
     """3x3 reflect conv (+ReLU, +2x2 max-pool, +1x1 head and sigmoid) in the one-product arithmetic of mode 'f16p' on planar H activations
     (wsu_conv3x3_h_fwd: the conv3x3_q kernel instantiated for format H).  x1 / x2: PlanarH; w_packed_h from pack_conv3x3_h; y / y_pool (and a y
     beside the head): PlanarH.  Returns y [, y_pool] or, with head_w, out [, logit][, y]."""
-    lib = _lib.load()
-    hw2 = None if head_w is None else head_w.detach().reshape(head_w.shape[0], -1).contiguous()
-    assert isinstance(x1, PlanarH) and (x2 is None or isinstance(x2, PlanarH)), "conv3x3_h reads planar H tensors (ops.PlanarH)"
-    _dev_check(x1.data, None if x2 is None else x2.data, w_packed_h, bias, hw2, head_b)
-    n, h, w, c1 = x1.n, x1.h, x1.w, x1.c
-    c2 = 0
-    if x2 is not None:
-        assert (x2.n, x2.h, x2.w) == (n, h, w)
-        c2 = x2.c
-    assert w_packed_h.numel() * w_packed_h.element_size() == int(lib.wsu_conv3x3_packed_h_bytes(c1 + c2, cout)), "w_packed_h is not pack_conv3x3_h of (cin, cout)"
-    hc = 0 if hw2 is None else hw2.shape[0]
-    y = PlanarH.empty(n, cout, h, w, x1.device) if want_y else None
-    yp = PlanarH.empty(n, cout, h // 2, w // 2, x1.device) if pool else None
-    out = torch.empty((n, hc, h, w), dtype=torch.float32, device=x1.device) if hc else None
-    logit = torch.empty_like(out) if (hc and want_logit) else None
-    act = n * h * w * ((c1 + c2) + (cout if want_y else 0)) + (n * (h // 2) * (w // 2) * cout if pool else 0)     # planar elements read + written
-    meta = {"flops": 2.0 * 9 * (c1 + c2) * cout * n * h * w,
-            "bytes": float(act * 2 + n * h * w * hc * 4 + 9 * (c1 + c2) * cout * 2),
-            "bytes_2B": float(act * 2 + n * h * w * hc * 4 + 9 * (c1 + c2) * cout * 2),
-            "tiles": n * ((h + 15) // 16) * ((w + 31) // 32) * (cout // 64), "steps_per_tile": (c1 + c2) // 16}
-    check(_launch("conv3x3_h", meta, lambda: lib.wsu_conv3x3_h_fwd(
-        x1.data_ptr(), _ptr(x2), w_packed_h.data_ptr(), _ptr(bias), _ptr(y), _ptr(yp), _ptr(hw2), _ptr(head_b), _ptr(out), _ptr(logit), hc,
-        n, h, w, c1, c2, cout, int(relu), PLANAR_H, _ptr(range_flag), _stream())), "wsu_conv3x3_h_fwd")
-    if hc:
-        res = [out] + ([logit] if want_logit else []) + ([y] if want_y else [])
-        return res[0] if len(res) == 1 else tuple(res)
-    return (y, yp) if pool else y
+    return _conv3x3_planar(PLANAR_H, x1, x2, w_packed_h, bias, cout, relu, pool, want_y, head_w, head_b, want_logit, range_flag, PLANAR_H)
 
 
 def pack_conv3x3_up_h(w3: torch.Tensor, wt: torch.Tensor, bt: Optional[torch.Tensor], b3: Optional[torch.Tensor], want_dense: bool = False):
     """Weights of conv3x3_up_h (wsu_conv3x3_up_pack_h): as pack_conv3x3_up, the skip half packed by pack_conv3x3_h and the parity-class weights
     combined in fp32 on the device and rounded to f16 once.  Returns (w_skip_packed, w_low_packed, bias[, wc_dense])."""
-    lib = _lib.load()
-    w3, wt = w3.detach().contiguous(), wt.detach().contiguous()
-    bt = None if bt is None else bt.detach().contiguous()
-    b3 = None if b3 is None else b3.detach().contiguous()
-    _dev_check(w3, wt, bt, b3)
-    assert w3.dtype == torch.float32 and w3.dim() == 4 and w3.shape[2:] == (3, 3) and wt.dtype == torch.float32 and wt.dim() == 4 and wt.shape[2:] == (2, 2)
-    cout, ctot = w3.shape[:2]
-    cl, cup = wt.shape[:2]
-    c2 = ctot - cup
-    nbytes = lib.wsu_conv3x3_up_packed_h_bytes(cl, cout)
-    if nbytes == 0 or c2 <= 0 or c2 % 16:
-        raise _lib.WsuError(f"fused upsample packing needs cl % 16 == 0, c2 % 16 == 0 (> 0) and cout % 64 == 0 (got cl={cl}, cup={cup}, c2={c2}, cout={cout})")
-    w_skip = pack_conv3x3_h(w3[:, cup:].contiguous())
-    w_low = torch.empty(nbytes, dtype=torch.uint8, device=w3.device)
-    bias = torch.empty(cout, dtype=torch.float32, device=w3.device)
-    dense = torch.empty((cout, cl, 2, 2, 2, 2), dtype=torch.float32, device=w3.device) if want_dense else None
-    check(lib.wsu_conv3x3_up_pack_h(w3.data_ptr(), wt.data_ptr(), _ptr(bt), _ptr(b3), w_low.data_ptr(), bias.data_ptr(), _ptr(dense),
-                                    cl, cup, c2, cout, _stream()), "wsu_conv3x3_up_pack_h")
-    return (w_skip, w_low, bias, dense) if want_dense else (w_skip, w_low, bias)
+    return _pack_conv3x3_up_planar(PLANAR_H, w3, wt, bt, b3, want_dense)
 
 
 def conv3x3_up_h(x_low: PlanarH, x_skip: PlanarH, w_skip_packed: torch.Tensor, w_low_packed: torch.Tensor, bias: torch.Tensor, cout: int,
@@ -529,26 +515,7 @@ def conv3x3_up_h(x_low: PlanarH, x_skip: PlanarH, w_skip_packed: torch.Tensor, w
     """conv3x3_up_q in the one-product arithmetic of mode 'f16p' on planar H tensors (wsu_conv3x3_up_h_fwd): relu(conv3x3_reflect(cat[
     conv_transpose2x2_s2(x_low), x_skip])) in one launch.  x_low: PlanarH at (h/2, w/2); x_skip: PlanarH at (h, w); weights from
     pack_conv3x3_up_h.  Returns y: PlanarH."""
-    lib = _lib.load()
-    assert isinstance(x_low, PlanarH) and isinstance(x_skip, PlanarH), "conv3x3_up_h reads planar H tensors (ops.PlanarH)"
-    _dev_check(x_low.data, x_skip.data, w_skip_packed, w_low_packed, bias)
-    n, h, w, c2, cl = x_skip.n, x_skip.h, x_skip.w, x_skip.c, x_low.c
-    assert (x_low.n, 2 * x_low.h, 2 * x_low.w) == (n, h, w), "x_low must have half the skip tensor's height and width"
-    assert w_skip_packed.numel() == int(lib.wsu_conv3x3_packed_h_bytes(c2, cout)), "w_skip_packed is not pack_conv3x3_h of (c2, cout)"
-    assert w_low_packed.numel() == int(lib.wsu_conv3x3_up_packed_h_bytes(cl, cout)), "w_low_packed is not pack_conv3x3_up_h of (cl, cout)"
-    assert bias is not None and bias.numel() == cout
-    y = PlanarH.empty(n, cout, h, w, x_skip.device)
-    cup = cl // 2
-    act = n * h * w * (c2 + cout) + n * (h // 2) * (w // 2) * cl
-    # algorithmic work = the two reference ops it replaces (as conv3x3_up_q); bytes at 2 B per element and weight
-    meta = {"flops": 2.0 * 9 * (cup + c2) * cout * n * h * w + 2.0 * 4 * cl * cup * n * (h // 2) * (w // 2),
-            "flops_executed": 2.0 * (9 * c2 + 4 * cl) * cout * n * h * w,
-            "bytes": float(act * 2 + (9 * c2 + 16 * cl) * cout * 2), "bytes_2B": float(act * 2 + (9 * (cup + c2) * cout + 4 * cl * cup) * 2),
-            "tiles": n * ((h + 15) // 16) * ((w + 31) // 32) * (cout // 64), "steps_per_tile": c2 // 16 + 2 * (cl // 16)}
-    check(_launch("conv3x3_up_h", meta, lambda: lib.wsu_conv3x3_up_h_fwd(
-        x_low.data_ptr(), x_skip.data_ptr(), w_skip_packed.data_ptr(), w_low_packed.data_ptr(), bias.data_ptr(), y.data_ptr(),
-        n, h, w, cl, c2, cout, int(relu), _ptr(range_flag), _stream())), "wsu_conv3x3_up_h_fwd")
-    return y
+    return _conv3x3_up_planar(PLANAR_H, x_low, x_skip, w_skip_packed, w_low_packed, bias, cout, relu, range_flag)
 
 
 def conv3x3_pl(x1: torch.Tensor, x2: Optional[torch.Tensor], w_packed: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
