@@ -178,8 +178,9 @@ def l1ws_loss(outputs, covers, alphas, inputs, use_l1=True, use_ws=True):
     return float(loss), grad
 
 
-def adamw_step(p, g, m, v, step, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2):
-    """One torch.optim.AdamW update (decoupled weight decay), float64 math on float32 state."""
+def adamw_step(p, g, m, v, step, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2, out_dtype=np.float32):
+    """One torch.optim.AdamW update (decoupled weight decay), float64 math on float32 state.
+    ``out_dtype=np.float64`` keeps the unrounded results (tests/train_np.py compares kernels with those)."""
     p = p.astype(np.float64) * (1.0 - lr * wd)
     m = b1 * m.astype(np.float64) + (1 - b1) * g
     v = b2 * v.astype(np.float64) + (1 - b2) * g.astype(np.float64) ** 2
@@ -187,4 +188,4 @@ def adamw_step(p, g, m, v, step, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2):
     bc2 = 1 - b2 ** step
     denom = np.sqrt(v) / np.sqrt(bc2) + eps
     p = p - (lr / bc1) * m / denom
-    return p.astype(np.float32), m.astype(np.float32), v.astype(np.float32)
+    return p.astype(out_dtype), m.astype(out_dtype), v.astype(out_dtype)

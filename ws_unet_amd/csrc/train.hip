@@ -129,14 +129,18 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
     if ((threadIdx.x & 63) == 0) atomicMax(out_bits, __builtin_bit_cast(unsigned, m));     // non-negative floats order like their bits
 }
 
-// scale = 2^floor(2 - log2(max |x|)): max |x| * scale in (2, 4] -- 2^14 of headroom below f16's largest value for gradients that grow on the
-// way down the network, while values 2^-27 of that maximum still keep an absolute error below theirs (autograd.py)
+// scale = 2^(2 - k) for max |x| in (2^(k-1), 2^k], the exact 2^floor(2 - log2(max |x|)): max |x| * scale in (2, 4] -- 2^14 of headroom below f16's
+// largest value for gradients that grow on the way down the network, while values 2^-27 of that maximum still keep an absolute error below theirs
+// (autograd.py).  k comes from the float's own exponent: log2f rounds a maximum one ulp above a power of two to that power (and 2 - log2f rounds
+// again), which doubled the scale there and put max |x| * scale at 4 (1 + 2^-23) (profiles/r17/train_step_kernels.md).
 __global__ void pow2_scale_kernel(const unsigned* __restrict__ bits, float* __restrict__ scale2) {
     float m = __builtin_bit_cast(float, bits[0]);
     if (!(m >= 1e-30f)) m = 1e-30f;                                  // zero gradient (or NaN: the finite guard deals with that)
     if (m > 1e30f) m = 1e30f;
-    const float s = exp2f(floorf(2.0f - log2f(m)));
-    scale2[0] = s; scale2[1] = 1.0f / s;
+    int e;
+    const float f = frexpf(m, &e);                                   // m = f * 2^e, f in [0.5, 1)
+    const int k = f == 0.5f ? e - 1 : e;
+    scale2[0] = ldexpf(1.0f, 2 - k); scale2[1] = ldexpf(1.0f, k - 2);
 }
 
 __global__ __launch_bounds__(256) void scale_kernel(const float* __restrict__ x, float* __restrict__ y, long long n, const float* __restrict__ factor) {
