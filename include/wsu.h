@@ -508,6 +508,21 @@ int wsu_ws_meter_beta(const float* x01, const float* y01, double* beta_hat, int 
 /* ---- u8 -> [0,1] fp32, numpy float32 division semantics of evaluate.py:45 (x / 255.) */
 int wsu_u8_to_unit_f32(const uint8_t* x, float* y, size_t count, void* stream);
 
+/* ---- one training batch in one launch (data/pairs.py): gather + dihedral transform + u8 -> [0,1] fp32, inputs and targets together:
+ *        inputs[s] = D(op[s])(planes[idx_in[s]]) / 255.0f        covers[s] = D(op[s])(planes[idx_cov[s]]) / 255.0f
+ * planes: DEVICE (files,H,W) uint8; idx_in, idx_cov (int32) and op (uint8): DEVICE arrays of n entries; inputs, covers: DEVICE (n,1,H,W)
+ * fp32.  The division is that of wsu_u8_to_unit_f32, so op = 0 gives the bits of that kernel followed by a gather.
+ * op holds the eight elements of D4 as three bits, applied in this order: bit 0 mirrors the columns (x[:, ::-1]), bit 1 mirrors the rows
+ * (x[::-1, :]), bit 2 transposes last.  Output pixel (i, j) reads source (r, c):
+ *        (r, c) = (j, i) if bit 2 else (i, j);   r = H-1-r if bit 1;   c = W-1-c if bit 0
+ *        op   0         1          2          3           4       5            6            7
+ *             identity  x[:,::-1]  x[::-1,:]  rot90(x,2)  x.T     rot90(x,1)   rot90(x,3)   x[::-1,::-1].T      (numpy)
+ * allow_transpose: 1 admits ops 4-7 and then requires H == W ("transposing ops need square planes"); 0 admits ops 0-3 on any H, W.
+ * A sample whose index is outside [0, files) or whose op is not admitted writes NOTHING (the Python wrapper validates before the launch).
+ * Any H, W >= 1; loads are 4 and stores 16 bytes wide when W % 4 == 0 and the pointers are aligned.  n == 0 is a no-op. */
+int wsu_pair_batch_f32(const uint8_t* planes, int files, int h, int w, const int32_t* idx_in, const int32_t* idx_cov, const uint8_t* op,
+                       int n, int allow_transpose, float* inputs, float* covers, void* stream);
+
 /* ======================= backward / train step (K7, K8, K9) =======================
  * The reference publishes no UNet training script; these entry points are the autograd of
  * UNet.forward (unet.py:137-189) + the loss classes (src/_defs/losses.py:28-121) + torch.optim.AdamW as used

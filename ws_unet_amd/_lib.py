@@ -115,6 +115,7 @@ SIGNATURES = {
     "wsu_embed_lsbr": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_u8_to_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
+    "wsu_pair_batch_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P]),
     # ---- backward / train step
     "wsu_conv3x3_bwd_data_workspace_bytes": (c_size_t, [c_int] * 6),
     "wsu_conv3x3_bwd_data": (c_int, [_P, _P, _P, _P, c_size_t, _P, _P, c_int, _P, _P] + [c_int] * 6 + [_P]),

@@ -14,8 +14,18 @@ stego sample is made on the device from the uploaded cover plane (ws_unet_amd.em
 order, alphas and the rank slices are those of the file route; 'HILLR' twins equal the files `embed.write_dataset` writes, 'LSBR'
 twins are drawn afresh every epoch (`lsbr_stream()`), the same on every rank for the same file.
 
+Three seeded draws per epoch, each over ALL pairs and indexed by pair id, so that every rank sees the same value for the same pair:
+  * `default_rng([seed, epoch])`     the order of the pairs (`pair_order()`);
+  * `default_rng([seed, epoch, 1])`  `post_flip` / `post_rotate` (the published configs' keys; data/__init__.py restates the reference's
+    per-image transform): a horizontal flip, a vertical flip and a `rot90` count per pair -> one D4 code (`aug_ops()`, FLIP_ROT_OP).  The
+    two samples and both targets of a pair share it -- the target stays aligned with its input; a simulated twin is made from the
+    unrotated cover and transformed with it;
+  * `default_rng([seed, epoch, 2])`  the payload, when `stego_method` and / or `alpha` is a list (`payload_plan()`): one
+    (method, alpha) of the row-major (methods x alphas) combinations per pair; `alphas` of the batch is the drawn payload.
+
 MI355X-side: files are decoded by libwsu_io on C++ threads into pinned buffers one batch ahead of the consumer, uploaded as
-uint8 and scaled on the device (wsu_u8_to_unit_f32) -- 1 byte per pixel over PCIe instead of 4.  Data-parallel ranks take
+uint8 and assembled on the device by ONE kernel (wsu_pair_batch_f32: gather + D4 transform + x / 255, inputs and targets together)
+-- 1 byte per pixel over PCIe instead of 4.  Data-parallel ranks take
 disjoint, equally sized slices of every epoch (rank r gets pairs r, r+world, ...; the ragged tail is dropped so that all ranks
 run the same number of steps and the per-step all-reduce never waits for a missing partner).
 """
@@ -43,11 +53,49 @@ def _cover_rows(df, **kw):
     return df
 
 
+def apply_op(x: np.ndarray, op: int) -> np.ndarray:
+    """The D4 element `op` on the last two axes (the codes of wsu_pair_batch_f32): bit 0 mirrors the columns, bit 1 the rows, bit 2
+    transposes last."""
+    op = int(op)
+    if not 0 <= op <= 7:
+        raise ValueError(f"op {op} outside 0..7")
+    if op & 1:
+        x = x[..., :, ::-1]
+    if op & 2:
+        x = x[..., ::-1, :]
+    if op & 4:
+        x = np.swapaxes(x, -1, -2)
+    return x
+
+
+def _flip_rot_table() -> np.ndarray:
+    ramp = np.arange(16).reshape(4, 4)
+    images = [apply_op(ramp, o) for o in range(8)]
+    table = []
+    for k in range(4):
+        for vflip in (0, 1):
+            for hflip in (0, 1):
+                y = ramp[:, ::-1] if hflip else ramp
+                y = np.rot90(y[::-1] if vflip else y, k)
+                table.append(next(o for o in range(8) if np.array_equal(images[o], y)))
+    return np.array(table, dtype=np.uint8)
+
+
+# op code of "horizontal flip, vertical flip, then np.rot90(., k)" at index hflip + 2 * vflip + 4 * k, found by comparing numpy's results
+FLIP_ROT_OP = _flip_rot_table()
+
+
+def _as_list(v) -> list:
+    return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v]
+
+
 class PairLoader:
-    def __init__(self, dataset: typing.Union[str, pathlib.Path], split: typing.Optional[str], stego_method: typing.Optional[str],
-                 alpha: typing.Optional[float], batch_size: int = 16, *, covers_only: bool = False, shuffle: bool = True,
+    def __init__(self, dataset: typing.Union[str, pathlib.Path], split: typing.Optional[str],
+                 stego_method: typing.Union[str, typing.Sequence[str], None], alpha: typing.Union[float, typing.Sequence[float], None],
+                 batch_size: int = 16, *, covers_only: bool = False, shuffle: bool = True,
                  seed: int = 0, rank: int = 0, world: int = 1, device: typing.Optional[torch.device] = None,
-                 take_num_images: typing.Optional[int] = None, threads: typing.Optional[int] = None, simulate: bool = False):
+                 take_num_images: typing.Optional[int] = None, threads: typing.Optional[int] = None, simulate: bool = False,
+                 post_flip: bool = False, post_rotate: bool = False):
         per_pair = 1 if covers_only else 2
         if batch_size % per_pair:
             raise ValueError("batch_size must be even: every pair contributes a cover and a stego sample")
@@ -55,8 +103,19 @@ class PairLoader:
         if simulate and device is None:
             raise ValueError("simulate=True makes the stego samples on the device: it needs `device` (host-logic mode has no simulator)")
         self.simulate = bool(simulate) and not covers_only
+        methods, alphas = _as_list(stego_method), _as_list(alpha)
+        if not methods or not alphas:
+            raise ValueError("an empty list of stego methods or alphas")
+        self.combos = None                                              # [(method, alpha)] when a pair draws its payload (payload_plan)
+        if len(methods) * len(alphas) == 1 or covers_only:
+            stego_method, alpha = methods[0], alphas[0]                 # one combination: the scalar route
+        else:
+            self.combos = [(m, float(a)) for m in methods for a in alphas]
+        self.method = None if covers_only or self.combos is not None else stego_method
         if self.simulate:
             self._simulated_rows(split, stego_method, alpha, take_num_images)
+        elif self.combos is not None:
+            self._combo_rows(split, take_num_images)
         else:
             df = _pair_rows(self.dataset, split=split, stego_method=stego_method, alpha=alpha, take_num_images=take_num_images)
             if not covers_only:
@@ -69,21 +128,46 @@ class PairLoader:
         self.batch_size, self.per_pair, self.covers_only = batch_size, per_pair, covers_only
         self.shuffle, self.seed, self.epoch = shuffle, seed, 0
         self.rank, self.world, self.device, self.threads = rank, world, device, threads
+        self.post_flip, self.post_rotate = bool(post_flip), bool(post_rotate)
         self._pinned = {}
         self._uploaded = {}                                             # slot -> event recorded behind its last upload
 
     def _simulated_rows(self, split, stego_method, alpha, take_num_images) -> None:
         from .. import embed
-        if stego_method is None or alpha is None:
-            raise ValueError("simulate=True needs a stego_method and an alpha")
-        self.sim_method, self.sim_alpha = embed.method_name(stego_method), float(alpha)
-        if not 0.0 <= self.sim_alpha <= 1.0:
-            raise ValueError(f"alpha={alpha!r} outside [0, 1]")
+        if self.combos is not None:
+            self.combos = [(embed.method_name(m), a) for m, a in self.combos]
+            bad = [a for _, a in self.combos if not 0.0 <= a <= 1.0]
+            if bad:
+                raise ValueError(f"alpha={bad[0]!r} outside [0, 1]")
+            self.sim_method = self.sim_alpha = None
+        else:
+            if stego_method is None or alpha is None:
+                raise ValueError("simulate=True needs a stego_method and an alpha")
+            self.sim_method, self.sim_alpha = embed.method_name(stego_method), float(alpha)
+            if not 0.0 <= self.sim_alpha <= 1.0:
+                raise ValueError(f"alpha={alpha!r} outside [0, 1]")
+            self.method = self.sim_method
         df = _cover_rows(self.dataset, split=split, take_num_images=take_num_images)
         names = [pathlib.Path(n).relative_to(self.dataset).as_posix() for n in df["name"]]
         self.covers = sorted(names, key=lambda f: (pathlib.Path(f).stem, f))        # cover_stego_spatial's row order
         self.stegos = []
-        self.alphas = [self.sim_alpha] * len(self.covers)
+        self.alphas = None if self.combos is not None else [self.sim_alpha] * len(self.covers)
+
+    def _combo_rows(self, split, take_num_images) -> None:
+        """File route with several (method, alpha): one query per combination, joined on the cover's name; a cover that lacks the twin
+        of any combination is dropped.  twins[k][p] = pair p's stego file under combination k."""
+        found, order = [], None
+        for m, a in self.combos:
+            df = _pair_rows(self.dataset, split=split, stego_method=m, alpha=a, take_num_images=take_num_images)
+            df = df[~df["name_s"].isna()]
+            found.append({str(c): str(s) for c, s in zip(df["name_c"], df["name_s"])})
+            if order is None:
+                order = [str(c) for c in df["name_c"]]
+        self.covers = [c for c in order if all(c in f for f in found)]
+        if not self.covers:
+            raise ValueError(f"no cover has a stego twin for every one of {self.combos} under {self.dataset}")
+        self.twins = [[f[c] for c in self.covers] for f in found]
+        self.stegos, self.alphas = [], None
 
     def lsbr_stream(self, epoch: typing.Optional[int] = None) -> int:
         """The `embed.image_seed` stream of the simulated 'LSBR' twins in `epoch` (default: the current one): a 32-bit function of
@@ -103,6 +187,28 @@ class PairLoader:
         steps = n // (ppb * self.world)                                 # same on every rank; ragged tail dropped
         return order[:steps * ppb * self.world].reshape(steps, ppb, self.world)[:, :, self.rank]
 
+    def aug_ops(self, epoch: typing.Optional[int] = None) -> np.ndarray:
+        """The D4 code (apply_op) of every pair in `epoch` (default: the current one), indexed by pair id: "flip, then np.rot90(., k)" with
+        the three draws of the module docstring.  All zero without `post_flip` / `post_rotate`."""
+        n = len(self.covers)
+        e = self.epoch if epoch is None else int(epoch)
+        rng = np.random.default_rng([self.seed, e, 1])
+        zero = np.zeros(n, dtype=np.int64)
+        hflip = rng.integers(0, 2, n) if self.post_flip else zero
+        vflip = rng.integers(0, 2, n) if self.post_flip else zero
+        k = rng.integers(0, 4, n) if self.post_rotate else zero
+        return FLIP_ROT_OP[hflip + 2 * vflip + 4 * k]
+
+    def _combo_draw(self, epoch: typing.Optional[int] = None) -> np.ndarray:
+        e = self.epoch if epoch is None else int(epoch)
+        return np.random.default_rng([self.seed, e, 2]).integers(0, len(self.combos), len(self.covers))
+
+    def payload_plan(self, epoch: typing.Optional[int] = None) -> typing.List[typing.Tuple[typing.Optional[str], float]]:
+        """(stego method, alpha) of every pair's stego sample in `epoch` (default: the current one), indexed by pair id."""
+        if self.combos is None:
+            return [(self.method, float(a)) for a in self.alphas]
+        return [self.combos[k] for k in self._combo_draw(epoch)]
+
     def __len__(self) -> int:
         return len(self.covers) // ((self.batch_size // self.per_pair) * self.world)
 
@@ -114,66 +220,83 @@ class PairLoader:
             self._pinned[key] = torch.empty((n, h, w), dtype=torch.uint8, pin_memory=pin)
         return self._pinned[key]
 
-    def _decode(self, pairs: np.ndarray, slot: int):
-        files_in, files_cov, alphas = [], [], []
-        for p in pairs:
-            c = str(self.dataset / self.covers[p])
-            files_in.append(c); files_cov.append(c); alphas.append(0.0)
-            if not self.covers_only:
-                files_in.append(str(self.dataset / self.stegos[p])); files_cov.append(c); alphas.append(self.alphas[p])
+    def _read(self, files, slot):
+        """Decode `files` into the pinned buffer of `slot` (once the upload that last read it has finished)."""
         from ..imread import png_shape, imread4_u8
-        hw = png_shape(files_in[0]) or imread4_u8(files_in[0]).shape[:2]
-        uniq = list(dict.fromkeys(files_in))                            # every cover is decoded once
-        buf = self._buffers(len(uniq), hw[0], hw[1], slot)
-        ev = self._uploaded.get(slot)
-        if ev is not None:
-            ev.synchronize()                                            # the upload that last read this pinned buffer has finished
-        read_luma_batch(uniq, out=buf.numpy(), threads=self.threads)
-        pos = {f: i for i, f in enumerate(uniq)}
-        idx_in = torch.tensor([pos[f] for f in files_in]); idx_cov = torch.tensor([pos[f] for f in files_cov])
-        return buf, idx_in, idx_cov, torch.tensor(alphas, dtype=torch.float32), slot
-
-    def _decode_simulated(self, pairs: np.ndarray, slot: int):
-        """One decode per pair: plane i of the buffer is pair i's cover, plane len(pairs) + i will be its twin (_finish)."""
-        from .. import embed
-        from ..imread import png_shape, imread4_u8
-        files = [str(self.dataset / self.covers[p]) for p in pairs]
         hw = png_shape(files[0]) or imread4_u8(files[0]).shape[:2]
+        if self.post_rotate and hw[0] != hw[1]:
+            raise ValueError(f"post_rotate needs square images, {files[0]} is {hw[0]}x{hw[1]}")
         buf = self._buffers(len(files), hw[0], hw[1], slot)
         ev = self._uploaded.get(slot)
         if ev is not None:
             ev.synchronize()
         read_luma_batch(files, out=buf.numpy(), threads=self.threads)
+        return buf
+
+    def _decode(self, pairs: np.ndarray, slot: int, ops_all: np.ndarray, draw: typing.Optional[np.ndarray]):
+        files_in, files_cov, alphas = [], [], []
+        for p in pairs:
+            c = str(self.dataset / self.covers[p])
+            files_in.append(c); files_cov.append(c); alphas.append(0.0)
+            if not self.covers_only:
+                twin, a = (self.stegos[p], self.alphas[p]) if draw is None else (self.twins[draw[p]][p], self.combos[draw[p]][1])
+                files_in.append(str(self.dataset / twin)); files_cov.append(c); alphas.append(a)     # only the drawn twin is decoded
+        uniq = list(dict.fromkeys(files_in))                            # every cover is decoded once
+        buf = self._read(uniq, slot)
+        pos = {f: i for i, f in enumerate(uniq)}
+        return {"buf": buf, "idx_in": np.array([pos[f] for f in files_in]), "idx_cov": np.array([pos[f] for f in files_cov]),
+                "alphas": torch.tensor(alphas, dtype=torch.float32), "slot": slot, "op": np.repeat(ops_all[pairs], self.per_pair)}
+
+    def _decode_simulated(self, pairs: np.ndarray, slot: int, ops_all: np.ndarray, draw: typing.Optional[np.ndarray]):
+        """One decode per pair: plane i of the buffer is pair i's cover, plane len(pairs) + i will be its twin (_finish)."""
+        from .. import embed
+        files = [str(self.dataset / self.covers[p]) for p in pairs]
+        buf = self._read(files, slot)
         m = len(files)
-        idx_in = torch.tensor([j for i in range(m) for j in (i, m + i)]); idx_cov = torch.tensor([i for i in range(m) for _ in (0, 1)])
-        alphas = torch.tensor([a for p in pairs for a in (0.0, self.alphas[p])], dtype=torch.float32)
+        payload = [(self.sim_method, self.sim_alpha) if draw is None else self.combos[draw[p]] for p in pairs]
         stream = self.lsbr_stream()
-        seeds = [embed.image_seed(f, stream) for f in files] if self.sim_method == "LSBR" else None
-        return buf, idx_in, idx_cov, alphas, slot, seeds
+        sim = {}                                                        # method -> (planes, alphas, seeds) of its share of the batch
+        for meth in dict.fromkeys(pm for pm, _ in payload):
+            sel = [i for i in range(m) if payload[i][0] == meth]
+            sim[meth] = (sel, [payload[i][1] for i in sel], [embed.image_seed(files[i], stream) for i in sel] if meth == "LSBR" else None)
+        return {"buf": buf, "idx_in": np.array([j for i in range(m) for j in (i, m + i)]), "idx_cov": np.repeat(np.arange(m), 2),
+                "alphas": torch.tensor([a for _, pa in payload for a in (0.0, pa)], dtype=torch.float32), "slot": slot,
+                "op": np.repeat(ops_all[pairs], 2), "sim": sim}
 
     def _finish(self, staged):
-        buf, idx_in, idx_cov, alphas, slot = staged[:5]
+        buf, idx_in, idx_cov, alphas, op = (staged[k] for k in ("buf", "idx_in", "idx_cov", "alphas", "op"))
         if self.device is None:                                         # host-logic mode: uint8 planes, no GPU involved
-            return buf[idx_in].clone(), (buf[idx_cov].clone(), alphas)
+            planes = buf.numpy()
+            x = np.stack([apply_op(planes[i], o) for i, o in zip(idx_in, op)])
+            c = np.stack([apply_op(planes[i], o) for i, o in zip(idx_cov, op)])
+            return torch.from_numpy(x), (torch.from_numpy(c), alphas)
         from .. import ops
         u8 = buf.to(self.device, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()                                                     # the producer waits for it before it reuses the slot
-        self._uploaded[slot] = ev
-        if self.simulate:                                               # the twins, made from the uploaded cover planes
+        self._uploaded[staged["slot"]] = ev
+        if self.simulate:                                               # the twins, made from the uploaded (untransformed) cover planes
             from .. import embed
-            u8 = torch.cat([u8, embed.simulate(u8, self.sim_method, self.sim_alpha, staged[5])[0]])
-        unit = ops.u8_to_unit(u8)[:, None]                              # (files,1,H,W) fp32 in [0,1], numpy's x / 255.
-        return unit[idx_in.to(self.device)], (unit[idx_cov.to(self.device)], alphas.to(self.device))
+            if self.combos is None:                                     # one method, one payload: the call this route always made
+                twins = embed.simulate(u8, self.sim_method, self.sim_alpha, staged["sim"][self.sim_method][2])[0]
+            else:
+                twins = torch.empty_like(u8)
+                for meth, (sel, a, seeds) in staged["sim"].items():     # one call per method present in the batch, per-image alphas
+                    twins[sel] = embed.simulate(u8[sel], meth, a, seeds)[0]
+            u8 = torch.cat([u8, twins])
+        x, c = ops.pair_batch(u8, idx_in, idx_cov, op)                  # (n,1,H,W) fp32 in [0,1], numpy's x / 255.
+        return x, (c, alphas.to(self.device))
 
     def __iter__(self):
         plan = self.pair_order()
+        ops_all = self.aug_ops()
+        draw = None if self.combos is None else self._combo_draw()
         q: Queue = Queue(maxsize=1)
 
         def producer():
             try:
                 for k, pairs in enumerate(plan):
-                    q.put(("ok", (self._decode_simulated if self.simulate else self._decode)(pairs, k % 3)))          # 3 slots: decoded ahead, queued, in use
+                    q.put(("ok", (self._decode_simulated if self.simulate else self._decode)(pairs, k % 3, ops_all, draw)))    # 3 slots: decoded ahead, queued, in use
                 q.put(("end", None))
             except BaseException as e:                                  # surfaced in the consumer
                 q.put(("err", e))

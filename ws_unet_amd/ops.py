@@ -1293,6 +1293,42 @@ def u8_to_unit(x_u8: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def pair_batch(planes_u8: torch.Tensor, idx_in, idx_cov, op) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One training batch in one launch (wsu_pair_batch_f32): planes_u8 (files,H,W) uint8 on the device; idx_in, idx_cov, op: HOST sequences
+    or arrays, one entry per sample -> (inputs, covers), both (n,1,H,W) fp32 with inputs[s] = D(op[s])(planes[idx_in[s]]) / 255 and
+    covers[s] = D(op[s])(planes[idx_cov[s]]) / 255.  op: bit 0 mirrors the columns, bit 1 the rows, bit 2 transposes last (include/wsu.h).
+    ValueError for an index outside [0, files), an op outside 0..7 or an op >= 4 on non-square planes; the three arrays go up in one copy."""
+    lib = _lib.load()
+    _dev_check(planes_u8)
+    if planes_u8.dim() != 3 or planes_u8.dtype != torch.uint8:
+        raise ValueError("pair_batch: planes_u8 must be a (files,H,W) uint8 tensor")
+    files, h, w = planes_u8.shape
+    ii, ic, o = (np.asarray(v).reshape(-1) for v in (idx_in, idx_cov, op))
+    n = ii.shape[0]
+    if ic.shape[0] != n or o.shape[0] != n:
+        raise ValueError(f"pair_batch: {n} input indices, {ic.shape[0]} cover indices and {o.shape[0]} ops")
+    inputs = torch.empty((n, 1, h, w), dtype=torch.float32, device=planes_u8.device)
+    covers = torch.empty((n, 1, h, w), dtype=torch.float32, device=planes_u8.device)
+    if n == 0:
+        return inputs, covers
+    for name, v in (("idx_in", ii), ("idx_cov", ic)):
+        if not np.issubdtype(v.dtype, np.integer) or v.min() < 0 or v.max() >= files:
+            raise ValueError(f"pair_batch: {name} outside [0, {files})")
+    if not np.issubdtype(o.dtype, np.integer) or o.min() < 0 or o.max() > 7:
+        raise ValueError("pair_batch: op outside 0..7")
+    if h != w and o.max() >= 4:
+        raise ValueError(f"pair_batch: transposing ops (op >= 4) need square planes, got {h}x{w}")
+    host = np.empty(9 * n, dtype=np.uint8)                              # [idx_in int32 | idx_cov int32 | op uint8]
+    host[:4 * n].view(np.int32)[:] = ii
+    host[4 * n:8 * n].view(np.int32)[:] = ic
+    host[8 * n:] = o
+    args = torch.from_numpy(host).to(planes_u8.device)
+    p = args.data_ptr()
+    check(lib.wsu_pair_batch_f32(planes_u8.data_ptr(), files, h, w, p, p + 4 * n, p + 8 * n, n, int(h == w), inputs.data_ptr(),
+                                 covers.data_ptr(), _stream()), "wsu_pair_batch_f32")
+    return inputs, covers
+
+
 # ---- backward ops (fp32 storage; g = pre-activation gradient, NHWC) -------------------------------------
 
 _ws_cache = {}

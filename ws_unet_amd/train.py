@@ -32,7 +32,33 @@ DEFAULTS: typing.Dict[str, typing.Any] = {
     "patience": 10, "resume": None, "resume_dir": None, "seed": None, "stego_method": None, "tr_csv": "split_tr.csv",
     "va_csv": "split_va.csv", "take_num_images": None, "mode": None, "train_mode": None,
     "simulate_stego": False,         # make the stego samples on the device from the covers (data/pairs.py simulate=True): no stego_* folders needed
+    # the published configs' augmentation and payload keys (data/pairs.py): random flips / rot90 per training pair; a list of payloads and / or
+    # methods of which every pair draws one per epoch.  A list that is not null overrides `alpha` / `stego_method`.
+    "post_flip": False, "post_rotate": False, "alphas": None, "stego_methods": None,
 }
+# written to config.json only when set, so that the config file of every run that does not use them is what it was
+OPTIONAL_KEYS = ("simulate_stego", "post_flip", "post_rotate", "alphas", "stego_methods")
+LIST_FLAGS = {"alphas": float, "stego_methods": str}
+
+
+def run_config(args: typing.Dict[str, typing.Any]) -> typing.Dict[str, typing.Any]:
+    """The dict a run writes to its config.json: the merged arguments without the keys that are this package's own switches, and with the
+    OPTIONAL_KEYS only where they are set."""
+    return {k: v for k, v in args.items() if k not in ("mode", "train_mode", "take_num_images")
+            and (k not in OPTIONAL_KEYS or v)}
+
+
+def payload_args(args: typing.Dict[str, typing.Any]):
+    """(stego method(s), alpha(s)) for the loaders: `stego_methods` / `alphas` where given, else the scalar keys; (None, None) for covers only."""
+    for key in ("stego_methods", "alphas"):                              # a list that is not null overrides its scalar key; an empty one is a mistake
+        if args.get(key) is not None and len(args[key]) == 0:
+            raise ValueError(f"{key} is an empty list: give at least one value, or null to use the scalar key")
+    if args["covers_only"]:
+        return None, None
+    methods = list(args["stego_methods"]) if args.get("stego_methods") is not None else args["stego_method"]
+    if args.get("alphas") is not None:
+        return methods, [float(a) for a in args["alphas"]]
+    return methods, None if args["alpha"] is None else float(args["alpha"])
 
 
 def train(args: typing.Dict[str, typing.Any]) -> float:
@@ -46,10 +72,13 @@ def train(args: typing.Dict[str, typing.Any]) -> float:
         raise ValueError(f"global batch_size {args['batch_size']} is not divisible by {world} ranks")
 
     # run directory: <output_dir>/<stego_method>/<yymmddHHMMSS>-<job>-<run name>[_suffix]   (detector/train.py:146-159)
-    name = time.strftime("%y%m%d%H%M%S") + "-" + str(args["SLURM_JOB_ID"]) + "-" + create_run_name(args)
+    # (a list of payloads has no place in the name: the `alpha_...` part is left out)
+    name = time.strftime("%y%m%d%H%M%S") + "-" + str(args["SLURM_JOB_ID"]) + "-" + create_run_name(
+        {**args, "alpha": None} if args["alphas"] is not None else args)
     if args["experiment_dir_suffix"]:
         name += "_" + args["experiment_dir_suffix"]
-    method_dir = args["stego_method"] or "dropout"
+    stego, alpha = payload_args(args)
+    method_dir = (args["stego_methods"][0] if args["stego_methods"] is not None else args["stego_method"]) or "dropout"
     out_dir = pathlib.Path(args["output_dir"]) / method_dir / name
     if world > 1:                                                        # every rank must agree on the timestamped name
         box = [str(out_dir)]
@@ -70,17 +99,15 @@ def train(args: typing.Dict[str, typing.Any]) -> float:
             raise Exception(f"no checkpoint found at '{args['resume']}'")
         resume(model, resume_dir, dev)
 
-    stego = None if args["covers_only"] else args["stego_method"]
-    alpha = None if args["covers_only"] or args["alpha"] is None else float(args["alpha"])
     kw = dict(covers_only=bool(args["covers_only"]), rank=rank, world=world, device=dev, take_num_images=args["take_num_images"],
               simulate=bool(args["simulate_stego"]))
     per_rank = args["batch_size"] // world
-    tr_loader = PairLoader(args["dataset"], args["tr_csv"], stego, alpha, per_rank, shuffle=True, seed=int(args["seed"] or 0), **kw)
+    # augmentation: the training loader only (the validation loader is never reshuffled either: its payload draw is the same every epoch)
+    tr_loader = PairLoader(args["dataset"], args["tr_csv"], stego, alpha, per_rank, shuffle=True, seed=int(args["seed"] or 0),
+                           post_flip=bool(args["post_flip"]), post_rotate=bool(args["post_rotate"]), **kw)
     va_loader = PairLoader(args["dataset"], args["va_csv"], stego, alpha, per_rank, shuffle=False, **kw)
 
-    # (simulate_stego: written only when set, so that the config.json of every other run is what it was)
-    cfg = {k: v for k, v in args.items() if k not in ("mode", "train_mode", "take_num_images") and (k != "simulate_stego" or v)}
-    trainer = Trainer(model, loss=args["loss"], lr=args["learning_rate"], out_dir=out_dir, config=cfg, patience=args["patience"])
+    trainer = Trainer(model, loss=args["loss"], lr=args["learning_rate"], out_dir=out_dir, config=run_config(args), patience=args["patience"])
     best = trainer.fit(tr_loader, va_loader, args["num_epochs"])
     if rank == 0:
         print(f"[train] {out_dir}: best val loss {best:.6f} after {len({e for e, _, _ in trainer.scalars})} epochs")
@@ -92,7 +119,9 @@ def main(argv=None) -> None:
     ap.add_argument("--config", help="a published run's config.json; explicit flags override its keys")
     for key, val in DEFAULTS.items():
         flag = "--" + key
-        if isinstance(val, bool):
+        if key in LIST_FLAGS:
+            ap.add_argument(flag, type=LIST_FLAGS[key], nargs="+", default=None)
+        elif isinstance(val, bool):
             ap.add_argument(flag, type=lambda s: s.lower() in ("1", "true", "yes"), default=None)
         elif isinstance(val, list):
             ap.add_argument(flag, type=int, nargs="+", default=None)
