@@ -360,6 +360,18 @@ size_t wsu_ws_attack_workspace_bytes(int n);
 int wsu_ws_attack(const uint8_t* x_u8, const float* x_hat, const float* x_bias, const float* pixel_filter, const float* mean_filter,
                   int hat_full, float hat_scale, int weighted, int correct_bias, float* beta_hat, double* sums,
                   void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
+/* K11 with one in-kernel filter per image: pixel_filters is DEVICE (N,9) fp32, row i = K[a][b] of image i's filter in pixel_filter's
+ * layout.  The same kernels as wsu_ws_attack (image i's numbers are those of wsu_ws_attack on image i alone with pixel_filter = row i);
+ * correct_bias uses the in-kernel filter on x_bar - x.  Workspace as for wsu_ws_attack. */
+int wsu_ws_attack_taps(const uint8_t* x_u8, const float* pixel_filters, const float* mean_filter, int weighted, int correct_bias,
+                       float* beta_hat, double* sums, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
+
+/* ---- K24: moments of the least-squares 3x3 pixel predictor.  x_u8: (N,H,W) DEVICE pixels.  At every interior pixel (r,c), with
+ *      xab = x[r-1+a][c-1+b], v = [x00 x01 x02 x12 x22 x21 x20 x10 x11] (the ring order of the flattened 8-tap filters,
+ *      _defs/filters.py:57-67, centre last).  moments: DEVICE (N,45) uint64, zeroed on the stream by this call:
+ *      moments[i][.] = sum over image i's interior of v_p * v_q, 0 <= p <= q <= 8, row-major upper triangle -- the Gram matrix X^T X of the
+ *      neighbours, X^T y (q = 8) and y^T y (last).  Exact integers (at most 255^2 (H-2)(W-2) each), the same bits on every run. */
+int wsu_ols_moments(const uint8_t* x_u8, unsigned long long* moments, int n, int h, int w, void* stream);
 
 /* ---- K12-K14: HILL-cost weighted prediction error (wMAE) of src/filters/evaluate.py:79-115 `get_filter_residuals_cover` and
  *      src/predictor_error.py:19-76 `attack`.  Both reference callers take HILL from a library (conseal.hill._costmap.compute_cost,

@@ -256,7 +256,7 @@ def table(frames):
     return res.T[model_names]
 
 
-def main(argv=None) -> None:
+def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(description="the predictor / stego-change correlation table (results/estimation/correlation.csv)")
     ap.add_argument("--data", required=True, help="dataset root with images*/ and stego*/ files.csv (the reference's ../data)")
     ap.add_argument("--out", required=True, help="output CSV (the reference writes results/estimation/correlation.csv)")
@@ -270,8 +270,16 @@ def main(argv=None) -> None:
     ap.add_argument("--per-image", action="store_true", help="one launch chain per pair instead of one per chunk of 32")
     ap.add_argument("--per-pair-out", default=None, help="also write the un-aggregated rows with their model_name")
     ap.add_argument("--progress", action="store_true")
-    a = ap.parse_args(argv)
+    from .ols import add_kernels_argument
+    add_kernels_argument(ap)
+    return ap.parse_args(argv)
+
+
+def main(argv=None) -> None:
+    a = parse_args(argv)
     logging.basicConfig(level=logging.INFO)
+    from .ols import register_from_args
+    register_from_args(a)
 
     import pandas as pd
     iterator = "python" if a.per_image else "batched"

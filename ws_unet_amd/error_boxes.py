@@ -16,7 +16,10 @@ sort and pandas' quantile would treat it differently) and images of different si
 Everything runs on the GPU: K16 (wsu_ae_values) writes one float32 key per pixel and predictor, K17 (wsu_ae_slices) finds the slice
 boundaries, K18 (wsu_ae_select) the order statistics by an exact radix select; the host does the linear interpolation and the IQR
 clip in float64, exactly as pandas does.  The keys are exact: K10's residual is float32 already, and a filter's AE is exact in
-float32 when its taps are multiples of 2^-12 and 255 * (1 + sum |f|) < 2^12 (KB and AVG are; other filters are refused).
+float32 when its taps are multiples of 2^-12 and 255 * (1 + sum |f|) < 2^12 (KB and AVG are; other filter taps are refused).
+A fitted filter registered by name (filters.register_filter, --kernels) has arbitrary taps: its key is its float64 AE rounded to
+float32.  Rounding is monotone, so each of its order statistics is the rounding of the exact one (relative error at most 2^-24); it
+cannot be the anchor, whose comparisons with the edges must be exact.
 """
 from __future__ import annotations
 
@@ -187,8 +190,8 @@ def box_table(results: typing.Mapping[str, typing.Any], anchor: str, edges=EDGE_
 # ---- predictors and their keys (K16) ------------------------------------------------------------------------------------------
 
 class _Pred:
-    def __init__(self, name, taps=None, model=None):
-        self.name, self.taps, self.model = name, taps, model
+    def __init__(self, name, taps=None, model=None, exact=True):
+        self.name, self.taps, self.model, self.exact = name, taps, model, exact
 
 
 def _resolve(name: str, spec, mode) -> _Pred:
@@ -199,7 +202,13 @@ def _resolve(name: str, spec, mode) -> _Pred:
     if isinstance(spec, str):
         if spec not in filters.NAMED_FILTERS:
             raise ValueError(f"predictor {name}: unknown filter {spec!r}")
-        return _Pred(name, taps=filter_taps(filters.get_coefficients(spec)))
+        try:
+            return _Pred(name, taps=filter_taps(filters.get_coefficients(spec)))
+        except ValueError:
+            if spec in filters.BUILTIN_FILTERS:
+                raise
+        from . import ops                                           # a registered fit: float32-rounded keys (module docstring)
+        return _Pred(name, taps=ops.filter_taps(filters.get_coefficients(spec), np.float64, "weights", "2d 8"), exact=False)
     if isinstance(spec, (UNetEstimator, torch.nn.Module)) or (isinstance(spec, tuple) and len(spec) == 2 and not isinstance(spec[0], (int, float))):
         return _Pred(name, model=as_unet_estimator(spec, mode).model)
     return _Pred(name, taps=filter_taps(spec))
@@ -281,6 +290,8 @@ def run(data_path, predictors: typing.Mapping[str, typing.Any] = None, anchor: s
     if iterator not in ("batched", "python"):
         raise ValueError(f"unknown iterator {iterator!r}")
     preds = [_resolve(name, spec, mode) for name, spec in predictors.items()]
+    if not preds[list(predictors).index(anchor)].exact:
+        raise ValueError(f"anchor {anchor!r}: a fitted filter's AE is not exact in float32, so it cannot define the slices")
     select = fabrika.precovers(iterator=None, convert_to=None, ignore_missing=True)(lambda df, **kw: df)
     df = select(data_path, split=split, shuffle_seed=shuffle_seed, take_num_images=take_num_images)
     if df.empty:
@@ -364,13 +375,18 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--split", default="split_te.csv")
     ap.add_argument("--mode", default=None, help="UNet inference mode (default: the package default)")
     ap.add_argument("--progress", action="store_true")
+    ap.add_argument("--filters", nargs="*", default=["KB", "AVG"], help="named filters of filters.NAMED_FILTERS; KB, the anchor, must be among them")
+    from .ols import add_kernels_argument
+    add_kernels_argument(ap)
     return ap.parse_args(argv)
 
 
 def main(argv=None) -> None:
     a = parse_args(argv)
     logging.basicConfig(level=logging.INFO)
-    predictors = {"KB": "KB", "AVG": "AVG"}
+    from .ols import register_from_args
+    register_from_args(a)
+    predictors = {name: name for name in a.filters}
     if a.model_dir:
         from .evaluate import trained_runs
         for method, model_name, config in trained_runs(a.model_dir, UNET_RUNS):

@@ -6,7 +6,8 @@ Mirrors the pieces of the reference that `src/ws/estimate.py:149-205 run` pulls 
 and the prediction-error table of the filters, results/prediction/filters.csv:
   get_filter_residuals_cover, run                                           src/filters/evaluate.py:53-115,149-205
 (mae and wmae per image and filter; wmae is the MAE over the 10 % of interior pixels with the lowest HILL cost, ws_unet_amd.hill).
-The OLS fits of the reference's filter tooling stay outside the UNet path.
+The OLS fits the reference's filter tooling reads (`OLS_*.csv`, `kernels.json`) are made by ws_unet_amd.ols; `register_filter` enters a
+fitted filter into the two name tables below, so that every driver that looks a name up accepts it.
 `infere_single` runs on the GPU (wsu_filter3x3_valid_f32); inside `ws.estimate` a `FilterEstimator` is recognised and its
 taps are evaluated in the statistic kernel itself, so the prediction never exists in memory.  The same holds for the filter table:
 the flattened 8-tap coefficients are evaluated inside the error kernel (wsu_prediction_error) in float64, as `x @ filter` is.
@@ -35,6 +36,31 @@ NAMED_FILTERS_2D = {
     "AVG9": _k2d([[1, 1, 1], [1, 1, 1], [1, 1, 1]], 9.),
     "1": _k2d([[0, 0, 0], [0, 1, 0], [0, 0, 0]], 1.),
 }
+
+
+BUILTIN_FILTERS = frozenset(NAMED_FILTERS_2D)
+
+
+def kernel_2d(taps8) -> np.ndarray:
+    """8 flattened taps (neighbour order x00 x01 x02 x12 x22 x21 x20 x10, the weight of x[r-1+a][c-1+b]) -> the (3,3,1) float32 kernel
+    array of NAMED_FILTERS_2D (`_k2d`: applied as a true convolution, so the weights appear reversed)."""
+    from .ops import _RING
+    wgt = np.zeros((3, 3))
+    for tap, (a, b) in zip(np.asarray(taps8, dtype="float64").reshape(8), _RING):
+        wgt[a, b] = tap
+    return _k2d(wgt[::-1, ::-1].T, 1.)
+
+
+def register_filter(name: str, taps8) -> None:
+    """Enter a fitted filter under `name`: NAMED_FILTERS[name] = the (8,1) float64 taps, NAMED_FILTERS_2D[name] = its (3,3,1) float32
+    kernel (ws.estimate.NAMED_FILTERS is that dict).  Registering a fitted name again replaces it; the built-in names are refused."""
+    taps = np.array(taps8, dtype="float64")
+    if taps.size != 8 or not np.all(np.isfinite(taps)):
+        raise ValueError(f"filter {name!r}: 8 finite taps expected, got shape {taps.shape}")
+    if not isinstance(name, str) or not name or name in BUILTIN_FILTERS:
+        raise ValueError(f"filter name {name!r} is empty or one of the built-in filters {sorted(BUILTIN_FILTERS)}")
+    NAMED_FILTERS[name] = taps.reshape(8, 1)
+    NAMED_FILTERS_2D[name] = kernel_2d(taps)
 
 
 def get_coefficients(filter_name: str, flatten: bool = True) -> np.ndarray:

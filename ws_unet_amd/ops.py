@@ -982,22 +982,47 @@ def ws_attack(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, x_bia
               return_sums: bool = False):
     """Batched WS payload estimate (wsu_ws_attack, src/ws/estimate.py:55-136).  x_u8: (N,H,W) uint8.
     x_hat: (N,H,W)/(N,1,H,W) full-frame prediction or (N,H-2,W-2) interior prediction, multiplied by `hat_scale`;
-    or `pixel_filter` (3,3[,1]) for an in-kernel linear predictor.  Returns beta_hat[N] (and the (N,3) fp64 sums)."""
+    or `pixel_filter` (3,3[,1]) for an in-kernel linear predictor, (N,3,3[,1]) for one per image (wsu_ws_attack_taps).
+    Returns beta_hat[N] (and the (N,3) fp64 sums)."""
     lib = _lib.load()
     _dev_check(x_u8, *[t for t in (x_hat, x_bias) if t is not None])
     n, h, w = x_u8.shape
     assert x_u8.dtype == torch.uint8
-    hat_full = _hat_full(x_hat, n, h, w, None, x_bias) if x_hat is not None else 1
-    pt, mt = filter_taps(pixel_filter, np.float32, "kernel"), filter_taps(mean_filter, np.float32, "kernel")
+    mt = filter_taps(mean_filter, np.float32, "kernel")
     beta = torch.empty(n, dtype=torch.float32, device=x_u8.device)
     sums = torch.empty((n, 3), dtype=torch.float64, device=x_u8.device) if return_sums else None
     ws = torch.empty(lib.wsu_ws_attack_workspace_bytes(n) // 8, dtype=torch.float64, device=x_u8.device)
+    tail = (beta.data_ptr(), sums.data_ptr() if sums is not None else None, ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())
+    if pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3):      # (N,3,3[,1])
+        if x_hat is not None or x_bias is not None:
+            raise ValueError("ws_attack: give exactly one of x_hat / pixel_filter")
+        if len(pixel_filter) != n:
+            raise ValueError(f"ws_attack: {len(pixel_filter)} filters for {n} images")
+        pts = torch.from_numpy(np.stack([filter_taps(k, np.float32, "kernel") for k in pixel_filter])).to(x_u8.device)
+        check(_launch("ws_attack", {}, lambda: lib.wsu_ws_attack_taps(
+            x_u8.data_ptr(), pts.data_ptr(), mt.ctypes.data if mt is not None else None, int(weighted), int(bool(correct_bias)),
+            *tail)), "wsu_ws_attack_taps")
+        return (beta, sums) if return_sums else beta
+    hat_full = _hat_full(x_hat, n, h, w, None, x_bias) if x_hat is not None else 1
+    pt = filter_taps(pixel_filter, np.float32, "kernel")
     check(_launch("ws_attack", {}, lambda: lib.wsu_ws_attack(
         x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, x_bias.data_ptr() if x_bias is not None else None,
         pt.ctypes.data if pt is not None else None, mt.ctypes.data if mt is not None else None,
-        hat_full, float(hat_scale), int(weighted), int(bool(correct_bias)), beta.data_ptr(),
-        sums.data_ptr() if sums is not None else None, ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())), "wsu_ws_attack")
+        hat_full, float(hat_scale), int(weighted), int(bool(correct_bias)), *tail)), "wsu_ws_attack")
     return (beta, sums) if return_sums else beta
+
+
+def ols_moments(x_u8: torch.Tensor) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,45) int64: per image the exact sums of v_i * v_j, i <= j (row-major upper triangle), over the interior
+    pixels, v = the eight neighbours in ring order (_RING) and the centre (wsu_ols_moments, K24; ws_unet_amd.ols unpacks and solves)."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(x_u8)
+    if n == 0:
+        raise ValueError("ols_moments: no images")
+    moments = torch.empty((n, 45), dtype=torch.int64, device=x_u8.device)
+    check(_launch("ols_moments", {"bytes": float(n * h * w)}, lambda: lib.wsu_ols_moments(
+        x_u8.data_ptr(), moments.data_ptr(), n, h, w, _stream())), "wsu_ols_moments")
+    return moments
 
 
 def hill_cost(x_u8: torch.Tensor, clamp: float = 1e10) -> torch.Tensor:

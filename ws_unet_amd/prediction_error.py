@@ -13,7 +13,7 @@ import logging
 import pathlib
 
 
-def main(argv=None) -> None:
+def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--data", required=True, help="dataset root with images*/files.csv (the reference's ../data)")
     ap.add_argument("--out", required=True, help="output CSV (the reference writes results/prediction/filters.csv)")
@@ -23,11 +23,23 @@ def main(argv=None) -> None:
     ap.add_argument("--model-name", default=None)
     ap.add_argument("--mode", default=None, help="UNet inference mode (default: the package default)")
     ap.add_argument("--progress", action="store_true")
+    from .ols import add_kernels_argument
+    add_kernels_argument(ap)
+    return ap
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    return _parser().parse_args(argv)
+
+
+def main(argv=None) -> None:
+    ap = _parser()
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
 
     import pandas as pd
-    from . import evaluate, filters
+    from . import evaluate, filters, ols
+    ols.register_from_args(a)
     data = pathlib.Path(a.data)
     iterator = "python" if a.per_image else "batched"
     res = filters.run(data, filter_names=a.filters, channels=[[3]] * len(a.filters), iterator=iterator, progress_on=a.progress)

@@ -24,7 +24,7 @@ import typing
 import numpy as np
 import torch
 
-from .. import fabrika, filters, ops
+from .. import fabrika, filters, ols, ops
 from ..evaluate import _decode_pool, _model_device, check_unet_geometry, unet_plane, upload_planes
 from ..imread import imread4_u8, u8_plane
 
@@ -94,6 +94,8 @@ def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct
         return ops.ws_attack(x_u8, y, x_bias=yb, hat_scale=255.0, **kw)
     if isinstance(pixel_estimator, filters.FilterEstimator):
         return ops.ws_attack(x_u8, None, pixel_filter=np.asarray(pixel_estimator.kernel)[..., ::-1], **kw)
+    if isinstance(pixel_estimator, ols.AdaptiveOLSEstimator):          # moments -> float64 fit on the host -> one filter per image
+        return ops.ws_attack(x_u8, None, pixel_filter=pixel_estimator.kernels(x_u8)[..., ::-1], **kw)
     # arbitrary host callable: reference call pattern, one image at a time
     hats, biases = [], []
     for xf in host_planes:
@@ -150,7 +152,7 @@ def attack_stego(*args, **kw):
 
 def _native_planes_ok(channels, pixel_estimator, imread, process_image) -> bool:
     """The default gray pipeline (Y plane, built-in predictor) needs no host arrays: native batched decode -> pinned buffer -> device."""
-    builtin = isinstance(pixel_estimator, (UNetEstimator, filters.FilterEstimator))
+    builtin = isinstance(pixel_estimator, (UNetEstimator, filters.FilterEstimator, ols.AdaptiveOLSEstimator))
     plain = process_image is None or getattr(process_image, "plane_selector", None) == (3,)
     return builtin and imread is imread4_u8 and plain and tuple(channels) == (3,)
 
@@ -211,7 +213,9 @@ def run(
 ):
     """WS attack over a data set with a named linear filter or a trained UNet as the pixel predictor (estimate.py:149-205)."""
     process_cover = filters.get_processor_2d(channels=channels)
-    if model_name in NAMED_FILTERS:
+    if model_name in ols.ADAPTIVE_NAMES:                       # 'OLSa' / 'OLSa2': the least-squares filter of each image under attack
+        pixel_estimator = ols.adaptive_estimator(model_name)
+    elif model_name in NAMED_FILTERS:
         pixel_estimator = filters.get_filter_estimator(filter_name=model_name, flatten=False)
     else:
         from .. import get_unet_estimator
@@ -240,13 +244,8 @@ def run(
     return res
 
 
-def main(argv=None) -> None:
-    """The reference's `python ws/estimate.py` (estimate.py:208-275): WS estimates of the covers and of the stego images at
-    alpha 0.4 / 0.2 / 0.1 with the AVG and KB filters and with the trained UNets ('l1' = dropout run, 'l1ws' = the run trained on
-    --train-method), one table -> results/estimation/ws_<train-method>.csv."""
+def parse_args(argv=None):
     import argparse
-    import pandas as pd
-    from .. import get_model_name
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--data", default="../data/")
     ap.add_argument("--model-dir", default="../models/unet")
@@ -259,7 +258,18 @@ def main(argv=None) -> None:
     ap.add_argument("--correct-bias", action="store_true")
     ap.add_argument("--per-image", action="store_true", help="use the per-image iterators instead of the batched ones")
     ap.add_argument("--out", default=None)
-    a = ap.parse_args(argv)
+    ols.add_kernels_argument(ap)
+    return ap.parse_args(argv)
+
+
+def main(argv=None) -> None:
+    """The reference's `python ws/estimate.py` (estimate.py:208-275): WS estimates of the covers and of the stego images at
+    alpha 0.4 / 0.2 / 0.1 with the AVG and KB filters and with the trained UNets ('l1' = dropout run, 'l1ws' = the run trained on
+    --train-method), one table -> results/estimation/ws_<train-method>.csv."""
+    import pandas as pd
+    from .. import get_model_name
+    a = parse_args(argv)
+    ols.register_from_args(a)
     model_dir = pathlib.Path(a.model_dir)
     settings = [(None, .0)] + [(sm, al) for sm in a.stego_methods for al in a.alphas]
     common = dict(demosaic=None, channels=(3,), correct_bias=a.correct_bias, weighted=a.weighted, batched=not a.per_image)

@@ -205,11 +205,12 @@ def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_MET
     inference `mode`.  Other keywords go to the fabrika iterators (take_num_images, split, ...)."""
     import pandas as pd
     from . import estimate
+    from .. import ols
     names = list(filters)
     for name in names:
-        if name not in estimate.NAMED_FILTERS:
-            raise ValueError(f"unknown filter {name!r}; choose from {sorted(estimate.NAMED_FILTERS)}")
-    preds = [(name, filters_lib.get_filter_estimator(filter_name=name, flatten=False)) for name in names]
+        if name not in estimate.NAMED_FILTERS and name not in ols.ADAPTIVE_NAMES:
+            raise ValueError(f"unknown filter {name!r}; choose from {sorted(estimate.NAMED_FILTERS) + sorted(ols.ADAPTIVE_NAMES)}")
+    preds = [(name, ols.adaptive_estimator(name) or filters_lib.get_filter_estimator(filter_name=name, flatten=False)) for name in names]
     est = estimate.as_unet_estimator(unet, mode)
     if est is not None:
         preds.append(("UNet", est))
@@ -274,6 +275,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "stego_method) added as model NAME, which must contain 'B0'; repeatable")
     ap.add_argument("--mode", default=None, help="UNet inference mode (default: the package default)")
     ap.add_argument("--progress", action="store_true")
+    from ..ols import add_kernels_argument
+    add_kernels_argument(ap)
     return ap.parse_args(argv)
 
 
@@ -281,6 +284,8 @@ def main(argv=None) -> None:
     import pandas as pd
     a = parse_args(argv)
     logging.basicConfig(level=logging.INFO)
+    from ..ols import register_from_args
+    register_from_args(a)
     detectors = [load_scores(path, name, a.stego_methods, a.alphas) for path, name in a.scores]      # input errors before GPU work
     unet = None
     if a.model_dir:
