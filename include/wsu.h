@@ -301,7 +301,8 @@ int wsu_colsum_pl(const void* g, float* db, float* workspace, size_t workspace_b
 int wsu_conv3x3_first_pl_bwd_weight(const void* g, const float* img, float* dw, float* db, float* workspace, size_t workspace_bytes,
                                     int n, int h, int w, int c, int products, void* stream);
 /*      wsu_conv3x3_first_pl_bwd_data (round 4): the INPUT gradient of the planar training path (saliency, src/saliency.py:159-174): g (planar gradient,
- *        c channels), w_oihw (c, cin <= 8, 3, 3) -> dx (N, cin, H, W) fp32 in g's power-of-two scale (the reflect adjoint included). */
+ *        c channels, a multiple of 16 up to 256), w_oihw (c, cin <= 8, 3, 3) -> dx (N, cin, H, W) fp32 in g's power-of-two scale (the reflect
+ *        adjoint included).  The whole range runs: the kernel's dynamic LDS (cin * 9 * c * 4 bytes, up to 73 728) is raised past 64 KB once. */
 int wsu_conv3x3_first_pl_bwd_data(const void* g, const float* w_oihw, float* dx_nchw, int n, int h, int w, int cin, int c, int products, void* stream);
 
 /* ---- K3p / K0p: the other two kernels of the planar (F16F8P) inference path (csrc/planar.hip).

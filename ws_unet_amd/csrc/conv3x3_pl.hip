@@ -75,6 +75,7 @@ struct PlArgs {
     // the tile's 8 granule planes x 512 bytes in by LDS-DMA instead of re-reading 2 bytes per element of the producing layer's f16 planes.
     unsigned char* relu_mask_out; const unsigned char* mbits; const unsigned char* mbits2;
     int msplit;                                           // 1: work items are half-blocks of 32 output channels (kernel variant MSPLIT); ncb = 2 * cout / 64
+    int rstore = 0;                                       // HONLY, 1: the residual plane of the output is stored all the same (kernel variant RSTORE: the border strips)
     int honly;                                            // GRAD, 1: f16 products only (kernel variant HONLY; wsu.h "products" of the backward entry points)
 };
 
@@ -431,7 +432,9 @@ template <bool ON> __device__ __forceinline__ int opaque_if(int v) { if constexp
 // cross terms; the residual plane of the gradient, the e4m3 weight planes and the derived plane are neither fetched nor built (needs XRES = false).
 // (Round 3's Q4 variant -- block-scaled fp4 cross terms with the fp4 operands derived by the loader waves -- moved to csrc/conv3x3_q.hip in round 4, where
 // the producers store those operands: the default inference mode no longer runs this kernel; training forwards, the data gradient and 'f16f8p' do.)
-template <int HC, bool POOL, bool XRES = true, bool F1 = false, bool GRAD = false, bool MSPLIT = false, bool HONLY = false>   // HC = head planes compiled in: 0 (no head), 1 (the reference's single output plane) or 4 (1..4)
+// RSTORE (with HONLY): f16 products, but the result keeps its residual plane -- the strips of the reflect adjoint, which the border fold adds to the
+// stored main result: a ring pixel is then rounded to f16 twice (main result, folded sum), not a third time in between.
+template <int HC, bool POOL, bool XRES = true, bool F1 = false, bool GRAD = false, bool MSPLIT = false, bool HONLY = false, bool RSTORE = false>   // HC = head planes compiled in: 0 (no head), 1 (the reference's single output plane) or 4 (1..4)
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 8)))
 void conv3x3_pl_kernel(const PlArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -676,7 +679,7 @@ _Pragma("unroll")
                             uint32_t hoff = hh ? plane_bytes : 0u;
                             asm volatile("" : "+v"(hoff));                     // (kept out of the 64-bit address arithmetic)
                             *reinterpret_cast<u32x4*>(base + (uint32_t)(off + hoff)) = mk_u4(xh0, xh1, yh0, yh1);
-                            if constexpr (!HONLY) {                                   // (HONLY = products F16: gradient tensors carry no residual plane)
+                            if constexpr (!HONLY || RSTORE) {                         // (HONLY = products F16: gradient tensors carry no residual plane)
                                 if (!hh) *reinterpret_cast<u32x4*>(base + (uint32_t)(off + 2u * plane_bytes)) = mk_u4(xlo, xlp, ylo, ylp);
                             }
                             if constexpr (!GRAD && !HEAD && !POOL) {            // the training forward's ReLU-mask byte of this lane's granule
@@ -769,7 +772,8 @@ int pl_launch(PlArgs a, bool first, hipStream_t s, bool grad = false) {
     if (!ncu) return WSU_ERR_HIP;
     static bool attr_done = false;
     if (!attr_done) {
-        void (*const fns[10])(const PlArgs) = {conv3x3_pl_kernel<0, false, false, false, true, false, true>, conv3x3_pl_kernel<0, false, true, false, true>,
+        void (*const fns[11])(const PlArgs) = {conv3x3_pl_kernel<0, false, false, false, true, false, true>, conv3x3_pl_kernel<0, false, true, false, true>,
+                                               conv3x3_pl_kernel<0, false, false, false, true, false, true, true>,
                                                conv3x3_pl_kernel<0, false>, conv3x3_pl_kernel<0, true>, conv3x3_pl_kernel<1, false>, conv3x3_pl_kernel<4, false>,
                                                conv3x3_pl_kernel<0, false, false>, conv3x3_pl_kernel<0, false, true, true>, conv3x3_pl_kernel<0, true, true, true>,
                                                conv3x3_pl_kernel<0, false, true, false, false, true>};
@@ -788,7 +792,8 @@ int pl_launch(PlArgs a, bool first, hipStream_t s, bool grad = false) {
     }
     const int grid = a.ntiles < ncu ? a.ntiles : ncu;
     const dim3 g(grid), b(NT);
-    if (grad && a.honly) hipLaunchKernelGGL((conv3x3_pl_kernel<0, false, false, false, true, false, true>), g, b, LDS_TOTAL, s, a);
+    if (grad && a.honly && a.rstore) hipLaunchKernelGGL((conv3x3_pl_kernel<0, false, false, false, true, false, true, true>), g, b, LDS_TOTAL, s, a);
+    else if (grad && a.honly) hipLaunchKernelGGL((conv3x3_pl_kernel<0, false, false, false, true, false, true>), g, b, LDS_TOTAL, s, a);
     else if (grad) hipLaunchKernelGGL((conv3x3_pl_kernel<0, false, true, false, true>), g, b, LDS_TOTAL, s, a);
     else if (first) {
         if (a.ypool) hipLaunchKernelGGL((conv3x3_pl_kernel<0, true, true, true>), g, b, LDS_TOTAL, s, a);
@@ -906,6 +911,10 @@ int wsu_conv3x3_pl_bwd_data(const void* g, const void* w_packed_dgrad, const voi
     WSU_REQUIRE((!mask1_bits || mask1) && (!mask2_bits || mask2), "conv3x3_pl_bwd_data: the 1-bit masks come WITH the activations they were taken from (the border fold reads those)");
     WSU_REQUIRE(!(mask1_bits || mask2_bits) || (long long)n * (cin / 8) * wsu_mask_hp(h) * wsu_mask_wp(w) < 0x7FFFFFF0LL, "conv3x3_pl_bwd_data: mask plane too large");
     WSU_REQUIRE((long long)h * w * 48 < 0xFFFFFFF0LL && (long long)n * ((h > w ? h : w) + 2) * 48 < 0xFFFFFFF0LL, "conv3x3_pl_bwd_data: h*w too large (a plane triple must stay below 4 GiB)");
+    if (!pad_zero) {                                          // (refused before the first launch: no half-done gradient behind an argument error)
+        WSU_REQUIRE(w_packed_ring && workspace, "conv3x3_pl_bwd_data: reflect padding needs the ring weights and a workspace");
+        WSU_REQUIRE(workspace_bytes >= wsu_conv3x3_pl_bwd_data_workspace_bytes(n, h, w, cin, cout), "conv3x3_pl_bwd_data: workspace of %zu bytes too small", workspace_bytes);
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     PlArgs a;
     a.x1 = (const char*)g; a.x2 = nullptr; a.wp = (const char*)w_packed_dgrad; a.bias = nullptr;
@@ -923,8 +932,6 @@ int wsu_conv3x3_pl_bwd_data(const void* g, const void* w_packed_dgrad, const voi
     int rc = pl_launch(a, false, s, true);
     if (rc || pad_zero) return rc;
     // ---- reflect adjoint: what the padded border ring folds back (train_pl.hip) ----
-    WSU_REQUIRE(w_packed_ring && workspace, "conv3x3_pl_bwd_data: reflect padding needs the ring weights and a workspace");
-    WSU_REQUIRE(workspace_bytes >= wsu_conv3x3_pl_bwd_data_workspace_bytes(n, h, w, cin, cout), "conv3x3_pl_bwd_data: workspace of %zu bytes too small", workspace_bytes);
     const int L = h > w ? h : w;
     char* strips_in = (char*)workspace;
     char* strips_out = strips_in + (size_t)4 * n * (L + 2) * 3 * cout;
@@ -932,7 +939,7 @@ int wsu_conv3x3_pl_bwd_data(const void* g, const void* w_packed_dgrad, const voi
     if (rc) return rc;
     PlArgs r = a;
     r.x1 = strips_in; r.wp = (const char*)w_packed_ring; r.y = strips_out; r.y2 = nullptr; r.nco1 = cin / 16; r.mask = nullptr; r.mask2 = nullptr;
-    r.mbits = nullptr; r.mbits2 = nullptr;
+    r.mbits = nullptr; r.mbits2 = nullptr; r.rstore = 1;      // (products F16: the strips keep their residual plane, the fold reads it)
     r.imgs_per_wset = 1; r.wset_bytes = (size_t)cin * cout * 9 * 4;
     r.n = 4; r.h = n; r.w = L + 2;
     r.tiles_x = (r.w + TW - 1) / TW; r.tiles_y = (r.h + TH - 1) / TH;

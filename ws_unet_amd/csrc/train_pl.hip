@@ -72,7 +72,9 @@ __global__ __launch_bounds__(256) void ring_gather_pl_kernel(const char* __restr
 __global__ __launch_bounds__(256) void ring_fold_pl_kernel(const char* __restrict__ so, char* __restrict__ dx1, char* __restrict__ dx2,
                                                            const char* __restrict__ mask1, const char* __restrict__ mask2,
                                                            int n, int h, int w, int nci, int nco1, int L, int gres) {
-    // gres = 0 (products F16): gradient tensors carry no residual plane -- it is neither read (dx, strips) nor written
+    // gres = 0 (products F16): gradient tensors carry no residual plane -- dx's is neither read nor written.  The strips' conv outputs are scratch of
+    // this entry, not gradient tensors: they keep their residual plane in either case (a ring pixel is rounded to f16 by the main result and by the sum
+    // stored here, not a third time in between)
     const u32x4 zres = mk_u4(0, 0, 0, 0);
     const int nrows = (h - 2 != 1) ? 2 : 1, ncols = (w - 2 != 1) ? 2 : 1;
     const int rlo = min(1, h - 2), rhi = max(1, h - 2);
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(256) void ring_fold_pl_kernel(const char* __restric
             const size_t p = (size_t)img * (L + 2) + col;
             float s[16];
             pl_decode16(*reinterpret_cast<const u32x4*>(so + pl_off(set, nci, ch, 0, shw, p)), *reinterpret_cast<const u32x4*>(so + pl_off(set, nci, ch, 1, shw, p)),
-                        gres ? *reinterpret_cast<const u32x4*>(so + pl_off(set, nci, ch, 2, shw, p)) : zres, WSU_F8_GLO_DIV, s);
+                        *reinterpret_cast<const u32x4*>(so + pl_off(set, nci, ch, 2, shw, p)), WSU_F8_GLO_DIV, s);
 #pragma unroll
             for (int e = 0; e < 16; ++e) add[e] += s[e];
         };
@@ -524,6 +526,11 @@ int wsu_conv3x3_first_pl_bwd_data(const void* g, const float* w_oihw, float* dx_
     WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && cin >= 1 && cin <= 8 && c >= 16 && c <= 256 && c % 16 == 0, "conv3x3_first_pl_bwd_data: bad shape cin=%d c=%d", cin, c);
     const long long total = (long long)n * cin * h * w;
     const unsigned nblk = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    static bool attr_done = false;                            // cin = 8, c = 256: 73 728 B of weights, above the 64 KB a kernel gets unasked
+    if (!attr_done) {
+        if (int rc = wsu_raise_lds(first_dgrad_pl_kernel, 8 * 9 * 256 * (int)sizeof(float), "first_dgrad_pl")) return rc;
+        attr_done = true;
+    }
     hipLaunchKernelGGL(first_dgrad_pl_kernel, dim3(nblk), dim3(256), (size_t)cin * 9 * c * sizeof(float), static_cast<hipStream_t>(stream),
                        (const char*)g, w_oihw, dx_nchw, n, h, w, cin, c, products == WSU_PRODUCTS_F16 ? 0 : 1);
     return wsu_check_launch("first_dgrad_pl_kernel");
