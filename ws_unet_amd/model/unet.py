@@ -96,6 +96,154 @@ class UniformDropout(nn.Module):
         return x
 
 
+PLANAR_MODES = (ops.MODE_F16F8P, ops.MODE_F16F8Q, ops.MODE_F16F4P, ops.MODE_F16P)
+W = ops.MODE_F16F8                                               # the planar paths' weights are packed as for 'f16f8'
+
+
+def _no_tag(name):
+    pass
+
+
+class _NHWC:
+    """What UNet._walk calls to run its layers on NHWC tensors ('f32', 'bf16', 'bf16x3', 'bf16x3s', 'f16f8', 'f16f8x'): the matrix layers in mode
+    `m`, e11 and the 1x1 head in `m0` (training: the train mode beside `train_fwd_mode`).  Keep policy: `t` (a dict, or None) receives the
+    reference's intermediates; `train` also keeps the 2-bit pool argmax `idx*`, fuses nothing and sets no layer tag."""
+
+    def __init__(self, net, m, m0=None, t=None, train=False, want_logit=False):
+        self.net, self.m, self.m0, self.t, self.train, self.want_logit = net, m, m if m0 is None else m0, t, train, want_logit
+        self.tag = _no_tag if train else ops.set_layer           # per-layer labels for bench.py's KernelTimer (a global assignment)
+        # e11 is folded into e12's input staging unless its output is asked for (xe11 then never reaches HBM)
+        self.fold_first = t is None and net.fuse_first and net._single_plane()
+        # last layer: d42 + outconv + sigmoid in one launch, xd42 never touches HBM
+        self.fused_head = t is None and net.nsteps >= 1 and net.fuse_head and net.outconv.out_channels <= 4
+
+    def first(self, x):
+        if self.fold_first:
+            return None
+        e11 = self.net.e11
+        self.tag("e11")
+        return ops.conv3x3_first(x, e11.weight.detach(), e11.bias.detach(), self.m0, relu=True)
+
+    def fused_first(self, x):
+        net, m = self.net, self.m
+        return ops.conv3x3_fused_first(x, net.e11.weight, net.e11.bias.detach(), net._packed("conv", ops.first_layer_weight_mode(m), net.e12),
+                                       net.e12.bias.detach(), net.e12.out_channels, m, pool=net.nsteps > 0)
+
+    def conv(self, name, xa, xb=None, pool=0, feeds=None, mask=False):
+        layer, m = getattr(self.net, name), self.m
+        res = ops.conv3x3(xa, xb, self.net._packed("conv", m, layer), layer.bias.detach(), layer.out_channels, m, pool=bool(pool), pool_idx=self.train)
+        if pool and self.train:
+            *res, self.t[f"idx{pool}"] = res
+        return res
+
+    def enter(self, depth, up, c1, cur, skip):
+        lu, m = getattr(self.net, up), self.m
+        self.tag(up)
+        xu = ops.convt2x2(cur, self.net._packed("convt", m, lu), lu.bias.detach(), lu.out_channels, m)
+        self.tag(c1)
+        return xu, self.conv(c1, xu, skip)
+
+    def head(self, name, cur):
+        layer, oc = getattr(self.net, name), self.net.outconv
+        self.tag(name + "+outconv")
+        return ops.conv3x3_head(cur, None, self.net._packed("conv", self.m, layer), layer.bias.detach(), oc.weight.detach(), oc.bias.detach(), self.m,
+                                want_logit=self.want_logit)
+
+    def outconv(self, cur):
+        oc, save = self.net.outconv, self.t is not None and not self.train
+        self.tag("outconv")
+        res = ops.conv1x1_sigmoid(cur, oc.weight.detach(), oc.bias.detach(), self.m0, want_logit=self.want_logit or save)
+        if save:
+            self.t["logit"] = res[1]
+        return res if self.want_logit or not save else res[0]
+
+
+class _Planar:
+    """What UNet._walk calls to run its layers on planar tensors of ONE storage format `S`, all persistent LDS-DMA kernels; no intermediate leaves
+    the format: ops.PLANAR_A ('f16f8p', 'f16f8q' and training: f16 + e4m3 residual), PLANAR_Q ('f16f4p': block-scaled fp4 cross terms, every
+    producer's epilogue writes the fp4 granule and scale byte its consumer multiplies) or PLANAR_H ('f16p': two f16 planes, one product per tap).
+    The head is always fused into the last 3x3 conv.  Keep policy: `train` keeps in `t` every activation the backward needs, the 1-bit ReLU
+    masks `m_x*` of those whose mask a data gradient applies (written by the producing kernel's epilogue, read by the consumer's loaders by
+    LDS-DMA: 1/8 byte per element instead of 2) and the last conv's output beside the head's; it fuses nothing else and sets no layer tag."""
+    CONV = {ops.PLANAR_A: ("conv3x3_pl", "conv"), ops.PLANAR_Q: ("conv3x3_q", "conv_f4"), ops.PLANAR_H: ("conv3x3_h", "conv_h")}
+    UP = {ops.PLANAR_Q: "conv3x3_up_q", ops.PLANAR_H: "conv3x3_up_h"}
+
+    def __init__(self, net, x, t=None, train=False, want_logit=False):
+        mode = "f16f8p" if train else net.mode
+        self.net, self.t, self.train, self.want_logit = net, t, train, want_logit
+        self.S = S = ops.PLANAR_H if mode == "f16p" else ops.PLANAR_Q if mode == "f16f4p" else ops.PLANAR_A
+        # 'f16f8q': the first conv of every decoder block (the two most expensive layers of unet_2) multiplies without the activations'
+        # residual term: 15 instead of 19 matrix units there, MAE 4e-6 -> ~4e-5 on the gate's weights (still 2.5x inside 1e-4)
+        self.quick = mode == "f16f8q"
+        self.rf = net._range_flag_tensor(x.device)               # OR-ed by every epilogue that stores an activation beyond the format's range
+        self.tag = _no_tag if train else ops.set_layer
+        self.fused_head = True
+        # e11 folded into e12's launch (its 64 channels are computed by the loader waves of the persistent kernel) for single-plane inputs: an
+        # experiment switch of the e4m3 modes (wsu_conv3x3_pl_fused_first_fwd) and of 'f16f4p' (ops.conv3x3_q_fused_first); 'f16p' has none
+        switch = {ops.PLANAR_A: net.fuse_first_planar, ops.PLANAR_Q: net.fuse_first_q, ops.PLANAR_H: False}[S]
+        self.fold_first = switch and not train and net._single_plane() and net.nsteps >= 1
+
+    def fused_up(self, depth):
+        """Decoder block `depth` runs upconv + concat + first conv as one launch: always in format H (it has no two-kernel decoder path), in
+        format Q unless switched off (WSU_FUSE_UP=0) or the block is wider than the kernel, never in format A."""
+        co = ENC_CH[depth - 1]                                   # the block's width (d*1.out_channels)
+        return self.S == ops.PLANAR_H or (self.S == ops.PLANAR_Q and self.net.fuse_up_planar and co <= 512 and co % 64 == 0)
+
+    def first(self, x):
+        if self.fold_first:
+            return None
+        e11 = self.net.e11
+        self.tag("e11")
+        res = ops.conv3x3_first_pl(x, e11.weight, e11.bias.detach(), range_flag=self.rf, want_mask=self.train, y_format=self.S)
+        if self.train:
+            res, self.t["m_xe11"] = res
+        return res
+
+    def fused_first(self, x):
+        net = self.net
+        e11, e12 = net.e11, net.e12
+        if self.S == ops.PLANAR_Q:                               # e11's weights tap-major: the kernel's scalar loads
+            return ops.conv3x3_q_fused_first(x, net._packed("taps", W, e11), None if e11.bias is None else e11.bias.detach(),
+                                             net._packed("conv_f4", W, e12), e12.bias.detach(), e12.out_channels, range_flag=self.rf)
+        return ops.conv3x3_pl_fused_first(x, e11.weight, e11.bias.detach(), net._packed("conv", W, e12), e12.bias.detach(), e12.out_channels,
+                                          pool=True, range_flag=self.rf)
+
+    def conv(self, name, xa, xb=None, pool=0, feeds=None, mask=False, **kw):
+        """One 3x3 conv in the format's arithmetic.  feeds: the decoder depth whose transposed conv reads the result (None: a 3x3 conv does);
+        mask: training keeps the result's ReLU mask; kw: the fused head's arguments."""
+        S, layer = self.S, getattr(self.net, name)
+        fn, kind = self.CONV[S]
+        if kw.get("want_y", True):                               # a head that stores no y stores no activation
+            kw["range_flag"] = self.rf
+        if S == ops.PLANAR_Q:                                    # only the tensor a transposed conv of its own reads stays in the e4m3-residual format
+            kw["y_format"] = S if feeds is None or self.fused_up(feeds) else ops.PLANAR_A
+        elif S == ops.PLANAR_A:
+            kw["x_residual"] = xb is None or not self.quick
+            kw["want_mask"] = mask and self.train
+        res = getattr(ops, fn)(xa, xb, self.net._packed(kind, W, layer), layer.bias.detach(), layer.out_channels, pool=bool(pool), **kw)
+        if kw.get("want_mask"):
+            res, self.t["m_x" + name] = res
+        return res
+
+    def enter(self, depth, up, c1, cur, skip):
+        net, lu, l1 = self.net, getattr(self.net, up), getattr(self.net, c1)
+        if self.fused_up(depth):
+            self.tag(up + "+" + c1)
+            return None, getattr(ops, self.UP[self.S])(cur, skip, *net._packed("up", self.S, lu, l1), l1.out_channels, range_flag=self.rf)
+        self.tag(up)
+        xu = ops.convt2x2_pl(cur, net._packed("convt", W, lu), lu.bias.detach(), lu.out_channels, range_flag=self.rf, y_format=self.S)
+        self.tag(c1)
+        return xu, self.conv(c1, xu, skip, mask=True)
+
+    def head(self, name, cur):
+        oc = self.net.outconv
+        self.tag(name + "+outconv")
+        res = self.conv(name, cur, want_y=self.train, head_w=oc.weight.detach(), head_b=oc.bias.detach(), want_logit=self.want_logit)
+        if self.train:
+            res, self.t["x" + name] = res
+        return res
+
+
 class UNet(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, nsteps: int, drop_rate: float,
                  drop_channel: Sequence[int], mode: Optional[str] = None):
@@ -124,8 +272,8 @@ class UNet(nn.Module):
         # xe11's memory (1.4 GB at batch 32 @ 512x512, 5.5 GB at 1024x1024) -- a switch for memory-bound callers, off by default
         self.fuse_first_q = os.environ.get("WSU_FUSE_FIRST_Q", "0") != "0"
         # arithmetic of the autograd path: exact fp32 MFMA for an 'f32' model; 'f16f8p' for a planar model -- the f16f8 arithmetic on planar
-        # activations AND gradients (3 bytes per element, model/autograd.py; single-plane inputs, falls back to 'bf16x3' otherwise and when the
-        # input gradient is asked for); else split-bf16 on fp32 tensors (~2^-16 relative per product -- finer than the TF32 convs PyTorch
+        # activations AND gradients (3 bytes per element, model/autograd.py; single-plane inputs, falls back to 'bf16x3' otherwise, the input gradient
+        # included); else split-bf16 on fp32 tensors (~2^-16 relative per product -- finer than the TF32 convs PyTorch
         # trains with by default on the reference's GPUs)
         self.train_mode = os.environ.get("WSU_TRAIN_MODE") or ("f32" if self.mode == "f32" else "f16f8p" if self.mode in ("f16f8p", "f16f8q", "f16f4p", "f16p") else "bf16x3")
         # train_mode 'f16f8p': the terms the BACKWARD matrix kernels (3x3 data and weight gradients) multiply -- 'f16' (default: exact products of
@@ -170,43 +318,35 @@ class UNet(nn.Module):
 
     # ---- packed-weight cache (re-packed only when a parameter was modified) -------------------------
     _PACKERS = {
-        "conv_f4": lambda p, mode: ops.pack_conv3x3_f4(p),
-        "conv_h": lambda p, mode: ops.pack_conv3x3_h(p),
-        "conv": ops.pack_conv3x3,
-        "dgrad": lambda p, mode: ops.pack_conv3x3(p, mode, dgrad=True),
-        "ring": lambda p, mode: ops.pack_conv3x3_ring(p),
+        "conv_f4": lambda mode, w: ops.pack_conv3x3_f4(w),
+        "conv_h": lambda mode, w: ops.pack_conv3x3_h(w),
+        "conv": lambda mode, w: ops.pack_conv3x3(w, mode),
+        "dgrad": lambda mode, w: ops.pack_conv3x3(w, mode, dgrad=True),
+        "ring": lambda mode, w: ops.pack_conv3x3_ring(w),
         # e11's weights tap-major (9, 64): the scalar loads of ops.conv3x3_q_fused_first
-        "taps": lambda p, mode: p.detach().reshape(p.shape[0], 9).t().contiguous(),
-        "convt_dgrad_pl": lambda p, mode: ops.pack_convt2x2_pl_dgrad(p),
-        "convt_dgrad": ops.pack_convt2x2_dgrad,
-        "convt": ops.pack_convt2x2,
+        "taps": lambda mode, w: w.detach().reshape(w.shape[0], 9).t().contiguous(),
+        "convt_dgrad_pl": lambda mode, w: ops.pack_convt2x2_pl_dgrad(w),
+        "convt_dgrad": lambda mode, w: ops.pack_convt2x2_dgrad(w, mode),
+        "convt": lambda mode, w: ops.pack_convt2x2(w, mode),
+        # (w_skip_packed, w_low_packed, bias) of the fused decoder-block entry; `mode` is the planar format
+        "up": lambda fmt, wu, bu, w1, b1: (ops.pack_conv3x3_up_h if fmt == ops.PLANAR_H else ops.pack_conv3x3_up)(w1, wu, bu, b1),
     }
-    _UP_PACKERS = {ops.PLANAR_Q: ops.pack_conv3x3_up, ops.PLANAR_H: ops.pack_conv3x3_up_h}
 
-    def _packed(self, name: str, mode: int, kind: str) -> torch.Tensor:
-        p = getattr(self, name).weight
-        key = (name, mode, kind)
-        tag = (p._version, p.data_ptr(), p.device)
+    def _packed(self, kind: str, mode: int, *layers):
+        """The `kind` packing (_PACKERS) in `mode` of one layer's weight or, kind 'up', of a decoder block's transposed conv and first conv, biases
+        included.  Cached on (version, address, device) of every parameter it reads."""
+        if kind == "up":
+            params = (layers[0].weight, layers[0].bias, layers[1].weight, layers[1].bias)
+        else:
+            params = (layers[0].weight,)
+        tag = []
+        for p in params:
+            tag += (p._version, p.data_ptr(), p.device)
+        key = (kind, mode) + layers
         hit = self._pack_cache.get(key)
-        if hit is not None and hit[0] == tag:
-            return hit[1]
-        packed = self._PACKERS[kind](p, mode)
-        self._pack_cache[key] = (tag, packed)
-        return packed
-
-    def _packed_up(self, up: str, c1: str, fmt: int = ops.PLANAR_Q):
-        """(w_skip_packed, w_low_packed, bias) of the fused decoder-block entry (ops.pack_conv3x3_up; fmt PLANAR_H: ops.pack_conv3x3_up_h), cached
-        on all four parameters' versions."""
-        lu, l1 = getattr(self, up), getattr(self, c1)
-        ps = (lu.weight, lu.bias, l1.weight, l1.bias)
-        key = (up, c1, "up", fmt)
-        tag = tuple((p._version, p.data_ptr(), p.device) for p in ps)
-        hit = self._pack_cache.get(key)
-        if hit is not None and hit[0] == tag:
-            return hit[1]
-        packed = self._UP_PACKERS[fmt](l1.weight, lu.weight, lu.bias, l1.bias)
-        self._pack_cache[key] = (tag, packed)
-        return packed
+        if hit is None or hit[0] != tag:
+            hit = self._pack_cache[key] = (tag, self._PACKERS[kind](mode, *params))
+        return hit[1]
 
     def _check_input(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda or not self.outconv.weight.is_cuda:
@@ -225,104 +365,81 @@ class UNet(nn.Module):
         """Inference forward.  ``keep`` (optional dict) receives every intermediate as an NHWC tensor,
         named as in the reference's forward (xe11 ... xd42, xp*, xu*)."""
         m = ops.mode_id(self.mode)
-        t = keep if keep is not None else {}
         save = keep is not None
-        e11 = self.e11
-        if m in (ops.MODE_F16F8P, ops.MODE_F16F8Q, ops.MODE_F16F4P, ops.MODE_F16P):
-            if save or not self._planar_ok():
-                m = ops.MODE_BF16X3             # intermediates are only kept in fp32 NHWC; odd channel counts take the general path
-            else:
-                res = self._forward_planar(x, want_logit)
-                if not getattr(self, "_range_checked", False):
-                    # first planar forward of this model: one synchronising look at the range flag.  Weights whose activations leave
-                    # the format's full-accuracy range (nobody knows that of a foreign checkpoint) fall back LOUDLY to fp32-range storage.
-                    self._range_checked = True
-                    if self.range_exceeded():
-                        import logging
-                        if self.mode == "f16p":
-                            logging.warning("ws_unet_amd.UNet: activations beyond +-65504 in mode 'f16p' (not a finite f16); "
-                                            "switching this model to mode 'bf16x3s'")
-                        else:
-                            logging.warning("ws_unet_amd.UNet: activations beyond +-448 in mode 'f16f8p' (the e4m3 residual saturates there); "
-                                            "switching this model to mode 'bf16x3s'")
-                        self.mode = "bf16x3s"
-                        self._range_switched = True                # (a sharded pass tells the other ranks: evaluate.range_fallback)
-                        return self.forward_features(x, keep, want_logit)
-                return res
+        if m in PLANAR_MODES and not save and self._planar_ok():
+            res = self._walk(x, _Planar(self, x, want_logit=want_logit))
+            if not getattr(self, "_range_checked", False):
+                # first planar forward of this model: one synchronising look at the range flag.  Weights whose activations leave
+                # the format's full-accuracy range (nobody knows that of a foreign checkpoint) fall back LOUDLY to fp32-range storage.
+                self._range_checked = True
+                if self.range_exceeded():
+                    import logging
+                    if self.mode == "f16p":
+                        logging.warning("ws_unet_amd.UNet: activations beyond +-65504 in mode 'f16p' (not a finite f16); "
+                                        "switching this model to mode 'bf16x3s'")
+                    else:
+                        logging.warning("ws_unet_amd.UNet: activations beyond +-448 in mode 'f16f8p' (the e4m3 residual saturates there); "
+                                        "switching this model to mode 'bf16x3s'")
+                    self.mode = "bf16x3s"
+                    self._range_switched = True                # (a sharded pass tells the other ranks: evaluate.range_fallback)
+                    return self.forward_features(x, keep, want_logit)
+            return res
+        if m in PLANAR_MODES:
+            m = ops.MODE_BF16X3                 # intermediates are only kept in fp32 NHWC; odd channel counts take the general path
         if m in (ops.MODE_BF16X3S, ops.MODE_F16F8) and (save or self.nsteps < 1 or not (self.fuse_first and self.fuse_head)
-                                     or e11.in_channels != 1 or e11.out_channels != 64 or self.outconv.out_channels > 4):
-            m = ops.MODE_BF16X3             # the split formats live only between the fused first layer and the fused head
-        # e11 is folded into e12's input staging unless its output is asked for (xe11 then never reaches HBM)
-        fuse_first = self.fuse_first and not save and e11.in_channels == 1 and e11.out_channels == 64
-        cur = None
-        tag = ops.set_layer                                        # per-layer labels for bench.py's KernelTimer (a global assignment)
-        if not fuse_first:
-            tag("e11")
-            cur = ops.conv3x3_first(x, e11.weight.detach(), e11.bias.detach(), m, relu=True)
-        if save:
+                                                       or not self._single_plane() or self.outconv.out_channels > 4):
+            m = ops.MODE_BF16X3                 # the split formats live only between the fused first layer and the fused head
+        return self._walk(x, _NHWC(self, m, t=keep, want_logit=want_logit))
+
+    def _walk(self, x: torch.Tensor, A):
+        """The reference's forward (unet.py:137-189), written once for every arithmetic and for training: `A` (_NHWC or _Planar above) runs each
+        layer, decides what is fused and keeps in `A.t` what its keep policy adds; the reference's intermediates are kept here, under the
+        reference's names.  Returns what the head returns."""
+        ns, tag, t = self.nsteps, A.tag, A.t
+        skips: List = []
+        cur = A.first(x)                                           # None: e11 runs inside e12's launch
+        if t is not None:
             t["xe11"] = cur
-        skips: List[torch.Tensor] = []
-        oc_fusable = self.fuse_head and self.outconv.out_channels <= 4
-        for lvl in range(self.nsteps + 1):
+        for lvl in range(ns + 1):
             a, b = ENC[lvl]
-            if lvl == 0 and fuse_first:
-                lb = self.e12
+            if lvl == 0 and cur is None:
                 tag("e11+e12")
-                res = ops.conv3x3_fused_first(x, e11.weight, e11.bias.detach(), self._packed("e12", ops.first_layer_weight_mode(m), "conv"), lb.bias.detach(),
-                                              lb.out_channels, m, pool=self.nsteps > 0)
-                if self.nsteps > 0:
+                res = A.fused_first(x)
+                if ns > 0:
                     skips.append(res[0])
                     cur = res[1]
                 else:
                     cur = res
                 continue
             if lvl >= 1:
-                la = getattr(self, a)
                 tag(a)
-                cur = ops.conv3x3(cur, None, self._packed(a, m, "conv"), la.bias.detach(), la.out_channels, m)
-                if save:
+                cur = A.conv(a, cur, mask=True)
+                if t is not None:
                     t["x" + a] = cur
-            lb = getattr(self, b)
             tag(b)
-            if lvl < self.nsteps:
-                full, cur = ops.conv3x3(cur, None, self._packed(b, m, "conv"), lb.bias.detach(), lb.out_channels, m, pool=True)
+            if lvl < ns:
+                full, cur = A.conv(b, cur, pool=lvl + 1)
                 skips.append(full)
-                if save:
-                    t["x" + b] = full
-                    t[f"xp{lvl + 1}"] = cur
+            elif ns == 0 and A.fused_head:
+                return A.head(b, cur)
             else:
-                cur = ops.conv3x3(cur, None, self._packed(b, m, "conv"), lb.bias.detach(), lb.out_channels, m)
-                if save:
-                    t["x" + b] = cur
-        for depth in range(self.nsteps, 0, -1):
+                full = cur = A.conv(b, cur, feeds=ns)              # feeds the transposed conv
+            if t is not None:
+                t["x" + b] = full
+                if lvl < ns:
+                    t[f"xp{lvl + 1}"] = cur
+        for depth in range(ns, 0, -1):
             up, c1, c2 = dec_names(depth)
-            lu, l1, l2 = getattr(self, up), getattr(self, c1), getattr(self, c2)
-            tag(up)
-            xu = ops.convt2x2(cur, self._packed(up, m, "convt"), lu.bias.detach(), lu.out_channels, m)
-            skip = skips[depth - 1]
-            tag(c1)
-            cur = ops.conv3x3(xu, skip, self._packed(c1, m, "conv"), l1.bias.detach(), l1.out_channels, m)
-            if save:
-                t["xu" + up[-1]] = xu
-                t["x" + c1] = cur
-            if depth == 1 and not save and oc_fusable:
-                # last layer: d42 + outconv + sigmoid in one launch, xd42 never touches HBM
-                tag(c2 + "+outconv")
-                return ops.conv3x3_head(cur, None, self._packed(c2, m, "conv"), l2.bias.detach(),
-                                        self.outconv.weight.detach(), self.outconv.bias.detach(), m, want_logit=want_logit)
+            xu, cur = A.enter(depth, up, c1, cur, skips[depth - 1])  # transposed conv + first conv, or the fused entry (xu is None)
+            if t is not None:
+                t["xu" + up[-1]], t["x" + c1] = xu, cur
+            if depth == 1 and A.fused_head:
+                return A.head(c2, cur)
             tag(c2)
-            cur = ops.conv3x3(cur, None, self._packed(c2, m, "conv"), l2.bias.detach(), l2.out_channels, m)
-            if save:
+            cur = A.conv(c2, cur, feeds=depth - 1)                 # feeds the next transposed conv
+            if t is not None:
                 t["x" + c2] = cur
-        oc = self.outconv
-        tag("outconv")
-        res = ops.conv1x1_sigmoid(cur, oc.weight.detach(), oc.bias.detach(), m, want_logit=want_logit or save)
-        if want_logit or save:
-            out, logit = res
-            if save:
-                t["logit"] = logit
-            return (out, logit) if want_logit else out
-        return res
+        return A.outconv(cur)
 
     def _range_flag_tensor(self, device) -> torch.Tensor:
         device = torch.device(device)
@@ -345,98 +462,13 @@ class UNet(nn.Module):
             rf.zero_()
         return hit
 
+    def _single_plane(self) -> bool:
+        return self.e11.in_channels == 1 and self.e11.out_channels == 64
+
     def _planar_ok(self) -> bool:
         """The planar path needs <= 8 input planes, at most 4 head planes and the reference's channel ladder (multiples of 64)."""
-        return self.e11.in_channels <= 8 and self.outconv.out_channels <= 4 and self.outconv.in_channels == 64 and self.e11.out_channels % 16 == 0
-
-    def _forward_planar(self, x: torch.Tensor, want_logit: bool = False):
-        """unet.py:137-189 on planar F16F8P activations: e11 (VALU) -> 3x3 convs with fused pool / concat / head and transposed convs, all
-        persistent LDS-DMA kernels; no intermediate leaves the format.  Mode 'f16p': planar H tensors throughout, every decoder block through
-        the fused entry ops.conv3x3_up_h (WSU_FUSE_UP and WSU_FUSE_FIRST_Q are ignored: the mode has no two-kernel decoder path)."""
-        W = ops.MODE_F16F8                                           # weights are packed as for 'f16f8'
-        # 'f16f8q': the first conv of every decoder block (the two most expensive layers of unet_2) multiplies without the activations'
-        # residual term: 15 instead of 19 matrix units there, MAE 4e-6 -> ~4e-5 on the gate's weights (still 2.5x inside 1e-4)
-        quick = self.mode == "f16f8q"
-        # 'f16f4p' (default): block-scaled fp4 cross terms on planar Q tensors (ops.PlanarQ; csrc/conv3x3_q.hip): every producer's epilogue writes
-        # the fp4 granule and scale byte its consumer multiplies; only the two tensors the transposed convs read stay in the e4m3-residual format
-        q4 = self.mode == "f16f4p"
-        # 'f16p': the walk of 'f16f4p' on planar H tensors (ops.PlanarH), the fused entry for every decoder block, no format-A tensor anywhere
-        h16 = self.mode == "f16p"
-        CK = "conv_h" if h16 else "conv_f4" if q4 else "conv"
-        A = ops.PLANAR_A
-        S = ops.PLANAR_H if h16 else ops.PLANAR_Q                    # the storage format between the layers of the 'f16f4p' / 'f16p' walk
-        tag = ops.set_layer
-        e11 = self.e11
-        rf = self._range_flag_tensor(x.device)
-
-        def conv(xa, xb, name, layer, fmt=S, xres=True, **kw):       # one 3x3 conv of the planar path in this mode's arithmetic
-            if h16:
-                return ops.conv3x3_h(xa, xb, self._packed(name, W, CK), layer.bias.detach(), layer.out_channels, **kw)
-            if q4:
-                return ops.conv3x3_q(xa, xb, self._packed(name, W, CK), layer.bias.detach(), layer.out_channels, y_format=fmt, **kw)
-            return ops.conv3x3_pl(xa, xb, self._packed(name, W, CK), layer.bias.detach(), layer.out_channels, x_residual=xres, **kw)
-
-        def fuse_up(depth):                                          # decoder block `depth` runs upconv + concat + first conv as one launch
-            l1 = getattr(self, dec_names(depth)[1])
-            return h16 or (q4 and self.fuse_up_planar and l1.out_channels <= 512 and l1.out_channels % 64 == 0)
-
-        # e11 is folded into e12 (its 64 channels are computed by the loader waves of the persistent kernel) for single-plane inputs -- an
-        # experiment switch of the e4m3 modes (the fused kernel multiplies e4m3 cross terms and writes the e4m3-residual format)
-        fuse_first = self.fuse_first_planar and not (q4 or h16) and e11.in_channels == 1 and e11.out_channels == 64 and self.nsteps >= 1
-        fuse_first_q = q4 and self.fuse_first_q and e11.in_channels == 1 and e11.out_channels == 64 and self.nsteps >= 1 and self.e12.in_channels == 64
-        cur = None
-        if not fuse_first and not fuse_first_q:
-            tag("e11")
-            cur = ops.conv3x3_first_pl(x, e11.weight, e11.bias.detach(), range_flag=rf, y_format=S if (q4 or h16) else A)
-        skips: List = []
-        for lvl in range(self.nsteps + 1):
-            a, b = ENC[lvl]
-            if lvl == 0 and fuse_first_q:
-                lb = self.e12
-                tag("e11+e12")
-                full, cur = ops.conv3x3_q_fused_first(x, self._packed("e11", W, "taps"), None if e11.bias is None else e11.bias.detach(),
-                                                      self._packed("e12", W, CK), lb.bias.detach(), lb.out_channels, range_flag=rf)
-                skips.append(full)
-                continue
-            if lvl == 0 and fuse_first:
-                lb = self.e12
-                tag("e11+e12")
-                full, cur = ops.conv3x3_pl_fused_first(x, e11.weight, e11.bias.detach(), self._packed("e12", W, "conv"), lb.bias.detach(),
-                                                       lb.out_channels, pool=True, range_flag=rf)
-                skips.append(full)
-                continue
-            if lvl >= 1:
-                la = getattr(self, a)
-                tag(a)
-                cur = conv(cur, None, a, la, range_flag=rf)
-            lb = getattr(self, b)
-            tag(b)
-            last = lvl == self.nsteps
-            if last and self.nsteps == 0:
-                tag(b + "+outconv")
-                return conv(cur, None, b, lb, want_y=False, head_w=self.outconv.weight.detach(), head_b=self.outconv.bias.detach(), want_logit=want_logit)
-            if not last:
-                full, cur = conv(cur, None, b, lb, pool=True, range_flag=rf)
-                skips.append(full)
-            else:
-                cur = conv(cur, None, b, lb, fmt=S if fuse_up(self.nsteps) else A, range_flag=rf)        # feeds the transposed conv
-        for depth in range(self.nsteps, 0, -1):
-            up, c1, c2 = dec_names(depth)
-            lu, l1, l2 = getattr(self, up), getattr(self, c1), getattr(self, c2)
-            if fuse_up(depth):
-                tag(up + "+" + c1)
-                cur = (ops.conv3x3_up_h if h16 else ops.conv3x3_up_q)(cur, skips[depth - 1], *self._packed_up(up, c1, S), l1.out_channels, range_flag=rf)
-            else:
-                tag(up)
-                xu = ops.convt2x2_pl(cur, self._packed(up, W, "convt"), lu.bias.detach(), lu.out_channels, range_flag=rf, y_format=S if q4 else A)
-                tag(c1)
-                cur = conv(xu, skips[depth - 1], c1, l1, xres=not quick, range_flag=rf)
-            if depth == 1:
-                tag(c2 + "+outconv")
-                return conv(cur, None, c2, l2, want_y=False, head_w=self.outconv.weight.detach(), head_b=self.outconv.bias.detach(), want_logit=want_logit)
-            tag(c2)
-            cur = conv(cur, None, c2, l2, fmt=S if fuse_up(depth - 1) else A, range_flag=rf)           # feeds the next transposed conv
-        raise AssertionError("unreachable")
+        e11, oc = self.e11, self.outconv
+        return e11.in_channels <= 8 and oc.out_channels <= 4 and oc.in_channels == 64 and e11.out_channels % 16 == 0
 
     def forward(self, x_in: torch.Tensor) -> torch.Tensor:
         x_in = self._check_input(x_in)
@@ -447,7 +479,7 @@ class UNet(nn.Module):
         x = x_in if (x_in.dtype == torch.float32 and x_in.is_contiguous()) else x_in.float().contiguous()
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if needs_grad:
-            from .autograd import unet_apply           # training path (exact fp32 kernels + saved activations)
+            from .autograd import unet_apply           # training path: the same walk, keeping what the backward reads
             return unet_apply(self, x)
         return self.forward_features(x)
 
