@@ -284,6 +284,10 @@ int wsu_convt2x2_pl_bwd_weight(const void* x, const void* dy, float* dw, float* 
  *        fp32 -> g (planar gradient w.r.t. the pre-activation of the layer that produced x), dw (cout, c), db (cout).
  *      wsu_colsum_pl: per-channel sums of a planar gradient (bias gradient of the transposed conv).
  *      wsu_conv3x3_first_pl_bwd_weight: first layer, single input plane: dw (c, 1, 3, 3), db (c) from the planar gradient g and img (N, 1, H, W).
+ *      wsu_conv3x3_first_pl_bwd_weight_planes: the same for cin <= 8 input planes (side-information planes, wsu_pair_batch_planes_f32): x_nchw
+ *        (N, cin, H, W) fp32 -> dw (c, cin, 3, 3), db (c) or NULL, dw[co,ci,u,v] = sum over n,i,j of g[n,co,i,j] * x[n,ci,reflect(i+u-1),reflect(j+v-1)];
+ *        c a multiple of 16 up to 256 as above.  Planes 0-3 and the bias sum take one pass over g, planes 4-7 a second one (9 * cin + 1 sums
+ *        per channel in registers: 8 planes at once do not fit a wave's register file).  Workspace: ..._workspace_bytes(cin, c).
  *      All reductions are two-stage with a fixed order (deterministic).
  *      products (every K7p entry point): with WSU_PRODUCTS_F16 a GRADIENT tensor carries no residual plane -- its producers (the data
  *        gradients, the pool and head backward) write the two f16 planes only and its consumers read only those (plane 2 of such a tensor
@@ -300,6 +304,9 @@ size_t wsu_chansum_pl_workspace_bytes(int c);
 int wsu_colsum_pl(const void* g, float* db, float* workspace, size_t workspace_bytes, int n, int h, int w, int c, int products, void* stream);
 int wsu_conv3x3_first_pl_bwd_weight(const void* g, const float* img, float* dw, float* db, float* workspace, size_t workspace_bytes,
                                     int n, int h, int w, int c, int products, void* stream);
+size_t wsu_conv3x3_first_pl_bwd_weight_planes_workspace_bytes(int cin, int c);
+int wsu_conv3x3_first_pl_bwd_weight_planes(const void* g, const float* x_nchw, float* dw, float* db, float* workspace, size_t workspace_bytes,
+                                           int n, int h, int w, int cin, int c, int products, void* stream);
 /*      wsu_conv3x3_first_pl_bwd_data (round 4): the INPUT gradient of the planar training path (saliency, src/saliency.py:159-174): g (planar gradient,
  *        c channels, a multiple of 16 up to 256), w_oihw (c, cin <= 8, 3, 3) -> dx (N, cin, H, W) fp32 in g's power-of-two scale (the reflect
  *        adjoint included).  The whole range runs: the kernel's dynamic LDS (cin * 9 * c * 4 bytes, up to 73 728) is raised past 64 KB once. */
@@ -535,6 +542,20 @@ int wsu_u8_to_unit_f32(const uint8_t* x, float* y, size_t count, void* stream);
  * Any H, W >= 1; loads are 4 and stores 16 bytes wide when W % 4 == 0 and the pointers are aligned.  n == 0 is a no-op. */
 int wsu_pair_batch_f32(const uint8_t* planes, int files, int h, int w, const int32_t* idx_in, const int32_t* idx_cov, const uint8_t* op,
                        int n, int allow_transpose, float* inputs, float* covers, void* stream);
+/* The same batch with side-information planes behind the image (the reference's ParityOracle / DemosaicOracle, src/_defs/loader.py:73-103),
+ * still one launch.  side: bit 0 appends the parity plane, bit 1 the three demosaic planes; inputs is (n,P,H,W), P = 1 + (side&1) +
+ * 3*((side>>1)&1); covers stays (n,1,H,W), or is NULL together with idx_cov (inference: the inputs alone).  With (r, c) the SOURCE coordinate
+ * of output pixel (i, j) under op[s] as defined above and v = planes[idx_in[s]][r][c], the planes are, in the reference's transform order:
+ *        image    float(v) / 255.0f                      (the bits wsu_pair_batch_f32 writes; so are covers)
+ *        parity   float(v & 1)
+ *        R site   1.0f where r%2==0 && c%2==0, else 0.0f
+ *        G site   1.0f where (r+c)%2==1
+ *        B site   1.0f where r%2==1 && c%2==1
+ * The reference appends these planes BEFORE its random flips and rotation, so the Bayer grid is transformed with the image: it is a function
+ * of the source coordinate, and a mirror of an even side moves its phase.  side outside 0..3 is an argument error (-1) before any HIP call;
+ * a sample with a bad index or a non-admitted op writes nothing; vector widths and the n == 0 rule are those of wsu_pair_batch_f32. */
+int wsu_pair_batch_planes_f32(const uint8_t* planes, int files, int h, int w, const int32_t* idx_in, const int32_t* idx_cov, const uint8_t* op,
+                              int n, int allow_transpose, int side, float* inputs, float* covers, void* stream);
 
 /* ======================= backward / train step (K7, K8, K9) =======================
  * The reference publishes no UNet training script; these entry points are the autograd of

@@ -82,6 +82,8 @@ SIGNATURES = {
     "wsu_chansum_pl_workspace_bytes": (c_size_t, [c_int]),
     "wsu_colsum_pl": (c_int, [_P, _P, _P, c_size_t] + [c_int] * 5 + [_P]),
     "wsu_conv3x3_first_pl_bwd_weight": (c_int, [_P] * 5 + [c_size_t] + [c_int] * 5 + [_P]),
+    "wsu_conv3x3_first_pl_bwd_weight_planes_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wsu_conv3x3_first_pl_bwd_weight_planes": (c_int, [_P] * 5 + [c_size_t] + [c_int] * 6 + [_P]),
     "wsu_conv3x3_first_pl_bwd_data": (c_int, [_P] * 3 + [c_int] * 6 + [_P]),
     "wsu_conv3x3_first_pl_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 7 + [_P, _P, _P]),
     "wsu_conv3x3_first_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 7 + [_P]),
@@ -118,6 +120,7 @@ SIGNATURES = {
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_u8_to_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     "wsu_pair_batch_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P]),
+    "wsu_pair_batch_planes_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     # ---- backward / train step
     "wsu_conv3x3_bwd_data_workspace_bytes": (c_size_t, [c_int] * 6),
     "wsu_conv3x3_bwd_data": (c_int, [_P, _P, _P, _P, c_size_t, _P, _P, c_int, _P, _P] + [c_int] * 6 + [_P]),

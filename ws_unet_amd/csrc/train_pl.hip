@@ -425,7 +425,75 @@ __global__ void first_split_kernel(const float* __restrict__ sums, float* __rest
     if (k < 9) dw[co * 9 + k] = sums[i]; else if (db) db[co] = sums[i];
 }
 
-constexpr int SUM_BLOCKS = 2048;                              // ~8 workgroups per CU: these kernels stream (2 - 3 loads in flight per thread), occupancy is their memory parallelism
+// The first layer's weight gradient for cin <= 8 input planes (side-information planes behind the image, data/pairs.py): chansum_pl_kernel<true>'s
+// scheme with 9 sums per plane.  One launch takes NP <= 4 planes from p0 on (and the bias sum if BIAS): 9 * NP + 1 accumulators per channel, 8
+// channels per thread -- 296 registers for NP = 4.  All 8 planes in one launch would need 584, beyond the 512 a wave can hold (the build reports
+// scratch for it), so cin > 4 takes a second launch and reads g twice.  Block partials [block][c][9 * cin + 1], column ci * 9 + tap, bias last.
+template <int NP, bool BIAS>
+__global__ __launch_bounds__(256) void first_planes_wgrad_kernel(const char* __restrict__ g, const float* __restrict__ x, float* __restrict__ part,
+                                                                 int n, int h, int w, int cin, int p0, int c, int gres) {
+    constexpr int NV = 9 * NP + (BIAS ? 1 : 0);
+    const int nvt = 9 * cin + 1;
+    const int ncg = c >> 3, ppb = 256 / ncg;
+    const int cg = threadIdx.x / ppb, pl = threadIdx.x % ppb;
+    const size_t hw = (size_t)h * w;
+    float acc[NV][8];
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[k][e] = 0.f;
+    const int rows = n * h;
+    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int im = row / h, y = row - im * h;
+        const size_t rowpix = (size_t)y * w;
+        const float* src = x + ((size_t)im * cin + p0) * hw;
+        const int ro[3] = {wsu_reflect(y - 1, h) * w, y * w, wsu_reflect(y + 1, h) * w};
+        for (int xx = pl; xx < w; xx += ppb) {
+            float gv[8];
+            pl_decode8(*reinterpret_cast<const u32x4*>(pl_h(g, im, c, cg, hw, rowpix + xx)), gres ? *reinterpret_cast<const u32x2*>(pl_r(g, im, c, cg, hw, rowpix + xx)) : mk_u2(0, 0), WSU_F8_GLO_DIV, gv);
+            const int co[3] = {wsu_reflect(xx - 1, w), xx, wsu_reflect(xx + 1, w)};
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+                for (int tp = 0; tp < 9; ++tp) {
+                    const float iv = src[p * hw + ro[tp / 3] + co[tp % 3]];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[p * 9 + tp][e] = fmaf(gv[e], iv, acc[p * 9 + tp][e]);
+                }
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[9 * NP][e] += gv[e];
+            }
+        }
+    }
+    __shared__ float red[256 * 8];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[threadIdx.x * 8 + e] = acc[k][e];
+        __syncthreads();
+        if (pl == 0) {
+            const int col = k < 9 * NP ? p0 * 9 + k : 9 * cin;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float sacc = 0.f;
+                for (int j = 0; j < ppb; ++j) sacc += red[(cg * ppb + j) * 8 + e];
+                part[((size_t)blockIdx.x * c + cg * 8 + e) * nvt + col] = sacc;
+            }
+        }
+    }
+}
+// [c][9 * cin + 1] sums -> dw (c, cin, 3, 3), db (c)
+__global__ void first_planes_split_kernel(const float* __restrict__ sums, float* __restrict__ dw, float* __restrict__ db, int c, int cin) {
+    const int nvt = 9 * cin + 1;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c * nvt) return;
+    const int co = i / nvt, k = i % nvt;
+    if (k < 9 * cin) dw[co * 9 * cin + k] = sums[i]; else if (db) db[co] = sums[i];
+}
+
+constexpr int SUM_BLOCKS = 2048;                             // ~8 workgroups per CU: these kernels stream (2 - 3 loads in flight per thread), occupancy is their memory parallelism
 
 inline unsigned grid_for(long long total) { return (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192); }
 
@@ -517,6 +585,41 @@ int wsu_conv3x3_first_pl_bwd_weight(const void* g, const float* img, float* dw, 
     if (rc) return rc;
     hipLaunchKernelGGL(first_split_kernel, dim3((c * 10 + 63) / 64), dim3(64), 0, s, (const float*)sums, dw, db, c);
     return wsu_check_launch("first_split_kernel");
+}
+
+size_t wsu_conv3x3_first_pl_bwd_weight_planes_workspace_bytes(int cin, int c) {
+    if (cin < 1 || c < 1) return 0;
+    return (size_t)(SUM_BLOCKS + 1) * c * (9 * cin + 1) * sizeof(float);
+}
+
+// K7p: weight / bias gradient of the first layer for cin <= 8 input planes: g (planar gradient, c channels), x_nchw (N, cin, H, W) fp32 ->
+// dw (c, cin, 3, 3), db (c) or NULL.  Planes 0-3 (and the bias sum) in one launch, planes 4-7 in a second; block partials summed in block order.
+int wsu_conv3x3_first_pl_bwd_weight_planes(const void* g, const float* x_nchw, float* dw, float* db, float* workspace, size_t workspace_bytes,
+                                           int n, int h, int w, int cin, int c, int products, void* stream) {
+    WSU_REQUIRE(g && x_nchw && dw && workspace, "conv3x3_first_pl_bwd_weight_planes: null pointer");
+    WSU_REQUIRE(products == WSU_PRODUCTS_F16F8 || products == WSU_PRODUCTS_F16, "conv3x3_first_pl_bwd_weight_planes: products must be WSU_PRODUCTS_F16F8 or WSU_PRODUCTS_F16");
+    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && cin >= 1 && cin <= 8 && c >= 16 && c <= 256 && c % 16 == 0 && 256 % (c / 8) == 0,
+                "conv3x3_first_pl_bwd_weight_planes: bad shape cin=%d c=%d", cin, c);
+    WSU_REQUIRE((long long)n * h <= 0x7FFFFFFFll, "conv3x3_first_pl_bwd_weight_planes: %lld rows exceed the row index", (long long)n * h);
+    WSU_REQUIRE(workspace_bytes >= wsu_conv3x3_first_pl_bwd_weight_planes_workspace_bytes(cin, c), "conv3x3_first_pl_bwd_weight_planes: workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nblk = (long long)n * h < SUM_BLOCKS ? n * h : SUM_BLOCKS;      // a block walks image rows
+    const int nvt = 9 * cin + 1, gres = products == WSU_PRODUCTS_F16 ? 0 : 1;
+    float* sums = workspace + (size_t)SUM_BLOCKS * c * nvt;
+    for (int p0 = 0; p0 < cin; p0 += 4) {
+        const int np = cin - p0 < 4 ? cin - p0 : 4;
+#define WSU_FIRST_PLANES(NP, BIAS) hipLaunchKernelGGL((first_planes_wgrad_kernel<NP, BIAS>), dim3(nblk), dim3(256), 0, s, (const char*)g, x_nchw, workspace, n, h, w, cin, p0, c, gres)
+        if (p0 == 0) { if (np == 1) WSU_FIRST_PLANES(1, true); else if (np == 2) WSU_FIRST_PLANES(2, true); else if (np == 3) WSU_FIRST_PLANES(3, true); else WSU_FIRST_PLANES(4, true); }
+        else { if (np == 1) WSU_FIRST_PLANES(1, false); else if (np == 2) WSU_FIRST_PLANES(2, false); else if (np == 3) WSU_FIRST_PLANES(3, false); else WSU_FIRST_PLANES(4, false); }
+#undef WSU_FIRST_PLANES
+        const int rc = wsu_check_launch("first_planes_wgrad_kernel");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(block_sum_kernel, dim3((c * nvt + 3) / 4), dim3(256), 0, s, workspace, sums, nblk, c * nvt);
+    int rc = wsu_check_launch("block_sum_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(first_planes_split_kernel, dim3((c * nvt + 63) / 64), dim3(64), 0, s, (const float*)sums, dw, db, c, cin);
+    return wsu_check_launch("first_planes_split_kernel");
 }
 
 // K7p: data gradient of the first layer: g (planar gradient, c channels at h x w), w_oihw (c, cin, 3, 3) fp32 -> dx (N, cin, H, W) fp32 (in g's scale).

@@ -23,6 +23,11 @@ Three seeded draws per epoch, each over ALL pairs and indexed by pair id, so tha
   * `default_rng([seed, epoch, 2])`  the payload, when `stego_method` and / or `alpha` is a list (`payload_plan()`): one
     (method, alpha) of the row-major (methods x alphas) combinations per pair; `alphas` of the batch is the drawn payload.
 
+`parity_oracle` / `demosaic_oracle` (the published configs' keys; the reference's ParityOracle / DemosaicOracle, _defs/loader.py:73-103) append
+side-information planes to every INPUT: the LSB plane, and the R, G, B site indicators of the RGGB grid.  The reference appends them before
+its flips and rotation, so they are transformed with the image (`side_planes_u8`, then `apply_op`); targets and alphas are unchanged.  A
+simulated twin's planes come from the twin's own pixels.
+
 MI355X-side: files are decoded by libwsu_io on C++ threads into pinned buffers one batch ahead of the consumer, uploaded as
 uint8 and assembled on the device by ONE kernel (wsu_pair_batch_f32: gather + D4 transform + x / 255, inputs and targets together)
 -- 1 byte per pixel over PCIe instead of 4.  Data-parallel ranks take
@@ -68,6 +73,18 @@ def apply_op(x: np.ndarray, op: int) -> np.ndarray:
     return x
 
 
+def side_planes_u8(plane: np.ndarray, parity: bool, demosaic: bool) -> np.ndarray:
+    """(H,W) uint8 -> (P,H,W) uint8 of the UNtransformed image: the pixels, then 0/1 planes in the reference's transform order -- the LSB
+    (parity), then the R (even row, even column), G (row + column odd) and B (odd row, odd column) sites (demosaic)."""
+    out = [plane]
+    if parity:
+        out.append(plane & 1)
+    if demosaic:
+        r, c = np.indices(plane.shape)
+        out += [((r | c) & 1) == 0, ((r ^ c) & 1) == 1, ((r & c) & 1) == 1]
+    return np.stack([np.asarray(p, dtype=np.uint8) for p in out])
+
+
 def _flip_rot_table() -> np.ndarray:
     ramp = np.arange(16).reshape(4, 4)
     images = [apply_op(ramp, o) for o in range(8)]
@@ -95,7 +112,7 @@ class PairLoader:
                  batch_size: int = 16, *, covers_only: bool = False, shuffle: bool = True,
                  seed: int = 0, rank: int = 0, world: int = 1, device: typing.Optional[torch.device] = None,
                  take_num_images: typing.Optional[int] = None, threads: typing.Optional[int] = None, simulate: bool = False,
-                 post_flip: bool = False, post_rotate: bool = False):
+                 post_flip: bool = False, post_rotate: bool = False, parity_oracle: bool = False, demosaic_oracle: bool = False):
         per_pair = 1 if covers_only else 2
         if batch_size % per_pair:
             raise ValueError("batch_size must be even: every pair contributes a cover and a stego sample")
@@ -129,6 +146,7 @@ class PairLoader:
         self.shuffle, self.seed, self.epoch = shuffle, seed, 0
         self.rank, self.world, self.device, self.threads = rank, world, device, threads
         self.post_flip, self.post_rotate = bool(post_flip), bool(post_rotate)
+        self.parity_oracle, self.demosaic_oracle = bool(parity_oracle), bool(demosaic_oracle)
         self._pinned = {}
         self._uploaded = {}                                             # slot -> event recorded behind its last upload
 
@@ -267,7 +285,10 @@ class PairLoader:
         buf, idx_in, idx_cov, alphas, op = (staged[k] for k in ("buf", "idx_in", "idx_cov", "alphas", "op"))
         if self.device is None:                                         # host-logic mode: uint8 planes, no GPU involved
             planes = buf.numpy()
-            x = np.stack([apply_op(planes[i], o) for i, o in zip(idx_in, op)])
+            if self.parity_oracle or self.demosaic_oracle:              # (n,P,H,W): plane 0 the transformed pixels, then the 0/1 side planes
+                x = np.stack([apply_op(side_planes_u8(planes[i], self.parity_oracle, self.demosaic_oracle), o) for i, o in zip(idx_in, op)])
+            else:
+                x = np.stack([apply_op(planes[i], o) for i, o in zip(idx_in, op)])
             c = np.stack([apply_op(planes[i], o) for i, o in zip(idx_cov, op)])
             return torch.from_numpy(x), (torch.from_numpy(c), alphas)
         from .. import ops
@@ -284,7 +305,10 @@ class PairLoader:
                 for meth, (sel, a, seeds) in staged["sim"].items():     # one call per method present in the batch, per-image alphas
                     twins[sel] = embed.simulate(u8[sel], meth, a, seeds)[0]
             u8 = torch.cat([u8, twins])
-        x, c = ops.pair_batch(u8, idx_in, idx_cov, op)                  # (n,1,H,W) fp32 in [0,1], numpy's x / 255.
+        if self.parity_oracle or self.demosaic_oracle:                  # inputs (n,P,H,W): the side planes behind the image, same launch
+            x, c = ops.pair_batch_planes(u8, idx_in, idx_cov, op, self.parity_oracle, self.demosaic_oracle)
+        else:
+            x, c = ops.pair_batch(u8, idx_in, idx_cov, op)              # (n,1,H,W) fp32 in [0,1], numpy's x / 255.
         return x, (c, alphas.to(self.device))
 
     def __iter__(self):

@@ -92,8 +92,12 @@ def range_retry(model, compute, **look):
 
 def unet_plane(model, x_u8: torch.Tensor) -> torch.Tensor:
     """(N,H,W) uint8 device planes -> the network's first output plane for x / 255 (wsu_u8_to_unit_f32 -> forward), a contiguous (N,H,W)
-    float32 tensor in [0,1]; no autograd graph."""
+    float32 tensor in [0,1]; no autograd graph.  A model trained with side-information planes (`model.side_planes`, set by get_pretrained from
+    the run's config) gets them behind the image: one launch builds the whole input (ops.side_planes)."""
+    parity, demosaic = getattr(model, "side_planes", (False, False))
     with torch.no_grad():
+        if parity or demosaic:
+            return model(ops.side_planes(x_u8, parity, demosaic))[:, 0].contiguous()
         return model(ops.u8_to_unit(x_u8)[:, None])[:, 0].contiguous()
 
 
@@ -109,8 +113,9 @@ def infere_single(
     device=None,
 ) -> np.ndarray:
     """(H,W,1) float32 in 0..255  ->  (510,510,1) float32 prediction in 0..255 (evaluate.py:31-52)."""
+    parity, demosaic = getattr(model, "side_planes", (False, False))       # the planes the run was trained with (get_pretrained)
     transform = get_timm_transform(
-        mean=None, std=None, grayscale=True, demosaic_oracle=False, post_flip=False, post_rotate=False,
+        mean=None, std=None, grayscale=True, parity_oracle=parity, demosaic_oracle=demosaic, post_flip=False, post_rotate=False,
     )
     x_ = transform(x / 255.)[None].to(_model_device(model))
     with torch.no_grad():
@@ -732,12 +737,16 @@ def get_pretrained(
     mode: str = None,
 ):
     """Build the network named in <model_path>/<model_name>/config.json and load model/best_model.pt.tar
-    (evaluate.py:162-188).  `channels` is accepted and ignored like in the reference."""
+    (evaluate.py:162-188).  `channels` is accepted and ignored like in the reference.  Unlike the reference (which hard-codes one input
+    plane) a run whose config sets `parity_oracle` / `demosaic_oracle` gets the input planes it was trained with; `model.side_planes`
+    tells the evaluation drivers to build them (unet_plane, infere_single)."""
     model_path = Path(model_path)
     with open(model_path / model_name / "config.json") as f:
         config = json.load(f)
     dev = torch.device(device) if device is not None and torch.device(device).type == "cuda" else DEVICE
-    model = get_model(config["network"], in_channels=1, out_channels=1, channel=[0], drop_rate=0., mode=mode).to(dev)
+    sides = (bool(config.get("parity_oracle", False)), bool(config.get("demosaic_oracle", False)))
+    model = get_model(config["network"], in_channels=ops.side_plane_count(*sides), out_channels=1, channel=[0], drop_rate=0., mode=mode).to(dev)
+    model.side_planes = sides
     checkpoint = torch.load(model_path / model_name / "model" / "best_model.pt.tar", map_location=dev, weights_only=True)
     model.load_state_dict(checkpoint["state_dict"])
     logging.info(f"model {model_name} loaded")

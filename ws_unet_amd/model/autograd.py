@@ -4,8 +4,9 @@ The reference has no hand-written backward -- it relies on autograd through
 src/unet/model/unet.py:137-189.  Here the whole network is ONE autograd node: the forward is UNet._walk keeping the activations, the backward
 (_backward below) walks the layers in reverse calling the K7 kernels (include/wsu.h).  `model.train_mode` picks the path:
   'f16f8p'  (default for planar models) activations AND gradients in the planar three-plane layout (3 bytes per element), the f16f8
-            arithmetic in forward, data gradient and weight gradient (unet._Planar / _PlanarBwd); single-plane inputs -- multi-plane
-            inputs fall back to 'bf16x3';
+            arithmetic in forward, data gradient and weight gradient (unet._Planar / _PlanarBwd); single-plane inputs, and inputs of 2..8
+            planes (side-information planes) when the model carries `train_planes_planar = True` -- other multi-plane inputs fall
+            back to 'bf16x3';
   'bf16x3'  fp32 NHWC tensors; the matrix kernels run the f16f8 arithmetic on them (`train_fwd_mode` / `train_bwd_mode` = 'f16f8x', default:
             exact f16 products + fp8 cross terms, ~2^-15 relative, 0.7 of bf16x3's matrix cycles) or split-bf16; 2-bit pool argmax saved by
             the forward;
@@ -101,6 +102,8 @@ class _PlanarBwd:
         return ops.maxpool2x2_pl_bwd(skip_g, g, t["x" + ENC[lvl][1]], **self.kw)
 
     def first_w(self, g, x):
+        if x.shape[1] > 1:
+            return ops.conv3x3_first_pl_bwd_weight_planes(g, x, **self.kw)
         return ops.conv3x3_first_pl_bwd_weight(g, x, **self.kw)
 
     def first_d(self, g, w):
@@ -178,7 +181,9 @@ class _UNetFn(torch.autograd.Function):
         """UNet._walk with the training keep policy: the reference's intermediates plus idx* (NHWC) or m_x* (planar), `last` and `out`."""
         tm = getattr(model, "train_mode", "f32")
         if tm == "f16f8p":
-            if model._planar_ok() and model.e11.in_channels == 1:     # what the planar inference path covers, for single-plane inputs
+            # what the planar inference path covers: for single-plane inputs, and for 2..8 planes where the model asks for it
+            cin = model.e11.in_channels
+            if model._planar_ok() and (cin == 1 or (cin <= 8 and getattr(model, "train_planes_planar", False))):
                 t: Dict[str, torch.Tensor] = {}
                 out = model._walk(x, _Planar(model, x, t=t, train=True))
                 ok = True

@@ -272,7 +272,7 @@ class UNet(nn.Module):
         # xe11's memory (1.4 GB at batch 32 @ 512x512, 5.5 GB at 1024x1024) -- a switch for memory-bound callers, off by default
         self.fuse_first_q = os.environ.get("WSU_FUSE_FIRST_Q", "0") != "0"
         # arithmetic of the autograd path: exact fp32 MFMA for an 'f32' model; 'f16f8p' for a planar model -- the f16f8 arithmetic on planar
-        # activations AND gradients (3 bytes per element, model/autograd.py; single-plane inputs, falls back to 'bf16x3' otherwise, the input gradient
+        # activations AND gradients (3 bytes per element, model/autograd.py; single-plane inputs, or 2..8 planes with train_planes_planar; falls back to 'bf16x3' otherwise, the input gradient
         # included); else split-bf16 on fp32 tensors (~2^-16 relative per product -- finer than the TF32 convs PyTorch
         # trains with by default on the reference's GPUs)
         self.train_mode = os.environ.get("WSU_TRAIN_MODE") or ("f32" if self.mode == "f32" else "f16f8p" if self.mode in ("f16f8p", "f16f8q", "f16f4p", "f16p") else "bf16x3")
@@ -282,6 +282,13 @@ class UNet(nn.Module):
         # train_products.md): a gradient element is a sum of 10^3 .. 10^7 products whose operand roundings (2^-12 relative, unbiased) average
         # out -- <= 2e-4 relative L2 per kernel on zero-mean random operands, the worst case -- while the forward's own rounding already puts
         # ~1e-3 between any two arithmetics through ReLU-mask flips; 300 AdamW steps track exact fp32 as closely as 'f16f8' does.
+        # train_mode 'f16f8p' with 2..8 input planes (side-information planes): True trains on the planar path too (first-layer weight gradient:
+        # ops.conv3x3_first_pl_bwd_weight_planes), False (default) on the fp32-storage fallback, as every multi-plane model did before the
+        # planar path took them.  ws_unet_amd.train decides for its own models.
+        self.train_planes_planar = False
+        # (parity_oracle, demosaic_oracle): the side-information planes this network's input carries behind the image (ops.side_planes);
+        # set by evaluate.get_pretrained and ws_unet_amd.train from the run's config, read by evaluate.unet_plane / infere_single
+        self.side_planes = (False, False)
         self.train_products = os.environ.get("WSU_TRAIN_PRODUCTS") or "f16"
         ops.products_id(self.train_products)
         # matrix layers of the training FORWARD when train_mode is 'bf16x3': 'f16f8x' (default) or 'bf16x3'

@@ -790,6 +790,27 @@ def conv3x3_first_pl_bwd_weight(g: torch.Tensor, x_nchw: torch.Tensor, want_bias
     return dw, db
 
 
+def conv3x3_first_pl_bwd_weight_planes(g: torch.Tensor, x_nchw: torch.Tensor, want_bias: bool = True, products: str = "f16f8"):
+    """First-layer weight / bias gradient from a planar gradient for an input of 1..8 planes (wsu_conv3x3_first_pl_bwd_weight_planes):
+    g planar (N, C/16, 3, H, W, 4), x_nchw (N, cin, H, W) fp32 -> dw (C, cin, 3, 3), db (C) or None."""
+    lib = _lib.load()
+    x_nchw = x_nchw.contiguous()
+    _dev_check(g, x_nchw)
+    n, nch, _, h, w, _ = g.shape
+    c, cin = nch * 16, x_nchw.shape[1]
+    if x_nchw.dtype != torch.float32 or tuple(x_nchw.shape) != (n, cin, h, w):
+        raise ValueError(f"conv3x3_first_pl_bwd_weight_planes: x_nchw must be ({n}, cin, {h}, {w}) float32, got {tuple(x_nchw.shape)} {x_nchw.dtype}")
+    dw = torch.empty((c, cin, 3, 3), dtype=torch.float32, device=g.device)
+    db = torch.empty(c, dtype=torch.float32, device=g.device) if want_bias else None
+    ws = workspace(lib.wsu_conv3x3_first_pl_bwd_weight_planes_workspace_bytes(cin, c), g.device)
+    reads = 1 if cin <= 4 else 2                            # passes over g (4 planes each)
+    meta = {"bytes": float(n * h * w * (reads * c * (2 if products == "f16" else 3) + 4 * cin))}
+    check(_launch("conv3x3_first_pl_bwd_weight_planes", meta, lambda: lib.wsu_conv3x3_first_pl_bwd_weight_planes(
+        g.data_ptr(), x_nchw.data_ptr(), dw.data_ptr(), _ptr(db), ws.data_ptr(), ws.numel() * 4, n, h, w, cin, c, products_id(products), _stream())),
+        "wsu_conv3x3_first_pl_bwd_weight_planes")
+    return dw, db
+
+
 def conv3x3_first_pl_bwd_data(g: torch.Tensor, w: torch.Tensor, products: str = "f16f8") -> torch.Tensor:
     """Input gradient of the first layer from a planar gradient (wsu_conv3x3_first_pl_bwd_data): g planar (N, C/16, 3, H, W, 4), w (C, cin, 3, 3)
     -> dx (N, cin, H, W) fp32 in g's scale."""
@@ -1318,40 +1339,84 @@ def u8_to_unit(x_u8: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _pair_batch_args(who: str, planes_u8: torch.Tensor, idx_in, idx_cov, op):
+    """Validation shared by pair_batch and pair_batch_planes -> (files, h, w, n, device block [idx_in int32 | idx_cov int32 | op uint8] or None
+    for n == 0).  ValueError for an index outside [0, files), an op outside 0..7 or an op >= 4 on non-square planes; one upload."""
+    _dev_check(planes_u8)
+    if planes_u8.dim() != 3 or planes_u8.dtype != torch.uint8:
+        raise ValueError(f"{who}: planes_u8 must be a (files,H,W) uint8 tensor")
+    files, h, w = planes_u8.shape
+    ii, ic, o = (np.asarray(v).reshape(-1) for v in (idx_in, idx_cov, op))
+    n = ii.shape[0]
+    if ic.shape[0] != n or o.shape[0] != n:
+        raise ValueError(f"{who}: {n} input indices, {ic.shape[0]} cover indices and {o.shape[0]} ops")
+    if n == 0:
+        return files, h, w, 0, None
+    for name, v in (("idx_in", ii), ("idx_cov", ic)):
+        if not np.issubdtype(v.dtype, np.integer) or v.min() < 0 or v.max() >= files:
+            raise ValueError(f"{who}: {name} outside [0, {files})")
+    if not np.issubdtype(o.dtype, np.integer) or o.min() < 0 or o.max() > 7:
+        raise ValueError(f"{who}: op outside 0..7")
+    if h != w and o.max() >= 4:
+        raise ValueError(f"{who}: transposing ops (op >= 4) need square planes, got {h}x{w}")
+    host = np.empty(9 * n, dtype=np.uint8)
+    host[:4 * n].view(np.int32)[:] = ii
+    host[4 * n:8 * n].view(np.int32)[:] = ic
+    host[8 * n:] = o
+    return files, h, w, n, torch.from_numpy(host).to(planes_u8.device)
+
+
 def pair_batch(planes_u8: torch.Tensor, idx_in, idx_cov, op) -> Tuple[torch.Tensor, torch.Tensor]:
     """One training batch in one launch (wsu_pair_batch_f32): planes_u8 (files,H,W) uint8 on the device; idx_in, idx_cov, op: HOST sequences
     or arrays, one entry per sample -> (inputs, covers), both (n,1,H,W) fp32 with inputs[s] = D(op[s])(planes[idx_in[s]]) / 255 and
     covers[s] = D(op[s])(planes[idx_cov[s]]) / 255.  op: bit 0 mirrors the columns, bit 1 the rows, bit 2 transposes last (include/wsu.h).
     ValueError for an index outside [0, files), an op outside 0..7 or an op >= 4 on non-square planes; the three arrays go up in one copy."""
     lib = _lib.load()
-    _dev_check(planes_u8)
-    if planes_u8.dim() != 3 or planes_u8.dtype != torch.uint8:
-        raise ValueError("pair_batch: planes_u8 must be a (files,H,W) uint8 tensor")
-    files, h, w = planes_u8.shape
-    ii, ic, o = (np.asarray(v).reshape(-1) for v in (idx_in, idx_cov, op))
-    n = ii.shape[0]
-    if ic.shape[0] != n or o.shape[0] != n:
-        raise ValueError(f"pair_batch: {n} input indices, {ic.shape[0]} cover indices and {o.shape[0]} ops")
+    files, h, w, n, args = _pair_batch_args("pair_batch", planes_u8, idx_in, idx_cov, op)
     inputs = torch.empty((n, 1, h, w), dtype=torch.float32, device=planes_u8.device)
     covers = torch.empty((n, 1, h, w), dtype=torch.float32, device=planes_u8.device)
     if n == 0:
         return inputs, covers
-    for name, v in (("idx_in", ii), ("idx_cov", ic)):
-        if not np.issubdtype(v.dtype, np.integer) or v.min() < 0 or v.max() >= files:
-            raise ValueError(f"pair_batch: {name} outside [0, {files})")
-    if not np.issubdtype(o.dtype, np.integer) or o.min() < 0 or o.max() > 7:
-        raise ValueError("pair_batch: op outside 0..7")
-    if h != w and o.max() >= 4:
-        raise ValueError(f"pair_batch: transposing ops (op >= 4) need square planes, got {h}x{w}")
-    host = np.empty(9 * n, dtype=np.uint8)                              # [idx_in int32 | idx_cov int32 | op uint8]
-    host[:4 * n].view(np.int32)[:] = ii
-    host[4 * n:8 * n].view(np.int32)[:] = ic
-    host[8 * n:] = o
-    args = torch.from_numpy(host).to(planes_u8.device)
     p = args.data_ptr()
     check(lib.wsu_pair_batch_f32(planes_u8.data_ptr(), files, h, w, p, p + 4 * n, p + 8 * n, n, int(h == w), inputs.data_ptr(),
                                  covers.data_ptr(), _stream()), "wsu_pair_batch_f32")
     return inputs, covers
+
+
+def side_plane_count(parity: bool = False, demosaic: bool = False) -> int:
+    """Planes of a network input with the given side information: the image, the parity plane, the three demosaic planes."""
+    return 1 + int(bool(parity)) + 3 * int(bool(demosaic))
+
+
+def _pair_batch_planes(planes_u8: torch.Tensor, idx_in, idx_cov, op, side: int, want_covers: bool):
+    lib = _lib.load()
+    if not 0 <= int(side) <= 3:
+        raise ValueError(f"pair_batch_planes: side={side} outside 0..3")
+    files, h, w, n, args = _pair_batch_args("pair_batch_planes", planes_u8, idx_in, idx_cov if want_covers else idx_in, op)
+    inputs = torch.empty((n, side_plane_count(side & 1, side & 2), h, w), dtype=torch.float32, device=planes_u8.device)
+    covers = torch.empty((n, 1, h, w), dtype=torch.float32, device=planes_u8.device) if want_covers else None
+    if n == 0:
+        return inputs, covers
+    p = args.data_ptr()
+    check(lib.wsu_pair_batch_planes_f32(planes_u8.data_ptr(), files, h, w, p, p + 4 * n if want_covers else None, p + 8 * n, n, int(h == w),
+                                        int(side), inputs.data_ptr(), _ptr(covers), _stream()), "wsu_pair_batch_planes_f32")
+    return inputs, covers
+
+
+def pair_batch_planes(planes_u8: torch.Tensor, idx_in, idx_cov, op, parity: bool = False, demosaic: bool = False):
+    """ops.pair_batch with side-information planes behind the image, still one launch (wsu_pair_batch_planes_f32): inputs (n,P,H,W) with
+    P = 1 + parity + 3 * demosaic planes in the reference's transform order -- image / 255, the LSB plane (ParityOracle), the R, G, B site
+    indicators of the RGGB grid (DemosaicOracle) -- and covers (n,1,H,W).  The side planes are functions of the SOURCE pixel, i.e. they are
+    transformed with the image as the reference's are (include/wsu.h).  Plane 0 and covers are ops.pair_batch's, bit for bit; so is the
+    validation.  idx_cov=None: no covers are made (returns (inputs, None))."""
+    return _pair_batch_planes(planes_u8, idx_in, idx_cov, op, int(bool(parity)) + 2 * int(bool(demosaic)), idx_cov is not None)
+
+
+def side_planes(x_u8: torch.Tensor, parity: bool, demosaic: bool) -> torch.Tensor:
+    """(N,H,W) uint8 device planes -> the network input (N,P,H,W) fp32 with the side-information planes (pair_batch_planes with identity
+    indices, op 0 and no covers output)."""
+    n = x_u8.shape[0]
+    return pair_batch_planes(x_u8, np.arange(n, dtype=np.int32), None, np.zeros(n, dtype=np.uint8), parity, demosaic)[0]
 
 
 # ---- backward ops (fp32 storage; g = pre-activation gradient, NHWC) -------------------------------------

@@ -35,10 +35,17 @@ DEFAULTS: typing.Dict[str, typing.Any] = {
     # the published configs' augmentation and payload keys (data/pairs.py): random flips / rot90 per training pair; a list of payloads and / or
     # methods of which every pair draws one per epoch.  A list that is not null overrides `alpha` / `stego_method`.
     "post_flip": False, "post_rotate": False, "alphas": None, "stego_methods": None,
+    # side-information planes behind the image (data/pairs.py; the reference's ParityOracle; `demosaic_oracle` above is its DemosaicOracle)
+    "parity_oracle": False,
 }
 # written to config.json only when set, so that the config file of every run that does not use them is what it was
-OPTIONAL_KEYS = ("simulate_stego", "post_flip", "post_rotate", "alphas", "stego_methods")
+OPTIONAL_KEYS = ("simulate_stego", "post_flip", "post_rotate", "alphas", "stego_methods", "parity_oracle")
 LIST_FLAGS = {"alphas": float, "stego_methods": str}
+# Whether a model with side-information planes trains on the planar path (UNet.train_planes_planar) or on the fp32-storage fallback.
+# Rule: True only if, with the two alternating three times in one process (tools/bench_side_planes.py: unet_2, batch 16 at 512x512, 5 planes,
+# L1WS, windows of 20 steps), the slowest planar window beats the fastest fallback window.
+# Measured on one MI355X (profiles/r19/README.md): planar 20.11 / 20.18 / 20.15 ms per step, fallback 32.28 / 32.35 / 32.49 ms -> True.
+PLANES_PLANAR = True
 
 
 def run_config(args: typing.Dict[str, typing.Any]) -> typing.Dict[str, typing.Any]:
@@ -59,6 +66,11 @@ def payload_args(args: typing.Dict[str, typing.Any]):
     if args.get("alphas") is not None:
         return methods, [float(a) for a in args["alphas"]]
     return methods, None if args["alpha"] is None else float(args["alpha"])
+
+
+def input_planes(args: typing.Dict[str, typing.Any]) -> int:
+    """Planes of the network input a run's config asks for: the image, + 1 with `parity_oracle`, + 3 with `demosaic_oracle`."""
+    return 1 + int(bool(args.get("parity_oracle"))) + 3 * int(bool(args.get("demosaic_oracle")))
 
 
 def train(args: typing.Dict[str, typing.Any]) -> float:
@@ -87,8 +99,11 @@ def train(args: typing.Dict[str, typing.Any]) -> float:
 
     if args["seed"]:
         torch.manual_seed(int(args["seed"]))
-    model = get_model(args["network"], in_channels=1, out_channels=1, channel=args["channel"],
+    sides = (bool(args["parity_oracle"]), bool(args["demosaic_oracle"]))
+    model = get_model(args["network"], in_channels=input_planes(args), out_channels=1, channel=args["channel"],
                       drop_rate=args["drop_rate"], mode=args["mode"]).to(dev)    # 0.0 still builds the (identity) dropout, like the reference
+    model.side_planes = sides
+    model.train_planes_planar = PLANES_PLANAR and any(sides)
     if args["train_mode"]:
         model.train_mode = args["train_mode"]
     if model.input_dropout is not None:
@@ -100,7 +115,7 @@ def train(args: typing.Dict[str, typing.Any]) -> float:
         resume(model, resume_dir, dev)
 
     kw = dict(covers_only=bool(args["covers_only"]), rank=rank, world=world, device=dev, take_num_images=args["take_num_images"],
-              simulate=bool(args["simulate_stego"]))
+              simulate=bool(args["simulate_stego"]), parity_oracle=sides[0], demosaic_oracle=sides[1])
     per_rank = args["batch_size"] // world
     # augmentation: the training loader only (the validation loader is never reshuffled either: its payload draw is the same every epoch)
     tr_loader = PairLoader(args["dataset"], args["tr_csv"], stego, alpha, per_rank, shuffle=True, seed=int(args["seed"] or 0),
@@ -114,7 +129,8 @@ def train(args: typing.Dict[str, typing.Any]) -> float:
     return best
 
 
-def main(argv=None) -> None:
+def parse_args(argv=None) -> typing.Dict[str, typing.Any]:
+    """The command line (and the config file it names) as the dict `train` takes: the keys of DEFAULTS that were given."""
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--config", help="a published run's config.json; explicit flags override its keys")
     for key, val in DEFAULTS.items():
@@ -141,7 +157,11 @@ def main(argv=None) -> None:
             args[key] = int(args[key])
     if not args.get("dataset"):
         ap.error("--dataset is required (directory with images*/files.csv, stego*/files.csv and the split CSVs)")
-    train(args)
+    return args
+
+
+def main(argv=None) -> None:
+    train(parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -126,11 +126,19 @@ class Trainer:
             with open(self.out_dir / "config.json", "w") as f:
                 json.dump(self.config, f, indent=4, sort_keys=True)
 
+    @staticmethod
+    def image_plane(inputs: torch.Tensor) -> torch.Tensor:
+        """Plane 0 of the network input as (n,1,H,W): the stego image the WS term, the L1 term and the meters are computed from.  A contiguous
+        copy when the input carries side-information planes behind it (data/pairs.py), the tensor itself otherwise.  With more than one plane
+        the reference's `WSLoss` would broadcast the single-plane prediction against EVERY input plane; that is an accident of an unpublished
+        driver, not a definition of the loss, and is not reproduced: the side planes are seen by the model alone."""
+        return inputs if inputs.shape[1] == 1 else inputs[:, :1].contiguous()
+
     # ---- one optimisation step on this rank's shard of the global batch --------------------------------
     def train_step(self, inputs: torch.Tensor, covers: torch.Tensor, alphas: torch.Tensor):
         self.opt.zero_grad()
         outputs = self.model(inputs)
-        loss = self.criterion(outputs, (covers, alphas), inputs)
+        loss = self.criterion(outputs, (covers, alphas), self.image_plane(inputs))
         self._last_l1 = self.criterion.last_parts[0]
         loss.backward()
         scale = parallel.allreduce_flat_(self.opt.flat_grad)             # C1: one 7.45 MB fp32 bucket over xGMI
@@ -143,7 +151,7 @@ class Trainer:
     @torch.no_grad()
     def eval_step(self, inputs, covers, alphas):
         outputs = self.model(inputs)
-        loss, _, parts, _ = ops.l1ws_loss_fwd_bwd(outputs, covers.contiguous(), inputs.contiguous(),
+        loss, _, parts, _ = ops.l1ws_loss_fwd_bwd(outputs, covers.contiguous(), self.image_plane(inputs).contiguous(),
                                                    torch.as_tensor(alphas, dtype=torch.float32, device=outputs.device),
                                                    self.criterion.use_l1, self.criterion.use_ws)
         self._last_l1 = parts[0]
@@ -157,7 +165,7 @@ class Trainer:
             mae = self._last_l1.double()
         else:
             mae = (covers - outputs).abs().mean(dtype=torch.float64)
-        beta = ops.ws_meter_beta(inputs.contiguous(), outputs.contiguous())
+        beta = ops.ws_meter_beta(self.image_plane(inputs).contiguous(), outputs.contiguous())
         ws = (beta.clamp_min(0) - alphas.double() / 2.).abs().mean()
         return torch.stack([loss.detach().double().reshape(()), mae.reshape(()), ws])
 

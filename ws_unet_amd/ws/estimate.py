@@ -78,6 +78,9 @@ def _as_u8_plane(x: np.ndarray) -> np.ndarray:
 
 def _unet_planes(model, x_u8: torch.Tensor, correct_bias: bool):
     """Full-frame network outputs in [0,1] for x and (if needed) for x_bar - x (estimate.py:89,127)."""
+    if correct_bias and any(getattr(model, "side_planes", (False, False))):
+        raise NotImplementedError("bias correction (correct_bias=True, the network applied to x_bar - x) is not defined for a network "
+                                  "whose input contains the parity of that difference image")
     y = unet_plane(model, x_u8)
     with torch.no_grad():
         yb = model(ops.lsb_delta_unit(x_u8)[:, None])[:, 0].contiguous() if correct_bias else None
