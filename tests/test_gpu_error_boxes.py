@@ -1,6 +1,7 @@
 """GPU: the KB-stratified absolute-error box table (K16-K18, ws_unet_amd/error_boxes.py) against the published
 results/prediction/ae_boxes_3.csv and the literal numpy / pandas restatement of the reference's plot_error (tests/boxes_np.py)."""
 import os
+import pathlib
 import shutil
 import subprocess
 import sys
@@ -126,7 +127,7 @@ def test_determinism_and_batch_independence(tmp_path):
         _assert_same(f, frames[0])
     # and the restatement of the same pixels, in fabrika's order
     order = [int(p.stem) for p in error_boxes.fabrika.precovers(iterator=None, convert_to=None)(lambda df, **kw: df)(
-        data, shuffle_seed=12345)["name"].map(lambda s: __import__("pathlib").Path(s))]
+        data, shuffle_seed=12345)["name"].map(pathlib.Path)]
     x = _planes(order)
     res = {name: np.stack([_filter_ae(p, name) for p in x]) for name in ("KB", "AVG")}
     _assert_same(frames[0], boxes_np.table(res, "KB"))

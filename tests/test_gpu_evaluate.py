@@ -9,7 +9,7 @@ from PIL import Image
 
 from conftest import GOLDEN
 from gpu_util import DEV, gpu_model, DEFAULT_MODE
-from ws_unet_amd import evaluate, formula, get_unet_estimator
+from ws_unet_amd import evaluate, formula, get_unet_estimator, per_image, planes, unet_run
 from ws_unet_amd.imread import imread4_f32
 from oracle import evaluate_ref, unet_ref
 
@@ -162,7 +162,7 @@ def test_sharded_dataset_evaluate_and_cli(tmp_path, mode):
         evaluate.main(["--data", str(data), "--model-dir", str(tmp_path / "models"), "--stego-method", "LSBR", "--eval-methods", "LSBR",
                        "--out", str(out2), "--u8-shards", str(tmp_path / "shards")] + (["--mode", mode] if mode else []))
     finally:
-        evaluate.use_u8_shards(None)
+        planes.use_u8_shards(None)
     assert (tmp_path / "shards" / "index.json").exists()
     pd.testing.assert_frame_equal(pd.read_csv(out2), table)
 
@@ -225,7 +225,7 @@ def test_load_state_dict_rearms_the_range_check(caplog):
 
 
 def test_u8_shards_give_the_identical_table(tmp_path):
-    """VERDICT r03 next #7d: the batched evaluate pass fed from pre-decoded uint8 shards (evaluate.write_u8_shards / use_u8_shards) returns the
+    """VERDICT r03 next #7d: the batched evaluate pass fed from pre-decoded uint8 shards (planes.write_u8_shards / use_u8_shards) returns the
     table of the PNG-fed pass, value for value (the planes are the same bytes; src/fabrika.py:85-89 row order)."""
     _make_dataset(tmp_path)
     model = gpu_model(2, "he", None, drop_rate=0.)
@@ -233,11 +233,11 @@ def test_u8_shards_give_the_identical_table(tmp_path):
     st0 = evaluate.predict_unet_stego_batched(tmp_path, model=model, stego_method="LSBR")
     files = [str(tmp_path / n) for n in df0["name"].tolist() + st0["name"].tolist()]
     try:
-        assert evaluate.use_u8_shards(evaluate.write_u8_shards(files, tmp_path / "shards", images_per_shard=4)) == len(files)
+        assert planes.use_u8_shards(planes.write_u8_shards(files, tmp_path / "shards", images_per_shard=4)) == len(files)
         df1 = evaluate.predict_unet_cover_batched(tmp_path, model=model)
         st1 = evaluate.predict_unet_stego_batched(tmp_path, model=model, stego_method="LSBR")
     finally:
-        evaluate.use_u8_shards(None)
+        planes.use_u8_shards(None)
     for a, b in ((df0, df1), (st0, st1)):
         assert a["name"].tolist() == b["name"].tolist()
         np.testing.assert_array_equal(a["beta_hat"].to_numpy(), b["beta_hat"].to_numpy())
@@ -252,8 +252,8 @@ def test_per_image_api_one_readback(tmp_path, caplog):
     per = evaluate.predict_unet_cover(tmp_path, model=model, progress_on=False)
     bat = evaluate.predict_unet_cover_batched(tmp_path, model=model)
     np.testing.assert_allclose(per["beta_hat"].to_numpy(float), bat["beta_hat"].to_numpy(float), atol=2e-5)
-    x = evaluate.load_planes_u8([str(tmp_path / "images" / "1.png")]).to(DEV)
-    b0, l0, tripped = evaluate.predict_u8_one_readback(x, model)
+    x = planes.load_planes_u8([str(tmp_path / "images" / "1.png")]).to(DEV)
+    b0, l0, tripped = unet_run.predict_u8_one_readback(x, model)
     assert not tripped and b0.shape == (1,) and np.float32(b0[0]) == np.float32(per["beta_hat"].iloc[0])
     model._range_flag_tensor(torch.device(DEV)).fill_(1)                   # as if an epilogue had stored a value beyond +-448
     import logging
@@ -274,19 +274,19 @@ def _many_pngs(root, n, seed=77):
 
 def test_per_image_api_rows_ahead_ride_along(tmp_path, monkeypatch):
     """The per-image API (the reference's call pattern, evaluate.py:48,142-149): rows announced ahead whose files are already decoded join the
-    launch of the row that is asked for (at most _MICRO_BATCH images), their statistics wait for their own calls.  Rows, order and numbers are
+    launch of the row that is asked for (at most MICRO_BATCH images), their statistics wait for their own calls.  Rows, order and numbers are
     those of the one-image-per-launch loop, bit for bit; every image is computed exactly once."""
     n = 40
     _many_pngs(tmp_path, n)
     model = gpu_model(2, "he", None, drop_rate=0.)
     sizes = []
-    real = evaluate.predict_u8_batch
-    monkeypatch.setattr(evaluate, "predict_u8_batch", lambda x, m: (sizes.append(int(x.shape[0])), real(x, m))[1])
+    real = unet_run.predict_u8_batch
+    monkeypatch.setattr(unet_run, "predict_u8_batch", lambda x, m: (sizes.append(int(x.shape[0])), real(x, m))[1])
     df = evaluate.predict_unet_cover(tmp_path, model=model, progress_on=False)
-    assert sum(sizes) == n and max(sizes) > 1 and max(sizes) <= evaluate._MICRO_BATCH, sizes
-    assert not evaluate._AHEAD["results"] and not evaluate._AHEAD["pending"] and not evaluate._AHEAD["inflight"]          # nothing left behind
+    assert sum(sizes) == n and max(sizes) > 1 and max(sizes) <= per_image.MICRO_BATCH, sizes
+    assert not per_image.rows_ahead.results and not per_image.rows_ahead.pending and not per_image.rows_ahead.inflight          # nothing left behind
     sizes.clear()
-    monkeypatch.setattr(evaluate, "_MICRO_BATCH", 1)
+    monkeypatch.setattr(per_image, "MICRO_BATCH", 1)
     df1 = evaluate.predict_unet_cover(tmp_path, model=model, progress_on=False)
     assert sizes == [1] * n
     assert df["name"].tolist() == df1["name"].tolist() == [f"images/{i:03d}.png" for i in range(n)]
@@ -302,13 +302,13 @@ def test_rows_computed_ahead_follow_the_file_and_the_model(tmp_path):
     files = [str(tmp_path / "images" / f"{i:03d}.png") for i in range(6)]
     model = gpu_model(2, "he", None, drop_rate=0.)
     plain = [evaluate.predict_unet(f, model) for f in files]                        # nothing announced: one image per launch
-    evaluate._lookahead_reset()
+    per_image.rows_ahead.reset()
     for f in files[1:]:
-        evaluate._lookahead(f)
-    for fut, _ in list(evaluate._AHEAD["pending"].values()):
+        per_image.rows_ahead.announce(f)
+    for fut, _ in list(per_image.rows_ahead.pending.values()):
         fut.result()                                                                # all five decoded
     r0 = evaluate.predict_unet(files[0], model)                                      # ... and computed with row 0
-    assert set(evaluate._AHEAD["results"]) == set(files[1:]) and not evaluate._AHEAD["inflight"] and r0["beta_hat"] == plain[0]["beta_hat"]
+    assert set(per_image.rows_ahead.results) == set(files[1:]) and not per_image.rows_ahead.inflight and r0["beta_hat"] == plain[0]["beta_hat"]
     # file 1 is rewritten before its row comes: its ahead result is dropped, the row is computed from the new file
     Image.fromarray(u8[5]).save(files[1], compress_level=1)
     r1 = evaluate.predict_unet(files[1], model)
@@ -319,6 +319,6 @@ def test_rows_computed_ahead_follow_the_file_and_the_model(tmp_path):
     assert r2["beta_hat"] != plain[2]["beta_hat"]
     # the same model: taken from the cache, same numbers as the plain loop
     r3 = evaluate.predict_unet(files[3], model)
-    assert r3["beta_hat"] == plain[3]["beta_hat"] and r3["l1"] == plain[3]["l1"] and files[3] not in evaluate._AHEAD["results"]
-    evaluate._lookahead_reset()
-    assert not evaluate._AHEAD["results"]
+    assert r3["beta_hat"] == plain[3]["beta_hat"] and r3["l1"] == plain[3]["l1"] and files[3] not in per_image.rows_ahead.results
+    per_image.rows_ahead.reset()
+    assert not per_image.rows_ahead.results

@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from gpu_util import DEV, gpu_model, images01, oracle_forward, planar_h_decode, planar_h_encode
-from ws_unet_amd import evaluate, formula, ops
+from ws_unet_amd import evaluate, formula, ops, unet_run
 from ws_unet_amd.model import get_model
 from ws_unet_amd.model.unet import ENC, dec_names
 from oracle import unet_ref
@@ -313,8 +313,8 @@ def test_evaluate_api(tmp_path):
     arr = np.concatenate([cov, st])
     exact = gpu_model(2, "he", "f32", drop_rate=0.)
     model = gpu_model(2, "he", "f16p", drop_rate=0.)
-    b0, l0 = evaluate.predict_u8_batch(torch.from_numpy(arr).to(DEV), exact)
-    b1, l1 = evaluate.predict_u8_batch(torch.from_numpy(arr).to(DEV), model)
+    b0, l0 = unet_run.predict_u8_batch(torch.from_numpy(arr).to(DEV), exact)
+    b1, l1 = unet_run.predict_u8_batch(torch.from_numpy(arr).to(DEV), model)
     db, dl = (b1 - b0).abs().cpu(), (l1 - l0).abs().cpu()
     print(f"[f16p evaluate] |beta_hat - f32| max {float(db.max()):.2e} mean {float(db.mean()):.2e}; |l1 - f32| max {float(dl.max()):.2e} (l1 ~{float(l0.mean()):.1f})")
     assert float(db.max()) <= 3e-4, float(db.max())                    # measured 1.1e-4 (mean 4.8e-5)

@@ -10,7 +10,7 @@ import torch
 from conftest import GOLDEN
 from gpu_util import DEV, gpu_model
 import hill_np
-from ws_unet_amd import evaluate, filters, formula, hill, ops
+from ws_unet_amd import evaluate, filters, formula, hill, ops, unet_run
 from ws_unet_amd.imread import imread4_u8
 
 pytestmark = pytest.mark.gpu
@@ -135,8 +135,8 @@ def test_unet_error_agrees_with_residual_stats_and_host():
     model = gpu_model(2, "he", "f32", drop_rate=0.)
     u8 = formula.synthetic_images(4, 64, 96, seed=21)
     x_u8 = torch.from_numpy(u8).to(DEV)
-    mae, wmae = evaluate.predict_u8_error_batch(x_u8, model)
-    _, l1 = evaluate.predict_u8_batch(x_u8, model)
+    mae, wmae = unet_run.predict_u8_error_batch(x_u8, model)
+    _, l1 = unet_run.predict_u8_batch(x_u8, model)
     mae, wmae, l1 = mae.cpu().numpy(), wmae.cpu().numpy(), l1.cpu().numpy()
     # both means sum the same float32 |x - fl32(y*255)| terms (wsu_metric.h residual_f32: the product is rounded before the subtraction
     # in K10 and in K14 alike) in fp64, in different fixed orders (K10: 1024 strided threads and one tree; K14: 64 row blocks x 256

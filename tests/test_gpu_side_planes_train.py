@@ -10,7 +10,7 @@ import torch
 
 from conftest import GOLDEN
 from gpu_util import DEV
-from ws_unet_amd import evaluate, formula, ops
+from ws_unet_amd import evaluate, formula, ops, planes, unet_run
 from ws_unet_amd.data.pairs import PairLoader
 from ws_unet_amd.model import get_model
 
@@ -132,10 +132,10 @@ def test_driver_trains_checkpoints_and_evaluates_with_both_oracles(tmp_path):
     model = evaluate.get_pretrained(tmp_path / "runs" / "LSBR", (3,), model_name=runs[0].name)
     assert model.side_planes == (True, True) and model.e11.in_channels == 5
     files = [str(data / "images" / f"{k}.png") for k in COVERS[:3]]
-    x_u8 = evaluate.load_planes_u8(files).to(DEV)
+    x_u8 = planes.load_planes_u8(files).to(DEV)
     with torch.no_grad():
         want = model(ops.side_planes(x_u8, True, True))[:, 0]
-    assert torch.equal(evaluate.unet_plane(model, x_u8), want)
+    assert torch.equal(unet_run.unet_plane(model, x_u8), want)
     est = estimate.UNetEstimator(model)
     batch = estimate.attack_batch(files, [{} for _ in files], channels=(3,), pixel_estimator=est)
     host_kw = dict(imread=imread4_u8, process_image=filters.get_processor_2d((3,)))

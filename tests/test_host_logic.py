@@ -272,32 +272,32 @@ def test_native_png_reader_every_filter_type_and_stream_shape(tmp_path):
 
 
 def test_u8_shards_serve_the_same_planes(tmp_path):
-    """Pre-decoded uint8 shards (evaluate.write_u8_shards / use_u8_shards, SURVEY 8d ".npy covers"): load_planes_u8 returns the bytes of the PNG
+    """Pre-decoded uint8 shards (planes.write_u8_shards / use_u8_shards, SURVEY 8d ".npy covers"): load_planes_u8 returns the bytes of the PNG
     decode; a file rewritten after the shards were made is decoded again instead of served stale; unknown files fall back to the decode."""
     from PIL import Image
-    from ws_unet_amd import evaluate, formula
+    from ws_unet_amd import formula, planes
     u8 = formula.synthetic_images(5, 64, 48, seed=8)
     files = []
     for i in range(5):
         files.append(tmp_path / f"{i}.png")
         Image.fromarray(u8[i]).save(files[-1])
     try:
-        sd = evaluate.write_u8_shards(files[:4], tmp_path / "shards", images_per_shard=3)
+        sd = planes.write_u8_shards(files[:4], tmp_path / "shards", images_per_shard=3)
         assert sorted(p.name for p in sd.iterdir()) == ["index.json", "planes_0000.npy", "planes_0001.npy"]
-        assert evaluate.use_u8_shards(sd) == 4
+        assert planes.use_u8_shards(sd) == 4
         buf = np.zeros((2, 64, 48), np.uint8)
-        assert evaluate._planes_from_shards([str(files[2]), str(files[3])], buf) and np.array_equal(buf, u8[2:4])
-        np.testing.assert_array_equal(evaluate.load_planes_u8([str(f) for f in files[:4]]).numpy(), u8[:4])
-        np.testing.assert_array_equal(evaluate.load_planes_u8([str(files[3]), str(files[4])]).numpy(), u8[3:5])      # one file not indexed: decoded
-        assert not evaluate._planes_from_shards([str(files[3]), str(files[4])], buf)
+        assert planes._planes_from_shards([str(files[2]), str(files[3])], buf) and np.array_equal(buf, u8[2:4])
+        np.testing.assert_array_equal(planes.load_planes_u8([str(f) for f in files[:4]]).numpy(), u8[:4])
+        np.testing.assert_array_equal(planes.load_planes_u8([str(files[3]), str(files[4])]).numpy(), u8[3:5])      # one file not indexed: decoded
+        assert not planes._planes_from_shards([str(files[3]), str(files[4])], buf)
         import os, time
         Image.fromarray(u8[4]).save(files[0])                                     # file 0 now holds image 4
         os.utime(files[0], ns=(time.time_ns(), time.time_ns() + 5_000_000))
-        assert not evaluate._planes_from_shards([str(files[0])], buf[:1])
-        np.testing.assert_array_equal(evaluate.load_planes_u8([str(files[0])]).numpy()[0], u8[4])
+        assert not planes._planes_from_shards([str(files[0])], buf[:1])
+        np.testing.assert_array_equal(planes.load_planes_u8([str(files[0])]).numpy()[0], u8[4])
     finally:
-        evaluate.use_u8_shards(None)
-    b = evaluate.decode_budget([str(f) for f in files[1:]], gpu_images_per_s=3000.0)
+        planes.use_u8_shards(None)
+    b = planes.decode_budget([str(f) for f in files[1:]], gpu_images_per_s=3000.0)
     assert b["decode_ms_per_image_per_thread"] > 0 and b["threads_needed_per_rank"] > 0 and b["usable_cores"] >= 1
 
 
@@ -599,7 +599,8 @@ def test_per_image_api_rows_ride_along_host_logic(tmp_path, monkeypatch):
     order, every image is computed once, a file rewritten after it was announced is recomputed, nothing is left behind -- also when the
     predictor raises in the middle of a pass."""
     from PIL import Image
-    from ws_unet_amd import evaluate
+    from ws_unet_amd import evaluate, per_image, unet_run
+    ahead = per_image.rows_ahead
     n = 30
     rng = np.random.default_rng(3)
     u8 = rng.integers(0, 256, size=(n, 512, 512), dtype=np.uint8)
@@ -619,30 +620,30 @@ def test_per_image_api_rows_ride_along_host_logic(tmp_path, monkeypatch):
         sizes.append(int(x_u8.shape[0]))
         f = x_u8.float()
         return f.mean(dim=(1, 2)), f.amax(dim=(1, 2))
-    monkeypatch.setattr(evaluate, "predict_u8_batch", fake_batch)
-    monkeypatch.setattr(evaluate, "_model_device", lambda m: torch.device("cpu"))
+    monkeypatch.setattr(unet_run, "predict_u8_batch", fake_batch)
+    monkeypatch.setattr(unet_run, "model_device", lambda m: torch.device("cpu"))
     df = evaluate.predict_unet_cover(tmp_path, model=model, progress_on=False)
     assert df["name"].tolist() == [f"images/{i:02d}.png" for i in range(n)]
     np.testing.assert_allclose(df["beta_hat"].to_numpy(float), u8.reshape(n, -1).mean(axis=1), rtol=1e-6)
     np.testing.assert_array_equal(df["l1"].to_numpy(float), u8.reshape(n, -1).max(axis=1).astype(float))
-    assert sum(sizes) == n and max(sizes) <= evaluate._MICRO_BATCH
-    assert not evaluate._AHEAD["results"] and not evaluate._AHEAD["pending"] and not evaluate._AHEAD["inflight"]
+    assert sum(sizes) == n and max(sizes) <= per_image.MICRO_BATCH
+    assert not ahead.results and not ahead.pending and not ahead.inflight
     # a file rewritten between its announcement and its row
     files = [str(tmp_path / "images" / f"{i:02d}.png") for i in range(4)]
-    evaluate._lookahead_reset()
+    ahead.reset()
     for f in files[1:]:
-        evaluate._lookahead(f)
-    for fut, _ in list(evaluate._AHEAD["pending"].values()):
+        ahead.announce(f)
+    for fut, _ in list(ahead.pending.values()):
         fut.result()
     r0 = evaluate.predict_unet(files[0], model)
-    assert float(r0["beta_hat"]) == pytest.approx(u8[0].mean(), rel=1e-6) and set(evaluate._AHEAD["results"]) == set(files[1:])
+    assert float(r0["beta_hat"]) == pytest.approx(u8[0].mean(), rel=1e-6) and set(ahead.results) == set(files[1:])
     Image.fromarray(u8[9]).save(files[1], compress_level=1)
     r1 = evaluate.predict_unet(files[1], model)
     assert float(r1["beta_hat"]) == pytest.approx(u8[9].mean(), rel=1e-6)
     r2 = evaluate.predict_unet(files[2], model)                      # ... the others come from the cache
     k = len(sizes)
     assert float(r2["beta_hat"]) == pytest.approx(u8[2].mean(), rel=1e-6) and len(sizes) == k
-    evaluate._lookahead_reset()
+    ahead.reset()
     # a predictor that raises mid-pass: the next pass starts clean
     calls = {"n": 0}
 
@@ -651,13 +652,105 @@ def test_per_image_api_rows_ride_along_host_logic(tmp_path, monkeypatch):
         if calls["n"] == 2:
             raise RuntimeError("device lost")
         return fake_batch(x_u8, m)
-    monkeypatch.setattr(evaluate, "predict_u8_batch", boom)
+    monkeypatch.setattr(unet_run, "predict_u8_batch", boom)
     with pytest.raises(RuntimeError, match="device lost"):
         evaluate.predict_unet_cover(tmp_path, model=model, progress_on=False)
-    assert not evaluate._AHEAD["results"] and not evaluate._AHEAD["pending"] and not evaluate._AHEAD["inflight"]
-    monkeypatch.setattr(evaluate, "predict_u8_batch", fake_batch)
+    assert not ahead.results and not ahead.pending and not ahead.inflight
+    monkeypatch.setattr(unet_run, "predict_u8_batch", fake_batch)
     df2 = evaluate.predict_unet_cover(tmp_path, model=model, progress_on=False, take_num_images=5)
     np.testing.assert_allclose(df2["beta_hat"].to_numpy(float)[2:], u8.reshape(n, -1).mean(axis=1)[2:5], rtol=1e-6)
+
+
+def _per_image_stub(tmp_path, monkeypatch, n):
+    """n random 512x512 PNGs and the per-image API's device legs replaced as in the test above: -> (u8, files, Stub, launch sizes)."""
+    from PIL import Image
+    from ws_unet_amd import unet_run
+    u8 = np.random.default_rng(5).integers(0, 256, size=(n, 512, 512), dtype=np.uint8)
+    files = [str(tmp_path / f"{i}.png") for i in range(n)]
+    for i, f in enumerate(files):
+        Image.fromarray(u8[i]).save(f, compress_level=1)
+
+    class Stub(torch.nn.Module):
+        mode = "f32"
+        def forward_features(self, x):
+            return x
+    sizes = []
+
+    def fake_batch(x_u8, m):
+        sizes.append(int(x_u8.shape[0]))
+        f = x_u8.float()
+        return f.mean(dim=(1, 2)), f.amax(dim=(1, 2))
+    monkeypatch.setattr(unet_run, "predict_u8_batch", fake_batch)
+    monkeypatch.setattr(unet_run, "model_device", lambda m: torch.device("cpu"))
+    return u8, files, Stub, sizes
+
+
+def test_per_image_api_decode_in_a_reissued_ring_buffer_is_decoded_again(tmp_path, monkeypatch):
+    """A single-image ring of 3 buffers and 5 rows decoded ahead: the two oldest decodes were overwritten by the two newest, and the row asked
+    for first (not announced) takes the third's buffer.  Every row still gets ITS image's numbers, every image is computed once: the rows
+    whose buffers were handed out again are decoded again by their own calls, not served from a buffer that holds another file."""
+    from ws_unet_amd import evaluate, per_image, planes
+    u8, files, Stub, sizes = _per_image_stub(tmp_path, monkeypatch, 6)
+    monkeypatch.setattr(planes, "_NBUF1", 3)
+    monkeypatch.setattr(planes, "_RINGS", {})
+    ahead, model = per_image.rows_ahead, Stub()
+    ahead.reset()
+    try:
+        for f in files[1:]:
+            ahead.announce(f)
+            ahead.pending[f].future.result()                 # one at a time: two decodes at once would write one buffer of so small a ring
+        handouts = [ahead.pending[f].future.result() for f in files[1:]]
+        assert [planes.still_holds(*h) for h in handouts] == [False, False, True, True, True]
+        for i, f in enumerate(files):
+            r = evaluate.predict_unet(f, model)
+            assert float(r["beta_hat"]) == pytest.approx(u8[i].mean(), rel=1e-6) and float(r["l1"]) == float(u8[i].max()), i
+        assert sum(sizes) == 6 and sizes[0] == 3, sizes      # rows 0, 4, 5 in the first launch; 1, 2 and (its buffer went to row 0) 3 on their own
+        assert not ahead.results and not ahead.pending and not ahead.inflight
+    finally:
+        ahead.reset()
+
+
+def test_per_image_api_results_hold_their_model(tmp_path, monkeypatch):
+    """A result computed ahead belongs to the model OBJECT that computed it: the record keeps the model alive (its address cannot pass to a
+    new model while the result waits), another model of the same mode gets a fresh computation, and reset() lets the model go."""
+    import gc
+    import weakref
+    from ws_unet_amd import evaluate, per_image
+    u8, files, Stub, sizes = _per_image_stub(tmp_path, monkeypatch, 4)
+    ahead, model = per_image.rows_ahead, Stub()
+    ahead.reset()
+    try:
+        for f in files[1:]:
+            ahead.announce(f)
+        for d in list(ahead.pending.values()):
+            d.future.result()
+        evaluate.predict_unet(files[0], model)
+        assert set(ahead.results) == set(files[1:]) and sizes == [4]
+        alive = weakref.ref(model)
+        del model
+        gc.collect()
+        assert alive() is not None                           # results are pending for it
+        r1 = evaluate.predict_unet(files[1], Stub())         # same mode, another object: not served from the first model's rows
+        assert sizes == [4, 1] and float(r1["beta_hat"]) == pytest.approx(u8[1].mean(), rel=1e-6)
+        ahead.reset()
+        gc.collect()
+        assert alive() is None
+    finally:
+        ahead.reset()
+
+
+@pytest.mark.parametrize("module, absent", [
+    ("ws_unet_amd.planes", ["pandas", "ws_unet_amd.evaluate", "ws_unet_amd.model", "ws_unet_amd.ops", "ws_unet_amd.fabrika"]),
+    ("ws_unet_amd.ols", ["ws_unet_amd.evaluate", "ws_unet_amd.model"]),
+])
+def test_plane_helpers_do_not_drag_in_the_model_stack(module, absent):
+    """planes is a leaf (torch, numpy, the native reader), and a filter-only driver reaches it without importing evaluate or the model."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    code = f"import sys, {module}; print([m for m in {absent!r} if m in sys.modules])"
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, check=True).stdout
+    assert out.strip() == "[]", out
 
 
 def test_forward_organisation_switches_are_read_at_construction(monkeypatch):

@@ -3,7 +3,7 @@
   * K15 (ops.pair_correlation) at 32 x 512^2 and 8 x 2048^2, with the filter taps evaluated in the kernel (KB) and with a full-frame
     x_hat (a network output), per call by HIP events (ops.KernelTimer) over --reps repetitions;
   * the batched UNet correlation on in-memory planes (unet_2, the default mode, batch 32 x 512^2): correlation_u8_batch (forward of
-    the stego planes + K15 + p-values on the host) against evaluate.predict_u8_batch (forward + WS statistics) on the same planes,
+    the stego planes + K15 + p-values on the host) against unet_run.predict_u8_batch (forward + WS statistics) on the same planes,
     same process, alternating arms.
 Usage: python tools/bench_correlation.py [--reps 50] [--rounds 6] [--steps 20]"""
 import argparse
@@ -16,7 +16,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np
 import torch
 
-from ws_unet_amd import correlation, evaluate, filters, formula, ops
+from ws_unet_amd import correlation, filters, formula, ops, unet_run
 from ws_unet_amd.model import get_model
 
 ap = argparse.ArgumentParser()
@@ -57,7 +57,7 @@ m.load_state_dict({k: torch.from_numpy(v) for k, v in formula.formula_state_dict
 m = m.cuda()
 xc = torch.from_numpy(formula.synthetic_images(32, 512, 512, seed=8)).cuda()
 xs = lsbr(xc, 2)
-arms = {"predict_u8_batch": lambda: evaluate.predict_u8_batch(xs, m)[0].cpu(),
+arms = {"predict_u8_batch": lambda: unet_run.predict_u8_batch(xs, m)[0].cpu(),
         "correlation_u8_batch": lambda: correlation.correlation_u8_batch(xc, xs, m)}
 for f in arms.values():
     for _ in range(3):

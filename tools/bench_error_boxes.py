@@ -3,7 +3,7 @@
   * error_boxes.run over a data set of the five fixture covers (512^2) listed over and over to --images rows (fabrika order, PNG
     decode on the native reader beside the GPU work), with the filters only (KB, AVG) and with one UNet added (unet_2, formula
     weights, the default inference mode): images/s, median of --rounds;
-  * evaluate.predict_u8_batch on in-memory planes (batch 32 x 512^2), same process, same model: images/s;
+  * unet_run.predict_u8_batch on in-memory planes (batch 32 x 512^2), same process, same model: images/s;
   * K16-K18 per call by HIP events (ops.KernelTimer) inside one run of each leg.
 Usage: python tools/bench_error_boxes.py [--images 2048] [--rounds 3] [--steps 20]"""
 import argparse
@@ -19,7 +19,7 @@ sys.path.insert(0, str(ROOT))
 import numpy as np
 import torch
 
-from ws_unet_amd import error_boxes, evaluate, formula, ops
+from ws_unet_amd import error_boxes, formula, ops, unet_run
 from ws_unet_amd.model import get_model
 
 ap = argparse.ArgumentParser()
@@ -45,7 +45,7 @@ x = torch.from_numpy(formula.synthetic_images(32, 512, 512, seed=8)).cuda()
 for name, preds in legs.items():                                # warm-up (decoder pools, allocator, first-forward checks)
     error_boxes.run(tmp, preds, split=None, take_num_images=64)
 for _ in range(3):
-    evaluate.predict_u8_batch(x, m)[0].cpu()
+    unet_run.predict_u8_batch(x, m)[0].cpu()
 torch.cuda.synchronize()
 
 rates = {k: [] for k in list(legs) + ["predict_u8_batch"]}
@@ -58,7 +58,7 @@ for r in range(a.rounds):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        evaluate.predict_u8_batch(x, m)[0].cpu()
+        unet_run.predict_u8_batch(x, m)[0].cpu()
     torch.cuda.synchronize()
     rates["predict_u8_batch"].append(32 * a.steps / (time.perf_counter() - t0))
 out["images_per_s"] = {k: round(float(np.median(v)), 1) for k, v in rates.items()}

@@ -7,13 +7,14 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np
 import torch
 from PIL import Image
-from ws_unet_amd import evaluate, fabrika, formula
+from ws_unet_amd import evaluate, fabrika, formula, planes, unet_run
 from ws_unet_amd.model import get_model
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--images", type=int, default=256)
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--mode", default="f16f4p")
+ap.add_argument("--per-image-rows", type=int, default=256, help="rows of the per-image leg (raise it for a leg that times long enough to compare)")
 a = ap.parse_args()
 root = Path(tempfile.mkdtemp())
 (root / "images").mkdir()
@@ -31,14 +32,13 @@ batched = fabrika.precovers(iterator="batched", convert_to="pandas", ignore_miss
 batched(root, model=m, take_num_images=a.batch)                 # warm-up
 torch.cuda.synchronize()
 t0 = time.perf_counter(); dfb = batched(root, model=m); torch.cuda.synchronize(); t_b = time.perf_counter() - t0
-import os
-n1 = min(a.images, 256)
+n1 = min(a.images, a.per_image_rows)
 evaluate.predict_unet_cover(root, model=m, take_num_images=8, progress_on=False)            # warm-up: range look, decode threads
 t0 = time.perf_counter(); df1 = evaluate.predict_unet_cover(root, model=m, take_num_images=n1, progress_on=False); torch.cuda.synchronize(); t_1 = time.perf_counter() - t0
-xd = evaluate.load_planes_u8([str(root / "images" / "0.png")]).to("cuda")
+xd = planes.load_planes_u8([str(root / "images" / "0.png")]).to("cuda")
 t0 = time.perf_counter()
 for _ in range(200):
-    evaluate.predict_u8_one_readback(xd, m)
+    unet_run.predict_u8_one_readback(xd, m)
 t_e = (time.perf_counter() - t0) / 200
 t0 = time.perf_counter()
 for i in range(min(a.images, 64)):
@@ -47,21 +47,21 @@ t_dec = (time.perf_counter() - t0) / min(a.images, 64)            # PIL on one t
 err = float(np.abs(dfb["beta_hat"].to_numpy(float)[:n1] - df1["beta_hat"].to_numpy(float)).max())
 # the host budget of the file-fed pass (VERDICT r03 next #7a) and the same pass fed from pre-decoded uint8 shards (#7d)
 files = [str(root / "images" / f"{i}.png") for i in range(a.images)]
-x = evaluate.load_planes_u8(files[:a.batch]).to("cuda")
+x = planes.load_planes_u8(files[:a.batch]).to("cuda")
 for _ in range(3):
-    evaluate.predict_u8_batch(x, m)
+    unet_run.predict_u8_batch(x, m)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(10):
-    evaluate.predict_u8_batch(x, m)
+    unet_run.predict_u8_batch(x, m)
 torch.cuda.synchronize()
 gpu_rate = 10 * a.batch / (time.perf_counter() - t0)             # images/s of the device side alone (planes resident)
-budget = evaluate.decode_budget(files, gpu_images_per_s=gpu_rate, sample=32)
-evaluate.use_u8_shards(evaluate.write_u8_shards(files, root / "shards"))
+budget = planes.decode_budget(files, gpu_images_per_s=gpu_rate, sample=32)
+planes.use_u8_shards(planes.write_u8_shards(files, root / "shards"))
 batched(root, model=m, take_num_images=a.batch)
 torch.cuda.synchronize()
 t0 = time.perf_counter(); dfs = batched(root, model=m); torch.cuda.synchronize(); t_s = time.perf_counter() - t0
-evaluate.use_u8_shards(None)
+planes.use_u8_shards(None)
 same = bool(np.array_equal(dfs["beta_hat"].to_numpy(), dfb["beta_hat"].to_numpy()) and np.array_equal(dfs["l1"].to_numpy(), dfb["l1"].to_numpy()))
 print(json.dumps({"metric": "evaluate loop images/s (PNG on disk -> beta_hat, l1)", "mode": a.mode, "images": a.images,
                   "batched_images_per_s": a.images / t_b, "per_image_api_images_per_s": n1 / t_1, "one_image_call_ms_resident_plane": t_e * 1e3,

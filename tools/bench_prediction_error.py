@@ -15,7 +15,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np
 import torch
 
-from ws_unet_amd import evaluate, formula, ops
+from ws_unet_amd import formula, ops, unet_run
 from ws_unet_amd.model import get_model
 
 ap = argparse.ArgumentParser()
@@ -47,7 +47,7 @@ m = get_model("unet_2", in_channels=1, out_channels=1, channel=[0], drop_rate=No
 m.load_state_dict({k: torch.from_numpy(v) for k, v in formula.formula_state_dict(2, "he").items()})
 m = m.cuda()
 x = torch.from_numpy(formula.synthetic_images(32, 512, 512, seed=8)).cuda()
-arms = {"without_wmae": lambda: evaluate.predict_u8_batch(x, m), "with_wmae": lambda: evaluate.predict_u8_error_batch(x, m)}
+arms = {"without_wmae": lambda: unet_run.predict_u8_batch(x, m), "with_wmae": lambda: unet_run.predict_u8_error_batch(x, m)}
 for f in arms.values():
     for _ in range(3):
         f()

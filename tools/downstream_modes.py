@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from ws_unet_amd import evaluate, formula
+from ws_unet_amd import formula, unet_run
 from ws_unet_amd.model import get_model
 
 if __name__ == "__main__":
@@ -24,7 +24,7 @@ if __name__ == "__main__":
         rows = []
         for arr in (cov, st):
             for i in range(0, n, 32):
-                b, l = evaluate.predict_u8_batch(torch.from_numpy(arr[i:i + 32]).to(dev), m)
+                b, l = unet_run.predict_u8_batch(torch.from_numpy(arr[i:i + 32]).to(dev), m)
                 rows.append(torch.stack([b, l], 1).cpu())
         res[mode] = torch.cat(rows).double().numpy()
     ref = res["f32"]

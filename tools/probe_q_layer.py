@@ -1,7 +1,7 @@
 """Timing of single conv3x3_q layers (planar Q tensors, the default inference mode's 3x3 conv) on random and on all-zero operands, optionally with
 an alternative build of libwsu (WSU_LIB=...): the power-management measurement of profiles/r03 for the round-4 kernel.
 python tools/probe_q_layer.py [--zeros]"""
-import sys, time
+import os, sys, time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent)); sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tests"))
 import torch
@@ -25,4 +25,4 @@ for (n, s, c1, c2, cout, pool) in [(32, 512, 64, 0, 64, True), (32, 256, 128, 0,
     e1.record(); torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / 20 * 1e3
     fl = 2.0 * 9 * (c1 + c2) * cout * n * s * s
-    print(f"{Path(_lib.LIB_PATH if not __import__('os').environ.get('WSU_LIB') else __import__('os').environ['WSU_LIB']).name}{' zeros' if ZEROS else ''}: {c1}+{c2}->{cout} @{s} pool={pool}: {us:8.1f} us  {fl / us / 1e6:7.1f} TFLOP/s = {fl / us / 1e6 / 2500:.3f} of the f16 peak", flush=True)
+    print(f"{Path(os.environ.get('WSU_LIB') or _lib.LIB_PATH).name}{' zeros' if ZEROS else ''}: {c1}+{c2}->{cout} @{s} pool={pool}: {us:8.1f} us  {fl / us / 1e6:7.1f} TFLOP/s = {fl / us / 1e6 / 2500:.3f} of the f16 peak", flush=True)

@@ -5,7 +5,7 @@ import sys, time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
-from ws_unet_amd import evaluate, formula, ops
+from ws_unet_amd import formula, ops, unet_run
 from ws_unet_amd.model import get_model
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -36,12 +36,12 @@ def fwd():
 
 
 def chunk_device():
-    return evaluate.predict_u8_batch(xd, m)
+    return unet_run.predict_u8_batch(xd, m)
 
 
 def chunk_with_upload():
     x = pin.to("cuda", non_blocking=True)
-    b, l = evaluate.predict_u8_batch(x, m)
+    b, l = unet_run.predict_u8_batch(x, m)
     return torch.stack([b, l], dim=1)
 
 

@@ -28,7 +28,8 @@ import typing
 
 import numpy as np
 
-from . import fabrika, filters
+from . import fabrika, filters, unet_run
+from .planes import load_planes_u8, upload_planes
 
 MODEL_NAMES = ("1", "AVG9", "AVG", "KB")
 UNET_STEGO_METHODS = ("dropout", "LSBR", "HILLR")
@@ -131,7 +132,7 @@ def correlation_u8_batch(xc_u8, xs_u8, predictor) -> typing.Tuple[np.ndarray, np
         where it is (512 x 512 planes only: the reference's CenterCrop(512) would change the geometry);
       * any other callable: the reference's call pattern, `predictor(x_s)` per image on the host with x_s (H,W,1) float32 in
         0..255, returning (H-2,W-2[,1]); the predictions are uploaded as float32."""
-    from . import evaluate, ops
+    from . import ops
     from .ws.estimate import unet_model_of
     if xc_u8.dim() != 3 or xc_u8.shape != xs_u8.shape:
         raise ValueError(f"cover and stego batches differ in shape: {tuple(xc_u8.shape)} and {tuple(xs_u8.shape)}")
@@ -140,8 +141,8 @@ def correlation_u8_batch(xc_u8, xs_u8, predictor) -> typing.Tuple[np.ndarray, np
     if isinstance(predictor, filters.FilterEstimator):
         cor = ops.pair_correlation(xc_u8, xs_u8, pixel_filter=np.asarray(predictor.kernel)[..., ::-1])
     elif model is not None:
-        evaluate.check_unet_geometry((h, w), "the UNet predictor")
-        cor = evaluate.range_retry(model, lambda: ops.pair_correlation(xc_u8, xs_u8, evaluate.unet_plane(model, xs_u8), hat_full=True,
+        unet_run.check_unet_geometry((h, w), "the UNet predictor")
+        cor = unet_run.range_retry(model, lambda: ops.pair_correlation(xc_u8, xs_u8, unet_run.unet_plane(model, xs_u8), hat_full=True,
                                                                       hat_scale=255.))
     else:
         import torch
@@ -186,13 +187,12 @@ def _row(name_c, name_s, cor, p) -> dict:
 
 def _pair_one(fname, name_c, name_s, predictor, **_kw) -> dict:
     import torch
-    from .evaluate import _model_device
     from .ws.estimate import unet_model_of
     path_c, path_s = _pair_paths(fname, name_c, name_s)
     x_c, x_s = _read_gray(path_c), _read_gray(path_s)
     if x_c.shape != x_s.shape:
         raise ValueError(f"cover {path_c} is {x_c.shape}, stego {path_s} is {x_s.shape}")
-    dev = _model_device(unet_model_of(predictor))
+    dev = unet_run.model_device(unet_model_of(predictor))
     cor, p = correlation_u8_batch(torch.from_numpy(x_c)[None].to(dev), torch.from_numpy(x_s)[None].to(dev), predictor)
     return _row(name_c, name_s, cor[0], p[0])
 
@@ -203,7 +203,6 @@ _pairs_python = fabrika.cover_stego_spatial(iterator="python", convert_to="panda
 def _chunk_planes(fnames, kws):
     """Cover and stego planes of a chunk as two (N,H,W) uint8 host tensors (native batched decode into pinned buffers), or None
     when the chunk's images differ in shape."""
-    from .evaluate import load_planes_u8
     paths = [_pair_paths(f, kw["name_c"], kw["name_s"]) for f, kw in zip(fnames, kws)]
     for pc, ps in paths:
         _check_gray(pc)
@@ -217,13 +216,12 @@ def _chunk_planes(fnames, kws):
 
 def _pair_chunk(fnames, kws, prefetched=None) -> typing.List[dict]:
     """_pair_one for a chunk of pairs (fabrika iterator='batched'): one upload and one K15 launch chain for the whole chunk."""
-    from .evaluate import _model_device, upload_planes
     from .ws.estimate import unet_model_of
     planes = prefetched if prefetched is not None else _chunk_planes(fnames, kws)
     if planes is None:                                              # ragged chunk
         return [_pair_one(f, **kw) for f, kw in zip(fnames, kws)]
     predictor = kws[0]["predictor"]
-    xc, xs = upload_planes(planes, _model_device(unet_model_of(predictor)))
+    xc, xs = upload_planes(planes, unet_run.model_device(unet_model_of(predictor)))
     cor, p = correlation_u8_batch(xc, xs, predictor)
     return [_row(kw["name_c"], kw["name_s"], cor[i], p[i]) for i, kw in enumerate(kws)]
 

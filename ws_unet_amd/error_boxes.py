@@ -31,9 +31,10 @@ import typing
 
 import numpy as np
 
-from . import fabrika, filters
+from . import fabrika, filters, unet_run
 from .hill import quantile_index
 from .imread import imread4_u8
+from .planes import plane_groups, upload_planes
 
 EDGE_VALUES = (.5, 1.5, 3.5, 7.5)
 STATS = ("min", "q_25_iqr", "q_25", "q_50", "q_75", "q_75_iqr", "max")
@@ -216,12 +217,12 @@ def _resolve(name: str, spec, mode) -> _Pred:
 
 def _keys_of(x, pred: _Pred, keys_row, offset: int, flag, idx) -> None:
     """K16 for one predictor over (N,H,W) device planes."""
-    from . import evaluate, ops
+    from . import ops
     if pred.taps is not None:
         ops.ae_values(x, keys_row, offset, flag, pixel_filter=pred.taps, idx=idx)
         return
-    evaluate.check_unet_geometry(x.shape[1:], f"predictor {pred.name}: the UNet")
-    ops.ae_values(x, keys_row, offset, flag, x_hat=evaluate.unet_plane(pred.model, x), hat_scale=255., idx=idx)
+    unet_run.check_unet_geometry(x.shape[1:], f"predictor {pred.name}: the UNet")
+    ops.ae_values(x, keys_row, offset, flag, x_hat=unet_run.unet_plane(pred.model, x), hat_scale=255., idx=idx)
 
 
 def _indices(fnames, count: int, num_pixels, device):
@@ -242,9 +243,7 @@ def _check_flags(flags, preds) -> None:
 
 def _groups(fnames, hw):
     """Decoded Y planes of a chunk: [(host (n,H,W) uint8 tensor, fnames)], one group for the chunk or one per image when ragged."""
-    from .evaluate import load_planes_u8
-    planes = load_planes_u8(fnames)
-    groups = [(planes, list(fnames))] if planes is not None else [(load_planes_u8([f]), [f]) for f in fnames]
+    groups = plane_groups(fnames)
     for (g, fs), i in zip(groups, np.cumsum([0] + [len(f) for _, f in groups])[:-1]):
         if tuple(g.shape[1:]) != tuple(hw[i]):
             raise ValueError(f"{fs[0]}: decoded as {tuple(g.shape[1:])}, files.csv says {tuple(hw[i])}")
@@ -255,7 +254,6 @@ def _fill(fnames, hw, per, preds, rows, keys, flags, num_pixels, batch_size, pro
     """Stream the files through the batched u8 reader (decode of chunk k+1 beside the GPU work on chunk k) and write the keys of
     `preds` into keys[rows[p]] at each image's offset."""
     import torch
-    from .evaluate import upload_planes
     chunks = [range(k, min(k + batch_size, len(fnames))) for k in range(0, len(fnames), batch_size)]
     offsets = np.concatenate([[0], np.cumsum(per)])
 
@@ -283,7 +281,6 @@ def run(data_path, predictors: typing.Mapping[str, typing.Any] = None, anchor: s
     K18.  `predictors`: name -> spec (see _resolve; default KB and AVG).  num_pixels: `subset_residual`'s per-image draws.
     iterator='batched' decodes and runs `batch_size` images at a time; 'python' one image at a time.  Same table either way."""
     import torch
-    from . import evaluate
     predictors = {"KB": "KB", "AVG": "AVG"} if predictors is None else dict(predictors)
     if anchor not in predictors:
         raise ValueError(f"anchor {anchor!r} is not among the predictors {list(predictors)}")
@@ -306,7 +303,7 @@ def run(data_path, predictors: typing.Mapping[str, typing.Any] = None, anchor: s
     flags = torch.zeros(len(preds), dtype=torch.int32, device="cuda")
     bs = batch_size if iterator == "batched" else 1
     _fill(fnames, hw, per, preds, list(range(len(preds))), keys, flags, num_pixels, bs, progress_on)
-    redo = [p for p, pred in enumerate(preds) if pred.model is not None and evaluate.range_fallback(pred.model)]
+    redo = [p for p, pred in enumerate(preds) if pred.model is not None and unet_run.range_fallback(pred.model)]
     if redo:                                                       # a planar forward left its range: that model's keys once more
         flags[redo] = 0                                            # (the overflow may have stored inf in the first pass)
         _fill(fnames, hw, per, [preds[p] for p in redo], redo, keys, flags, num_pixels, bs, progress_on)

@@ -18,7 +18,8 @@ import typing
 import numpy as np
 
 from . import fabrika
-from .imread import imread4_u8, u8_plane
+from .imread import imread4_f32, imread4_u8, u8_plane
+from .planes import load_planes_u8, upload_planes
 
 NAMED_FILTERS = {
     "KB": np.array([[-1], [+2], [-1], [+2], [-1], [+2], [-1], [+2]], dtype="float64") / 4.,
@@ -117,8 +118,8 @@ def _plane_u8(img: np.ndarray, channel: int) -> np.ndarray:
 def _device_error(x_u8_host, filter):
     """(N,H,W) uint8 host planes -> numpy (mae[N], wmae[N]) of the in-kernel filter prediction."""
     import torch
-    from . import evaluate, ops
-    mae, wmae = ops.prediction_error(evaluate.upload_planes(torch.as_tensor(x_u8_host), "cuda"), pixel_filter=filter)
+    from . import ops
+    mae, wmae = ops.prediction_error(upload_planes(torch.as_tensor(x_u8_host), "cuda"), pixel_filter=filter)
     return mae.cpu().numpy(), wmae.cpu().numpy()
 
 
@@ -152,8 +153,6 @@ def _residuals_batch(fnames, kws, *, filter, filter_name, channels, imread=imrea
 
 
 def _chunk_planes(fnames, channels, imread):
-    from .evaluate import load_planes_u8
-    from .imread import imread4_f32
     if tuple(channels) == (3,) and imread in (imread4_u8, imread4_f32):
         return load_planes_u8(fnames, imread4_u8)                  # native batched decode of the Y plane into a pinned buffer
     planes = [_plane_u8(imread(f), channels[0]) for f in fnames]

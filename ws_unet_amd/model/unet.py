@@ -287,7 +287,7 @@ class UNet(nn.Module):
         # planar path took them.  ws_unet_amd.train decides for its own models.
         self.train_planes_planar = False
         # (parity_oracle, demosaic_oracle): the side-information planes this network's input carries behind the image (ops.side_planes);
-        # set by evaluate.get_pretrained and ws_unet_amd.train from the run's config, read by evaluate.unet_plane / infere_single
+        # set by evaluate.get_pretrained and ws_unet_amd.train from the run's config, read by unet_run.unet_plane / evaluate.infere_single
         self.side_planes = (False, False)
         self.train_products = os.environ.get("WSU_TRAIN_PRODUCTS") or "f16"
         ops.products_id(self.train_products)
@@ -388,7 +388,7 @@ class UNet(nn.Module):
                         logging.warning("ws_unet_amd.UNet: activations beyond +-448 in mode 'f16f8p' (the e4m3 residual saturates there); "
                                         "switching this model to mode 'bf16x3s'")
                     self.mode = "bf16x3s"
-                    self._range_switched = True                # (a sharded pass tells the other ranks: evaluate.range_fallback)
+                    self._range_switched = True                # (a sharded pass tells the other ranks: unet_run.range_fallback)
                     return self.forward_features(x, keep, want_logit)
             return res
         if m in PLANAR_MODES:

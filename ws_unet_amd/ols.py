@@ -28,6 +28,7 @@ import pathlib
 import numpy as np
 
 from . import filters
+from .planes import load_planes_u8, plane_groups, upload_planes
 
 COND_MAX = 1e12
 _IU = np.triu_indices(9)
@@ -179,13 +180,10 @@ def fit_dataset(data_dir, split: str = None, take_num_images: int = None, symmet
     read back once.  -> DatasetFit(taps (8,) float64, ok, moments (45,) int64, count = interior pixels summed).  Single process."""
     import torch
     from . import fabrika, ops
-    from .evaluate import load_planes_u8, upload_planes
     total, count = [None], [0]
 
     def chunk(fnames, kws, prefetched=None):
-        planes = prefetched[0] if prefetched is not None else load_planes_u8(fnames)
-        groups = [planes] if planes is not None else [load_planes_u8([f]) for f in fnames]          # a ragged chunk: image by image
-        for g in groups:
+        for g, _ in plane_groups(fnames, prefetched):             # (a ragged chunk: image by image)
             m = ops.ols_moments(upload_planes(g, "cuda")).sum(dim=0)
             total[0] = m if total[0] is None else total[0] + m
             count[0] += g.shape[0] * (g.shape[1] - 2) * (g.shape[2] - 2)

@@ -25,8 +25,9 @@ import numpy as np
 import torch
 
 from .. import fabrika, filters, ols, ops
-from ..evaluate import _decode_pool, _model_device, check_unet_geometry, unet_plane, upload_planes
 from ..imread import imread4_u8, u8_plane
+from ..planes import decode_pool, load_planes_u8, upload_planes
+from ..unet_run import check_unet_geometry, model_device, unet_plane
 
 NAMED_FILTERS = filters.NAMED_FILTERS_2D
 
@@ -53,7 +54,7 @@ class UNetEstimator:
 
 def unet_model_of(predictor):
     """The UNet whose forward a driver runs on the device for this predictor (a UNetEstimator's, or a bare model), or None.
-    (Where a predictor's planes go is evaluate._model_device of it: the UNet's device, the default GPU for None.)"""
+    (Where a predictor's planes go is unet_run.model_device of it: the UNet's device, the default GPU for None.)"""
     if isinstance(predictor, UNetEstimator):
         return predictor.model
     return predictor if isinstance(predictor, torch.nn.Module) else None
@@ -128,7 +129,7 @@ def attack(
     """WS estimate of one image (estimate.py:55-136): returns kw | {beta_hat, channels, weighted, correct_bias}."""
     x = process_image(imread(fname))                         # x_bar = process(x ^ 1) is formed on the device
     try:
-        x_u8 = torch.from_numpy(_as_u8_plane(x))[None].to(_model_device(unet_model_of(pixel_estimator)))
+        x_u8 = torch.from_numpy(_as_u8_plane(x))[None].to(model_device(unet_model_of(pixel_estimator)))
         beta_hat = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=[x])[0].item()
         beta_hat = np.float32(beta_hat)
     except ValueError:                                      # estimate.py:122-123
@@ -164,12 +165,11 @@ def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED
                  weighted=1, imread=imread4_u8, process_image=None, prefetched=None, **_ignored):
     """`attack` for a chunk of files (fabrika iterator='batched'): one result dict per (fname, kw)."""
     if _native_planes_ok(channels, pixel_estimator, imread, process_image):
-        from ..evaluate import load_planes_u8
         u8 = prefetched[0] if prefetched is not None else load_planes_u8(fnames, imread)
         planes = None if u8 is None else [None] * len(fnames)
     else:
         process_image = process_image or filters.get_processor_2d(channels)
-        planes = list(_decode_pool().map(lambda f: process_image(imread(f)), fnames))
+        planes = list(decode_pool().map(lambda f: process_image(imread(f)), fnames))
         u8 = None
         if len({p.shape for p in planes}) != 1:
             planes = None
@@ -180,7 +180,7 @@ def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED
     try:
         if u8 is None:
             u8 = torch.from_numpy(np.stack([_as_u8_plane(p) for p in planes]))
-        x_u8 = upload_planes(u8, _model_device(unet_model_of(pixel_estimator)))
+        x_u8 = upload_planes(u8, model_device(unet_model_of(pixel_estimator)))
         beta = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=planes).cpu().numpy()
     except ValueError:
         beta = [None] * len(fnames)
@@ -195,7 +195,6 @@ def _prefetch_native(fnames, kws):
     k0 = kws[0]
     if not _native_planes_ok(k0["channels"], k0["pixel_estimator"], k0.get("imread", imread4_u8), k0.get("process_image")):
         return None
-    from ..evaluate import load_planes_u8
     return (load_planes_u8(fnames, imread4_u8),)
 
 

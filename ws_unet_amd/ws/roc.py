@@ -32,6 +32,8 @@ import numpy as np
 from .. import fabrika
 from .. import filters as filters_lib
 from ..imread import imread4_u8
+from ..planes import load_planes_u8, upload_planes
+from ..unet_run import model_device
 
 TAUS = np.linspace(0, 1, 501, endpoint=True)       # ascending; the reference walks them reversed
 AUC_COLUMNS = ["stego_method", "model_name", "auc", "p_e", "tau0", "fpr_tau0", "tpr_tau0", "fpr_50", "tpr_50"]
@@ -150,21 +152,19 @@ def roc_table(df_roc):
 # ---- WS scores of every predictor from one decode ------------------------------------------------------------------------------
 
 def _prefetch(fnames, kws):
-    from ..evaluate import load_planes_u8
     return (load_planes_u8(fnames),)
 
 
 def _submit(fnames, clean, *, predictors, prefetched=None):
     """Upload the chunk once and queue every predictor's statistic (ws.estimate._stat) on it; nothing waits for the GPU.  A ragged
     chunk goes through ws.estimate.attack image by image, as ws.estimate.attack_batch does."""
-    from ..evaluate import load_planes_u8, upload_planes
     from . import estimate
     planes = prefetched[0] if prefetched is not None else load_planes_u8(fnames)
     if planes is None:
         proc = filters_lib.get_processor_2d((3,))
         return "host", [[estimate.attack(f, (3,), est, estimate.NAMED_FILTERS["AVG"], False, 0, imread4_u8, proc, **{**kw, "model_name": name})
                          for name, est in predictors] for f, kw in zip(fnames, clean)]
-    x = upload_planes(planes, estimate._model_device(estimate.unet_model_of(predictors[-1][1])))
+    x = upload_planes(planes, model_device(estimate.unet_model_of(predictors[-1][1])))
     betas = []
     for _, est in predictors:
         try:
