@@ -321,7 +321,9 @@ void conv3x3_q_kernel(const QArgs a) {
     Tile cur = tile_of(a, lw);
     constexpr int MH = MSPLIT ? 1 : 2;                                        // accumulator tiles along the output channels
     constexpr bool PIPE = RQ == 4 && !H;                                        // explicit software pipeline of the fragment reads (below)
-    constexpr bool EPO = !MSPLIT && HC == 0 && RQ != 4;                       // the last step of a tile is split by accumulator tile: its second half shares a basic block with the first half of the epilogue
+    // the last step of a tile is split by accumulator tile: its second half shares a basic block with the first half of the epilogue.  (Not the head
+    // variants: split, they fit -- 147-149 registers, no scratch, the same bits -- but the forward was 0.2 % slower in a same-box A/B: profiles/r21)
+    constexpr bool EPO = !MSPLIT && HC == 0 && RQ != 4;
     f32x16 acc[2][4];                                                         // [MH][RQ] used (fixed bounds: a template-dependent bound made hipcc (ROCm 7.2) drop the host stubs)
     int kt = 0, j = 0;
     // the slots of this step and of the next one as running offsets (step j lives in input slot j % NIN and weight slot j % NWS, as the loaders count them)
@@ -545,32 +547,71 @@ _Pragma("unroll")
         for (int q = 0; q < RQ; ++q)
 #pragma unroll
             for (int o = 0; o < (HC > 0 ? HC : 1); ++o) hz[q][o] = 0.f;
+        // store set-up of the format-Q outputs, once per tile: behind the opaque copies above and opaque itself, so the four (m, piece) calls
+        // of a tile provably share it (four registers per row pair; profiles/r21: the plain instantiation shared it already, the pooled one did not quite)
+        struct QOff { unsigned g0, g1, q, s; };
+        auto pair_off = [&](unsigned plane_bytes, unsigned off0, unsigned off1, unsigned soff0, unsigned soff1, bool ok0, bool ok1) __attribute__((always_inline)) {
+            const unsigned hp = hh ? plane_bytes : 0u;
+            const bool okm = hh ? ok1 : ok0;
+            QOff o = {ok0 ? off0 + hp : OOB, ok1 ? off1 + hp : OOB, okm ? (hh ? off1 : off0) + 2u * plane_bytes : OOB, okm ? 3u * plane_bytes + (hh ? soff1 : soff0) : OOB};
+            asm volatile("" : "+v"(o.g0), "+v"(o.g1), "+v"(o.q), "+v"(o.s));
+            return o;
+        };
+        constexpr bool YQ = FQ && !H;                                          // y / ypool are format-Q tensors
+        QOff qo[RQ / 2] = {}, qop = {};                                        // a.y: one per row pair; a.ypool: the pooled pair (RQ = 4) or the pooled row (RQ = 2)
+        if constexpr (YQ) {
+            const unsigned sblk = (unsigned)(((cur.y0 >> 4) * a.tiles_x + (cur.x0 >> 5)) * 512);
+_Pragma("unroll")
+            for (int rp = 0; rp < RQ / 2; ++rp) {
+                const int r0 = RQ * wv + 2 * rp, row0 = cur.y0 + r0;
+                qo[rp] = pair_off(hw16, (unsigned)(row0 * a.w + col) * 16u, (unsigned)((row0 + 1) * a.w + col) * 16u,
+                                  sblk + (unsigned)(r0 * 32 + l31), sblk + (unsigned)((r0 + 1) * 32 + l31), row0 < a.h && col < a.w, row0 + 1 < a.h && col < a.w);
+            }
+            if constexpr (POOL) {
+                const int hp = a.h >> 1, wp2 = a.w >> 1, ptx = (wp2 + 31) >> 5;
+                const int gy0 = (cur.y0 >> 1) + (RQ / 2) * wv, gx = (cur.x0 >> 1) + (l31 >> 1);
+                const unsigned php16 = (unsigned)(hp * wp2) * 16u;
+                if constexpr (RQ == 4) {
+                    const bool okx = !(l31 & 1) && gx < wp2;
+                    qop = pair_off(php16, (unsigned)(gy0 * wp2 + gx) * 16u, (unsigned)((gy0 + 1) * wp2 + gx) * 16u,
+                                   wsu_q_soff(gy0, gx, ptx), wsu_q_soff(gy0 + 1, gx, ptx), okx && gy0 < hp, okx && gy0 + 1 < hp);
+                } else {
+                    // the odd lanes store piece 1's chunk, one chunk (cbp bytes) further (see the pooled stores below)
+                    const unsigned coff = (l31 & 1) ? (unsigned)wsu_q_chunk_bytes(hp, wp2) : 0u;
+                    const unsigned off = (unsigned)(gy0 * wp2 + gx) * 16u + coff, soff = wsu_q_soff(gy0, gx, ptx) + coff;
+                    const bool ok = gx < wp2 && gy0 < hp;
+                    qop = {ok ? off + (hh ? php16 : 0u) : OOB, OOB, (ok && !hh) ? off + 2u * php16 : OOB, (ok && !hh) ? 3u * php16 + soff : OOB};
+                    asm volatile("" : "+v"(qop.g0), "+v"(qop.q), "+v"(qop.s));
+                }
+            }
+        }
         // stores: wave-uniform descriptor of the (image, output chunk), 32-bit lane offsets; a lane that must not store passes an offset beyond the
         // descriptor's extent, which the hardware drops -- no branch (a branch would end the basic block the matrix instructions are scheduled in)
         // format Q: rows in pairs -- lanes 0-31 assemble and store the Q granule and scale byte of the pair's first row, lanes 32-63 the second's
-        auto store_pair_q = [&](const f32x4& X0, const f32x4& Y0, const f32x4& X1, const f32x4& Y1, char* base, unsigned chunk_bytes, unsigned plane_bytes,
-                                unsigned off0, unsigned off1, unsigned soff0, unsigned soff1, bool ok0, bool ok1, bool have) __attribute__((always_inline)) {
+        // The lane offsets of a row pair's four stores depend on (tile, lane) only -- the (m, piece) calls change the descriptor -- so they are
+        // formed once per tile (QOff, above) with the predicates folded in: g0 / g1 = the f16 granules of rows 0 / 1 (plane hh), q = the Q granule and
+        // s = the scale byte of row hh.  store_pair_q returns with the lane's largest |value| (wsu_q4_pre's) folded into vmax where `fold` is set.
+        auto store_pair_q = [&](const f32x4& X0, const f32x4& Y0, const f32x4& X1, const f32x4& Y1, char* base, unsigned chunk_bytes, const QOff& o, bool have, bool fold) __attribute__((always_inline)) {
             u32x4 g0, g1; uint32_t dh0, dr0, sb0, dh1, dr1, sb1;
-            wsu_q4_pre(X0, Y0, g0, dh0, dr0, sb0);
-            wsu_q4_pre(X1, Y1, g1, dh1, dr1, sb1);
+            const float mx0 = wsu_q4_pre(X0, Y0, g0, dh0, dr0, sb0);
+            const float mx1 = wsu_q4_pre(X1, Y1, g1, dh1, dr1, sb1);
+            if (fold) vmax = wsu_max3(vmax, mx0, mx1);
             const u32x4 qg = wsu_q4_pair(dh0, dr0, dh1, dr1);
             const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, have ? (int)chunk_bytes : 0, 0x00020000);
-            const unsigned hp = hh ? plane_bytes : 0u;
-            __builtin_amdgcn_raw_buffer_store_b128(g0, rs, (int)(ok0 ? off0 + hp : OOB), 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(g1, rs, (int)(ok1 ? off1 + hp : OOB), 0, 0);
-            const bool okm = hh ? ok1 : ok0;
-            __builtin_amdgcn_raw_buffer_store_b128(qg, rs, (int)(okm ? (hh ? off1 : off0) + 2u * plane_bytes : OOB), 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(hh ? sb1 : sb0), rs, (int)(okm ? 3u * plane_bytes + (hh ? soff1 : soff0) : OOB), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(g0, rs, (int)o.g0, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(g1, rs, (int)o.g1, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(qg, rs, (int)o.q, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(hh ? sb1 : sb0), rs, (int)o.s, 0, 0);
         };
-        // ... one row (the pooled row of RQ = 2): lanes 0-31 store the Q granule and the scale byte
-        auto store_one_q = [&](const f32x4& X, const f32x4& Y, char* base, unsigned chunk_bytes, unsigned plane_bytes, unsigned off, unsigned soff, bool ok, bool have) __attribute__((always_inline)) {
+        // ... one row (the pooled row of RQ = 2): lanes 0-31 store the Q granule and the scale byte (o.g0 / o.q / o.s)
+        auto store_one_q = [&](const f32x4& X, const f32x4& Y, char* base, unsigned chunk_bytes, const QOff& o) __attribute__((always_inline)) {
             u32x4 g; uint32_t dh, dr, sb;
             wsu_q4_pre(X, Y, g, dh, dr, sb);
             const u32x4 qg = wsu_q4_single(dh, dr);
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, have ? (int)chunk_bytes : 0, 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b128(g, rs, (int)(ok ? off + (hh ? plane_bytes : 0u) : OOB), 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(qg, rs, (int)((ok && !hh) ? off + 2u * plane_bytes : OOB), 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)sb, rs, (int)((ok && !hh) ? 3u * plane_bytes + soff : OOB), 0, 0);
+            const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)chunk_bytes, 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b128(g, rs, (int)o.g0, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(qg, rs, (int)o.q, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)sb, rs, (int)o.s, 0, 0);
         };
         // format H: the f16 granules alone -- lanes 0-31 store plane 0 (ch 0-7), lanes 32-63 plane 1 (ch 8-15)
         auto store_one_h = [&](const f32x4& X, const f32x4& Y, char* base, unsigned plane_bytes, unsigned off, bool ok, bool have) __attribute__((always_inline)) {
@@ -612,14 +653,15 @@ _Pragma("unroll")
                             // ReLU as one max against a wave-uniform floor (0 or -inf): no select per value
                             const float x = fmaxf(acc[m][2 * rp + u][8 * cp + e] + bx[e], relu_floor), y = fmaxf(acc[m][2 * rp + u][8 * cp + 4 + e] + by[e], relu_floor);
                             vx[u][e] = x; vy[u][e] = y;
-                            vmax = fmaxf(vmax, fmaxf(fabsf(x), fabsf(y)));
+                            // (format Q: the encode's own maximum chain feeds the range flag -- store_pair_q below)
+                            if constexpr (H || !FQ) vmax = fmaxf(fmaxf(vmax, fabsf(x)), fabsf(y));
                         }
                     }
                     if constexpr (HEAD) {
                         const int lc = (m * 2 + cp) * 16 + 4 * hh;             // channel inside the 64-wide block
 _Pragma("unroll")
                         for (int o = 0; o < HC; ++o)
-                            if (o < a.head_cout)
+                            if (HC == 1 || o < a.head_cout)                    // (HC == 1 is launched for one head plane only: no test, no block boundary)
 _Pragma("unroll")
                                 for (int u = 0; u < 2; ++u)
 _Pragma("unroll")
@@ -636,11 +678,7 @@ _Pragma("unroll")
                         } else if constexpr (FQ) {
                             const unsigned cb_ = (unsigned)wsu_q_chunk_bytes(a.h, a.w);
                             char* base = a.y + ((size_t)cur.n * nco + oc) * cb_;
-                            const unsigned sblk = (unsigned)(((cur.y0 >> 4) * a.tiles_x + (cur.x0 >> 5)) * 512);
-                            store_pair_q(vx[0], vy[0], vx[1], vy[1], base, cb_, hw16,
-                                         (unsigned)(row0 * a.w + col) * 16u, (unsigned)((row0 + 1) * a.w + col) * 16u,
-                                         sblk + (unsigned)(r0 * 32 + l31), sblk + (unsigned)((r0 + 1) * 32 + l31),
-                                         row0 < a.h && col < a.w, row0 + 1 < a.h && col < a.w, have_y);
+                            store_pair_q(vx[0], vy[0], vx[1], vy[1], base, cb_, qo[rp], have_y, true);
                         } else {
                             char* base = a.y + (((size_t)cur.n * nco + oc) * 3) * hw16;
                             WSU_STATIC_FOR(2, u, {
@@ -670,11 +708,9 @@ _Pragma("unroll")
                             store_one_h(px[rp], py[rp], base, php16, (unsigned)((gy0 + rp) * wp2 + gx) * 16u, okx && gy0 + rp < hp, true);
                     } else if constexpr (FQ) {
                         const unsigned cbp = (unsigned)wsu_q_chunk_bytes(hp, wp2);
-                        const int ptx = (wp2 + 31) >> 5;
                         char* base = a.ypool + ((size_t)cur.n * nco + oc) * cbp;
                         if constexpr (RQ == 4) {
-                            store_pair_q(px[0], py[0], px[1], py[1], base, cbp, php16, (unsigned)(gy0 * wp2 + gx) * 16u, (unsigned)((gy0 + 1) * wp2 + gx) * 16u,
-                                         wsu_q_soff(gy0, gx, ptx), wsu_q_soff(gy0 + 1, gx, ptx), okx && gy0 < hp, okx && gy0 + 1 < hp, true);
+                            store_pair_q(px[0], py[0], px[1], py[1], base, cbp, qop, true, false);      // (pooled values: maxima of values vmax has seen)
                         } else if constexpr (cp == 0) {
                             spx = px[0]; spy = py[0];
                         } else {
@@ -688,8 +724,7 @@ _Pragma("unroll")
                             f32x4 sx, sy;
 _Pragma("unroll")
                             for (int e = 0; e < 4; ++e) { sx[e] = odd ? px[0][e] : spx[e]; sy[e] = odd ? py[0][e] : spy[e]; }
-                            const unsigned coff = odd ? cbp : 0u;
-                            store_one_q(sx, sy, base - cbp, 2u * cbp, php16, (unsigned)(gy0 * wp2 + gx) * 16u + coff, wsu_q_soff(gy0, gx, ptx) + coff, gx < wp2 && gy0 < hp, true);
+                            store_one_q(sx, sy, base - cbp, 2u * cbp, qop);
                         }
                     } else {
                         char* base = a.ypool + (((size_t)cur.n * nco + oc) * 3) * php16;
@@ -723,7 +758,7 @@ _Pragma("unroll")
                 const int row = cur.y0 + RQ * wv + q;
 #pragma unroll
                 for (int o = 0; o < HC; ++o)
-                    if (o < a.head_cout) {
+                    if (HC == 1 || o < a.head_cout) {
                         uint32_t mine = __builtin_bit_cast(uint32_t, hz[q][o]), other = mine;
                         wsu_swap32(mine, other);                            // lanes 0-31: other = partner's sum; lanes 32-63: mine = partner's
                         const float z = __builtin_bit_cast(float, mine) + __builtin_bit_cast(float, other) + s_hb[o];

@@ -416,6 +416,13 @@ _Pragma("unroll")
         const bool ok0 = Y0 < a.h && X < a.w, ok1 = Y1 < a.h && X < a.w;
         const unsigned off0 = (unsigned)(Y0 * a.w + X) * 16u, off1 = (unsigned)(Y1 * a.w + X) * 16u;
         const unsigned so0 = wsu_q_soff(Y0, X, a.tiles_x), so1 = wsu_q_soff(Y1, X, a.tiles_x);
+        // the lane offsets of a piece's stores with their predicates folded in, once per tile and opaque (the four pieces change the descriptor only):
+        // f16 granules of matrix tiles 0 / 1 (plane hh), the Q granule and the scale byte of tile hh
+        const unsigned hpl = hho ? hw16 : 0u;
+        const bool okm = hho ? ok1 : ok0;
+        unsigned og0 = ok0 ? off0 + hpl : OOB, og1 = ok1 ? off1 + hpl : OOB;
+        unsigned oq = okm ? (hho ? off1 : off0) + 2u * hw16 : OOB, os = okm ? 3u * hw16 + (hho ? so1 : so0) : OOB;
+        asm volatile("" : "+v"(og0), "+v"(og1), "+v"(oq), "+v"(os));
         const float relu_floor = a.relu ? 0.f : -__builtin_inff();
         float vmax = 0.f;
         WSU_STATIC_FOR(2, m, {
@@ -430,28 +437,26 @@ _Pragma("unroll")
                     for (int e = 0; e < 4; ++e) {
                         const float x = fmaxf(acc[m][q][8 * cp + e] + bx[e], relu_floor), y = fmaxf(acc[m][q][8 * cp + 4 + e] + by[e], relu_floor);
                         vx[q][e] = x; vy[q][e] = y;
-                        vmax = fmaxf(vmax, fmaxf(fabsf(x), fabsf(y)));
+                        if constexpr (H) vmax = fmaxf(fmaxf(vmax, fabsf(x)), fabsf(y));   // (format Q: the encode's maximum chain below)
                     }
                 if constexpr (H) {                                              // f16 granules only: lanes 0-31 plane 0, lanes 32-63 plane 1
                     char* base = a.y + ((size_t)cur.n * nco + oc) * (2u * hw16);
                     const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)(2u * hw16), 0x00020000);
-                    const unsigned hp = hho ? hw16 : 0u;
-                    __builtin_amdgcn_raw_buffer_store_b128(wsu_h_granule(vx[0], vy[0]), rs, (int)(ok0 ? off0 + hp : OOB), 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(wsu_h_granule(vx[1], vy[1]), rs, (int)(ok1 ? off1 + hp : OOB), 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(wsu_h_granule(vx[0], vy[0]), rs, (int)og0, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(wsu_h_granule(vx[1], vy[1]), rs, (int)og1, 0, 0);
                     return;                                                     // (this piece's lambda)
                 }
                 u32x4 g0, g1; uint32_t dh0, dr0, sb0, dh1, dr1, sb1;
-                wsu_q4_pre(vx[0], vy[0], g0, dh0, dr0, sb0);
-                wsu_q4_pre(vx[1], vy[1], g1, dh1, dr1, sb1);
+                const float mx0 = wsu_q4_pre(vx[0], vy[0], g0, dh0, dr0, sb0);
+                const float mx1 = wsu_q4_pre(vx[1], vy[1], g1, dh1, dr1, sb1);
+                vmax = wsu_max3(vmax, mx0, mx1);
                 const u32x4 qg = wsu_q4_pair(dh0, dr0, dh1, dr1);           // lanes 0-31: matrix tile 0's granule, lanes 32-63: tile 1's
                 char* base = a.y + ((size_t)cur.n * nco + oc) * cbytes;
                 const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)cbytes, 0x00020000);
-                const unsigned hp = hho ? hw16 : 0u;
-                __builtin_amdgcn_raw_buffer_store_b128(g0, rs, (int)(ok0 ? off0 + hp : OOB), 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(g1, rs, (int)(ok1 ? off1 + hp : OOB), 0, 0);
-                const bool okm = hho ? ok1 : ok0;
-                __builtin_amdgcn_raw_buffer_store_b128(qg, rs, (int)(okm ? (hho ? off1 : off0) + 2u * hw16 : OOB), 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(hho ? sb1 : sb0), rs, (int)(okm ? 3u * hw16 + (hho ? so1 : so0) : OOB), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(g0, rs, (int)og0, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(g1, rs, (int)og1, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(qg, rs, (int)oq, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(hho ? sb1 : sb0), rs, (int)os, 0, 0);
             });
         });
         if (a.range_flag && __builtin_amdgcn_ballot_w64(!(vmax <= (H ? WSU_F16_RANGE : WSU_F8_RANGE))) != 0 && lane == 0) atomicOr(a.range_flag, 1u);

@@ -258,10 +258,10 @@ __global__ __launch_bounds__(ct::NT) void convt2x2_pl_kernel(const CtpArgs a) {
                         const int otx = (ow + 31) >> 5;
                         f32x4 X, Y; u32x4 g; uint32_t dh0, dr0, sb0, dh1, dr1, sb1;
                         value(0, X, Y);
-                        wsu_q4_pre(X, Y, g, dh0, dr0, sb0);
+                        wsu_q4_pre_bits(X, Y, g, dh0, dr0, sb0);
                         __builtin_amdgcn_raw_buffer_store_b128(g, rs, (int)(ok ? off + (hh ? pb : 0u) : OOB_), 0, 0);
                         value(1, X, Y);
-                        wsu_q4_pre(X, Y, g, dh1, dr1, sb1);
+                        wsu_q4_pre_bits(X, Y, g, dh1, dr1, sb1);
                         __builtin_amdgcn_raw_buffer_store_b128(g, rs, (int)(ok ? off + 16u + (hh ? pb : 0u) : OOB_), 0, 0);
                         const u32x4 qg = wsu_q4_pair(dh0, dr0, dh1, dr1);
                         __builtin_amdgcn_raw_buffer_store_b128(qg, rs, (int)(ok ? 2u * pb + off + (hh ? 16u : 0u) : OOB_), 0, 0);

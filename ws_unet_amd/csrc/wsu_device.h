@@ -251,20 +251,19 @@ __device__ __forceinline__ void wsu_swap32(uint32_t& upper_of, uint32_t& lower_o
 // lanes 32-63: ch 8-15, as the e4m3 format's epilogues arrange it); dhi / dres = this lane's eight fp4 nibbles of the f16 parts / of the
 // residuals (x - f16 x) * 2^11, both as [X: 16 bits | Y: 16 bits] and both divided by the block scale 2^E; sb = E + 127 (equal in both lanes).
 // The residual nibbles come from the exact fp32 residual (the loaders of round 3 re-rounded the stored e4m3 residual).
-__device__ __forceinline__ void wsu_q4_pre(const f32x4& X, const f32x4& Y, u32x4& g, uint32_t& dhi, uint32_t& dres, uint32_t& sb) {
+// Two front ends share the encoding (wsu_q4_pre_enc): they differ in how the lane's largest |f16| bit pattern `mb` (<= 0x7FFF) is found.
+__device__ __forceinline__ void wsu_q4_pre_cvt(const f32x4& X, const f32x4& Y, uint32_t& xh0, uint32_t& xh1, uint32_t& yh0, uint32_t& yh1) {
     const f32x2 xa = {X[0], X[1]}, xb = {X[2], X[3]}, ya = {Y[0], Y[1]}, yb = {Y[2], Y[3]};
-    uint32_t xh0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(xa, f16x2)), xh1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(xb, f16x2));
-    uint32_t yh0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(ya, f16x2)), yh1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(yb, f16x2));
+    xh0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(xa, f16x2)); xh1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(xb, f16x2));
+    yh0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(ya, f16x2)); yh1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(yb, f16x2));
+}
+__device__ __forceinline__ void wsu_q4_pre_enc(const f32x4& X, const f32x4& Y, uint32_t xh0, uint32_t xh1, uint32_t yh0, uint32_t yh1, uint32_t mb,
+                                               u32x4& g, uint32_t& dhi, uint32_t& dres, uint32_t& sb) {
     const float r0 = wsu_sub_f16_lo(X[0], xh0), r1 = wsu_sub_f16_hi(X[1], xh0), r2 = wsu_sub_f16_lo(X[2], xh1), r3 = wsu_sub_f16_hi(X[3], xh1);
     const float r4 = wsu_sub_f16_lo(Y[0], yh0), r5 = wsu_sub_f16_hi(Y[1], yh0), r6 = wsu_sub_f16_lo(Y[2], yh1), r7 = wsu_sub_f16_hi(Y[3], yh1);
-    // largest |f16| of the block: eight values here, eight in the partner lane
-    u16x2_t m = __builtin_elementwise_max(__builtin_bit_cast(u16x2_t, xh0 & 0x7FFF7FFFu), __builtin_bit_cast(u16x2_t, xh1 & 0x7FFF7FFFu));
-    m = __builtin_elementwise_max(m, __builtin_bit_cast(u16x2_t, yh0 & 0x7FFF7FFFu));
-    m = __builtin_elementwise_max(m, __builtin_bit_cast(u16x2_t, yh1 & 0x7FFF7FFFu));
-    uint32_t mw = __builtin_bit_cast(uint32_t, m), mp = mw;
+    uint32_t mw = mb, mp = mb;                                             // largest |f16| of the block: eight values here, eight in the partner lane
     wsu_swap32(mw, mp);                                                   // one of (mw, mp) is now the partner's, the other this lane's
-    m = __builtin_elementwise_max(__builtin_bit_cast(u16x2_t, mw), __builtin_bit_cast(u16x2_t, mp));
-    const int e = wsu_q4_block_exp(m.x > m.y ? m.x : m.y);
+    const int e = wsu_q4_block_exp(mw > mp ? mw : mp);
     const float sc = wsu_pow2f(e), scr = wsu_pow2f(e - 11);
     sb = (uint32_t)(e + 127);
     uint32_t dh = 0, dr = 0;
@@ -279,6 +278,40 @@ __device__ __forceinline__ void wsu_q4_pre(const f32x4& X, const f32x4& Y, u32x4
     dhi = dh; dres = dr;
     wsu_swap32(xh0, yh0); wsu_swap32(xh1, yh1);                            // lanes 0-31: f16 ch 0-7, lanes 32-63: f16 ch 8-15
     g = mk_u4(xh0, xh1, yh0, yh1);
+}
+// For values that CANNOT be NaN (the conv epilogues: every value went through v_max_f32(x, floor) with floor = 0 or -inf, which returns the
+// floor for a NaN x).  ONE maximum chain serves the block scale and the caller's range flag: the lane's largest |fp32| (three v_max3_f32 and a
+// v_max_f32 with |.| source modifiers), returned to the caller, and ONE conversion of it.  Round-to-nearest-even f32 -> f16 is monotone
+// (a <= b => f16 a <= f16 b, overflow to inf and the flush / denormal mode included) and odd (f16(-a) = -f16 a), so
+// f16(max |x_i|) = max f16 |x_i| = max |f16 x_i|, and non-negative f16 values (inf included) order like their bit patterns: the bits converted
+// here ARE the largest of the eight masked bit patterns the stored values would give.  The conversion is the instruction that converts the
+// values (v_cvt_pk_f16_f32, same rounding and denormal mode).  The range flag keeps its fp32 test (448.1 rounds to 448 in f16).
+__device__ __forceinline__ float wsu_q4_pre(const f32x4& X, const f32x4& Y, u32x4& g, uint32_t& dhi, uint32_t& dres, uint32_t& sb) {
+    uint32_t xh0, xh1, yh0, yh1;
+    wsu_q4_pre_cvt(X, Y, xh0, xh1, yh0, yh1);
+    float mx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(X[0]), __builtin_fabsf(X[1])), __builtin_fabsf(X[2]));
+    mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(X[3])), __builtin_fabsf(Y[0]));
+    mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(Y[1])), __builtin_fabsf(Y[2]));
+    mx = __builtin_fmaxf(mx, __builtin_fabsf(Y[3]));
+    const f32x2 mm = {mx, 0.f};
+    wsu_q4_pre_enc(X, Y, xh0, xh1, yh0, yh1, __builtin_bit_cast(uint32_t, __builtin_convertvector(mm, f16x2)), g, dhi, dres, sb);
+    return mx;
+}
+// For values that may be NaN (the transposed conv's epilogue adds its bias and stores): the maximum of the converted bit patterns, under
+// which a NaN is the largest element of its block -- a float maximum would skip it.
+__device__ __forceinline__ void wsu_q4_pre_bits(const f32x4& X, const f32x4& Y, u32x4& g, uint32_t& dhi, uint32_t& dres, uint32_t& sb) {
+    uint32_t xh0, xh1, yh0, yh1;
+    wsu_q4_pre_cvt(X, Y, xh0, xh1, yh0, yh1);
+    u16x2_t m = __builtin_elementwise_max(__builtin_bit_cast(u16x2_t, xh0 & 0x7FFF7FFFu), __builtin_bit_cast(u16x2_t, xh1 & 0x7FFF7FFFu));
+    m = __builtin_elementwise_max(m, __builtin_bit_cast(u16x2_t, yh0 & 0x7FFF7FFFu));
+    m = __builtin_elementwise_max(m, __builtin_bit_cast(u16x2_t, yh1 & 0x7FFF7FFFu));
+    wsu_q4_pre_enc(X, Y, xh0, xh1, yh0, yh1, m.x > m.y ? m.x : m.y, g, dhi, dres, sb);
+}
+// max(a, b, c) in one instruction, where it stands (the range flag's running maximum over the lane maxima wsu_q4_pre returns: written as
+// fmaxf the folds were sunk behind the test of the flag's pointer, with every lane maximum live until then and a canonicalising
+// v_max_f32 v, v, v in front of each).  No operand is NaN at its call sites.
+__device__ __forceinline__ float wsu_max3(float a, float b, float c) {
+    float r; asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
 }
 // Q granules of TWO pixels from their nibble words: lanes 0-31 return pixel 0's granule, lanes 32-63 pixel 1's (one exchange serves both: a
 // lower lane needs its partner's words of pixel 0, an upper lane its partner's words of pixel 1).
