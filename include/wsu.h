@@ -324,11 +324,16 @@ int wsu_conv3x3_first_pl_fwd(const float* x_nchw, const float* w_oihw, const flo
                              int relu, int y_format, unsigned* range_flag, unsigned char* relu_mask_out, void* stream);
 
 /* ---- first layer: conv3x3 reflect on a few input planes given as NCHW fp32 (the model input).
- *      Replaces e11 (unet.py:82,141).  cin <= 8, cout multiple of 8.  w is plain OIHW fp32. */
+ *      Replaces e11 (unet.py:82,141).  cin 1..8; cout = 8 * 2^k (8, 16, .. 2048) with cin * cout * 36 <= 163 840: the weights live in
+ *      the LDS of one compute unit (cin = 8: cout <= 512); more is an argument error that names cin and cout.  w is plain OIHW fp32.
+ *      mode BF16 stores y as bf16, each value rounded ONCE from the fp32 sum, to nearest, ties to even (v_cvt_pk_bf16_f32); the other
+ *      modes store fp32. */
 int wsu_conv3x3_first_fwd(const float* x_nchw, const float* w_oihw, const float* bias, void* y,
                           int n, int h, int w, int cin, int cout, int mode, int relu, void* stream);
 
-/* ---- K2 standalone 2x2/2 max-pool (used when not fused). */
+/* ---- K2 standalone 2x2/2 max-pool (used when not fused).  A last odd row / column belongs to no window.  pool_idx (optional): the window
+ *      position 0..3 of the result, row-major (0,0) (0,1) (1,0) (1,1); of equal values the FIRST wins and the result carries its bits
+ *      (+0 and -0 are equal).  A NaN in the window is the result, as in torch / numpy max; its index is that of the window's LAST NaN. */
 int wsu_maxpool2x2_fwd(const void* x, void* y, uint8_t* pool_idx, int n, int h, int w, int c, int mode, void* stream);
 
 /* ---- K3: y[n,2i+a,2j+b,co] = bias[co] + sum_ci x[n,i,j,ci] * w[ci,co,a,b]   (unet.py:177,183) */
@@ -585,7 +590,8 @@ size_t wsu_first_bwd_workspace_bytes(int n, int h, int w, int cin, int cout);
 int wsu_conv3x3_first_bwd_weight(const float* g, const float* x_nchw, float* dw, float* db,
                                  float* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, void* stream);
 
-/* first layer: dx (N,cin,H,W) NCHW fp32 -- the input saliency gradient (src/saliency.py:159-174). */
+/* first layer: dx (N,cin,H,W) NCHW fp32 -- the input saliency gradient (src/saliency.py:159-174).  cin 1..8, cout a multiple of 4 with
+ * cin * cout * 36 <= 163 840 (the weights live in the LDS of one compute unit); more is an argument error that names cin and cout. */
 int wsu_conv3x3_first_bwd_data(const float* g, const float* w_oihw, float* dx_nchw, int n, int h, int w, int cin, int cout, void* stream);
 
 /* transposed conv: dW (Cin x Cout x 2 x 2), db (Cout, optional) from x (N,h,w,Cin) and dy (N,2h,2w,Cout) ... */

@@ -508,7 +508,14 @@ int wsu_conv3x3_first_bwd_data(const float* g, const float* w_oihw, float* dx_nc
     WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && cin >= 1 && cin <= 8 && cout % 4 == 0 && cout > 0, "conv3x3_first_bwd_data: bad shape");
     const long long total = (long long)n * cin * h * w;
     const unsigned nblk = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(first_dgrad_kernel, dim3(nblk), dim3(256), (size_t)cin * 9 * cout * sizeof(float), static_cast<hipStream_t>(stream),
+    const size_t lds = (size_t)cin * 9 * cout * sizeof(float);
+    WSU_REQUIRE(lds <= (size_t)WSU_LDS_CU, "conv3x3_first_bwd_data: cin=%d x cout=%d weights need %zu B of LDS, a compute unit has %d", cin, cout, lds, WSU_LDS_CU);
+    static bool attr_done = false;                            // cin = 8, cout = 256: 73 728 B of weights, above the 64 KB a kernel gets unasked
+    if (lds > (size_t)WSU_LDS_DEFAULT && !attr_done) {
+        if (int rc = wsu_raise_lds(first_dgrad_kernel, WSU_LDS_CU, "first_dgrad")) return rc;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(first_dgrad_kernel, dim3(nblk), dim3(256), lds, static_cast<hipStream_t>(stream),
                        g, w_oihw, dx_nchw, n, h, w, cin, cout);
     return wsu_check_launch("first_dgrad_kernel");
 }
@@ -645,7 +652,7 @@ size_t wsu_first_bwd_workspace_bytes(int n, int h, int w, int cin, int cout) {
 int wsu_conv3x3_first_bwd_weight(const float* g, const float* x_nchw, float* dw, float* db,
                                  float* workspace, size_t workspace_bytes, int n, int h, int w, int cin, int cout, void* stream) {
     WSU_REQUIRE(g && x_nchw && dw && workspace, "conv3x3_first_bwd_weight: null pointer");
-    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && cin >= 1 && cin <= 8 && cout % 64 == 0, "conv3x3_first_bwd_weight: bad shape");
+    WSU_REQUIRE(n > 0 && h >= 2 && w >= 2 && cin >= 1 && cin <= 8 && cout > 0 && cout % 64 == 0, "conv3x3_first_bwd_weight: bad shape");
     const long long npix = (long long)n * h * w;
     const int chunk = first_bwd_chunk(npix);
     const int nchunks = (int)((npix + chunk - 1) / chunk);

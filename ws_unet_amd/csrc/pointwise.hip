@@ -273,6 +273,13 @@ int wsu_conv3x3_first_fwd(const float* x_nchw, const float* w_oihw, const float*
     WSU_REQUIRE(nblk < 0x7FFFFFFFLL, "conv3x3_first: grid too large");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t lds = (size_t)cin * 9 * cout * sizeof(float);
+    WSU_REQUIRE(lds <= (size_t)WSU_LDS_CU, "conv3x3_first: cin=%d x cout=%d weights need %zu B of LDS, a compute unit has %d", cin, cout, lds, WSU_LDS_CU);
+    static bool attr_done = false;                            // cin = 8, cout = 256: 73 728 B of weights, above the 64 KB a kernel gets unasked
+    if (lds > (size_t)WSU_LDS_DEFAULT && !attr_done) {
+        if (int rc = wsu_raise_lds(conv3x3_first_kernel<WSU_MODE_BF16>, WSU_LDS_CU, "conv3x3_first")) return rc;
+        if (int rc = wsu_raise_lds(conv3x3_first_kernel<WSU_MODE_F32>, WSU_LDS_CU, "conv3x3_first")) return rc;
+        attr_done = true;
+    }
     if (mode == WSU_MODE_BF16)
         hipLaunchKernelGGL(conv3x3_first_kernel<WSU_MODE_BF16>, dim3((unsigned)nblk), dim3(256), lds, s, x_nchw, w_oihw, bias, (char*)y, n, h, w, cin, cout, relu);
     else

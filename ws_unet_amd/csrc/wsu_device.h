@@ -35,6 +35,8 @@ WSU_INTERNAL int wsu_raise_lds_ptr(const void* kernel, int bytes, const char* wh
 template <class... A> inline int wsu_raise_lds(void (*kernel)(A...), int bytes, const char* who) {
     return wsu_raise_lds_ptr(reinterpret_cast<const void*>(kernel), bytes, who);
 }
+constexpr int WSU_LDS_DEFAULT = 64 * 1024;      // dynamic LDS a kernel gets without wsu_raise_lds
+constexpr int WSU_LDS_CU = 160 * 1024;          // LDS of one CDNA4 compute unit: what no workgroup can exceed
 
 // ---- tiling constants shared by packers and kernels ----------------------------------------------
 // A "chunk" is 64 bytes of channel data per pixel, staged in LDS as 4 granule planes of 16 bytes:
