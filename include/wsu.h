@@ -386,6 +386,26 @@ int wsu_ws_attack_taps(const uint8_t* x_u8, const float* pixel_filters, const fl
  *      neighbours, X^T y (q = 8) and y^T y (last).  Exact integers (at most 255^2 (H-2)(W-2) each), the same bits on every run. */
 int wsu_ols_moments(const uint8_t* x_u8, unsigned long long* moments, int n, int h, int w, void* stream);
 
+/* ---- K25: the trace-set table of Sample Pairs Analysis (Dumitrescu, Wu, Wang 2003).  x_u8: (N,H,W) DEVICE pixels, any H, W >= 1.  The
+ *      pairs of an image are all horizontally adjacent (x[r][c], x[r][c+1]) and all vertically adjacent (x[r][c], x[r+1][c]):
+ *      H (W-1) + (H-1) W of them.  For a pair (u,v): d = |u - v|, m = d >> 1, hi = max(u,v).  tables: DEVICE (N,3,128) uint64, zeroed on the
+ *      stream by this call:
+ *        tables[i][0][m] (E) = pairs with d even (d = 2m);
+ *        tables[i][1][m] (X) = pairs with d odd and hi even (their halves u >> 1, v >> 1 differ by m + 1);
+ *        tables[i][2][m] (Y) = pairs with d odd and hi odd (their halves differ by m).
+ *      With C_m = pairs whose halves differ by m and D_n = pairs with d = n: D_2m = E[m], D_2m+1 = X[m] + Y[m],
+ *      C_m = E[m] + Y[m] + X[m-1] (X[-1] = 0).  An image without a pair has an all-zero table.  Exact integers, the same bits on every run. */
+int wsu_spa_tables(const uint8_t* x_u8, unsigned long long* tables, int n, int h, int w, void* stream);
+
+/* ---- K26: the regular / singular group counts of RS analysis (Fridrich, Goljan, Du 2001).  x_u8: (N,H,W) DEVICE pixels, any H, W >= 1.
+ *      Groups are the non-overlapping runs of 4 consecutive pixels of every row from column 0: G = x[r][4g .. 4g+3], g < W / 4 (the trailing
+ *      W % 4 columns are ignored; W < 4 gives zeros).  f(G) = |g1-g0| + |g2-g1| + |g3-g2| in integers; F1(v) = v ^ 1;
+ *      F-1(v) = ((v + 1) ^ 1) - 1 in integers (0 -> -1, 255 -> 256, not clamped).  Mask M = (0,1,1,0): G_M applies F1 to g1 and g2,
+ *      G_-M applies F-1 to g1 and g2.  counts: DEVICE (N,8) uint64, zeroed on the stream by this call, per image in this order:
+ *        R_M = #{f(G_M) > f(G)}, S_M = #{f(G_M) < f(G)}, R_-M = #{f(G_-M) > f(G)}, S_-M = #{f(G_-M) < f(G)},
+ *      then the same four on the plane with every LSB flipped (G ^ 1 element-wise in the place of G).  Exact integers. */
+int wsu_rs_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
+
 /* ---- K12-K14: HILL-cost weighted prediction error (wMAE) of src/filters/evaluate.py:79-115 `get_filter_residuals_cover` and
  *      src/predictor_error.py:19-76 `attack`.  Both reference callers take HILL from a library (conseal.hill._costmap.compute_cost,
  *      stegolab2.hill.compute_rho); here both are the textbook cost, the one pinned by results/prediction/filters.csv:

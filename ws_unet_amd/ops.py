@@ -1046,6 +1046,33 @@ def ols_moments(x_u8: torch.Tensor) -> torch.Tensor:
     return moments
 
 
+def spa_tables(x_u8: torch.Tensor) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,3,128) int64: per image the sample-pairs table over all horizontally and vertically adjacent pixel pairs
+    (u,v), indexed by m = |u-v| >> 1: [0] E, |u-v| even; [1] X, odd with max(u,v) even; [2] Y, odd with max(u,v) odd (wsu_spa_tables, K25;
+    ws_unet_amd.ws.structural.spa solves)."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(x_u8)
+    if n == 0:
+        raise ValueError("spa_tables: no images")
+    tables = torch.empty((n, 3, 128), dtype=torch.int64, device=x_u8.device)
+    check(_launch("spa_tables", {"bytes": float(n * h * w)}, lambda: lib.wsu_spa_tables(
+        x_u8.data_ptr(), tables.data_ptr(), n, h, w, _stream())), "wsu_spa_tables")
+    return tables
+
+
+def rs_counts(x_u8: torch.Tensor) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,8) int64: per image R_M, S_M, R_-M, S_-M over the groups of 4 consecutive pixels of every row with the
+    mask (0,1,1,0), then the same four on the plane with every LSB flipped (wsu_rs_counts, K26; ws_unet_amd.ws.structural.rs solves)."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(x_u8)
+    if n == 0:
+        raise ValueError("rs_counts: no images")
+    counts = torch.empty((n, 8), dtype=torch.int64, device=x_u8.device)
+    check(_launch("rs_counts", {"bytes": float(n * h * w)}, lambda: lib.wsu_rs_counts(
+        x_u8.data_ptr(), counts.data_ptr(), n, h, w, _stream())), "wsu_rs_counts")
+    return counts
+
+
 def hill_cost(x_u8: torch.Tensor, clamp: float = 1e10) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,H,W) fp32 HILL cost with cost[inf | nan | > clamp] = clamp (wsu_hill_cost, K12)."""
     lib = _lib.load()

@@ -9,6 +9,8 @@ kernel, wsu_ws_attack; there is no host implementation in this package.
     the kernel; any other callable is called on the host like in the reference and its (H-2,W-2,1) result uploaded.
   * `attack_batch` / `attack_cover_batched` / `attack_stego_batched` run whole batches (fabrika iterator='batched'):
     threaded PNG decode -> one u8 upload -> UNet forward(s) -> statistic -> 4 bytes per image back.
+  * the model names of `structural.NAMES` ('SPA', 'RS') are no pixel predictors but whole estimators of their own (ws/structural.py:
+    an exact count kernel and a float64 solve); they go through the same drivers, unweighted and without bias correction.
   * `run(..., batched=True)` is `run` on the batched iterators; the joblib iterators of the reference (:139,144) cannot
     carry a GPU model into worker processes, so the per-image decorators use iterator='python'.
 
@@ -28,6 +30,7 @@ from .. import fabrika, filters, ols, ops
 from ..imread import imread4_u8, u8_plane
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import check_unet_geometry, model_device, unet_plane
+from . import structural
 
 NAMED_FILTERS = filters.NAMED_FILTERS_2D
 
@@ -90,6 +93,9 @@ def _unet_planes(model, x_u8: torch.Tensor, correct_bias: bool):
 
 def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=None) -> torch.Tensor:
     """beta_hat[N] on the device for a batch of planes."""
+    if isinstance(pixel_estimator, structural.StructuralEstimator):    # no predictor, no weights: the estimator is the statistic
+        structural.require_unweighted(weighted, correct_bias)
+        return pixel_estimator.beta(x_u8).to(torch.float32)
     kw = dict(mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted) if abs(int(weighted)) == 1 else 0,
               correct_bias=correct_bias)
     if isinstance(pixel_estimator, UNetEstimator):
@@ -115,6 +121,13 @@ def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct
     return ops.ws_attack(x_u8, x_hat, x_bias=x_bias, hat_scale=1.0, **kw)
 
 
+def _check_options(pixel_estimator, weighted, correct_bias) -> None:
+    """An option an estimator does not have is the caller's error, not an image without an estimate (`attack` turns a ValueError of
+    the statistic into beta_hat = None, as the reference does)."""
+    if isinstance(pixel_estimator, structural.StructuralEstimator):
+        structural.require_unweighted(weighted, correct_bias)
+
+
 def attack(
     fname: str,
     channels: typing.List[int],
@@ -127,6 +140,7 @@ def attack(
     **kw,
 ) -> dict:
     """WS estimate of one image (estimate.py:55-136): returns kw | {beta_hat, channels, weighted, correct_bias}."""
+    _check_options(pixel_estimator, weighted, correct_bias)
     x = process_image(imread(fname))                         # x_bar = process(x ^ 1) is formed on the device
     try:
         x_u8 = torch.from_numpy(_as_u8_plane(x))[None].to(model_device(unet_model_of(pixel_estimator)))
@@ -156,7 +170,7 @@ def attack_stego(*args, **kw):
 
 def _native_planes_ok(channels, pixel_estimator, imread, process_image) -> bool:
     """The default gray pipeline (Y plane, built-in predictor) needs no host arrays: native batched decode -> pinned buffer -> device."""
-    builtin = isinstance(pixel_estimator, (UNetEstimator, filters.FilterEstimator, ols.AdaptiveOLSEstimator))
+    builtin = isinstance(pixel_estimator, (UNetEstimator, filters.FilterEstimator, ols.AdaptiveOLSEstimator, structural.StructuralEstimator))
     plain = process_image is None or getattr(process_image, "plane_selector", None) == (3,)
     return builtin and imread is imread4_u8 and plain and tuple(channels) == (3,)
 
@@ -164,6 +178,7 @@ def _native_planes_ok(channels, pixel_estimator, imread, process_image) -> bool:
 def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED_FILTERS["AVG"], correct_bias=False,
                  weighted=1, imread=imread4_u8, process_image=None, prefetched=None, **_ignored):
     """`attack` for a chunk of files (fabrika iterator='batched'): one result dict per (fname, kw)."""
+    _check_options(pixel_estimator, weighted, correct_bias)
     if _native_planes_ok(channels, pixel_estimator, imread, process_image):
         u8 = prefetched[0] if prefetched is not None else load_planes_u8(fnames, imread)
         planes = None if u8 is None else [None] * len(fnames)
@@ -213,9 +228,13 @@ def run(
     batched: bool = False,
     **kw,
 ):
-    """WS attack over a data set with a named linear filter or a trained UNet as the pixel predictor (estimate.py:149-205)."""
+    """WS attack over a data set with a named linear filter or a trained UNet as the pixel predictor (estimate.py:149-205), or one of
+    the structural estimators of ws/structural.py ('SPA', 'RS': weighted=0, correct_bias=False) in the same rows."""
     process_cover = filters.get_processor_2d(channels=channels)
-    if model_name in ols.ADAPTIVE_NAMES:                       # 'OLSa' / 'OLSa2': the least-squares filter of each image under attack
+    if model_name in structural.NAMES:
+        pixel_estimator = structural.StructuralEstimator(model_name)
+        _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False))
+    elif model_name in ols.ADAPTIVE_NAMES:                       # 'OLSa' / 'OLSa2': the least-squares filter of each image under attack
         pixel_estimator = ols.adaptive_estimator(model_name)
     elif model_name in NAMED_FILTERS:
         pixel_estimator = filters.get_filter_estimator(filter_name=model_name, flatten=False)
@@ -254,7 +273,8 @@ def parse_args(argv=None):
     ap.add_argument("--train-method", default="LSBR", help="stego method the l1ws UNet was trained on")
     ap.add_argument("--stego-methods", nargs="*", default=["LSBR"])
     ap.add_argument("--alphas", nargs="*", type=float, default=[.4, .2, .1])
-    ap.add_argument("--filters", nargs="*", default=["AVG", "KB"])
+    ap.add_argument("--filters", nargs="*", default=["AVG", "KB"],
+                    help="named filters, the adaptive 'OLSa' / 'OLSa2', and the structural estimators 'SPA' / 'RS' (with --weighted 0)")
     ap.add_argument("--losses", nargs="*", default=["l1", "l1ws"])
     ap.add_argument("--weighted", type=int, default=0)
     ap.add_argument("--correct-bias", action="store_true")

@@ -15,7 +15,8 @@ the 501 thresholds of linspace(0, 1, 501) from 1 down to 0.  `produce_roc` resta
 
 The confusion counts of every group and threshold come from ONE call of K19 (wsu_roc_counts, exact integer counts of s > tau in
 float64); the host forms the rates and the table in fp64 with numpy, in the reference's array order.  The B0 detector itself is out of
-scope: its scores enter as files in the schema of results/detection/b0.csv (`load_scores`, `--scores`).
+scope: its scores enter as files in the schema of results/detection/b0.csv (`load_scores`, `--scores`).  The structural estimators of
+ws/structural.py ('SPA', 'RS') are further curves: rows like a predictor's (beta_hat = the estimated change rate), labelled by their own names.
 
 `collect_ws_scores` is the reference main's WS half (roc.py:372-395): ws.estimate.run per (image set, predictor), unweighted, without
 bias correction, on the Y plane -- but every image is decoded and uploaded once and all predictors score the device batch.
@@ -34,6 +35,7 @@ from .. import filters as filters_lib
 from ..imread import imread4_u8
 from ..planes import load_planes_u8, upload_planes
 from ..unet_run import model_device
+from . import structural
 
 TAUS = np.linspace(0, 1, 501, endpoint=True)       # ascending; the reference walks them reversed
 AUC_COLUMNS = ["stego_method", "model_name", "auc", "p_e", "tau0", "fpr_tau0", "tpr_tau0", "fpr_50", "tpr_50"]
@@ -97,7 +99,7 @@ def roc_rows(stego_method: str, model_name: str, taus_desc: np.ndarray, counts: 
         tp50, fp50, tn50 = (np.int64(counts_50[c]) for c in range(3))
         fn_stale = np.int64(FN[-1])                           # FN of the loop's last tau, not of 0.5 (roc.py:247-251)
         fpr50, tpr50 = fp50 / (fp50 + tn50), tp50 / (tp50 + fn_stale)
-    label = model_name if "B0" in model_name else f"WS-{model_name}"
+    label = model_name if "B0" in model_name or model_name in structural.NAMES else f"WS-{model_name}"
     return pd.DataFrame({
         "stego_method": stego_method,
         "model_name": model_name,
@@ -198,7 +200,8 @@ _score_stegos = fabrika.stego_spatial(iterator="batched", convert_to=None, ignor
 def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_METHODS, alphas: typing.Sequence[float] = ALPHAS,
                       filters: typing.Sequence[str] = WS_FILTERS, unet=None, mode: str = None, progress_on: bool = False, **kw):
     """The WS rows the reference's main concatenates (roc.py:372-395): for the cover set, then each stego method x alpha, the rows of
-    ws.estimate.run(..., weighted=0, correct_bias=False, channels=(3,), batched=True) of each named filter and then of the UNet
+    ws.estimate.run(..., weighted=0, correct_bias=False, channels=(3,), batched=True) of each named filter (or structural estimator,
+    'SPA' / 'RS', whose curves are labelled with their own names, not 'WS-<name>') and then of the UNet
     (model_name 'UNet'), concatenated, index reset, stego_method NaN -> 'Cover', alpha NaN -> 0.  The same frame, but each image is
     decoded (native PNG reader, one chunk ahead) and uploaded once, and every predictor's statistic runs on that device batch.
     unet: None (no UNet rows), a ws.estimate.UNetEstimator, a model, or (model_path, model_name) of a trained run loaded in
@@ -208,9 +211,11 @@ def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_MET
     from .. import ols
     names = list(filters)
     for name in names:
-        if name not in estimate.NAMED_FILTERS and name not in ols.ADAPTIVE_NAMES:
-            raise ValueError(f"unknown filter {name!r}; choose from {sorted(estimate.NAMED_FILTERS) + sorted(ols.ADAPTIVE_NAMES)}")
-    preds = [(name, ols.adaptive_estimator(name) or filters_lib.get_filter_estimator(filter_name=name, flatten=False)) for name in names]
+        if name not in estimate.NAMED_FILTERS and name not in ols.ADAPTIVE_NAMES and name not in structural.NAMES:
+            raise ValueError(f"unknown filter {name!r}; choose from "
+                             f"{sorted(estimate.NAMED_FILTERS) + sorted(ols.ADAPTIVE_NAMES) + sorted(structural.NAMES)}")
+    preds = [(name, structural.StructuralEstimator(name) if name in structural.NAMES else
+              ols.adaptive_estimator(name) or filters_lib.get_filter_estimator(filter_name=name, flatten=False)) for name in names]
     est = estimate.as_unet_estimator(unet, mode)
     if est is not None:
         preds.append(("UNet", est))
@@ -269,7 +274,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--stego-methods", nargs="*", default=list(STEGO_METHODS))
     ap.add_argument("--alphas", nargs="+", type=float, default=list(ALPHAS),
                     help="pooled into one curve per stego method; the LAST one names the output files")
-    ap.add_argument("--filters", nargs="*", default=list(WS_FILTERS), help="named filters of filters.NAMED_FILTERS_2D")
+    ap.add_argument("--filters", nargs="*", default=list(WS_FILTERS), help="named filters of filters.NAMED_FILTERS_2D, 'OLSa' / 'OLSa2', and the structural estimators 'SPA' / 'RS'")
     ap.add_argument("--scores", nargs=2, action="append", default=[], metavar=("FILE", "NAME"),
                     help="detector scores in the schema of results/detection/b0.csv (the `output` column; covers have an empty "
                          "stego_method) added as model NAME, which must contain 'B0'; repeatable")
