@@ -379,6 +379,31 @@ int wsu_ws_attack(const uint8_t* x_u8, const float* x_hat, const float* x_bias, 
 int wsu_ws_attack_taps(const uint8_t* x_u8, const float* pixel_filters, const float* mean_filter, int weighted, int correct_bias,
                        float* beta_hat, double* sums, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
 
+/* ---- K27: the WS changepoint for sequentially placed payloads (Ker, SPIE 2007; not part of the reference).  Inputs as K11's: x_u8 (N,H,W)
+ *      DEVICE pixels and exactly ONE prediction source:
+ *        x_hat (DEVICE fp32; hat_full = 1: (N,H,W) frames, hat_full = 0: (N,H-2,W-2) interiors; multiplied by hat_scale),
+ *        pixel_filter (HOST, 9 floats K[a][b], evaluated in the kernel as in K11), or
+ *        pixel_filters (DEVICE (N,9) fp32, one such filter per image, as wsu_ws_attack_taps).
+ *      mean_filter (HOST, 9 floats) feeds the local variance for weighted = 1; weighted = 0 -> unit weights.  weighted = -1 and the bias
+ *      correction are not defined for this statistic: weighted = -1 is an argument error (checked before any HIP call).
+ *      The path visits the interior pixels [1:-1, 1:-1] row by row, left to right within a row; order = 0: rows from the top,
+ *      order = 1: rows from the bottom.  M = (H-2)(W-2) positions, M <= 2^27.  Per interior pixel, in float32 with K11's operation
+ *      sequence and nothing contracted (s = x - x_bar = +-1, res = x - x_hat, var as in K11):
+ *        r = s * res;   d = r - 0.25f;   t = wgt * d,   wgt = 1.0f or 1.0f / (5.0f + var);
+ *        q = 0 where t is NaN, otherwise llrint((double)min(max(t, -4096), 4096) * 2^24)        (round to nearest even, int64).
+ *      Outputs per image, DEVICE int64 [N], with T(j) = q_1 + .. + q_j along the path and T(0) = 0:
+ *        k     = the smallest k in 0..M at which T(k) is maximal (the empty prefix takes part; among equal maxima the first);
+ *        t_max = T(k);   t_all = T(M);
+ *        curve = optional DEVICE int64 (N,H-2) (may be null): T at the end of every interior row, in path order.
+ *      All sums are exact integers (|q| <= 2^36), so the results do not depend on how the work is split, on the batch or on the run.
+ *      Image i's outputs are those of a call on image i alone.  workspace: DEVICE, 8-byte aligned,
+ *      wsu_ws_sequential_workspace_bytes(n, h) = 24 (H-2) bytes per image (0 for bad arguments); fully written before it is read.
+ *      n <= 65535, h, w >= 3.  The payload estimate from k is host arithmetic (ws_unet_amd/ws/sequential.py). */
+size_t wsu_ws_sequential_workspace_bytes(int n, int h);
+int wsu_ws_sequential(const uint8_t* x_u8, const float* x_hat, const float* pixel_filter, const float* pixel_filters, const float* mean_filter,
+                      int hat_full, float hat_scale, int weighted, int order, long long* k, long long* t_max, long long* t_all,
+                      long long* curve, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
+
 /* ---- K24: moments of the least-squares 3x3 pixel predictor.  x_u8: (N,H,W) DEVICE pixels.  At every interior pixel (r,c), with
  *      xab = x[r-1+a][c-1+b], v = [x00 x01 x02 x12 x22 x21 x20 x10 x11] (the ring order of the flattened 8-tap filters,
  *      _defs/filters.py:57-67, centre last).  moments: DEVICE (N,45) uint64, zeroed on the stream by this call:
@@ -504,7 +529,7 @@ size_t wsu_roc_counts_workspace_bytes(int groups, int t);
 int wsu_roc_counts(const double* scores, const signed char* labels, const long long* offsets, int groups, const double* taus, int t,
                    long long* counts, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- K20-K23: the stego simulators HILLR and LSBR.  The reference's stego twins were made by a library outside its tree; HILLR is
+/* ---- K20-K23, K28: the stego simulators HILLR, LSBR and LSBRS.  The reference's stego twins were made by a library outside its tree; HILLR is
  *      pinned to them bit for bit (tests/golden/stego_HILLR_*), LSBR's realisation is defined here.  Every plane is DEVICE (N,H,W) and
  *      contiguous; H, W >= 1, H*W < 2^32, N <= 65535.  stego may alias cover.  Deterministic: integer atomics only, two calls give the
  *      same bits, and an image's result does not depend on its position in the batch or on the batch size.
@@ -538,6 +563,15 @@ int wsu_embed_threshold(const uint8_t* cover, const double* key, const uint64_t*
 int wsu_lsbr_threshold(double alpha, uint32_t* threshold);
 int wsu_embed_lsbr(const uint8_t* cover, const uint64_t* seeds, const uint32_t* thresholds, uint8_t* stego, long long* changes,
                    int n, int h, int w, void* stream);
+/* K28: LSBRS, sequential LSB replacement: the message occupies the first counts[image] pixels of the path over the WHOLE plane (row by
+ *      row, left to right within a row; order = 0: rows from the top, order = 1: rows from the bottom).  Pixel i (linear index) flips iff
+ *      its path position (order 0: i; order 1: (H - 1 - i / W) * W + i % W) is < counts[image] AND it flips under K23 at alpha = 1 with the
+ *      same seed (word i % 4 of Philox4x32-10 on counter (i / 4, 0, 0, 0) < 2^31).  So at counts = H*W the twin is K23's alpha = 1 twin bit
+ *      for bit in both orders, every pixel at a path position >= counts is the cover's, and a twin at a smaller count is a prefix of one at
+ *      a larger count.  counts: DEVICE int64 [N], for a payload alpha the HOST value floor(alpha * H * W) in float64 (clamped to 0..H*W
+ *      here); seeds, changes, limits and aliasing as in K23. */
+int wsu_embed_lsbr_seq(const uint8_t* cover, const uint64_t* seeds, const long long* counts, int order, uint8_t* stego, long long* changes,
+                       int n, int h, int w, void* stream);
 
 /* Linear pixel predictor on its own (filters/evaluate.py:136-141): y (N,H-2,W-2) = convolve(x/255., K, 'valid')*255.
  * x: DEVICE (N,H,W) fp32; filter: HOST 9 floats K[a][b]. */

@@ -1,4 +1,4 @@
-// K20-K23: the stego simulators HILLR and LSBR (the reference ships ready-made twins of its five covers, made by a library outside its
+// K20-K23, K28: the stego simulators HILLR, LSBR and LSBRS (the reference ships ready-made twins of its five covers, made by a library outside its
 // tree; tests/golden/stego_HILLR_* pins HILLR to those files bit for bit, LSBR's realisation is this package's own):
 //
 //   HILLR   key = HILL cost in float64 (the operation order of tests/hill_np.hill_cost), full frame
@@ -6,6 +6,8 @@
 //           stego = cover ^ (key <= c_(k))                 (k + 1 changes when c_(k) is held by one pixel; ties are all flipped)
 //   LSBR    stego = cover ^ (word < T),  T = floor(alpha / 2 * 2^32),  word = Philox4x32-10 word (i % 4) of counter (i / 4, 0, 0, 0)
 //           under the image's 64-bit seed as key (low, high), i = the pixel's linear index in its image
+//   LSBRS   stego = cover ^ (path position of i < m  and  word < 2^31),  m = floor(alpha * H * W): LSBR at alpha = 1 on the first m pixels
+//           of the path over the whole plane, row by row from the top or from the bottom (K28)
 //
 // K20 is K12 in float64 on a 32 x 32 tile (the float64 arrays of a 64 x 64 tile would need 97 KB of LDS; a 32 x 32 tile needs 36 KB
 // and stays static): every sum is a direct sum in numpy's order, the two divisions are IEEE divisions, nothing is contracted.  K21 is an
@@ -285,6 +287,64 @@ __global__ __launch_bounds__(256) void embed_lsbr_kernel(const uint8_t* __restri
     add_changes(cnt, changes + nn, tid);
 }
 
+// K28.  LSBRS: the message occupies the first m pixels of the path over the whole plane (row by row, left to right; rows from the top,
+// order 0, or from the bottom, order 1); a pixel on it flips as under K23 at alpha = 1 (word < 2^31).  The first m path positions are at
+// most two runs of linear indices: order 0: [0, m); order 1: the m / w full rows at the bottom, [(h - m / w) w, h w), and the first m % w
+// pixels of the row above them.  A quad of pixels outside both runs costs no generator call.
+struct Runs { long long a0, a1, b0, b1; };
+__device__ __forceinline__ bool in_runs(const Runs& u, long long i) { return (i >= u.a0 && i < u.a1) || (i >= u.b0 && i < u.b1); }
+
+__global__ __launch_bounds__(256) void embed_lsbr_seq_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ seeds,
+                                                             const long long* __restrict__ counts, int order, uint8_t* __restrict__ stego,
+                                                             long long* __restrict__ changes, long long hw, int w) {
+    const int nn = blockIdx.y, tid = threadIdx.x;
+    const uint8_t* cin = cover + (size_t)nn * hw;
+    uint8_t* cout = stego + (size_t)nn * hw;
+    const uint32_t k0 = (uint32_t)seeds[nn], k1 = (uint32_t)(seeds[nn] >> 32), thr = 0x80000000u;
+    long long m = counts[nn];
+    m = m < 0 ? 0 : m > hw ? hw : m;
+    Runs u{0, m, 0, 0};
+    if (order) {
+        const long long full = hw - m / w * w;                              // the first pixel of the full rows
+        u = Runs{full, hw, full - w, full - w + m % w};                     // (m % w == 0: the second run is empty, also where full == 0)
+    }
+    const Span sp = image_span(cin, cout, hw, true);
+    int cnt = 0;
+    for (long long g = (long long)blockIdx.x * 256 + tid; g < sp.groups; g += (long long)gridDim.x * 256) {
+        const long long p = sp.head + 16 * g;                               // a multiple of 4
+        u32x4 v = *reinterpret_cast<const u32x4*>(cin + p);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t on = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) on |= (in_runs(u, p + 4 * q + e) ? 1u : 0u) << (8 * e);
+            if (on) {
+                const Words4 wd = philox4x32_10((uint32_t)(p / 4 + q), k0, k1);
+                uint32_t flips = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) flips |= (wd.v[e] < thr ? 1u : 0u) << (8 * e);
+                flips &= on;
+                v[q] ^= flips;
+                cnt += __popc(flips);
+            }
+        }
+        *reinterpret_cast<u32x4*>(cout + p) = v;
+    }
+    for (long long j = (long long)blockIdx.x * 256 + tid; j < sp.bytes; j += (long long)gridDim.x * 256) {
+        const long long i = span_byte_index(sp, j);
+        uint8_t flip = 0;
+        if (in_runs(u, i)) {
+            const Words4 wd = philox4x32_10((uint32_t)(i / 4), k0, k1);
+            const int e = (int)(i & 3);
+            const uint32_t word = e == 0 ? wd.v[0] : e == 1 ? wd.v[1] : e == 2 ? wd.v[2] : wd.v[3];
+            flip = word < thr ? 1 : 0;
+        }
+        cout[i] = cin[i] ^ flip;
+        cnt += flip;
+    }
+    add_changes(cnt, changes + nn, tid);
+}
+
 int embed_blocks(long long hw) {
     const long long b = (hw / 16 + 255) / 256;
     return (int)(b < 1 ? 1 : b > EMB_MAX_BLOCKS ? EMB_MAX_BLOCKS : b);
@@ -363,6 +423,18 @@ int wsu_embed_lsbr(const uint8_t* cover, const uint64_t* seeds, const uint32_t* 
     if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbr memset");
     hipLaunchKernelGGL(embed_lsbr_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, thresholds, stego, changes, hw);
     return wsu_check_launch("embed_lsbr_kernel");
+}
+
+int wsu_embed_lsbr_seq(const uint8_t* cover, const uint64_t* seeds, const long long* counts, int order, uint8_t* stego, long long* changes,
+                       int n, int h, int w, void* stream) {
+    WSU_REQUIRE(cover && seeds && counts && stego && changes, "embed_lsbr_seq: null pointer");
+    WSU_REQUIRE(order == 0 || order == 1, "embed_lsbr_seq: order=%d outside {0 = rows from the top, 1 = rows from the bottom}", order);
+    EMBED_REQUIRE_SHAPE("embed_lsbr_seq");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long hw = (long long)h * w;
+    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbr_seq memset");
+    hipLaunchKernelGGL(embed_lsbr_seq_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, counts, order, stego, changes, hw, w);
+    return wsu_check_launch("embed_lsbr_seq_kernel");
 }
 
 }  // extern "C"

@@ -46,48 +46,12 @@ __global__ __launch_bounds__(256) void ws_attack_partial_kernel(
     double sw = 0.0, sb = 0.0, sc = 0.0;
     for (int r = 1 + part; r <= h - 2; r += WSA_PARTS) {
         for (int c = 1 + tid; c <= w - 2; c += 256) {
-            float v[3][3], v2[3][3];
-            uint8_t u[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    u[i][j] = img[(size_t)(r - 1 + i) * w + (c - 1 + j)];
-                    v[i][j] = (float)u[i][j];
-                    v2[i][j] = v[i][j] * v[i][j];
-                }
-            float wgt = 1.0f;
-            if (weighted != 0) {
-                const float mu = conv9(mean_taps, v);
-                const float mu2 = conv9(mean_taps, v2);
-                const float mu_sq = mu * mu;
-                const float var = mu2 - mu_sq;
-                const float t = 5.0f + var;
-                wgt = weighted > 0 ? 1.0f / t : t;
-            }
-            const float x = v[1][1];
-            const float s = x - (float)(uint8_t)(u[1][1] ^ 1);                       // x - x_bar = +-1
-            float res, bias = 0.f;                                                    // res = x - x_hat
-            if (use_pixel_filter) {
-                float q[3][3], qb[3][3];
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        q[i][j] = unit[u[i][j]];                                        // x / 255. (filters/evaluate.py:136-141)
-                        qb[i][j] = (u[i][j] & 1) ? -unit[1] : unit[1];                  // (x_bar - x) / 255. = -+1 / 255.
-                    }
-                res = residual_f32(x, conv9(pixel_taps, q), 255.0f);
-                if (correct_bias) bias = conv9(pixel_taps, qb) * 255.0f;
-            } else {
-                const size_t o = hat_index(hat_full, hbase, r, c, w);
-                res = residual_f32(x, xhat[o], hat_scale);
-                if (correct_bias) bias = xbias[o] * hat_scale;
-            }
-            const float ws = wgt * s;
-            sw += (double)wgt;
-            sb += (double)(ws * res);
-            sc += (double)(ws * bias);
+            const WsTerms t = ws_pixel_terms(img, xhat, xbias, unit, mean_taps, pixel_taps, use_pixel_filter, hat_full, hbase, hat_scale,
+                                             weighted, correct_bias, r, c, w);
+            const float ws = t.wgt * t.s;
+            sw += (double)t.wgt;
+            sb += (double)(ws * t.res);
+            sc += (double)(ws * t.bias);
         }
     }
     red[0][tid] = sw; red[1][tid] = sb; red[2][tid] = sc;

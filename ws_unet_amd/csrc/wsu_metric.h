@@ -1,6 +1,7 @@
-// Device helpers shared by the metric kernels K10-K18 and the simulators K20-K23 (pointwise.hip K10 + WS meter, ws_attack.hip, hill.hip,
-// correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's taps, the prediction at a pixel, the float32
-// residual, the HILL cost's input window, the fixed-order block sum and the radix-select steps.
+// Device helpers shared by the metric kernels K10-K18 and K27 and the simulators K20-K23 and K28 (pointwise.hip K10 + WS meter,
+// ws_attack.hip, ws_sequential.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's
+// taps, the prediction at a pixel, the float32 residual, the WS statistic's per-pixel terms, the HILL cost's input window, the fixed-order
+// block sum and the radix-select steps.
 //
 // Rounding policy: these functions restate numpy's float32 / float64 operation sequences with PLAIN operators, one rounding each.  That
 // holds only under `#pragma clang fp contract(off)`, which is per translation unit: every including .hip file sets it BEFORE this
@@ -60,6 +61,61 @@ __device__ __forceinline__ size_t hat_index(int hat_full, size_t base, int r, in
 __device__ __forceinline__ float residual_f32(float x, float y, float scale) {
     const float xhat = y * scale;
     return x - xhat;
+}
+
+// ---- the WS statistic's per-pixel terms (K11, K27) ---------------------------------------------------------------------------------
+// At interior pixel (r, c) of the uint8 plane `img` (row stride w), in numpy's float32 operation sequence (src/ws/estimate.py:90-121):
+//   wgt  = 1 (weighted 0) | 1 / (5 + var) (weighted > 0) | 5 + var (weighted < 0),  var = conv(x*x, mean) - conv(x, mean)^2
+//   s    = x - x_bar = +-1
+//   res  = x - x_hat,  x_hat = conv(x / 255., pixel_taps) * 255. (use_pixel_filter; `unit` = the 256 quotients u / 255.f) or
+//          xhat[o] * hat_scale, o = hat_index(...)
+//   bias = the predictor applied to x_bar - x (correct_bias only, else 0)
+// Convolutions are true convolutions summed K00 .. K22 (conv9_f32<true>).
+struct WsTerms { float wgt, s, res, bias; };
+__device__ __forceinline__ WsTerms ws_pixel_terms(const uint8_t* __restrict__ img, const float* __restrict__ xhat,
+                                                  const float* __restrict__ xbias, const float* unit, const Taps3x3<float>& mean_taps,
+                                                  const Taps3x3<float>& pixel_taps, int use_pixel_filter, int hat_full, size_t hbase,
+                                                  float hat_scale, int weighted, int correct_bias, int r, int c, int w) {
+    float v[3][3], v2[3][3];
+    uint8_t u[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            u[i][j] = img[(size_t)(r - 1 + i) * w + (c - 1 + j)];
+            v[i][j] = (float)u[i][j];
+            v2[i][j] = v[i][j] * v[i][j];
+        }
+    WsTerms o;
+    o.wgt = 1.0f;
+    if (weighted != 0) {
+        const float mu = conv9_f32<true>(mean_taps, v);
+        const float mu2 = conv9_f32<true>(mean_taps, v2);
+        const float mu_sq = mu * mu;
+        const float var = mu2 - mu_sq;
+        const float t = 5.0f + var;
+        o.wgt = weighted > 0 ? 1.0f / t : t;
+    }
+    const float x = v[1][1];
+    o.s = x - (float)(uint8_t)(u[1][1] ^ 1);                                          // x - x_bar = +-1
+    o.bias = 0.f;
+    if (use_pixel_filter) {
+        float q[3][3], qb[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                q[i][j] = unit[u[i][j]];                                                // x / 255. (filters/evaluate.py:136-141)
+                qb[i][j] = (u[i][j] & 1) ? -unit[1] : unit[1];                          // (x_bar - x) / 255. = -+1 / 255.
+            }
+        o.res = residual_f32(x, conv9_f32<true>(pixel_taps, q), 255.0f);
+        if (correct_bias) o.bias = conv9_f32<true>(pixel_taps, qb) * 255.0f;
+    } else {
+        const size_t at = hat_index(hat_full, hbase, r, c, w);
+        o.res = residual_f32(x, xhat[at], hat_scale);
+        if (correct_bias) o.bias = xbias[at] * hat_scale;
+    }
+    return o;
 }
 
 // ---- the HILL cost's input window (K12 fp32, K20 fp64) -----------------------------------------------------------------------------

@@ -152,8 +152,16 @@ class PairLoader:
 
     def _simulated_rows(self, split, stego_method, alpha, take_num_images) -> None:
         from .. import embed
+
+        def training_method(m):                                         # the two methods a network is trained on
+            name = embed.method_name(m)
+            if name not in ("LSBR", "HILLR"):
+                raise ValueError(f"PairLoader(simulate=True) makes 'LSBR' / 'HILLR' twins; {name!r} (sequential placement) is not a "
+                                 f"training method: write its twins with embed.write_dataset")
+            return name
+
         if self.combos is not None:
-            self.combos = [(embed.method_name(m), a) for m, a in self.combos]
+            self.combos = [(training_method(m), a) for m, a in self.combos]
             bad = [a for _, a in self.combos if not 0.0 <= a <= 1.0]
             if bad:
                 raise ValueError(f"alpha={bad[0]!r} outside [0, 1]")
@@ -161,7 +169,7 @@ class PairLoader:
         else:
             if stego_method is None or alpha is None:
                 raise ValueError("simulate=True needs a stego_method and an alpha")
-            self.sim_method, self.sim_alpha = embed.method_name(stego_method), float(alpha)
+            self.sim_method, self.sim_alpha = training_method(stego_method), float(alpha)
             if not 0.0 <= self.sim_alpha <= 1.0:
                 raise ValueError(f"alpha={alpha!r} outside [0, 1]")
             self.method = self.sim_method

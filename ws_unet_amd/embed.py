@@ -1,5 +1,5 @@
-"""Stego simulators on the device: HILLR and LSBR twins of cover images (wsu_hill_cost_f64, wsu_rank_select_f64,
-wsu_embed_threshold, wsu_embed_lsbr; include/wsu.h K20-K23).
+"""Stego simulators on the device: HILLR, LSBR and LSBRS twins of cover images (wsu_hill_cost_f64, wsu_rank_select_f64,
+wsu_embed_threshold, wsu_embed_lsbr, wsu_embed_lsbr_seq; include/wsu.h K20-K23, K28).
 
 The reference ships its five covers with ready-made `stego_*` folders from a library outside its tree.  Here a covers-only data
 set gets its twins from the package itself:
@@ -14,6 +14,10 @@ HILLR is deterministic and reproduces the reference's files bit for bit: the LSB
 cost, k = floor((H*W - 1) * alpha / 2); every pixel that ties with the threshold flips too (a flat image flips entirely).  LSBR
 flips each LSB independently with probability alpha / 2 from Philox4x32-10 keyed by the image's seed: the realisation is a function
 of (seed, alpha, pixel index) alone -- `image_seed(filename, stream)` makes it a function of the file stem and a stream number.
+LSBRS is what most LSB-replacement tools do: the message goes into the first m = floor(alpha * H * W) pixels in file order, `order`
+'rows' (row by row from the top) or 'rows_up' (from the bottom row, as BMP-style tools write).  A pixel on that path flips as under LSBR
+at alpha = 1 with the same seed, so LSBRS at alpha = 1 is LSBR at alpha = 1, everything beyond position m is the cover, and a twin at a
+smaller alpha is a prefix of one at a larger alpha (ws.estimate's placement='sequential' is the matching estimator).
 """
 from __future__ import annotations
 
@@ -26,11 +30,12 @@ import torch
 
 from . import fabrika
 
-METHODS = ("LSBR", "HILLR")
+METHODS = ("LSBR", "HILLR", "LSBRS")
+ORDERS = ("rows", "rows_up")
 
 
 def method_name(stego_method: str) -> str:
-    """'LSBR' / 'HILLR', matched case-insensitively (the reference spells both 'LSBr' and 'LSBR')."""
+    """'LSBR' / 'HILLR' / 'LSBRS', matched case-insensitively (the reference spells both 'LSBr' and 'LSBR')."""
     m = str(stego_method).upper()
     if m not in METHODS:
         raise NotImplementedError(f"stego method {stego_method!r} is not simulated here: choose one of {' / '.join(METHODS)}")
@@ -50,6 +55,17 @@ def hillr_rank(alpha: float, h: int, w: int) -> int:
     return int(np.floor((h * w - 1) * (float(alpha) / 2))) if alpha > 0 else -1
 
 
+def lsbrs_count(alpha: float, h: int, w: int) -> int:
+    """m = floor(alpha * H * W) in float64: the number of path positions an LSBRS message occupies."""
+    return int(np.floor(np.float64(alpha) * np.float64(h * w)))
+
+
+def _check_order(order) -> str:
+    if order not in ORDERS:
+        raise ValueError(f"unknown order {order!r}; choose from {ORDERS}")
+    return order
+
+
 def _alphas(alpha, n: int) -> np.ndarray:
     a = np.asarray(alpha, dtype=np.float64)
     if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
@@ -60,12 +76,15 @@ def _alphas(alpha, n: int) -> np.ndarray:
     return a
 
 
-def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, key: typing.Optional[torch.Tensor] = None):
+def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, key: typing.Optional[torch.Tensor] = None,
+             order: str = "rows"):
     """cover_u8: (N,H,W) uint8 on the device; alpha: a scalar or one value per image -> (stego (N,H,W) uint8, changes (N) int64), both
-    on the device.  'LSBR' needs `seeds`, one 64-bit integer per image (image_seed); 'HILLR' ignores them and takes an optional
-    `key` = ops.hill_cost_f64(cover_u8) made earlier (several alphas of the same covers)."""
+    on the device.  'LSBR' and 'LSBRS' need `seeds`, one 64-bit integer per image (image_seed); 'HILLR' ignores them and takes an optional
+    `key` = ops.hill_cost_f64(cover_u8) made earlier (several alphas of the same covers).  `order` ('rows' / 'rows_up') is the path of
+    'LSBRS'; the other methods have none."""
     from . import ops
     method = method_name(stego_method)
+    _check_order(order)
     if not (isinstance(cover_u8, torch.Tensor) and cover_u8.dim() == 3 and cover_u8.dtype == torch.uint8):
         raise ValueError("simulate: cover_u8 must be an (N,H,W) uint8 tensor")
     n, h, w = cover_u8.shape
@@ -77,20 +96,26 @@ def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, ke
         k = torch.tensor([hillr_rank(v, h, w) for v in a], dtype=torch.int64).to(dev)
         return ops.embed_threshold(cover_u8, key, ops.rank_select_f64(key, k))
     if seeds is None:
-        raise ValueError("simulate: 'LSBR' needs one seed per image (embed.image_seed)")
+        raise ValueError(f"simulate: {method!r} needs one seed per image (embed.image_seed)")
     s = np.array([int(v) % 2 ** 64 for v in (seeds.tolist() if isinstance(seeds, (torch.Tensor, np.ndarray)) else seeds)], dtype=np.uint64)
     if s.shape != (n,):
         raise ValueError(f"simulate: {s.shape[0] if s.ndim else 1} seeds for {n} images")
+    if method == "LSBRS":
+        m = torch.tensor([lsbrs_count(v, h, w) for v in a], dtype=torch.int64).to(dev)
+        return ops.embed_lsbr_seq(cover_u8, torch.from_numpy(s.view(np.int64)).to(dev), m, order)
     t = np.array([ops.lsbr_threshold(v) for v in a], dtype=np.uint32)
     return ops.embed_lsbr(cover_u8, torch.from_numpy(s.view(np.int64)).to(dev), torch.from_numpy(t.view(np.int32)).to(dev))
 
 
 # ---- whole data sets --------------------------------------------------------------------------------------------------------
 
-def folder_name(stego_method: str, alpha: float) -> str:
+def folder_name(stego_method: str, alpha: float, order: str = "rows") -> str:
     """`stego_<METHOD>_alpha_<a>_independent_images`: the reference's folder scheme with the method in upper case, as its files.csv
-    spells it (the reference's own folders say 'HILLr' / 'LSBr' beside 'HILLR' / 'LSBR' in the name column; that mismatch is not copied)."""
-    return f"stego_{method_name(stego_method)}_alpha_{float(alpha)}_independent_images"
+    spells it (the reference's own folders say 'HILLr' / 'LSBr' beside 'HILLR' / 'LSBR' in the name column; that mismatch is not copied).
+    The bottom-up twins of 'LSBRS' (order 'rows_up') go to `stego_LSBRS_alpha_<a>_rows_up_independent_images`."""
+    method = method_name(stego_method)
+    suffix = "_rows_up" if method == "LSBRS" and _check_order(order) == "rows_up" else ""
+    return f"stego_{method}_alpha_{float(alpha)}{suffix}_independent_images"
 
 
 def _prefetch(fnames, kws):
@@ -98,7 +123,7 @@ def _prefetch(fnames, kws):
     return (read_luma_batch(fnames),)
 
 
-def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, prefetched=None):
+def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, order="rows", prefetched=None):
     """One chunk of covers -> their twins at every alpha, written as 8-bit gray PNGs; one list of files.csv rows per cover."""
     from PIL import Image
     from . import ops
@@ -106,11 +131,11 @@ def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, prefetch
     cover = torch.from_numpy(np.ascontiguousarray(planes)).to("cuda")
     method = method_name(stego_method)
     key = ops.hill_cost_f64(cover) if method == "HILLR" else None
-    seeds = [image_seed(f, stream) for f in fnames] if method == "LSBR" else None
+    seeds = [image_seed(f, stream) for f in fnames] if method in ("LSBR", "LSBRS") else None
     rows = [[] for _ in fnames]
     for a in alphas:
-        stego = simulate(cover, method, a, seeds, key=key)[0].cpu().numpy()
-        folder = folder_name(method, a)
+        stego = simulate(cover, method, a, seeds, key=key, order=order)[0].cpu().numpy()
+        folder = folder_name(method, a, order)
         (pathlib.Path(out_dir) / folder).mkdir(parents=True, exist_ok=True)
         for i, f in enumerate(fnames):
             name = f"{folder}/{pathlib.Path(f).stem}.png"
@@ -120,35 +145,38 @@ def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, prefetch
 
 
 _write_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(
-    fabrika.shared_kwargs(_write_chunk, ("stego_method", "alphas", "stream", "out_dir"), _prefetch))
+    fabrika.shared_kwargs(_write_chunk, ("stego_method", "alphas", "stream", "out_dir", "order"), _prefetch))
 
 
-def write_dataset(data_dir, stego_method: str, alpha, *, split: typing.Optional[str] = None, stream: int = 0) -> typing.List[pathlib.Path]:
+def write_dataset(data_dir, stego_method: str, alpha, *, split: typing.Optional[str] = None, stream: int = 0,
+                  order: str = "rows") -> typing.List[pathlib.Path]:
     """Twins of every cover of `data_dir` (images*/files.csv, or the rows of `split`) at `alpha` (one value or several), written
-    beside the covers; returns the folders.  A folder's files.csv lists exactly the files of this call."""
+    beside the covers; returns the folders.  A folder's files.csv lists exactly the files of this call.  `order`: the path of 'LSBRS'."""
     import pandas as pd
     data_dir = pathlib.Path(data_dir)
     method = method_name(stego_method)
+    _check_order(order)
     alphas = [float(a) for a in np.atleast_1d(np.asarray(alpha, dtype=np.float64))]
     _alphas(alphas, len(alphas))
-    rows = _write_covers(data_dir, split=split, stego_method=method, alphas=alphas, stream=int(stream), out_dir=str(data_dir))
+    rows = _write_covers(data_dir, split=split, stego_method=method, alphas=alphas, stream=int(stream), out_dir=str(data_dir), order=order)
     folders = []
     for j, a in enumerate(alphas):
-        folder = data_dir / folder_name(method, a)
+        folder = data_dir / folder_name(method, a, order)
         pd.DataFrame([r[j] for r in rows], columns=["name", "height", "width", "stego_method", "alpha"]).to_csv(folder / "files.csv", index=False)
         folders.append(folder)
     return folders
 
 
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(description="Write simulated stego twins of a data set's covers (HILLR / LSBR, made on the GPU).")
+    ap = argparse.ArgumentParser(description="Write simulated stego twins of a data set's covers (HILLR / LSBR / LSBRS, made on the GPU).")
     ap.add_argument("--data", required=True, help="data set directory (images*/files.csv)")
     ap.add_argument("--stego-method", required=True, help=" / ".join(METHODS))
     ap.add_argument("--alphas", type=float, nargs="+", required=True, help="embedding rates in [0, 1]")
     ap.add_argument("--split", default=None, help="a split CSV of the data set: only its covers")
-    ap.add_argument("--stream", type=int, default=0, help="LSBR realisation number (image_seed)")
+    ap.add_argument("--stream", type=int, default=0, help="LSBR / LSBRS realisation number (image_seed)")
+    ap.add_argument("--order", choices=ORDERS, default="rows", help="LSBRS: the message runs row by row from the top, or from the bottom row up")
     ns = ap.parse_args(argv)
-    for folder in write_dataset(ns.data, ns.stego_method, ns.alphas, split=ns.split, stream=ns.stream):
+    for folder in write_dataset(ns.data, ns.stego_method, ns.alphas, split=ns.split, stream=ns.stream, order=ns.order):
         print(folder)
 
 

@@ -1033,6 +1033,54 @@ def ws_attack(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, x_bia
     return (beta, sums) if return_sums else beta
 
 
+ORDERS = ("rows", "rows_up")               # path orders of the sequential statistic and simulator: rows from the top / from the bottom
+
+
+def order_id(order) -> int:
+    """'rows' -> 0 (row by row from the top), 'rows_up' -> 1 (from the bottom row upwards); anything else raises ValueError."""
+    if order not in ORDERS:
+        raise ValueError(f"unknown order {order!r}; choose from {ORDERS}")
+    return ORDERS.index(order)
+
+
+def ws_sequential(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, mean_filter=None,
+                  hat_scale: float = 255., weighted: int = 1, order: str = "rows", return_curve: bool = False):
+    """The WS changepoint of a sequentially placed payload (wsu_ws_sequential, K27).  x_u8: (N,H,W) uint8; the prediction as for
+    ws_attack: x_hat (N,H,W)/(N,1,H,W) full frames or (N,H-2,W-2) interiors, multiplied by `hat_scale`, or `pixel_filter` (3,3[,1]) for an
+    in-kernel linear predictor, (N,3,3[,1]) for one per image.  weighted: 0 or 1.  order: 'rows' (the path takes the interior rows from
+    the top) or 'rows_up' (from the bottom).  Returns int64 (N,) tensors (k, t_max, t_all[, curve (N,H-2)]): the first maximiser k in
+    0..(H-2)(W-2) of the fixed-point cumulative statistic T (2^24 units), T(k), T at the path's end, and T at the end of every row."""
+    if int(weighted) not in (0, 1):
+        raise ValueError(f"ws_sequential: weighted must be 0 or 1 (weighted=-1 is not defined for the sequential statistic), got {weighted}")
+    if (x_hat is None) == (pixel_filter is None):
+        raise ValueError("ws_sequential: give exactly one of x_hat / pixel_filter")
+    oid = order_id(order)
+    lib = _lib.load()
+    _dev_check(x_u8, *[t for t in (x_hat,) if t is not None])
+    n, h, w = _u8_planes(x_u8)
+    mt = filter_taps(mean_filter, np.float32, "kernel")
+    dev = x_u8.device
+    k, t_max, t_all = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+    curve = torch.empty((n, h - 2), dtype=torch.int64, device=dev) if return_curve else None
+    ws = torch.empty(max(lib.wsu_ws_sequential_workspace_bytes(n, h) // 8, 1), dtype=torch.int64, device=dev)
+    pt = pts = None
+    hat_full = 1
+    if pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3):      # (N,3,3[,1])
+        if len(pixel_filter) != n:
+            raise ValueError(f"ws_sequential: {len(pixel_filter)} filters for {n} images")
+        pts = torch.from_numpy(np.stack([filter_taps(f, np.float32, "kernel") for f in pixel_filter])).to(dev)
+    elif pixel_filter is not None:
+        pt = filter_taps(pixel_filter, np.float32, "kernel")
+    else:
+        hat_full = _hat_full(x_hat, n, h, w, None)
+    check(_launch("ws_sequential", {"bytes": float(n * h * w * (1 if x_hat is None else 5))}, lambda: lib.wsu_ws_sequential(
+        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
+        pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
+        oid, k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), curve.data_ptr() if curve is not None else None,
+        ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())), "wsu_ws_sequential")
+    return (k, t_max, t_all, curve) if return_curve else (k, t_max, t_all)
+
+
 def ols_moments(x_u8: torch.Tensor) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,45) int64: per image the exact sums of v_i * v_j, i <= j (row-major upper triangle), over the interior
     pixels, v = the eight neighbours in ring order (_RING) and the centre (wsu_ols_moments, K24; ws_unet_amd.ols unpacks and solves)."""
@@ -1164,6 +1212,23 @@ def embed_lsbr(cover_u8: torch.Tensor, seeds: torch.Tensor, thresholds: torch.Te
     changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
     check(_launch("embed_lsbr", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbr(
         cover_u8.data_ptr(), seeds.data_ptr(), thresholds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_lsbr")
+    return stego, changes
+
+
+def embed_lsbr_seq(cover_u8: torch.Tensor, seeds: torch.Tensor, counts: torch.Tensor, order="rows") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Sequential LSB replacement (K28): the first counts[i] pixels of the path over the whole plane ('rows': row by row from the top,
+    'rows_up': from the bottom row upwards) flip as under embed_lsbr at alpha = 1.  seeds: (N) int64 holding the 64-bit seeds; counts:
+    (N) int64 -> (stego (N,H,W) uint8, changes (N) int64)."""
+    oid = order_id(order)
+    lib = _lib.load()
+    n, h, w = _u8_planes(cover_u8)
+    _dev_check(seeds, counts)
+    assert seeds.dtype == torch.int64 and seeds.shape == (n,) and counts.dtype == torch.int64 and counts.shape == (n,)
+    stego = torch.empty_like(cover_u8)
+    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
+    check(_launch("embed_lsbr_seq", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbr_seq(
+        cover_u8.data_ptr(), seeds.data_ptr(), counts.data_ptr(), oid, stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())),
+        "wsu_embed_lsbr_seq")
     return stego, changes
 
 

@@ -11,6 +11,9 @@ kernel, wsu_ws_attack; there is no host implementation in this package.
     threaded PNG decode -> one u8 upload -> UNet forward(s) -> statistic -> 4 bytes per image back.
   * the model names of `structural.NAMES` ('SPA', 'RS') are no pixel predictors but whole estimators of their own (ws/structural.py:
     an exact count kernel and a float64 solve); they go through the same drivers, unweighted and without bias correction.
+  * `placement='sequential'` (with `order='rows'` or 'rows_up') replaces the statistic by the changepoint estimator for payloads written
+    into the first pixels of the file order (ws/sequential.py, wsu_ws_sequential): every pixel predictor works, the structural
+    estimators, weighted=-1 and correct_bias do not.  The default, placement='random', is the reference's statistic.
   * `run(..., batched=True)` is `run` on the batched iterators; the joblib iterators of the reference (:139,144) cannot
     carry a GPU model into worker processes, so the per-image decorators use iterator='python'.
 
@@ -30,7 +33,7 @@ from .. import fabrika, filters, ols, ops
 from ..imread import imread4_u8, u8_plane
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import check_unet_geometry, model_device, unet_plane
-from . import structural
+from . import sequential, structural
 
 NAMED_FILTERS = filters.NAMED_FILTERS_2D
 
@@ -91,8 +94,32 @@ def _unet_planes(model, x_u8: torch.Tensor, correct_bias: bool):
     return y, yb
 
 
-def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=None) -> torch.Tensor:
+def _changepoint(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, order, host_planes=None, return_curve=False):
+    """ops.ws_sequential's (k, t_max, t_all[, curve]) on the device for a batch of planes, with any pixel predictor `_stat` knows."""
+    kw = dict(mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted), order=order, return_curve=return_curve)
+    if isinstance(pixel_estimator, UNetEstimator):
+        check_unet_geometry(x_u8.shape[1:], "the UNet estimator")
+        return ops.ws_sequential(x_u8, unet_plane(pixel_estimator.model, x_u8), hat_scale=255.0, **kw)
+    if isinstance(pixel_estimator, filters.FilterEstimator):
+        return ops.ws_sequential(x_u8, None, pixel_filter=np.asarray(pixel_estimator.kernel)[..., ::-1], **kw)
+    if isinstance(pixel_estimator, ols.AdaptiveOLSEstimator):
+        return ops.ws_sequential(x_u8, None, pixel_filter=pixel_estimator.kernels(x_u8)[..., ::-1], **kw)
+    hats = []                                               # arbitrary host callable: the interior layout, scale 1
+    for xf in host_planes:
+        h = np.asarray(pixel_estimator(xf), dtype=np.float32)
+        if h.shape[:2] != (xf.shape[0] - 2, xf.shape[1] - 2):
+            raise ValueError(f"pixel_estimator returned {h.shape} for an image of {xf.shape}")
+        hats.append(h[..., 0])
+    return ops.ws_sequential(x_u8, torch.from_numpy(np.stack(hats)).to(x_u8.device), hat_scale=1.0, **kw)
+
+
+def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=None, placement="random",
+          order="rows") -> torch.Tensor:
     """beta_hat[N] on the device for a batch of planes."""
+    _check_options(pixel_estimator, weighted, correct_bias, placement, order)
+    if placement == "sequential":                                      # the changepoint k -> the change rate of the whole plane
+        k = _changepoint(x_u8, pixel_estimator, mean_estimator, weighted, order, host_planes)[0]
+        return sequential.beta(k, x_u8.shape[1], x_u8.shape[2], order).to(torch.float32)
     if isinstance(pixel_estimator, structural.StructuralEstimator):    # no predictor, no weights: the estimator is the statistic
         structural.require_unweighted(weighted, correct_bias)
         return pixel_estimator.beta(x_u8).to(torch.float32)
@@ -121,11 +148,23 @@ def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct
     return ops.ws_attack(x_u8, x_hat, x_bias=x_bias, hat_scale=1.0, **kw)
 
 
-def _check_options(pixel_estimator, weighted, correct_bias) -> None:
+def _check_options(pixel_estimator, weighted, correct_bias, placement="random", order="rows") -> None:
     """An option an estimator does not have is the caller's error, not an image without an estimate (`attack` turns a ValueError of
     the statistic into beta_hat = None, as the reference does)."""
-    if isinstance(pixel_estimator, structural.StructuralEstimator):
+    sequential.check_placement(placement, order)
+    if placement == "sequential":
+        if isinstance(pixel_estimator, structural.StructuralEstimator):
+            raise ValueError(f"placement='sequential' needs a pixel predictor; the structural estimators {structural.NAMES} have none")
+        if int(weighted) not in (0, 1) or correct_bias:
+            raise ValueError(f"placement='sequential' takes weighted 0 or 1 and correct_bias=False, got weighted={weighted} "
+                             f"correct_bias={correct_bias}")
+    elif isinstance(pixel_estimator, structural.StructuralEstimator):
         structural.require_unweighted(weighted, correct_bias)
+
+
+def _placement_tail(placement, order) -> dict:
+    """The row columns of a placement other than the default: existing tables keep their columns."""
+    return {} if placement == "random" else {"placement": placement, "order": order}
 
 
 def attack(
@@ -137,14 +176,18 @@ def attack(
     weighted: bool = 1,
     imread: typing.Callable = None,
     process_image: typing.Callable = None,
+    placement: str = "random",
+    order: str = "rows",
     **kw,
 ) -> dict:
-    """WS estimate of one image (estimate.py:55-136): returns kw | {beta_hat, channels, weighted, correct_bias}."""
-    _check_options(pixel_estimator, weighted, correct_bias)
+    """WS estimate of one image (estimate.py:55-136): returns kw | {beta_hat, channels, weighted, correct_bias}; with
+    placement='sequential' the changepoint estimate of ws/sequential.py, and the row also says placement and order."""
+    _check_options(pixel_estimator, weighted, correct_bias, placement, order)
     x = process_image(imread(fname))                         # x_bar = process(x ^ 1) is formed on the device
     try:
         x_u8 = torch.from_numpy(_as_u8_plane(x))[None].to(model_device(unet_model_of(pixel_estimator)))
-        beta_hat = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=[x])[0].item()
+        beta_hat = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=[x], placement=placement,
+                         order=order)[0].item()
         beta_hat = np.float32(beta_hat)
     except ValueError:                                      # estimate.py:122-123
         beta_hat = None
@@ -153,7 +196,7 @@ def attack(
         "channels": "".join(map(str, channels)),
         "weighted": weighted,
         "correct_bias": correct_bias,
-    }
+    } | _placement_tail(placement, order)
 
 
 @fabrika.precovers(iterator="python", ignore_missing=True)
@@ -176,9 +219,9 @@ def _native_planes_ok(channels, pixel_estimator, imread, process_image) -> bool:
 
 
 def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED_FILTERS["AVG"], correct_bias=False,
-                 weighted=1, imread=imread4_u8, process_image=None, prefetched=None, **_ignored):
+                 weighted=1, imread=imread4_u8, process_image=None, prefetched=None, placement="random", order="rows", **_ignored):
     """`attack` for a chunk of files (fabrika iterator='batched'): one result dict per (fname, kw)."""
-    _check_options(pixel_estimator, weighted, correct_bias)
+    _check_options(pixel_estimator, weighted, correct_bias, placement, order)
     if _native_planes_ok(channels, pixel_estimator, imread, process_image):
         u8 = prefetched[0] if prefetched is not None else load_planes_u8(fnames, imread)
         planes = None if u8 is None else [None] * len(fnames)
@@ -190,20 +233,21 @@ def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED
             planes = None
     if planes is None:
         process_image = process_image or filters.get_processor_2d(channels)
-        return [attack(f, channels, pixel_estimator, mean_estimator, correct_bias, weighted, imread, process_image, **kw)
+        return [attack(f, channels, pixel_estimator, mean_estimator, correct_bias, weighted, imread, process_image, placement, order, **kw)
                 for f, kw in zip(fnames, kws)]
     try:
         if u8 is None:
             u8 = torch.from_numpy(np.stack([_as_u8_plane(p) for p in planes]))
         x_u8 = upload_planes(u8, model_device(unet_model_of(pixel_estimator)))
-        beta = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=planes).cpu().numpy()
+        beta = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=planes, placement=placement,
+                     order=order).cpu().numpy()
     except ValueError:
         beta = [None] * len(fnames)
-    tail = {"channels": "".join(map(str, channels)), "weighted": weighted, "correct_bias": correct_bias}
+    tail = {"channels": "".join(map(str, channels)), "weighted": weighted, "correct_bias": correct_bias} | _placement_tail(placement, order)
     return [kw | {"beta_hat": beta[i]} | tail for i, kw in enumerate(kws)]
 
 
-_ATTACK_KEYS = ("channels", "pixel_estimator", "mean_estimator", "correct_bias", "weighted", "imread", "process_image")
+_ATTACK_KEYS = ("channels", "pixel_estimator", "mean_estimator", "correct_bias", "weighted", "imread", "process_image", "placement", "order")
 
 
 def _prefetch_native(fnames, kws):
@@ -229,11 +273,14 @@ def run(
     **kw,
 ):
     """WS attack over a data set with a named linear filter or a trained UNet as the pixel predictor (estimate.py:149-205), or one of
-    the structural estimators of ws/structural.py ('SPA', 'RS': weighted=0, correct_bias=False) in the same rows."""
+    the structural estimators of ws/structural.py ('SPA', 'RS': weighted=0, correct_bias=False) in the same rows.  placement='sequential'
+    (with order='rows' / 'rows_up') among the keywords: the changepoint estimator of ws/sequential.py with the same predictors."""
     process_cover = filters.get_processor_2d(channels=channels)
+    placed = (kw.get("placement", "random"), kw.get("order", "rows"))
+    _check_options(None, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
     if model_name in structural.NAMES:
         pixel_estimator = structural.StructuralEstimator(model_name)
-        _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False))
+        _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
     elif model_name in ols.ADAPTIVE_NAMES:                       # 'OLSa' / 'OLSa2': the least-squares filter of each image under attack
         pixel_estimator = ols.adaptive_estimator(model_name)
     elif model_name in NAMED_FILTERS:
@@ -279,6 +326,9 @@ def parse_args(argv=None):
     ap.add_argument("--weighted", type=int, default=0)
     ap.add_argument("--correct-bias", action="store_true")
     ap.add_argument("--per-image", action="store_true", help="use the per-image iterators instead of the batched ones")
+    ap.add_argument("--placement", choices=sequential.PLACEMENTS, default="random",
+                    help="where the payload is assumed to lie: spread uniformly (the WS statistic) or in the first pixels of the file order")
+    ap.add_argument("--order", choices=sequential.ORDERS, default="rows", help="sequential placement: rows from the top, or from the bottom")
     ap.add_argument("--out", default=None)
     ols.add_kernels_argument(ap)
     return ap.parse_args(argv)
@@ -295,6 +345,8 @@ def main(argv=None) -> None:
     model_dir = pathlib.Path(a.model_dir)
     settings = [(None, .0)] + [(sm, al) for sm in a.stego_methods for al in a.alphas]
     common = dict(demosaic=None, channels=(3,), correct_bias=a.correct_bias, weighted=a.weighted, batched=not a.per_image)
+    if a.placement != "random":
+        common |= dict(placement=a.placement, order=a.order)
     res = []
     for stego_method, alpha in settings:
         for model_name in a.filters:

@@ -157,23 +157,24 @@ def _prefetch(fnames, kws):
     return (load_planes_u8(fnames),)
 
 
-def _submit(fnames, clean, *, predictors, prefetched=None):
+def _submit(fnames, clean, *, predictors, placement="random", order="rows", prefetched=None):
     """Upload the chunk once and queue every predictor's statistic (ws.estimate._stat) on it; nothing waits for the GPU.  A ragged
     chunk goes through ws.estimate.attack image by image, as ws.estimate.attack_batch does."""
     from . import estimate
     planes = prefetched[0] if prefetched is not None else load_planes_u8(fnames)
     if planes is None:
         proc = filters_lib.get_processor_2d((3,))
-        return "host", [[estimate.attack(f, (3,), est, estimate.NAMED_FILTERS["AVG"], False, 0, imread4_u8, proc, **{**kw, "model_name": name})
+        return "host", [[estimate.attack(f, (3,), est, estimate.NAMED_FILTERS["AVG"], False, 0, imread4_u8, proc, placement, order,
+                                        **{**kw, "model_name": name})
                          for name, est in predictors] for f, kw in zip(fnames, clean)]
     x = upload_planes(planes, model_device(estimate.unet_model_of(predictors[-1][1])))
     betas = []
     for _, est in predictors:
         try:
-            betas.append(estimate._stat(x, est, estimate.NAMED_FILTERS["AVG"], 0, False))
+            betas.append(estimate._stat(x, est, estimate.NAMED_FILTERS["AVG"], 0, False, placement=placement, order=order))
         except ValueError:                                   # ws.estimate.attack_batch: no estimate for this chunk
             betas.append(None)
-    return "device", (clean, [name for name, _ in predictors], betas)
+    return "device", (clean, [name for name, _ in predictors], betas, estimate._placement_tail(placement, order))
 
 
 def _collect(handle):
@@ -181,9 +182,9 @@ def _collect(handle):
     kind, val = handle
     if kind == "host":
         return val
-    clean, names, betas = val
+    clean, names, betas, placed = val
     betas = [b.cpu().numpy() if b is not None else [None] * len(clean) for b in betas]
-    tail = {"channels": "3", "weighted": 0, "correct_bias": False}
+    tail = {"channels": "3", "weighted": 0, "correct_bias": False} | placed
     return [[{**kw, "model_name": name, "beta_hat": betas[p][i], **tail} for p, name in enumerate(names)] for i, kw in enumerate(clean)]
 
 
@@ -192,20 +193,23 @@ def _score_chunk(fnames, kws, prefetched=None, **shared):
 
 
 _score_chunk.submit, _score_chunk.collect = _submit, _collect
-_score_chunk = fabrika.shared_kwargs(_score_chunk, ("predictors",), _prefetch)
+_score_chunk = fabrika.shared_kwargs(_score_chunk, ("predictors", "placement", "order"), _prefetch)
 _score_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(_score_chunk)
 _score_stegos = fabrika.stego_spatial(iterator="batched", convert_to=None, ignore_missing=True)(_score_chunk)
 
 
 def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_METHODS, alphas: typing.Sequence[float] = ALPHAS,
-                      filters: typing.Sequence[str] = WS_FILTERS, unet=None, mode: str = None, progress_on: bool = False, **kw):
+                      filters: typing.Sequence[str] = WS_FILTERS, unet=None, mode: str = None, progress_on: bool = False,
+                      placement: str = "random", order: str = "rows", **kw):
     """The WS rows the reference's main concatenates (roc.py:372-395): for the cover set, then each stego method x alpha, the rows of
     ws.estimate.run(..., weighted=0, correct_bias=False, channels=(3,), batched=True) of each named filter (or structural estimator,
     'SPA' / 'RS', whose curves are labelled with their own names, not 'WS-<name>') and then of the UNet
     (model_name 'UNet'), concatenated, index reset, stego_method NaN -> 'Cover', alpha NaN -> 0.  The same frame, but each image is
     decoded (native PNG reader, one chunk ahead) and uploaded once, and every predictor's statistic runs on that device batch.
     unet: None (no UNet rows), a ws.estimate.UNetEstimator, a model, or (model_path, model_name) of a trained run loaded in
-    inference `mode`.  Other keywords go to the fabrika iterators (take_num_images, split, ...)."""
+    inference `mode`.  placement='sequential' (with `order`) scores every image with the changepoint estimator of ws/sequential.py instead
+    (pixel predictors only); the rows then also carry `placement` and `order`.  Other keywords go to the fabrika iterators
+    (take_num_images, split, ...)."""
     import pandas as pd
     from . import estimate
     from .. import ols
@@ -221,13 +225,16 @@ def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_MET
         preds.append(("UNet", est))
     if not preds:
         raise ValueError("no predictor: give filters and / or a UNet")
+    for _, p in preds:                                       # an option a predictor does not have is an error up front, not an empty curve
+        estimate._check_options(p, 0, False, placement, order)
+    placed = dict(placement=placement, order=order) if placement != "random" else {}
     frames = []
     for stego_method, alpha in [(None, None)] + [(sm, al) for sm in stego_methods for al in alphas]:
         if stego_method:
             rows = _score_stegos(input_dir, inbayer=None, stego_method=stego_method, alpha=alpha, model_name=None, predictors=preds,
-                                 progress_on=progress_on, **kw)
+                                 progress_on=progress_on, **placed, **kw)
         else:
-            rows = _score_covers(input_dir, inbayer=None, model_name=None, predictors=preds, progress_on=progress_on, **kw)
+            rows = _score_covers(input_dir, inbayer=None, model_name=None, predictors=preds, progress_on=progress_on, **placed, **kw)
         for p in range(len(preds)):                          # ws.estimate.run's frame of predictor p on this set
             res = pd.DataFrame([r[p] for r in rows])
             res["channels"] = "3"
@@ -280,6 +287,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "stego_method) added as model NAME, which must contain 'B0'; repeatable")
     ap.add_argument("--mode", default=None, help="UNet inference mode (default: the package default)")
     ap.add_argument("--progress", action="store_true")
+    ap.add_argument("--placement", choices=("random", "sequential"), default="random",
+                    help="where the payload is assumed to lie: spread uniformly (the WS statistic) or in the first pixels of the file order")
+    ap.add_argument("--order", choices=("rows", "rows_up"), default="rows", help="sequential placement: rows from the top, or from the bottom")
     from ..ols import add_kernels_argument
     add_kernels_argument(ap)
     return ap.parse_args(argv)
@@ -297,7 +307,8 @@ def main(argv=None) -> None:
         from ..evaluate import trained_runs
         (method, model_name, _), = trained_runs(a.model_dir, [a.train_method])
         unet = (pathlib.Path(a.model_dir) / method, model_name)
-    res = collect_ws_scores(a.data, a.stego_methods, a.alphas, a.filters, unet=unet, mode=a.mode, progress_on=a.progress)
+    res = collect_ws_scores(a.data, a.stego_methods, a.alphas, a.filters, unet=unet, mode=a.mode, progress_on=a.progress, placement=a.placement,
+                            order=a.order)
     res = pd.concat([res] + detectors).reset_index(drop=True)
     res["stego_method"] = res["stego_method"].fillna("Cover")
     res["alpha"] = res["alpha"].fillna(0.)
