@@ -404,6 +404,23 @@ int wsu_ws_sequential(const uint8_t* x_u8, const float* x_hat, const float* pixe
                       int hat_full, float hat_scale, int weighted, int order, long long* k, long long* t_max, long long* t_all,
                       long long* curve, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
 
+/* ---- K29: per-pixel sums of the WS residual terms across images (Ker, "Locating steganographic payload via WS residuals", MM&Sec 2008;
+ *      not part of the reference).  Inputs as K27's: x_u8 (N,H,W) DEVICE pixels, exactly ONE of x_hat (hat_full, hat_scale) /
+ *      pixel_filter (HOST) / pixel_filters (DEVICE (N,9)), mean_filter (HOST) for weighted = 1; weighted = -1 is an argument error.
+ *      num, den: DEVICE int64 (H-2,W-2), 8-byte aligned.  The call ADDS to them (the caller zeroes them before the first batch): per
+ *      interior pixel and image, in float32 with K11's operation sequence and nothing contracted,
+ *        r = s * res;   t = wgt * r,   wgt = 1.0f or 1.0f / (5.0f + var);
+ *        where t is NaN nothing is added, otherwise
+ *        num += llrint((double)min(max(t, -4096), 4096) * 2^24);      den += llrint((double)wgt * 2^32)          (round to nearest even).
+ *      The weighted mean of r at a pixel is (num / 2^24) / (den / 2^32) = num * 256 / den: about 1/2 where every image carries payload,
+ *      about 0 where none does.  All sums are exact integers, so the accumulators depend on neither the split of the images into calls,
+ *      their order, nor `parts`: the number of workgroups that share a pixel tile's images (1: one owner per pixel and plain stores;
+ *      more: 64-bit integer atomics; 0: as many as bring the grid to about 4096 workgroups, the fastest measured).  After at most 65536 images in total |num| < 2^53 and, for the
+ *      weights of a non-negative mean filter (wgt <= 1), den < 2^53.  n <= 65535, h, w >= 3, (H-2)(W-2) <= 2^31. */
+int wsu_ws_residual_accumulate(const uint8_t* x_u8, const float* x_hat, const float* pixel_filter, const float* pixel_filters,
+                               const float* mean_filter, int hat_full, float hat_scale, int weighted, int parts, long long* num, long long* den,
+                               int n, int h, int w, void* stream);
+
 /* ---- K24: moments of the least-squares 3x3 pixel predictor.  x_u8: (N,H,W) DEVICE pixels.  At every interior pixel (r,c), with
  *      xab = x[r-1+a][c-1+b], v = [x00 x01 x02 x12 x22 x21 x20 x10 x11] (the ring order of the flattened 8-tap filters,
  *      _defs/filters.py:57-67, centre last).  moments: DEVICE (N,45) uint64, zeroed on the stream by this call:
@@ -529,7 +546,7 @@ size_t wsu_roc_counts_workspace_bytes(int groups, int t);
 int wsu_roc_counts(const double* scores, const signed char* labels, const long long* offsets, int groups, const double* taus, int t,
                    long long* counts, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- K20-K23, K28: the stego simulators HILLR, LSBR and LSBRS.  The reference's stego twins were made by a library outside its tree; HILLR is
+/* ---- K20-K23, K28, K30: the stego simulators HILLR, LSBR, LSBRS and LSBRK.  The reference's stego twins were made by a library outside its tree; HILLR is
  *      pinned to them bit for bit (tests/golden/stego_HILLR_*), LSBR's realisation is defined here.  Every plane is DEVICE (N,H,W) and
  *      contiguous; H, W >= 1, H*W < 2^32, N <= 65535.  stego may alias cover.  Deterministic: integer atomics only, two calls give the
  *      same bits, and an image's result does not depend on its position in the batch or on the batch size.
@@ -572,6 +589,17 @@ int wsu_embed_lsbr(const uint8_t* cover, const uint64_t* seeds, const uint32_t* 
  *      here); seeds, changes, limits and aliasing as in K23. */
 int wsu_embed_lsbr_seq(const uint8_t* cover, const uint64_t* seeds, const long long* counts, int order, uint8_t* stego, long long* changes,
                        int n, int h, int w, void* stream);
+
+/* K30: LSBRK, LSB replacement at the positions a stego key selects, the same in every image: pixel i (linear index) is USED iff
+ *      key word < alpha_threshold, compared in 64 bits, key word = word i % 4 of Philox4x32-10 on counter (i / 4, 0, 0, 0) under the key
+ *      (low, high word of key_seed); alpha_threshold = floor(alpha * 2^32) in 0..2^32, so alpha = 1 uses every pixel.  A used pixel flips
+ *      iff it flips under K23 at alpha = 1 with its image's seed (the same word under seeds[image] < 2^31).  So at alpha_threshold = 2^32
+ *      the twin is K23's alpha = 1 twin bit for bit, at 0 it is the cover, and the flips are a subset of the used positions, which depend
+ *      on (key_seed, alpha_threshold, H, W) alone.  seeds, changes, limits and aliasing as in K23.
+ *      wsu_lsbr_key_mask writes those used positions as a DEVICE (H,W) uint8 plane of 1 / 0. */
+int wsu_embed_lsbr_keyed(const uint8_t* cover, const uint64_t* seeds, uint64_t key_seed, uint64_t alpha_threshold, uint8_t* stego,
+                         long long* changes, int n, int h, int w, void* stream);
+int wsu_lsbr_key_mask(uint64_t key_seed, uint64_t alpha_threshold, uint8_t* mask, int h, int w, void* stream);
 
 /* Linear pixel predictor on its own (filters/evaluate.py:136-141): y (N,H-2,W-2) = convolve(x/255., K, 'valid')*255.
  * x: DEVICE (N,H,W) fp32; filter: HOST 9 floats K[a][b]. */

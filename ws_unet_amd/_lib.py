@@ -97,6 +97,7 @@ SIGNATURES = {
     "wsu_ws_attack_taps": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
     "wsu_ws_sequential_workspace_bytes": (c_size_t, [c_int, c_int]),
     "wsu_ws_sequential": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_int] + [_P] * 5 + [c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_ws_residual_accumulate": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_int, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_ols_moments": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_spa_tables": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_rs_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
@@ -122,6 +123,8 @@ SIGNATURES = {
     "wsu_lsbr_threshold": (c_int, [c_double, _P]),
     "wsu_embed_lsbr": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_embed_lsbr_seq": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    "wsu_embed_lsbr_keyed": (c_int, [_P, _P, c_uint64, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
+    "wsu_lsbr_key_mask": (c_int, [c_uint64, c_uint64, _P, c_int, c_int, _P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_u8_to_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     "wsu_pair_batch_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P]),

@@ -1,4 +1,4 @@
-// K20-K23, K28: the stego simulators HILLR, LSBR and LSBRS (the reference ships ready-made twins of its five covers, made by a library outside its
+// K20-K23, K28, K30: the stego simulators HILLR, LSBR, LSBRS and LSBRK (the reference ships ready-made twins of its five covers, made by a library outside its
 // tree; tests/golden/stego_HILLR_* pins HILLR to those files bit for bit, LSBR's realisation is this package's own):
 //
 //   HILLR   key = HILL cost in float64 (the operation order of tests/hill_np.hill_cost), full frame
@@ -8,6 +8,8 @@
 //           under the image's 64-bit seed as key (low, high), i = the pixel's linear index in its image
 //   LSBRS   stego = cover ^ (path position of i < m  and  word < 2^31),  m = floor(alpha * H * W): LSBR at alpha = 1 on the first m pixels
 //           of the path over the whole plane, row by row from the top or from the bottom (K28)
+//   LSBRK   stego = cover ^ (key word < T  and  word < 2^31),  T = floor(alpha * 2^32) compared in 64 bits, key word = the same Philox word
+//           under the 64-bit stego key shared by all images: LSBR at alpha = 1 on the pixels the key selects (K30)
 //
 // K20 is K12 in float64 on a 32 x 32 tile (the float64 arrays of a 64 x 64 tile would need 97 KB of LDS; a 32 x 32 tile needs 36 KB
 // and stays static): every sum is a direct sum in numpy's order, the two divisions are IEEE divisions, nothing is contracted.  K21 is an
@@ -345,6 +347,64 @@ __global__ __launch_bounds__(256) void embed_lsbr_seq_kernel(const uint8_t* __re
     add_changes(cnt, changes + nn, tid);
 }
 
+// K30.  LSBRK: the message occupies the pixels a stego key selects, the same in every image: pixel i is used iff word i % 4 of counter
+// (i / 4, 0, 0, 0) under the key is below `thr` (floor(alpha * 2^32), up to 2^32: 64-bit comparison); a used pixel flips as under K23 at
+// alpha = 1 with the image's own seed.  A quad without a used pixel costs one generator call, not two.  MASK: the used positions
+// themselves (1 / 0), one plane, no cover.
+__device__ __forceinline__ uint32_t below_bytes(const Words4& wd, uint64_t thr) {        // byte e = (word e < thr)
+    uint32_t m = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) m |= ((uint64_t)wd.v[e] < thr ? 1u : 0u) << (8 * e);
+    return m;
+}
+__device__ __forceinline__ uint32_t word_of(const Words4& wd, int e) {                   // (selects: a dynamic index would put the words in LDS)
+    return e == 0 ? wd.v[0] : e == 1 ? wd.v[1] : e == 2 ? wd.v[2] : wd.v[3];
+}
+
+template <bool MASK>
+__global__ __launch_bounds__(256) void embed_lsbr_keyed_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ seeds,
+                                                               uint64_t key, uint64_t thr, uint8_t* __restrict__ stego,
+                                                               long long* __restrict__ changes, long long hw) {
+    const int nn = blockIdx.y, tid = threadIdx.x;
+    uint8_t* cout = stego + (size_t)nn * hw;
+    const uint8_t* cin = MASK ? cout : cover + (size_t)nn * hw;
+    const uint32_t kk0 = (uint32_t)key, kk1 = (uint32_t)(key >> 32);
+    uint32_t k0 = 0, k1 = 0;
+    if (!MASK) { k0 = (uint32_t)seeds[nn]; k1 = (uint32_t)(seeds[nn] >> 32); }
+    const Span sp = image_span(cin, cout, hw, true);
+    int cnt = 0;
+    for (long long g = (long long)blockIdx.x * 256 + tid; g < sp.groups; g += (long long)gridDim.x * 256) {
+        const long long p = sp.head + 16 * g;                               // a multiple of 4
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (!MASK) v = *reinterpret_cast<const u32x4*>(cin + p);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t on = below_bytes(philox4x32_10((uint32_t)(p / 4 + q), kk0, kk1), thr);
+            if (MASK) {
+                v[q] = on;
+            } else if (on) {
+                const uint32_t flips = below_bytes(philox4x32_10((uint32_t)(p / 4 + q), k0, k1), 0x80000000ull) & on;
+                v[q] ^= flips;
+                cnt += __popc(flips);
+            }
+        }
+        *reinterpret_cast<u32x4*>(cout + p) = v;
+    }
+    for (long long j = (long long)blockIdx.x * 256 + tid; j < sp.bytes; j += (long long)gridDim.x * 256) {
+        const long long i = span_byte_index(sp, j);
+        const int e = (int)(i & 3);
+        const bool on = (uint64_t)word_of(philox4x32_10((uint32_t)(i / 4), kk0, kk1), e) < thr;
+        if (MASK) {
+            cout[i] = on ? 1 : 0;
+        } else {
+            const uint8_t flip = on && word_of(philox4x32_10((uint32_t)(i / 4), k0, k1), e) < 0x80000000u ? 1 : 0;
+            cout[i] = cin[i] ^ flip;
+            cnt += flip;
+        }
+    }
+    if (!MASK) add_changes(cnt, changes + nn, tid);
+}
+
 int embed_blocks(long long hw) {
     const long long b = (hw / 16 + 255) / 256;
     return (int)(b < 1 ? 1 : b > EMB_MAX_BLOCKS ? EMB_MAX_BLOCKS : b);
@@ -435,6 +495,30 @@ int wsu_embed_lsbr_seq(const uint8_t* cover, const uint64_t* seeds, const long l
     if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbr_seq memset");
     hipLaunchKernelGGL(embed_lsbr_seq_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, counts, order, stego, changes, hw, w);
     return wsu_check_launch("embed_lsbr_seq_kernel");
+}
+
+int wsu_embed_lsbr_keyed(const uint8_t* cover, const uint64_t* seeds, uint64_t key_seed, uint64_t alpha_threshold, uint8_t* stego,
+                         long long* changes, int n, int h, int w, void* stream) {
+    WSU_REQUIRE(cover && seeds && stego && changes, "embed_lsbr_keyed: null pointer");
+    WSU_REQUIRE(alpha_threshold <= (1ull << 32), "embed_lsbr_keyed: alpha_threshold=%llu above 2^32", (unsigned long long)alpha_threshold);
+    EMBED_REQUIRE_SHAPE("embed_lsbr_keyed");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long hw = (long long)h * w;
+    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbr_keyed memset");
+    hipLaunchKernelGGL(embed_lsbr_keyed_kernel<false>, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, key_seed, alpha_threshold, stego,
+                       changes, hw);
+    return wsu_check_launch("embed_lsbr_keyed_kernel");
+}
+
+int wsu_lsbr_key_mask(uint64_t key_seed, uint64_t alpha_threshold, uint8_t* mask, int h, int w, void* stream) {
+    const int n = 1;
+    WSU_REQUIRE(mask, "lsbr_key_mask: null pointer");
+    WSU_REQUIRE(alpha_threshold <= (1ull << 32), "lsbr_key_mask: alpha_threshold=%llu above 2^32", (unsigned long long)alpha_threshold);
+    EMBED_REQUIRE_SHAPE("lsbr_key_mask");
+    const long long hw = (long long)h * w;
+    hipLaunchKernelGGL(embed_lsbr_keyed_kernel<true>, dim3(embed_blocks(hw), 1), dim3(256), 0, static_cast<hipStream_t>(stream), nullptr, nullptr,
+                       key_seed, alpha_threshold, mask, nullptr, hw);
+    return wsu_check_launch("embed_lsbr_keyed_kernel");
 }
 
 }  // extern "C"

@@ -62,12 +62,6 @@ template <typename A> __device__ __forceinline__ MaxPrefix<A> mp_wave(MaxPrefix<
     return a;
 }
 
-__device__ __forceinline__ long long ws_seq_term(float t) {
-    if (t != t) return 0;                               // NaN
-    const float c = t < -4096.0f ? -4096.0f : t > 4096.0f ? 4096.0f : t;
-    return __builtin_llrint((double)c * 16777216.0);
-}
-
 __global__ __launch_bounds__(256) void ws_sequential_rows_kernel(
     const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, Taps mean_taps, Taps pixel_taps, const float* __restrict__ image_filters,
     int use_pixel_filter, int hat_full, float hat_scale, int weighted, long long* __restrict__ rows, int h, int w) {

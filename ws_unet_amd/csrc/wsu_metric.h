@@ -1,5 +1,5 @@
-// Device helpers shared by the metric kernels K10-K18 and K27 and the simulators K20-K23 and K28 (pointwise.hip K10 + WS meter,
-// ws_attack.hip, ws_sequential.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's
+// Device helpers shared by the metric kernels K10-K18, K27 and K29 and the simulators K20-K23, K28 and K30 (pointwise.hip K10 + WS meter,
+// ws_attack.hip, ws_sequential.hip, ws_locate.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's
 // taps, the prediction at a pixel, the float32 residual, the WS statistic's per-pixel terms, the HILL cost's input window, the fixed-order
 // block sum and the radix-select steps.
 //
@@ -63,7 +63,7 @@ __device__ __forceinline__ float residual_f32(float x, float y, float scale) {
     return x - xhat;
 }
 
-// ---- the WS statistic's per-pixel terms (K11, K27) ---------------------------------------------------------------------------------
+// ---- the WS statistic's per-pixel terms (K11, K27, K29) ---------------------------------------------------------------------------------
 // At interior pixel (r, c) of the uint8 plane `img` (row stride w), in numpy's float32 operation sequence (src/ws/estimate.py:90-121):
 //   wgt  = 1 (weighted 0) | 1 / (5 + var) (weighted > 0) | 5 + var (weighted < 0),  var = conv(x*x, mean) - conv(x, mean)^2
 //   s    = x - x_bar = +-1
@@ -116,6 +116,14 @@ __device__ __forceinline__ WsTerms ws_pixel_terms(const uint8_t* __restrict__ im
         if (correct_bias) o.bias = xbias[at] * hat_scale;
     }
     return o;
+}
+
+// The fixed-point form of a float32 term t (K27, K29): 0 where t is NaN, else llrint((double)min(max(t, -4096), 4096) * 2^24), round to
+// nearest even.  |q| <= 2^36, so sums of such terms are exact integers whatever their order.
+__device__ __forceinline__ long long ws_seq_term(float t) {
+    if (t != t) return 0;                               // NaN
+    const float c = t < -4096.0f ? -4096.0f : t > 4096.0f ? 4096.0f : t;
+    return __builtin_llrint((double)c * 16777216.0);
 }
 
 // ---- the HILL cost's input window (K12 fp32, K20 fp64) -----------------------------------------------------------------------------

@@ -156,7 +156,7 @@ class PairLoader:
         def training_method(m):                                         # the two methods a network is trained on
             name = embed.method_name(m)
             if name not in ("LSBR", "HILLR"):
-                raise ValueError(f"PairLoader(simulate=True) makes 'LSBR' / 'HILLR' twins; {name!r} (sequential placement) is not a "
+                raise ValueError(f"PairLoader(simulate=True) makes 'LSBR' / 'HILLR' twins; {name!r} is not a "
                                  f"training method: write its twins with embed.write_dataset")
             return name
 

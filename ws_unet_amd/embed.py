@@ -1,5 +1,5 @@
-"""Stego simulators on the device: HILLR, LSBR and LSBRS twins of cover images (wsu_hill_cost_f64, wsu_rank_select_f64,
-wsu_embed_threshold, wsu_embed_lsbr, wsu_embed_lsbr_seq; include/wsu.h K20-K23, K28).
+"""Stego simulators on the device: HILLR, LSBR, LSBRS and LSBRK twins of cover images (wsu_hill_cost_f64, wsu_rank_select_f64,
+wsu_embed_threshold, wsu_embed_lsbr, wsu_embed_lsbr_seq, wsu_embed_lsbr_keyed; include/wsu.h K20-K23, K28, K30).
 
 The reference ships its five covers with ready-made `stego_*` folders from a library outside its tree.  Here a covers-only data
 set gets its twins from the package itself:
@@ -18,6 +18,9 @@ LSBRS is what most LSB-replacement tools do: the message goes into the first m =
 'rows' (row by row from the top) or 'rows_up' (from the bottom row, as BMP-style tools write).  A pixel on that path flips as under LSBR
 at alpha = 1 with the same seed, so LSBRS at alpha = 1 is LSBR at alpha = 1, everything beyond position m is the cover, and a twin at a
 smaller alpha is a prefix of one at a larger alpha (ws.estimate's placement='sequential' is the matching estimator).
+LSBRK is LSB replacement under a shared stego key: the 64-bit `placement_key` selects a fraction alpha of the pixel positions, the same
+in every image of the same size (ops.lsbr_key_mask), and a selected pixel flips as under LSBR at alpha = 1 with the image's seed.  So
+LSBRK at alpha = 1 is LSBR at alpha = 1 and at alpha = 0 the cover (ws.locate finds the selected positions from many such images).
 """
 from __future__ import annotations
 
@@ -30,12 +33,12 @@ import torch
 
 from . import fabrika
 
-METHODS = ("LSBR", "HILLR", "LSBRS")
+METHODS = ("LSBR", "HILLR", "LSBRS", "LSBRK")
 ORDERS = ("rows", "rows_up")
 
 
 def method_name(stego_method: str) -> str:
-    """'LSBR' / 'HILLR' / 'LSBRS', matched case-insensitively (the reference spells both 'LSBr' and 'LSBR')."""
+    """'LSBR' / 'HILLR' / 'LSBRS' / 'LSBRK', matched case-insensitively (the reference spells both 'LSBr' and 'LSBR')."""
     m = str(stego_method).upper()
     if m not in METHODS:
         raise NotImplementedError(f"stego method {stego_method!r} is not simulated here: choose one of {' / '.join(METHODS)}")
@@ -60,6 +63,18 @@ def lsbrs_count(alpha: float, h: int, w: int) -> int:
     return int(np.floor(np.float64(alpha) * np.float64(h * w)))
 
 
+def _check_placement_key(method: str, placement_key) -> typing.Optional[int]:
+    """The 64-bit stego key of 'LSBRK' as an int; the other methods have none (None)."""
+    if method != "LSBRK":
+        return None
+    if placement_key is None:
+        raise ValueError("'LSBRK' needs placement_key: the 64-bit stego key that selects the used pixels of every image")
+    k = int(placement_key)
+    if not 0 <= k < 2 ** 64:
+        raise ValueError(f"placement_key {placement_key!r} outside [0, 2^64)")
+    return k
+
+
 def _check_order(order) -> str:
     if order not in ORDERS:
         raise ValueError(f"unknown order {order!r}; choose from {ORDERS}")
@@ -77,14 +92,16 @@ def _alphas(alpha, n: int) -> np.ndarray:
 
 
 def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, key: typing.Optional[torch.Tensor] = None,
-             order: str = "rows"):
+             order: str = "rows", placement_key: typing.Optional[int] = None):
     """cover_u8: (N,H,W) uint8 on the device; alpha: a scalar or one value per image -> (stego (N,H,W) uint8, changes (N) int64), both
-    on the device.  'LSBR' and 'LSBRS' need `seeds`, one 64-bit integer per image (image_seed); 'HILLR' ignores them and takes an optional
+    on the device.  'LSBR', 'LSBRS' and 'LSBRK' need `seeds`, one 64-bit integer per image (image_seed); 'HILLR' ignores them and takes an optional
     `key` = ops.hill_cost_f64(cover_u8) made earlier (several alphas of the same covers).  `order` ('rows' / 'rows_up') is the path of
-    'LSBRS'; the other methods have none."""
+    'LSBRS'; the other methods have none.  `placement_key` is the shared stego key of 'LSBRK' (one alpha for the whole batch: the used
+    positions are the same in every image)."""
     from . import ops
     method = method_name(stego_method)
     _check_order(order)
+    placement_key = _check_placement_key(method, placement_key)
     if not (isinstance(cover_u8, torch.Tensor) and cover_u8.dim() == 3 and cover_u8.dtype == torch.uint8):
         raise ValueError("simulate: cover_u8 must be an (N,H,W) uint8 tensor")
     n, h, w = cover_u8.shape
@@ -100,6 +117,10 @@ def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, ke
     s = np.array([int(v) % 2 ** 64 for v in (seeds.tolist() if isinstance(seeds, (torch.Tensor, np.ndarray)) else seeds)], dtype=np.uint64)
     if s.shape != (n,):
         raise ValueError(f"simulate: {s.shape[0] if s.ndim else 1} seeds for {n} images")
+    if method == "LSBRK":
+        if not np.all(a == a[0]):
+            raise ValueError(f"simulate: 'LSBRK' takes one alpha for all images (one key selects one set of pixels), got {alpha!r}")
+        return ops.embed_lsbr_keyed(cover_u8, torch.from_numpy(s.view(np.int64)).to(dev), placement_key, ops.lsbr_key_threshold(a[0]))
     if method == "LSBRS":
         m = torch.tensor([lsbrs_count(v, h, w) for v in a], dtype=torch.int64).to(dev)
         return ops.embed_lsbr_seq(cover_u8, torch.from_numpy(s.view(np.int64)).to(dev), m, order)
@@ -109,12 +130,15 @@ def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, ke
 
 # ---- whole data sets --------------------------------------------------------------------------------------------------------
 
-def folder_name(stego_method: str, alpha: float, order: str = "rows") -> str:
+def folder_name(stego_method: str, alpha: float, order: str = "rows", placement_key: typing.Optional[int] = None) -> str:
     """`stego_<METHOD>_alpha_<a>_independent_images`: the reference's folder scheme with the method in upper case, as its files.csv
     spells it (the reference's own folders say 'HILLr' / 'LSBr' beside 'HILLR' / 'LSBR' in the name column; that mismatch is not copied).
-    The bottom-up twins of 'LSBRS' (order 'rows_up') go to `stego_LSBRS_alpha_<a>_rows_up_independent_images`."""
+    The bottom-up twins of 'LSBRS' (order 'rows_up') go to `stego_LSBRS_alpha_<a>_rows_up_independent_images`, the twins of 'LSBRK' under
+    the stego key K to `stego_LSBRK_alpha_<a>_key_<K>_independent_images`."""
     method = method_name(stego_method)
     suffix = "_rows_up" if method == "LSBRS" and _check_order(order) == "rows_up" else ""
+    if method == "LSBRK":
+        suffix = f"_key_{_check_placement_key(method, placement_key)}"
     return f"stego_{method}_alpha_{float(alpha)}{suffix}_independent_images"
 
 
@@ -123,7 +147,7 @@ def _prefetch(fnames, kws):
     return (read_luma_batch(fnames),)
 
 
-def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, order="rows", prefetched=None):
+def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, order="rows", placement_key=None, prefetched=None):
     """One chunk of covers -> their twins at every alpha, written as 8-bit gray PNGs; one list of files.csv rows per cover."""
     from PIL import Image
     from . import ops
@@ -131,11 +155,11 @@ def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, order="r
     cover = torch.from_numpy(np.ascontiguousarray(planes)).to("cuda")
     method = method_name(stego_method)
     key = ops.hill_cost_f64(cover) if method == "HILLR" else None
-    seeds = [image_seed(f, stream) for f in fnames] if method in ("LSBR", "LSBRS") else None
+    seeds = [image_seed(f, stream) for f in fnames] if method in ("LSBR", "LSBRS", "LSBRK") else None
     rows = [[] for _ in fnames]
     for a in alphas:
-        stego = simulate(cover, method, a, seeds, key=key, order=order)[0].cpu().numpy()
-        folder = folder_name(method, a, order)
+        stego = simulate(cover, method, a, seeds, key=key, order=order, placement_key=placement_key)[0].cpu().numpy()
+        folder = folder_name(method, a, order, placement_key)
         (pathlib.Path(out_dir) / folder).mkdir(parents=True, exist_ok=True)
         for i, f in enumerate(fnames):
             name = f"{folder}/{pathlib.Path(f).stem}.png"
@@ -145,38 +169,42 @@ def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, order="r
 
 
 _write_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(
-    fabrika.shared_kwargs(_write_chunk, ("stego_method", "alphas", "stream", "out_dir", "order"), _prefetch))
+    fabrika.shared_kwargs(_write_chunk, ("stego_method", "alphas", "stream", "out_dir", "order", "placement_key"), _prefetch))
 
 
 def write_dataset(data_dir, stego_method: str, alpha, *, split: typing.Optional[str] = None, stream: int = 0,
-                  order: str = "rows") -> typing.List[pathlib.Path]:
+                  order: str = "rows", placement_key: typing.Optional[int] = None) -> typing.List[pathlib.Path]:
     """Twins of every cover of `data_dir` (images*/files.csv, or the rows of `split`) at `alpha` (one value or several), written
-    beside the covers; returns the folders.  A folder's files.csv lists exactly the files of this call.  `order`: the path of 'LSBRS'."""
+    beside the covers; returns the folders.  A folder's files.csv lists exactly the files of this call.  `order`: the path of 'LSBRS'; `placement_key`: the shared
+    stego key of 'LSBRK'."""
     import pandas as pd
     data_dir = pathlib.Path(data_dir)
     method = method_name(stego_method)
     _check_order(order)
+    placement_key = _check_placement_key(method, placement_key)
     alphas = [float(a) for a in np.atleast_1d(np.asarray(alpha, dtype=np.float64))]
     _alphas(alphas, len(alphas))
-    rows = _write_covers(data_dir, split=split, stego_method=method, alphas=alphas, stream=int(stream), out_dir=str(data_dir), order=order)
+    rows = _write_covers(data_dir, split=split, stego_method=method, alphas=alphas, stream=int(stream), out_dir=str(data_dir), order=order,
+                         placement_key=placement_key)
     folders = []
     for j, a in enumerate(alphas):
-        folder = data_dir / folder_name(method, a, order)
+        folder = data_dir / folder_name(method, a, order, placement_key)
         pd.DataFrame([r[j] for r in rows], columns=["name", "height", "width", "stego_method", "alpha"]).to_csv(folder / "files.csv", index=False)
         folders.append(folder)
     return folders
 
 
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(description="Write simulated stego twins of a data set's covers (HILLR / LSBR / LSBRS, made on the GPU).")
+    ap = argparse.ArgumentParser(description="Write simulated stego twins of a data set's covers (HILLR / LSBR / LSBRS / LSBRK, made on the GPU).")
     ap.add_argument("--data", required=True, help="data set directory (images*/files.csv)")
     ap.add_argument("--stego-method", required=True, help=" / ".join(METHODS))
     ap.add_argument("--alphas", type=float, nargs="+", required=True, help="embedding rates in [0, 1]")
     ap.add_argument("--split", default=None, help="a split CSV of the data set: only its covers")
     ap.add_argument("--stream", type=int, default=0, help="LSBR / LSBRS realisation number (image_seed)")
     ap.add_argument("--order", choices=ORDERS, default="rows", help="LSBRS: the message runs row by row from the top, or from the bottom row up")
+    ap.add_argument("--key", type=int, default=None, help="LSBRK: the 64-bit stego key that selects the used pixels of every image")
     ns = ap.parse_args(argv)
-    for folder in write_dataset(ns.data, ns.stego_method, ns.alphas, split=ns.split, stream=ns.stream, order=ns.order):
+    for folder in write_dataset(ns.data, ns.stego_method, ns.alphas, split=ns.split, stream=ns.stream, order=ns.order, placement_key=ns.key):
         print(folder)
 
 

@@ -1081,6 +1081,46 @@ def ws_sequential(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, p
     return (k, t_max, t_all, curve) if return_curve else (k, t_max, t_all)
 
 
+MAX_LOCATE_IMAGES = 65536                  # images one pair of accumulators may hold: |num| < 2^53 and den < 2^53 stay exact in float64
+
+
+def ws_residual_accumulate(x_u8: torch.Tensor, num: torch.Tensor, den: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *,
+                           pixel_filter=None, mean_filter=None, hat_scale: float = 255., weighted: int = 1, parts: int = 0) -> None:
+    """Adds a batch's per-pixel WS residual terms to two accumulators (wsu_ws_residual_accumulate, K29).  x_u8: (N,H,W) uint8; the
+    prediction as for ws_sequential: x_hat (N,H,W)/(N,1,H,W) full frames or (N,H-2,W-2) interiors, multiplied by `hat_scale`, or
+    `pixel_filter` (3,3[,1]) for an in-kernel linear predictor, (N,3,3[,1]) for one per image.  weighted: 0 or 1.  num, den: contiguous
+    int64 (H-2,W-2) on x_u8's device; per interior pixel num gains the images' terms wgt * r in 2^-24 units, den their weights in 2^-32
+    units, an image whose term is NaN adds to neither.  parts: workgroups sharing a pixel tile's images (0: chosen from the plane size);
+    the sums are exact integers and do not depend on it."""
+    if int(weighted) not in (0, 1):
+        raise ValueError(f"ws_residual_accumulate: weighted must be 0 or 1 (weighted=-1 is not defined for the residual means), got {weighted}")
+    if (x_hat is None) == (pixel_filter is None):
+        raise ValueError("ws_residual_accumulate: give exactly one of x_hat / pixel_filter")
+    lib = _lib.load()
+    n, h, w = _u8_planes(x_u8)
+    for name, t in (("num", num), ("den", den)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and tuple(t.shape) == (h - 2, w - 2) and t.is_contiguous()):
+            raise ValueError(f"ws_residual_accumulate: {name} must be a contiguous int64 tensor of shape {(h - 2, w - 2)} for planes of "
+                             f"{(h, w)}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    _dev_check(x_u8, num, den, *[t for t in (x_hat,) if t is not None])
+    mt = filter_taps(mean_filter, np.float32, "kernel")
+    pt = pts = None
+    hat_full = 1
+    if pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3):      # (N,3,3[,1])
+        if len(pixel_filter) != n:
+            raise ValueError(f"ws_residual_accumulate: {len(pixel_filter)} filters for {n} images")
+        pts = torch.from_numpy(np.stack([filter_taps(f, np.float32, "kernel") for f in pixel_filter])).to(x_u8.device)
+    elif pixel_filter is not None:
+        pt = filter_taps(pixel_filter, np.float32, "kernel")
+    else:
+        hat_full = _hat_full(x_hat, n, h, w, None)
+    check(_launch("ws_residual_accumulate", {"bytes": float(n * h * w * (1 if x_hat is None else 5) + 32 * (h - 2) * (w - 2))},
+                  lambda: lib.wsu_ws_residual_accumulate(
+        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
+        pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
+        int(parts), num.data_ptr(), den.data_ptr(), n, h, w, _stream())), "wsu_ws_residual_accumulate")
+
+
 def ols_moments(x_u8: torch.Tensor) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,45) int64: per image the exact sums of v_i * v_j, i <= j (row-major upper triangle), over the interior
     pixels, v = the eight neighbours in ring order (_RING) and the centre (wsu_ols_moments, K24; ws_unet_amd.ols unpacks and solves)."""
@@ -1230,6 +1270,55 @@ def embed_lsbr_seq(cover_u8: torch.Tensor, seeds: torch.Tensor, counts: torch.Te
         cover_u8.data_ptr(), seeds.data_ptr(), counts.data_ptr(), oid, stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())),
         "wsu_embed_lsbr_seq")
     return stego, changes
+
+
+def lsbr_key_threshold(alpha: float) -> int:
+    """T = floor(alpha * 2^32) in 0..2^32 of wsu_embed_lsbr_keyed (a pixel is used iff its key word < T, compared in 64 bits, so alpha = 1
+    uses every pixel); alpha outside [0, 1] raises."""
+    a = float(alpha)
+    if not 0.0 <= a <= 1.0:
+        raise ValueError(f"lsbr_key_threshold: alpha={alpha!r} outside [0, 1]")
+    return int(np.floor(np.float64(a) * 4294967296.0))
+
+
+def _key_args(who: str, key_seed, alpha_threshold) -> Tuple[int, int]:
+    key, thr = int(key_seed), int(alpha_threshold)
+    if not 0 <= key < 2 ** 64:
+        raise ValueError(f"{who}: key_seed {key_seed!r} outside [0, 2^64)")
+    if not 0 <= thr <= 2 ** 32:
+        raise ValueError(f"{who}: alpha_threshold {alpha_threshold!r} outside 0..2^32 (lsbr_key_threshold)")
+    return key, thr
+
+
+def embed_lsbr_keyed(cover_u8: torch.Tensor, seeds: torch.Tensor, key_seed: int, alpha_threshold: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """LSB replacement at the positions one stego key selects in every image (K30): pixel i is used iff its Philox word under `key_seed`
+    is below `alpha_threshold` (lsbr_key_threshold) and a used pixel flips as under embed_lsbr at alpha = 1 with the image's seed.  seeds:
+    (N) int64 holding the 64-bit seeds -> (stego (N,H,W) uint8, changes (N) int64)."""
+    key, thr = _key_args("embed_lsbr_keyed", key_seed, alpha_threshold)
+    lib = _lib.load()
+    n, h, w = _u8_planes(cover_u8)
+    _dev_check(seeds)
+    assert seeds.dtype == torch.int64 and seeds.shape == (n,)
+    stego = torch.empty_like(cover_u8)
+    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
+    check(_launch("embed_lsbr_keyed", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbr_keyed(
+        cover_u8.data_ptr(), seeds.data_ptr(), key, thr, stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_lsbr_keyed")
+    return stego, changes
+
+
+def lsbr_key_mask(key_seed: int, alpha_threshold: int, h: int, w: int, device=None) -> torch.Tensor:
+    """The positions embed_lsbr_keyed uses under (key_seed, alpha_threshold) in an (H,W) plane: (H,W) uint8 of 1 / 0 on `device` (the
+    current GPU by default)."""
+    key, thr = _key_args("lsbr_key_mask", key_seed, alpha_threshold)
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"lsbr_key_mask: bad shape {h} x {w}")
+    lib = _lib.load()
+    mask = torch.empty((h, w), dtype=torch.uint8, device=torch.device("cuda") if device is None else device)
+    _dev_check(mask)
+    check(_launch("lsbr_key_mask", {"bytes": float(h * w)}, lambda: lib.wsu_lsbr_key_mask(key, thr, mask.data_ptr(), h, w, _stream())),
+          "wsu_lsbr_key_mask")
+    return mask
 
 
 def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, hat_scale: float = 255.,

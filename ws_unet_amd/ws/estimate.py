@@ -94,23 +94,39 @@ def _unet_planes(model, x_u8: torch.Tensor, correct_bias: bool):
     return y, yb
 
 
-def _changepoint(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, order, host_planes=None, return_curve=False):
-    """ops.ws_sequential's (k, t_max, t_all[, curve]) on the device for a batch of planes, with any pixel predictor `_stat` knows."""
-    kw = dict(mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted), order=order, return_curve=return_curve)
+def predictor_arguments(x_u8: torch.Tensor, pixel_estimator, host_planes=None, correct_bias: bool = False) -> dict:
+    """A pixel predictor as the keywords the statistic kernels take (ops.ws_attack, ops.ws_sequential, ops.ws_residual_accumulate):
+    `pixel_filter` for a filters.FilterEstimator (evaluated in the kernel) and an ols.AdaptiveOLSEstimator (moments -> float64 fit on the
+    host -> one filter per image); `x_hat` with `hat_scale` for a UNetEstimator (the full-frame output stays on the device, scale 255)
+    and for any other callable (the reference's call pattern on `host_planes`, one image at a time; interior layout, scale 1).  With
+    correct_bias also `x_bias`, the predictor applied to x_bar - x, where the predictor has one outside the kernel."""
     if isinstance(pixel_estimator, UNetEstimator):
         check_unet_geometry(x_u8.shape[1:], "the UNet estimator")
-        return ops.ws_sequential(x_u8, unet_plane(pixel_estimator.model, x_u8), hat_scale=255.0, **kw)
+        y, yb = _unet_planes(pixel_estimator.model, x_u8, correct_bias)
+        return dict(x_hat=y, hat_scale=255.0) | ({"x_bias": yb} if correct_bias else {})
     if isinstance(pixel_estimator, filters.FilterEstimator):
-        return ops.ws_sequential(x_u8, None, pixel_filter=np.asarray(pixel_estimator.kernel)[..., ::-1], **kw)
+        return dict(pixel_filter=np.asarray(pixel_estimator.kernel)[..., ::-1])
     if isinstance(pixel_estimator, ols.AdaptiveOLSEstimator):
-        return ops.ws_sequential(x_u8, None, pixel_filter=pixel_estimator.kernels(x_u8)[..., ::-1], **kw)
-    hats = []                                               # arbitrary host callable: the interior layout, scale 1
+        return dict(pixel_filter=pixel_estimator.kernels(x_u8)[..., ::-1])
+    if host_planes is None:
+        raise ValueError(f"a host predictor ({type(pixel_estimator).__name__}) needs the planes on the host (host_planes)")
+    hats, biases = [], []
     for xf in host_planes:
         h = np.asarray(pixel_estimator(xf), dtype=np.float32)
         if h.shape[:2] != (xf.shape[0] - 2, xf.shape[1] - 2):
             raise ValueError(f"pixel_estimator returned {h.shape} for an image of {xf.shape}")
         hats.append(h[..., 0])
-    return ops.ws_sequential(x_u8, torch.from_numpy(np.stack(hats)).to(x_u8.device), hat_scale=1.0, **kw)
+        if correct_bias:
+            xbar = (xf.astype(np.uint8) ^ 1).astype(np.float32)
+            biases.append(np.asarray(pixel_estimator(xbar - xf), dtype=np.float32)[..., 0])
+    kw = dict(x_hat=torch.from_numpy(np.stack(hats)).to(x_u8.device), hat_scale=1.0)
+    return kw | ({"x_bias": torch.from_numpy(np.stack(biases)).to(x_u8.device)} if correct_bias else {})
+
+
+def _changepoint(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, order, host_planes=None, return_curve=False):
+    """ops.ws_sequential's (k, t_max, t_all[, curve]) on the device for a batch of planes, with any pixel predictor `_stat` knows."""
+    return ops.ws_sequential(x_u8, mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted), order=order,
+                             return_curve=return_curve, **predictor_arguments(x_u8, pixel_estimator, host_planes))
 
 
 def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=None, placement="random",
@@ -123,29 +139,8 @@ def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct
     if isinstance(pixel_estimator, structural.StructuralEstimator):    # no predictor, no weights: the estimator is the statistic
         structural.require_unweighted(weighted, correct_bias)
         return pixel_estimator.beta(x_u8).to(torch.float32)
-    kw = dict(mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted) if abs(int(weighted)) == 1 else 0,
-              correct_bias=correct_bias)
-    if isinstance(pixel_estimator, UNetEstimator):
-        check_unet_geometry(x_u8.shape[1:], "the UNet estimator")
-        y, yb = _unet_planes(pixel_estimator.model, x_u8, correct_bias)
-        return ops.ws_attack(x_u8, y, x_bias=yb, hat_scale=255.0, **kw)
-    if isinstance(pixel_estimator, filters.FilterEstimator):
-        return ops.ws_attack(x_u8, None, pixel_filter=np.asarray(pixel_estimator.kernel)[..., ::-1], **kw)
-    if isinstance(pixel_estimator, ols.AdaptiveOLSEstimator):          # moments -> float64 fit on the host -> one filter per image
-        return ops.ws_attack(x_u8, None, pixel_filter=pixel_estimator.kernels(x_u8)[..., ::-1], **kw)
-    # arbitrary host callable: reference call pattern, one image at a time
-    hats, biases = [], []
-    for xf in host_planes:
-        h = np.asarray(pixel_estimator(xf), dtype=np.float32)
-        if h.shape[:2] != (xf.shape[0] - 2, xf.shape[1] - 2):
-            raise ValueError(f"pixel_estimator returned {h.shape} for an image of {xf.shape}")
-        hats.append(h[..., 0])
-        if correct_bias:
-            xbar = (xf.astype(np.uint8) ^ 1).astype(np.float32)
-            biases.append(np.asarray(pixel_estimator(xbar - xf), dtype=np.float32)[..., 0])
-    x_hat = torch.from_numpy(np.stack(hats)).to(x_u8.device)
-    x_bias = torch.from_numpy(np.stack(biases)).to(x_u8.device) if correct_bias else None
-    return ops.ws_attack(x_u8, x_hat, x_bias=x_bias, hat_scale=1.0, **kw)
+    return ops.ws_attack(x_u8, mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted) if abs(int(weighted)) == 1 else 0,
+                         correct_bias=correct_bias, **predictor_arguments(x_u8, pixel_estimator, host_planes, correct_bias))
 
 
 def _check_options(pixel_estimator, weighted, correct_bias, placement="random", order="rows") -> None:
