@@ -16,6 +16,13 @@
 // Same persistent structure as conv3x3_pl.hip: one workgroup per CU walks 16 x 32-pixel x 64-co tiles; inputs travel two steps ahead into a ring
 // of three slots, weights one step ahead into two; ONE s_barrier per chunk step; epilogue straight from the accumulators (bias, ReLU, fused 2x2
 // max-pool, fused 1x1 head + sigmoid), the last step of a tile split by accumulator tile so that its second half overlaps the first half's stores.
+// The step head (begin_step): everything a step's fragment reads need beside compile-time constants -- the slot, the tile's channel half, the
+// lane -- is formed in front of the step's barrier, where a wave waits anyway: two lane bases for the f16 products and ten for the five fp4
+// units (weights, weight scales, Q granules and scale slots with the lane half's tap folded in: the partner tap is always the next tap, i.e. one
+// column on or, for tap pair 1, a row on and two columns back).  Behind the barrier every `ds_read` is base + immediate (at most 27 136) and a
+// steady step issues ~19 vector instructions beside its 56 matrix instructions (it recomputed ~55 per step until profiles/r25).  The ninth
+// tap has no partner: its lanes 32-63 multiply zeros, which they read from a zero block in LDS (cleared at kernel entry; one address select per
+// operand in the step head instead of sixteen register selects per step); the scale bytes of those lanes are tap 8's real ones (0xFF = NaN).
 // Replaces nn.Conv2d(k=3, reflect) + F.relu (+ torch.cat, nn.MaxPool2d, outconv + sigmoid) of src/unet/model/unet.py:141-189.
 // Weights: wsu_conv3x3_pack_f4 (below).
 // Format H (mode 'f16p', include/wsu.h K1h): the same kernel instantiated with FMT = WSU_PLANAR_H -- the f16 products alone (9 instead of 14 matrix
@@ -37,7 +44,10 @@ constexpr int W_SLOT = W_GRAN + 1024;                     // + [9][64] scale byt
 constexpr int NIN = 3, NWS = 2;
 constexpr int W_BASE = NIN * IN_SLOT;                     // 95808
 constexpr int LDS_EXTRA = W_BASE + NWS * W_SLOT;          // 153152: bias [1024] | head_w [4][64] | head_b [4]
-constexpr int LDS_TOTAL = LDS_EXTRA + 1024 * 4 + 4 * 64 * 4 + 16;     // 158288
+// format Q: a block of zeros behind the bias and the head's weights -- what lanes 32-63 of the ninth tap's fp4 unit read (begin_step).  It covers
+// the reads' immediates from one base: weights + m * 512, Q granules + q * IW * 16 (q < 4), 16 bytes each
+constexpr int ZERO_BYTES = 3 * IW * 16 + 32;              // 1664
+constexpr int LDS_TOTAL = LDS_EXTRA + 1024 * 4 + 4 * 64 * 4 + 16 + ZERO_BYTES;     // 159952
 static_assert(LDS_TOTAL <= 160 * 1024 && W_SLOT % 1024 == 0, "LDS budget");
 constexpr int NLOAD = 4;
 constexpr int W_PIECES = W_SLOT / 1024;                   // 28
@@ -52,9 +62,11 @@ template <int FMT> struct QGeo {
     static constexpr int in_slot = H ? IN_SLOT_H : IN_SLOT, w_slot = H ? W_SLOT_H : W_SLOT;
     static constexpr int w_planes = H ? 2 : 3;                                   // weight granule planes per tap
     static constexpr int w_base = NIN * in_slot, lds_extra = w_base + NWS * w_slot;
-    static constexpr int lds_total = lds_extra + 1024 * 4 + 4 * 64 * 4 + 16;      // H: 100752
+    static constexpr int lds_zero = lds_extra + 1024 * 4 + 4 * 64 * 4 + 16;       // the zero block (format Q only)
+    static constexpr int lds_total = lds_zero + (H ? 0 : ZERO_BYTES);             // H: 100752
     static constexpr int w_pieces = w_slot / 1024;
 };
+static_assert(QGeo<WSU_PLANAR_Q>::lds_zero % 16 == 0 && ZERO_BYTES % 16 == 0 && ZERO_BYTES >= 3 * IW * 16 + 16 && ZERO_BYTES >= 512 + 16, "zero block");
 static_assert(QGeo<WSU_PLANAR_Q>::lds_total == LDS_TOTAL && QGeo<WSU_PLANAR_Q>::w_pieces == W_PIECES && W_SLOT_H % 1024 == 0, "LDS geometry");
 
 struct QArgs {
@@ -305,6 +317,11 @@ void conv3x3_q_kernel(const QArgs a) {
     }
     // (these plain loads have retired -- their values went into the LDS stores -- before the first vmcnt wait of a loader; the barrier of step 0
     // publishes them)
+    if constexpr (!Gm::H) {
+        // the zero block: cleared once, nothing writes it afterwards.  Step 0 reads it right behind its barrier, so the stores are waited for here
+        for (int i = tid; i < ZERO_BYTES / 4; i += NT) reinterpret_cast<unsigned*>(smem + Gm::lds_zero)[i] = 0u;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
 
     if (wv >= NWAVE) {
         if constexpr (F1) { q_loader_f1(a, smem, lane, lw, G, J, wv - NWAVE); return; }
@@ -329,15 +346,22 @@ void conv3x3_q_kernel(const QArgs a) {
     // the slots of this step and of the next one as running offsets (step j lives in input slot j % NIN and weight slot j % NWS, as the loaders count them)
     unsigned q_in_off = 0, q_w_off = Gm::w_base;
     unsigned nx_in = 0, nx_w = Gm::w_base;
-    // lane bases of a step's fragment reads, formed BEFORE the step's barrier (begin_step): a_off / b_off of the f16 products
-    // (+ ((tap * planes) * 64 + m * 32) * 16 and + ((q + dy) * IW + dx) * 16), hd_* of the first fp4 unit (tap pair 0), whose reads open the step
-    unsigned a_off = 0, b_off = 0, hd_w = 0, hd_sa = 0, hd_b = 0, hd_sb = 0;
-    int hh_q = hh;                                                            // an opaque copy of the lane half per step: keeps the tap-pair offsets of the cross terms from being hoisted out of the tile loop (and spilled)
+    // lane bases of a step's fragment reads, ALL formed BEFORE the step's barrier (begin_step); behind it every read is base + immediate.
+    // a_off / b_off: the f16 products (+ ((tap * planes) * 64 + m * 32) * 16 and + ((q + dy) * IW + dx) * 16).  The five fp4 units (tap pair tp:
+    // lanes 0-31 tap 2 tp, lanes 32-63 tap 2 tp + 1) share one set -- the lane half's term is a constant of the base, not of the unit:
+    //   weights  x_w  = plane 2 of tap hh:  + ((6 tp + 2) * 64 + m * 32) * 16;     x_sa = scale byte of tap hh:  + 128 tp + 32 m
+    //   pixels   x_b1 / x_sb1 = Q granule / scale slot of pixel + hh          (pairs 0, 2, 3: the partner tap is one column on)
+    //            x_b2 / x_sb2 = ... of pixel + hh * (IW - 2)                  (pair 1: tap 2 -> tap 3 = next row, two columns back)
+    //            each + (pixoff(2 tp) + q * IW) * 16 (* 4)
+    //   the ninth tap (pair 4) has no partner: lanes 32-63 multiply zeros, which they READ -- x_w4 / x_b4 are the tap's own bases in lanes
+    //   0-31 and point lanes 32-63 at the zero block (the reads' immediates included); both scale bytes keep real addresses, those of tap 8
+    //   itself (x_sa4, x_sb0: a byte of 0xFF would be a NaN scale)
+    unsigned a_off = 0, b_off = 0, x_w = 0, x_w4 = 0, x_sa = 0, x_sa4 = 0, x_b1 = 0, x_b2 = 0, x_b4 = 0, x_sb0 = 0, x_sb1 = 0, x_sb2 = 0;
+    constexpr unsigned W4_IMM = (unsigned)((8 * 3 + 2) * 64) * 16u, B4_IMM = (unsigned)(2 * IW + 2) * 16u;     // tap 8: weight plane 2, pixel offset
     typedef __attribute__((address_space(3))) const unsigned char lds_cuchar;
     typedef __attribute__((address_space(3))) const int lds_cint;
     typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
-    lds_char* const L = (lds_char*)smem;
-    const unsigned Lb = (unsigned)(size_t)L;                                  // the pinned bases are absolute LDS addresses (at()): no add behind the barrier
+    const unsigned Lb = (unsigned)(size_t)(lds_char*)smem;                                 // the pinned bases are absolute LDS addresses (at()): no add behind the barrier
     auto at = [](unsigned addr) __attribute__((always_inline)) { return (lds_char*)(size_t)addr; };
     auto begin_step = [&]() __attribute__((always_inline)) {
         // everything the first reads of the step need depends on the step count, the tile and the lane only: it is formed here, where a wave waits
@@ -347,18 +371,26 @@ void conv3x3_q_kernel(const QArgs a) {
         nx_in = nx_in + (unsigned)Gm::in_slot == (unsigned)(NIN * Gm::in_slot) ? 0u : nx_in + (unsigned)Gm::in_slot;
         static_assert(NWS == 2, "nx_w toggles between the two weight slots the loaders fill as s % NWS");
         nx_w = (unsigned)(2 * Gm::w_base + Gm::w_slot) - nx_w;
-        hh_q = hh;
-        asm volatile("" : "+v"(hh_q));
         a_off = Lb + q_w_off + (unsigned)((cur.mh * 32 + l31) * 16) + (unsigned)(hh * 64 * 16);
         b_off = Lb + q_in_off + (unsigned)(((RQ * wv) * IW + l31) * 16) + (unsigned)(hh * PLANE);
         if constexpr (!H) {
-            const int tap = hh_q ? 1 : 0;                                     // tap pair 0: lanes 0-31 tap 0, lanes 32-63 tap 1 (pixel offset = tap)
-            const unsigned pix = (unsigned)((RQ * wv) * IW + l31 + tap);
-            hd_w = Lb + q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u + (unsigned)((tap * 3 + 2) * 64) * 16u;
-            hd_sa = Lb + q_w_off + W_GRAN + (unsigned)(tap * 64 + cur.mh * 32 + l31);
-            hd_b = Lb + q_in_off + 2 * PLANE + pix * 16u;
-            hd_sb = Lb + q_in_off + 3 * PLANE + pix * 4u;
-            asm volatile("" : "+v"(a_off), "+v"(b_off), "+v"(hd_w), "+v"(hd_sa), "+v"(hd_b), "+v"(hd_sb));
+            unsigned hq = (unsigned)hh;                                       // an opaque copy of the lane half per step: its multiples are formed here, not hoisted out of the tile loop (and spilled)
+            asm volatile("" : "+v"(hq));
+            const unsigned zero = Lb + (unsigned)Gm::lds_zero;
+            const unsigned w0 = Lb + q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u;
+            const unsigned p0 = Lb + q_in_off + 2 * PLANE + (unsigned)((RQ * wv) * IW + l31) * 16u;
+            x_w = w0 + hq * (unsigned)(3 * 64 * 16);
+            x_w4 = hq ? zero - W4_IMM : w0;
+            x_sa4 = Lb + q_w_off + W_GRAN + (unsigned)(cur.mh * 32 + l31);
+            x_sa = x_sa4 + hq * 64u;
+            x_b1 = p0 + hq * 16u;
+            x_b2 = p0 + hq * (unsigned)((IW - 2) * 16);
+            x_b4 = hq ? zero - B4_IMM : p0;
+            x_sb0 = Lb + q_in_off + 3 * PLANE + (unsigned)((RQ * wv) * IW + l31) * 4u;
+            x_sb1 = x_sb0 + hq * 4u;
+            x_sb2 = x_sb0 + hq * (unsigned)((IW - 2) * 4);
+            asm volatile("" : "+v"(a_off), "+v"(b_off), "+v"(x_w), "+v"(x_w4), "+v"(x_sa), "+v"(x_sa4));
+            asm volatile("" : "+v"(x_b1), "+v"(x_b2), "+v"(x_b4), "+v"(x_sb0), "+v"(x_sb1), "+v"(x_sb2));
         } else {
             asm volatile("" : "+v"(a_off), "+v"(b_off));
         }
@@ -394,39 +426,31 @@ _Pragma("unroll")
             }
     };
     // both cross terms of a tap pair in one fp4 instruction -- lane half hh carries tap 2 tp + hh: weight granule plane 2 and the pixel's Q granule,
-    // each with its E8M0 scale byte (per (tap, co) / per pixel)
-    auto cross_q4 = [&](auto tp_c, auto ms_c, auto first_c) __attribute__((always_inline)) {
-        constexpr int tp = decltype(tp_c)::value;
-        constexpr int ms = decltype(ms_c)::value, ML = ms < 0 ? 0 : ms, MU = ms < 0 ? MH : ms + 1;
-        constexpr bool FIRST = decltype(first_c)::value;
-        constexpr int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 2 * tp;
-        constexpr bool single = 2 * tp + 1 >= 9;
-        constexpr bool HEAD_UNIT = tp == 0 && ms <= 0;                        // the unit that opens a step: its lane bases come from begin_step
-        const int tap = hh_q ? t1 : t0;
-        const int pixoff = (tap / 3) * IW + tap % 3;
-        u32x4 a4[2], b4[4]; int sa[2], sb[4];
-        const unsigned pix = (unsigned)((RQ * wv) * IW + l31 + pixoff);
-        const unsigned wbase = HEAD_UNIT ? hd_w : Lb + q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u + (unsigned)((tap * 3 + 2) * 64) * 16u;
-        const unsigned sabase = HEAD_UNIT ? hd_sa : Lb + q_w_off + W_GRAN + (unsigned)(tap * 64 + cur.mh * 32 + l31);
-        const unsigned bbase = HEAD_UNIT ? hd_b : Lb + q_in_off + 2 * PLANE + pix * 16u;
-        const unsigned sbbase = HEAD_UNIT ? hd_sb : Lb + q_in_off + 3 * PLANE + pix * 4u;
+    // each with its E8M0 scale byte (per (tap, co) / per pixel).  q4_reads: the unit's fragment reads, lane bases of begin_step + immediates
+    auto q4_reads = [&](auto tp_c, auto ml_c, auto mu_c, u32x4* a4, u32x4* b4, int* sa, int* sb) __attribute__((always_inline)) {
+        constexpr int tp = decltype(tp_c)::value, ML = decltype(ml_c)::value, MU = decltype(mu_c)::value;
+        constexpr bool single = 2 * tp + 1 >= 9;                              // the ninth tap
+        constexpr int t0 = 2 * tp, pix0 = (t0 / 3) * IW + t0 % 3;
+        constexpr unsigned wimm = (unsigned)((6 * tp + 2) * 64) * 16u;
+        static_assert(!single || (wimm == W4_IMM && (unsigned)pix0 * 16u == B4_IMM), "tap 8");
+        const unsigned wbase = single ? x_w4 : x_w, sabase = single ? x_sa4 : x_sa;
+        const unsigned bbase = single ? x_b4 : (tp == 1 ? x_b2 : x_b1), sbbase = single ? x_sb0 : (tp == 1 ? x_sb2 : x_sb1);
 _Pragma("unroll")
         for (int m = ML; m < MU; ++m) {
-            a4[m] = *(lds_cu32x4*)(at(wbase) + m * 32 * 16);
-            sa[m] = *(lds_cuchar*)(at(sabase) + m * 32);
+            a4[m] = *(lds_cu32x4*)(at(wbase) + wimm + m * 32 * 16);
+            sa[m] = *(lds_cuchar*)(at(sabase) + 128 * tp + m * 32);
         }
 _Pragma("unroll")
         for (int q = 0; q < RQ; ++q) {
-            b4[q] = *(lds_cu32x4*)(at(bbase) + (q * IW) * 16u);
-            sb[q] = *(lds_cint*)(at(sbbase) + (q * IW) * 4u);                  // the pixel's dword slot: byte 0 = its scale byte
+            b4[q] = *(lds_cu32x4*)(at(bbase) + (pix0 + q * IW) * 16);
+            sb[q] = *(lds_cint*)(at(sbbase) + (pix0 + q * IW) * 4);            // the pixel's dword slot: byte 0 = its scale byte
         }
-        if (single && hh_q) {
-            const u32x4 z = mk_u4(0, 0, 0, 0);
-_Pragma("unroll")
-            for (int m = ML; m < MU; ++m) a4[m] = z;
-_Pragma("unroll")
-            for (int q = 0; q < RQ; ++q) b4[q] = z;
-        }
+    };
+    auto cross_q4 = [&](auto tp_c, auto ms_c, auto first_c) __attribute__((always_inline)) {
+        constexpr int ms = decltype(ms_c)::value, ML = ms < 0 ? 0 : ms, MU = ms < 0 ? MH : ms + 1;
+        constexpr bool FIRST = decltype(first_c)::value;
+        u32x4 a4[2], b4[4]; int sa[2], sb[4];
+        q4_reads(tp_c, std::integral_constant<int, ML>{}, std::integral_constant<int, MU>{}, a4, b4, sa, sb);
 _Pragma("unroll")
         for (int m = ML; m < MU; ++m)
 _Pragma("unroll")
@@ -441,9 +465,6 @@ _Pragma("unroll")
         constexpr int lo = decltype(lo_c)::value, hi = decltype(hi_c)::value;
         constexpr bool FIRST = decltype(first_c)::value;
         static_assert(!FIRST || lo == 0, "a tile opens with tap pair 0");
-        // (per call: the paths of a step must not share -- and hoist -- their lane offsets.  Not in front of the unit that opens a step: its
-        // offsets were formed before the barrier)
-        if constexpr (EPO && !(lo == 0 && decltype(ms_c)::value <= 0)) asm volatile("" : "+v"(hh_q));
         WSU_STATIC_FOR(hi - lo, i, {
             constexpr int tp = lo + i;
             if constexpr (!H) cross_q4(std::integral_constant<int, tp>{}, ms_c, std::integral_constant<bool, FIRST && tp == 0>{});
@@ -462,45 +483,19 @@ _Pragma("unroll")
     auto load_unit = [&](auto u_c, Frag& f) __attribute__((always_inline)) {
         constexpr int u = decltype(u_c)::value, tp = u / 3, k = u % 3;
         if constexpr (k == 0) {
-            constexpr int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 2 * tp;
-            const int tap = hh_q ? t1 : t0;
-            const int pixoff = (tap / 3) * IW + tap % 3;
-            const unsigned pix = (unsigned)((RQ * wv) * IW + l31 + pixoff);
-            const unsigned wbase = u == 0 ? hd_w : Lb + q_w_off + (unsigned)(cur.mh * 32 + l31) * 16u + (unsigned)((tap * 3 + 2) * 64) * 16u;
-            const unsigned sabase = u == 0 ? hd_sa : Lb + q_w_off + W_GRAN + (unsigned)(tap * 64 + cur.mh * 32 + l31);
-            const unsigned bbase = u == 0 ? hd_b : Lb + q_in_off + 2 * PLANE + pix * 16u;
-            const unsigned sbbase = u == 0 ? hd_sb : Lb + q_in_off + 3 * PLANE + pix * 4u;
-_Pragma("unroll")
-            for (int m = 0; m < MH; ++m) {
-                f.a[m] = *(lds_cu32x4*)(at(wbase) + m * 32 * 16);
-                f.sa[m] = *(lds_cuchar*)(at(sabase) + m * 32);
-            }
-_Pragma("unroll")
-            for (int q = 0; q < RQ; ++q) {
-                f.b[q] = *(lds_cu32x4*)(at(bbase) + (q * IW) * 16u);
-                f.sb[q] = *(lds_cint*)(at(sbbase) + (q * IW) * 4u);
-            }
+            q4_reads(std::integral_constant<int, tp>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, MH>{}, f.a, f.b, f.sa, f.sb);
         } else {
             constexpr int tap = 2 * tp + k - 1, dy = tap / 3, dx = tap % 3;
-            const unsigned abase = q_w_off + (unsigned)((cur.mh * 32 + l31) * 16) + (unsigned)(hh_q * 64 * 16);          // 32-bit LDS offsets (no 64-bit pointer arithmetic per read)
-            const unsigned bbase = q_in_off + (unsigned)(((RQ * wv) * IW + l31) * 16) + (unsigned)(hh_q * PLANE);
 _Pragma("unroll")
-            for (int m = 0; m < MH; ++m) f.a[m] = *(lds_cu32x4*)(L + abase + ((tap * 3) * 64 + m * 32) * 16);
+            for (int m = 0; m < MH; ++m) f.a[m] = *(lds_cu32x4*)(at(a_off) + ((tap * 3) * 64 + m * 32) * 16);
 _Pragma("unroll")
-            for (int q = 0; q < RQ; ++q) f.b[q] = *(lds_cu32x4*)(L + bbase + ((q + dy) * IW + dx) * 16);
+            for (int q = 0; q < RQ; ++q) f.b[q] = *(lds_cu32x4*)(at(b_off) + ((q + dy) * IW + dx) * 16);
         }
     };
     auto mma_unit = [&](auto u_c, Frag& f, auto first_c) __attribute__((always_inline)) {
-        constexpr int u = decltype(u_c)::value, tp = u / 3, k = u % 3;
+        constexpr int u = decltype(u_c)::value, k = u % 3;
         constexpr bool FIRST = decltype(first_c)::value && u == 0;
         if constexpr (k == 0) {
-            if (2 * tp + 1 >= 9 && hh_q) {                                    // the ninth tap has no partner: lanes 32-63 multiply zeros
-                const u32x4 z = mk_u4(0, 0, 0, 0);
-_Pragma("unroll")
-                for (int m = 0; m < MH; ++m) f.a[m] = z;
-_Pragma("unroll")
-                for (int q = 0; q < RQ; ++q) f.b[q] = z;
-            }
 _Pragma("unroll")
             for (int m = 0; m < MH; ++m)
 _Pragma("unroll")

@@ -21,6 +21,12 @@
 //     lives in region j & 1, so the loaders fetch step j + 1 while the matrix waves work on step j and wait for all of it (`s_waitcnt
 //     vmcnt(0)`) before the barrier that opens it.  (Until round 5 a low chunk was two half-steps L0 / L1 in a ring of five 31.5 KB slots:
 //     a barrier, a slice wait and an exposed first fragment read per 3 matrix units.)
+// The step head (sync_step) forms the lane bases of a step's fragment reads in front of its barrier, as in conv3x3_q.hip.  A skip step's five
+// fp4 units share one set of weight bases (the lane half's tap folded in, immediates per unit); on the pixel side the class planes leave no
+// compile-time tap offsets (they depend on the wave's class), but which of a pair's two taps a lane reads is a constant of the lane, kept as five
+// registers for the launch (tap_sel): one add and one shift-add per unit.  The ninth tap's lanes 32-63 read their zero operands from a zero block
+// in the unused tail of the second step region.  A skip step issues 26-28 vector instructions beside its 56 matrix instructions (70-78 until
+// profiles/r25); the low step is as it was.
 // Accuracy: Wc is formed in fp32 and then split like any weight (f16 + fp4 residual terms); `xu` is never rounded to storage -- the fused
 // result is closer to the exact composition than the two-kernel path.  Replaces ops.convt2x2_pl + ops.conv3x3_q in UNet._forward_planar.
 // Format H (mode 'f16p', template argument FMT = WSU_PLANAR_H): planar H tensors in and out, the f16 products alone (no fp4 instruction, no Q /
@@ -57,6 +63,12 @@ constexpr int MAX_COUT = 512;
 constexpr int LDS_TOTAL = LDS_BIAS + MAX_COUT * 4;        // 163328
 static_assert(IN_S + W_S <= REGION && OFF_LW1 + W_L <= REGION && (REGION & 0xF) == 0 && LDS_TOTAL <= 160 * 1024, "LDS budget");
 static_assert((OFF_SW | OFF_LIN | OFF_LW1) % 16 == 0, "16-byte aligned allocations");
+// format Q: a block of zeros -- what lanes 32-63 of the ninth tap's fp4 unit read in a skip step (sync_step): weights + m * 512, Q granules
+// + q * 544, 16 bytes each.  It lies in the tail of the second step region, which no allocation of a step reaches (the bias area behind the
+// regions fills LDS to 512 bytes)
+constexpr int ZERO_BYTES = 576;
+constexpr int LDS_ZERO = 2 * REGION - ZERO_BYTES;
+static_assert(IN_S + W_S <= REGION - ZERO_BYTES && OFF_LW1 + W_L <= REGION - ZERO_BYTES && LDS_ZERO % 16 == 0 && ZERO_BYTES >= 2 * CW * 16 + 16 + 16, "zero block");
 constexpr int NLOAD = 4, NWAVE = 8, NT = (NWAVE + NLOAD) * 64;
 constexpr unsigned OOB = 0xFFFFFFF0u;
 // format H: weight slices without the fp4 plane and the scale bytes
@@ -247,6 +259,11 @@ void conv3x3_qu_kernel(const UArgs a) {
     const int K = a.ntiles > lw ? (a.ntiles - lw + G - 1) / G : 0;          // tiles walked by this workgroup
     float* s_bias = reinterpret_cast<float*>(smem + LDS_BIAS);
     for (int i = tid; i < a.cout; i += NT) s_bias[i] = a.bias ? a.bias[i] : 0.f;
+    if constexpr (!H) {
+        // the zero block: cleared once, nothing writes it afterwards.  Step 0 reads it right behind its barrier, so the stores are waited for here
+        for (int i = tid; i < ZERO_BYTES / 4; i += NT) reinterpret_cast<unsigned*>(smem + LDS_ZERO)[i] = 0u;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
 
     if (wv >= NWAVE) {
         switch (wv - NWAVE) {
@@ -281,8 +298,24 @@ void conv3x3_qu_kernel(const UArgs a) {
         return (unsigned)(((((py + ky) & 1) * 2 + ((px + kx) & 1)) * CPIX + ((py + ky) >> 1) * CW + ((px + kx) >> 1)) * 16);
     };
     // lane bases of a step's fragment reads, formed BEFORE the step's barrier (sync_step): a_off / b_off of the f16 products (weights: + the
-    // unit's planes and the 32-channel half; input: + the tap's pixel offset and the matrix tile), hd_* of the fp4 unit that opens the step
-    unsigned a_off = 0, b_off = 0, hd_w = 0, hd_sa = 0, hd_b = 0, hd_sb = 0;
+    // unit's planes and the 32-channel half; input: + the tap's pixel offset and the matrix tile), hd_* of the fp4 unit that opens the step.
+    // A skip step's five fp4 units (tap pair tp: lanes 0-31 tap 2 tp, lanes 32-63 tap 2 tp + 1) share ONE set of weight bases, as in
+    // conv3x3_q.hip: x_w = plane 2 of tap hh (+ ((6 tp + 2) * 64 + m * 32) * 16), x_sa = scale byte of tap hh (+ 128 tp + 32 m).  The ninth
+    // tap (pair 4) has no partner: lanes 32-63 multiply zeros, which they READ -- x_w4 / x_b4 are the tap's own weight / Q-granule bases in
+    // lanes 0-31 and point lanes 32-63 at the zero block; both scale bytes keep real addresses, those of tap 8 itself (x_sa4, tap8_s).
+    unsigned a_off = 0, b_off = 0, hd_w = 0, hd_sa = 0, hd_b = 0, hd_sb = 0, x_w = 0, x_w4 = 0, x_sa = 0, x_sa4 = 0, x_b4 = 0;
+    constexpr unsigned W4_IMM = (unsigned)((8 * 3 + 2) * 64) * 16u;           // tap 8: weight plane 2
+    // The pixel side has no compile-time tap offsets here (the class planes: tap_s depends on the wave's class), but the lane half's choice
+    // between a pair's two taps is a constant of the lane: tap_sel[tp] = (its tap's offset + the lane's pixel) / 4, formed once per launch --
+    // the scale slot's offset as it stands, the Q granule's times 4 (one add, one shift-add per unit)
+    unsigned tap_sel[5] = {};
+    if constexpr (!H) {
+        WSU_STATIC_FOR(5, tp, {
+            constexpr int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 2 * tp;
+            tap_sel[tp] = ((hh ? tap_s(t1 / 3, t1 % 3) : tap_s(t0 / 3, t0 % 3)) + laneS) >> 2;
+            asm volatile("" : "+v"(tap_sel[tp]));
+        });
+    }
     // a step of kind S (LOW = false) or L: takes the next region and forms everything the step's first reads need -- it depends on the step
     // count, the wave and the lane only -- in front of the barrier, where a wave waits for the others anyway.  The empty asm statements pin the
     // values there (they and the barrier keep their order) and make them opaque per step, like hh_q: nothing is hoisted out of the tile loop.
@@ -296,14 +329,26 @@ void conv3x3_qu_kernel(const UArgs a) {
         asm volatile("" : "+v"(hh_q));
         a_off = Lb + w_off + (unsigned)l31 * 16u + (unsigned)hh * 1024u;
         b_off = Lb + in_off + (unsigned)hh * (LOW ? PLANE_L : PLANE_S) + (LOW ? laneL : laneS);
-        if constexpr (!H) {
-            // S: tap pair 0 = taps (0, 0) | (0, 1) by lane half; L: dy = 0, unit cls * 2 + dx with dx = the lane half
-            const int u = LOW ? cls * 2 + hh_q : hh_q;
-            const unsigned pb = LOW ? (unsigned)((py * LP + px) * 16) + (unsigned)hh_q * 16u + laneL : (hh_q ? tap_s(0, 1) : tap_s(0, 0)) + laneS;
+        if constexpr (!H && !LOW) {
+            // S: every fragment base of the step's fp4 units (the Q granules and scale slots of pairs 1-3 are tap_sel + a wave-uniform base)
+            const unsigned hq = (unsigned)hh_q, zero = Lb + (unsigned)LDS_ZERO;
+            const unsigned w0 = Lb + w_off + (unsigned)l31 * 16u;
+            x_w = w0 + hq * (unsigned)(3 * 64 * 16);
+            x_w4 = hq ? zero - W4_IMM : w0;
+            x_sa4 = Lb + w_off + W_GRAN_S + (unsigned)l31;
+            x_sa = x_sa4 + hq * 64u;
+            hd_b = Lb + in_off + 2 * PLANE_S + tap_sel[0] * 4u;
+            hd_sb = Lb + in_off + 3 * PLANE_S + tap_sel[0];
+            x_b4 = hq ? zero : Lb + in_off + 2 * PLANE_S + tap_sel[4] * 4u;
+            asm volatile("" : "+v"(a_off), "+v"(b_off), "+v"(x_w), "+v"(x_w4), "+v"(x_sa), "+v"(x_sa4), "+v"(hd_b), "+v"(hd_sb), "+v"(x_b4));
+        } else if constexpr (!H) {
+            // L: dy = 0, unit cls * 2 + dx with dx = the lane half
+            const int u = cls * 2 + hh_q;
+            const unsigned pb = (unsigned)((py * LP + px) * 16) + (unsigned)hh_q * 16u + laneL;
             hd_w = Lb + w_off + (unsigned)((u * 3 + 2) * 64 + l31) * 16u;
-            hd_sa = Lb + w_off + (LOW ? W_GRAN_L : W_GRAN_S) + (unsigned)(u * 64 + l31);
-            hd_b = Lb + in_off + 2 * (LOW ? PLANE_L : PLANE_S) + pb;
-            hd_sb = Lb + in_off + 3 * (LOW ? PLANE_L : PLANE_S) + (pb >> 2);
+            hd_sa = Lb + w_off + W_GRAN_L + (unsigned)(u * 64 + l31);
+            hd_b = Lb + in_off + 2 * PLANE_L + pb;
+            hd_sb = Lb + in_off + 3 * PLANE_L + (pb >> 2);
             asm volatile("" : "+v"(a_off), "+v"(b_off), "+v"(hd_w), "+v"(hd_sa), "+v"(hd_b), "+v"(hd_sb));
         } else {
             asm volatile("" : "+v"(a_off), "+v"(b_off));
@@ -316,26 +361,20 @@ void conv3x3_qu_kernel(const UArgs a) {
     auto skip_units = [&](auto first_c) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(first_c)::value;
         WSU_STATIC_FOR(5, tp, {
-            constexpr int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 2 * tp;
             if constexpr (!H) {
-                const unsigned tapo = hh_q ? tap_s(t1 / 3, t1 % 3) : tap_s(t0 / 3, t0 % 3);
-                const int tap = hh_q ? t1 : t0;
+                constexpr bool single = 2 * tp + 1 >= 9;                  // the ninth tap
+                constexpr unsigned wimm = (unsigned)((6 * tp + 2) * 64) * 16u;
+                static_assert(!single || wimm == W4_IMM, "tap 8");
                 u32x4 a4[2], b4[2]; int sa[2], sb[2];
-                const unsigned pb = tapo + laneS;
-                const unsigned wb = tp == 0 ? hd_w : Lb + w_off + (unsigned)((tap * 3 + 2) * 64 + l31) * 16u;
-                const unsigned sab = tp == 0 ? hd_sa : Lb + w_off + W_GRAN_S + (unsigned)(tap * 64 + l31);
-                const unsigned bb = tp == 0 ? hd_b : Lb + in_off + 2 * PLANE_S + pb;
-                const unsigned sbb = tp == 0 ? hd_sb : Lb + in_off + 3 * PLANE_S + (pb >> 2);
+                const unsigned wb = single ? x_w4 : x_w, sab = single ? x_sa4 : x_sa;
+                const unsigned bb = tp == 0 ? hd_b : (single ? x_b4 : Lb + in_off + 2 * PLANE_S + tap_sel[tp] * 4u);
+                const unsigned sbb = tp == 0 ? hd_sb : Lb + in_off + 3 * PLANE_S + tap_sel[tp];
 _Pragma("unroll")
-                for (int m = 0; m < 2; ++m) { a4[m] = *(lds_cu32x4*)(at(wb) + m * 512); sa[m] = *(lds_cuchar*)(at(sab) + m * 32); }
+                for (int m = 0; m < 2; ++m) { a4[m] = *(lds_cu32x4*)(at(wb) + wimm + m * 512); sa[m] = *(lds_cuchar*)(at(sab) + 128 * tp + m * 32); }
 _Pragma("unroll")
                 for (int q = 0; q < 2; ++q) {
                     b4[q] = *(lds_cu32x4*)(at(bb) + q * QS);
                     sb[q] = *(lds_cint*)(at(sbb) + q * (QS >> 2));
-                }
-                if (2 * tp + 1 >= 9 && hh_q) {                            // the ninth tap has no partner: lanes 32-63 multiply zeros
-                    const u32x4 z = mk_u4(0, 0, 0, 0);
-                    a4[0] = z; a4[1] = z; b4[0] = z; b4[1] = z;
                 }
 _Pragma("unroll")
                 for (int m = 0; m < 2; ++m)
