@@ -601,6 +601,30 @@ int wsu_embed_lsbr_keyed(const uint8_t* cover, const uint64_t* seeds, uint64_t k
                          long long* changes, int n, int h, int w, void* stream);
 int wsu_lsbr_key_mask(uint64_t key_seed, uint64_t alpha_threshold, uint8_t* mask, int h, int w, void* stream);
 
+/* ---- K31, K32: the JPEG history of a bitmap (Boehme, "Weighted stego-image steganalysis for JPEG covers", IH 2008; not part of the
+ *      reference): which quantisation table an image was compressed with, and the image after a round trip through a table -- the WS
+ *      predictor for covers that were a JPEG once (the quantiser rounds the +-1 embedding noise away).  All arithmetic is exact integers:
+ *        blocks of 8 x 8 on the grid at the plane's origin; H and W multiples of 8, H*W <= 2^24, N <= 65535;
+ *        C[k][n] = rint(2^13 c_k cos((2n+1) k pi / 16)) as int64, c_0 = sqrt(1/8), c_k = sqrt(2/8);
+ *        Y = C (X - 128) C^T at scale 2^26;   for a table entry Q in 1..255, D = Q 2^26:   k = sign(Y) ((|Y| + D/2) / D), half away from zero.
+ *      x_u8: DEVICE (N,H,W), 8-byte aligned.  tables: HOST int32, entries in 1..255 (checked with every other argument before any HIP
+ *      call); the kernels know nothing of JPEG qualities (ws_unet_amd.ops.jpeg_tables builds the IJG luminance tables).
+ *
+ * K31: tables (m,64), m >= 1, row-major 8 x 8 by frequency [u][v].  energies: DEVICE int64 (N,m), 8-byte aligned, zeroed on the stream by
+ *      this call:  energies[i][j] = sum over image i's coefficients of r'^2,  r = Y - k D,  r' = (r + 2^15) >> 16 (arithmetic shift; scale 2^10).
+ *      energies / 2^20 / (H W) is the residual energy per pixel.  Integer sums (64-bit atomics): the same bits on every run. */
+int wsu_jpeg_energies(const uint8_t* x_u8, const int* tables, int m, long long* energies, int n, int h, int w, void* stream);
+/* K32: tables (N,64), one per image; use: HOST uint8 [N].  Where use[i] != 0, with Z = C^T (k Q) C + 128 2^26 (int64):
+ *        x_hat[i]    = float32(clamp(Z, 0, 255 2^26) / 2^26)       (the quotient in float64, rounded once to float32)
+ *        x_u8_out[i] = clamp((Z + 2^25) >> 26, 0, 255)             (the recompressed image)
+ *      Where use[i] == 0 the table is not read: x_hat[i] is the KB filter's prediction in K11's float32 operation sequence
+ *      (convolve(x / 255.f, KB) summed K00 .. K22, times 255.f) on the interior and the pixel itself on the border (the statistics ignore
+ *      it), so K11 with this plane and hat_scale = 1 has the bits of K11 with pixel_filter = KB; x_u8_out[i] is the input.
+ *      x_hat: DEVICE fp32 (N,H,W), 16-byte aligned, or null; x_u8_out: DEVICE (N,H,W), 8-byte aligned, not aliasing x_u8, or null; one
+ *      of the two must be given.  Plain vector stores; every output element is written. */
+int wsu_jpeg_predict(const uint8_t* x_u8, const int* tables, const uint8_t* use, float* x_hat, uint8_t* x_u8_out, int n, int h, int w,
+                     void* stream);
+
 /* Linear pixel predictor on its own (filters/evaluate.py:136-141): y (N,H-2,W-2) = convolve(x/255., K, 'valid')*255.
  * x: DEVICE (N,H,W) fp32; filter: HOST 9 floats K[a][b]. */
 int wsu_filter3x3_valid_f32(const float* x, const float* filter, float* y, int n, int h, int w, void* stream);

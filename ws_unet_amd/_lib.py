@@ -125,6 +125,8 @@ SIGNATURES = {
     "wsu_embed_lsbr_seq": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_embed_lsbr_keyed": (c_int, [_P, _P, c_uint64, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_lsbr_key_mask": (c_int, [c_uint64, c_uint64, _P, c_int, c_int, _P]),
+    "wsu_jpeg_energies": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, _P]),
+    "wsu_jpeg_predict": (c_int, [_P] * 5 + [c_int] * 3 + [_P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_u8_to_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     "wsu_pair_batch_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P]),

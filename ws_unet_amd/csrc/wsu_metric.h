@@ -1,5 +1,5 @@
-// Device helpers shared by the metric kernels K10-K18, K27 and K29 and the simulators K20-K23, K28 and K30 (pointwise.hip K10 + WS meter,
-// ws_attack.hip, ws_sequential.hip, ws_locate.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's
+// Device helpers shared by the metric kernels K10-K18, K27, K29 and K32 and the simulators K20-K23, K28 and K30 (pointwise.hip K10 + WS meter,
+// ws_attack.hip, ws_sequential.hip, ws_locate.hip, jpeg_history.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's
 // taps, the prediction at a pixel, the float32 residual, the WS statistic's per-pixel terms, the HILL cost's input window, the fixed-order
 // block sum and the radix-select steps.
 //

@@ -1161,6 +1161,78 @@ def rs_counts(x_u8: torch.Tensor) -> torch.Tensor:
     return counts
 
 
+# IJG luminance base table (the JPEG standard's Annex K.1), row-major by frequency [u][v]
+_IJG_LUMINANCE = np.array([
+    [16, 11, 10, 16, 24, 40, 51, 61], [12, 12, 14, 19, 26, 58, 60, 55], [14, 13, 16, 24, 40, 57, 69, 56], [14, 17, 22, 29, 51, 87, 80, 62],
+    [18, 22, 37, 56, 68, 109, 103, 77], [24, 35, 55, 64, 81, 104, 113, 92], [49, 64, 78, 87, 103, 121, 120, 101],
+    [72, 92, 95, 98, 112, 100, 103, 99]], dtype=np.int64)
+
+
+def jpeg_tables(qualities) -> np.ndarray:
+    """IJG qualities (each in 1..100) -> HOST int32 (M,8,8) luminance quantisation tables: Q = clip((T s + 50) // 100, 1, 255) with
+    s = 5000 // q for q < 50, 200 - 2 q otherwise."""
+    q = np.atleast_1d(np.asarray(qualities))
+    if q.ndim != 1 or q.dtype.kind not in "iu" or (q.size and (q.min() < 1 or q.max() > 100)):
+        raise ValueError(f"jpeg_tables: integer qualities in 1..100 expected, got {qualities!r}")
+    q = q.astype(np.int64)
+    s = np.where(q < 50, 5000 // q, 200 - 2 * q)
+    return np.clip((_IJG_LUMINANCE[None] * s[:, None, None] + 50) // 100, 1, 255).astype(np.int32)
+
+
+def _jpeg_args(who: str, x_u8: torch.Tensor, tables, rows: Optional[int]) -> Tuple[int, int, int, np.ndarray]:
+    n, h, w = _u8_planes(x_u8)
+    if n == 0:
+        raise ValueError(f"{who}: no images")
+    if h % 8 or w % 8 or h * w > 1 << 24:
+        raise ValueError(f"{who}: planes of h={h} w={w}: h and w must be multiples of 8 and h * w at most 2^24")
+    t = np.asarray(tables)
+    if t.dtype.kind not in "iu" or t.ndim != 3 or t.shape[1:] != (8, 8) or t.shape[0] == 0 or (rows is not None and t.shape[0] != rows):
+        raise ValueError(f"{who}: integer tables of shape ({'M' if rows is None else rows},8,8) expected, got {t.dtype} {t.shape}")
+    if t.min() < 1 or t.max() > 255:
+        raise ValueError(f"{who}: table entries must lie in 1..255")
+    return n, h, w, np.ascontiguousarray(t, dtype=np.int32)
+
+
+def jpeg_energies(x_u8: torch.Tensor, tables) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8, H and W multiples of 8; tables: HOST integer (M,8,8), entries 1..255 -> int64 (N,M): the residual energy of
+    every image's 8x8 DCT coefficients against every table, in 2^-20 units (wsu_jpeg_energies, K31; ws_unet_amd.ws.jpeg reads the
+    compression history from it).  Exact integers."""
+    lib = _lib.load()
+    n, h, w, t = _jpeg_args("jpeg_energies", x_u8, tables, None)
+    energies = torch.empty((n, t.shape[0]), dtype=torch.int64, device=x_u8.device)
+    check(_launch("jpeg_energies", {"bytes": float(n * h * w)}, lambda: lib.wsu_jpeg_energies(
+        x_u8.data_ptr(), t.ctypes.data, t.shape[0], energies.data_ptr(), n, h, w, _stream())), "wsu_jpeg_energies")
+    return energies
+
+
+def jpeg_predict(x_u8: torch.Tensor, tables, use=None, want_u8: bool = False, want_hat: bool = True):
+    """The images after quantisation with their own table and the way back (wsu_jpeg_predict, K32).  x_u8: (N,H,W) uint8; tables: HOST
+    integer (N,8,8), one per image; use: HOST (N,) booleans or None (all): an image with use = 0 gets the KB filter's prediction in the place
+    of the round trip (its table is ignored).  Returns x_hat float32 (N,H,W) in pixel units (hat_scale = 1 for the WS statistics);
+    with want_u8 (x_hat, the recompressed uint8 planes -- the input where use = 0); without want_hat x_hat is None and not computed."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(x_u8)
+    u = np.ones(n, dtype=np.uint8) if use is None else np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+    if u.shape != (n,):
+        raise ValueError(f"jpeg_predict: use of shape {u.shape} for {n} images")
+    t = np.asarray(tables)
+    if t.ndim == 3 and t.shape[0] == n and t.dtype.kind in "iu":
+        t = np.where(u[:, None, None] != 0, t, 1)                      # (an unused table is not read)
+    n, h, w, t = _jpeg_args("jpeg_predict", x_u8, t, n)
+    x_hat = torch.empty((n, h, w), dtype=torch.float32, device=x_u8.device) if want_hat else None
+    out = torch.empty_like(x_u8) if want_u8 else None
+    check(_launch("jpeg_predict", {"bytes": float(n * h * w * (1 + 4 * want_hat + want_u8))}, lambda: lib.wsu_jpeg_predict(
+        x_u8.data_ptr(), t.ctypes.data, u.ctypes.data, _ptr(x_hat), _ptr(out), n, h, w, _stream())), "wsu_jpeg_predict")
+    return (x_hat, out) if want_u8 else x_hat
+
+
+def jpeg_recompress(x_u8: torch.Tensor, quality: int) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> the planes after a round trip through the IJG luminance table of `quality` (K32's uint8 output): a
+    JPEG-precompressed twin made without any JPEG library."""
+    n = _u8_planes(x_u8)[0]
+    return jpeg_predict(x_u8, np.repeat(jpeg_tables([int(quality)]), max(n, 1), axis=0), want_u8=True, want_hat=False)[1]
+
+
 def hill_cost(x_u8: torch.Tensor, clamp: float = 1e10) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,H,W) fp32 HILL cost with cost[inf | nan | > clamp] = clamp (wsu_hill_cost, K12)."""
     lib = _lib.load()

@@ -14,6 +14,8 @@ kernel, wsu_ws_attack; there is no host implementation in this package.
   * `placement='sequential'` (with `order='rows'` or 'rows_up') replaces the statistic by the changepoint estimator for payloads written
     into the first pixels of the file order (ws/sequential.py, wsu_ws_sequential): every pixel predictor works, the structural
     estimators, weighted=-1 and correct_bias do not.  The default, placement='random', is the reference's statistic.
+  * the model name 'JPEG' (ws/jpeg.py, a `jpeg.JPEGEstimator`) predicts every image by its own round trip through the JPEG quantiser it
+    was once compressed with: a full-frame device prediction like a UNet's, for both placements, without bias correction.
   * `run(..., batched=True)` is `run` on the batched iterators; the joblib iterators of the reference (:139,144) cannot
     carry a GPU model into worker processes, so the per-image decorators use iterator='python'.
 
@@ -33,7 +35,7 @@ from .. import fabrika, filters, ols, ops
 from ..imread import imread4_u8, u8_plane
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import check_unet_geometry, model_device, unet_plane
-from . import sequential, structural
+from . import jpeg, sequential, structural
 
 NAMED_FILTERS = filters.NAMED_FILTERS_2D
 
@@ -98,7 +100,8 @@ def predictor_arguments(x_u8: torch.Tensor, pixel_estimator, host_planes=None, c
     """A pixel predictor as the keywords the statistic kernels take (ops.ws_attack, ops.ws_sequential, ops.ws_residual_accumulate):
     `pixel_filter` for a filters.FilterEstimator (evaluated in the kernel) and an ols.AdaptiveOLSEstimator (moments -> float64 fit on the
     host -> one filter per image); `x_hat` with `hat_scale` for a UNetEstimator (the full-frame output stays on the device, scale 255)
-    and for any other callable (the reference's call pattern on `host_planes`, one image at a time; interior layout, scale 1).  With
+    and for any other callable (the reference's call pattern on `host_planes`, one image at a time; interior layout, scale 1); `x_hat`
+    with scale 1 for a jpeg.JPEGEstimator (history search and round trip on the device, full frames in pixel units).  With
     correct_bias also `x_bias`, the predictor applied to x_bar - x, where the predictor has one outside the kernel."""
     if isinstance(pixel_estimator, UNetEstimator):
         check_unet_geometry(x_u8.shape[1:], "the UNet estimator")
@@ -108,6 +111,9 @@ def predictor_arguments(x_u8: torch.Tensor, pixel_estimator, host_planes=None, c
         return dict(pixel_filter=np.asarray(pixel_estimator.kernel)[..., ::-1])
     if isinstance(pixel_estimator, ols.AdaptiveOLSEstimator):
         return dict(pixel_filter=pixel_estimator.kernels(x_u8)[..., ::-1])
+    if isinstance(pixel_estimator, jpeg.JPEGEstimator):
+        _require_no_bias_correction(pixel_estimator, correct_bias)
+        return dict(x_hat=pixel_estimator.planes(x_u8), hat_scale=1.0)
     if host_planes is None:
         raise ValueError(f"a host predictor ({type(pixel_estimator).__name__}) needs the planes on the host (host_planes)")
     hats, biases = [], []
@@ -123,30 +129,41 @@ def predictor_arguments(x_u8: torch.Tensor, pixel_estimator, host_planes=None, c
     return kw | ({"x_bias": torch.from_numpy(np.stack(biases)).to(x_u8.device)} if correct_bias else {})
 
 
-def _changepoint(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, order, host_planes=None, return_curve=False):
-    """ops.ws_sequential's (k, t_max, t_all[, curve]) on the device for a batch of planes, with any pixel predictor `_stat` knows."""
+def _changepoint(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, order, host_planes=None, return_curve=False, pred=None):
+    """ops.ws_sequential's (k, t_max, t_all[, curve]) on the device for a batch of planes, with any pixel predictor `_stat` knows
+    (pred: its predictor_arguments, where the caller has made them)."""
+    pred = predictor_arguments(x_u8, pixel_estimator, host_planes) if pred is None else pred
     return ops.ws_sequential(x_u8, mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted), order=order,
-                             return_curve=return_curve, **predictor_arguments(x_u8, pixel_estimator, host_planes))
+                             return_curve=return_curve, **pred)
 
 
 def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=None, placement="random",
           order="rows") -> torch.Tensor:
     """beta_hat[N] on the device for a batch of planes."""
     _check_options(pixel_estimator, weighted, correct_bias, placement, order)
-    if placement == "sequential":                                      # the changepoint k -> the change rate of the whole plane
-        k = _changepoint(x_u8, pixel_estimator, mean_estimator, weighted, order, host_planes)[0]
-        return sequential.beta(k, x_u8.shape[1], x_u8.shape[2], order).to(torch.float32)
     if isinstance(pixel_estimator, structural.StructuralEstimator):    # no predictor, no weights: the estimator is the statistic
         structural.require_unweighted(weighted, correct_bias)
         return pixel_estimator.beta(x_u8).to(torch.float32)
-    return ops.ws_attack(x_u8, mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted) if abs(int(weighted)) == 1 else 0,
-                         correct_bias=correct_bias, **predictor_arguments(x_u8, pixel_estimator, host_planes, correct_bias))
+    pred = predictor_arguments(x_u8, pixel_estimator, host_planes, correct_bias)
+    if placement == "sequential":                                      # the changepoint k -> the change rate of the whole plane
+        k = _changepoint(x_u8, pixel_estimator, mean_estimator, weighted, order, pred=pred)[0]
+        beta = sequential.beta(k, x_u8.shape[1], x_u8.shape[2], order).to(torch.float32)
+    else:
+        beta = ops.ws_attack(x_u8, mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted) if abs(int(weighted)) == 1 else 0,
+                             correct_bias=correct_bias, **pred)
+    return jpeg.without_estimate(beta, pred["x_hat"]) if isinstance(pixel_estimator, jpeg.JPEGEstimator) else beta
+
+
+def _require_no_bias_correction(pixel_estimator, correct_bias) -> None:
+    if correct_bias and isinstance(pixel_estimator, jpeg.JPEGEstimator):
+        raise ValueError("correct_bias=True is not defined for the JPEG predictor: it is not linear, so there is no prediction of x_bar - x")
 
 
 def _check_options(pixel_estimator, weighted, correct_bias, placement="random", order="rows") -> None:
     """An option an estimator does not have is the caller's error, not an image without an estimate (`attack` turns a ValueError of
     the statistic into beta_hat = None, as the reference does)."""
     sequential.check_placement(placement, order)
+    _require_no_bias_correction(pixel_estimator, correct_bias)
     if placement == "sequential":
         if isinstance(pixel_estimator, structural.StructuralEstimator):
             raise ValueError(f"placement='sequential' needs a pixel predictor; the structural estimators {structural.NAMES} have none")
@@ -208,7 +225,8 @@ def attack_stego(*args, **kw):
 
 def _native_planes_ok(channels, pixel_estimator, imread, process_image) -> bool:
     """The default gray pipeline (Y plane, built-in predictor) needs no host arrays: native batched decode -> pinned buffer -> device."""
-    builtin = isinstance(pixel_estimator, (UNetEstimator, filters.FilterEstimator, ols.AdaptiveOLSEstimator, structural.StructuralEstimator))
+    builtin = isinstance(pixel_estimator, (UNetEstimator, filters.FilterEstimator, ols.AdaptiveOLSEstimator, structural.StructuralEstimator,
+                                           jpeg.JPEGEstimator))
     plain = process_image is None or getattr(process_image, "plane_selector", None) == (3,)
     return builtin and imread is imread4_u8 and plain and tuple(channels) == (3,)
 
@@ -278,6 +296,9 @@ def run(
         _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
     elif model_name in ols.ADAPTIVE_NAMES:                       # 'OLSa' / 'OLSa2': the least-squares filter of each image under attack
         pixel_estimator = ols.adaptive_estimator(model_name)
+    elif model_name in jpeg.NAMES:                               # 'JPEG': each image after a round trip through its own quantisation table
+        pixel_estimator = jpeg.estimator(model_name)
+        _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
     elif model_name in NAMED_FILTERS:
         pixel_estimator = filters.get_filter_estimator(filter_name=model_name, flatten=False)
     else:
@@ -316,7 +337,8 @@ def parse_args(argv=None):
     ap.add_argument("--stego-methods", nargs="*", default=["LSBR"])
     ap.add_argument("--alphas", nargs="*", type=float, default=[.4, .2, .1])
     ap.add_argument("--filters", nargs="*", default=["AVG", "KB"],
-                    help="named filters, the adaptive 'OLSa' / 'OLSa2', and the structural estimators 'SPA' / 'RS' (with --weighted 0)")
+                    help="named filters, the adaptive 'OLSa' / 'OLSa2', the recompression predictor 'JPEG', and the structural estimators "
+                         "'SPA' / 'RS' (with --weighted 0)")
     ap.add_argument("--losses", nargs="*", default=["l1", "l1ws"])
     ap.add_argument("--weighted", type=int, default=0)
     ap.add_argument("--correct-bias", action="store_true")

@@ -28,7 +28,7 @@ from .. import fabrika, filters, ols, ops
 from ..imread import imread4_u8
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import model_device
-from . import estimate, structural
+from . import estimate, jpeg, structural
 
 MAX_IMAGES = ops.MAX_LOCATE_IMAGES
 THRESHOLD = 0.25                                           # halfway between the two expectations of the mean
@@ -206,12 +206,14 @@ _ITERATORS = {
 
 
 def pixel_predictor(model_name: str, model_path, channels):
-    """A named filter, 'OLSa' / 'OLSa2' or a trained UNet run as (pixel predictor, the name its rows carry); the structural estimators
+    """A named filter, 'OLSa' / 'OLSa2', 'JPEG' or a trained UNet run as (pixel predictor, the name its rows carry); the structural estimators
     have no per-pixel prediction and raise."""
     if model_name in structural.NAMES:
         raise ValueError(f"ws.locate needs a pixel predictor; the structural estimators {structural.NAMES} have none")
     if model_name in ols.ADAPTIVE_NAMES:
         return ols.adaptive_estimator(model_name), model_name
+    if model_name in jpeg.NAMES:
+        return jpeg.estimator(model_name), model_name
     if model_name in estimate.NAMED_FILTERS:
         return filters.get_filter_estimator(filter_name=model_name, flatten=False), model_name
     from .. import get_unet_estimator
@@ -272,7 +274,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--stego-method", default="LSBRK")
     ap.add_argument("--alpha", type=float, required=True)
-    ap.add_argument("--filters", nargs="*", default=["AVG", "KB"], help="named filters and the adaptive 'OLSa' / 'OLSa2'")
+    ap.add_argument("--filters", nargs="*", default=["AVG", "KB"], help="named filters, the adaptive 'OLSa' / 'OLSa2' and the recompression predictor 'JPEG'")
     ap.add_argument("--model-dir", default=None, help="trained UNets in the reference's layout <dir>/<train method>/<run>/; no UNet rows without it")
     ap.add_argument("--losses", nargs="*", default=["l1ws"], help="UNet runs under --model-dir: 'l1' (the dropout run), 'l1ws' (--train-method)")
     ap.add_argument("--train-method", default="LSBR", help="stego method the l1ws UNet was trained on")

@@ -35,7 +35,7 @@ from .. import filters as filters_lib
 from ..imread import imread4_u8
 from ..planes import load_planes_u8, upload_planes
 from ..unet_run import model_device
-from . import structural
+from . import jpeg, structural
 
 TAUS = np.linspace(0, 1, 501, endpoint=True)       # ascending; the reference walks them reversed
 AUC_COLUMNS = ["stego_method", "model_name", "auc", "p_e", "tau0", "fpr_tau0", "tpr_tau0", "fpr_50", "tpr_50"]
@@ -215,11 +215,12 @@ def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_MET
     from .. import ols
     names = list(filters)
     for name in names:
-        if name not in estimate.NAMED_FILTERS and name not in ols.ADAPTIVE_NAMES and name not in structural.NAMES:
+        if name not in estimate.NAMED_FILTERS and name not in ols.ADAPTIVE_NAMES and name not in structural.NAMES and name not in jpeg.NAMES:
             raise ValueError(f"unknown filter {name!r}; choose from "
-                             f"{sorted(estimate.NAMED_FILTERS) + sorted(ols.ADAPTIVE_NAMES) + sorted(structural.NAMES)}")
+                             f"{sorted(estimate.NAMED_FILTERS) + sorted(ols.ADAPTIVE_NAMES) + sorted(jpeg.NAMES) + sorted(structural.NAMES)}")
     preds = [(name, structural.StructuralEstimator(name) if name in structural.NAMES else
-              ols.adaptive_estimator(name) or filters_lib.get_filter_estimator(filter_name=name, flatten=False)) for name in names]
+              ols.adaptive_estimator(name) or jpeg.estimator(name) or filters_lib.get_filter_estimator(filter_name=name, flatten=False))
+             for name in names]
     est = estimate.as_unet_estimator(unet, mode)
     if est is not None:
         preds.append(("UNet", est))
@@ -281,7 +282,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--stego-methods", nargs="*", default=list(STEGO_METHODS))
     ap.add_argument("--alphas", nargs="+", type=float, default=list(ALPHAS),
                     help="pooled into one curve per stego method; the LAST one names the output files")
-    ap.add_argument("--filters", nargs="*", default=list(WS_FILTERS), help="named filters of filters.NAMED_FILTERS_2D, 'OLSa' / 'OLSa2', and the structural estimators 'SPA' / 'RS'")
+    ap.add_argument("--filters", nargs="*", default=list(WS_FILTERS), help="named filters of filters.NAMED_FILTERS_2D, 'OLSa' / 'OLSa2', the recompression predictor 'JPEG', and the structural estimators 'SPA' / 'RS'")
     ap.add_argument("--scores", nargs=2, action="append", default=[], metavar=("FILE", "NAME"),
                     help="detector scores in the schema of results/detection/b0.csv (the `output` column; covers have an empty "
                          "stego_method) added as model NAME, which must contain 'B0'; repeatable")
