@@ -24,8 +24,9 @@ def demangle(names):
         return {n: n for n in names}
 
 
-def kernels(path):
-    """{symbol: [[opcode, ...] per basic block]} for every .amdhsa kernel body of the listing"""
+def kernels(path, waitcnt_operands=False):
+    """{symbol: [[opcode, ...] per basic block]} for every .amdhsa kernel body of the listing.  waitcnt_operands: an `s_waitcnt` keeps its
+    operands (`s_waitcnt lgkmcnt(4)`, one space between the words), every other instruction is its opcode alone"""
     res, cur, name = {}, None, None
     lab = re.compile(r"^([A-Za-z_.$][\w.$]*):")
     for line in open(path):
@@ -46,7 +47,7 @@ def kernels(path):
                 cur = None
             continue
         op = s.split()[0]
-        cur[-1].append(op)
+        cur[-1].append(" ".join(s.split()) if waitcnt_operands and op == "s_waitcnt" else op)
         if op.startswith("s_cbranch") or op in ("s_branch", "s_endpgm"):
             cur.append([])
     return res

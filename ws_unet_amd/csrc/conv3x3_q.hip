@@ -23,6 +23,13 @@
 // steady step issues ~19 vector instructions beside its 56 matrix instructions (it recomputed ~55 per step until profiles/r25).  The ninth
 // tap has no partner: its lanes 32-63 multiply zeros, which they read from a zero block in LDS (cleared at kernel entry; one address select per
 // operand in the step head instead of sixteen register selects per step); the scale bytes of those lanes are tap 8's real ones (0xFF = NaN).
+// The fragment pipeline (units_pipelined; format Q, both RQ): a whole step is 14 units -- per tap pair the fp4 unit, then the f16 products of its
+// taps -- and the fragment reads of unit u + 1 are issued before the matrix instructions of unit u, into the other of two fragment sets, one
+// scheduling region per unit: the wait in front of a unit's matrix instructions leaves the next unit's reads in flight, and a wave waits out
+// an LDS latency of its own only for the step's first and last unit (left to the compiler most units' reads stood right in front of their
+// wait, in both waves of a SIMD at once; tools/step_isa.py --stream shows the order, tests/test_isa_pipeline.py holds it).  The split last
+// step of a tile (EPO) keeps the compiler's order: its halves are scheduled with the epilogue.  Registers: the second set lives beside the
+// accumulators where the epilogue's values do later, so no instantiation grows (profiles/r26/resources.md).
 // Replaces nn.Conv2d(k=3, reflect) + F.relu (+ torch.cat, nn.MaxPool2d, outconv + sigmoid) of src/unet/model/unet.py:141-189.
 // Weights: wsu_conv3x3_pack_f4 (below).
 // Format H (mode 'f16p', include/wsu.h K1h): the same kernel instantiated with FMT = WSU_PLANAR_H -- the f16 products alone (9 instead of 14 matrix
@@ -337,7 +344,7 @@ void conv3x3_q_kernel(const QArgs a) {
     // ================= matrix waves ===================================================================================================
     Tile cur = tile_of(a, lw);
     constexpr int MH = MSPLIT ? 1 : 2;                                        // accumulator tiles along the output channels
-    constexpr bool PIPE = RQ == 4 && !H;                                        // explicit software pipeline of the fragment reads (below)
+    constexpr bool PIPE = !H;                                                   // explicit software pipeline of the fragment reads (below)
     // the last step of a tile is split by accumulator tile: its second half shares a basic block with the first half of the epilogue.  (Not the head
     // variants: split, they fit -- 147-149 registers, no scratch, the same bits -- but the forward was 0.2 % slower in a same-box A/B: profiles/r21)
     constexpr bool EPO = !MSPLIT && HC == 0 && RQ != 4;
@@ -473,14 +480,18 @@ _Pragma("unroll")
         });
     };
     constexpr std::integral_constant<int, -1> all_m{};
-    // ---- RQ = 4, one matrix wave per SIMD: nobody fills the matrix pipe while this wave waits for its fragments, and hipcc issues a unit's LDS reads
-    // right in front of its matrix instructions (ISA of the first build: `10 x ds_read, s_waitcnt, mfma` fourteen times per step = fourteen exposed
-    // LDS latencies; 6 % SLOWER than two waves per SIMD).  So the step is written as a software pipeline: the fragments of unit u + 1 are requested
-    // before the matrix instructions of unit u, into the other of two fragment sets, one scheduling region per unit (the compiler's
-    // `s_waitcnt lgkmcnt(n)` then leaves exactly the younger unit's reads in flight).  Units of a step, in the accumulation order of the other
-    // variants: u = 3 tp + k: k = 0 the fp4 cross terms of tap pair tp, k = 1 / 2 the f16 products of taps 2 tp / 2 tp + 1 (14 units).
+    // ---- the fragment pipeline of a whole step (format Q).  It was written for RQ = 4, one matrix wave per SIMD: nobody fills the matrix pipe while
+    // that wave waits for its fragments, and hipcc issues a unit's LDS reads right in front of its matrix instructions (ISA of the first build:
+    // `10 x ds_read, s_waitcnt, mfma` fourteen times per step = fourteen exposed LDS latencies; 6 % SLOWER than two waves per SIMD).  With two
+    // waves per SIMD (RQ = 2) the partner could cover such a wait, but it runs the same program from the same barrier and reaches its own read
+    // bursts at the same time.  So the step is written as a software pipeline: the fragments of unit u + 1 are requested before the matrix
+    // instructions of unit u, into the other of two fragment sets, one scheduling region per unit (the compiler's `s_waitcnt lgkmcnt(n)` then
+    // leaves exactly the younger unit's reads in flight).  Units of a step, in the accumulation order of units_range: u = 3 tp + k: k = 0 the
+    // fp4 cross terms of tap pair tp, k = 1 / 2 the f16 products of taps 2 tp / 2 tp + 1 (14 units).
     struct Frag { u32x4 a[2]; u32x4 b[4]; int sa[2]; int sb[4]; };
-    auto load_unit = [&](auto u_c, Frag& f) __attribute__((always_inline)) {
+    // RQ = 2: row 1 of tap (dy, dx) is row 0 of tap (dy + 1, dx) -- the unpipelined step reads those six granules once (the compiler merges the
+    // two loads), and so does the pipeline: `row1` hands them on by name, three taps later (no load is merged across a scheduling fence)
+    auto load_unit = [&](auto u_c, Frag& f, u32x4* row1) __attribute__((always_inline)) {
         constexpr int u = decltype(u_c)::value, tp = u / 3, k = u % 3;
         if constexpr (k == 0) {
             q4_reads(std::integral_constant<int, tp>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, MH>{}, f.a, f.b, f.sa, f.sb);
@@ -488,8 +499,14 @@ _Pragma("unroll")
             constexpr int tap = 2 * tp + k - 1, dy = tap / 3, dx = tap % 3;
 _Pragma("unroll")
             for (int m = 0; m < MH; ++m) f.a[m] = *(lds_cu32x4*)(at(a_off) + ((tap * 3) * 64 + m * 32) * 16);
+            if constexpr (RQ == 2) {
+                if constexpr (dy > 0) f.b[0] = row1[tap - 3];
+                else f.b[0] = *(lds_cu32x4*)(at(b_off) + (dy * IW + dx) * 16);
+                f.b[1] = row1[tap] = *(lds_cu32x4*)(at(b_off) + ((1 + dy) * IW + dx) * 16);
+            } else {
 _Pragma("unroll")
-            for (int q = 0; q < RQ; ++q) f.b[q] = *(lds_cu32x4*)(at(b_off) + ((q + dy) * IW + dx) * 16);
+                for (int q = 0; q < RQ; ++q) f.b[q] = *(lds_cu32x4*)(at(b_off) + ((q + dy) * IW + dx) * 16);
+            }
         }
     };
     auto mma_unit = [&](auto u_c, Frag& f, auto first_c) __attribute__((always_inline)) {
@@ -511,11 +528,12 @@ _Pragma("unroll")
         }
     };
     auto units_pipelined = [&](auto first_c) __attribute__((always_inline)) {
-        constexpr int NU = 14;                                                // one unit of reads in flight, two fragment sets
+        constexpr int NU = 14;                                                // one unit of reads in flight, two fragment sets (two units ahead, three sets: fits, and is 0.3 % slower -- profiles/r26)
         Frag fr[2];
-        load_unit(std::integral_constant<int, 0>{}, fr[0]);
+        u32x4 row1[9];
+        load_unit(std::integral_constant<int, 0>{}, fr[0], row1);
         WSU_STATIC_FOR(NU, u, {
-            if constexpr (u + 1 < NU) load_unit(std::integral_constant<int, u + 1>{}, fr[(u + 1) % 2]);
+            if constexpr (u + 1 < NU) load_unit(std::integral_constant<int, u + 1>{}, fr[(u + 1) % 2], row1);
             __builtin_amdgcn_sched_barrier(0);                                // (the reads FIRST: left to itself the scheduler sinks them behind most of the unit's matrix instructions)
             mma_unit(u_c, fr[u % 2], first_c);
             __builtin_amdgcn_sched_barrier(0);

@@ -27,6 +27,11 @@
 // registers for the launch (tap_sel): one add and one shift-add per unit.  The ninth tap's lanes 32-63 read their zero operands from a zero block
 // in the unused tail of the second step region.  A skip step issues 26-28 vector instructions beside its 56 matrix instructions (70-78 until
 // profiles/r25); the low step is as it was.
+// A skip step's 14 units run as the fragment pipeline of conv3x3_q.hip (reads of unit u + 1 before the matrix instructions of unit u, two
+// fragment sets).  The low steps keep the compiler's order: in the stamps on record (profiles/r06/stamps_merged_step.log) a skip step's
+// loaders are early (barrier wait 1823-1902 cycles, vmcnt wait 680-743) while its matrix waves lose 1256-1433 cycles at the barrier among
+// themselves, whereas in a low step the loaders are the late ones (vmcnt wait 983-1071, loader barrier wait 176-285): a low step ends when
+// its DMA lands, not when the fragments do.
 // Accuracy: Wc is formed in fp32 and then split like any weight (f16 + fp4 residual terms); `xu` is never rounded to storage -- the fused
 // result is closer to the exact composition than the two-kernel path.  Replaces ops.convt2x2_pl + ops.conv3x3_q in UNet._forward_planar.
 // Format H (mode 'f16p', template argument FMT = WSU_PLANAR_H): planar H tensors in and out, the f16 products alone (no fp4 instruction, no Q /
@@ -357,35 +362,63 @@ void conv3x3_qu_kernel(const UArgs a) {
         asm volatile("" ::: "memory");
     };
     // ---- a skip chunk: the nine taps of the ordinary conv, operands of conv3x3_q.hip (f16 products per tap, both cross terms of a tap pair as one fp4 instruction)
-    // FIRST: the step opens a tile -- the matrix instructions of its first unit take the literal zero for C and define the accumulators
+    // FIRST: the step opens a tile -- the matrix instructions of its first unit take the literal zero for C and define the accumulators.
+    // Format Q: the step is the software pipeline of conv3x3_q.hip (units_pipelined) -- 14 units in the accumulation order u = 3 tp + k (k = 0 the
+    // fp4 unit of tap pair tp, k = 1 / 2 the f16 products of taps 2 tp / 2 tp + 1), the fragment reads of unit u + 1 issued before the matrix
+    // instructions of unit u into the other of two fragment sets, one scheduling region per unit.  Left to the compiler a unit's reads stood
+    // right in front of the wait and the matrix instructions that use them, in both waves of a SIMD at once.
+    struct Frag { u32x4 a[2]; u32x4 b[2]; int sa[2]; int sb[2]; };
+    auto load_unit = [&](auto u_c, Frag& f) __attribute__((always_inline)) {
+        constexpr int u = decltype(u_c)::value, tp = u / 3, k = u % 3;
+        if constexpr (k == 0) {
+            constexpr bool single = 2 * tp + 1 >= 9;                      // the ninth tap
+            constexpr unsigned wimm = (unsigned)((6 * tp + 2) * 64) * 16u;
+            static_assert(!single || wimm == W4_IMM, "tap 8");
+            const unsigned wb = single ? x_w4 : x_w, sab = single ? x_sa4 : x_sa;
+            const unsigned bb = tp == 0 ? hd_b : (single ? x_b4 : Lb + in_off + 2 * PLANE_S + tap_sel[tp] * 4u);
+            const unsigned sbb = tp == 0 ? hd_sb : Lb + in_off + 3 * PLANE_S + tap_sel[tp];
+_Pragma("unroll")
+            for (int m = 0; m < 2; ++m) { f.a[m] = *(lds_cu32x4*)(at(wb) + wimm + m * 512); f.sa[m] = *(lds_cuchar*)(at(sab) + 128 * tp + m * 32); }
+_Pragma("unroll")
+            for (int q = 0; q < 2; ++q) {
+                f.b[q] = *(lds_cu32x4*)(at(bb) + q * QS);
+                f.sb[q] = *(lds_cint*)(at(sbb) + q * (QS >> 2));
+            }
+        } else {
+            constexpr int tap = 2 * tp + k - 1;
+            const unsigned pb = b_off + tap_s(tap / 3, tap % 3);
+_Pragma("unroll")
+            for (int m = 0; m < 2; ++m) f.a[m] = *(lds_cu32x4*)(at(a_off) + ((tap * WPL) * 64) * 16 + m * 512);
+_Pragma("unroll")
+            for (int q = 0; q < 2; ++q) f.b[q] = *(lds_cu32x4*)(at(pb) + q * QS);
+        }
+    };
+    auto mma_unit = [&](auto u_c, Frag& f, auto first_c) __attribute__((always_inline)) {
+        constexpr int u = decltype(u_c)::value, k = u % 3;
+        constexpr bool FIRST = decltype(first_c)::value && u == 0;
+_Pragma("unroll")
+        for (int m = 0; m < 2; ++m)
+_Pragma("unroll")
+            for (int q = 0; q < 2; ++q) {
+                if constexpr (k != 0) wsu_mfma_f16(f.a[m], f.b[q], acc[m][q]);
+                else if constexpr (FIRST) acc[m][q] = wsu_mfma_q4_z(f.a[m], f.b[q], f.sa[m], f.sb[q]);
+                else wsu_mfma_q4(f.a[m], f.b[q], f.sa[m], f.sb[q], acc[m][q]);
+            }
+    };
     auto skip_units = [&](auto first_c) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(first_c)::value;
-        WSU_STATIC_FOR(5, tp, {
-            if constexpr (!H) {
-                constexpr bool single = 2 * tp + 1 >= 9;                  // the ninth tap
-                constexpr unsigned wimm = (unsigned)((6 * tp + 2) * 64) * 16u;
-                static_assert(!single || wimm == W4_IMM, "tap 8");
-                u32x4 a4[2], b4[2]; int sa[2], sb[2];
-                const unsigned wb = single ? x_w4 : x_w, sab = single ? x_sa4 : x_sa;
-                const unsigned bb = tp == 0 ? hd_b : (single ? x_b4 : Lb + in_off + 2 * PLANE_S + tap_sel[tp] * 4u);
-                const unsigned sbb = tp == 0 ? hd_sb : Lb + in_off + 3 * PLANE_S + tap_sel[tp];
-_Pragma("unroll")
-                for (int m = 0; m < 2; ++m) { a4[m] = *(lds_cu32x4*)(at(wb) + wimm + m * 512); sa[m] = *(lds_cuchar*)(at(sab) + 128 * tp + m * 32); }
-_Pragma("unroll")
-                for (int q = 0; q < 2; ++q) {
-                    b4[q] = *(lds_cu32x4*)(at(bb) + q * QS);
-                    sb[q] = *(lds_cint*)(at(sbb) + q * (QS >> 2));
-                }
-_Pragma("unroll")
-                for (int m = 0; m < 2; ++m)
-_Pragma("unroll")
-                    for (int q = 0; q < 2; ++q) {
-                        if constexpr (FIRST && tp == 0) acc[m][q] = wsu_mfma_q4_z(a4[m], b4[q], sa[m], sb[q]);
-                        else wsu_mfma_q4(a4[m], b4[q], sa[m], sb[q], acc[m][q]);
-                    }
-            }
-            WSU_STATIC_FOR((2 * tp + 1 < 9 ? 2 : 1), k, {
-                constexpr int tap = 2 * tp + k;
+        if constexpr (!H) {
+            constexpr int NU = 14;                                        // one unit of reads in flight, two fragment sets
+            Frag fr[2];
+            load_unit(std::integral_constant<int, 0>{}, fr[0]);
+            WSU_STATIC_FOR(NU, u, {
+                if constexpr (u + 1 < NU) load_unit(std::integral_constant<int, u + 1>{}, fr[(u + 1) % 2]);
+                __builtin_amdgcn_sched_barrier(0);                        // (the reads FIRST: left to itself the scheduler sinks them behind the unit's matrix instructions)
+                mma_unit(u_c, fr[u % 2], first_c);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        } else {
+            WSU_STATIC_FOR(9, tap, {
                 u32x4 ah[2], bh[2];
                 const unsigned pb = b_off + tap_s(tap / 3, tap % 3);
 _Pragma("unroll")
@@ -396,11 +429,11 @@ _Pragma("unroll")
                 for (int m = 0; m < 2; ++m)
 _Pragma("unroll")
                     for (int q = 0; q < 2; ++q) {
-                        if constexpr (FIRST && H && tap == 0) acc[m][q] = wsu_mfma_f16_z(ah[m], bh[q]);
+                        if constexpr (FIRST && tap == 0) acc[m][q] = wsu_mfma_f16_z(ah[m], bh[q]);
                         else wsu_mfma_f16(ah[m], bh[q], acc[m][q]);
                     }
             });
-        });
+        }
     };
     // ---- a dy slice of a low chunk: taps (dy, 0) and (dy, 1) of this wave's class -- units cls * 2 + dx of the slice [8][3 planes][64 co][16 B] + [8][64] scale bytes
     auto low_units = [&](auto dy_c) __attribute__((always_inline)) {
