@@ -404,6 +404,33 @@ int wsu_ws_sequential(const uint8_t* x_u8, const float* x_hat, const float* pixe
                       int hat_full, float hat_scale, int weighted, int order, long long* k, long long* t_max, long long* t_all,
                       long long* curve, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
 
+/* ---- K33: the WS changepoint along a path given per image, for payloads placed in the order of an adaptivity criterion that the attacker
+ *      recomputes from the stego image (Schoettle, Korff, Boehme, WIFS 2012; not part of the reference).  x_u8, the ONE prediction source
+ *      (x_hat with hat_full and hat_scale / pixel_filter HOST / pixel_filters DEVICE (N,9)), mean_filter and weighted in {0, 1} as K27's.
+ *      tau = flip rate / 2 with 0 < tau <= 0.5: a used pixel is assumed flipped with probability 2 tau (1/4: a real message, K27's term;
+ *      1/2: every used pixel flipped, as HILLR does).  Per interior pixel, in float32 with K11's operation sequence, nothing contracted:
+ *        r = s * res;   d = r - tau;   t = wgt * d;   q = K27's fixed-point form of t (int64, 2^24 units, 0 for NaN).
+ *      path: DEVICE int32 (N,M), M = (H-2)(W-2) <= 2^27: image i's interior raster indices (r-1)(W-2) + (c-1) in the order the path
+ *      visits them, meant to be a permutation of 0..M-1.  An entry outside 0..M-1 is never dereferenced and contributes a zero term.
+ *      Outputs per image, DEVICE int64 [N], with T(j) = q[path[0]] + .. + q[path[j-1]] and T(0) = 0:
+ *        k = the smallest k in 0..M at which T(k) is maximal;   t_max = T(k);   t_all = T(M).
+ *      Exact integer sums and no atomics: the results depend on neither the split of the work, the batch nor the run.
+ *      wsu_ws_ordered_terms writes the term plane `terms` (DEVICE int64 (N,M), 8-byte aligned, raster order); wsu_ws_ordered_fold reduces
+ *      such a plane along `path` (workspace: wsu_ws_ordered_fold_workspace_bytes: 24 bytes per 2048 path positions of an image);
+ *      wsu_ws_ordered is the two in one call with the term plane in its workspace (wsu_ws_ordered_workspace_bytes = 8 M bytes per image
+ *      plus the fold's).  Workspaces: DEVICE, 8-byte aligned, fully written before they are read; the size functions give 0 for bad
+ *      arguments.  n <= 65535, h, w >= 3. */
+size_t wsu_ws_ordered_workspace_bytes(int n, int h, int w);
+size_t wsu_ws_ordered_fold_workspace_bytes(int n, int h, int w);
+int wsu_ws_ordered_terms(const uint8_t* x_u8, const float* x_hat, const float* pixel_filter, const float* pixel_filters,
+                         const float* mean_filter, int hat_full, float hat_scale, int weighted, float tau, long long* terms, int n, int h, int w,
+                         void* stream);
+int wsu_ws_ordered_fold(const long long* terms, const int* path, long long* k, long long* t_max, long long* t_all, void* workspace,
+                        size_t workspace_bytes, int n, int h, int w, void* stream);
+int wsu_ws_ordered(const uint8_t* x_u8, const float* x_hat, const float* pixel_filter, const float* pixel_filters, const float* mean_filter,
+                   int hat_full, float hat_scale, int weighted, float tau, const int* path, long long* k, long long* t_max, long long* t_all,
+                   void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
+
 /* ---- K29: per-pixel sums of the WS residual terms across images (Ker, "Locating steganographic payload via WS residuals", MM&Sec 2008;
  *      not part of the reference).  Inputs as K27's: x_u8 (N,H,W) DEVICE pixels, exactly ONE of x_hat (hat_full, hat_scale) /
  *      pixel_filter (HOST) / pixel_filters (DEVICE (N,9)), mean_filter (HOST) for weighted = 1; weighted = -1 is an argument error.
@@ -546,7 +573,7 @@ size_t wsu_roc_counts_workspace_bytes(int groups, int t);
 int wsu_roc_counts(const double* scores, const signed char* labels, const long long* offsets, int groups, const double* taus, int t,
                    long long* counts, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- K20-K23, K28, K30: the stego simulators HILLR, LSBR, LSBRS and LSBRK.  The reference's stego twins were made by a library outside its tree; HILLR is
+/* ---- K20-K23, K28, K30, K34: the stego simulators HILLR, LSBR, LSBRS, LSBRK and HILLRM.  The reference's stego twins were made by a library outside its tree; HILLR is
  *      pinned to them bit for bit (tests/golden/stego_HILLR_*), LSBR's realisation is defined here.  Every plane is DEVICE (N,H,W) and
  *      contiguous; H, W >= 1, H*W < 2^32, N <= 65535.  stego may alias cover.  Deterministic: integer atomics only, two calls give the
  *      same bits, and an image's result does not depend on its position in the batch or on the batch size.
@@ -600,6 +627,12 @@ int wsu_embed_lsbr_seq(const uint8_t* cover, const uint64_t* seeds, const long l
 int wsu_embed_lsbr_keyed(const uint8_t* cover, const uint64_t* seeds, uint64_t key_seed, uint64_t alpha_threshold, uint8_t* stego,
                          long long* changes, int n, int h, int w, void* stream);
 int wsu_lsbr_key_mask(uint64_t key_seed, uint64_t alpha_threshold, uint8_t* mask, int h, int w, void* stream);
+/* K34: HILLRM, HILLR's pixel selection carrying a real message: a pixel whose key (K20) is <= the key whose pattern is bits[image] (K21,
+ *      for a payload alpha at the HOST rank floor((H*W - 1) * alpha), -1 for alpha = 0) is USED, ties included as in K22; a used pixel
+ *      flips iff it flips under K23 at alpha = 1 with its image's seed.  So the flips are a subset of K22's at the same threshold, and a
+ *      negative rank leaves the cover.  seeds, changes, limits and aliasing as in K23. */
+int wsu_embed_threshold_lsbr(const uint8_t* cover, const double* key, const uint64_t* bits, const uint64_t* seeds, uint8_t* stego,
+                             long long* changes, int n, int h, int w, void* stream);
 
 /* ---- K31, K32: the JPEG history of a bitmap (Boehme, "Weighted stego-image steganalysis for JPEG covers", IH 2008; not part of the
  *      reference): which quantisation table an image was compressed with, and the image after a round trip through a table -- the WS

@@ -97,6 +97,11 @@ SIGNATURES = {
     "wsu_ws_attack_taps": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
     "wsu_ws_sequential_workspace_bytes": (c_size_t, [c_int, c_int]),
     "wsu_ws_sequential": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_int] + [_P] * 5 + [c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_ws_ordered_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wsu_ws_ordered_fold_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wsu_ws_ordered_terms": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_float, _P, c_int, c_int, c_int, _P]),
+    "wsu_ws_ordered_fold": (c_int, [_P] * 6 + [c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_ws_ordered": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_float] + [_P] * 5 + [c_size_t, c_int, c_int, c_int, _P]),
     "wsu_ws_residual_accumulate": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_int, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_ols_moments": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_spa_tables": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
@@ -124,6 +129,7 @@ SIGNATURES = {
     "wsu_embed_lsbr": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_embed_lsbr_seq": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_embed_lsbr_keyed": (c_int, [_P, _P, c_uint64, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
+    "wsu_embed_threshold_lsbr": (c_int, [_P] * 6 + [c_int, c_int, c_int, _P]),
     "wsu_lsbr_key_mask": (c_int, [c_uint64, c_uint64, _P, c_int, c_int, _P]),
     "wsu_jpeg_energies": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, _P]),
     "wsu_jpeg_predict": (c_int, [_P] * 5 + [c_int] * 3 + [_P]),

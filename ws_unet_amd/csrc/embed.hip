@@ -1,4 +1,4 @@
-// K20-K23, K28, K30: the stego simulators HILLR, LSBR, LSBRS and LSBRK (the reference ships ready-made twins of its five covers, made by a library outside its
+// K20-K23, K28, K30, K34: the stego simulators HILLR, LSBR, LSBRS, LSBRK and HILLRM (the reference ships ready-made twins of its five covers, made by a library outside its
 // tree; tests/golden/stego_HILLR_* pins HILLR to those files bit for bit, LSBR's realisation is this package's own):
 //
 //   HILLR   key = HILL cost in float64 (the operation order of tests/hill_np.hill_cost), full frame
@@ -10,6 +10,8 @@
 //           of the path over the whole plane, row by row from the top or from the bottom (K28)
 //   LSBRK   stego = cover ^ (key word < T  and  word < 2^31),  T = floor(alpha * 2^32) compared in 64 bits, key word = the same Philox word
 //           under the 64-bit stego key shared by all images: LSBR at alpha = 1 on the pixels the key selects (K30)
+//   HILLRM  stego = cover ^ (key <= c_(k)  and  word < 2^31),  k = floor((H*W - 1) * alpha): LSBR at alpha = 1 on the pixels HILLR's
+//           criterion selects, i.e. a real message instead of HILLR's flip of every selected pixel (K34)
 //
 // K20 is K12 in float64 on a 32 x 32 tile (the float64 arrays of a 64 x 64 tile would need 97 KB of LDS; a 32 x 32 tile needs 36 KB
 // and stays static): every sum is a direct sum in numpy's order, the two divisions are IEEE divisions, nothing is contracted.  K21 is an
@@ -405,6 +407,41 @@ __global__ __launch_bounds__(256) void embed_lsbr_keyed_kernel(const uint8_t* __
     if (!MASK) add_changes(cnt, changes + nn, tid);
 }
 
+// K34.  HILLRM: HILLR's pixel selection with a real message: a pixel whose key is at most the threshold pattern is USED, and a used pixel
+// flips as under K23 at alpha = 1 with the image's seed (word < 2^31).  One thread per quad of pixels (one generator call, none where no
+// pixel of the quad is used); bytes in and out, so any alignment and in-place use are fine.
+__global__ __launch_bounds__(256) void embed_threshold_lsbr_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ keys,
+                                                                   const uint64_t* __restrict__ bits, const uint64_t* __restrict__ seeds,
+                                                                   uint8_t* __restrict__ stego, long long* __restrict__ changes, long long hw) {
+    const int nn = blockIdx.y, tid = threadIdx.x;
+    const uint8_t* cin = cover + (size_t)nn * hw;
+    uint8_t* cout = stego + (size_t)nn * hw;
+    const uint64_t* kin = keys + (size_t)nn * hw;
+    const uint64_t thr = bits[nn];
+    const uint32_t k0 = (uint32_t)seeds[nn], k1 = (uint32_t)(seeds[nn] >> 32);
+    int cnt = 0;
+    for (long long g = (long long)blockIdx.x * 256 + tid; 4 * g < hw; g += (long long)gridDim.x * 256) {
+        bool used[4];
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            used[e] = 4 * g + e < hw && kin[4 * g + e] <= thr;
+            any = any || used[e];
+        }
+        Words4 wd{{~0u, ~0u, ~0u, ~0u}};
+        if (any) wd = philox4x32_10((uint32_t)g, k0, k1);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * g + e < hw) {
+                const uint8_t flip = used[e] && wd.v[e] < 0x80000000u ? 1 : 0;
+                cout[4 * g + e] = cin[4 * g + e] ^ flip;
+                cnt += flip;
+            }
+        }
+    }
+    add_changes(cnt, changes + nn, tid);
+}
+
 int embed_blocks(long long hw) {
     const long long b = (hw / 16 + 255) / 256;
     return (int)(b < 1 ? 1 : b > EMB_MAX_BLOCKS ? EMB_MAX_BLOCKS : b);
@@ -508,6 +545,18 @@ int wsu_embed_lsbr_keyed(const uint8_t* cover, const uint64_t* seeds, uint64_t k
     hipLaunchKernelGGL(embed_lsbr_keyed_kernel<false>, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, key_seed, alpha_threshold, stego,
                        changes, hw);
     return wsu_check_launch("embed_lsbr_keyed_kernel");
+}
+
+int wsu_embed_threshold_lsbr(const uint8_t* cover, const double* key, const uint64_t* bits, const uint64_t* seeds, uint8_t* stego,
+                             long long* changes, int n, int h, int w, void* stream) {
+    WSU_REQUIRE(cover && key && bits && seeds && stego && changes, "embed_threshold_lsbr: null pointer");
+    EMBED_REQUIRE_SHAPE("embed_threshold_lsbr");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long hw = (long long)h * w;
+    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_threshold_lsbr memset");
+    hipLaunchKernelGGL(embed_threshold_lsbr_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, reinterpret_cast<const uint64_t*>(key),
+                       bits, seeds, stego, changes, hw);
+    return wsu_check_launch("embed_threshold_lsbr_kernel");
 }
 
 int wsu_lsbr_key_mask(uint64_t key_seed, uint64_t alpha_threshold, uint8_t* mask, int h, int w, void* stream) {

@@ -42,26 +42,6 @@ constexpr int WSS_STEP = 64 * WSS_PER;                  // pixels of a row per w
 constexpr int WSS_PITCH = WSS_PER + 1;                  // LDS pitch of a lane's run in 8-byte words: 72 B, a half-wave's b64 reads hit 32 different bank pairs
 using Taps = Taps3x3<float>;
 
-template <typename A> struct MaxPrefix { long long sum, best; A arg; };
-template <typename A> __device__ __forceinline__ MaxPrefix<A> mp_combine(const MaxPrefix<A>& a, const MaxPrefix<A>& b) {
-    const long long cand = a.sum + b.best;
-    const bool keep = a.best >= cand;                   // >=: among equal maxima the first
-    return MaxPrefix<A>{a.sum + b.sum, keep ? a.best : cand, keep ? a.arg : b.arg};
-}
-// lane 0 receives the wave's 64 triples combined in lane order (lane l holds lanes l .. l + 2 off - 1 after the step `off` where that range
-// exists; the other lanes' values are not used)
-template <typename A> __device__ __forceinline__ MaxPrefix<A> mp_wave(MaxPrefix<A> a) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        MaxPrefix<A> b;
-        b.sum = __shfl_down(a.sum, off, 64);
-        b.best = __shfl_down(a.best, off, 64);
-        b.arg = __shfl_down(a.arg, off, 64);
-        a = mp_combine(a, b);
-    }
-    return a;
-}
-
 __global__ __launch_bounds__(256) void ws_sequential_rows_kernel(
     const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, Taps mean_taps, Taps pixel_taps, const float* __restrict__ image_filters,
     int use_pixel_filter, int hat_full, float hat_scale, int weighted, long long* __restrict__ rows, int h, int w) {

@@ -1,6 +1,6 @@
-// Device helpers shared by the metric kernels K10-K18, K27, K29 and K32 and the simulators K20-K23, K28 and K30 (pointwise.hip K10 + WS meter,
-// ws_attack.hip, ws_sequential.hip, ws_locate.hip, jpeg_history.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's
-// taps, the prediction at a pixel, the float32 residual, the WS statistic's per-pixel terms, the HILL cost's input window, the fixed-order
+// Device helpers shared by the metric kernels K10-K18, K27, K29, K32 and K33 and the simulators K20-K23, K28, K30 and K34 (pointwise.hip K10 + WS meter,
+// ws_attack.hip, ws_sequential.hip, ws_ordered.hip, ws_locate.hip, jpeg_history.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip): the one definition each of a 3x3 predictor's
+// taps, the prediction at a pixel, the float32 residual, the WS statistic's per-pixel terms, the maximum-prefix triple, the HILL cost's input window, the fixed-order
 // block sum and the radix-select steps.
 //
 // Rounding policy: these functions restate numpy's float32 / float64 operation sequences with PLAIN operators, one rounding each.  That
@@ -63,7 +63,7 @@ __device__ __forceinline__ float residual_f32(float x, float y, float scale) {
     return x - xhat;
 }
 
-// ---- the WS statistic's per-pixel terms (K11, K27, K29) ---------------------------------------------------------------------------------
+// ---- the WS statistic's per-pixel terms (K11, K27, K29, K33) -----------------------------------------------------------------------------
 // At interior pixel (r, c) of the uint8 plane `img` (row stride w), in numpy's float32 operation sequence (src/ws/estimate.py:90-121):
 //   wgt  = 1 (weighted 0) | 1 / (5 + var) (weighted > 0) | 5 + var (weighted < 0),  var = conv(x*x, mean) - conv(x, mean)^2
 //   s    = x - x_bar = +-1
@@ -118,12 +118,36 @@ __device__ __forceinline__ WsTerms ws_pixel_terms(const uint8_t* __restrict__ im
     return o;
 }
 
-// The fixed-point form of a float32 term t (K27, K29): 0 where t is NaN, else llrint((double)min(max(t, -4096), 4096) * 2^24), round to
+// The fixed-point form of a float32 term t (K27, K29, K33): 0 where t is NaN, else llrint((double)min(max(t, -4096), 4096) * 2^24), round to
 // nearest even.  |q| <= 2^36, so sums of such terms are exact integers whatever their order.
 __device__ __forceinline__ long long ws_seq_term(float t) {
     if (t != t) return 0;                               // NaN
     const float c = t < -4096.0f ? -4096.0f : t > 4096.0f ? 4096.0f : t;
     return __builtin_llrint((double)c * 16777216.0);
+}
+
+// ---- the maximum-prefix triple of a run of fixed-point terms (K27, K33) ---------------------------------------------------------------
+// (sum, best, arg): the run's sum, the largest of its prefix sums (the empty prefix, 0, takes part) and the position behind the FIRST
+// prefix that reaches it, counted from the start of the whole sequence, so that combining shifts nothing.  Runs combine associatively,
+// left before right; a single term q at position p is (q, max(q, 0), p + (q > 0)), and a term of 0 never wins on the right.
+template <typename A> struct MaxPrefix { long long sum, best; A arg; };
+template <typename A> __device__ __forceinline__ MaxPrefix<A> mp_combine(const MaxPrefix<A>& a, const MaxPrefix<A>& b) {
+    const long long cand = a.sum + b.best;
+    const bool keep = a.best >= cand;                   // >=: among equal maxima the first
+    return MaxPrefix<A>{a.sum + b.sum, keep ? a.best : cand, keep ? a.arg : b.arg};
+}
+// lane 0 receives the wave's 64 triples combined in lane order (lane l holds lanes l .. l + 2 off - 1 after the step `off` where that range
+// exists; the other lanes' values are not used)
+template <typename A> __device__ __forceinline__ MaxPrefix<A> mp_wave(MaxPrefix<A> a) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        MaxPrefix<A> b;
+        b.sum = __shfl_down(a.sum, off, 64);
+        b.best = __shfl_down(a.best, off, 64);
+        b.arg = __shfl_down(a.arg, off, 64);
+        a = mp_combine(a, b);
+    }
+    return a;
 }
 
 // ---- the HILL cost's input window (K12 fp32, K20 fp64) -----------------------------------------------------------------------------

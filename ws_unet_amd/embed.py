@@ -1,5 +1,6 @@
-"""Stego simulators on the device: HILLR, LSBR, LSBRS and LSBRK twins of cover images (wsu_hill_cost_f64, wsu_rank_select_f64,
-wsu_embed_threshold, wsu_embed_lsbr, wsu_embed_lsbr_seq, wsu_embed_lsbr_keyed; include/wsu.h K20-K23, K28, K30).
+"""Stego simulators on the device: HILLR, LSBR, LSBRS, LSBRK and HILLRM twins of cover images (wsu_hill_cost_f64, wsu_rank_select_f64,
+wsu_embed_threshold, wsu_embed_lsbr, wsu_embed_lsbr_seq, wsu_embed_lsbr_keyed, wsu_embed_threshold_lsbr; include/wsu.h K20-K23, K28, K30,
+K34).
 
 The reference ships its five covers with ready-made `stego_*` folders from a library outside its tree.  Here a covers-only data
 set gets its twins from the package itself:
@@ -21,6 +22,10 @@ smaller alpha is a prefix of one at a larger alpha (ws.estimate's placement='seq
 LSBRK is LSB replacement under a shared stego key: the 64-bit `placement_key` selects a fraction alpha of the pixel positions, the same
 in every image of the same size (ops.lsbr_key_mask), and a selected pixel flips as under LSBR at alpha = 1 with the image's seed.  So
 LSBRK at alpha = 1 is LSBR at alpha = 1 and at alpha = 0 the cover (ws.locate finds the selected positions from many such images).
+HILLRM is HILLR with a real message instead of its flip of every selected pixel: the pixels whose float64 HILL cost is at most the order
+statistic of rank floor((H*W - 1) * alpha) are used (ties included, as HILLR flips them), and a used pixel flips as under LSBR at
+alpha = 1 with the image's seed.  So about alpha / 2 of the pixels change, all among the cheapest; at alpha = 0 the twin is the cover
+(ws.estimate's placement='adaptive' with flip_rate=0.5 is the matching estimator).
 """
 from __future__ import annotations
 
@@ -33,12 +38,12 @@ import torch
 
 from . import fabrika
 
-METHODS = ("LSBR", "HILLR", "LSBRS", "LSBRK")
+METHODS = ("LSBR", "HILLR", "LSBRS", "LSBRK", "HILLRM")
 ORDERS = ("rows", "rows_up")
 
 
 def method_name(stego_method: str) -> str:
-    """'LSBR' / 'HILLR' / 'LSBRS' / 'LSBRK', matched case-insensitively (the reference spells both 'LSBr' and 'LSBR')."""
+    """'LSBR' / 'HILLR' / 'LSBRS' / 'LSBRK' / 'HILLRM', matched case-insensitively (the reference spells both 'LSBr' and 'LSBR')."""
     m = str(stego_method).upper()
     if m not in METHODS:
         raise NotImplementedError(f"stego method {stego_method!r} is not simulated here: choose one of {' / '.join(METHODS)}")
@@ -56,6 +61,11 @@ def image_seed(filename, stream: int = 0) -> int:
 def hillr_rank(alpha: float, h: int, w: int) -> int:
     """k = floor((H*W - 1) * alpha / 2) in float64: the k + 1 cheapest pixels change.  alpha == 0 -> -1 (no pixel changes)."""
     return int(np.floor((h * w - 1) * (float(alpha) / 2))) if alpha > 0 else -1
+
+
+def hillrm_rank(alpha: float, h: int, w: int) -> int:
+    """floor((H*W - 1) * alpha) in float64: the pixels up to the key of this rank are used by 'HILLRM'.  alpha == 0 -> -1 (none is)."""
+    return int(np.floor((h * w - 1) * float(alpha))) if alpha > 0 else -1
 
 
 def lsbrs_count(alpha: float, h: int, w: int) -> int:
@@ -94,9 +104,9 @@ def _alphas(alpha, n: int) -> np.ndarray:
 def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, key: typing.Optional[torch.Tensor] = None,
              order: str = "rows", placement_key: typing.Optional[int] = None):
     """cover_u8: (N,H,W) uint8 on the device; alpha: a scalar or one value per image -> (stego (N,H,W) uint8, changes (N) int64), both
-    on the device.  'LSBR', 'LSBRS' and 'LSBRK' need `seeds`, one 64-bit integer per image (image_seed); 'HILLR' ignores them and takes an optional
-    `key` = ops.hill_cost_f64(cover_u8) made earlier (several alphas of the same covers).  `order` ('rows' / 'rows_up') is the path of
-    'LSBRS'; the other methods have none.  `placement_key` is the shared stego key of 'LSBRK' (one alpha for the whole batch: the used
+    on the device.  'LSBR', 'LSBRS', 'LSBRK' and 'HILLRM' need `seeds`, one 64-bit integer per image (image_seed); 'HILLR' ignores them.
+    'HILLR' and 'HILLRM' take an optional `key` = ops.hill_cost_f64(cover_u8) made earlier (several alphas of the same covers).  `order`
+    ('rows' / 'rows_up') is the path of 'LSBRS'; the other methods have none.  `placement_key` is the shared stego key of 'LSBRK' (one alpha for the whole batch: the used
     positions are the same in every image)."""
     from . import ops
     method = method_name(stego_method)
@@ -117,6 +127,11 @@ def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, ke
     s = np.array([int(v) % 2 ** 64 for v in (seeds.tolist() if isinstance(seeds, (torch.Tensor, np.ndarray)) else seeds)], dtype=np.uint64)
     if s.shape != (n,):
         raise ValueError(f"simulate: {s.shape[0] if s.ndim else 1} seeds for {n} images")
+    if method == "HILLRM":
+        if key is None:
+            key = ops.hill_cost_f64(cover_u8)
+        k = torch.tensor([hillrm_rank(v, h, w) for v in a], dtype=torch.int64).to(dev)
+        return ops.embed_threshold_lsbr(cover_u8, key, ops.rank_select_f64(key, k), torch.from_numpy(s.view(np.int64)).to(dev))
     if method == "LSBRK":
         if not np.all(a == a[0]):
             raise ValueError(f"simulate: 'LSBRK' takes one alpha for all images (one key selects one set of pixels), got {alpha!r}")
@@ -154,8 +169,8 @@ def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, order="r
     planes = prefetched[0] if prefetched is not None else _prefetch(fnames, kws)[0]
     cover = torch.from_numpy(np.ascontiguousarray(planes)).to("cuda")
     method = method_name(stego_method)
-    key = ops.hill_cost_f64(cover) if method == "HILLR" else None
-    seeds = [image_seed(f, stream) for f in fnames] if method in ("LSBR", "LSBRS", "LSBRK") else None
+    key = ops.hill_cost_f64(cover) if method in ("HILLR", "HILLRM") else None
+    seeds = [image_seed(f, stream) for f in fnames] if method != "HILLR" else None
     rows = [[] for _ in fnames]
     for a in alphas:
         stego = simulate(cover, method, a, seeds, key=key, order=order, placement_key=placement_key)[0].cpu().numpy()
@@ -195,12 +210,12 @@ def write_dataset(data_dir, stego_method: str, alpha, *, split: typing.Optional[
 
 
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(description="Write simulated stego twins of a data set's covers (HILLR / LSBR / LSBRS / LSBRK, made on the GPU).")
+    ap = argparse.ArgumentParser(description="Write simulated stego twins of a data set's covers (HILLR / LSBR / LSBRS / LSBRK / HILLRM, made on the GPU).")
     ap.add_argument("--data", required=True, help="data set directory (images*/files.csv)")
     ap.add_argument("--stego-method", required=True, help=" / ".join(METHODS))
     ap.add_argument("--alphas", type=float, nargs="+", required=True, help="embedding rates in [0, 1]")
     ap.add_argument("--split", default=None, help="a split CSV of the data set: only its covers")
-    ap.add_argument("--stream", type=int, default=0, help="LSBR / LSBRS realisation number (image_seed)")
+    ap.add_argument("--stream", type=int, default=0, help="LSBR / LSBRS / LSBRK / HILLRM realisation number (image_seed)")
     ap.add_argument("--order", choices=ORDERS, default="rows", help="LSBRS: the message runs row by row from the top, or from the bottom row up")
     ap.add_argument("--key", type=int, default=None, help="LSBRK: the 64-bit stego key that selects the used pixels of every image")
     ns = ap.parse_args(argv)

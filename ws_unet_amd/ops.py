@@ -1033,6 +1033,22 @@ def ws_attack(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, x_bia
     return (beta, sums) if return_sums else beta
 
 
+def _predictor_pointers(who: str, x_hat, pixel_filter, n: int, h: int, w: int, dev):
+    """(x_hat pointer, HOST filter, DEVICE per-image filters, hat_full) of the ONE prediction source of K27-style entry points; the
+    returned arrays must stay alive until the launch."""
+    pt = pts = None
+    hat_full = 1
+    if pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3):      # (N,3,3[,1])
+        if len(pixel_filter) != n:
+            raise ValueError(f"{who}: {len(pixel_filter)} filters for {n} images")
+        pts = torch.from_numpy(np.stack([filter_taps(f, np.float32, "kernel") for f in pixel_filter])).to(dev)
+    elif pixel_filter is not None:
+        pt = filter_taps(pixel_filter, np.float32, "kernel")
+    else:
+        hat_full = _hat_full(x_hat, n, h, w, None)
+    return pt, pts, hat_full
+
+
 ORDERS = ("rows", "rows_up")               # path orders of the sequential statistic and simulator: rows from the top / from the bottom
 
 
@@ -1063,22 +1079,118 @@ def ws_sequential(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, p
     k, t_max, t_all = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
     curve = torch.empty((n, h - 2), dtype=torch.int64, device=dev) if return_curve else None
     ws = torch.empty(max(lib.wsu_ws_sequential_workspace_bytes(n, h) // 8, 1), dtype=torch.int64, device=dev)
-    pt = pts = None
-    hat_full = 1
-    if pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3):      # (N,3,3[,1])
-        if len(pixel_filter) != n:
-            raise ValueError(f"ws_sequential: {len(pixel_filter)} filters for {n} images")
-        pts = torch.from_numpy(np.stack([filter_taps(f, np.float32, "kernel") for f in pixel_filter])).to(dev)
-    elif pixel_filter is not None:
-        pt = filter_taps(pixel_filter, np.float32, "kernel")
-    else:
-        hat_full = _hat_full(x_hat, n, h, w, None)
+    pt, pts, hat_full = _predictor_pointers("ws_sequential", x_hat, pixel_filter, n, h, w, dev)
     check(_launch("ws_sequential", {"bytes": float(n * h * w * (1 if x_hat is None else 5))}, lambda: lib.wsu_ws_sequential(
         x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
         pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
         oid, k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), curve.data_ptr() if curve is not None else None,
         ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())), "wsu_ws_sequential")
     return (k, t_max, t_all, curve) if return_curve else (k, t_max, t_all)
+
+
+def _flip_tau(who: str, flip_rate) -> float:
+    """tau = (float32)(flip_rate / 2) of the ordered statistic; flip_rate outside (0, 1] raises ValueError."""
+    f = float(flip_rate)
+    if not 0.0 < f <= 1.0:
+        raise ValueError(f"{who}: flip_rate must lie in (0, 1] (1: every used pixel flipped, 0.5: a real message), got {flip_rate!r}")
+    return float(np.float32(f / 2.0))
+
+
+def _ordered_path(who: str, path, n: int, m: int, dev) -> None:
+    if not (isinstance(path, torch.Tensor) and path.dtype == torch.int32 and tuple(path.shape) == (n, m)):
+        raise ValueError(f"{who}: path must be an int32 tensor of shape {(n, m)} (one permutation of the interior raster indices per image), "
+                         f"got {tuple(path.shape) if isinstance(path, torch.Tensor) else type(path).__name__}"
+                         f"{' ' + str(path.dtype) if isinstance(path, torch.Tensor) else ''}")
+    _dev_check(path)
+    if path.device != dev:
+        raise ValueError(f"{who}: path lives on {path.device}, the pixels on {dev}")
+
+
+def _ordered_arguments(who: str, x_u8, x_hat, pixel_filter, mean_filter, weighted, flip_rate):
+    """The checked arguments kernel A of K33 takes: ((n, h, w), tau, HOST mean filter, HOST filter, DEVICE per-image filters, hat_full)."""
+    if int(weighted) not in (0, 1):
+        raise ValueError(f"{who}: weighted must be 0 or 1 (weighted=-1 is not defined for the changepoint statistic), got {weighted}")
+    if (x_hat is None) == (pixel_filter is None):
+        raise ValueError(f"{who}: give exactly one of x_hat / pixel_filter")
+    tau = _flip_tau(who, flip_rate)
+    _dev_check(x_u8, x_hat)
+    n, h, w = _u8_planes(x_u8)
+    if h < 3 or w < 3:
+        raise ValueError(f"{who}: planes of at least 3 x 3 pixels expected, got {h} x {w}")
+    mt = filter_taps(mean_filter, np.float32, "kernel")
+    return (n, h, w), tau, mt, *_predictor_pointers(who, x_hat, pixel_filter, n, h, w, x_u8.device)
+
+
+def ws_ordered_terms(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, mean_filter=None,
+                     hat_scale: float = 255., weighted: int = 1, flip_rate: float = 1.0) -> torch.Tensor:
+    """Kernel A of K33 alone (wsu_ws_ordered_terms): the fixed-point terms q = ws_seq_term(wgt * (s * res - flip_rate / 2)) of every
+    interior pixel, int64 (N, (H-2)(W-2)) in raster order.  Arguments as ws_ordered's."""
+    lib = _lib.load()
+    (n, h, w), tau, mt, pt, pts, hat_full = _ordered_arguments("ws_ordered_terms", x_u8, x_hat, pixel_filter, mean_filter, weighted, flip_rate)
+    terms = torch.empty((n, (h - 2) * (w - 2)), dtype=torch.int64, device=x_u8.device)
+    check(_launch("ws_ordered_terms", {"bytes": float(n * h * w * (9 if x_hat is None else 13))}, lambda: lib.wsu_ws_ordered_terms(
+        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
+        pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
+        tau, terms.data_ptr(), n, h, w, _stream())), "wsu_ws_ordered_terms")
+    return terms
+
+
+def ws_ordered_fold(terms: torch.Tensor, path: torch.Tensor, h: int, w: int):
+    """Kernels B and C of K33 alone (wsu_ws_ordered_fold): terms int64 (N,M) as ws_ordered_terms makes them, path int32 (N,M), M =
+    (h-2)(w-2) -> int64 (N,) tensors (k, t_max, t_all) of the cumulative sums of terms[i, path[i, :]]."""
+    who = "ws_ordered_fold"
+    h, w = int(h), int(w)
+    m = (h - 2) * (w - 2)
+    if not (isinstance(terms, torch.Tensor) and terms.dtype == torch.int64 and terms.dim() == 2 and terms.shape[1] == m and h >= 3 and w >= 3):
+        raise ValueError(f"{who}: terms must be an int64 (N,{m}) tensor for planes of {h} x {w}")
+    _dev_check(terms)
+    n, dev = terms.shape[0], terms.device
+    _ordered_path(who, path, n, m, dev)
+    lib = _lib.load()
+    k, t_max, t_all = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+    ws = torch.empty(max(lib.wsu_ws_ordered_fold_workspace_bytes(n, h, w) // 8, 1), dtype=torch.int64, device=dev)
+    check(_launch("ws_ordered_fold", {"bytes": float(n * m * 12)}, lambda: lib.wsu_ws_ordered_fold(
+        terms.data_ptr(), path.data_ptr(), k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), ws.data_ptr(), ws.numel() * 8, n, h, w,
+        _stream())), "wsu_ws_ordered_fold")
+    return k, t_max, t_all
+
+
+def ws_ordered(x_u8: torch.Tensor, path: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, mean_filter=None,
+               hat_scale: float = 255., weighted: int = 1, flip_rate: float = 1.0):
+    """The WS changepoint along a given path (wsu_ws_ordered, K33), for payloads placed in the order of an adaptivity criterion.  x_u8:
+    (N,H,W) uint8; path: int32 (N,M) on the same device, M = (H-2)(W-2): per image the interior raster indices (r-1)(W-2) + (c-1) in the
+    order the path visits them (interior_order makes one from a key plane); an entry outside 0..M-1 contributes nothing.  The prediction
+    as for ws_sequential: x_hat (N,H,W)/(N,1,H,W) full frames or (N,H-2,W-2) interiors, multiplied by `hat_scale`, or `pixel_filter`
+    (3,3[,1]) for an in-kernel linear predictor, (N,3,3[,1]) for one per image.  weighted: 0 or 1.  flip_rate in (0, 1]: the probability
+    that a used pixel was flipped (1: HILLR flips every used pixel; 0.5: a real message, ws_sequential's term).  Returns int64 (N,)
+    tensors (k, t_max, t_all): the first maximiser k in 0..M of the fixed-point cumulative statistic T (2^24 units) along the path, T(k)
+    and T(M).  The change rate is flip_rate * k / M (ws.adaptive.beta)."""
+    lib = _lib.load()
+    (n, h, w), tau, mt, pt, pts, hat_full = _ordered_arguments("ws_ordered", x_u8, x_hat, pixel_filter, mean_filter, weighted, flip_rate)
+    dev = x_u8.device
+    _ordered_path("ws_ordered", path, n, (h - 2) * (w - 2), dev)
+    k, t_max, t_all = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+    ws = torch.empty(max(lib.wsu_ws_ordered_workspace_bytes(n, h, w) // 8, 1), dtype=torch.int64, device=dev)
+    check(_launch("ws_ordered", {"bytes": float(n * h * w * (29 if x_hat is None else 33))}, lambda: lib.wsu_ws_ordered(
+        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
+        pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
+        tau, path.data_ptr(), k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())),
+        "wsu_ws_ordered")
+    return k, t_max, t_all
+
+
+def interior_order(keys: torch.Tensor) -> torch.Tensor:
+    """keys: (N,H,W) float32 on the device, e.g. hill_cost's output -> int32 (N,M), M = (H-2)(W-2): per image the interior raster indices
+    in ascending order of keys[:, 1:-1, 1:-1], ties to the smaller index: the `path` of ws_ordered.  This is torch.sort(stable=True) on
+    the device, not a kernel of this library: the sort is plumbing around K33, and a hand-written one is a follow-up."""
+    if not (isinstance(keys, torch.Tensor) and keys.dtype == torch.float32 and keys.dim() == 3 and keys.shape[1] >= 3 and keys.shape[2] >= 3):
+        raise ValueError(f"interior_order: an (N,H,W) float32 tensor with H, W >= 3 expected, got "
+                         f"{tuple(keys.shape) if isinstance(keys, torch.Tensor) else type(keys).__name__}")
+    if not keys.is_cuda:
+        raise _lib.WsuError("interior_order sorts on the GPU: got a CPU tensor")
+    n = keys.shape[0]
+    order = torch.sort(keys[:, 1:-1, 1:-1].reshape(n, -1), dim=1, stable=True).indices
+    return order.to(torch.int32).contiguous()
 
 
 MAX_LOCATE_IMAGES = 65536                  # images one pair of accumulators may hold: |num| < 2^53 and den < 2^53 stay exact in float64
@@ -1104,16 +1216,7 @@ def ws_residual_accumulate(x_u8: torch.Tensor, num: torch.Tensor, den: torch.Ten
                              f"{(h, w)}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
     _dev_check(x_u8, num, den, *[t for t in (x_hat,) if t is not None])
     mt = filter_taps(mean_filter, np.float32, "kernel")
-    pt = pts = None
-    hat_full = 1
-    if pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3):      # (N,3,3[,1])
-        if len(pixel_filter) != n:
-            raise ValueError(f"ws_residual_accumulate: {len(pixel_filter)} filters for {n} images")
-        pts = torch.from_numpy(np.stack([filter_taps(f, np.float32, "kernel") for f in pixel_filter])).to(x_u8.device)
-    elif pixel_filter is not None:
-        pt = filter_taps(pixel_filter, np.float32, "kernel")
-    else:
-        hat_full = _hat_full(x_hat, n, h, w, None)
+    pt, pts, hat_full = _predictor_pointers("ws_residual_accumulate", x_hat, pixel_filter, n, h, w, x_u8.device)
     check(_launch("ws_residual_accumulate", {"bytes": float(n * h * w * (1 if x_hat is None else 5) + 32 * (h - 2) * (w - 2))},
                   lambda: lib.wsu_ws_residual_accumulate(
         x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
@@ -1341,6 +1444,23 @@ def embed_lsbr_seq(cover_u8: torch.Tensor, seeds: torch.Tensor, counts: torch.Te
     check(_launch("embed_lsbr_seq", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbr_seq(
         cover_u8.data_ptr(), seeds.data_ptr(), counts.data_ptr(), oid, stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())),
         "wsu_embed_lsbr_seq")
+    return stego, changes
+
+
+def embed_threshold_lsbr(cover_u8: torch.Tensor, key: torch.Tensor, bits: torch.Tensor, seeds: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """HILLR's selection with a real message (K34): a pixel with key <= the key whose pattern is bits[i] is used, and a used pixel flips as
+    under embed_lsbr at alpha = 1 with the image's seed.  key: (N,H,W) float64; bits, seeds: (N) int64 -> (stego (N,H,W) uint8, changes
+    (N) int64)."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(cover_u8)
+    _dev_check(key, bits, seeds)
+    assert key.dtype == torch.float64 and key.shape == cover_u8.shape and bits.dtype == torch.int64 and bits.shape == (n,)
+    assert seeds.dtype == torch.int64 and seeds.shape == (n,)
+    stego = torch.empty_like(cover_u8)
+    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
+    check(_launch("embed_threshold_lsbr", {"bytes": float(n * h * w * 10)}, lambda: lib.wsu_embed_threshold_lsbr(
+        cover_u8.data_ptr(), key.data_ptr(), bits.data_ptr(), seeds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())),
+        "wsu_embed_threshold_lsbr")
     return stego, changes
 
 

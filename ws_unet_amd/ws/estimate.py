@@ -14,6 +14,8 @@ kernel, wsu_ws_attack; there is no host implementation in this package.
   * `placement='sequential'` (with `order='rows'` or 'rows_up') replaces the statistic by the changepoint estimator for payloads written
     into the first pixels of the file order (ws/sequential.py, wsu_ws_sequential): every pixel predictor works, the structural
     estimators, weighted=-1 and correct_bias do not.  The default, placement='random', is the reference's statistic.
+  * `placement='adaptive'` (with `criterion='hill'` and `flip_rate`) is the changepoint estimator along the order of an adaptivity
+    criterion recomputed from the image under attack (ws/adaptive.py, wsu_ws_ordered), for HILLR-style payloads; options as 'sequential'.
   * the model name 'JPEG' (ws/jpeg.py, a `jpeg.JPEGEstimator`) predicts every image by its own round trip through the JPEG quantiser it
     was once compressed with: a full-frame device prediction like a UNet's, for both placements, without bias correction.
   * `run(..., batched=True)` is `run` on the batched iterators; the joblib iterators of the reference (:139,144) cannot
@@ -35,7 +37,7 @@ from .. import fabrika, filters, ols, ops
 from ..imread import imread4_u8, u8_plane
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import check_unet_geometry, model_device, unet_plane
-from . import jpeg, sequential, structural
+from . import adaptive, jpeg, sequential, structural
 
 NAMED_FILTERS = filters.NAMED_FILTERS_2D
 
@@ -138,9 +140,9 @@ def _changepoint(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, 
 
 
 def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=None, placement="random",
-          order="rows") -> torch.Tensor:
+          order="rows", criterion="hill", flip_rate=1.0) -> torch.Tensor:
     """beta_hat[N] on the device for a batch of planes."""
-    _check_options(pixel_estimator, weighted, correct_bias, placement, order)
+    _check_options(pixel_estimator, weighted, correct_bias, placement, order, criterion, flip_rate)
     if isinstance(pixel_estimator, structural.StructuralEstimator):    # no predictor, no weights: the estimator is the statistic
         structural.require_unweighted(weighted, correct_bias)
         return pixel_estimator.beta(x_u8).to(torch.float32)
@@ -148,6 +150,10 @@ def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct
     if placement == "sequential":                                      # the changepoint k -> the change rate of the whole plane
         k = _changepoint(x_u8, pixel_estimator, mean_estimator, weighted, order, pred=pred)[0]
         beta = sequential.beta(k, x_u8.shape[1], x_u8.shape[2], order).to(torch.float32)
+    elif placement == "adaptive":                                      # the changepoint along the recomputed cost order
+        k = ops.ws_ordered(x_u8, adaptive.path_for(x_u8, criterion), mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted),
+                           flip_rate=flip_rate, **pred)[0]
+        beta = adaptive.beta(k, x_u8.shape[1], x_u8.shape[2], flip_rate).to(torch.float32)
     else:
         beta = ops.ws_attack(x_u8, mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted) if abs(int(weighted)) == 1 else 0,
                              correct_bias=correct_bias, **pred)
@@ -159,23 +165,27 @@ def _require_no_bias_correction(pixel_estimator, correct_bias) -> None:
         raise ValueError("correct_bias=True is not defined for the JPEG predictor: it is not linear, so there is no prediction of x_bar - x")
 
 
-def _check_options(pixel_estimator, weighted, correct_bias, placement="random", order="rows") -> None:
+def _check_options(pixel_estimator, weighted, correct_bias, placement="random", order="rows", criterion="hill", flip_rate=1.0) -> None:
     """An option an estimator does not have is the caller's error, not an image without an estimate (`attack` turns a ValueError of
     the statistic into beta_hat = None, as the reference does)."""
     sequential.check_placement(placement, order)
     _require_no_bias_correction(pixel_estimator, correct_bias)
-    if placement == "sequential":
+    if placement == "adaptive":
+        adaptive.check_options(criterion, flip_rate)
+    if placement in ("sequential", "adaptive"):
         if isinstance(pixel_estimator, structural.StructuralEstimator):
-            raise ValueError(f"placement='sequential' needs a pixel predictor; the structural estimators {structural.NAMES} have none")
+            raise ValueError(f"placement={placement!r} needs a pixel predictor; the structural estimators {structural.NAMES} have none")
         if int(weighted) not in (0, 1) or correct_bias:
-            raise ValueError(f"placement='sequential' takes weighted 0 or 1 and correct_bias=False, got weighted={weighted} "
+            raise ValueError(f"placement={placement!r} takes weighted 0 or 1 and correct_bias=False, got weighted={weighted} "
                              f"correct_bias={correct_bias}")
     elif isinstance(pixel_estimator, structural.StructuralEstimator):
         structural.require_unweighted(weighted, correct_bias)
 
 
-def _placement_tail(placement, order) -> dict:
+def _placement_tail(placement, order, criterion="hill", flip_rate=1.0) -> dict:
     """The row columns of a placement other than the default: existing tables keep their columns."""
+    if placement == "adaptive":
+        return {"placement": placement, "criterion": criterion, "flip_rate": flip_rate}
     return {} if placement == "random" else {"placement": placement, "order": order}
 
 
@@ -190,16 +200,19 @@ def attack(
     process_image: typing.Callable = None,
     placement: str = "random",
     order: str = "rows",
+    criterion: str = "hill",
+    flip_rate: float = 1.0,
     **kw,
 ) -> dict:
     """WS estimate of one image (estimate.py:55-136): returns kw | {beta_hat, channels, weighted, correct_bias}; with
-    placement='sequential' the changepoint estimate of ws/sequential.py, and the row also says placement and order."""
-    _check_options(pixel_estimator, weighted, correct_bias, placement, order)
+    placement='sequential' the changepoint estimate of ws/sequential.py, and the row also says placement and order; with
+    placement='adaptive' that of ws/adaptive.py, and the row says placement, criterion and flip_rate."""
+    _check_options(pixel_estimator, weighted, correct_bias, placement, order, criterion, flip_rate)
     x = process_image(imread(fname))                         # x_bar = process(x ^ 1) is formed on the device
     try:
         x_u8 = torch.from_numpy(_as_u8_plane(x))[None].to(model_device(unet_model_of(pixel_estimator)))
         beta_hat = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=[x], placement=placement,
-                         order=order)[0].item()
+                         order=order, criterion=criterion, flip_rate=flip_rate)[0].item()
         beta_hat = np.float32(beta_hat)
     except ValueError:                                      # estimate.py:122-123
         beta_hat = None
@@ -208,7 +221,7 @@ def attack(
         "channels": "".join(map(str, channels)),
         "weighted": weighted,
         "correct_bias": correct_bias,
-    } | _placement_tail(placement, order)
+    } | _placement_tail(placement, order, criterion, flip_rate)
 
 
 @fabrika.precovers(iterator="python", ignore_missing=True)
@@ -232,9 +245,10 @@ def _native_planes_ok(channels, pixel_estimator, imread, process_image) -> bool:
 
 
 def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED_FILTERS["AVG"], correct_bias=False,
-                 weighted=1, imread=imread4_u8, process_image=None, prefetched=None, placement="random", order="rows", **_ignored):
+                 weighted=1, imread=imread4_u8, process_image=None, prefetched=None, placement="random", order="rows", criterion="hill",
+                 flip_rate=1.0, **_ignored):
     """`attack` for a chunk of files (fabrika iterator='batched'): one result dict per (fname, kw)."""
-    _check_options(pixel_estimator, weighted, correct_bias, placement, order)
+    _check_options(pixel_estimator, weighted, correct_bias, placement, order, criterion, flip_rate)
     if _native_planes_ok(channels, pixel_estimator, imread, process_image):
         u8 = prefetched[0] if prefetched is not None else load_planes_u8(fnames, imread)
         planes = None if u8 is None else [None] * len(fnames)
@@ -246,21 +260,23 @@ def attack_batch(fnames, kws, *, channels, pixel_estimator, mean_estimator=NAMED
             planes = None
     if planes is None:
         process_image = process_image or filters.get_processor_2d(channels)
-        return [attack(f, channels, pixel_estimator, mean_estimator, correct_bias, weighted, imread, process_image, placement, order, **kw)
-                for f, kw in zip(fnames, kws)]
+        return [attack(f, channels, pixel_estimator, mean_estimator, correct_bias, weighted, imread, process_image, placement, order,
+                       criterion, flip_rate, **kw) for f, kw in zip(fnames, kws)]
     try:
         if u8 is None:
             u8 = torch.from_numpy(np.stack([_as_u8_plane(p) for p in planes]))
         x_u8 = upload_planes(u8, model_device(unet_model_of(pixel_estimator)))
         beta = _stat(x_u8, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=planes, placement=placement,
-                     order=order).cpu().numpy()
+                     order=order, criterion=criterion, flip_rate=flip_rate).cpu().numpy()
     except ValueError:
         beta = [None] * len(fnames)
-    tail = {"channels": "".join(map(str, channels)), "weighted": weighted, "correct_bias": correct_bias} | _placement_tail(placement, order)
+    tail = {"channels": "".join(map(str, channels)), "weighted": weighted, "correct_bias": correct_bias}
+    tail |= _placement_tail(placement, order, criterion, flip_rate)
     return [kw | {"beta_hat": beta[i]} | tail for i, kw in enumerate(kws)]
 
 
-_ATTACK_KEYS = ("channels", "pixel_estimator", "mean_estimator", "correct_bias", "weighted", "imread", "process_image", "placement", "order")
+_ATTACK_KEYS = ("channels", "pixel_estimator", "mean_estimator", "correct_bias", "weighted", "imread", "process_image", "placement", "order",
+                "criterion", "flip_rate")
 
 
 def _prefetch_native(fnames, kws):
@@ -287,9 +303,10 @@ def run(
 ):
     """WS attack over a data set with a named linear filter or a trained UNet as the pixel predictor (estimate.py:149-205), or one of
     the structural estimators of ws/structural.py ('SPA', 'RS': weighted=0, correct_bias=False) in the same rows.  placement='sequential'
-    (with order='rows' / 'rows_up') among the keywords: the changepoint estimator of ws/sequential.py with the same predictors."""
+    (with order='rows' / 'rows_up') among the keywords: the changepoint estimator of ws/sequential.py with the same predictors;
+    placement='adaptive' (with criterion='hill' and flip_rate): the one of ws/adaptive.py along the recomputed cost order."""
     process_cover = filters.get_processor_2d(channels=channels)
-    placed = (kw.get("placement", "random"), kw.get("order", "rows"))
+    placed = (kw.get("placement", "random"), kw.get("order", "rows"), kw.get("criterion", "hill"), kw.get("flip_rate", 1.0))
     _check_options(None, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
     if model_name in structural.NAMES:
         pixel_estimator = structural.StructuralEstimator(model_name)
@@ -344,8 +361,12 @@ def parse_args(argv=None):
     ap.add_argument("--correct-bias", action="store_true")
     ap.add_argument("--per-image", action="store_true", help="use the per-image iterators instead of the batched ones")
     ap.add_argument("--placement", choices=sequential.PLACEMENTS, default="random",
-                    help="where the payload is assumed to lie: spread uniformly (the WS statistic) or in the first pixels of the file order")
+                    help="where the payload is assumed to lie: spread uniformly (the WS statistic), in the first pixels of the file order, or "
+                         "in the pixels of lowest cost under --criterion, recomputed from each image under attack")
     ap.add_argument("--order", choices=sequential.ORDERS, default="rows", help="sequential placement: rows from the top, or from the bottom")
+    ap.add_argument("--criterion", choices=adaptive.CRITERIA, default="hill", help="adaptive placement: the cost that orders the pixels")
+    ap.add_argument("--flip-rate", type=float, default=1.0,
+                    help="adaptive placement: the probability that a used pixel was flipped (1: HILLR flips every used pixel; 0.5: a real message)")
     ap.add_argument("--out", default=None)
     ols.add_kernels_argument(ap)
     return ap.parse_args(argv)
@@ -362,7 +383,9 @@ def main(argv=None) -> None:
     model_dir = pathlib.Path(a.model_dir)
     settings = [(None, .0)] + [(sm, al) for sm in a.stego_methods for al in a.alphas]
     common = dict(demosaic=None, channels=(3,), correct_bias=a.correct_bias, weighted=a.weighted, batched=not a.per_image)
-    if a.placement != "random":
+    if a.placement == "adaptive":
+        common |= dict(placement=a.placement, criterion=a.criterion, flip_rate=a.flip_rate)
+    elif a.placement != "random":
         common |= dict(placement=a.placement, order=a.order)
     res = []
     for stego_method, alpha in settings:

@@ -35,7 +35,7 @@ from .. import filters as filters_lib
 from ..imread import imread4_u8
 from ..planes import load_planes_u8, upload_planes
 from ..unet_run import model_device
-from . import jpeg, structural
+from . import adaptive, jpeg, sequential, structural
 
 TAUS = np.linspace(0, 1, 501, endpoint=True)       # ascending; the reference walks them reversed
 AUC_COLUMNS = ["stego_method", "model_name", "auc", "p_e", "tau0", "fpr_tau0", "tpr_tau0", "fpr_50", "tpr_50"]
@@ -157,7 +157,7 @@ def _prefetch(fnames, kws):
     return (load_planes_u8(fnames),)
 
 
-def _submit(fnames, clean, *, predictors, placement="random", order="rows", prefetched=None):
+def _submit(fnames, clean, *, predictors, placement="random", order="rows", criterion="hill", flip_rate=1.0, prefetched=None):
     """Upload the chunk once and queue every predictor's statistic (ws.estimate._stat) on it; nothing waits for the GPU.  A ragged
     chunk goes through ws.estimate.attack image by image, as ws.estimate.attack_batch does."""
     from . import estimate
@@ -165,16 +165,17 @@ def _submit(fnames, clean, *, predictors, placement="random", order="rows", pref
     if planes is None:
         proc = filters_lib.get_processor_2d((3,))
         return "host", [[estimate.attack(f, (3,), est, estimate.NAMED_FILTERS["AVG"], False, 0, imread4_u8, proc, placement, order,
-                                        **{**kw, "model_name": name})
+                                        criterion, flip_rate, **{**kw, "model_name": name})
                          for name, est in predictors] for f, kw in zip(fnames, clean)]
     x = upload_planes(planes, model_device(estimate.unet_model_of(predictors[-1][1])))
     betas = []
     for _, est in predictors:
         try:
-            betas.append(estimate._stat(x, est, estimate.NAMED_FILTERS["AVG"], 0, False, placement=placement, order=order))
+            betas.append(estimate._stat(x, est, estimate.NAMED_FILTERS["AVG"], 0, False, placement=placement, order=order, criterion=criterion,
+                                        flip_rate=flip_rate))
         except ValueError:                                   # ws.estimate.attack_batch: no estimate for this chunk
             betas.append(None)
-    return "device", (clean, [name for name, _ in predictors], betas, estimate._placement_tail(placement, order))
+    return "device", (clean, [name for name, _ in predictors], betas, estimate._placement_tail(placement, order, criterion, flip_rate))
 
 
 def _collect(handle):
@@ -193,14 +194,14 @@ def _score_chunk(fnames, kws, prefetched=None, **shared):
 
 
 _score_chunk.submit, _score_chunk.collect = _submit, _collect
-_score_chunk = fabrika.shared_kwargs(_score_chunk, ("predictors", "placement", "order"), _prefetch)
+_score_chunk = fabrika.shared_kwargs(_score_chunk, ("predictors", "placement", "order", "criterion", "flip_rate"), _prefetch)
 _score_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(_score_chunk)
 _score_stegos = fabrika.stego_spatial(iterator="batched", convert_to=None, ignore_missing=True)(_score_chunk)
 
 
 def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_METHODS, alphas: typing.Sequence[float] = ALPHAS,
                       filters: typing.Sequence[str] = WS_FILTERS, unet=None, mode: str = None, progress_on: bool = False,
-                      placement: str = "random", order: str = "rows", **kw):
+                      placement: str = "random", order: str = "rows", criterion: str = "hill", flip_rate: float = 1.0, **kw):
     """The WS rows the reference's main concatenates (roc.py:372-395): for the cover set, then each stego method x alpha, the rows of
     ws.estimate.run(..., weighted=0, correct_bias=False, channels=(3,), batched=True) of each named filter (or structural estimator,
     'SPA' / 'RS', whose curves are labelled with their own names, not 'WS-<name>') and then of the UNet
@@ -208,8 +209,9 @@ def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_MET
     decoded (native PNG reader, one chunk ahead) and uploaded once, and every predictor's statistic runs on that device batch.
     unet: None (no UNet rows), a ws.estimate.UNetEstimator, a model, or (model_path, model_name) of a trained run loaded in
     inference `mode`.  placement='sequential' (with `order`) scores every image with the changepoint estimator of ws/sequential.py instead
-    (pixel predictors only); the rows then also carry `placement` and `order`.  Other keywords go to the fabrika iterators
-    (take_num_images, split, ...)."""
+    (pixel predictors only); the rows then also carry `placement` and `order`.  placement='adaptive' (with `criterion` and `flip_rate`) scores
+    with the estimator of ws/adaptive.py along the recomputed cost order; the rows then carry `placement`, `criterion` and `flip_rate`.
+    Other keywords go to the fabrika iterators (take_num_images, split, ...)."""
     import pandas as pd
     from . import estimate
     from .. import ols
@@ -227,8 +229,10 @@ def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_MET
     if not preds:
         raise ValueError("no predictor: give filters and / or a UNet")
     for _, p in preds:                                       # an option a predictor does not have is an error up front, not an empty curve
-        estimate._check_options(p, 0, False, placement, order)
+        estimate._check_options(p, 0, False, placement, order, criterion, flip_rate)
     placed = dict(placement=placement, order=order) if placement != "random" else {}
+    if placement == "adaptive":
+        placed = dict(placement=placement, criterion=criterion, flip_rate=flip_rate)
     frames = []
     for stego_method, alpha in [(None, None)] + [(sm, al) for sm in stego_methods for al in alphas]:
         if stego_method:
@@ -288,9 +292,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "stego_method) added as model NAME, which must contain 'B0'; repeatable")
     ap.add_argument("--mode", default=None, help="UNet inference mode (default: the package default)")
     ap.add_argument("--progress", action="store_true")
-    ap.add_argument("--placement", choices=("random", "sequential"), default="random",
-                    help="where the payload is assumed to lie: spread uniformly (the WS statistic) or in the first pixels of the file order")
-    ap.add_argument("--order", choices=("rows", "rows_up"), default="rows", help="sequential placement: rows from the top, or from the bottom")
+    ap.add_argument("--placement", choices=sequential.PLACEMENTS, default="random",
+                    help="where the payload is assumed to lie: spread uniformly (the WS statistic), in the first pixels of the file order, or "
+                         "in the pixels of lowest cost under --criterion, recomputed from each image under attack")
+    ap.add_argument("--order", choices=sequential.ORDERS, default="rows", help="sequential placement: rows from the top, or from the bottom")
+    ap.add_argument("--criterion", choices=adaptive.CRITERIA, default="hill", help="adaptive placement: the cost that orders the pixels")
+    ap.add_argument("--flip-rate", type=float, default=1.0,
+                    help="adaptive placement: the probability that a used pixel was flipped (1: HILLR flips every used pixel; 0.5: a real message)")
     from ..ols import add_kernels_argument
     add_kernels_argument(ap)
     return ap.parse_args(argv)
@@ -309,7 +317,7 @@ def main(argv=None) -> None:
         (method, model_name, _), = trained_runs(a.model_dir, [a.train_method])
         unet = (pathlib.Path(a.model_dir) / method, model_name)
     res = collect_ws_scores(a.data, a.stego_methods, a.alphas, a.filters, unet=unet, mode=a.mode, progress_on=a.progress, placement=a.placement,
-                            order=a.order)
+                            order=a.order, criterion=a.criterion, flip_rate=a.flip_rate)
     res = pd.concat([res] + detectors).reset_index(drop=True)
     res["stego_method"] = res["stego_method"].fillna("Cover")
     res["alpha"] = res["alpha"].fillna(0.)

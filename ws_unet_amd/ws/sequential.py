@@ -31,7 +31,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-PLACEMENTS = ("random", "sequential")
+PLACEMENTS = ("random", "sequential", "adaptive")      # 'adaptive': along a recomputed cost order, ws/adaptive.py
 ORDERS = ("rows", "rows_up")
 
 
