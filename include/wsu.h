@@ -448,6 +448,22 @@ int wsu_ws_residual_accumulate(const uint8_t* x_u8, const float* x_hat, const fl
                                const float* mean_filter, int hat_full, float hat_scale, int weighted, int parts, long long* num, long long* den,
                                int n, int h, int w, void* stream);
 
+/* ---- K35: the stego-key search over K29's sums (Fridrich, Goljan, Soukal, "Searching for the stego-key", SPIE 5306, 2004; not part of
+ *      the reference): masked sums of two int64 planes under many Philox keys.  num, den: DEVICE int64, `count` entries in FRAME layout
+ *      (entry i = the pixel of linear index i, K30's i; the caller zero-fills the frame's border), 1 <= count <= 2^34.  The K candidate
+ *      keys, 1 <= K <= 2^31-1, are EITHER `keys`, a DEVICE array of K 64-bit patterns (key_range = 0), OR the range key_first + j,
+ *      j = 0..K-1, wrapping mod 2^64 (keys = NULL, key_range = 1).  thr in 0..2^32.  Pixel i is SELECTED under a key iff word i % 4 of
+ *      Philox4x32-10 on counter (i / 4, 0, 0, 0) under the key (low, high word) is below thr, compared in 64 bits: K30's rule, so the
+ *      selection is wsu_lsbr_key_mask(key, thr) and thresholds nest (a smaller thr selects a subset).  snum, sden: DEVICE int64 [K],
+ *      zeroed on the stream by the call:
+ *        snum[j] = sum of num[i] over the selected i < count;   sden[j] = the same sum of den[i];
+ *      two's-complement int64 addition, wrapping, which is the definition: the result depends on neither the grid, the order of the adds
+ *      nor `parts`, the number of workgroups that share a key's pixels (1: one owner per key and plain stores; more: 64-bit integer
+ *      atomics; 0: as many as bring the grid to about 1024 workgroups, at least 64 quads of pixels each).  All arrays 8-byte aligned;
+ *      every argument is checked before any HIP call. */
+int wsu_ws_key_search(const long long* num, const long long* den, long long count, const uint64_t* keys, uint64_t key_first, int key_range,
+                      int k, uint64_t thr, int parts, long long* snum, long long* sden, void* stream);
+
 /* ---- K24: moments of the least-squares 3x3 pixel predictor.  x_u8: (N,H,W) DEVICE pixels.  At every interior pixel (r,c), with
  *      xab = x[r-1+a][c-1+b], v = [x00 x01 x02 x12 x22 x21 x20 x10 x11] (the ring order of the flattened 8-tap filters,
  *      _defs/filters.py:57-67, centre last).  moments: DEVICE (N,45) uint64, zeroed on the stream by this call:

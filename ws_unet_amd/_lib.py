@@ -103,6 +103,7 @@ SIGNATURES = {
     "wsu_ws_ordered_fold": (c_int, [_P] * 6 + [c_size_t, c_int, c_int, c_int, _P]),
     "wsu_ws_ordered": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_float] + [_P] * 5 + [c_size_t, c_int, c_int, c_int, _P]),
     "wsu_ws_residual_accumulate": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    "wsu_ws_key_search": (c_int, [_P, _P, c_longlong, _P, c_uint64, c_int, c_int, c_uint64, c_int, _P, _P, _P]),
     "wsu_ols_moments": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_spa_tables": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_rs_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),

@@ -20,6 +20,7 @@
 // workspace and the change counters are zeroed on the stream: two calls give the same bits.
 #pragma clang fp contract(off)
 #include "wsu_metric.h"
+#include "wsu_philox.h"
 
 namespace {
 
@@ -242,20 +243,7 @@ __global__ __launch_bounds__(256) void embed_threshold_kernel(const uint8_t* __r
     add_changes(cnt, changes + nn, tid);
 }
 
-// K23.  Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32 x 32 -> 64 bit products, the key bumped between rounds.
-struct Words4 { uint32_t v[4]; };
-__device__ __forceinline__ Words4 philox4x32_10(uint32_t c0, uint32_t k0, uint32_t k1) {
-    uint32_t c[4] = {c0, 0u, 0u, 0u};
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Words4{{c[0], c[1], c[2], c[3]}};
-}
-
+// K23.  Philox4x32-10 (Salmon et al., SC'11): philox4x32_10 of wsu_philox.h, shared with the stego-key search (K35).
 __global__ __launch_bounds__(256) void embed_lsbr_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ seeds,
                                                          const uint32_t* __restrict__ thresholds, uint8_t* __restrict__ stego,
                                                          long long* __restrict__ changes, long long hw) {
@@ -352,17 +340,7 @@ __global__ __launch_bounds__(256) void embed_lsbr_seq_kernel(const uint8_t* __re
 // K30.  LSBRK: the message occupies the pixels a stego key selects, the same in every image: pixel i is used iff word i % 4 of counter
 // (i / 4, 0, 0, 0) under the key is below `thr` (floor(alpha * 2^32), up to 2^32: 64-bit comparison); a used pixel flips as under K23 at
 // alpha = 1 with the image's own seed.  A quad without a used pixel costs one generator call, not two.  MASK: the used positions
-// themselves (1 / 0), one plane, no cover.
-__device__ __forceinline__ uint32_t below_bytes(const Words4& wd, uint64_t thr) {        // byte e = (word e < thr)
-    uint32_t m = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) m |= ((uint64_t)wd.v[e] < thr ? 1u : 0u) << (8 * e);
-    return m;
-}
-__device__ __forceinline__ uint32_t word_of(const Words4& wd, int e) {                   // (selects: a dynamic index would put the words in LDS)
-    return e == 0 ? wd.v[0] : e == 1 ? wd.v[1] : e == 2 ? wd.v[2] : wd.v[3];
-}
-
+// themselves (1 / 0), one plane, no cover.  (below_bytes, word_of: wsu_philox.h.)
 template <bool MASK>
 __global__ __launch_bounds__(256) void embed_lsbr_keyed_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ seeds,
                                                                uint64_t key, uint64_t thr, uint8_t* __restrict__ stego,

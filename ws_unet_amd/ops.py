@@ -1224,6 +1224,76 @@ def ws_residual_accumulate(x_u8: torch.Tensor, num: torch.Tensor, den: torch.Ten
         int(parts), num.data_ptr(), den.data_ptr(), n, h, w, _stream())), "wsu_ws_residual_accumulate")
 
 
+MAX_KEY_SEARCH_KEYS = 2 ** 31 - 1          # keys one call of ws_key_search takes
+KEY_SEARCH_SUM_LIMIT = 2 ** 62             # sum |num| and sum |den| stay below it, so no masked sum can wrap
+
+
+def _abs_sum(t: torch.Tensor) -> int:
+    """The exact sum of |t| of an int64 tensor as a Python int (the high and the low 32 bits are summed apart: no int64 sum can wrap)."""
+    if bool((t == torch.iinfo(torch.int64).min).any()):
+        return 2 ** 63 * int((t == torch.iinfo(torch.int64).min).sum())
+    a = t.abs()
+    return (int((a >> 32).sum()) << 32) + int((a & 0xFFFFFFFF).sum())
+
+
+def ws_key_search(num: torch.Tensor, den: torch.Tensor, h: int, w: int, *, keys: Optional[torch.Tensor] = None, key_first: Optional[int] = None,
+                  count: Optional[int] = None, alpha_threshold: int, rows: Optional[int] = None, parts: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The sums of K29's accumulators over the pixels each of many candidate stego keys selects (wsu_ws_key_search, K35).  num, den: the
+    int64 (H-2,W-2) accumulators of ws_residual_accumulate for (h, w) planes; they are padded to zero-bordered (H,W) frames here, since a
+    key selects by the pixel's linear index in the frame, exactly as lsbr_key_mask(key, alpha_threshold, h, w) does.  The candidates are
+    EITHER `keys`, an int64 (K) device tensor holding 64-bit patterns (as seeds do), OR the range key_first + j, j = 0..count-1, wrapping
+    mod 2^64.  alpha_threshold: 0..2^32 (lsbr_key_threshold); a threshold below the embedder's selects a subset of the used pixels.
+    rows = R scans the first R frame rows only, a cheap prefilter.  parts: workgroups sharing a key's pixels (0: chosen from K) -- the
+    sums are exact integers and do not depend on it.  -> (snum, sden), int64 (K).  Raises ValueError when sum |num| or sum |den| reaches
+    2^62: below it no masked sum can wrap."""
+    who = "ws_key_search"
+    h, w = int(h), int(w)
+    if h < 3 or w < 3:
+        raise ValueError(f"{who}: a frame of at least 3 x 3 pixels expected, got {h} x {w}")
+    for name, t in (("num", num), ("den", den)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and tuple(t.shape) == (h - 2, w - 2)):
+            raise ValueError(f"{who}: {name} must be an int64 tensor of shape {(h - 2, w - 2)} for frames of {(h, w)}, got "
+                             f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if (keys is None) == (key_first is None and count is None):
+        raise ValueError(f"{who}: give exactly one of keys and (key_first, count)")
+    if keys is None and (key_first is None or count is None):
+        raise ValueError(f"{who}: a key range needs both key_first and count")
+    thr = int(alpha_threshold)
+    if not 0 <= thr <= 2 ** 32:
+        raise ValueError(f"{who}: alpha_threshold {alpha_threshold!r} outside 0..2^32 (lsbr_key_threshold)")
+    r = h if rows is None else int(rows)
+    if not 1 <= r <= h:
+        raise ValueError(f"{who}: rows={rows!r} outside 1..{h}")
+    if not 0 <= int(parts) <= 65535:
+        raise ValueError(f"{who}: parts={parts!r} outside 0 (automatic) .. 65535")
+    if keys is not None:
+        if not (isinstance(keys, torch.Tensor) and keys.dtype == torch.int64 and keys.dim() == 1 and 1 <= keys.shape[0] <= MAX_KEY_SEARCH_KEYS):
+            raise ValueError(f"{who}: keys must be an int64 tensor of 1..2^31-1 64-bit patterns")
+        keys = keys.contiguous()
+        k, first = keys.shape[0], 0
+        _dev_check(num, den, keys)
+    else:
+        k, first = int(count), int(key_first)
+        if not 1 <= k <= MAX_KEY_SEARCH_KEYS:
+            raise ValueError(f"{who}: count={count!r} keys outside 1..2^31-1")
+        if not 0 <= first < 2 ** 64:
+            raise ValueError(f"{who}: key_first {key_first!r} outside [0, 2^64)")
+        _dev_check(num, den)
+    for name, t in (("num", num), ("den", den)):
+        if _abs_sum(t) >= KEY_SEARCH_SUM_LIMIT:
+            raise ValueError(f"{who}: the sum of |{name}| is 2^62 or more: a masked sum could wrap")
+    lib = _lib.load()
+    frames = torch.zeros((2, h, w), dtype=torch.int64, device=num.device)
+    frames[0, 1:-1, 1:-1] = num
+    frames[1, 1:-1, 1:-1] = den
+    snum = torch.empty(k, dtype=torch.int64, device=num.device)
+    sden = torch.empty(k, dtype=torch.int64, device=num.device)
+    check(_launch("ws_key_search", {"bytes": float(16 * r * w + 16 * k), "keys": float(k)}, lambda: lib.wsu_ws_key_search(
+        frames[0].data_ptr(), frames[1].data_ptr(), r * w, keys.data_ptr() if keys is not None else None, first, 0 if keys is not None else 1,
+        k, thr, int(parts), snum.data_ptr(), sden.data_ptr(), _stream())), "wsu_ws_key_search")
+    return snum, sden
+
+
 def ols_moments(x_u8: torch.Tensor) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,45) int64: per image the exact sums of v_i * v_j, i <= j (row-major upper triangle), over the interior
     pixels, v = the eight neighbours in ring order (_RING) and the centre (wsu_ols_moments, K24; ws_unet_amd.ols unpacks and solves)."""
