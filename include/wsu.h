@@ -491,6 +491,19 @@ int wsu_spa_tables(const uint8_t* x_u8, unsigned long long* tables, int n, int h
  *      then the same four on the plane with every LSB flipped (G ^ 1 element-wise in the place of G).  Exact integers. */
 int wsu_rs_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
 
+/* ---- K36: the co-occurrence counts of the subtractive pixel adjacency matrix (SPAM; Pevny, Bas, Fridrich, IEEE TIFS 5(2), 2010; not part
+ *      of the reference).  x_u8: (N,H,W) DEVICE pixels, any H, W >= 1.  order in {1,2}; T in 1..8 at order 1, 1..4 at order 2; B = 2T + 1.
+ *      A direction is a step (dr,dc); the four counted ones, in this index order: 0 (0,+1), 1 (+1,0), 2 (+1,+1), 3 (+1,-1).  In integers
+ *        D_k(r,c) = clip(x[r + k dr][c + k dc] - x[r + (k+1) dr][c + (k+1) dc], -T, T),   k = 0 .. order
+ *      (a difference beyond +-T is clipped into the border bins, not dropped).  A position (r,c) counts for a direction when all order + 2
+ *      pixels x[r + k dr][c + k dc], k = 0 .. order + 1, lie in the image; it adds 1 to bin sum_k (D_k + T) B^(order - k) (D_0 is the most
+ *      significant digit).  counts: DEVICE (N, 4, B^(order+1)) uint64, zeroed on the stream by this call.  An image too small for a direction
+ *      has zero counts there; otherwise counts[i][d] sums to H (W - order - 1), (H - order - 1) W and, for both diagonals,
+ *      (H - order - 1)(W - order - 1).  The counts of the opposite step are C_opp[d_0, .., d_order] = C[-d_order, .., -d_0] (the same runs
+ *      walked backwards), so they are not counted.  order 2, T 3: 343 bins per direction (SPAM-686); order 1, T 4: 81 (SPAM-162).  Exact
+ *      integers, the same bits on every run.  n in 1..65535; every argument is checked before any HIP call. */
+int wsu_spam_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, int order, int T, void* stream);
+
 /* ---- K12-K14: HILL-cost weighted prediction error (wMAE) of src/filters/evaluate.py:79-115 `get_filter_residuals_cover` and
  *      src/predictor_error.py:19-76 `attack`.  Both reference callers take HILL from a library (conseal.hill._costmap.compute_cost,
  *      stegolab2.hill.compute_rho); here both are the textbook cost, the one pinned by results/prediction/filters.csv:

@@ -1334,6 +1334,35 @@ def rs_counts(x_u8: torch.Tensor) -> torch.Tensor:
     return counts
 
 
+def spam_bins(order: int, T: int) -> int:
+    """B^(order+1), B = 2T + 1: the bins of one direction of the SPAM counts; the (order, T) that K36 takes, else ValueError."""
+    if order not in (1, 2) or isinstance(T, bool) or int(T) != T or not 1 <= T <= (8 if order == 1 else 4):
+        raise ValueError(f"spam: order={order!r} T={T!r}: order must be 1 (T in 1..8) or 2 (T in 1..4)")
+    return (2 * int(T) + 1) ** (order + 1)
+
+
+def spam_counts(x_u8: torch.Tensor, order: int = 2, T: int = 3, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,4,B^(order+1)) int64, B = 2T + 1: per image and direction (right, down, down-right, down-left) the counts of
+    the runs of order + 1 clipped differences clip(x[p + k s] - x[p + (k+1) s], -T, T), k = 0..order, along the step s, over every position
+    whose order + 2 pixels lie in the image; bin = the differences + T as base-B digits, the first one most significant (wsu_spam_counts,
+    K36; ws_unet_amd.spam makes the features).  The defaults are SPAM-686.  `out`: an int64 tensor of that shape to write into (the call
+    zeroes it)."""
+    lib = _lib.load()
+    bins = spam_bins(order, T)
+    n, h, w = _u8_planes(x_u8)
+    if n == 0:
+        raise ValueError("spam_counts: no images")
+    if out is None:
+        out = torch.empty((n, 4, bins), dtype=torch.int64, device=x_u8.device)
+    else:
+        _dev_check(out)
+        if out.dtype != torch.int64 or tuple(out.shape) != (n, 4, bins) or out.device != x_u8.device:
+            raise ValueError(f"spam_counts: out must be an int64 tensor of shape {(n, 4, bins)} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
+    check(_launch("spam_counts", {"bytes": float(n * h * w)}, lambda: lib.wsu_spam_counts(
+        x_u8.data_ptr(), out.data_ptr(), n, h, w, int(order), int(T), _stream())), "wsu_spam_counts")
+    return out
+
+
 # IJG luminance base table (the JPEG standard's Annex K.1), row-major by frequency [u][v]
 _IJG_LUMINANCE = np.array([
     [16, 11, 10, 16, 24, 40, 51, 61], [12, 12, 14, 19, 26, 58, 60, 55], [14, 13, 16, 24, 40, 57, 69, 56], [14, 17, 22, 29, 51, 87, 80, 62],
