@@ -663,6 +663,32 @@ int wsu_lsbr_key_mask(uint64_t key_seed, uint64_t alpha_threshold, uint8_t* mask
 int wsu_embed_threshold_lsbr(const uint8_t* cover, const double* key, const uint64_t* bits, const uint64_t* seeds, uint8_t* stego,
                              long long* changes, int n, int h, int w, void* stream);
 
+/* ---- K37-K39: the +-1 embedding simulators LSBM and HILL (LSB matching: Sharp, IH 2001; the payload-limited sender: Filler & Fridrich, IEEE TIFS
+ *      5(4), 2010; not part of the reference).  Planes, limits, aliasing, seeds, the generator word of pixel i and `changes` as in K23.  For a
+ *      multiplier lambda > 0 and a cost rho > 0 (+inf: a wet pixel), in float64 with one rounding per operation:
+ *        a = lambda * rho;   a+ = +inf where x == 255, else a;   a- = +inf where x == 0, else a;   e+- = exp(-a+-), exp(-inf) = 0;
+ *        Z = (1 + e+) + e-;   p+- = e+- / Z:  the probabilities of the changes +1 and -1, never out of 0..255.
+ *
+ * K37: entropy[i][l] = the sum over image i's pixels of h = log2(Z) + (t+ + t-) / (Z ln 2), t+- = a e+- where e+- > 0 else 0, at
+ *      lambda = lambdas[i][l]: the bits a sender with these change probabilities embeds.  One pass over rho serves all l multipliers,
+ *      1 <= l <= 16.  x_u8: (N,H,W); rho: DEVICE float64 (N,H,W); lambdas: DEVICE float64 [N][l]; entropy: DEVICE float64 [N][l].  Sums
+ *      are taken in a fixed order (no float atomics): two calls give the same bits, whatever the batch.  workspace: DEVICE, 8-byte aligned,
+ *      wsu_ternary_entropy_workspace_bytes(n) (0 for n <= 0), written before it is read by every call. */
+size_t wsu_ternary_entropy_workspace_bytes(int n);
+int wsu_ternary_entropy(const uint8_t* x_u8, const double* rho, const double* lambdas, int l, double* entropy, void* workspace,
+                        size_t workspace_bytes, int n, int h, int w, void* stream);
+/* K38: HILL when rho is K20's cost: with T+- = floor(p+- * 2^32) at lambda = lambdas[image] (DEVICE float64 [N]; +inf leaves the cover) and
+ *      u the generator word of pixel i, stego = cover + 1 where u < T+, cover - 1 where T+ <= u < T+ + T-, else cover. */
+int wsu_embed_ternary(const uint8_t* cover, const double* rho, const double* lambdas, const uint64_t* seeds, uint8_t* stego,
+                      long long* changes, int n, int h, int w, void* stream);
+/* K39: LSBM, the same draw with constant thresholds: T+ = T- = T = thresholds[image] inside the range, (2T, 0) at x == 0 and (0, 2T) at
+ *      x == 255, so a fraction alpha / 2 of the pixels changes by +-1 with a random sign, inwards at the ends of the range.  thresholds:
+ *      DEVICE uint32 [N], each from wsu_lsbm_threshold (HOST: *threshold = floor(alpha / 4 * 2^32) in float64, alpha in [0, 1]; 0 copies
+ *      the cover). */
+int wsu_lsbm_threshold(double alpha, uint32_t* threshold);
+int wsu_embed_lsbm(const uint8_t* cover, const uint64_t* seeds, const uint32_t* thresholds, uint8_t* stego, long long* changes,
+                   int n, int h, int w, void* stream);
+
 /* ---- K31, K32: the JPEG history of a bitmap (Boehme, "Weighted stego-image steganalysis for JPEG covers", IH 2008; not part of the
  *      reference): which quantisation table an image was compressed with, and the image after a round trip through a table -- the WS
  *      predictor for covers that were a JPEG once (the quantiser rounds the +-1 embedding noise away).  All arithmetic is exact integers:

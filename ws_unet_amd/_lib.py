@@ -133,6 +133,11 @@ SIGNATURES = {
     "wsu_embed_lsbr_keyed": (c_int, [_P, _P, c_uint64, c_uint64, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_embed_threshold_lsbr": (c_int, [_P] * 6 + [c_int, c_int, c_int, _P]),
     "wsu_lsbr_key_mask": (c_int, [c_uint64, c_uint64, _P, c_int, c_int, _P]),
+    "wsu_ternary_entropy_workspace_bytes": (c_size_t, [c_int]),
+    "wsu_ternary_entropy": (c_int, [_P, _P, _P, c_int, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_embed_ternary": (c_int, [_P] * 6 + [c_int, c_int, c_int, _P]),
+    "wsu_lsbm_threshold": (c_int, [c_double, _P]),
+    "wsu_embed_lsbm": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_jpeg_energies": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, _P]),
     "wsu_jpeg_predict": (c_int, [_P] * 5 + [c_int] * 3 + [_P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),

@@ -173,34 +173,7 @@ __global__ __launch_bounds__(256) void rank_select_pick_kernel(void* __restrict_
 }
 
 // ---- K22 / K23: the pixel loops -----------------------------------------------------------------------------------------------
-// An image's pixels as `head` leading bytes, `groups` 16-byte groups whose loads and stores are aligned, and trailing bytes; `bytes` =
-// head + tail.  Input and output must share their alignment, else every pixel is a byte; quad: a group must start at a multiple of 4
-// pixels (K23: one generator call serves pixels 4g .. 4g+3).
-struct Span { long long head, groups, bytes; };
-__device__ __forceinline__ Span image_span(const uint8_t* in, const uint8_t* out, long long hw, bool quad) {
-    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-    long long head = hw;
-    if (((a ^ b) & 15) == 0) {
-        const long long hd = (long long)((16 - (a & 15)) & 15);
-        if (hd <= hw && (!quad || hd % 4 == 0)) head = hd;
-    }
-    const long long groups = (hw - head) / 16;
-    return Span{head, groups, hw - 16 * groups};
-}
-__device__ __forceinline__ long long span_byte_index(const Span& sp, long long j) { return j < sp.head ? j : j + 16 * sp.groups; }
-
-// this thread's count -> one integer atomic per workgroup (wave reduction, then the four wave sums)
-__device__ __forceinline__ void add_changes(int cnt, long long* __restrict__ dst, int tid) {
-    __shared__ int wsum[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((tid & 63) == 0) wsum[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (total) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)total);
-    }
-}
+// (image_span, span_byte_index and add_changes: wsu_metric.h, shared with the +-1 simulators of ternary.hip.)
 
 // K22.  A wave takes 1024 consecutive pixels at a time: lane l owns pixels 16 l .. 16 l + 15 (one 16-byte load and store), the keys are
 // read 64 consecutive ones per step (lane l: key 64 j + l) and a ballot hands every lane the 16 decisions of its pixels.

@@ -1612,6 +1612,118 @@ def lsbr_key_mask(key_seed: int, alpha_threshold: int, h: int, w: int, device=No
     return mask
 
 
+# ---- the +-1 simulators (K37-K39) ---------------------------------------------------------------------------------------------------
+
+TERNARY_MAX_LAMBDAS = 16                                            # multipliers per wsu_ternary_entropy launch
+# ternary_lambda: 2^-50, 2^-45, .., 2^25, then 8 times the 16 inner points that cut the bracket into 17 geometric steps: 9 launches and
+# lam_hi / lam_lo = 2^(5 / 17^8) = 1 + 5.0e-10.  HILL's costs lie between 9 / (9 * 16 * 255) = 2.5e-4 and the clamp 1e10: at 2^-50 every a
+# is below 1e-5 (h is log2 3, or 1 at a wet end, to 11 digits) and at 2^25 every a exceeds 8000 (exp underflows: h = 0).
+TERNARY_LADDER = tuple(2.0 ** e for e in range(-50, 26, 5))
+TERNARY_REFINEMENTS = 8
+
+
+def _ternary_planes(who: str, x_u8: torch.Tensor, rho: torch.Tensor) -> Tuple[int, int, int]:
+    n, h, w = _u8_planes(x_u8)
+    _dev_check(rho)
+    if rho.dtype != torch.float64 or rho.shape != x_u8.shape:
+        raise ValueError(f"{who}: rho must be float64 of shape {tuple(x_u8.shape)}, got {tuple(rho.shape)} {rho.dtype}")
+    return n, h, w
+
+
+def ternary_entropy(x_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor) -> torch.Tensor:
+    """The bits a +-1 sender with change probabilities exp(-lambda rho) / Z embeds (K37).  x_u8: (N,H,W) uint8; rho: (N,H,W) float64,
+    positive, +inf = wet; lambdas: (N,L) float64, positive, 1 <= L <= 16 -> (N,L) float64.  The +1 change is wet at 255, the -1 change at
+    0.  Same bits on every call and in every batch."""
+    lib = _lib.load()
+    n, h, w = _ternary_planes("ternary_entropy", x_u8, rho)
+    _dev_check(lambdas)
+    if lambdas.dtype != torch.float64 or lambdas.dim() != 2 or lambdas.shape[0] != n or not 1 <= lambdas.shape[1] <= TERNARY_MAX_LAMBDAS:
+        raise ValueError(f"ternary_entropy: lambdas must be float64 of shape ({n}, 1..{TERNARY_MAX_LAMBDAS}), got {tuple(lambdas.shape)} {lambdas.dtype}")
+    nl = lambdas.shape[1]
+    out = torch.empty((n, nl), dtype=torch.float64, device=x_u8.device)
+    ws = torch.empty(lib.wsu_ternary_entropy_workspace_bytes(n) // 8, dtype=torch.float64, device=x_u8.device)
+    check(_launch("ternary_entropy", {"bytes": float(n * h * w * 9)}, lambda: lib.wsu_ternary_entropy(
+        x_u8.data_ptr(), rho.data_ptr(), lambdas.data_ptr(), nl, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())),
+        "wsu_ternary_entropy")
+    return out
+
+
+def _last_true(flags: torch.Tensor) -> torch.Tensor:
+    """(N,K) bool -> (N,1) int64: the largest index that holds True (0 where none does)."""
+    idx = torch.arange(flags.shape[1], device=flags.device)
+    return (flags.to(torch.int64) * idx).amax(dim=1, keepdim=True)
+
+
+def ternary_lambda(x_u8: torch.Tensor, rho: torch.Tensor, message_bits: torch.Tensor):
+    """The multiplier at which ternary_entropy equals the payload, per image: (lam_lo, lam_hi, ok), all (N) on the device, with
+    H(lam_lo) >= message_bits >= H(lam_hi) and lam_hi / lam_lo - 1 <= 2^-29; embed with lam_lo, whose capacity is not short.  message_bits:
+    (N) float64 on the device, not negative.  ok[i] is False where even the lowest multiplier of TERNARY_LADDER carries less than the
+    payload (lam_lo = lam_hi = that multiplier then).  Where the highest still carries it (a payload of 0) lam_lo = lam_hi = the highest.
+    Nine K37 launches; the bracket is chosen between them on the device, nothing waits for the GPU."""
+    n, h, w = _ternary_planes("ternary_lambda", x_u8, rho)
+    _dev_check(message_bits)
+    if message_bits.dtype != torch.float64 or message_bits.shape != (n,):
+        raise ValueError(f"ternary_lambda: message_bits must be float64 of shape ({n},), got {tuple(message_bits.shape)} {message_bits.dtype}")
+    dev = x_u8.device
+    m = message_bits[:, None]
+    ladder = torch.tensor(TERNARY_LADDER, dtype=torch.float64, device=dev).expand(n, -1).contiguous()
+    ge = ternary_entropy(x_u8, rho, ladder) >= m
+    ok = ge[:, 0].clone()
+    k = _last_true(ge)
+    lo = ladder.gather(1, k)
+    hi = ladder.gather(1, (k + 1).clamp_max(ladder.shape[1] - 1))
+    hi = torch.where(ok[:, None], hi, lo)
+    steps = torch.arange(1, TERNARY_MAX_LAMBDAS + 1, dtype=torch.float64, device=dev) / (TERNARY_MAX_LAMBDAS + 1)
+    true, false = torch.ones((n, 1), dtype=torch.bool, device=dev), torch.zeros((n, 1), dtype=torch.bool, device=dev)
+    for _ in range(TERNARY_REFINEMENTS):
+        inner = torch.minimum(torch.maximum(lo * torch.exp2(torch.log2(hi / lo) * steps), lo), hi)
+        ge = ternary_entropy(x_u8, rho, inner.contiguous()) >= m
+        points = torch.cat([lo, inner, hi], dim=1)
+        k = _last_true(torch.cat([true, ge, false], dim=1))
+        lo, hi = points.gather(1, k), points.gather(1, k + 1)
+    return lo[:, 0], hi[:, 0], ok
+
+
+def embed_ternary(cover_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor, seeds: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The +-1 sender's draw (K38): pixel i becomes x + 1 with probability exp(-lambda rho) / Z, x - 1 with the same (never out of 0..255:
+    that direction is wet), from the generator word embed_lsbr gives it.  rho: (N,H,W) float64; lambdas: (N) float64, positive (+inf: the
+    cover); seeds: (N) int64 holding the 64-bit seeds -> (stego (N,H,W) uint8, changes (N) int64)."""
+    lib = _lib.load()
+    n, h, w = _ternary_planes("embed_ternary", cover_u8, rho)
+    _dev_check(lambdas, seeds)
+    assert lambdas.dtype == torch.float64 and lambdas.shape == (n,) and seeds.dtype == torch.int64 and seeds.shape == (n,)
+    stego = torch.empty_like(cover_u8)
+    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
+    check(_launch("embed_ternary", {"bytes": float(n * h * w * 10)}, lambda: lib.wsu_embed_ternary(
+        cover_u8.data_ptr(), rho.data_ptr(), lambdas.data_ptr(), seeds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())),
+        "wsu_embed_ternary")
+    return stego, changes
+
+
+def lsbm_threshold(alpha: float) -> int:
+    """T = floor(alpha / 4 * 2^32) of wsu_embed_lsbm (a pixel goes up iff its generator word < T, down iff it is in [T, 2T)); alpha
+    outside [0, 1] raises."""
+    import ctypes
+    t = ctypes.c_uint32(0)
+    check(_lib.load().wsu_lsbm_threshold(float(alpha), ctypes.byref(t)), "wsu_lsbm_threshold")
+    return t.value
+
+
+def embed_lsbm(cover_u8: torch.Tensor, seeds: torch.Tensor, thresholds: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """LSB matching with Philox4x32-10 (K39): a fraction alpha / 2 of the pixels changes by +-1, the sign random, inwards at 0 and 255.
+    seeds: (N) int64 holding the images' 64-bit seeds; thresholds: (N) int32 holding the uint32 lsbm_threshold of each image's alpha ->
+    (stego (N,H,W) uint8, changes (N) int64)."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(cover_u8)
+    _dev_check(seeds, thresholds)
+    assert seeds.dtype == torch.int64 and seeds.shape == (n,) and thresholds.dtype == torch.int32 and thresholds.shape == (n,)
+    stego = torch.empty_like(cover_u8)
+    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
+    check(_launch("embed_lsbm", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbm(
+        cover_u8.data_ptr(), seeds.data_ptr(), thresholds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_lsbm")
+    return stego, changes
+
+
 def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, hat_scale: float = 255.,
                      quantile: float = 0.1, cost: Optional[torch.Tensor] = None, return_threshold: bool = False):
     """Per-image MAE and HILL-cost weighted MAE of a pixel prediction on the interior [1:-1,1:-1] (K12-K14).

@@ -37,7 +37,7 @@ import torch
 from . import fabrika
 
 NORMALISE = ("joint", "transition")
-SIMULATED = ("LSBR", "HILLR")                         # the stego methods `simulate=True` makes on the device
+SIMULATED = ("LSBR", "HILLR", "LSBM", "HILL")                       # the stego methods `simulate=True` makes on the device
 CSV_COLUMNS = ["name", "height", "width", "output", "prediction", "stego_method", "alpha"]
 
 
@@ -161,14 +161,17 @@ def _prefetch(fnames, kws):
 
 def _submit(fnames, clean, *, order, T, twin=None, prefetched=None):
     """Upload the chunk's Y planes once, make their twins when asked (twin = (method, alpha, stream)), queue K36; nothing waits for the GPU."""
-    from . import embed, ops
+    from . import embed, embed_pm1, ops
     from .planes import plane_groups, upload_planes
     counts = []
     for planes, names in plane_groups(fnames, prefetched):
         x = upload_planes(planes, "cuda")
         if twin is not None:
             method, alpha, stream = twin
-            x = embed.simulate(x, method, alpha, [embed.image_seed(f, stream) for f in names] if method != "HILLR" else None)[0]
+            if method in embed_pm1.METHODS:
+                x = embed_pm1.simulate(x, method, alpha, [embed.image_seed(f, stream) for f in names])[0]
+            else:
+                x = embed.simulate(x, method, alpha, [embed.image_seed(f, stream) for f in names] if method != "HILLR" else None)[0]
         counts.append(ops.spam_counts(x, order, T))
     return clean, counts
 
@@ -198,10 +201,11 @@ def extract(data_dir, stego_method: typing.Optional[str] = None, alpha: typing.O
     """(rows, F): the file rows (a frame with name, height, width, stego_method, alpha) and the (N, 2 B^(order+1)) float64 feature matrix of
     the covers of `data_dir` (stego_method None) or of one stego folder (stego_method, alpha), from the Y plane of every image, decoded a
     chunk ahead and uploaded a chunk at a time.  simulate=True makes the twins of the uploaded covers on the device instead of reading stego
-    files ('LSBR' with embed.image_seed(file, stream), 'HILLR'); their rows are named as embed.write_dataset would name the files.
+    files ('LSBR' with embed.image_seed(file, stream), 'HILLR'; 'LSBM' and 'HILL' of embed_pm1 with the same seeds); their rows are named as
+    embed.write_dataset / embed_pm1.write_dataset would name the files.
     Other keywords go to the fabrika iterators (take_num_images, shuffle_seed, ...)."""
     import pandas as pd
-    from . import embed
+    from . import embed, embed_pm1
     bins(order, T)
     if normalise not in NORMALISE:
         raise ValueError(f"unknown normalise {normalise!r}; choose from {NORMALISE}")
@@ -212,10 +216,11 @@ def extract(data_dir, stego_method: typing.Optional[str] = None, alpha: typing.O
     if stego_method is None:
         res = covers(data_dir, **shared)
     elif simulate:
-        method = embed.method_name(stego_method)
+        maker = embed_pm1 if str(stego_method).upper() in embed_pm1.METHODS else embed
+        method = maker.method_name(stego_method)
         if method not in SIMULATED:
             raise ValueError(f"simulate=True makes {' / '.join(SIMULATED)} twins only, not {stego_method!r}")
-        folder = embed.folder_name(method, alpha)
+        folder = maker.folder_name(method, alpha)
         res = [{**r, "name": f"{folder}/{pathlib.Path(r['name']).stem}.png", "stego_method": method, "alpha": float(alpha)}
                for r in covers(data_dir, twin=(method, float(alpha), int(stream)), **shared)]
     else:
