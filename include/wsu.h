@@ -367,8 +367,11 @@ int wsu_ws_residual_stats(const uint8_t* x_u8, const float* y01, float* beta_hat
  *                             x_hat = convolve(x/255, K, 'valid')*255 evaluated inside the kernel.
  *      mean_filter (HOST, 9 floats, same layout; NAMED_FILTERS['AVG'] by default, estimate.py:60,93-95) feeds the local
  *      variance for weighted = 1 (1/(5+var)) or -1 (5+var); weighted = 0 -> uniform weights (:97-110).
- *      correct_bias (:126-128) needs x_bias = pixel_estimator(x_bar - x) in x_hat's layout (not with pixel_filter).
- *      beta_hat: (N) fp32, clipped at 0 (:121); sums: optional (N,3) fp64 {sum w, sum w*s*(x-x_hat), sum w*s*x_bias}. */
+ *      correct_bias (:126-128) needs x_bias = pixel_estimator(x_bar - x) in x_hat's layout; with pixel_filter the kernel applies the
+ *      filter to (x_bar - x)/255 itself and x_bias is not read.
+ *      beta_hat: (N) fp32, clipped at 0 (:121) before the bias correction; NaN stays NaN, as np.clip: a NaN in an interior prediction
+ *      (or, with correct_bias, in x_bias) gives a NaN estimate, not 0.  sums: optional (N,3) fp64 {sum w, sum w*s*(x-x_hat),
+ *      sum w*s*x_bias}. */
 size_t wsu_ws_attack_workspace_bytes(int n);
 int wsu_ws_attack(const uint8_t* x_u8, const float* x_hat, const float* x_bias, const float* pixel_filter, const float* mean_filter,
                   int hat_full, float hat_scale, int weighted, int correct_bias, float* beta_hat, double* sums,

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64) void ws_attack_finish_kernel(const double* __re
     if (tid == 0) {
         const double sw = red[0][0], sb = red[1][0], sc = red[2][0];
         double beta = sb / sw;
-        beta = beta > 0.0 ? beta : 0.0;                                               // np.clip(beta_hat, 0, None)
+        beta = beta < 0.0 ? 0.0 : beta;                                               // np.clip(beta_hat, 0, None): NaN stays NaN
         if (correct_bias) beta -= beta * (sc / sw);
         beta_hat[nn] = (float)beta;
         if (sums) { sums[nn * 3 + 0] = sw; sums[nn * 3 + 1] = sb; sums[nn * 3 + 2] = sc; }

@@ -122,8 +122,9 @@ class JPEGEstimator:
 
 
 def without_estimate(beta: torch.Tensor, x_hat: torch.Tensor) -> torch.Tensor:
-    """beta (N,) with NaN where image i's plane of x_hat (N,H,W) is the NaN plane of fallback=None.  The statistics themselves do not
-    carry the NaN through: K11 clips its quotient at 0 with a comparison, which a NaN fails, and K27 / K29 skip NaN terms."""
+    """beta (N,) with NaN where image i's plane of x_hat (N,H,W) is the NaN plane of fallback=None.  K11 carries a NaN of its prediction
+    into its estimate itself (its clip at 0 keeps NaN, as np.clip does), so for placement='random' this changes nothing; the changepoint
+    statistics K27 / K33 and the accumulator K29 skip NaN terms and would report a number for such a plane, so the function stays."""
     return torch.where(torch.isnan(x_hat[:, 0, 0]), torch.full_like(beta, float("nan")), beta)
 
 
