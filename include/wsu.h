@@ -692,6 +692,38 @@ int wsu_lsbm_threshold(double alpha, uint32_t* threshold);
 int wsu_embed_lsbm(const uint8_t* cover, const uint64_t* seeds, const uint32_t* thresholds, uint8_t* stego, long long* changes,
                    int n, int h, int w, void* stream);
 
+/* ---- K40-K42: binary syndrome-trellis codes (Filler, Judas, Fridrich, IEEE TIFS 6(3), 2011; not part of the reference): a message that is
+ *      really carried, embedded with near-minimal additive cost and read back.  Planes, limits and seeds as in K23, but H * W < 2^31.
+ *      Per image, over the LSBs x[0..n) along a pixel path (n = H * W), costs rho[0..n) >= 0 (+inf: wet, NaN: not allowed), a message
+ *      m[0..k) of bytes 0 / 1, 1 <= k <= n, a constraint height 1 <= height <= 10, S = 2^height states and a column table
+ *      cols[0..ceil(n / k)) of height-bit integers:
+ *        block i owns the path positions [floor(i n / k), floor((i + 1) n / k));  its position t has the column
+ *        cols[t] & ((1 << min(height, k - i)) - 1), whose bit r reaches message bit i + r;
+ *        forward:  W[0] = 0, W[s > 0] = +inf;  per position j with column c:  a = W[s] + (x_j ? rho_j : 0),  b = W[s ^ c] + (x_j ? 0 : rho_j),
+ *                  take[j][s] = b < a (a tie keeps y_j = 0),  W[s] = take ? b : a;  after block i: W[s] = W[2 s + m_i] for s < S / 2, +inf above;
+ *        cost = W[0] after the last block: the least sum of rho_j over y_j != x_j among all y with syndrome m;  ok = cost < +inf;
+ *        backward: s = 0;  for i = k - 1 .. 0:  s = 2 s + m_i, then down the block's positions  y_j = take[j][s],  s ^= c_j where y_j is set;
+ *        extract:  m_b = XOR of y_j over the blocks i in (b - height, b] and their positions t whose column has bit b - i set.
+ *      Only float64 additions and comparisons touch a cost: the results are bit for bit those of a numpy restatement.
+ *      path: DEVICE int32 [N][n], per image a permutation of the raster indices (position -> pixel), or NULL for raster order; an entry
+ *      outside [0, n) is never dereferenced (the position counts as wet and its pixel is not written).  cols: DEVICE uint32.
+ *
+ * K40: words[i][p] = the generator word of pixel p under seeds[i] (word p % 4 of Philox4x32-10 on counter (p / 4, 0, 0, 0), K23's): the
+ *      sort key of the keyed path and the sign bit of K41's +-1 change.  words: DEVICE uint32 (N,H,W); H * W < 2^32. */
+int wsu_philox_words(const uint64_t* seeds, uint32_t* words, int n, int h, int w, void* stream);
+/* K41: phases 1: forward (writes cost, ok and the workspace), 2: backward (reads them, writes stego and changes), 3: both.  Where y_j differs
+ *      from the cover's LSB the pixel becomes x ^ 1 (change 0) or x + d, d = +1 / -1 as bit 0 of its generator word is 1 / 0, inwards at 0
+ *      and 255 (change 1); every other pixel, and every pixel of an image that is not ok, is copied.  cost: DEVICE float64 [N]; changes:
+ *      DEVICE int64 [N]; ok: DEVICE uint8 [N]; stego may alias cover.  workspace: DEVICE, 8-byte aligned, n * wsu_stc_workspace_bytes(H * W,
+ *      height) bytes (pixels * max(2^height, 64) / 8 each: the take bits; 0 for bad arguments), written by phase 1 before phase 2 reads it. */
+size_t wsu_stc_workspace_bytes(long long pixels, int height);
+int wsu_stc_embed(const uint8_t* cover, const double* rho, const uint8_t* message, const uint32_t* cols, const int32_t* path,
+                  const uint64_t* seeds, int change, int height, int k, int phases, uint8_t* stego, double* cost, long long* changes,
+                  uint8_t* ok, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
+/* K42: message[i][b] = m_b of stego image i, one thread per message bit.  message: DEVICE uint8 [N][k]. */
+int wsu_stc_extract(const uint8_t* stego, const uint32_t* cols, const int32_t* path, int height, int k, uint8_t* message, int n, int h,
+                    int w, void* stream);
+
 /* ---- K31, K32: the JPEG history of a bitmap (Boehme, "Weighted stego-image steganalysis for JPEG covers", IH 2008; not part of the
  *      reference): which quantisation table an image was compressed with, and the image after a round trip through a table -- the WS
  *      predictor for covers that were a JPEG once (the quantiser rounds the +-1 embedding noise away).  All arithmetic is exact integers:

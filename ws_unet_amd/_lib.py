@@ -138,6 +138,10 @@ SIGNATURES = {
     "wsu_embed_ternary": (c_int, [_P] * 6 + [c_int, c_int, c_int, _P]),
     "wsu_lsbm_threshold": (c_int, [c_double, _P]),
     "wsu_embed_lsbm": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "wsu_philox_words": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "wsu_stc_workspace_bytes": (c_size_t, [c_longlong, c_int]),
+    "wsu_stc_embed": (c_int, [_P] * 6 + [c_int] * 4 + [_P] * 5 + [c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_stc_extract": (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, _P]),
     "wsu_jpeg_energies": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, _P]),
     "wsu_jpeg_predict": (c_int, [_P] * 5 + [c_int] * 3 + [_P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),

@@ -1724,6 +1724,119 @@ def embed_lsbm(cover_u8: torch.Tensor, seeds: torch.Tensor, thresholds: torch.Te
     return stego, changes
 
 
+# ---- syndrome-trellis codes (K40-K42) ----------------------------------------------------------------------------------------------
+
+STC_MAX_H = 10                                                      # constraint heights 1..10: up to 1024 states, one thread each
+STC_CHANGES = ("flip", "pm1")
+# stc_embed's take bits need pixels * max(2^h, 64) / 8 bytes per image (32 MiB at 512 x 512, h = 10); a batch is embedded in slices whose
+# workspace stays under this many bytes (at least one image per slice).  8 GiB: 256 such images, one workgroup for each compute unit
+STC_WORKSPACE_CAP = 8 << 30
+
+
+def philox_words(seeds: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """The generator word embed_lsbr gives every pixel (K40): seeds: (N) int64 holding the images' 64-bit seeds -> (N,H,W) int32 holding
+    the uint32 words."""
+    lib = _lib.load()
+    _dev_check(seeds)
+    h, w = int(h), int(w)
+    if seeds.dtype != torch.int64 or seeds.dim() != 1 or h < 1 or w < 1:
+        raise ValueError(f"philox_words: (N) int64 seeds and a shape expected, got {tuple(seeds.shape)} {seeds.dtype}, {h} x {w}")
+    n = seeds.shape[0]
+    words = torch.empty((n, h, w), dtype=torch.int32, device=seeds.device)
+    check(_launch("philox_words", {"bytes": float(n * h * w * 4)}, lambda: lib.wsu_philox_words(
+        seeds.data_ptr(), words.data_ptr(), n, h, w, _stream())), "wsu_philox_words")
+    return words
+
+
+def _stc_code(who: str, n: int, hw: int, h, k, cols: torch.Tensor, path: Optional[torch.Tensor]) -> Tuple[int, int]:
+    h, k = int(h), int(k)
+    if not 1 <= h <= STC_MAX_H:
+        raise ValueError(f"{who}: constraint height h={h} outside 1..{STC_MAX_H}")
+    if not 1 <= k <= hw:
+        raise ValueError(f"{who}: k={k} message bits outside 1..{hw} (the pixels of an image)")
+    _dev_check(cols, path)
+    wmax = -(-hw // k)
+    if cols.dtype != torch.int32 or cols.dim() != 1 or cols.shape[0] < wmax:
+        raise ValueError(f"{who}: cols must be int32 with at least ceil(n / k) = {wmax} entries, got {tuple(cols.shape)} {cols.dtype}")
+    if path is not None and (path.dtype != torch.int32 or path.shape != (n, hw)):
+        raise ValueError(f"{who}: path must be int32 of shape ({n}, {hw}), got {tuple(path.shape)} {path.dtype}")
+    return h, k
+
+
+def stc_workspace_bytes(pixels: int, h: int) -> int:
+    """Bytes of take bits stc_embed needs per image of `pixels` pixels at constraint height h (wsu_stc_workspace_bytes)."""
+    b = _lib.load().wsu_stc_workspace_bytes(int(pixels), int(h))
+    if b == 0:
+        raise ValueError(f"stc_workspace_bytes: pixels={pixels}, h={h}: a positive pixel count and h in 1..{STC_MAX_H} expected")
+    return b
+
+
+def stc_embed(cover_u8: torch.Tensor, rho: torch.Tensor, message: torch.Tensor, cols: torch.Tensor, seeds: torch.Tensor, *, h: int = 10,
+              path: Optional[torch.Tensor] = None, change: str = "flip", workspace_cap: Optional[int] = None, phases: int = 3,
+              workspace: Optional[torch.Tensor] = None):
+    """Embeds a message with a binary syndrome-trellis code (K41): the Viterbi pass over 2^h states per pixel and the walk back.  cover_u8:
+    (N,H,W) uint8; rho: (N,H,W) float64 costs, >= 0, +inf = wet; message: (N,k) uint8 of 0 / 1, 1 <= k <= H W; cols: int32 column table
+    with at least ceil(H W / k) entries (stc.columns); seeds: (N) int64 holding the 64-bit seeds (they choose the sign of a 'pm1' change);
+    path: (N, H W) int32, per image a permutation of the raster indices, or None for raster order; change: 'flip' (x ^ 1) or 'pm1' (x +- 1,
+    inwards at 0 and 255) where the coded LSB differs from the cover's -> (stego (N,H,W) uint8, cost (N) float64, changes (N) int64, ok (N)
+    uint8).  cost is the least total cost of a stego with this syndrome; where it is +inf (too many wet pixels) ok is 0 and the stego is
+    the cover.  Bit for bit a numpy restatement.  The batch is cut into slices whose take bits fit `workspace_cap` bytes
+    (STC_WORKSPACE_CAP by default; a slice holds at least one image).  phases=1 runs only the forward pass: cost and ok are final, stego
+    and changes are not written, and the take bits stay in the caller's `workspace` (uint8, N * stc_workspace_bytes(H W, h) bytes, which
+    also turns the slicing off) for a later walk back through the C entry (phases 2 there reads cost and ok as arguments)."""
+    lib = _lib.load()
+    n, hh, ww = _ternary_planes("stc_embed", cover_u8, rho)
+    hw = hh * ww
+    if not (isinstance(message, torch.Tensor) and message.dtype == torch.uint8 and message.dim() == 2 and message.shape[0] == n):
+        raise ValueError(f"stc_embed: message must be an ({n}, k) uint8 tensor of 0 / 1")
+    h, k = _stc_code("stc_embed", n, hw, h, message.shape[1], cols, path)
+    _dev_check(message, seeds)
+    if seeds.dtype != torch.int64 or seeds.shape != (n,):
+        raise ValueError(f"stc_embed: seeds must be int64 of shape ({n},), got {tuple(seeds.shape)} {seeds.dtype}")
+    if change not in STC_CHANGES:
+        raise ValueError(f"stc_embed: change {change!r} is not one of {' / '.join(STC_CHANGES)}")
+    if phases not in (1, 3) or (phases == 1 and workspace is None):
+        raise ValueError("stc_embed: phases is 1 (forward only, into the caller's workspace) or 3 (both)")
+    per = stc_workspace_bytes(hw, h)
+    cap = STC_WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
+    if cap < 1:
+        raise ValueError(f"stc_embed: workspace_cap={workspace_cap!r} is not a positive byte count")
+    dev = cover_u8.device
+    if workspace is not None:
+        _dev_check(workspace)
+        if workspace.dtype != torch.uint8 or workspace.numel() < n * per:
+            raise ValueError(f"stc_embed: workspace must be uint8 with at least {n * per} bytes")
+        step, ws = n, workspace
+    else:
+        step = max(1, min(n, cap // per))
+        ws = torch.empty(step * per, dtype=torch.uint8, device=dev)
+    stego = torch.empty_like(cover_u8)
+    cost = torch.empty(n, dtype=torch.float64, device=dev)
+    changes = torch.zeros(n, dtype=torch.int64, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    cid = STC_CHANGES.index(change)
+    for a in range(0, n, step):
+        b = min(n, a + step)
+        p = path[a:b].data_ptr() if path is not None else None
+        check(_launch("stc_embed", {"bytes": float((b - a) * (hw * 14 + 2 * per))}, lambda: lib.wsu_stc_embed(
+            cover_u8[a:b].data_ptr(), rho[a:b].data_ptr(), message[a:b].data_ptr(), cols.data_ptr(), p, seeds[a:b].data_ptr(), cid, h, k,
+            phases, stego[a:b].data_ptr(), cost[a:b].data_ptr(), changes[a:b].data_ptr(), ok[a:b].data_ptr(), ws.data_ptr(), ws.numel(),
+            b - a, hh, ww, _stream())), "wsu_stc_embed")
+    return stego, cost, changes, ok
+
+
+def stc_extract(stego_u8: torch.Tensor, cols: torch.Tensor, k: int, *, h: int = 10, path: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Reads the k message bits a syndrome-trellis code left in the LSBs (K42): stego_u8: (N,H,W) uint8; cols, h, path as stc_embed was
+    given them -> (N,k) uint8 of 0 / 1."""
+    lib = _lib.load()
+    n, hh, ww = _u8_planes(stego_u8)
+    h, k = _stc_code("stc_extract", n, hh * ww, h, k, cols, path)
+    message = torch.empty((n, k), dtype=torch.uint8, device=stego_u8.device)
+    check(_launch("stc_extract", {"bytes": float(n * hh * ww * 5)}, lambda: lib.wsu_stc_extract(
+        stego_u8.data_ptr(), cols.data_ptr(), _ptr(path), h, k, message.data_ptr(), n, hh, ww, _stream())), "wsu_stc_extract")
+    return message
+
+
 def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, hat_scale: float = 255.,
                      quantile: float = 0.1, cost: Optional[torch.Tensor] = None, return_threshold: bool = False):
     """Per-image MAE and HILL-cost weighted MAE of a pixel prediction on the interior [1:-1,1:-1] (K12-K14).
