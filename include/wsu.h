@@ -723,6 +723,58 @@ int wsu_stc_embed(const uint8_t* cover, const double* rho, const uint8_t* messag
 /* K42: message[i][b] = m_b of stego image i, one thread per message bit.  message: DEVICE uint8 [N][k]. */
 int wsu_stc_extract(const uint8_t* stego, const uint32_t* cols, const int32_t* path, int height, int k, uint8_t* message, int n, int h,
                     int w, void* stream);
+/* K43, K44: K41 (both phases) and K42 with a message length per image, for messages of unequal length in one batch: image i embeds / reads
+ *      the ks[i] bits message[i * message_stride + first[i] ..].  ks, first: DEVICE int32 [N], 0 <= ks[i] <= H * W, first[i] >= 0,
+ *      first[i] + ks[i] <= max_bits <= message_stride (max_bits: HOST, the most bits of a row any image may touch).  cols: DEVICE uint32
+ *      [cols_len], cols_len >= ceil(H * W / ks[i]) for every positive ks[i].  ks[i] == 0: no block exists; K43 gives stego = cover, cost 0,
+ *      changes 0, ok 1, and K44 writes nothing for that image.  A workgroup reads its image's ks and first once at entry; what they hold
+ *      is only known on the device, so an image whose values break a condition above is treated as ks[i] = 0 and K43 reports cost +inf and
+ *      ok 0 for it (stego = cover): no access leaves the buffers on its account.  Everything else, and every bit of the results, as K41 /
+ *      K42 with k = ks[i]; wsu_stc_embed / wsu_stc_extract are these kernels with one k for all.
+ *      K44's `bit` (0..7) names the bit of the stego byte that is the code's bit (K42 reads bit 0); rows of `message` are written only in
+ *      [first[i], first[i] + ks[i]). */
+int wsu_stc_embed_ragged(const uint8_t* cover, const double* rho, const uint8_t* message, long long message_stride, const int32_t* ks,
+                         const int32_t* first, int max_bits, const uint32_t* cols, int cols_len, const int32_t* path, const uint64_t* seeds,
+                         int change, int height, uint8_t* stego, double* cost, long long* changes, uint8_t* ok, void* workspace,
+                         size_t workspace_bytes, int n, int h, int w, void* stream);
+int wsu_stc_extract_ragged(const uint8_t* stego, const uint32_t* cols, int cols_len, const int32_t* path, int height, int bit,
+                           const int32_t* ks, const int32_t* first, int max_bits, uint8_t* message, long long message_stride, int n, int h,
+                           int w, void* stream);
+
+/* ---- K45-K47: the planes of the ternary two-layer syndrome-trellis embedder (Filler, Judas, Fridrich 2011, sections V-VI, for +-1 changes; not
+ *      part of the reference; ws_unet_amd.stc_ml drives them).  Two binary codes (K43) run along one keyed path with one column table:
+ *      first over bit 1 of the pixels, then over bit 0.  Per image: cover x in 0..255, n = H * W pixels, one cost rho >= 0 per pixel for both
+ *      directions (+inf: wet), a message m[0..k), k >= 2, and the multiplier lambda of K37's search for k bits (its lower bracket end).
+ *      With K37's text unchanged:  a = lambda * rho;  a+ = +inf where x == 255, else a;  a- = +inf where x == 0, else a;  e+- = exp(-a+-);
+ *      Z = (1 + e+) + e-.   d = the direction that changes bit 1 of x: +1 for odd x, -1 for even x;  o = the other direction.
+ *        high layer:  cover bit u1 = (x >> 1) & 1;  cost rho1 = a_d + log1p(e_o)  (= ln((1 - q1) / q1) for q1 = e_d / Z without overflow or
+ *                     cancellation; +inf where a_d is);  H1 = the sum over the pixels of the binary entropy of q1 in bits, each term
+ *                     h1 = (r log1p(t)) / ln 2 - q1 log2(q1) where e_d > 0 and 0 elsewhere, r = (1 + e_o) / Z, t = e_d / (1 + e_o);
+ *                     k1 = min(floor(H1), k - 1);  k1 == 0: the layer is not run, y1 = u1;  else y1 = K43's solution for (u1, rho1, m[0..k1));
+ *        low layer:   k0 = k - k1 >= 1;  where y1 != u1 the pixel is decided (it becomes x + d): u0 = 1 - (x & 1), rho0 = +inf;  elsewhere
+ *                     u0 = x & 1, rho0 = a_o (the product lambda * rho itself, +inf at the range's end);  y0 = K43's solution for
+ *                     (u0, rho0, m[k1..k));
+ *        stego:       x + d where y1 != u1;  x + o where bit 1 was kept and y0 != (x & 1);  x otherwise.  Then (y >> 1) & 1 == y1 and
+ *                     y & 1 == y0, the stego stays in 0..255 and a wet pixel never changes.  ok = ok1 and ok0; an image that is not ok is
+ *                     copied.  The receiver reads m[0..k1) from bit 1 and m[k1..k) from bit 0 (K44), knowing (seed, H, W, height, k1, k0).
+ *      The first layer is sized by its entropy, the last takes the rest; no smaller payload is tried when a layer has no solution.
+ *      Planes (N,H,W), H * W < 2^31, N <= 65535; lambdas: DEVICE float64 [N]; k1: DEVICE int32 [N].  Sums are taken in K37's fixed order (no
+ *      float atomics): the same bits whatever the batch.  workspace: DEVICE, 8-byte aligned, wsu_stc_layer_workspace_bytes(n) bytes (0 for
+ *      n <= 0), written before it is read by every call.
+ *
+ * K45: u1 (DEVICE uint8 plane of 0 / 1), rho1 (DEVICE float64 plane) and entropy[i] = H1 of image i (DEVICE float64 [N]) in one pass. */
+size_t wsu_stc_layer_workspace_bytes(int n);
+int wsu_stc_layer_high(const uint8_t* x_u8, const double* rho, const double* lambdas, uint8_t* u1, double* rho1, double* entropy,
+                       void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
+/* K46: u0 and rho0 from bit 0 of the plane y1 (K43's output over u1); where k1[i] <= 0, y1 is not read. */
+int wsu_stc_layer_low(const uint8_t* x_u8, const double* rho, const double* lambdas, const uint8_t* y1, const int32_t* k1, uint8_t* u0,
+                      double* rho0, int n, int h, int w, void* stream);
+/* K47: the stego plane from bit 0 of y1 (ignored where k1[i] <= 0) and of y0;  ok[i] = ok1[i] and ok0[i] (DEVICE uint8 [N] each), else image i
+ *      is copied;  changes[i] (DEVICE int64) = its changed pixels, distortion[i] (DEVICE float64) = the sum of rho over them.  A pixel whose
+ *      planes ask for a step out of 0..255 (they cannot, when they are K43's over K45 / K46's costs) is not changed.  stego may alias cover. */
+int wsu_stc_layer_compose(const uint8_t* cover, const double* rho, const uint8_t* y1, const uint8_t* y0, const int32_t* k1,
+                          const uint8_t* ok1, const uint8_t* ok0, uint8_t* stego, long long* changes, double* distortion, uint8_t* ok,
+                          void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
 
 /* ---- K31, K32: the JPEG history of a bitmap (Boehme, "Weighted stego-image steganalysis for JPEG covers", IH 2008; not part of the
  *      reference): which quantisation table an image was compressed with, and the image after a round trip through a table -- the WS

@@ -28,7 +28,7 @@ def __getattr__(name):
     if name in _LAZY:
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(mod), attr)
-    if name in ("data", "evaluate", "planes", "unet_run", "per_image", "model", "fabrika", "ops", "formula", "losses", "metrics", "imread", "parallel", "trainer", "filters", "ws", "embed", "embed_pm1", "stc"):
+    if name in ("data", "evaluate", "planes", "unet_run", "per_image", "model", "fabrika", "ops", "formula", "losses", "metrics", "imread", "parallel", "trainer", "filters", "ws", "embed", "embed_pm1", "stc", "stc_ml"):
         return importlib.import_module(f"ws_unet_amd.{name}")
     raise AttributeError(name)
 

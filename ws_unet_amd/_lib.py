@@ -142,6 +142,13 @@ SIGNATURES = {
     "wsu_stc_workspace_bytes": (c_size_t, [c_longlong, c_int]),
     "wsu_stc_embed": (c_int, [_P] * 6 + [c_int] * 4 + [_P] * 5 + [c_size_t, c_int, c_int, c_int, _P]),
     "wsu_stc_extract": (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, _P]),
+    "wsu_stc_embed_ragged": (c_int, [_P, _P, _P, c_longlong, _P, _P, c_int, _P, c_int, _P, _P, c_int, c_int] + [_P] * 5
+                             + [c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_stc_extract_ragged": (c_int, [_P, _P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, c_longlong, c_int, c_int, c_int, _P]),
+    "wsu_stc_layer_workspace_bytes": (c_size_t, [c_int]),
+    "wsu_stc_layer_high": (c_int, [_P] * 7 + [c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_stc_layer_low": (c_int, [_P] * 7 + [c_int, c_int, c_int, _P]),
+    "wsu_stc_layer_compose": (c_int, [_P] * 12 + [c_size_t, c_int, c_int, c_int, _P]),
     "wsu_jpeg_energies": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, _P]),
     "wsu_jpeg_predict": (c_int, [_P] * 5 + [c_int] * 3 + [_P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),

@@ -1,4 +1,4 @@
-// K40-K42: binary syndrome-trellis codes (Filler, Judas, Fridrich, "Minimizing additive distortion in steganography using syndrome-trellis
+// K40-K44: binary syndrome-trellis codes (Filler, Judas, Fridrich, "Minimizing additive distortion in steganography using syndrome-trellis
 // codes", IEEE TIFS 6(3), 2011): a real message embedded with near-minimal cost and read back.  Not part of the reference.
 //
 //   the code, per image, over the LSBs x[0..n) along a pixel path, costs rho[0..n) >= 0 (+inf: wet), message m[0..k), constraint height
@@ -13,6 +13,12 @@
 //   K41  forward and backward; where y_j != x_j the pixel flips its LSB (change 0) or moves by d = +1 / -1 as bit 0 of its generator word
 //        is 1 / 0, inwards at 0 and 255 (change 1)
 //   K42  extract
+//   K43  K41 with a message length, a row stride and a first bit per image (ks, first: DEVICE int32 [N]); ks[i] == 0: no block exists, y = x,
+//        cost 0, ok 1.  An image whose (ks, first) is out of range (k < 0, k > n, first < 0, first + k > max_bits, ceil(n / k) > cols_len) is
+//        clamped to k = 0 and reported with cost +inf and ok 0: nothing is read or written out of bounds on its account.
+//   K44  K42 with the same per-image arguments and the code's bit within the stego byte; an image with k == 0 or out of range writes nothing
+//
+// K41 / K43 and K42 / K44 are the same kernels: a workgroup reads its image's (k, message row) once at entry (StcImage), uniform or ragged.
 //
 // Only float64 additions and comparisons touch a cost, so the bits are those of the numpy restatement whatever the schedule.
 //
@@ -22,7 +28,7 @@
 // position's x, rho, path and column are staged by the whole workgroup 1024 positions at a time; a wave then holds 64 positions in
 // registers and hands one to all its lanes per step as scalars.  take[j] is one ballot word per wave; lane p keeps position p's and the
 // wave stores its 64 words together.  The backward walk is a chain of dependent reads: the workgroup copies 256 positions' take words into LDS, thread 0 walks them there, then
-// 256 threads apply the changes.  Every loop's trip count is known at launch; nothing waits on a flag.
+// 256 threads apply the changes.  Every loop's trip count is known when the workgroup starts (it has read its image's k by then); nothing waits on a flag.
 #pragma clang fp contract(off)
 #include "wsu_metric.h"
 #include "wsu_philox.h"
@@ -54,6 +60,16 @@ __device__ __forceinline__ double lane_double(double v, int lane) {            /
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
 
+// what a workgroup knows of its image's code: the message length, the row its bits start at, and whether ragged arguments were out of range
+struct StcImage { int k; bool bad; size_t at; };                               // at: the first message byte, from `message`
+struct StcRagged { const int32_t* ks; const int32_t* first; long long stride; int max_bits, cols_len; };     // ks == nullptr: uniform k
+__device__ __forceinline__ StcImage stc_image(const StcRagged& rg, long long n, int k, int nn) {
+    if (!rg.ks) return StcImage{k, false, (size_t)nn * k};
+    const int ki = rg.ks[nn], f = rg.first[nn];
+    const bool bad = ki < 0 || ki > n || f < 0 || (long long)f + ki > rg.max_bits || (ki > 0 && (n + ki - 1) / ki > rg.cols_len);
+    return StcImage{bad ? 0 : ki, bad, (size_t)nn * rg.stride + (bad ? 0 : f)};
+}
+
 // ---- K40 ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void philox_words_kernel(const uint64_t* __restrict__ seeds, uint32_t* __restrict__ words, long long hw) {
     const int nn = blockIdx.y;
@@ -73,8 +89,8 @@ template <bool ONE_WAVE>
 __global__ __launch_bounds__(1024) void stc_forward_kernel(const uint8_t* __restrict__ cover, const double* __restrict__ rho,
                                                            const uint8_t* __restrict__ message, const uint32_t* __restrict__ cols,
                                                            const int32_t* __restrict__ path, unsigned long long* __restrict__ take,
-                                                           double* __restrict__ cost, uint8_t* __restrict__ ok, long long n, int k,
-                                                           int height) {
+                                                           double* __restrict__ cost, uint8_t* __restrict__ ok, long long n, int k_uniform,
+                                                           int height, StcRagged rg) {
     __shared__ double wb[ONE_WAVE ? 1 : 2][ONE_WAVE ? 1 : 1 << STC_MAX_H];
     __shared__ double rs[STC_STAGE];
     __shared__ uint32_t cfs[STC_STAGE];
@@ -83,13 +99,16 @@ __global__ __launch_bounds__(1024) void stc_forward_kernel(const uint8_t* __rest
     const double inf = __builtin_inf();
     const uint8_t* cimg = cover + (size_t)nn * n;
     const double* rimg = rho + (size_t)nn * n;
-    const uint8_t* msg = message + (size_t)nn * k;
+    const StcImage im = stc_image(rg, n, k_uniform, nn);
+    const int k = im.k;
+    const uint8_t* msg = message + im.at;
+    const long long nrun = k > 0 ? n : 0;                                      // k == 0: no block, W stays (0, +inf ..)
     const int32_t* pimg = path ? path + (size_t)nn * n : nullptr;
     unsigned long long* timg = take + (size_t)nn * n * wpp;
     double wreg = tid == 0 ? 0.0 : inf;                                        // ONE_WAVE: W[lane]
     int cur = 0;
     if (!ONE_WAVE) wb[0][tid] = wreg;                                          // (the staging barrier below publishes it)
-    for (long long base = 0; base < n; base += STC_STAGE) {
+    for (long long base = 0; base < nrun; base += STC_STAGE) {
         const int cnt = n - base < STC_STAGE ? (int)(n - base) : STC_STAGE;
         __syncthreads();                                                       // the previous stage has been read
         for (int q = tid; q < cnt; q += nthreads) {
@@ -146,7 +165,7 @@ __global__ __launch_bounds__(1024) void stc_forward_kernel(const uint8_t* __rest
         }
     }
     if (tid == 0) {
-        const double total = ONE_WAVE ? wreg : wb[cur][0];
+        const double total = im.bad ? inf : ONE_WAVE ? wreg : wb[cur][0];
         cost[nn] = total;
         ok[nn] = total < inf ? 1 : 0;
     }
@@ -157,7 +176,8 @@ __global__ __launch_bounds__(1024) void stc_backward_kernel(const uint8_t* __res
                                                             const uint32_t* __restrict__ cols, const int32_t* __restrict__ path,
                                                             const uint64_t* __restrict__ seeds, const unsigned long long* __restrict__ take,
                                                             const double* __restrict__ cost, uint8_t* __restrict__ stego,
-                                                            long long* __restrict__ changes, long long n, int k, int height, int change) {
+                                                            long long* __restrict__ changes, long long n, int k_uniform, int height, int change,
+                                                            StcRagged rg) {
     __shared__ unsigned long long tks[STC_BACK << (STC_MAX_H - 6)];            // 32 KiB
     __shared__ uint32_t cfs[STC_BACK];
     __shared__ uint8_t ys[STC_BACK];
@@ -167,11 +187,13 @@ __global__ __launch_bounds__(1024) void stc_backward_kernel(const uint8_t* __res
     const uint32_t smask = (1u << height) - 1u;
     const uint8_t* cimg = cover + (size_t)nn * n;
     uint8_t* simg = stego + (size_t)nn * n;
-    const uint8_t* msg = message + (size_t)nn * k;
+    const StcImage im = stc_image(rg, n, k_uniform, nn);
+    const int k = im.k;
+    const uint8_t* msg = message + im.at;
     const int32_t* pimg = path ? path + (size_t)nn * n : nullptr;
     const unsigned long long* timg = take + (size_t)nn * n * wpp;
     const uint32_t k0 = (uint32_t)seeds[nn], k1 = (uint32_t)(seeds[nn] >> 32);
-    const bool good = cost[nn] < __builtin_inf();                              // else the stego is the cover
+    const bool good = k > 0 && cost[nn] < __builtin_inf();                     // else the stego is the cover
     uint32_t s = 0;                                                            // thread 0's state
     int cnt = 0;
     if (tid == 0) total = 0;
@@ -220,9 +242,11 @@ __global__ __launch_bounds__(1024) void stc_backward_kernel(const uint8_t* __res
 // ---- K42 ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void stc_extract_kernel(const uint8_t* __restrict__ stego, const uint32_t* __restrict__ cols,
                                                           const int32_t* __restrict__ path, uint8_t* __restrict__ message, long long n,
-                                                          int k, int height) {
+                                                          int k_uniform, int height, int plane, StcRagged rg) {
     const int nn = blockIdx.y;
     const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+    const StcImage im = stc_image(rg, n, k_uniform, nn);
+    const int k = im.k;
     if (b >= k) return;
     const uint8_t* simg = stego + (size_t)nn * n;
     const int32_t* pimg = path ? path + (size_t)nn * n : nullptr;
@@ -232,14 +256,36 @@ __global__ __launch_bounds__(256) void stc_extract_kernel(const uint8_t* __restr
         for (long long j = start; j < end; ++j) {
             if ((cols[j - start] >> r) & 1u) {
                 const long long pix = stc_pixel(pimg, j, n);
-                if (pix >= 0) bit ^= simg[pix] & 1u;
+                if (pix >= 0) bit ^= (simg[pix] >> plane) & 1u;
             }
         }
     }
-    message[(size_t)nn * k + b] = (uint8_t)bit;
+    message[im.at + b] = (uint8_t)bit;
 }
 
 int stc_threads(int height) { return height <= 6 ? 64 : 1 << height; }
+
+// K41 / K43 after their argument checks: the forward and the backward kernel of `phases`, with the uniform k or the ragged arguments
+int stc_embed_launch(const uint8_t* cover, const double* rho, const uint8_t* message, const uint32_t* cols, const int32_t* path,
+                     const uint64_t* seeds, int change, int height, int k, const StcRagged& rg, int phases, uint8_t* stego, double* cost,
+                     long long* changes, uint8_t* ok, void* workspace, int n, long long hw, hipStream_t s) {
+    unsigned long long* take = static_cast<unsigned long long*>(workspace);
+    const int threads = stc_threads(height);
+    if (phases & 1) {
+        if (height <= 6)
+            hipLaunchKernelGGL(stc_forward_kernel<true>, dim3(n), dim3(threads), 0, s, cover, rho, message, cols, path, take, cost, ok, hw, k, height, rg);
+        else
+            hipLaunchKernelGGL(stc_forward_kernel<false>, dim3(n), dim3(threads), 0, s, cover, rho, message, cols, path, take, cost, ok, hw, k, height, rg);
+        const int rc = wsu_check_launch("stc_forward_kernel");
+        if (rc) return rc;
+    }
+    if (phases & 2) {
+        hipLaunchKernelGGL(stc_backward_kernel, dim3(n), dim3(threads), 0, s, cover, message, cols, path, seeds, take, cost, stego, changes, hw, k,
+                           height, change, rg);
+        return wsu_check_launch("stc_backward_kernel");
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -247,10 +293,18 @@ int stc_threads(int height) { return height <= 6 ? 64 : 1 << height; }
 #define STC_REQUIRE_SHAPE(what)                                                                                       \
     WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, what ": bad shape n=%d h=%d w=%d", n, h, w);                 \
     WSU_REQUIRE((long long)h * w < (1LL << 31), what ": %lld pixels per image exceed the 32-bit path", (long long)h * w)
+#define STC_REQUIRE_HEIGHT(what)                                                                                      \
+    WSU_REQUIRE(height >= 1 && height <= STC_MAX_H, what ": constraint height %d outside 1..%d", height, STC_MAX_H)
 #define STC_REQUIRE_CODE(what)                                                                                        \
-    WSU_REQUIRE(height >= 1 && height <= STC_MAX_H, what ": constraint height %d outside 1..%d", height, STC_MAX_H);  \
+    STC_REQUIRE_HEIGHT(what);                                                                                         \
     WSU_REQUIRE(k >= 1, what ": k=%d message bits, at least 1 expected", k);                                          \
     WSU_REQUIRE((long long)k <= (long long)h * w, what ": k=%d message bits exceed the %lld pixels", k, (long long)h * w)
+// the host's part of the ragged arguments; what ks and first hold is checked by every workgroup (stc_image)
+#define STC_REQUIRE_RAGGED(what)                                                                                      \
+    WSU_REQUIRE(ks && first, what ": null ks or first");                                                              \
+    WSU_REQUIRE(max_bits >= 1 && (long long)max_bits <= message_stride,                                               \
+                what ": max_bits=%d outside 1..message_stride=%lld", max_bits, message_stride);                       \
+    WSU_REQUIRE(cols_len >= 1, what ": cols_len=%d, at least 1 expected", cols_len)
 
 extern "C" {
 
@@ -280,23 +334,8 @@ int wsu_stc_embed(const uint8_t* cover, const double* rho, const uint8_t* messag
     const long long hw = (long long)h * w;
     WSU_REQUIRE(workspace_bytes >= (size_t)n * wsu_stc_workspace_bytes(hw, height), "stc_embed: workspace too small");
     WSU_REQUIRE((uintptr_t)workspace % 8 == 0, "stc_embed: workspace must be 8-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    unsigned long long* take = static_cast<unsigned long long*>(workspace);
-    const int threads = stc_threads(height);
-    if (phases & 1) {
-        if (height <= 6)
-            hipLaunchKernelGGL(stc_forward_kernel<true>, dim3(n), dim3(threads), 0, s, cover, rho, message, cols, path, take, cost, ok, hw, k, height);
-        else
-            hipLaunchKernelGGL(stc_forward_kernel<false>, dim3(n), dim3(threads), 0, s, cover, rho, message, cols, path, take, cost, ok, hw, k, height);
-        const int rc = wsu_check_launch("stc_forward_kernel");
-        if (rc) return rc;
-    }
-    if (phases & 2) {
-        hipLaunchKernelGGL(stc_backward_kernel, dim3(n), dim3(threads), 0, s, cover, message, cols, path, seeds, take, cost, stego, changes, hw, k,
-                           height, change);
-        return wsu_check_launch("stc_backward_kernel");
-    }
-    return 0;
+    return stc_embed_launch(cover, rho, message, cols, path, seeds, change, height, k, StcRagged{nullptr, nullptr, 0, 0, 0}, phases, stego, cost,
+                            changes, ok, workspace, n, hw, static_cast<hipStream_t>(stream));
 }
 
 int wsu_stc_extract(const uint8_t* stego, const uint32_t* cols, const int32_t* path, int height, int k, uint8_t* message, int n, int h,
@@ -305,7 +344,38 @@ int wsu_stc_extract(const uint8_t* stego, const uint32_t* cols, const int32_t* p
     STC_REQUIRE_SHAPE("stc_extract");
     STC_REQUIRE_CODE("stc_extract");
     hipLaunchKernelGGL(stc_extract_kernel, dim3((unsigned)((k + 255) / 256), n), dim3(256), 0, static_cast<hipStream_t>(stream), stego, cols,
-                       path, message, (long long)h * w, k, height);
+                       path, message, (long long)h * w, k, height, 0, StcRagged{nullptr, nullptr, 0, 0, 0});
+    return wsu_check_launch("stc_extract_kernel");
+}
+
+int wsu_stc_embed_ragged(const uint8_t* cover, const double* rho, const uint8_t* message, long long message_stride, const int32_t* ks,
+                         const int32_t* first, int max_bits, const uint32_t* cols, int cols_len, const int32_t* path, const uint64_t* seeds,
+                         int change, int height, uint8_t* stego, double* cost, long long* changes, uint8_t* ok, void* workspace,
+                         size_t workspace_bytes, int n, int h, int w, void* stream) {
+    WSU_REQUIRE(cover && rho && message && cols && seeds && stego && cost && changes && ok && workspace, "stc_embed_ragged: null pointer");
+    STC_REQUIRE_SHAPE("stc_embed_ragged");
+    STC_REQUIRE_HEIGHT("stc_embed_ragged");
+    STC_REQUIRE_RAGGED("stc_embed_ragged");
+    WSU_REQUIRE(change == 0 || change == 1, "stc_embed_ragged: change=%d is neither 0 (flip) nor 1 (pm1)", change);
+    const long long hw = (long long)h * w;
+    WSU_REQUIRE(workspace_bytes >= (size_t)n * wsu_stc_workspace_bytes(hw, height), "stc_embed_ragged: workspace too small");
+    WSU_REQUIRE((uintptr_t)workspace % 8 == 0, "stc_embed_ragged: workspace must be 8-byte aligned");
+    return stc_embed_launch(cover, rho, message, cols, path, seeds, change, height, 0, StcRagged{ks, first, message_stride, max_bits, cols_len}, 3,
+                            stego, cost, changes, ok, workspace, n, hw, static_cast<hipStream_t>(stream));
+}
+
+int wsu_stc_extract_ragged(const uint8_t* stego, const uint32_t* cols, int cols_len, const int32_t* path, int height, int bit,
+                           const int32_t* ks, const int32_t* first, int max_bits, uint8_t* message, long long message_stride, int n, int h,
+                           int w, void* stream) {
+    WSU_REQUIRE(stego && cols && message, "stc_extract_ragged: null pointer");
+    STC_REQUIRE_SHAPE("stc_extract_ragged");
+    STC_REQUIRE_HEIGHT("stc_extract_ragged");
+    STC_REQUIRE_RAGGED("stc_extract_ragged");
+    WSU_REQUIRE(bit >= 0 && bit <= 7, "stc_extract_ragged: bit=%d outside 0..7", bit);
+    const long long hw = (long long)h * w;
+    const long long most = max_bits < hw ? max_bits : hw;                        // no image has more bits than pixels
+    hipLaunchKernelGGL(stc_extract_kernel, dim3((unsigned)((most + 255) / 256), n), dim3(256), 0, static_cast<hipStream_t>(stream), stego, cols,
+                       path, message, hw, 0, height, bit, StcRagged{ks, first, message_stride, max_bits, cols_len});
     return wsu_check_launch("stc_extract_kernel");
 }
 

@@ -26,12 +26,7 @@ constexpr int PM_MAX_BLOCKS = 64;      // K38 / K39 workgroups per image, at mos
 constexpr double LN2 = 0.693147180559945309417232121458;
 constexpr double TWO32 = 4294967296.0;
 
-// e = exp(-a) for the two directions of a pixel of value x: 0 for a wet direction and for a = +inf (or NaN)
-__device__ __forceinline__ void ternary_exp(uint8_t x, double a, double& ep, double& em) {
-    const double e = a < __builtin_inf() ? exp(-a) : 0.0;
-    ep = x == 255 ? 0.0 : e;
-    em = x == 0 ? 0.0 : e;
-}
+// (ternary_exp: wsu_metric.h, shared with the layer kernels K45-K47.)
 
 // ---- K37 ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ternary_entropy_partial_kernel(const uint8_t* __restrict__ x, const double* __restrict__ rho,

@@ -1,5 +1,5 @@
-// Device helpers shared by the metric kernels K10-K18, K27, K29, K32 and K33 and the simulators K20-K23, K28, K30, K34 and K37-K39 (pointwise.hip K10 + WS meter,
-// ws_attack.hip, ws_sequential.hip, ws_ordered.hip, ws_locate.hip, jpeg_history.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip, ternary.hip): the one definition each of a 3x3 predictor's
+// Device helpers shared by the metric kernels K10-K18, K27, K29, K32 and K33 and the simulators K20-K23, K28, K30, K34, K37-K39 and K45-K47 (pointwise.hip K10 + WS meter,
+// ws_attack.hip, ws_sequential.hip, ws_ordered.hip, ws_locate.hip, jpeg_history.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip, ternary.hip, stc_layers.hip): the one definition each of a 3x3 predictor's
 // taps, the prediction at a pixel, the float32 residual, the WS statistic's per-pixel terms, the maximum-prefix triple, the HILL cost's input window, the fixed-order
 // block sum, the simulators' pixel loops and the radix-select steps.
 //
@@ -218,6 +218,14 @@ __device__ __forceinline__ void add_changes(int cnt, long long* __restrict__ dst
         const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
         if (total) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)total);
     }
+}
+
+// ---- the +-1 sender's exponentials (K37, K38, K45) -------------------------------------------------------------------------------------------
+// e = exp(-a) for the two directions of a pixel of value x: 0 for a wet direction and for a = +inf (or NaN)
+__device__ __forceinline__ void ternary_exp(uint8_t x, double a, double& ep, double& em) {
+    const double e = a < __builtin_inf() ? exp(-a) : 0.0;
+    ep = x == 255 ? 0.0 : e;
+    em = x == 0 ? 0.0 : e;
 }
 
 // ---- exact radix select over float32 bit patterns (K13, K18) -----------------------------------------------------------------------

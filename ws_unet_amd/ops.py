@@ -1771,6 +1771,22 @@ def stc_workspace_bytes(pixels: int, h: int) -> int:
     return b
 
 
+def _stc_slices(who: str, n: int, hw: int, h: int, workspace_cap, workspace: Optional[torch.Tensor], dev):
+    """(bytes of take bits per image, images per slice, the slices' workspace): the caller's `workspace` holds the whole batch, else one
+    of at most `workspace_cap` bytes (at least one image) is made."""
+    per = stc_workspace_bytes(hw, h)
+    cap = STC_WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
+    if cap < 1:
+        raise ValueError(f"{who}: workspace_cap={workspace_cap!r} is not a positive byte count")
+    if workspace is not None:
+        _dev_check(workspace)
+        if workspace.dtype != torch.uint8 or workspace.numel() < n * per:
+            raise ValueError(f"{who}: workspace must be uint8 with at least {n * per} bytes")
+        return per, n, workspace
+    step = max(1, min(n, cap // per))
+    return per, step, torch.empty(step * per, dtype=torch.uint8, device=dev)
+
+
 def stc_embed(cover_u8: torch.Tensor, rho: torch.Tensor, message: torch.Tensor, cols: torch.Tensor, seeds: torch.Tensor, *, h: int = 10,
               path: Optional[torch.Tensor] = None, change: str = "flip", workspace_cap: Optional[int] = None, phases: int = 3,
               workspace: Optional[torch.Tensor] = None):
@@ -1797,19 +1813,8 @@ def stc_embed(cover_u8: torch.Tensor, rho: torch.Tensor, message: torch.Tensor, 
         raise ValueError(f"stc_embed: change {change!r} is not one of {' / '.join(STC_CHANGES)}")
     if phases not in (1, 3) or (phases == 1 and workspace is None):
         raise ValueError("stc_embed: phases is 1 (forward only, into the caller's workspace) or 3 (both)")
-    per = stc_workspace_bytes(hw, h)
-    cap = STC_WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
-    if cap < 1:
-        raise ValueError(f"stc_embed: workspace_cap={workspace_cap!r} is not a positive byte count")
     dev = cover_u8.device
-    if workspace is not None:
-        _dev_check(workspace)
-        if workspace.dtype != torch.uint8 or workspace.numel() < n * per:
-            raise ValueError(f"stc_embed: workspace must be uint8 with at least {n * per} bytes")
-        step, ws = n, workspace
-    else:
-        step = max(1, min(n, cap // per))
-        ws = torch.empty(step * per, dtype=torch.uint8, device=dev)
+    per, step, ws = _stc_slices("stc_embed", n, hw, h, workspace_cap, workspace, dev)
     stego = torch.empty_like(cover_u8)
     cost = torch.empty(n, dtype=torch.float64, device=dev)
     changes = torch.zeros(n, dtype=torch.int64, device=dev)
@@ -1835,6 +1840,169 @@ def stc_extract(stego_u8: torch.Tensor, cols: torch.Tensor, k: int, *, h: int = 
     check(_launch("stc_extract", {"bytes": float(n * hh * ww * 5)}, lambda: lib.wsu_stc_extract(
         stego_u8.data_ptr(), cols.data_ptr(), _ptr(path), h, k, message.data_ptr(), n, hh, ww, _stream())), "wsu_stc_extract")
     return message
+
+
+# ---- ragged codes and the two-layer planes (K43-K47) ---------------------------------------------------------------------------------
+
+def _stc_ragged(who: str, n: int, hw: int, h, message: torch.Tensor, ks: torch.Tensor, first: Optional[torch.Tensor], cols: torch.Tensor,
+                path: Optional[torch.Tensor]) -> Tuple[int, torch.Tensor]:
+    """The checks of _stc_code for per-image lengths; what ks and first hold stays on the device, where the kernels check it."""
+    h = int(h)
+    if not 1 <= h <= STC_MAX_H:
+        raise ValueError(f"{who}: constraint height h={h} outside 1..{STC_MAX_H}")
+    if not (isinstance(message, torch.Tensor) and message.dtype == torch.uint8 and message.dim() == 2 and message.shape[0] == n
+            and message.shape[1] >= 1):
+        raise ValueError(f"{who}: message must be an ({n}, bits) uint8 tensor of 0 / 1")
+    if not (isinstance(ks, torch.Tensor) and ks.dtype == torch.int32 and ks.shape == (n,)):
+        raise ValueError(f"{who}: ks must be an int32 tensor of shape ({n},): the message bits of each image")
+    if first is None:
+        first = torch.zeros(n, dtype=torch.int32, device=ks.device)
+    if not (isinstance(first, torch.Tensor) and first.dtype == torch.int32 and first.shape == (n,)):
+        raise ValueError(f"{who}: first must be an int32 tensor of shape ({n},): the first bit of each row that is used")
+    _dev_check(message, ks, first, cols, path)
+    if cols.dtype != torch.int32 or cols.dim() != 1 or cols.shape[0] < 1:
+        raise ValueError(f"{who}: cols must be int32 with at least ceil(n / k) entries for the smallest positive k, got {tuple(cols.shape)} {cols.dtype}")
+    if path is not None and (path.dtype != torch.int32 or path.shape != (n, hw)):
+        raise ValueError(f"{who}: path must be int32 of shape ({n}, {hw}), got {tuple(path.shape)} {path.dtype}")
+    return h, first
+
+
+def stc_embed_ragged(cover_u8: torch.Tensor, rho: torch.Tensor, message: torch.Tensor, cols: torch.Tensor, seeds: torch.Tensor, *,
+                     ks: torch.Tensor, first: Optional[torch.Tensor] = None, h: int = 10, path: Optional[torch.Tensor] = None,
+                     change: str = "flip", workspace_cap: Optional[int] = None):
+    """stc_embed with a message length per image (K43): image i embeds the ks[i] bits message[i, first[i] : first[i] + ks[i]].  message:
+    (N,B) uint8; ks, first: (N) int32 on the device, 0 <= ks[i] <= H W, first[i] + ks[i] <= B (first:
+    zeros when None); cols: at least ceil(H W / k) entries for the smallest positive k -> (stego, cost, changes, ok) as stc_embed.
+    ks[i] == 0 copies the image: cost 0, ok 1.  Nothing is read back, so values of ks / first outside these ranges are found by the
+    kernel: such an image is copied and has cost +inf and ok 0.  With all ks equal the results are stc_embed's bit for bit."""
+    lib = _lib.load()
+    n, hh, ww = _ternary_planes("stc_embed_ragged", cover_u8, rho)
+    hw = hh * ww
+    h, first = _stc_ragged("stc_embed_ragged", n, hw, h, message, ks, first, cols, path)
+    _dev_check(seeds)
+    if seeds.dtype != torch.int64 or seeds.shape != (n,):
+        raise ValueError(f"stc_embed_ragged: seeds must be int64 of shape ({n},), got {tuple(seeds.shape)} {seeds.dtype}")
+    if change not in STC_CHANGES:
+        raise ValueError(f"stc_embed_ragged: change {change!r} is not one of {' / '.join(STC_CHANGES)}")
+    dev = cover_u8.device
+    per, step, ws = _stc_slices("stc_embed_ragged", n, hw, h, workspace_cap, None, dev)
+    stego = torch.empty_like(cover_u8)
+    cost = torch.empty(n, dtype=torch.float64, device=dev)
+    changes = torch.zeros(n, dtype=torch.int64, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    cid, bits, stride = STC_CHANGES.index(change), message.shape[1], message.stride(0)
+    for a in range(0, n, step):
+        b = min(n, a + step)
+        p = path[a:b].data_ptr() if path is not None else None
+        check(_launch("stc_embed_ragged", {"bytes": float((b - a) * (hw * 14 + 2 * per))}, lambda: lib.wsu_stc_embed_ragged(
+            cover_u8[a:b].data_ptr(), rho[a:b].data_ptr(), message[a:b].data_ptr(), stride, ks[a:b].data_ptr(), first[a:b].data_ptr(), bits,
+            cols.data_ptr(), cols.shape[0], p, seeds[a:b].data_ptr(), cid, h, stego[a:b].data_ptr(), cost[a:b].data_ptr(),
+            changes[a:b].data_ptr(), ok[a:b].data_ptr(), ws.data_ptr(), ws.numel(), b - a, hh, ww, _stream())), "wsu_stc_embed_ragged")
+    return stego, cost, changes, ok
+
+
+def stc_extract_ragged(stego_u8: torch.Tensor, cols: torch.Tensor, *, ks: torch.Tensor, first: Optional[torch.Tensor] = None, bits: Optional[int] = None,
+                       bit: int = 0, h: int = 10, path: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """stc_extract with a message length per image (K44): reads ks[i] bits of image i from bit `bit` (0..7) of its bytes into
+    out[i, first[i] : first[i] + ks[i]].  out: (N,B) uint8 on the device, written only there (several calls can fill one row); when None a
+    zeroed (N, bits) tensor is made.  ks, first, cols, h, path as stc_embed_ragged was given them; an image with ks[i] == 0 or with
+    values out of range writes nothing."""
+    lib = _lib.load()
+    n, hh, ww = _u8_planes(stego_u8)
+    if out is None:
+        if bits is None or int(bits) < 1:
+            raise ValueError("stc_extract_ragged: give `out`, or `bits` >= 1 for the width of a new one")
+        out = torch.zeros((n, int(bits)), dtype=torch.uint8, device=stego_u8.device)
+    h, first = _stc_ragged("stc_extract_ragged", n, hh * ww, h, out, ks, first, cols, path)
+    bit = int(bit)
+    if not 0 <= bit <= 7:
+        raise ValueError(f"stc_extract_ragged: bit={bit} outside 0..7")
+    check(_launch("stc_extract_ragged", {"bytes": float(n * hh * ww * 5)}, lambda: lib.wsu_stc_extract_ragged(
+        stego_u8.data_ptr(), cols.data_ptr(), cols.shape[0], _ptr(path), h, bit, ks.data_ptr(), first.data_ptr(), out.shape[1], out.data_ptr(),
+        out.stride(0), n, hh, ww, _stream())), "wsu_stc_extract_ragged")
+    return out
+
+
+def _layer_workspace(n: int, dev) -> torch.Tensor:
+    return torch.empty(_lib.load().wsu_stc_layer_workspace_bytes(n) // 8, dtype=torch.float64, device=dev)
+
+
+def _layer_lambdas(who: str, n: int, lambdas: torch.Tensor) -> None:
+    _dev_check(lambdas)
+    if lambdas.dtype != torch.float64 or lambdas.shape != (n,):
+        raise ValueError(f"{who}: lambdas must be float64 of shape ({n},), got {tuple(lambdas.shape)} {lambdas.dtype}")
+
+
+def _layer_plane(who: str, name: str, t: torch.Tensor, like: torch.Tensor) -> None:
+    _dev_check(t)
+    if t.dtype != torch.uint8 or t.shape != like.shape:
+        raise ValueError(f"{who}: {name} must be uint8 of shape {tuple(like.shape)}, got {tuple(t.shape)} {t.dtype}")
+
+
+def _layer_vector(who: str, name: str, t: torch.Tensor, n: int, dtype) -> None:
+    _dev_check(t)
+    if t.dtype != dtype or t.shape != (n,):
+        raise ValueError(f"{who}: {name} must be {dtype} of shape ({n},), got {tuple(t.shape)} {t.dtype}")
+
+
+def stc_layer_high(x_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor):
+    """The high layer of the two-layer +-1 code (K45): x_u8: (N,H,W) uint8; rho: (N,H,W) float64, >= 0, +inf = wet; lambdas: (N) float64
+    (ternary_lambda's lam_lo) -> (u1 (N,H,W) uint8 = bit 1 of the pixels, rho1 (N,H,W) float64 = the cost of changing it, H1 (N) float64 =
+    the layer's entropy in bits).  include/wsu.h has the formulas.  The same bits in every batch."""
+    lib = _lib.load()
+    n, h, w = _ternary_planes("stc_layer_high", x_u8, rho)
+    _layer_lambdas("stc_layer_high", n, lambdas)
+    dev = x_u8.device
+    u1 = torch.empty_like(x_u8)
+    rho1 = torch.empty_like(rho)
+    ent = torch.empty(n, dtype=torch.float64, device=dev)
+    ws = _layer_workspace(n, dev)
+    check(_launch("stc_layer_high", {"bytes": float(n * h * w * 18)}, lambda: lib.wsu_stc_layer_high(
+        x_u8.data_ptr(), rho.data_ptr(), lambdas.data_ptr(), u1.data_ptr(), rho1.data_ptr(), ent.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+        n, h, w, _stream())), "wsu_stc_layer_high")
+    return u1, rho1, ent
+
+
+def stc_layer_low(x_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor, y1: torch.Tensor, k1: torch.Tensor):
+    """The low layer's planes (K46): y1: (N,H,W) uint8, the high layer's solution (bit 0 of each byte; not read where k1[i] <= 0); k1: (N)
+    int32 -> (u0 (N,H,W) uint8, rho0 (N,H,W) float64): a pixel whose bit 1 changed is decided (u0 = the other LSB, rho0 = +inf), every
+    other keeps its LSB at cost lambda rho."""
+    lib = _lib.load()
+    n, h, w = _ternary_planes("stc_layer_low", x_u8, rho)
+    _layer_lambdas("stc_layer_low", n, lambdas)
+    _layer_plane("stc_layer_low", "y1", y1, x_u8)
+    _layer_vector("stc_layer_low", "k1", k1, n, torch.int32)
+    u0 = torch.empty_like(x_u8)
+    rho0 = torch.empty_like(rho)
+    check(_launch("stc_layer_low", {"bytes": float(n * h * w * 19)}, lambda: lib.wsu_stc_layer_low(
+        x_u8.data_ptr(), rho.data_ptr(), lambdas.data_ptr(), y1.data_ptr(), k1.data_ptr(), u0.data_ptr(), rho0.data_ptr(),
+        n, h, w, _stream())), "wsu_stc_layer_low")
+    return u0, rho0
+
+
+def stc_layer_compose(cover_u8: torch.Tensor, rho: torch.Tensor, y1: torch.Tensor, y0: torch.Tensor, k1: torch.Tensor, ok1: torch.Tensor,
+                      ok0: torch.Tensor):
+    """The stego image of the two layers' solutions (K47): x + d where bit 1 changed (d: +1 for odd x, -1 for even x), x - d where only
+    the LSB did, in images whose ok1 and ok0 (N, uint8) are both set; every other image is copied -> (stego (N,H,W) uint8, changes (N)
+    int64, distortion (N) float64 = the sum of rho over the changed pixels in a fixed order, ok (N) uint8)."""
+    lib = _lib.load()
+    n, h, w = _ternary_planes("stc_layer_compose", cover_u8, rho)
+    _layer_plane("stc_layer_compose", "y1", y1, cover_u8)
+    _layer_plane("stc_layer_compose", "y0", y0, cover_u8)
+    _layer_vector("stc_layer_compose", "k1", k1, n, torch.int32)
+    _layer_vector("stc_layer_compose", "ok1", ok1, n, torch.uint8)
+    _layer_vector("stc_layer_compose", "ok0", ok0, n, torch.uint8)
+    dev = cover_u8.device
+    stego = torch.empty_like(cover_u8)
+    changes = torch.empty(n, dtype=torch.int64, device=dev)
+    dist = torch.empty(n, dtype=torch.float64, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = _layer_workspace(n, dev)
+    check(_launch("stc_layer_compose", {"bytes": float(n * h * w * 12)}, lambda: lib.wsu_stc_layer_compose(
+        cover_u8.data_ptr(), rho.data_ptr(), y1.data_ptr(), y0.data_ptr(), k1.data_ptr(), ok1.data_ptr(), ok0.data_ptr(),
+        stego.data_ptr(), changes.data_ptr(), dist.data_ptr(), ok.data_ptr(), ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())),
+        "wsu_stc_layer_compose")
+    return stego, changes, dist, ok
 
 
 def prediction_error(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, hat_scale: float = 255.,

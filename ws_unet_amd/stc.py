@@ -13,7 +13,8 @@ the LSB vector with syndrome m and the least total cost by the Viterbi algorithm
 gives the exact definition (block widths floor(n / k) or one more, the cropped bottom, ties keep the cover bit); `columns` makes the
 submatrix.  'STCR' flips the LSBs that differ (LSB replacement with a cost-coded message), 'STCM' moves such a pixel by +1 or -1, the sign
 from one bit of its generator word, inwards at 0 and 255 (LSB matching under an STC).  The cost is ops.hill_cost_f64 by default, so 'STCM'
-is the binary single-layer relative of embed_pm1's simulated 'HILL'; the ternary multi-layer construction of the paper is not built.
+is the binary single-layer relative of embed_pm1's simulated 'HILL'; the paper's ternary two-layer construction is `ws_unet_amd.stc_ml`
+('STCT'), which runs two of these codes per image through the per-image-length entries ops.stc_embed_ragged / stc_extract_ragged (K43, K44).
 
 The stego key: sender and receiver share `seeds` (embed.image_seed: file stem and stream).  The pixel path is the stable ascending sort of
 the generator word embed_lsbr gives each pixel under the image's seed (`key_path`), so it depends on (seed, H, W) alone; a random message
