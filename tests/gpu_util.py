@@ -17,6 +17,37 @@ OUT_ATOL_DEEP = {"f32": 1e-5, "bf16x3": 4e-5, "bf16": 5e-2, "f16f8": 1.5e-4, "f1
 ACT_RTOL = {"f32": 2e-5, "bf16x3": 1e-4, "bf16": 6e-2}
 
 
+# ---- the simulators' pixel loop (csrc/wsu_embed.h) at every placement of a plane ------------------------------------------------------------
+# image_span has five ways through: (a) no head, a tail remains; (b) a head that is a multiple of 4, with and without a 16-byte group
+# behind it; (c) a head that is no multiple of 4: bytes; (d) a head longer than the plane: bytes; (e) cover and stego differ in
+# alignment: bytes.  Freshly allocated tensors start on the 16-byte grid, so a plane is carved out of a larger buffer instead:
+# path -> ((H, W), the cover's byte offset, the stego's)
+SPAN_PLACEMENTS = {"a": [((5, 13), 0, 0)], "b": [((5, 13), 4, 4), ((3, 5), 4, 4)], "c": [((5, 13), 1, 1)], "d": [((1, 1), 4, 4)],
+                   "e": [((5, 13), 4, 0)]}
+
+
+def check_span_placements(paths: str, call, restate, counts: bool = True):
+    """The raw C entry of one simulator on a single plane at the placements of `paths` (letters of SPAN_PLACEMENTS): call(cover pointer,
+    stego pointer, changes pointer, h, w) runs it and returns its status, restate(plane (h,w) uint8) -> the stego plane it must give
+    whatever the placement.  Also: changes == the differing bytes (counts), and no byte outside the stego plane is written."""
+    for path in paths:
+        for (h, w), off_in, off_out in SPAN_PLACEMENTS[path]:
+            plane = np.random.default_rng(97 * h + w).integers(0, 256, (h, w), dtype=np.uint8)
+            plane.reshape(-1)[:2] = (0, 255)[:h * w]                                 # both ends of the range, where +-1 changes are one-sided
+            buf_in = torch.zeros(h * w + 32, dtype=torch.uint8, device=DEV)
+            buf_out = torch.full((h * w + 32,), 0xA5, dtype=torch.uint8, device=DEV)
+            assert buf_in.data_ptr() % 16 == 0 and buf_out.data_ptr() % 16 == 0
+            cin, cout = buf_in[off_in:off_in + h * w], buf_out[off_out:off_out + h * w]
+            cin.copy_(torch.from_numpy(plane.reshape(-1)))
+            ch = torch.full((1,), 7, dtype=torch.int64, device=DEV)
+            ops.check(call(cin.data_ptr(), cout.data_ptr(), ch.data_ptr(), h, w), f"path ({path}) {h}x{w} at {off_in} -> {off_out}")
+            want = np.asarray(restate(plane)).astype(np.uint8)
+            np.testing.assert_array_equal(cout.cpu().numpy().reshape(h, w), want, err_msg=f"path ({path}) {h}x{w} at {off_in} -> {off_out}")
+            assert ch.item() == (int((want != plane).sum()) if counts else 7), (path, h, w, ch.item())
+            rest = torch.cat([buf_out[:off_out], buf_out[off_out + h * w:]])
+            assert bool((rest == 0xA5).all()) and torch.equal(cin.cpu(), torch.from_numpy(plane.reshape(-1))), (path, h, w)
+
+
 def to_nhwc(x_nchw: torch.Tensor, mode: str) -> torch.Tensor:
     """CPU NCHW fp32 -> device NHWC in the activation dtype of ``mode``."""
     dt = ops.act_dtype(ops.mode_id(mode))

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from gpu_util import DEV
+from gpu_util import DEV, check_span_placements
 import embed_np
 import hill_np
 from ws_unet_amd import embed, fabrika, ops
@@ -174,6 +174,16 @@ def test_lsbr_equals_numpy(shape):
     assert torch.equal(alone[0], stego[2]) and ch1[0] == ch[2]
     again, ch2 = embed.simulate(xd, "LSBR", mixed, SEEDS)
     assert torch.equal(again, stego) and torch.equal(ch2, ch)
+
+
+def test_lsbr_where_cover_and_stego_differ_in_alignment():
+    """test_lsbr_equals_numpy reaches the pixel loop's paths (a) - (d) (three images of 1x1, 3x5 and 70x90 start off the 16-byte grid);
+    (e) needs the raw entry."""
+    lib = ops._lib.load()
+    seeds = torch.tensor([SEEDS[1]], dtype=torch.int64, device=DEV)
+    thr = torch.from_numpy(np.array([ops.lsbr_threshold(0.4)], dtype=np.uint32).view(np.int32)).to(DEV)
+    check_span_placements("e", lambda ci, co, ch, h, w: lib.wsu_embed_lsbr(ci, seeds.data_ptr(), thr.data_ptr(), co, ch, 1, h, w, ops._stream()),
+                          lambda plane: embed_np.lsbr_np(plane, 0.4, SEEDS[1]))
 
 
 def test_lsbr_rate_on_a_cover(covers):

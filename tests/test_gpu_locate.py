@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from gpu_util import DEV, DEFAULT_MODE, gpu_model
+from gpu_util import DEV, DEFAULT_MODE, check_span_placements, gpu_model
 import locate_np
 from ws_unet_amd import embed, filters, ops
 from ws_unet_amd.imread import imread4_u8
@@ -270,6 +270,13 @@ def test_the_mask_is_one_for_every_image_and_the_simulator_may_write_in_place():
     ops.check(lib.wsu_embed_lsbr_keyed(buf.data_ptr(), sd.data_ptr(), KEY, thr, buf.data_ptr(), ch.data_ptr(), 3, 19, 23, ops._stream()),
               "wsu_embed_lsbr_keyed")
     assert torch.equal(buf, stego) and torch.equal(ch, changes)
+    # the shapes above reach the pixel loop's paths (a) and (c), the mask (always a fresh tensor) only (a); the others need a plane placed
+    # by hand ((e) is about a cover, which the mask has not)
+    sd1 = sd[:1].contiguous()
+    check_span_placements("bde", lambda ci, co, c, h, w: lib.wsu_embed_lsbr_keyed(ci, sd1.data_ptr(), KEY, thr, co, c, 1, h, w, ops._stream()),
+                          lambda p: locate_np.lsbrk_np(p, 0.5, seeds[0], KEY))
+    check_span_placements("bcd", lambda ci, co, c, h, w: lib.wsu_lsbr_key_mask(KEY, thr, co, h, w, ops._stream()),
+                          lambda p: locate_np.key_mask_np(KEY, 0.5, *p.shape), counts=False)
     with pytest.raises(ValueError, match="one alpha"):
         embed.simulate(xs, "LSBRK", [0.1, 0.2, 0.3], seeds, placement_key=KEY)
 

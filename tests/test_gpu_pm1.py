@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from gpu_util import DEV
+from gpu_util import DEV, check_span_placements
 import pm1_np
 import spam_np
 from ws_unet_amd import embed, embed_pm1, fabrika, ops, spam
@@ -124,6 +124,30 @@ def test_draws_equal_the_restatement_bit_for_bit(content, shape):
         assert torch.equal(buf, stego) and torch.equal(ch, changes), name
     assert torch.equal(ops.embed_lsbm(cover, seeds, torch.zeros_like(thr))[0], cover)
     assert torch.equal(ops.embed_ternary(cover, cost, torch.full_like(lam, float("inf")), seeds)[0], cover)
+
+
+def test_draws_where_the_plane_is_short_or_cover_and_stego_differ_in_alignment():
+    """The shapes above reach the pixel loop's paths (a), (b) (70 x 90) and (c) (65 x 130); (d) and (e) need a plane placed by hand."""
+    lib = ops._lib.load()
+    seeds, lam = _dev([pm1_np.SEED], torch.int64), _dev([0.7], torch.float64)
+    thr = _dev([pm1_np.lsbm_threshold(0.4)], torch.int32)
+
+    def cost(h, w):                                                           # positive, finite, different from pixel to pixel
+        return 0.25 + (np.arange(h * w, dtype=np.float64) % 5).reshape(h, w)
+
+    costs = []                                                                # (alive until the test ends)
+
+    def hill(ci, co, ch, h, w):
+        costs.append(_dev(cost(h, w)[None]))
+        return lib.wsu_embed_ternary(ci, costs[-1].data_ptr(), lam.data_ptr(), seeds.data_ptr(), co, ch, 1, h, w, ops._stream())
+
+    def hill_np(p):
+        assert pm1_np.min_gap(p, *pm1_np.ternary_thresholds(p, cost(*p.shape), 0.7), pm1_np.SEED) > 64      # no draw hangs on exp's last bits
+        return pm1_np.ternary_np(p, cost(*p.shape), 0.7, pm1_np.SEED)[0]
+
+    check_span_placements("de", hill, hill_np)
+    check_span_placements("de", lambda ci, co, ch, h, w: lib.wsu_embed_lsbm(ci, seeds.data_ptr(), thr.data_ptr(), co, ch, 1, h, w, ops._stream()),
+                          lambda p: pm1_np.lsbm_np(p, 0.4, pm1_np.SEED)[0])
 
 
 def test_draws_depend_on_the_seed_alone():

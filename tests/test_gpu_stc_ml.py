@@ -54,7 +54,7 @@ def test_every_stage_equals_the_restatement(shape, alpha, h):
     seeds = [SEED] * n
     msg = stc.random_message(seeds, k, DEV)
     np.testing.assert_array_equal(msg[0].cpu().numpy(), m_np)
-    s = stc._seeds("test", seeds, n, DEV)
+    s = embed.seeds_tensor("test", seeds, n, DEV)
     path = stc.key_path(s, *shape, DEV)
     path_np = stc_np.key_path(SEED, hw)
     lam, _, fits = ops.ternary_lambda(cover, rho, torch.full((n,), float(k), dtype=torch.float64, device=DEV))
@@ -155,7 +155,7 @@ def test_compose_writes_over_the_cover_and_copies_what_is_not_ok():
     cover, rho = _batch(shape)
     n, hw = 4, 1023
     k = stc_ml_np.bits_of(shape, 0.4)
-    s = stc._seeds("test", [SEED] * n, n, DEV)
+    s = embed.seeds_tensor("test", [SEED] * n, n, DEV)
     msg = stc.random_message([SEED] * n, k, DEV)
     lam = ops.ternary_lambda(cover, rho, torch.full((n,), float(k), dtype=torch.float64, device=DEV))[0]
     u1, rho1, ent = ops.stc_layer_high(cover, rho, lam)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from gpu_util import DEV, DEFAULT_MODE, gpu_model
+from gpu_util import DEV, DEFAULT_MODE, check_span_placements, gpu_model
 import embed_np
 import sequential_np
 from ws_unet_amd import embed, filters, ops
@@ -266,6 +266,13 @@ def test_sequential_simulator_takes_one_count_per_image_and_may_write_in_place()
     stego = embed.simulate(xs, "LSBRS", alphas, seeds, order="rows_up")[0].cpu().numpy()
     for i, a in enumerate(alphas):
         np.testing.assert_array_equal(stego[i], sequential_np.lsbrs_np(cover[i], a, seeds[i], "rows_up"))
+    # the shapes above reach the pixel loop's paths (a) and (c); (b), (d) and (e) need a plane placed by hand.  Two thirds of the pixels
+    # are on the path: from the bottom that is whole rows and a part of one
+    sd1, ms = sd[:1].contiguous(), {hw: torch.tensor([max(1, 2 * hw // 3)], dtype=torch.int64, device=DEV) for hw in (65, 15, 1)}
+    for order in ORDERS:
+        def run(ci, co, ch, h, w):
+            return lib.wsu_embed_lsbr_seq(ci, sd1.data_ptr(), ms[h * w].data_ptr(), ops.order_id(order), co, ch, 1, h, w, ops._stream())
+        check_span_placements("bde", run, lambda p: sequential_np.lsbrs_np(p, None, seeds[0], order, count=max(1, 2 * p.size // 3)))
 
 
 # ---- both ends on the golden covers ------------------------------------------------------------------------------------------

@@ -13,6 +13,8 @@
 //   HILLRM  stego = cover ^ (key <= c_(k)  and  word < 2^31),  k = floor((H*W - 1) * alpha): LSBR at alpha = 1 on the pixels HILLR's
 //           criterion selects, i.e. a real message instead of HILLR's flip of every selected pixel (K34)
 //
+// K23 is a rule of the pixel loop embed_span of wsu_embed.h (as K38 / K39 of ternary.hip are), which also holds the span, the change
+// count and the launch set-up that K22, K28, K30 and K34 share; the shape check is WSU_REQUIRE_SHAPE of wsu_device.h.
 // K20 is K12 in float64 on a 32 x 32 tile (the float64 arrays of a 64 x 64 tile would need 97 KB of LDS; a 32 x 32 tile needs 36 KB
 // and stays static): every sum is a direct sum in numpy's order, the two divisions are IEEE divisions, nothing is contracted.  K21 is an
 // exact radix select over the keys' uint64 patterns (positive and finite after the clamp, so monotone): six histogram passes of
@@ -20,6 +22,7 @@
 // workspace and the change counters are zeroed on the stream: two calls give the same bits.
 #pragma clang fp contract(off)
 #include "wsu_metric.h"
+#include "wsu_embed.h"
 #include "wsu_philox.h"
 
 namespace {
@@ -35,7 +38,6 @@ constexpr int ES = ET + 14;            // S / rho0 extent
 constexpr int SEL_LEVELS = 6;          // K21 radix: 11 / 11 / 11 / 11 / 11 / 9 bits
 constexpr int SEL_BINS = 2048;
 constexpr int SEL_PARTS = 64;          // K21 workgroups per image
-constexpr int EMB_MAX_BLOCKS = 64;     // K22 / K23 workgroups per image, at most
 
 // ---- K20 ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hill_cost_f64_kernel(const uint8_t* __restrict__ x, double* __restrict__ cost, int h, int w,
@@ -172,10 +174,8 @@ __global__ __launch_bounds__(256) void rank_select_pick_kernel(void* __restrict_
     }
 }
 
-// ---- K22 / K23: the pixel loops -----------------------------------------------------------------------------------------------
-// (image_span, span_byte_index and add_changes: wsu_metric.h, shared with the +-1 simulators of ternary.hip.)
-
-// K22.  A wave takes 1024 consecutive pixels at a time: lane l owns pixels 16 l .. 16 l + 15 (one 16-byte load and store), the keys are
+// ---- K22: a pixel loop of its own (wsu_embed.h says why) ------------------------------------------------------------------------------
+// A wave takes 1024 consecutive pixels at a time: lane l owns pixels 16 l .. 16 l + 15 (one 16-byte load and store), the keys are
 // read 64 consecutive ones per step (lane l: key 64 j + l) and a ballot hands every lane the 16 decisions of its pixels.
 __global__ __launch_bounds__(256) void embed_threshold_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ keys,
                                                               const uint64_t* __restrict__ bits, uint8_t* __restrict__ stego,
@@ -216,40 +216,30 @@ __global__ __launch_bounds__(256) void embed_threshold_kernel(const uint8_t* __r
     add_changes(cnt, changes + nn, tid);
 }
 
-// K23.  Philox4x32-10 (Salmon et al., SC'11): philox4x32_10 of wsu_philox.h, shared with the stego-key search (K35).
+// ---- K23: a rule of embed_span; K28 and K30: the same loop written out (why: at K30) ---------------------------------------------------
+// Pixel i draws the Philox word philox_byte(i, seed) (philox_quad: the four of a quad, wsu_philox.h); a rule says what the draw does to
+// the pixel.
+
+// K23.  LSBR: a pixel flips iff its word is below the image's threshold.
+struct LsbrRule {
+    SeedKey k;
+    uint32_t thr;
+    __device__ __forceinline__ uint32_t quad(long long i0, uint32_t x, int& cnt) const {
+        const uint32_t flips = below_bytes(philox_quad(i0, k), thr);
+        cnt += __popc(flips);
+        return x ^ flips;
+    }
+    __device__ __forceinline__ uint8_t byte(long long i, uint8_t x, int& cnt) const {
+        const uint8_t flip = philox_byte(i, k) < thr ? 1 : 0;
+        cnt += flip;
+        return x ^ flip;
+    }
+};
 __global__ __launch_bounds__(256) void embed_lsbr_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ seeds,
                                                          const uint32_t* __restrict__ thresholds, uint8_t* __restrict__ stego,
                                                          long long* __restrict__ changes, long long hw) {
-    const int nn = blockIdx.y, tid = threadIdx.x;
-    const uint8_t* cin = cover + (size_t)nn * hw;
-    uint8_t* cout = stego + (size_t)nn * hw;
-    const uint32_t k0 = (uint32_t)seeds[nn], k1 = (uint32_t)(seeds[nn] >> 32), thr = thresholds[nn];
-    const Span sp = image_span(cin, cout, hw, true);
-    int cnt = 0;
-    for (long long g = (long long)blockIdx.x * 256 + tid; g < sp.groups; g += (long long)gridDim.x * 256) {
-        const long long p = sp.head + 16 * g;                               // a multiple of 4
-        u32x4 v = *reinterpret_cast<const u32x4*>(cin + p);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const Words4 wd = philox4x32_10((uint32_t)(p / 4 + q), k0, k1);
-            uint32_t flips = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) flips |= (wd.v[e] < thr ? 1u : 0u) << (8 * e);
-            v[q] ^= flips;
-            cnt += __popc(flips);
-        }
-        *reinterpret_cast<u32x4*>(cout + p) = v;
-    }
-    for (long long j = (long long)blockIdx.x * 256 + tid; j < sp.bytes; j += (long long)gridDim.x * 256) {
-        const long long i = span_byte_index(sp, j);
-        const Words4 wd = philox4x32_10((uint32_t)(i / 4), k0, k1);
-        const int e = (int)(i & 3);                                          // (selects: a dynamic index would put the words in LDS)
-        const uint32_t word = e == 0 ? wd.v[0] : e == 1 ? wd.v[1] : e == 2 ? wd.v[2] : wd.v[3];
-        const uint8_t flip = word < thr ? 1 : 0;
-        cout[i] = cin[i] ^ flip;
-        cnt += flip;
-    }
-    add_changes(cnt, changes + nn, tid);
+    const int nn = blockIdx.y;
+    embed_span(LsbrRule{SeedKey(seeds[nn]), thresholds[nn]}, cover + (size_t)nn * hw, stego + (size_t)nn * hw, hw, changes + nn);
 }
 
 // K28.  LSBRS: the message occupies the first m pixels of the path over the whole plane (row by row, left to right; rows from the top,
@@ -313,7 +303,9 @@ __global__ __launch_bounds__(256) void embed_lsbr_seq_kernel(const uint8_t* __re
 // K30.  LSBRK: the message occupies the pixels a stego key selects, the same in every image: pixel i is used iff word i % 4 of counter
 // (i / 4, 0, 0, 0) under the key is below `thr` (floor(alpha * 2^32), up to 2^32: 64-bit comparison); a used pixel flips as under K23 at
 // alpha = 1 with the image's own seed.  A quad without a used pixel costs one generator call, not two.  MASK: the used positions
-// themselves (1 / 0), one plane, no cover.  (below_bytes, word_of: wsu_philox.h.)
+// themselves (1 / 0), one plane, no cover, no change count.  Written as rules of embed_span, K28 and this kernel compiled to all but the
+// same instructions and yet measured slower than before (K28 3.4 % on average, K30 up to 4.7 % in single runs, profiles/r33), so both
+// keep their own loops over image_span.
 template <bool MASK>
 __global__ __launch_bounds__(256) void embed_lsbr_keyed_kernel(const uint8_t* __restrict__ cover, const uint64_t* __restrict__ seeds,
                                                                uint64_t key, uint64_t thr, uint8_t* __restrict__ stego,
@@ -393,23 +385,13 @@ __global__ __launch_bounds__(256) void embed_threshold_lsbr_kernel(const uint8_t
     add_changes(cnt, changes + nn, tid);
 }
 
-int embed_blocks(long long hw) {
-    const long long b = (hw / 16 + 255) / 256;
-    return (int)(b < 1 ? 1 : b > EMB_MAX_BLOCKS ? EMB_MAX_BLOCKS : b);
-}
-
 }  // namespace
-
-// a frame's pixel count must fit the 32-bit histogram counters and Philox's 32-bit counter word (4 pixels each)
-#define EMBED_REQUIRE_SHAPE(what)                                                                                     \
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, what ": bad shape n=%d h=%d w=%d", n, h, w);                 \
-    WSU_REQUIRE((long long)h * w < (1LL << 32), what ": %lld pixels per image exceed the 32-bit counters", (long long)h * w)
 
 extern "C" {
 
 int wsu_hill_cost_f64(const uint8_t* x_u8, double* key, double clamp, int n, int h, int w, void* stream) {
     WSU_REQUIRE(x_u8 && key, "hill_cost_f64: null pointer");
-    EMBED_REQUIRE_SHAPE("hill_cost_f64");
+    WSU_REQUIRE_SHAPE("hill_cost_f64", WSU_COUNTER_PIXELS, "counters");
     WSU_REQUIRE(clamp > 0.0 && clamp < __builtin_inf(), "hill_cost_f64: clamp=%g must be positive and finite", clamp);
     const int vec_in = (w % 16 == 0) && ((uintptr_t)x_u8 % 16 == 0);
     const int vec_out = (w % 2 == 0) && ((uintptr_t)key % 16 == 0);
@@ -425,7 +407,7 @@ size_t wsu_rank_select_f64_workspace_bytes(int n) {
 int wsu_rank_select_f64(const double* key, const long long* k, uint64_t* bits, void* workspace, size_t workspace_bytes,
                         int n, int h, int w, void* stream) {
     WSU_REQUIRE(key && k && bits && workspace, "rank_select_f64: null pointer");
-    EMBED_REQUIRE_SHAPE("rank_select_f64");
+    WSU_REQUIRE_SHAPE("rank_select_f64", WSU_COUNTER_PIXELS, "counters");
     WSU_REQUIRE(workspace_bytes >= wsu_rank_select_f64_workspace_bytes(n), "rank_select_f64: workspace too small");
     WSU_REQUIRE((uintptr_t)workspace % 8 == 0, "rank_select_f64: workspace must be 8-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -446,13 +428,9 @@ int wsu_rank_select_f64(const double* key, const long long* k, uint64_t* bits, v
 int wsu_embed_threshold(const uint8_t* cover, const double* key, const uint64_t* bits, uint8_t* stego, long long* changes,
                         int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && key && bits && stego && changes, "embed_threshold: null pointer");
-    EMBED_REQUIRE_SHAPE("embed_threshold");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long hw = (long long)h * w;
-    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_threshold memset");
-    hipLaunchKernelGGL(embed_threshold_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, reinterpret_cast<const uint64_t*>(key),
-                       bits, stego, changes, hw);
-    return wsu_check_launch("embed_threshold_kernel");
+    WSU_REQUIRE_SHAPE("embed_threshold", WSU_COUNTER_PIXELS, "counters");
+    return embed_launch("embed_threshold memset", "embed_threshold_kernel", embed_threshold_kernel, changes, n, h, w, stream, cover,
+                        reinterpret_cast<const uint64_t*>(key), bits, stego, changes, (long long)h * w);
 }
 
 int wsu_lsbr_threshold(double alpha, uint32_t* threshold) {
@@ -465,56 +443,43 @@ int wsu_lsbr_threshold(double alpha, uint32_t* threshold) {
 int wsu_embed_lsbr(const uint8_t* cover, const uint64_t* seeds, const uint32_t* thresholds, uint8_t* stego, long long* changes,
                    int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && seeds && thresholds && stego && changes, "embed_lsbr: null pointer");
-    EMBED_REQUIRE_SHAPE("embed_lsbr");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long hw = (long long)h * w;
-    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbr memset");
-    hipLaunchKernelGGL(embed_lsbr_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, thresholds, stego, changes, hw);
-    return wsu_check_launch("embed_lsbr_kernel");
+    WSU_REQUIRE_SHAPE("embed_lsbr", WSU_COUNTER_PIXELS, "counters");
+    return embed_launch("embed_lsbr memset", "embed_lsbr_kernel", embed_lsbr_kernel, changes, n, h, w, stream, cover, seeds, thresholds, stego,
+                        changes, (long long)h * w);
 }
 
 int wsu_embed_lsbr_seq(const uint8_t* cover, const uint64_t* seeds, const long long* counts, int order, uint8_t* stego, long long* changes,
                        int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && seeds && counts && stego && changes, "embed_lsbr_seq: null pointer");
     WSU_REQUIRE(order == 0 || order == 1, "embed_lsbr_seq: order=%d outside {0 = rows from the top, 1 = rows from the bottom}", order);
-    EMBED_REQUIRE_SHAPE("embed_lsbr_seq");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long hw = (long long)h * w;
-    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbr_seq memset");
-    hipLaunchKernelGGL(embed_lsbr_seq_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, counts, order, stego, changes, hw, w);
-    return wsu_check_launch("embed_lsbr_seq_kernel");
+    WSU_REQUIRE_SHAPE("embed_lsbr_seq", WSU_COUNTER_PIXELS, "counters");
+    return embed_launch("embed_lsbr_seq memset", "embed_lsbr_seq_kernel", embed_lsbr_seq_kernel, changes, n, h, w, stream, cover, seeds, counts,
+                        order, stego, changes, (long long)h * w, w);
 }
 
 int wsu_embed_lsbr_keyed(const uint8_t* cover, const uint64_t* seeds, uint64_t key_seed, uint64_t alpha_threshold, uint8_t* stego,
                          long long* changes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && seeds && stego && changes, "embed_lsbr_keyed: null pointer");
     WSU_REQUIRE(alpha_threshold <= (1ull << 32), "embed_lsbr_keyed: alpha_threshold=%llu above 2^32", (unsigned long long)alpha_threshold);
-    EMBED_REQUIRE_SHAPE("embed_lsbr_keyed");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long hw = (long long)h * w;
-    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbr_keyed memset");
-    hipLaunchKernelGGL(embed_lsbr_keyed_kernel<false>, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, seeds, key_seed, alpha_threshold, stego,
-                       changes, hw);
-    return wsu_check_launch("embed_lsbr_keyed_kernel");
+    WSU_REQUIRE_SHAPE("embed_lsbr_keyed", WSU_COUNTER_PIXELS, "counters");
+    return embed_launch("embed_lsbr_keyed memset", "embed_lsbr_keyed_kernel", embed_lsbr_keyed_kernel<false>, changes, n, h, w, stream, cover,
+                        seeds, key_seed, alpha_threshold, stego, changes, (long long)h * w);
 }
 
 int wsu_embed_threshold_lsbr(const uint8_t* cover, const double* key, const uint64_t* bits, const uint64_t* seeds, uint8_t* stego,
                              long long* changes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && key && bits && seeds && stego && changes, "embed_threshold_lsbr: null pointer");
-    EMBED_REQUIRE_SHAPE("embed_threshold_lsbr");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long hw = (long long)h * w;
-    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_threshold_lsbr memset");
-    hipLaunchKernelGGL(embed_threshold_lsbr_kernel, dim3(embed_blocks(hw), n), dim3(256), 0, s, cover, reinterpret_cast<const uint64_t*>(key),
-                       bits, seeds, stego, changes, hw);
-    return wsu_check_launch("embed_threshold_lsbr_kernel");
+    WSU_REQUIRE_SHAPE("embed_threshold_lsbr", WSU_COUNTER_PIXELS, "counters");
+    return embed_launch("embed_threshold_lsbr memset", "embed_threshold_lsbr_kernel", embed_threshold_lsbr_kernel, changes, n, h, w, stream,
+                        cover, reinterpret_cast<const uint64_t*>(key), bits, seeds, stego, changes, (long long)h * w);
 }
 
+// (no change counters to zero: the launch is written out)
 int wsu_lsbr_key_mask(uint64_t key_seed, uint64_t alpha_threshold, uint8_t* mask, int h, int w, void* stream) {
     const int n = 1;
     WSU_REQUIRE(mask, "lsbr_key_mask: null pointer");
     WSU_REQUIRE(alpha_threshold <= (1ull << 32), "lsbr_key_mask: alpha_threshold=%llu above 2^32", (unsigned long long)alpha_threshold);
-    EMBED_REQUIRE_SHAPE("lsbr_key_mask");
+    WSU_REQUIRE_SHAPE("lsbr_key_mask", WSU_COUNTER_PIXELS, "counters");
     const long long hw = (long long)h * w;
     hipLaunchKernelGGL(embed_lsbr_keyed_kernel<true>, dim3(embed_blocks(hw), 1), dim3(256), 0, static_cast<hipStream_t>(stream), nullptr, nullptr,
                        key_seed, alpha_threshold, mask, nullptr, hw);

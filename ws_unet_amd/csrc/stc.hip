@@ -289,10 +289,7 @@ int stc_embed_launch(const uint8_t* cover, const double* rho, const uint8_t* mes
 
 }  // namespace
 
-// path entries are int32 and the products (j + 1) * k stay below 2^62
-#define STC_REQUIRE_SHAPE(what)                                                                                       \
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, what ": bad shape n=%d h=%d w=%d", n, h, w);                 \
-    WSU_REQUIRE((long long)h * w < (1LL << 31), what ": %lld pixels per image exceed the 32-bit path", (long long)h * w)
+// (shapes: WSU_PATH_PIXELS, so path entries are int32 and the products (j + 1) * k stay below 2^62)
 #define STC_REQUIRE_HEIGHT(what)                                                                                      \
     WSU_REQUIRE(height >= 1 && height <= STC_MAX_H, what ": constraint height %d outside 1..%d", height, STC_MAX_H)
 #define STC_REQUIRE_CODE(what)                                                                                        \
@@ -310,8 +307,7 @@ extern "C" {
 
 int wsu_philox_words(const uint64_t* seeds, uint32_t* words, int n, int h, int w, void* stream) {
     WSU_REQUIRE(seeds && words, "philox_words: null pointer");
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, "philox_words: bad shape n=%d h=%d w=%d", n, h, w);
-    WSU_REQUIRE((long long)h * w < (1LL << 32), "philox_words: %lld pixels per image exceed the 32-bit counters", (long long)h * w);
+    WSU_REQUIRE_SHAPE("philox_words", WSU_COUNTER_PIXELS, "counters");
     const long long hw = (long long)h * w, blocks = (hw / 4 + 255) / 256;
     hipLaunchKernelGGL(philox_words_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 256 ? 256 : blocks), n), dim3(256), 0,
                        static_cast<hipStream_t>(stream), seeds, words, hw);
@@ -327,7 +323,7 @@ int wsu_stc_embed(const uint8_t* cover, const double* rho, const uint8_t* messag
                   const uint64_t* seeds, int change, int height, int k, int phases, uint8_t* stego, double* cost, long long* changes,
                   uint8_t* ok, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && rho && message && cols && seeds && stego && cost && changes && ok && workspace, "stc_embed: null pointer");
-    STC_REQUIRE_SHAPE("stc_embed");
+    WSU_REQUIRE_SHAPE("stc_embed", WSU_PATH_PIXELS, "path");
     STC_REQUIRE_CODE("stc_embed");
     WSU_REQUIRE(change == 0 || change == 1, "stc_embed: change=%d is neither 0 (flip) nor 1 (pm1)", change);
     WSU_REQUIRE(phases >= 1 && phases <= 3, "stc_embed: phases=%d outside 1..3 (1 forward, 2 backward, 3 both)", phases);
@@ -341,7 +337,7 @@ int wsu_stc_embed(const uint8_t* cover, const double* rho, const uint8_t* messag
 int wsu_stc_extract(const uint8_t* stego, const uint32_t* cols, const int32_t* path, int height, int k, uint8_t* message, int n, int h,
                     int w, void* stream) {
     WSU_REQUIRE(stego && cols && message, "stc_extract: null pointer");
-    STC_REQUIRE_SHAPE("stc_extract");
+    WSU_REQUIRE_SHAPE("stc_extract", WSU_PATH_PIXELS, "path");
     STC_REQUIRE_CODE("stc_extract");
     hipLaunchKernelGGL(stc_extract_kernel, dim3((unsigned)((k + 255) / 256), n), dim3(256), 0, static_cast<hipStream_t>(stream), stego, cols,
                        path, message, (long long)h * w, k, height, 0, StcRagged{nullptr, nullptr, 0, 0, 0});
@@ -353,7 +349,7 @@ int wsu_stc_embed_ragged(const uint8_t* cover, const double* rho, const uint8_t*
                          int change, int height, uint8_t* stego, double* cost, long long* changes, uint8_t* ok, void* workspace,
                          size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && rho && message && cols && seeds && stego && cost && changes && ok && workspace, "stc_embed_ragged: null pointer");
-    STC_REQUIRE_SHAPE("stc_embed_ragged");
+    WSU_REQUIRE_SHAPE("stc_embed_ragged", WSU_PATH_PIXELS, "path");
     STC_REQUIRE_HEIGHT("stc_embed_ragged");
     STC_REQUIRE_RAGGED("stc_embed_ragged");
     WSU_REQUIRE(change == 0 || change == 1, "stc_embed_ragged: change=%d is neither 0 (flip) nor 1 (pm1)", change);
@@ -368,7 +364,7 @@ int wsu_stc_extract_ragged(const uint8_t* stego, const uint32_t* cols, int cols_
                            const int32_t* ks, const int32_t* first, int max_bits, uint8_t* message, long long message_stride, int n, int h,
                            int w, void* stream) {
     WSU_REQUIRE(stego && cols && message, "stc_extract_ragged: null pointer");
-    STC_REQUIRE_SHAPE("stc_extract_ragged");
+    WSU_REQUIRE_SHAPE("stc_extract_ragged", WSU_PATH_PIXELS, "path");
     STC_REQUIRE_HEIGHT("stc_extract_ragged");
     STC_REQUIRE_RAGGED("stc_extract_ragged");
     WSU_REQUIRE(bit >= 0 && bit <= 7, "stc_extract_ragged: bit=%d outside 0..7", bit);

@@ -158,11 +158,6 @@ __global__ __launch_bounds__(64) void stc_layer_compose_finish_kernel(const doub
 
 }  // namespace
 
-// the planes feed K43, whose paths are int32
-#define SL_REQUIRE_SHAPE(what)                                                                                        \
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, what ": bad shape n=%d h=%d w=%d", n, h, w);                 \
-    WSU_REQUIRE((long long)h * w < (1LL << 31), what ": %lld pixels per image exceed the 32-bit path", (long long)h * w)
-
 extern "C" {
 
 size_t wsu_stc_layer_workspace_bytes(int n) { return n > 0 ? (size_t)n * SL_PARTS * (sizeof(double) + sizeof(long long)) : 0; }
@@ -170,7 +165,7 @@ size_t wsu_stc_layer_workspace_bytes(int n) { return n > 0 ? (size_t)n * SL_PART
 int wsu_stc_layer_high(const uint8_t* x_u8, const double* rho, const double* lambdas, uint8_t* u1, double* rho1, double* entropy,
                        void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(x_u8 && rho && lambdas && u1 && rho1 && entropy && workspace, "stc_layer_high: null pointer");
-    SL_REQUIRE_SHAPE("stc_layer_high");
+    WSU_REQUIRE_SHAPE("stc_layer_high", WSU_PATH_PIXELS, "path");       // (the planes feed K43, whose paths are int32)
     WSU_REQUIRE(workspace_bytes >= wsu_stc_layer_workspace_bytes(n), "stc_layer_high: workspace too small");
     WSU_REQUIRE((uintptr_t)workspace % 8 == 0, "stc_layer_high: workspace must be 8-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -185,7 +180,7 @@ int wsu_stc_layer_high(const uint8_t* x_u8, const double* rho, const double* lam
 int wsu_stc_layer_low(const uint8_t* x_u8, const double* rho, const double* lambdas, const uint8_t* y1, const int32_t* k1, uint8_t* u0,
                       double* rho0, int n, int h, int w, void* stream) {
     WSU_REQUIRE(x_u8 && rho && lambdas && y1 && k1 && u0 && rho0, "stc_layer_low: null pointer");
-    SL_REQUIRE_SHAPE("stc_layer_low");
+    WSU_REQUIRE_SHAPE("stc_layer_low", WSU_PATH_PIXELS, "path");
     hipLaunchKernelGGL(stc_layer_low_kernel, dim3(SL_PARTS, n), dim3(256), 0, static_cast<hipStream_t>(stream), x_u8, rho, lambdas, y1, k1, u0,
                        rho0, (long long)h * w);
     return wsu_check_launch("stc_layer_low_kernel");
@@ -196,7 +191,7 @@ int wsu_stc_layer_compose(const uint8_t* cover, const double* rho, const uint8_t
                           void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && rho && y1 && y0 && k1 && ok1 && ok0 && stego && changes && distortion && ok && workspace,
                 "stc_layer_compose: null pointer");
-    SL_REQUIRE_SHAPE("stc_layer_compose");
+    WSU_REQUIRE_SHAPE("stc_layer_compose", WSU_PATH_PIXELS, "path");
     WSU_REQUIRE(workspace_bytes >= wsu_stc_layer_workspace_bytes(n), "stc_layer_compose: workspace too small");
     WSU_REQUIRE((uintptr_t)workspace % 8 == 0, "stc_layer_compose: workspace must be 8-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -9,6 +9,7 @@
 //        u < T+ : x + 1;   T+ <= u < T+ + T- : x - 1;   else x.   T+ + T- <= 2/3 * 2^32: the sum fits 32 bits.
 //   K39  the same draw with constant thresholds: T+ = T- = T inside the range, (2T, 0) at x == 0, (0, 2T) at x == 255, T = floor(alpha / 4 * 2^32).
 //
+// K38 and K39 are one rule (Pm1Rule) of the simulators' pixel loop, embed_span of wsu_embed.h, which also owns the launch set-up.
 // A wet direction has threshold 0, so no byte leaves 0..255 and the changes are added to four packed bytes at once without a carry between
 // them; nothing is clamped.  float64 operations are plain operators in the order above (contract(off): lambda * rho is a multiply of its own
 // that feeds exp).  K37 sums in a fixed order: pixel i of an image belongs to workgroup (i / 256) % TE_PARTS, thread i % 256; a thread adds
@@ -16,13 +17,13 @@
 // depend on (x, rho, lambda, H*W) alone: not on the run, the batch size or the image's place in the batch.
 #pragma clang fp contract(off)
 #include "wsu_metric.h"
+#include "wsu_embed.h"
 #include "wsu_philox.h"
 
 namespace {
 
 constexpr int TE_PARTS = 64;           // K37 workgroups per image
 constexpr int TE_MAXL = 16;            // K37 multipliers per launch, at most
-constexpr int PM_MAX_BLOCKS = 64;      // K38 / K39 workgroups per image, at most
 constexpr double LN2 = 0.693147180559945309417232121458;
 constexpr double TWO32 = 4294967296.0;
 
@@ -76,8 +77,7 @@ __global__ __launch_bounds__(64) void ternary_entropy_finish_kernel(const double
     entropy[(size_t)nn * nl + l] = s;
 }
 
-// ---- K38 / K39 ------------------------------------------------------------------------------------------------------------
-// (image_span, span_byte_index, add_changes: wsu_metric.h, as K22 / K23 use them.)
+// ---- K38 / K39: a rule of embed_span ------------------------------------------------------------------------------------------------------
 // the two thresholds of a pixel of value x.  LSBM: thr = T, `c` unused; else lam * c is the pixel's a.
 template <bool LSBM> __device__ __forceinline__ void pm1_thresholds(uint8_t x, double lam, double c, uint32_t thr, uint32_t& tp, uint32_t& tm) {
     if (LSBM) {
@@ -93,66 +93,54 @@ template <bool LSBM> __device__ __forceinline__ void pm1_thresholds(uint8_t x, d
         tm = (uint32_t)(pm * TWO32);
     }
 }
-// +1 / -1 / 0 for the draw u
-__device__ __forceinline__ int pm1_draw(uint32_t u, uint32_t tp, uint32_t tm) { return u < tp ? 1 : u - tp < tm ? -1 : 0; }
 
+// The image's state: seed halves, lambda with the cost row (K38) or the constant threshold (K39, no cost is read).
+template <bool LSBM> struct Pm1Rule {
+    SeedKey k;
+    uint32_t thr;
+    double lam;
+    const double* rin;
+    // +1 / -1 / 0 for pixel i of value x under the draw u
+    __device__ __forceinline__ int draw(long long i, uint8_t x, uint32_t u) const {
+        uint32_t tp, tm;
+        pm1_thresholds<LSBM>(x, lam, LSBM ? 0.0 : rin[i], thr, tp, tm);
+        return u < tp ? 1 : u - tp < tm ? -1 : 0;
+    }
+    __device__ __forceinline__ uint32_t quad(long long i0, uint32_t x, int& cnt) const {
+        const Words4 wd = philox_quad(i0, k);
+        uint32_t up = 0, dn = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int d = draw(i0 + e, (uint8_t)(x >> (8 * e)), wd.v[e]);
+            up |= (d > 0 ? 1u : 0u) << (8 * e);
+            dn |= (d < 0 ? 1u : 0u) << (8 * e);
+        }
+        cnt += __popc(up | dn);
+        return x + up - dn;                                                  // no byte carries: a wet direction is never drawn
+    }
+    __device__ __forceinline__ uint8_t byte(long long i, uint8_t x, int& cnt) const {
+        const int d = draw(i, x, philox_byte(i, k));
+        cnt += d != 0 ? 1 : 0;
+        return (uint8_t)((int)x + d);
+    }
+};
+
+// (At most 100 SGPRs: beyond them a SIMD holds 7 waves instead of 8, and 32 planes of 512 x 512 are 8 waves per SIMD.  K39 took 106 without
+// the limit and was 1.2 % slower for it, profiles/r33.  The attribute is on the template, so K38 has it too and does not need it: it
+// takes 84.  The limit does not fail a build: a change that needs more spills SGPRs to VGPR lanes in silence.  If K39 slows down, look at
+// `make isa` for v_writelane / v_readlane in its loop and at the kernel's VGPRs in -Rpass-analysis=kernel-resource-usage: above 64 a SIMD
+// holds 7 waves again, and then the limit is better raised or dropped.)
 template <bool LSBM>
-__global__ __launch_bounds__(256) void embed_pm1_kernel(const uint8_t* __restrict__ cover, const double* __restrict__ rho,
+__global__ __attribute__((amdgpu_num_sgpr(100))) __launch_bounds__(256) void embed_pm1_kernel(const uint8_t* __restrict__ cover, const double* __restrict__ rho,
                                                         const double* __restrict__ lambdas, const uint32_t* __restrict__ thresholds,
                                                         const uint64_t* __restrict__ seeds, uint8_t* __restrict__ stego,
                                                         long long* __restrict__ changes, long long hw) {
-    const int nn = blockIdx.y, tid = threadIdx.x;
-    const uint8_t* cin = cover + (size_t)nn * hw;
-    uint8_t* cout = stego + (size_t)nn * hw;
-    const double* rin = LSBM ? nullptr : rho + (size_t)nn * hw;
-    const double lam = LSBM ? 0.0 : lambdas[nn];
-    const uint32_t thr = LSBM ? thresholds[nn] : 0u;
-    const uint32_t k0 = (uint32_t)seeds[nn], k1 = (uint32_t)(seeds[nn] >> 32);
-    const Span sp = image_span(cin, cout, hw, true);
-    int cnt = 0;
-    for (long long g = (long long)blockIdx.x * 256 + tid; g < sp.groups; g += (long long)gridDim.x * 256) {
-        const long long p = sp.head + 16 * g;                               // a multiple of 4
-        u32x4 v = *reinterpret_cast<const u32x4*>(cin + p);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const Words4 wd = philox4x32_10((uint32_t)(p / 4 + q), k0, k1);
-            uint32_t up = 0, dn = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t tp, tm;
-                pm1_thresholds<LSBM>((uint8_t)(v[q] >> (8 * e)), lam, LSBM ? 0.0 : rin[p + 4 * q + e], thr, tp, tm);
-                const int d = pm1_draw(wd.v[e], tp, tm);
-                up |= (d > 0 ? 1u : 0u) << (8 * e);
-                dn |= (d < 0 ? 1u : 0u) << (8 * e);
-            }
-            v[q] = v[q] + up - dn;                                          // no byte carries: a wet direction is never drawn
-            cnt += __popc(up | dn);
-        }
-        *reinterpret_cast<u32x4*>(cout + p) = v;
-    }
-    for (long long j = (long long)blockIdx.x * 256 + tid; j < sp.bytes; j += (long long)gridDim.x * 256) {
-        const long long i = span_byte_index(sp, j);
-        const uint8_t xv = cin[i];
-        uint32_t tp, tm;
-        pm1_thresholds<LSBM>(xv, lam, LSBM ? 0.0 : rin[i], thr, tp, tm);
-        const int d = pm1_draw(word_of(philox4x32_10((uint32_t)(i / 4), k0, k1), (int)(i & 3)), tp, tm);
-        cout[i] = (uint8_t)((int)xv + d);
-        cnt += d != 0 ? 1 : 0;
-    }
-    add_changes(cnt, changes + nn, tid);
-}
-
-int pm1_blocks(long long hw) {
-    const long long b = (hw / 16 + 255) / 256;
-    return (int)(b < 1 ? 1 : b > PM_MAX_BLOCKS ? PM_MAX_BLOCKS : b);
+    const int nn = blockIdx.y;
+    const Pm1Rule<LSBM> rule{SeedKey(seeds[nn]), LSBM ? thresholds[nn] : 0u, LSBM ? 0.0 : lambdas[nn], LSBM ? nullptr : rho + (size_t)nn * hw};
+    embed_span(rule, cover + (size_t)nn * hw, stego + (size_t)nn * hw, hw, changes + nn);
 }
 
 }  // namespace
-
-// a frame's pixel count must fit Philox's 32-bit counter word (4 pixels each), as in embed.hip
-#define PM1_REQUIRE_SHAPE(what)                                                                                       \
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, what ": bad shape n=%d h=%d w=%d", n, h, w);                 \
-    WSU_REQUIRE((long long)h * w < (1LL << 32), what ": %lld pixels per image exceed the 32-bit counters", (long long)h * w)
 
 extern "C" {
 
@@ -161,7 +149,7 @@ size_t wsu_ternary_entropy_workspace_bytes(int n) { return n > 0 ? (size_t)n * T
 int wsu_ternary_entropy(const uint8_t* x_u8, const double* rho, const double* lambdas, int l, double* entropy, void* workspace,
                         size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(x_u8 && rho && lambdas && entropy && workspace, "ternary_entropy: null pointer");
-    PM1_REQUIRE_SHAPE("ternary_entropy");
+    WSU_REQUIRE_SHAPE("ternary_entropy", WSU_COUNTER_PIXELS, "counters");
     WSU_REQUIRE(l >= 1 && l <= TE_MAXL, "ternary_entropy: l=%d multipliers outside 1..%d", l, TE_MAXL);
     WSU_REQUIRE(workspace_bytes >= wsu_ternary_entropy_workspace_bytes(n), "ternary_entropy: workspace too small");
     WSU_REQUIRE((uintptr_t)workspace % 8 == 0, "ternary_entropy: workspace must be 8-byte aligned");
@@ -177,13 +165,9 @@ int wsu_ternary_entropy(const uint8_t* x_u8, const double* rho, const double* la
 int wsu_embed_ternary(const uint8_t* cover, const double* rho, const double* lambdas, const uint64_t* seeds, uint8_t* stego,
                       long long* changes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && rho && lambdas && seeds && stego && changes, "embed_ternary: null pointer");
-    PM1_REQUIRE_SHAPE("embed_ternary");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long hw = (long long)h * w;
-    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_ternary memset");
-    hipLaunchKernelGGL(embed_pm1_kernel<false>, dim3(pm1_blocks(hw), n), dim3(256), 0, s, cover, rho, lambdas,
-                       static_cast<const uint32_t*>(nullptr), seeds, stego, changes, hw);
-    return wsu_check_launch("embed_pm1_kernel");
+    WSU_REQUIRE_SHAPE("embed_ternary", WSU_COUNTER_PIXELS, "counters");
+    return embed_launch("embed_ternary memset", "embed_pm1_kernel", embed_pm1_kernel<false>, changes, n, h, w, stream, cover, rho, lambdas,
+                        static_cast<const uint32_t*>(nullptr), seeds, stego, changes, (long long)h * w);
 }
 
 int wsu_lsbm_threshold(double alpha, uint32_t* threshold) {
@@ -196,13 +180,10 @@ int wsu_lsbm_threshold(double alpha, uint32_t* threshold) {
 int wsu_embed_lsbm(const uint8_t* cover, const uint64_t* seeds, const uint32_t* thresholds, uint8_t* stego, long long* changes,
                    int n, int h, int w, void* stream) {
     WSU_REQUIRE(cover && seeds && thresholds && stego && changes, "embed_lsbm: null pointer");
-    PM1_REQUIRE_SHAPE("embed_lsbm");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long hw = (long long)h * w;
-    if (hipMemsetAsync(changes, 0, (size_t)n * sizeof(long long), s) != hipSuccess) return wsu_check_launch("embed_lsbm memset");
-    hipLaunchKernelGGL(embed_pm1_kernel<true>, dim3(pm1_blocks(hw), n), dim3(256), 0, s, cover, static_cast<const double*>(nullptr),
-                       static_cast<const double*>(nullptr), thresholds, seeds, stego, changes, hw);
-    return wsu_check_launch("embed_pm1_kernel");
+    WSU_REQUIRE_SHAPE("embed_lsbm", WSU_COUNTER_PIXELS, "counters");
+    return embed_launch("embed_lsbm memset", "embed_pm1_kernel", embed_pm1_kernel<true>, changes, n, h, w, stream, cover,
+                        static_cast<const double*>(nullptr), static_cast<const double*>(nullptr), thresholds, seeds, stego, changes,
+                        (long long)h * w);
 }
 
 }  // extern "C"

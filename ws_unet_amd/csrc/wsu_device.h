@@ -26,6 +26,15 @@ int wsu_check_launch(const char* what);
             return WSU_ERR_ARG;           \
         }                                 \
     } while (0)
+// The shape check of an entry that takes n planes of h x w pixels (it names the caller's n, h, w): `limit` is what a plane's pixel count
+// must stay below and `noun` what overflows otherwise.
+//   WSU_COUNTER_PIXELS, "counters": the 32-bit histogram counters and Philox's 32-bit counter word (4 pixels each)
+//   WSU_PATH_PIXELS, "path":        int32 path entries (the trellis kernels and the planes that feed them)
+constexpr long long WSU_COUNTER_PIXELS = 1LL << 32;
+constexpr long long WSU_PATH_PIXELS = 1LL << 31;
+#define WSU_REQUIRE_SHAPE(what, limit, noun)                                                                           \
+    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, what ": bad shape n=%d h=%d w=%d", n, h, w);                 \
+    WSU_REQUIRE((long long)h * w < (limit), what ": %lld pixels per image exceed the 32-bit " noun, (long long)h * w)
 // a C-linkage helper called across translation units that is no part of include/wsu.h: not exported by libwsu.so
 #define WSU_INTERNAL extern "C" __attribute__((visibility("hidden")))
 // CU count of the current device, queried once per process; 0 after "<who>: cannot query the device" has been set (the caller returns WSU_ERR_HIP)

@@ -1,7 +1,7 @@
-// Device helpers shared by the metric kernels K10-K18, K27, K29, K32 and K33 and the simulators K20-K23, K28, K30, K34, K37-K39 and K45-K47 (pointwise.hip K10 + WS meter,
+// Device helpers shared by the metric kernels K10-K18, K27, K29, K32 and K33 and the simulators K20, K37, K38 and K45-K47 (pointwise.hip K10 + WS meter,
 // ws_attack.hip, ws_sequential.hip, ws_ordered.hip, ws_locate.hip, jpeg_history.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip, ternary.hip, stc_layers.hip): the one definition each of a 3x3 predictor's
 // taps, the prediction at a pixel, the float32 residual, the WS statistic's per-pixel terms, the maximum-prefix triple, the HILL cost's input window, the fixed-order
-// block sum, the simulators' pixel loops and the radix-select steps.
+// block sum, the +-1 sender's exponentials and the radix-select steps.  (The simulators' pixel loop: wsu_embed.h.)
 //
 // Rounding policy: these functions restate numpy's float32 / float64 operation sequences with PLAIN operators, one rounding each.  That
 // holds only under `#pragma clang fp contract(off)`, which is per translation unit: every including .hip file sets it BEFORE this
@@ -187,36 +187,6 @@ template <int THREADS, typename... T> __device__ __forceinline__ void block_sum(
     for (int st = THREADS / 2; st > 0; st >>= 1) {
         if (tid < st) ((rows[tid] += rows[tid + st]), ...);
         __syncthreads();
-    }
-}
-
-// ---- the pixel loops of the simulators (K22, K23, K28, K30, K38, K39) ---------------------------------------------------------------------
-// An image's pixels as `head` leading bytes, `groups` 16-byte groups whose loads and stores are aligned, and trailing bytes; `bytes` =
-// head + tail.  Input and output must share their alignment, else every pixel is a byte; quad: a group must start at a multiple of 4
-// pixels (K23: one generator call serves pixels 4g .. 4g+3).
-struct Span { long long head, groups, bytes; };
-__device__ __forceinline__ Span image_span(const uint8_t* in, const uint8_t* out, long long hw, bool quad) {
-    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-    long long head = hw;
-    if (((a ^ b) & 15) == 0) {
-        const long long hd = (long long)((16 - (a & 15)) & 15);
-        if (hd <= hw && (!quad || hd % 4 == 0)) head = hd;
-    }
-    const long long groups = (hw - head) / 16;
-    return Span{head, groups, hw - 16 * groups};
-}
-__device__ __forceinline__ long long span_byte_index(const Span& sp, long long j) { return j < sp.head ? j : j + 16 * sp.groups; }
-
-// this thread's count -> one integer atomic per workgroup (wave reduction, then the four wave sums)
-__device__ __forceinline__ void add_changes(int cnt, long long* __restrict__ dst, int tid) {
-    __shared__ int wsum[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((tid & 63) == 0) wsum[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (total) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)total);
     }
 }
 

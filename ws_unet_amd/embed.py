@@ -30,6 +30,7 @@ alpha = 1 with the image's seed.  So about alpha / 2 of the pixels change, all a
 from __future__ import annotations
 
 import argparse
+import math
 import pathlib
 import typing
 
@@ -91,14 +92,59 @@ def _check_order(order) -> str:
     return order
 
 
-def _alphas(alpha, n: int) -> np.ndarray:
+# ---- what the four drivers (embed, embed_pm1, stc, stc_ml) check alike ---------------------------------------------------------------------
+
+def planes_shape(who: str, t, name: str = "cover_u8") -> typing.Tuple[int, int, int]:
+    """(N, H, W) of a batch of planes, which must be an (N,H,W) uint8 tensor."""
+    if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.uint8):
+        raise ValueError(f"{who}: {name} must be an (N,H,W) uint8 tensor")
+    return tuple(t.shape)
+
+
+def seeds_tensor(who: str, seeds, n: int, dev, method: typing.Optional[str] = None) -> torch.Tensor:
+    """One 64-bit seed per image (a list, an array or a tensor of integers, taken modulo 2^64) -> (N) int64 on `dev` holding them.
+    method: the simulator that asks, for the message about missing seeds."""
+    if seeds is None:
+        raise ValueError(f"{who}: {method!r} needs one seed per image (embed.image_seed)" if method else
+                         f"{who}: one seed per image is needed (embed.image_seed)")
+    s = np.array([int(v) % 2 ** 64 for v in (seeds.tolist() if isinstance(seeds, (torch.Tensor, np.ndarray)) else seeds)], dtype=np.uint64)
+    if s.shape != (n,):
+        raise ValueError(f"{who}: {s.shape[0] if s.ndim else 1} seeds for {n} images")
+    return torch.from_numpy(s.view(np.int64)).to(dev)
+
+
+# the payload ranges of the methods, by the name an error message gives them: (0 excluded, the upper end, the upper end excluded)
+ALPHA_RANGES = {"[0, 1]": (False, 1.0, False), "[0, log2 3)": (False, math.log2(3.0), True),
+                "(0, 1]": (True, 1.0, False), "(0, log2 3)": (True, math.log2(3.0), True)}
+
+
+def alpha_values(alpha, within: str, n: typing.Optional[int] = None, who: str = "", whose: str = "") -> np.ndarray:
+    """alpha, a scalar or a sequence, as float64 values inside the range `within` of ALPHA_RANGES: one per image of a batch of n (a scalar
+    serves all), or, with n None, the values as given.  The error reads `<who>alpha outside <within><whose>: <alpha>`."""
     a = np.asarray(alpha, dtype=np.float64)
-    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
-        raise ValueError(f"alpha must be a scalar or one value per image ({n}), got shape {a.shape}")
-    a = np.broadcast_to(a, (n,))
-    if not np.all((a >= 0) & (a <= 1)):
-        raise ValueError(f"alpha outside [0, 1]: {alpha!r}")
+    if n is None:
+        a = np.atleast_1d(a)
+    else:
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+            raise ValueError(f"alpha must be a scalar or one value per image ({n}), got shape {a.shape}")
+        a = np.broadcast_to(a, (n,))
+    open_low, top, open_top = ALPHA_RANGES[within]
+    if not np.all(((a > 0) if open_low else (a >= 0)) & ((a < top) if open_top else (a <= top))):
+        raise ValueError(f"{who}alpha outside {within}{whose}: {alpha!r}")
     return a
+
+
+def payload_list(within: str, alphas, message: typing.Optional[bytes] = None, with_message: bool = False, whose: str = "") -> typing.List:
+    """The payloads of one write_dataset call: floats inside `within`, or, where the method embeds real messages (with_message), one
+    bytes object given instead of them."""
+    if with_message:
+        if (alphas is None) == (message is None):
+            raise ValueError("give either alpha(s) or a message, not both and not neither")
+        if message is not None:
+            if len(bytes(message)) < 1:
+                raise ValueError("the message is empty")
+            return [bytes(message)]
+    return [float(a) for a in alpha_values(alphas, within, whose=whose)]
 
 
 def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, key: typing.Optional[torch.Tensor] = None,
@@ -112,49 +158,68 @@ def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds=None, *, ke
     method = method_name(stego_method)
     _check_order(order)
     placement_key = _check_placement_key(method, placement_key)
-    if not (isinstance(cover_u8, torch.Tensor) and cover_u8.dim() == 3 and cover_u8.dtype == torch.uint8):
-        raise ValueError("simulate: cover_u8 must be an (N,H,W) uint8 tensor")
-    n, h, w = cover_u8.shape
-    a = _alphas(alpha, n)
+    n, h, w = planes_shape("simulate", cover_u8)
+    a = alpha_values(alpha, "[0, 1]", n)
     dev = cover_u8.device
     if method == "HILLR":
         if key is None:
             key = ops.hill_cost_f64(cover_u8)
         k = torch.tensor([hillr_rank(v, h, w) for v in a], dtype=torch.int64).to(dev)
         return ops.embed_threshold(cover_u8, key, ops.rank_select_f64(key, k))
-    if seeds is None:
-        raise ValueError(f"simulate: {method!r} needs one seed per image (embed.image_seed)")
-    s = np.array([int(v) % 2 ** 64 for v in (seeds.tolist() if isinstance(seeds, (torch.Tensor, np.ndarray)) else seeds)], dtype=np.uint64)
-    if s.shape != (n,):
-        raise ValueError(f"simulate: {s.shape[0] if s.ndim else 1} seeds for {n} images")
+    s = seeds_tensor("simulate", seeds, n, dev, method)
     if method == "HILLRM":
         if key is None:
             key = ops.hill_cost_f64(cover_u8)
         k = torch.tensor([hillrm_rank(v, h, w) for v in a], dtype=torch.int64).to(dev)
-        return ops.embed_threshold_lsbr(cover_u8, key, ops.rank_select_f64(key, k), torch.from_numpy(s.view(np.int64)).to(dev))
+        return ops.embed_threshold_lsbr(cover_u8, key, ops.rank_select_f64(key, k), s)
     if method == "LSBRK":
         if not np.all(a == a[0]):
             raise ValueError(f"simulate: 'LSBRK' takes one alpha for all images (one key selects one set of pixels), got {alpha!r}")
-        return ops.embed_lsbr_keyed(cover_u8, torch.from_numpy(s.view(np.int64)).to(dev), placement_key, ops.lsbr_key_threshold(a[0]))
+        return ops.embed_lsbr_keyed(cover_u8, s, placement_key, ops.lsbr_key_threshold(a[0]))
     if method == "LSBRS":
         m = torch.tensor([lsbrs_count(v, h, w) for v in a], dtype=torch.int64).to(dev)
-        return ops.embed_lsbr_seq(cover_u8, torch.from_numpy(s.view(np.int64)).to(dev), m, order)
+        return ops.embed_lsbr_seq(cover_u8, s, m, order)
     t = np.array([ops.lsbr_threshold(v) for v in a], dtype=np.uint32)
-    return ops.embed_lsbr(cover_u8, torch.from_numpy(s.view(np.int64)).to(dev), torch.from_numpy(t.view(np.int32)).to(dev))
+    return ops.embed_lsbr(cover_u8, s, torch.from_numpy(t.view(np.int32)).to(dev))
 
 
-# ---- whole data sets --------------------------------------------------------------------------------------------------------
+# ---- whole data sets: the twin writer and reader of the four drivers ------------------------------------------------------------------------
+
+CSV_COLUMNS = ("name", "height", "width", "stego_method", "alpha")      # of every twin folder's files.csv; a method may add its own
+
+
+def twin_folder(method: str, alpha: float, suffix: str = "") -> str:
+    """`stego_<METHOD>_alpha_<a><suffix>_independent_images`: the reference's folder scheme with the method in upper case, as its
+    files.csv spells it (the reference's own folders say 'HILLr' / 'LSBr' beside 'HILLR' / 'LSBR' in the name column; that mismatch is
+    not copied)."""
+    return f"stego_{method}_alpha_{float(alpha)}{suffix}_independent_images"
+
 
 def folder_name(stego_method: str, alpha: float, order: str = "rows", placement_key: typing.Optional[int] = None) -> str:
-    """`stego_<METHOD>_alpha_<a>_independent_images`: the reference's folder scheme with the method in upper case, as its files.csv
-    spells it (the reference's own folders say 'HILLr' / 'LSBr' beside 'HILLR' / 'LSBR' in the name column; that mismatch is not copied).
-    The bottom-up twins of 'LSBRS' (order 'rows_up') go to `stego_LSBRS_alpha_<a>_rows_up_independent_images`, the twins of 'LSBRK' under
-    the stego key K to `stego_LSBRK_alpha_<a>_key_<K>_independent_images`."""
+    """twin_folder for this module's methods.  The bottom-up twins of 'LSBRS' (order 'rows_up') go to
+    `stego_LSBRS_alpha_<a>_rows_up_independent_images`, the twins of 'LSBRK' under the stego key K to
+    `stego_LSBRK_alpha_<a>_key_<K>_independent_images`."""
     method = method_name(stego_method)
-    suffix = "_rows_up" if method == "LSBRS" and _check_order(order) == "rows_up" else ""
+    return twin_folder(method, alpha, _folder_suffix(method, order, placement_key))
+
+
+def _folder_suffix(method: str, order: str, placement_key) -> str:
     if method == "LSBRK":
-        suffix = f"_key_{_check_placement_key(method, placement_key)}"
-    return f"stego_{method}_alpha_{float(alpha)}{suffix}_independent_images"
+        return f"_key_{_check_placement_key(method, placement_key)}"
+    return "_rows_up" if method == "LSBRS" and _check_order(order) == "rows_up" else ""
+
+
+def bits_from_bytes(data: bytes) -> np.ndarray:
+    """bytes -> their bits as uint8 0 / 1, the most significant bit of each byte first."""
+    return np.unpackbits(np.frombuffer(bytes(data), dtype=np.uint8))
+
+
+def bytes_from_bits(bits) -> bytes:
+    """The inverse of bits_from_bytes; a trailing group of fewer than 8 bits is dropped."""
+    b = np.asarray(bits, dtype=np.uint8).reshape(-1)
+    if b.size and b.max() > 1:
+        raise ValueError("bytes_from_bits: bits must be 0 / 1")
+    return np.packbits(b[:b.size // 8 * 8]).tobytes()
 
 
 def _prefetch(fnames, kws):
@@ -162,51 +227,104 @@ def _prefetch(fnames, kws):
     return (read_luma_batch(fnames),)
 
 
-def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, order="rows", placement_key=None, prefetched=None):
-    """One chunk of covers -> their twins at every alpha, written as 8-bit gray PNGs; one list of files.csv rows per cover."""
+def _write_chunk(fnames, kws, *, method, payloads, stream, out_dir, make, prepare=None, suffix="", prefetched=None):
+    """One chunk of covers -> their twins at every payload, written as 8-bit gray PNGs; one list of files.csv rows per cover.  What the
+    method does is two callables: prepare(cover) -> what it makes once per chunk (its cost map; None: nothing) and make(cover, payload,
+    seeds, prepared) -> (stego (N,H,W) uint8 on the device, {column: one value per image} for columns beyond CSV_COLUMNS).  A payload is
+    an alpha, or a bytes message: make then gets its bits as an (N, bits) uint8 tensor, and alpha is bits per pixel.  A ValueError of
+    make names the batch's files."""
     from PIL import Image
-    from . import ops
     planes = prefetched[0] if prefetched is not None else _prefetch(fnames, kws)[0]
     cover = torch.from_numpy(np.ascontiguousarray(planes)).to("cuda")
-    method = method_name(stego_method)
-    key = ops.hill_cost_f64(cover) if method in ("HILLR", "HILLRM") else None
-    seeds = [image_seed(f, stream) for f in fnames] if method != "HILLR" else None
+    n, hh, ww = cover.shape
+    prepared = prepare(cover) if prepare is not None else None
+    seeds = [image_seed(f, stream) for f in fnames]
     rows = [[] for _ in fnames]
-    for a in alphas:
-        stego = simulate(cover, method, a, seeds, key=key, order=order, placement_key=placement_key)[0].cpu().numpy()
-        folder = folder_name(method, a, order, placement_key)
+    for p in payloads:
+        a = p
+        if isinstance(p, bytes):
+            bits = bits_from_bytes(p)
+            if bits.size > hh * ww:
+                raise ValueError(f"the message has {bits.size} bits, the images {hh * ww} pixels")
+            p, a = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(bits, (n, bits.size)))), bits.size / (hh * ww)
+        try:
+            stego, extra = make(cover, p, seeds, prepared)
+        except ValueError as e:
+            raise ValueError(f"{e} (the batch: {[pathlib.Path(f).name for f in fnames]})") from e
+        stego = stego.cpu().numpy()
+        folder = twin_folder(method, a, suffix)
         (pathlib.Path(out_dir) / folder).mkdir(parents=True, exist_ok=True)
         for i, f in enumerate(fnames):
             name = f"{folder}/{pathlib.Path(f).stem}.png"
             Image.fromarray(stego[i]).save(pathlib.Path(out_dir) / name)
-            rows[i].append({"name": name, "height": stego.shape[1], "width": stego.shape[2], "stego_method": method, "alpha": float(a)})
+            rows[i].append({"name": name, "height": hh, "width": ww, "stego_method": method, "alpha": float(a),
+                            **{k: v[i] for k, v in extra.items()}})
     return rows
 
 
 _write_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(
-    fabrika.shared_kwargs(_write_chunk, ("stego_method", "alphas", "stream", "out_dir", "order", "placement_key"), _prefetch))
+    fabrika.shared_kwargs(_write_chunk, ("method", "payloads", "stream", "out_dir", "make", "prepare", "suffix"), _prefetch))
+
+
+def write_twins(data_dir, method: str, payloads: typing.List, make, *, prepare=None, suffix: str = "", columns=(),
+                split: typing.Optional[str] = None, stream: int = 0) -> typing.List[pathlib.Path]:
+    """The body of every driver's write_dataset: twins of every cover of `data_dir` (images*/files.csv, or the rows of `split`) at every
+    payload (payload_list), through _write_chunk's `make` and `prepare`; returns the folders, one per payload.  A folder's files.csv lists
+    exactly the files of this call, with CSV_COLUMNS and the method's own `columns`.  A bytes payload names its folder by its bits per
+    pixel, so the covers must share one size."""
+    import pandas as pd
+    data_dir = pathlib.Path(data_dir)
+    rows = _write_covers(data_dir, split=split, method=method, payloads=payloads, stream=int(stream), out_dir=str(data_dir), make=make,
+                         prepare=prepare, suffix=suffix)
+    folders = []
+    for j, p in enumerate(payloads):
+        if isinstance(p, bytes):
+            names = {pathlib.Path(r[j]["name"]).parent.name for r in rows}
+            if len(names) != 1:
+                raise ValueError(f"the covers differ in size, so one message gives several payloads: {sorted(names)}")
+            folder = data_dir / names.pop()
+        else:
+            folder = data_dir / twin_folder(method, p, suffix)
+        pd.DataFrame([r[j] for r in rows], columns=[*CSV_COLUMNS, *columns]).to_csv(folder / "files.csv", index=False)
+        folders.append(folder)
+    return folders
+
+
+def read_twins(data_dir, folder: str, out_dir, read, *, stream: int = 0, batch_size: int = 32) -> typing.List[pathlib.Path]:
+    """The body of every driver's extract_dataset: the images `folder`'s files.csv lists, in batches of one size; read(stego (N,H,W) uint8
+    on the device, seeds, the batch's rows of the csv) -> one array of message bits per image, written, packed by stc.bytes_from_bits, to
+    `out_dir/<stem>.bin`; returns the files."""
+    import pandas as pd
+    from .imread import read_luma_batch
+    data_dir, out_dir = pathlib.Path(data_dir), pathlib.Path(out_dir)
+    table = pd.read_csv(data_dir / folder / "files.csv")
+    names = [str(v) for v in table["name"]]
+    out_dir.mkdir(parents=True, exist_ok=True)
+    written = []
+    for a in range(0, len(names), int(batch_size)):
+        chunk = names[a:a + int(batch_size)]
+        stego = torch.from_numpy(np.ascontiguousarray(read_luma_batch([data_dir / v for v in chunk]))).to("cuda")
+        for v, b in zip(chunk, read(stego, [image_seed(v, stream) for v in chunk], table.iloc[a:a + len(chunk)])):
+            written.append(out_dir / f"{pathlib.Path(v).stem}.bin")
+            written[-1].write_bytes(bytes_from_bits(b))
+    return written
 
 
 def write_dataset(data_dir, stego_method: str, alpha, *, split: typing.Optional[str] = None, stream: int = 0,
                   order: str = "rows", placement_key: typing.Optional[int] = None) -> typing.List[pathlib.Path]:
     """Twins of every cover of `data_dir` (images*/files.csv, or the rows of `split`) at `alpha` (one value or several), written
-    beside the covers; returns the folders.  A folder's files.csv lists exactly the files of this call.  `order`: the path of 'LSBRS'; `placement_key`: the shared
-    stego key of 'LSBRK'."""
-    import pandas as pd
-    data_dir = pathlib.Path(data_dir)
+    beside the covers; returns the folders.  A folder's files.csv lists exactly the files of this call.  `order`: the path of 'LSBRS';
+    `placement_key`: the shared stego key of 'LSBRK'."""
+    from . import ops
     method = method_name(stego_method)
     _check_order(order)
     placement_key = _check_placement_key(method, placement_key)
-    alphas = [float(a) for a in np.atleast_1d(np.asarray(alpha, dtype=np.float64))]
-    _alphas(alphas, len(alphas))
-    rows = _write_covers(data_dir, split=split, stego_method=method, alphas=alphas, stream=int(stream), out_dir=str(data_dir), order=order,
-                         placement_key=placement_key)
-    folders = []
-    for j, a in enumerate(alphas):
-        folder = data_dir / folder_name(method, a, order, placement_key)
-        pd.DataFrame([r[j] for r in rows], columns=["name", "height", "width", "stego_method", "alpha"]).to_csv(folder / "files.csv", index=False)
-        folders.append(folder)
-    return folders
+
+    def make(cover, a, seeds, key):
+        return simulate(cover, method, a, seeds, key=key, order=order, placement_key=placement_key)[0], {}
+
+    return write_twins(data_dir, method, payload_list("[0, 1]", alpha), make, prepare=ops.hill_cost_f64 if method in ("HILLR", "HILLRM") else None,
+                       suffix=_folder_suffix(method, order, placement_key), split=split, stream=stream)
 
 
 def main(argv=None) -> None:

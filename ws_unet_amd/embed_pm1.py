@@ -30,10 +30,10 @@ import typing
 import numpy as np
 import torch
 
-from . import embed, fabrika
+from . import embed
 
 METHODS = ("LSBM", "HILL")
-ALPHA_MAX = {"LSBM": 1.0, "HILL": math.log2(3.0)}                   # HILL: below it; LSBM: up to it
+ALPHA_RANGE = {"LSBM": "[0, 1]", "HILL": "[0, log2 3)"}             # of embed.ALPHA_RANGES
 
 
 def method_name(stego_method: str) -> str:
@@ -44,17 +44,6 @@ def method_name(stego_method: str) -> str:
     return m
 
 
-def _alphas(method: str, alpha, n: int) -> np.ndarray:
-    a = np.asarray(alpha, dtype=np.float64)
-    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
-        raise ValueError(f"alpha must be a scalar or one value per image ({n}), got shape {a.shape}")
-    a = np.broadcast_to(a, (n,))
-    top = ALPHA_MAX[method]
-    if not np.all((a >= 0) & ((a <= top) if method == "LSBM" else (a < top))):
-        raise ValueError(f"alpha outside {'[0, 1]' if method == 'LSBM' else '[0, log2 3)'} for {method!r}: {alpha!r}")
-    return a
-
-
 def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds, *, rho: typing.Optional[torch.Tensor] = None):
     """cover_u8: (N,H,W) uint8 on the device; alpha: bits per pixel, a scalar or one value per image; seeds: one 64-bit integer per image
     (embed.image_seed) -> (stego (N,H,W) uint8, changes (N) int64), both on the device.  'HILL' takes an optional `rho` =
@@ -62,17 +51,10 @@ def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds, *, rho: ty
     naming the images whose capacity is short of alpha H W bits; alpha == 0 gives the cover."""
     from . import ops
     method = method_name(stego_method)
-    if not (isinstance(cover_u8, torch.Tensor) and cover_u8.dim() == 3 and cover_u8.dtype == torch.uint8):
-        raise ValueError("simulate: cover_u8 must be an (N,H,W) uint8 tensor")
-    n, h, w = cover_u8.shape
-    a = _alphas(method, alpha, n)
-    if seeds is None:
-        raise ValueError(f"simulate: {method!r} needs one seed per image (embed.image_seed)")
-    s = np.array([int(v) % 2 ** 64 for v in (seeds.tolist() if isinstance(seeds, (torch.Tensor, np.ndarray)) else seeds)], dtype=np.uint64)
-    if s.shape != (n,):
-        raise ValueError(f"simulate: {s.shape[0] if s.ndim else 1} seeds for {n} images")
+    n, h, w = embed.planes_shape("simulate", cover_u8)
+    a = embed.alpha_values(alpha, ALPHA_RANGE[method], n, whose=f" for {method!r}")
     dev = cover_u8.device
-    seeds_dev = torch.from_numpy(s.view(np.int64)).to(dev)
+    seeds_dev = embed.seeds_tensor("simulate", seeds, n, dev, method)
     if method == "LSBM":
         t = np.array([ops.lsbm_threshold(v) for v in a], dtype=np.uint32)
         return ops.embed_lsbm(cover_u8, seeds_dev, torch.from_numpy(t.view(np.int32)).to(dev))
@@ -91,53 +73,21 @@ def simulate(cover_u8: torch.Tensor, stego_method: str, alpha, seeds, *, rho: ty
 # ---- whole data sets --------------------------------------------------------------------------------------------------------
 
 def folder_name(stego_method: str, alpha: float) -> str:
-    """`stego_<METHOD>_alpha_<a>_independent_images`, embed.folder_name's scheme."""
-    return f"stego_{method_name(stego_method)}_alpha_{float(alpha)}_independent_images"
-
-
-def _write_chunk(fnames, kws, *, stego_method, alphas, stream, out_dir, prefetched=None):
-    """One chunk of covers -> their twins at every alpha, written as 8-bit gray PNGs; one list of files.csv rows per cover."""
-    from PIL import Image
-    from . import ops
-    planes = prefetched[0] if prefetched is not None else embed._prefetch(fnames, kws)[0]
-    cover = torch.from_numpy(np.ascontiguousarray(planes)).to("cuda")
-    method = method_name(stego_method)
-    rho = ops.hill_cost_f64(cover) if method == "HILL" else None
-    seeds = [embed.image_seed(f, stream) for f in fnames]
-    rows = [[] for _ in fnames]
-    for a in alphas:
-        try:
-            stego = simulate(cover, method, a, seeds, rho=rho)[0].cpu().numpy()
-        except ValueError as e:
-            raise ValueError(f"{e} (the batch: {[pathlib.Path(f).name for f in fnames]})") from e
-        folder = folder_name(method, a)
-        (pathlib.Path(out_dir) / folder).mkdir(parents=True, exist_ok=True)
-        for i, f in enumerate(fnames):
-            name = f"{folder}/{pathlib.Path(f).stem}.png"
-            Image.fromarray(stego[i]).save(pathlib.Path(out_dir) / name)
-            rows[i].append({"name": name, "height": stego.shape[1], "width": stego.shape[2], "stego_method": method, "alpha": float(a)})
-    return rows
-
-
-_write_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(
-    fabrika.shared_kwargs(_write_chunk, ("stego_method", "alphas", "stream", "out_dir"), embed._prefetch))
+    """`stego_<METHOD>_alpha_<a>_independent_images` (embed.twin_folder)."""
+    return embed.twin_folder(method_name(stego_method), alpha)
 
 
 def write_dataset(data_dir, stego_method: str, alpha, *, split: typing.Optional[str] = None, stream: int = 0) -> typing.List[pathlib.Path]:
     """Twins of every cover of `data_dir` (images*/files.csv, or the rows of `split`) at `alpha` (one value or several), written beside
     the covers; returns the folders.  A folder's files.csv lists exactly the files of this call."""
-    import pandas as pd
-    data_dir = pathlib.Path(data_dir)
+    from . import ops
     method = method_name(stego_method)
-    alphas = [float(a) for a in np.atleast_1d(np.asarray(alpha, dtype=np.float64))]
-    _alphas(method, alphas, len(alphas))
-    rows = _write_covers(data_dir, split=split, stego_method=method, alphas=alphas, stream=int(stream), out_dir=str(data_dir))
-    folders = []
-    for j, a in enumerate(alphas):
-        folder = data_dir / folder_name(method, a)
-        pd.DataFrame([r[j] for r in rows], columns=["name", "height", "width", "stego_method", "alpha"]).to_csv(folder / "files.csv", index=False)
-        folders.append(folder)
-    return folders
+
+    def make(cover, a, seeds, rho):
+        return simulate(cover, method, a, seeds, rho=rho)[0], {}
+
+    return embed.write_twins(data_dir, method, embed.payload_list(ALPHA_RANGE[method], alpha, whose=f" for {method!r}"), make,
+                             prepare=ops.hill_cost_f64 if method == "HILL" else None, split=split, stream=stream)
 
 
 def main(argv=None) -> None:

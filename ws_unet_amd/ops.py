@@ -1494,17 +1494,42 @@ def rank_select_f64(key: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
     return bits
 
 
-def embed_threshold(cover_u8: torch.Tensor, key: torch.Tensor, bits: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """stego = cover ^ (key <= the key whose pattern is bits[i]), every tie flipped (K22) -> (stego (N,H,W) uint8, changes (N) int64)."""
-    lib = _lib.load()
-    n, h, w = _u8_planes(cover_u8)
-    _dev_check(key, bits)
-    assert key.dtype == torch.float64 and key.shape == cover_u8.shape and bits.dtype == torch.int64 and bits.shape == (n,)
+def _f64_planes(who: str, x_u8: torch.Tensor, rho: torch.Tensor, name: str = "rho") -> Tuple[int, int, int]:
+    """(N,H,W) uint8 planes with a float64 plane (a cost, a key) for every one of them."""
+    n, h, w = _u8_planes(x_u8)
+    _dev_check(rho)
+    if rho.dtype != torch.float64 or rho.shape != x_u8.shape:
+        raise ValueError(f"{who}: {name} must be float64 of shape {tuple(x_u8.shape)}, got {tuple(rho.shape)} {rho.dtype}")
+    return n, h, w
+
+
+def _vector(who: str, name: str, t: torch.Tensor, n: int, dtype) -> int:
+    """An (N) device vector of `dtype`, one entry per image -> its pointer."""
+    if not (t.is_cuda and t.is_contiguous()):
+        _dev_check(t)                                               # (raises; asked inline first because these wrappers are host-bound)
+    if t.dtype != dtype or t.shape != (n,):
+        raise ValueError(f"{who}: {name} must be {str(dtype).replace('torch.', '')} of shape ({n},), got {tuple(t.shape)} {t.dtype}")
+    return t.data_ptr()
+
+
+def _embed_entry(entry: str, cover_u8: torch.Tensor, bytes_per_pixel: int, *middle) -> Tuple[torch.Tensor, torch.Tensor]:
+    """wsu_<entry>(cover, *middle, stego, changes, n, h, w, stream), the form of every simulator entry -> (stego (N,H,W) uint8, changes
+    (N) int64).  The caller has checked the cover (_u8_planes / _f64_planes) and `middle`; bytes_per_pixel: the timer's traffic figure."""
+    n, h, w = cover_u8.shape
+    symbol = "wsu_" + entry
+    fn = getattr(_lib.load(), symbol)
     stego = torch.empty_like(cover_u8)
     changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
-    check(_launch("embed_threshold", {"bytes": float(n * h * w * 10)}, lambda: lib.wsu_embed_threshold(
-        cover_u8.data_ptr(), key.data_ptr(), bits.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_threshold")
+    check(_launch(entry, {"bytes": float(n * h * w * bytes_per_pixel)}, lambda: fn(
+        cover_u8.data_ptr(), *middle, stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), symbol)
     return stego, changes
+
+
+def embed_threshold(cover_u8: torch.Tensor, key: torch.Tensor, bits: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """stego = cover ^ (key <= the key whose pattern is bits[i]), every tie flipped (K22) -> (stego (N,H,W) uint8, changes (N) int64)."""
+    who = "embed_threshold"
+    n = _f64_planes(who, cover_u8, key, "key")[0]
+    return _embed_entry(who, cover_u8, 10, key.data_ptr(), _vector(who, "bits", bits, n, torch.int64))
 
 
 def lsbr_threshold(alpha: float) -> int:
@@ -1518,49 +1543,27 @@ def lsbr_threshold(alpha: float) -> int:
 def embed_lsbr(cover_u8: torch.Tensor, seeds: torch.Tensor, thresholds: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """LSB replacement with Philox4x32-10 (K23).  seeds: (N) int64 holding the images' 64-bit seeds; thresholds: (N) int32 holding
     the uint32 lsbr_threshold of each image's alpha -> (stego (N,H,W) uint8, changes (N) int64)."""
-    lib = _lib.load()
-    n, h, w = _u8_planes(cover_u8)
-    _dev_check(seeds, thresholds)
-    assert seeds.dtype == torch.int64 and seeds.shape == (n,) and thresholds.dtype == torch.int32 and thresholds.shape == (n,)
-    stego = torch.empty_like(cover_u8)
-    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
-    check(_launch("embed_lsbr", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbr(
-        cover_u8.data_ptr(), seeds.data_ptr(), thresholds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_lsbr")
-    return stego, changes
+    who = "embed_lsbr"
+    n = _u8_planes(cover_u8)[0]
+    return _embed_entry(who, cover_u8, 2, _vector(who, "seeds", seeds, n, torch.int64), _vector(who, "thresholds", thresholds, n, torch.int32))
 
 
 def embed_lsbr_seq(cover_u8: torch.Tensor, seeds: torch.Tensor, counts: torch.Tensor, order="rows") -> Tuple[torch.Tensor, torch.Tensor]:
     """Sequential LSB replacement (K28): the first counts[i] pixels of the path over the whole plane ('rows': row by row from the top,
     'rows_up': from the bottom row upwards) flip as under embed_lsbr at alpha = 1.  seeds: (N) int64 holding the 64-bit seeds; counts:
     (N) int64 -> (stego (N,H,W) uint8, changes (N) int64)."""
-    oid = order_id(order)
-    lib = _lib.load()
-    n, h, w = _u8_planes(cover_u8)
-    _dev_check(seeds, counts)
-    assert seeds.dtype == torch.int64 and seeds.shape == (n,) and counts.dtype == torch.int64 and counts.shape == (n,)
-    stego = torch.empty_like(cover_u8)
-    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
-    check(_launch("embed_lsbr_seq", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbr_seq(
-        cover_u8.data_ptr(), seeds.data_ptr(), counts.data_ptr(), oid, stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())),
-        "wsu_embed_lsbr_seq")
-    return stego, changes
+    who, oid = "embed_lsbr_seq", order_id(order)
+    n = _u8_planes(cover_u8)[0]
+    return _embed_entry(who, cover_u8, 2, _vector(who, "seeds", seeds, n, torch.int64), _vector(who, "counts", counts, n, torch.int64), oid)
 
 
 def embed_threshold_lsbr(cover_u8: torch.Tensor, key: torch.Tensor, bits: torch.Tensor, seeds: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """HILLR's selection with a real message (K34): a pixel with key <= the key whose pattern is bits[i] is used, and a used pixel flips as
     under embed_lsbr at alpha = 1 with the image's seed.  key: (N,H,W) float64; bits, seeds: (N) int64 -> (stego (N,H,W) uint8, changes
     (N) int64)."""
-    lib = _lib.load()
-    n, h, w = _u8_planes(cover_u8)
-    _dev_check(key, bits, seeds)
-    assert key.dtype == torch.float64 and key.shape == cover_u8.shape and bits.dtype == torch.int64 and bits.shape == (n,)
-    assert seeds.dtype == torch.int64 and seeds.shape == (n,)
-    stego = torch.empty_like(cover_u8)
-    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
-    check(_launch("embed_threshold_lsbr", {"bytes": float(n * h * w * 10)}, lambda: lib.wsu_embed_threshold_lsbr(
-        cover_u8.data_ptr(), key.data_ptr(), bits.data_ptr(), seeds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())),
-        "wsu_embed_threshold_lsbr")
-    return stego, changes
+    who = "embed_threshold_lsbr"
+    n = _f64_planes(who, cover_u8, key, "key")[0]
+    return _embed_entry(who, cover_u8, 10, key.data_ptr(), _vector(who, "bits", bits, n, torch.int64), _vector(who, "seeds", seeds, n, torch.int64))
 
 
 def lsbr_key_threshold(alpha: float) -> int:
@@ -1585,16 +1588,10 @@ def embed_lsbr_keyed(cover_u8: torch.Tensor, seeds: torch.Tensor, key_seed: int,
     """LSB replacement at the positions one stego key selects in every image (K30): pixel i is used iff its Philox word under `key_seed`
     is below `alpha_threshold` (lsbr_key_threshold) and a used pixel flips as under embed_lsbr at alpha = 1 with the image's seed.  seeds:
     (N) int64 holding the 64-bit seeds -> (stego (N,H,W) uint8, changes (N) int64)."""
-    key, thr = _key_args("embed_lsbr_keyed", key_seed, alpha_threshold)
-    lib = _lib.load()
-    n, h, w = _u8_planes(cover_u8)
-    _dev_check(seeds)
-    assert seeds.dtype == torch.int64 and seeds.shape == (n,)
-    stego = torch.empty_like(cover_u8)
-    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
-    check(_launch("embed_lsbr_keyed", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbr_keyed(
-        cover_u8.data_ptr(), seeds.data_ptr(), key, thr, stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_lsbr_keyed")
-    return stego, changes
+    who = "embed_lsbr_keyed"
+    key, thr = _key_args(who, key_seed, alpha_threshold)
+    n = _u8_planes(cover_u8)[0]
+    return _embed_entry(who, cover_u8, 2, _vector(who, "seeds", seeds, n, torch.int64), key, thr)
 
 
 def lsbr_key_mask(key_seed: int, alpha_threshold: int, h: int, w: int, device=None) -> torch.Tensor:
@@ -1622,20 +1619,12 @@ TERNARY_LADDER = tuple(2.0 ** e for e in range(-50, 26, 5))
 TERNARY_REFINEMENTS = 8
 
 
-def _ternary_planes(who: str, x_u8: torch.Tensor, rho: torch.Tensor) -> Tuple[int, int, int]:
-    n, h, w = _u8_planes(x_u8)
-    _dev_check(rho)
-    if rho.dtype != torch.float64 or rho.shape != x_u8.shape:
-        raise ValueError(f"{who}: rho must be float64 of shape {tuple(x_u8.shape)}, got {tuple(rho.shape)} {rho.dtype}")
-    return n, h, w
-
-
 def ternary_entropy(x_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor) -> torch.Tensor:
     """The bits a +-1 sender with change probabilities exp(-lambda rho) / Z embeds (K37).  x_u8: (N,H,W) uint8; rho: (N,H,W) float64,
     positive, +inf = wet; lambdas: (N,L) float64, positive, 1 <= L <= 16 -> (N,L) float64.  The +1 change is wet at 255, the -1 change at
     0.  Same bits on every call and in every batch."""
     lib = _lib.load()
-    n, h, w = _ternary_planes("ternary_entropy", x_u8, rho)
+    n, h, w = _f64_planes("ternary_entropy", x_u8, rho)
     _dev_check(lambdas)
     if lambdas.dtype != torch.float64 or lambdas.dim() != 2 or lambdas.shape[0] != n or not 1 <= lambdas.shape[1] <= TERNARY_MAX_LAMBDAS:
         raise ValueError(f"ternary_entropy: lambdas must be float64 of shape ({n}, 1..{TERNARY_MAX_LAMBDAS}), got {tuple(lambdas.shape)} {lambdas.dtype}")
@@ -1660,10 +1649,8 @@ def ternary_lambda(x_u8: torch.Tensor, rho: torch.Tensor, message_bits: torch.Te
     (N) float64 on the device, not negative.  ok[i] is False where even the lowest multiplier of TERNARY_LADDER carries less than the
     payload (lam_lo = lam_hi = that multiplier then).  Where the highest still carries it (a payload of 0) lam_lo = lam_hi = the highest.
     Nine K37 launches; the bracket is chosen between them on the device, nothing waits for the GPU."""
-    n, h, w = _ternary_planes("ternary_lambda", x_u8, rho)
-    _dev_check(message_bits)
-    if message_bits.dtype != torch.float64 or message_bits.shape != (n,):
-        raise ValueError(f"ternary_lambda: message_bits must be float64 of shape ({n},), got {tuple(message_bits.shape)} {message_bits.dtype}")
+    n, h, w = _f64_planes("ternary_lambda", x_u8, rho)
+    _vector("ternary_lambda", "message_bits", message_bits, n, torch.float64)
     dev = x_u8.device
     m = message_bits[:, None]
     ladder = torch.tensor(TERNARY_LADDER, dtype=torch.float64, device=dev).expand(n, -1).contiguous()
@@ -1688,16 +1675,10 @@ def embed_ternary(cover_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tens
     """The +-1 sender's draw (K38): pixel i becomes x + 1 with probability exp(-lambda rho) / Z, x - 1 with the same (never out of 0..255:
     that direction is wet), from the generator word embed_lsbr gives it.  rho: (N,H,W) float64; lambdas: (N) float64, positive (+inf: the
     cover); seeds: (N) int64 holding the 64-bit seeds -> (stego (N,H,W) uint8, changes (N) int64)."""
-    lib = _lib.load()
-    n, h, w = _ternary_planes("embed_ternary", cover_u8, rho)
-    _dev_check(lambdas, seeds)
-    assert lambdas.dtype == torch.float64 and lambdas.shape == (n,) and seeds.dtype == torch.int64 and seeds.shape == (n,)
-    stego = torch.empty_like(cover_u8)
-    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
-    check(_launch("embed_ternary", {"bytes": float(n * h * w * 10)}, lambda: lib.wsu_embed_ternary(
-        cover_u8.data_ptr(), rho.data_ptr(), lambdas.data_ptr(), seeds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())),
-        "wsu_embed_ternary")
-    return stego, changes
+    who = "embed_ternary"
+    n = _f64_planes(who, cover_u8, rho)[0]
+    return _embed_entry(who, cover_u8, 10, rho.data_ptr(), _vector(who, "lambdas", lambdas, n, torch.float64),
+                        _vector(who, "seeds", seeds, n, torch.int64))
 
 
 def lsbm_threshold(alpha: float) -> int:
@@ -1713,15 +1694,9 @@ def embed_lsbm(cover_u8: torch.Tensor, seeds: torch.Tensor, thresholds: torch.Te
     """LSB matching with Philox4x32-10 (K39): a fraction alpha / 2 of the pixels changes by +-1, the sign random, inwards at 0 and 255.
     seeds: (N) int64 holding the images' 64-bit seeds; thresholds: (N) int32 holding the uint32 lsbm_threshold of each image's alpha ->
     (stego (N,H,W) uint8, changes (N) int64)."""
-    lib = _lib.load()
-    n, h, w = _u8_planes(cover_u8)
-    _dev_check(seeds, thresholds)
-    assert seeds.dtype == torch.int64 and seeds.shape == (n,) and thresholds.dtype == torch.int32 and thresholds.shape == (n,)
-    stego = torch.empty_like(cover_u8)
-    changes = torch.empty(n, dtype=torch.int64, device=cover_u8.device)
-    check(_launch("embed_lsbm", {"bytes": float(n * h * w * 2)}, lambda: lib.wsu_embed_lsbm(
-        cover_u8.data_ptr(), seeds.data_ptr(), thresholds.data_ptr(), stego.data_ptr(), changes.data_ptr(), n, h, w, _stream())), "wsu_embed_lsbm")
-    return stego, changes
+    who = "embed_lsbm"
+    n = _u8_planes(cover_u8)[0]
+    return _embed_entry(who, cover_u8, 2, _vector(who, "seeds", seeds, n, torch.int64), _vector(who, "thresholds", thresholds, n, torch.int32))
 
 
 # ---- syndrome-trellis codes (K40-K42) ----------------------------------------------------------------------------------------------
@@ -1748,18 +1723,28 @@ def philox_words(seeds: torch.Tensor, h: int, w: int) -> torch.Tensor:
     return words
 
 
-def _stc_code(who: str, n: int, hw: int, h, k, cols: torch.Tensor, path: Optional[torch.Tensor]) -> Tuple[int, int]:
-    h, k = int(h), int(k)
+def _stc_height(who: str, h) -> int:
+    h = int(h)
     if not 1 <= h <= STC_MAX_H:
         raise ValueError(f"{who}: constraint height h={h} outside 1..{STC_MAX_H}")
-    if not 1 <= k <= hw:
-        raise ValueError(f"{who}: k={k} message bits outside 1..{hw} (the pixels of an image)")
+    return h
+
+
+def _stc_table(who: str, n: int, hw: int, cols: torch.Tensor, path: Optional[torch.Tensor], least: int, least_what: str) -> None:
+    """The column table (at least `least` entries, which the message calls `least_what`) and the paths of a uniform or a ragged code."""
     _dev_check(cols, path)
-    wmax = -(-hw // k)
-    if cols.dtype != torch.int32 or cols.dim() != 1 or cols.shape[0] < wmax:
-        raise ValueError(f"{who}: cols must be int32 with at least ceil(n / k) = {wmax} entries, got {tuple(cols.shape)} {cols.dtype}")
+    if cols.dtype != torch.int32 or cols.dim() != 1 or cols.shape[0] < least:
+        raise ValueError(f"{who}: cols must be int32 with at least {least_what}, got {tuple(cols.shape)} {cols.dtype}")
     if path is not None and (path.dtype != torch.int32 or path.shape != (n, hw)):
         raise ValueError(f"{who}: path must be int32 of shape ({n}, {hw}), got {tuple(path.shape)} {path.dtype}")
+
+
+def _stc_code(who: str, n: int, hw: int, h, k, cols: torch.Tensor, path: Optional[torch.Tensor]) -> Tuple[int, int]:
+    h, k = _stc_height(who, h), int(k)
+    if not 1 <= k <= hw:
+        raise ValueError(f"{who}: k={k} message bits outside 1..{hw} (the pixels of an image)")
+    wmax = -(-hw // k)
+    _stc_table(who, n, hw, cols, path, wmax, f"ceil(n / k) = {wmax} entries")
     return h, k
 
 
@@ -1787,6 +1772,30 @@ def _stc_slices(who: str, n: int, hw: int, h: int, workspace_cap, workspace: Opt
     return per, step, torch.empty(step * per, dtype=torch.uint8, device=dev)
 
 
+def _stc_embed_slices(who: str, cover_u8: torch.Tensor, seeds: torch.Tensor, change: str, h: int, workspace_cap, workspace, call, phases: int = 3):
+    """What stc_embed and stc_embed_ragged share: the seeds, the change and the phases, the outputs, and the loop over the slices of the
+    batch.  call(a, b, change id, tail) runs wsu_<who> on images a .. b - 1; `tail` is what both entries end with, from `stego` on."""
+    n, hh, ww = cover_u8.shape
+    _vector(who, "seeds", seeds, n, torch.int64)
+    if change not in STC_CHANGES:
+        raise ValueError(f"{who}: change {change!r} is not one of {' / '.join(STC_CHANGES)}")
+    if phases not in (1, 3) or (phases == 1 and workspace is None):
+        raise ValueError(f"{who}: phases is 1 (forward only, into the caller's workspace) or 3 (both)")
+    dev = cover_u8.device
+    per, step, ws = _stc_slices(who, n, hh * ww, h, workspace_cap, workspace, dev)
+    stego = torch.empty_like(cover_u8)
+    cost = torch.empty(n, dtype=torch.float64, device=dev)
+    changes = torch.zeros(n, dtype=torch.int64, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    cid = STC_CHANGES.index(change)
+    for a in range(0, n, step):
+        b = min(n, a + step)
+        tail = (stego[a:b].data_ptr(), cost[a:b].data_ptr(), changes[a:b].data_ptr(), ok[a:b].data_ptr(), ws.data_ptr(), ws.numel(), b - a, hh, ww,
+                _stream())
+        check(_launch(who, {"bytes": float((b - a) * (hh * ww * 14 + 2 * per))}, lambda: call(a, b, cid, tail)), "wsu_" + who)
+    return stego, cost, changes, ok
+
+
 def stc_embed(cover_u8: torch.Tensor, rho: torch.Tensor, message: torch.Tensor, cols: torch.Tensor, seeds: torch.Tensor, *, h: int = 10,
               path: Optional[torch.Tensor] = None, change: str = "flip", workspace_cap: Optional[int] = None, phases: int = 3,
               workspace: Optional[torch.Tensor] = None):
@@ -1801,33 +1810,14 @@ def stc_embed(cover_u8: torch.Tensor, rho: torch.Tensor, message: torch.Tensor, 
     and changes are not written, and the take bits stay in the caller's `workspace` (uint8, N * stc_workspace_bytes(H W, h) bytes, which
     also turns the slicing off) for a later walk back through the C entry (phases 2 there reads cost and ok as arguments)."""
     lib = _lib.load()
-    n, hh, ww = _ternary_planes("stc_embed", cover_u8, rho)
-    hw = hh * ww
+    n, hh, ww = _f64_planes("stc_embed", cover_u8, rho)
     if not (isinstance(message, torch.Tensor) and message.dtype == torch.uint8 and message.dim() == 2 and message.shape[0] == n):
         raise ValueError(f"stc_embed: message must be an ({n}, k) uint8 tensor of 0 / 1")
-    h, k = _stc_code("stc_embed", n, hw, h, message.shape[1], cols, path)
-    _dev_check(message, seeds)
-    if seeds.dtype != torch.int64 or seeds.shape != (n,):
-        raise ValueError(f"stc_embed: seeds must be int64 of shape ({n},), got {tuple(seeds.shape)} {seeds.dtype}")
-    if change not in STC_CHANGES:
-        raise ValueError(f"stc_embed: change {change!r} is not one of {' / '.join(STC_CHANGES)}")
-    if phases not in (1, 3) or (phases == 1 and workspace is None):
-        raise ValueError("stc_embed: phases is 1 (forward only, into the caller's workspace) or 3 (both)")
-    dev = cover_u8.device
-    per, step, ws = _stc_slices("stc_embed", n, hw, h, workspace_cap, workspace, dev)
-    stego = torch.empty_like(cover_u8)
-    cost = torch.empty(n, dtype=torch.float64, device=dev)
-    changes = torch.zeros(n, dtype=torch.int64, device=dev)
-    ok = torch.empty(n, dtype=torch.uint8, device=dev)
-    cid = STC_CHANGES.index(change)
-    for a in range(0, n, step):
-        b = min(n, a + step)
-        p = path[a:b].data_ptr() if path is not None else None
-        check(_launch("stc_embed", {"bytes": float((b - a) * (hw * 14 + 2 * per))}, lambda: lib.wsu_stc_embed(
-            cover_u8[a:b].data_ptr(), rho[a:b].data_ptr(), message[a:b].data_ptr(), cols.data_ptr(), p, seeds[a:b].data_ptr(), cid, h, k,
-            phases, stego[a:b].data_ptr(), cost[a:b].data_ptr(), changes[a:b].data_ptr(), ok[a:b].data_ptr(), ws.data_ptr(), ws.numel(),
-            b - a, hh, ww, _stream())), "wsu_stc_embed")
-    return stego, cost, changes, ok
+    h, k = _stc_code("stc_embed", n, hh * ww, h, message.shape[1], cols, path)
+    _dev_check(message)
+    return _stc_embed_slices("stc_embed", cover_u8, seeds, change, h, workspace_cap, workspace, lambda a, b, cid, tail: lib.wsu_stc_embed(
+        cover_u8[a:b].data_ptr(), rho[a:b].data_ptr(), message[a:b].data_ptr(), cols.data_ptr(), _ptr(path[a:b] if path is not None else None),
+        seeds[a:b].data_ptr(), cid, h, k, phases, *tail), phases)
 
 
 def stc_extract(stego_u8: torch.Tensor, cols: torch.Tensor, k: int, *, h: int = 10, path: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1847,9 +1837,7 @@ def stc_extract(stego_u8: torch.Tensor, cols: torch.Tensor, k: int, *, h: int = 
 def _stc_ragged(who: str, n: int, hw: int, h, message: torch.Tensor, ks: torch.Tensor, first: Optional[torch.Tensor], cols: torch.Tensor,
                 path: Optional[torch.Tensor]) -> Tuple[int, torch.Tensor]:
     """The checks of _stc_code for per-image lengths; what ks and first hold stays on the device, where the kernels check it."""
-    h = int(h)
-    if not 1 <= h <= STC_MAX_H:
-        raise ValueError(f"{who}: constraint height h={h} outside 1..{STC_MAX_H}")
+    h = _stc_height(who, h)
     if not (isinstance(message, torch.Tensor) and message.dtype == torch.uint8 and message.dim() == 2 and message.shape[0] == n
             and message.shape[1] >= 1):
         raise ValueError(f"{who}: message must be an ({n}, bits) uint8 tensor of 0 / 1")
@@ -1859,11 +1847,8 @@ def _stc_ragged(who: str, n: int, hw: int, h, message: torch.Tensor, ks: torch.T
         first = torch.zeros(n, dtype=torch.int32, device=ks.device)
     if not (isinstance(first, torch.Tensor) and first.dtype == torch.int32 and first.shape == (n,)):
         raise ValueError(f"{who}: first must be an int32 tensor of shape ({n},): the first bit of each row that is used")
-    _dev_check(message, ks, first, cols, path)
-    if cols.dtype != torch.int32 or cols.dim() != 1 or cols.shape[0] < 1:
-        raise ValueError(f"{who}: cols must be int32 with at least ceil(n / k) entries for the smallest positive k, got {tuple(cols.shape)} {cols.dtype}")
-    if path is not None and (path.dtype != torch.int32 or path.shape != (n, hw)):
-        raise ValueError(f"{who}: path must be int32 of shape ({n}, {hw}), got {tuple(path.shape)} {path.dtype}")
+    _dev_check(message, ks, first)
+    _stc_table(who, n, hw, cols, path, 1, "ceil(n / k) entries for the smallest positive k")
     return h, first
 
 
@@ -1876,29 +1861,12 @@ def stc_embed_ragged(cover_u8: torch.Tensor, rho: torch.Tensor, message: torch.T
     ks[i] == 0 copies the image: cost 0, ok 1.  Nothing is read back, so values of ks / first outside these ranges are found by the
     kernel: such an image is copied and has cost +inf and ok 0.  With all ks equal the results are stc_embed's bit for bit."""
     lib = _lib.load()
-    n, hh, ww = _ternary_planes("stc_embed_ragged", cover_u8, rho)
-    hw = hh * ww
-    h, first = _stc_ragged("stc_embed_ragged", n, hw, h, message, ks, first, cols, path)
-    _dev_check(seeds)
-    if seeds.dtype != torch.int64 or seeds.shape != (n,):
-        raise ValueError(f"stc_embed_ragged: seeds must be int64 of shape ({n},), got {tuple(seeds.shape)} {seeds.dtype}")
-    if change not in STC_CHANGES:
-        raise ValueError(f"stc_embed_ragged: change {change!r} is not one of {' / '.join(STC_CHANGES)}")
-    dev = cover_u8.device
-    per, step, ws = _stc_slices("stc_embed_ragged", n, hw, h, workspace_cap, None, dev)
-    stego = torch.empty_like(cover_u8)
-    cost = torch.empty(n, dtype=torch.float64, device=dev)
-    changes = torch.zeros(n, dtype=torch.int64, device=dev)
-    ok = torch.empty(n, dtype=torch.uint8, device=dev)
-    cid, bits, stride = STC_CHANGES.index(change), message.shape[1], message.stride(0)
-    for a in range(0, n, step):
-        b = min(n, a + step)
-        p = path[a:b].data_ptr() if path is not None else None
-        check(_launch("stc_embed_ragged", {"bytes": float((b - a) * (hw * 14 + 2 * per))}, lambda: lib.wsu_stc_embed_ragged(
-            cover_u8[a:b].data_ptr(), rho[a:b].data_ptr(), message[a:b].data_ptr(), stride, ks[a:b].data_ptr(), first[a:b].data_ptr(), bits,
-            cols.data_ptr(), cols.shape[0], p, seeds[a:b].data_ptr(), cid, h, stego[a:b].data_ptr(), cost[a:b].data_ptr(),
-            changes[a:b].data_ptr(), ok[a:b].data_ptr(), ws.data_ptr(), ws.numel(), b - a, hh, ww, _stream())), "wsu_stc_embed_ragged")
-    return stego, cost, changes, ok
+    n, hh, ww = _f64_planes("stc_embed_ragged", cover_u8, rho)
+    h, first = _stc_ragged("stc_embed_ragged", n, hh * ww, h, message, ks, first, cols, path)
+    bits, stride = message.shape[1], message.stride(0)
+    return _stc_embed_slices("stc_embed_ragged", cover_u8, seeds, change, h, workspace_cap, None, lambda a, b, cid, tail: lib.wsu_stc_embed_ragged(
+        cover_u8[a:b].data_ptr(), rho[a:b].data_ptr(), message[a:b].data_ptr(), stride, ks[a:b].data_ptr(), first[a:b].data_ptr(), bits,
+        cols.data_ptr(), cols.shape[0], _ptr(path[a:b] if path is not None else None), seeds[a:b].data_ptr(), cid, h, *tail))
 
 
 def stc_extract_ragged(stego_u8: torch.Tensor, cols: torch.Tensor, *, ks: torch.Tensor, first: Optional[torch.Tensor] = None, bits: Optional[int] = None,
@@ -1927,22 +1895,10 @@ def _layer_workspace(n: int, dev) -> torch.Tensor:
     return torch.empty(_lib.load().wsu_stc_layer_workspace_bytes(n) // 8, dtype=torch.float64, device=dev)
 
 
-def _layer_lambdas(who: str, n: int, lambdas: torch.Tensor) -> None:
-    _dev_check(lambdas)
-    if lambdas.dtype != torch.float64 or lambdas.shape != (n,):
-        raise ValueError(f"{who}: lambdas must be float64 of shape ({n},), got {tuple(lambdas.shape)} {lambdas.dtype}")
-
-
 def _layer_plane(who: str, name: str, t: torch.Tensor, like: torch.Tensor) -> None:
     _dev_check(t)
     if t.dtype != torch.uint8 or t.shape != like.shape:
         raise ValueError(f"{who}: {name} must be uint8 of shape {tuple(like.shape)}, got {tuple(t.shape)} {t.dtype}")
-
-
-def _layer_vector(who: str, name: str, t: torch.Tensor, n: int, dtype) -> None:
-    _dev_check(t)
-    if t.dtype != dtype or t.shape != (n,):
-        raise ValueError(f"{who}: {name} must be {dtype} of shape ({n},), got {tuple(t.shape)} {t.dtype}")
 
 
 def stc_layer_high(x_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor):
@@ -1950,8 +1906,8 @@ def stc_layer_high(x_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor)
     (ternary_lambda's lam_lo) -> (u1 (N,H,W) uint8 = bit 1 of the pixels, rho1 (N,H,W) float64 = the cost of changing it, H1 (N) float64 =
     the layer's entropy in bits).  include/wsu.h has the formulas.  The same bits in every batch."""
     lib = _lib.load()
-    n, h, w = _ternary_planes("stc_layer_high", x_u8, rho)
-    _layer_lambdas("stc_layer_high", n, lambdas)
+    n, h, w = _f64_planes("stc_layer_high", x_u8, rho)
+    _vector("stc_layer_high", "lambdas", lambdas, n, torch.float64)
     dev = x_u8.device
     u1 = torch.empty_like(x_u8)
     rho1 = torch.empty_like(rho)
@@ -1968,10 +1924,10 @@ def stc_layer_low(x_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor, 
     int32 -> (u0 (N,H,W) uint8, rho0 (N,H,W) float64): a pixel whose bit 1 changed is decided (u0 = the other LSB, rho0 = +inf), every
     other keeps its LSB at cost lambda rho."""
     lib = _lib.load()
-    n, h, w = _ternary_planes("stc_layer_low", x_u8, rho)
-    _layer_lambdas("stc_layer_low", n, lambdas)
+    n, h, w = _f64_planes("stc_layer_low", x_u8, rho)
+    _vector("stc_layer_low", "lambdas", lambdas, n, torch.float64)
     _layer_plane("stc_layer_low", "y1", y1, x_u8)
-    _layer_vector("stc_layer_low", "k1", k1, n, torch.int32)
+    _vector("stc_layer_low", "k1", k1, n, torch.int32)
     u0 = torch.empty_like(x_u8)
     rho0 = torch.empty_like(rho)
     check(_launch("stc_layer_low", {"bytes": float(n * h * w * 19)}, lambda: lib.wsu_stc_layer_low(
@@ -1986,12 +1942,12 @@ def stc_layer_compose(cover_u8: torch.Tensor, rho: torch.Tensor, y1: torch.Tenso
     the LSB did, in images whose ok1 and ok0 (N, uint8) are both set; every other image is copied -> (stego (N,H,W) uint8, changes (N)
     int64, distortion (N) float64 = the sum of rho over the changed pixels in a fixed order, ok (N) uint8)."""
     lib = _lib.load()
-    n, h, w = _ternary_planes("stc_layer_compose", cover_u8, rho)
+    n, h, w = _f64_planes("stc_layer_compose", cover_u8, rho)
     _layer_plane("stc_layer_compose", "y1", y1, cover_u8)
     _layer_plane("stc_layer_compose", "y0", y0, cover_u8)
-    _layer_vector("stc_layer_compose", "k1", k1, n, torch.int32)
-    _layer_vector("stc_layer_compose", "ok1", ok1, n, torch.uint8)
-    _layer_vector("stc_layer_compose", "ok0", ok0, n, torch.uint8)
+    _vector("stc_layer_compose", "k1", k1, n, torch.int32)
+    _vector("stc_layer_compose", "ok1", ok1, n, torch.uint8)
+    _vector("stc_layer_compose", "ok0", ok0, n, torch.uint8)
     dev = cover_u8.device
     stego = torch.empty_like(cover_u8)
     changes = torch.empty(n, dtype=torch.int64, device=dev)

@@ -33,7 +33,6 @@ import numpy as np
 import torch
 
 from . import embed as _embed
-from . import fabrika
 
 METHODS = ("STCR", "STCM")
 CHANGE = {"STCR": "flip", "STCM": "pm1"}
@@ -50,8 +49,8 @@ def method_name(stego_method: str) -> str:
 
 
 def folder_name(stego_method: str, alpha: float) -> str:
-    """`stego_<METHOD>_alpha_<a>_independent_images`, embed.folder_name's scheme."""
-    return f"stego_{method_name(stego_method)}_alpha_{float(alpha)}_independent_images"
+    """`stego_<METHOD>_alpha_<a>_independent_images` (embed.twin_folder)."""
+    return _embed.twin_folder(method_name(stego_method), alpha)
 
 
 # ---- the code's pieces on the host ----------------------------------------------------------------------------------------------------
@@ -90,36 +89,21 @@ def block_widths(n: int, k: int) -> np.ndarray:
     return np.diff(edges)
 
 
-def bits_from_bytes(data: bytes) -> np.ndarray:
-    """bytes -> their bits as uint8 0 / 1, the most significant bit of each byte first."""
-    return np.unpackbits(np.frombuffer(bytes(data), dtype=np.uint8))
-
-
-def bytes_from_bits(bits) -> bytes:
-    """The inverse of bits_from_bytes; a trailing group of fewer than 8 bits is dropped."""
-    b = np.asarray(bits, dtype=np.uint8).reshape(-1)
-    if b.size and b.max() > 1:
-        raise ValueError("bytes_from_bits: bits must be 0 / 1")
-    return np.packbits(b[:b.size // 8 * 8]).tobytes()
-
-
-def _seeds(who: str, seeds, n: int, dev) -> torch.Tensor:
-    if seeds is None:
-        raise ValueError(f"{who}: one seed per image is needed (embed.image_seed)")
-    s = np.array([int(v) % 2 ** 64 for v in (seeds.tolist() if isinstance(seeds, (torch.Tensor, np.ndarray)) else seeds)], dtype=np.uint64)
-    if s.shape != (n,):
-        raise ValueError(f"{who}: {s.shape[0] if s.ndim else 1} seeds for {n} images")
-    return torch.from_numpy(s.view(np.int64)).to(dev)
+bits_from_bytes, bytes_from_bits = _embed.bits_from_bytes, _embed.bytes_from_bits       # (they live beside the twin writer that uses them)
 
 
 # ---- on the device ------------------------------------------------------------------------------------------------------------------------
+
+_seeds = _embed.seeds_tensor                                         # (its name while it lived here: callers outside the package, such as
+                                                                     # tests written against the earlier layout, still reach it; one definition)
+
 
 def key_path(seeds, h: int, w: int, device=None) -> torch.Tensor:
     """The keyed pixel paths: int32 (N, h w), per image the raster indices in stable ascending order of the pixels' generator words under
     the image's seed (ops.philox_words; the sort is torch.sort on the device, as in ops.interior_order)."""
     from . import ops
     dev = torch.device("cuda") if device is None else device
-    s = seeds if isinstance(seeds, torch.Tensor) and seeds.is_cuda else _seeds("key_path", seeds, len(seeds), dev)
+    s = seeds if isinstance(seeds, torch.Tensor) and seeds.is_cuda else _embed.seeds_tensor("key_path", seeds, len(seeds), dev)
     words = ops.philox_words(s, h, w).reshape(s.shape[0], -1).to(torch.int64) & 0xFFFFFFFF
     return torch.sort(words, dim=1, stable=True).indices.to(torch.int32).contiguous()
 
@@ -128,7 +112,7 @@ def random_message(seeds, k: int, device=None) -> torch.Tensor:
     """(N,k) uint8 of 0 / 1: bit 0 of the first k generator words under each seed with MESSAGE_STREAM xored into its stream word."""
     from . import ops
     dev = torch.device("cuda") if device is None else device
-    s = _seeds("random_message", seeds, len(seeds), dev) ^ (MESSAGE_STREAM << 32)
+    s = _embed.seeds_tensor("random_message", seeds, len(seeds), dev) ^ (MESSAGE_STREAM << 32)
     return (ops.philox_words(s, 1, int(k)).reshape(s.shape[0], -1) & 1).to(torch.uint8).contiguous()
 
 
@@ -146,25 +130,21 @@ def embed(cover_u8: torch.Tensor, message, *, rho: typing.Optional[torch.Tensor]
     cost of the changes, the least any stego with this message can have under this code.  An image whose wet pixels leave no solution
     has ok False and stego = cover; with `strict` (the default) the flags are read back and such images raise ValueError by index."""
     from . import ops
-    if not (isinstance(cover_u8, torch.Tensor) and cover_u8.dim() == 3 and cover_u8.dtype == torch.uint8):
-        raise ValueError("embed: cover_u8 must be an (N,H,W) uint8 tensor")
-    n, hh, ww = cover_u8.shape
+    n, hh, ww = _embed.planes_shape("embed", cover_u8)
     dev = cover_u8.device
     if isinstance(message, torch.Tensor):
         if message.dtype != torch.uint8 or message.dim() != 2 or message.shape[0] != n:
             raise ValueError(f"embed: message must be an ({n}, k) uint8 tensor of 0 / 1 or a payload in bits per pixel")
         msg = message.to(dev).contiguous()
     else:
-        alpha = float(message)
-        if not 0.0 < alpha <= 1.0:
-            raise ValueError(f"embed: alpha outside (0, 1]: {message!r}")
+        alpha = float(_embed.alpha_values(float(message), "(0, 1]", who="embed: ")[0])
         k = int(round(alpha * hh * ww))
         if k < 1:
             raise ValueError(f"embed: alpha {alpha} is less than one bit in {hh} x {ww} pixels")
         msg = random_message(seeds, k, dev)
     if change not in ops.STC_CHANGES:
         raise ValueError(f"embed: change {change!r} is not one of {' / '.join(ops.STC_CHANGES)}")
-    s = _seeds("embed", seeds, n, dev)
+    s = _embed.seeds_tensor("embed", seeds, n, dev)
     k = msg.shape[1]
     if not 1 <= k <= hh * ww:
         raise ValueError(f"embed: k={k} message bits outside 1..{hh * ww}")
@@ -185,68 +165,22 @@ def embed(cover_u8: torch.Tensor, message, *, rho: typing.Optional[torch.Tensor]
 def extract(stego_u8: torch.Tensor, k: int, *, h: int = 10, seeds, permute: bool = True, key: int = 0) -> torch.Tensor:
     """The k message bits of every stego image: (N,k) uint8 of 0 / 1 on the device.  h, seeds, permute and key as `embed` was given them."""
     from . import ops
-    if not (isinstance(stego_u8, torch.Tensor) and stego_u8.dim() == 3 and stego_u8.dtype == torch.uint8):
-        raise ValueError("extract: stego_u8 must be an (N,H,W) uint8 tensor")
-    n, hh, ww = stego_u8.shape
+    n, hh, ww = _embed.planes_shape("extract", stego_u8, "stego_u8")
     k = int(k)
     if not 1 <= k <= hh * ww:
         raise ValueError(f"extract: k={k} message bits outside 1..{hh * ww}")
     dev = stego_u8.device
-    s = _seeds("extract", seeds, n, dev)
+    s = _embed.seeds_tensor("extract", seeds, n, dev)
     path = key_path(s, hh, ww, dev) if permute else None
     return ops.stc_extract(stego_u8, _columns_dev(h, hh * ww, k, key, dev), k, h=h, path=path)
 
 
 # ---- whole data sets --------------------------------------------------------------------------------------------------------
 
-def _payloads(alphas, message) -> typing.List:
-    """The payloads of one call: floats (alpha) or one bytes object"""
-    if (alphas is None) == (message is None):
-        raise ValueError("give either alpha(s) or a message, not both and not neither")
-    if message is not None:
-        if len(bytes(message)) < 1:
-            raise ValueError("the message is empty")
-        return [bytes(message)]
-    out = [float(a) for a in np.atleast_1d(np.asarray(alphas, dtype=np.float64))]
-    if not all(0.0 < a <= 1.0 for a in out):
-        raise ValueError(f"alpha outside (0, 1]: {alphas!r}")
-    return out
-
-
-def _write_chunk(fnames, kws, *, stego_method, payloads, stream, out_dir, height, prefetched=None):
-    """One chunk of covers -> their stego images at every payload, written as 8-bit gray PNGs; one list of files.csv rows per cover."""
-    from PIL import Image
-    from . import ops
-    planes = prefetched[0] if prefetched is not None else _embed._prefetch(fnames, kws)[0]
-    cover = torch.from_numpy(np.ascontiguousarray(planes)).to("cuda")
-    method = method_name(stego_method)
-    n, hh, ww = cover.shape
-    rho = ops.hill_cost_f64(cover)
-    seeds = [_embed.image_seed(f, stream) for f in fnames]
-    rows = [[] for _ in fnames]
-    for p in payloads:
-        if isinstance(p, bytes):
-            bits = bits_from_bytes(p)
-            if bits.size > hh * ww:
-                raise ValueError(f"the message has {bits.size} bits, the images {hh * ww} pixels")
-            msg, a = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(bits, (n, bits.size)))), bits.size / (hh * ww)
-        else:
-            msg, a = p, p
-        try:
-            stego = embed(cover, msg, rho=rho, h=height, seeds=seeds, change=CHANGE[method])[0].cpu().numpy()
-        except ValueError as e:
-            raise ValueError(f"{e} (the batch: {[pathlib.Path(f).name for f in fnames]})") from e
-        folder = folder_name(method, a)
-        (pathlib.Path(out_dir) / folder).mkdir(parents=True, exist_ok=True)
-        for i, f in enumerate(fnames):
-            name = f"{folder}/{pathlib.Path(f).stem}.png"
-            Image.fromarray(stego[i]).save(pathlib.Path(out_dir) / name)
-            rows[i].append({"name": name, "height": hh, "width": ww, "stego_method": method, "alpha": float(a)})
-    return rows
-
-
-_write_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(
-    fabrika.shared_kwargs(_write_chunk, ("stego_method", "payloads", "stream", "out_dir", "height"), _embed._prefetch))
+def check_height(who: str, h) -> int:
+    if not 1 <= int(h) <= MAX_H:
+        raise ValueError(f"{who}constraint height h={h} outside 1..{MAX_H}")
+    return int(h)
 
 
 def write_dataset(data_dir, stego_method: str, alpha=None, *, message: typing.Optional[bytes] = None, h: int = 10,
@@ -255,69 +189,63 @@ def write_dataset(data_dir, stego_method: str, alpha=None, *, message: typing.Op
     folders.  Either `alpha` (one value or several, in (0, 1]: k = round(alpha H W) random bits per image) or `message` (bytes, the same in
     every image; the folder's alpha is 8 len(message) / (H W), so the covers must share one size).  A folder's files.csv lists exactly the
     files of this call.  An image in which the code has no solution raises ValueError naming its batch."""
-    import pandas as pd
-    data_dir = pathlib.Path(data_dir)
+    from . import ops
     method = method_name(stego_method)
-    payloads = _payloads(alpha, message)
-    if not 1 <= int(h) <= MAX_H:
-        raise ValueError(f"constraint height h={h} outside 1..{MAX_H}")
-    rows = _write_covers(data_dir, split=split, stego_method=method, payloads=payloads, stream=int(stream), out_dir=str(data_dir), height=int(h))
-    folders = []
-    for j in range(len(payloads)):
-        names = {pathlib.Path(r[j]["name"]).parent.name for r in rows}
-        if len(names) != 1:
-            raise ValueError(f"the covers differ in size, so one message gives several payloads: {sorted(names)}")
-        folder = data_dir / names.pop()
-        pd.DataFrame([r[j] for r in rows], columns=["name", "height", "width", "stego_method", "alpha"]).to_csv(folder / "files.csv", index=False)
-        folders.append(folder)
-    return folders
+    payloads = _embed.payload_list("(0, 1]", alpha, message, with_message=True)
+    h = check_height("", h)
+
+    def make(cover, msg, seeds, rho):
+        return embed(cover, msg, rho=rho, h=h, seeds=seeds, change=CHANGE[method])[0], {}
+
+    return _embed.write_twins(data_dir, method, payloads, make, prepare=ops.hill_cost_f64, split=split, stream=stream)
 
 
 def extract_dataset(data_dir, stego_method: str, alpha: float, bits: int, out_dir, *, h: int = 10, stream: int = 0,
                     batch_size: int = 32) -> typing.List[pathlib.Path]:
     """Reads `bits` message bits from every image the folder of (stego_method, alpha) lists in its files.csv and writes them, packed by
     bytes_from_bits, to `out_dir/<stem>.bin`; returns the files.  Images are read in batches of one size."""
-    import pandas as pd
-    from .imread import read_luma_batch
-    data_dir, out_dir = pathlib.Path(data_dir), pathlib.Path(out_dir)
-    folder = data_dir / folder_name(stego_method, alpha)
-    names = [str(v) for v in pd.read_csv(folder / "files.csv")["name"]]
-    out_dir.mkdir(parents=True, exist_ok=True)
-    written = []
-    for a in range(0, len(names), int(batch_size)):
-        chunk = names[a:a + int(batch_size)]
-        stego = torch.from_numpy(np.ascontiguousarray(read_luma_batch([data_dir / v for v in chunk]))).to("cuda")
-        got = extract(stego, bits, h=h, seeds=[_embed.image_seed(v, stream) for v in chunk]).cpu().numpy()
-        for v, b in zip(chunk, got):
-            written.append(out_dir / f"{pathlib.Path(v).stem}.bin")
-            written[-1].write_bytes(bytes_from_bits(b))
-    return written
+    def read(stego, seeds, rows):
+        return extract(stego, bits, h=h, seeds=seeds).cpu().numpy()
+
+    return _embed.read_twins(data_dir, folder_name(stego_method, alpha), out_dir, read, stream=stream, batch_size=batch_size)
 
 
-def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(description="Embed a message in a data set's covers with a syndrome-trellis code over the HILL cost, and "
-                                             "read it back (STCR flips LSBs, STCM changes by +-1; both on the GPU).")
+def cli_parser(description: str, methods, alphas_help: str, method_default: typing.Optional[str] = None):
+    """The command line stc and stc_ml share: `embed` (--alphas or --message, --split) and `extract` (--alpha, --out), both with --data,
+    --stego-method, --h and --stream -> (the parser, its embed subparser, its extract subparser) for the caller's own options."""
+    ap = argparse.ArgumentParser(description=description)
     sub = ap.add_subparsers(dest="command", required=True)
     for name in ("embed", "extract"):
         p = sub.add_parser(name)
         p.add_argument("--data", required=True, help="data set directory (images*/files.csv)")
-        p.add_argument("--stego-method", required=True, help=" / ".join(METHODS))
+        p.add_argument("--stego-method", required=method_default is None, default=method_default, help=" / ".join(methods))
         p.add_argument("--h", type=int, default=10, help="constraint height 1..10")
         p.add_argument("--stream", type=int, default=0, help="realisation number (embed.image_seed): part of the stego key")
     p = sub.choices["embed"]
     what = p.add_mutually_exclusive_group(required=True)
-    what.add_argument("--alphas", type=float, nargs="+", help="payloads in bits per pixel, (0, 1]: random bits")
+    what.add_argument("--alphas", type=float, nargs="+", help=alphas_help)
     what.add_argument("--message", help="a file whose bytes every cover carries")
     p.add_argument("--split", default=None, help="a split CSV of the data set: only its covers")
     p = sub.choices["extract"]
     p.add_argument("--alpha", type=float, required=True, help="the payload the folder is named after")
-    p.add_argument("--bits", type=int, required=True, help="message bits to read from each image")
     p.add_argument("--out", required=True, help="directory for the recovered bytes, <stem>.bin per image")
+    return ap, sub.choices["embed"], sub.choices["extract"]
+
+
+def cli_embed(ns, write) -> None:
+    """The `embed` command of cli_parser's arguments through a module's write_dataset."""
+    message = pathlib.Path(ns.message).read_bytes() if ns.message else None
+    for folder in write(ns.data, ns.stego_method, ns.alphas, message=message, h=ns.h, split=ns.split, stream=ns.stream):
+        print(folder)
+
+
+def main(argv=None) -> None:
+    ap, _, p = cli_parser("Embed a message in a data set's covers with a syndrome-trellis code over the HILL cost, and read it back (STCR "
+                          "flips LSBs, STCM changes by +-1; both on the GPU).", METHODS, "payloads in bits per pixel, (0, 1]: random bits")
+    p.add_argument("--bits", type=int, required=True, help="message bits to read from each image")
     ns = ap.parse_args(argv)
     if ns.command == "embed":
-        message = pathlib.Path(ns.message).read_bytes() if ns.message else None
-        for folder in write_dataset(ns.data, ns.stego_method, ns.alphas, message=message, h=ns.h, split=ns.split, stream=ns.stream):
-            print(folder)
+        cli_embed(ns, write_dataset)
     else:
         for f in extract_dataset(ns.data, ns.stego_method, ns.alpha, ns.bits, ns.out, h=ns.h, stream=ns.stream):
             print(f)

@@ -22,8 +22,6 @@ compared with another implementation of syndrome-trellis codes.
 """
 from __future__ import annotations
 
-import argparse
-import math
 import pathlib
 import typing
 
@@ -31,10 +29,10 @@ import numpy as np
 import torch
 
 from . import embed as _embed
-from . import fabrika, stc
+from . import stc
 
 METHODS = ("STCT",)
-ALPHA_MAX = math.log2(3.0)                                           # payloads lie below it
+ALPHA_RANGE = "(0, log2 3)"                                          # of embed.ALPHA_RANGES
 REASONS = ("the payload exceeds the capacity", "the high layer has no solution", "the low layer has no solution")
 
 
@@ -47,20 +45,8 @@ def method_name(stego_method: str = "STCT") -> str:
 
 
 def folder_name(stego_method: str, alpha: float) -> str:
-    """`stego_STCT_alpha_<a>_independent_images`, embed.folder_name's scheme."""
-    return f"stego_{method_name(stego_method)}_alpha_{float(alpha)}_independent_images"
-
-
-def _planes(who: str, t) -> typing.Tuple[int, int, int]:
-    if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.uint8):
-        raise ValueError(f"{who}: an (N,H,W) uint8 tensor is expected")
-    return tuple(t.shape)
-
-
-def _height(who: str, h) -> int:
-    if not 1 <= int(h) <= stc.MAX_H:
-        raise ValueError(f"{who}: constraint height h={h} outside 1..{stc.MAX_H}")
-    return int(h)
+    """`stego_STCT_alpha_<a>_independent_images` (embed.twin_folder)."""
+    return _embed.twin_folder(method_name(stego_method), alpha)
 
 
 def _columns_for(h: int, n: int, lengths: torch.Tensor, key: int, dev) -> torch.Tensor:
@@ -85,23 +71,21 @@ def embed(cover_u8: torch.Tensor, message, *, rho: typing.Optional[torch.Tensor]
     The host waits for the device once between the layers: the high layer's entropies decide the lengths k1, and the column table's
     size depends on the shortest of them.  Besides that only `strict` reads anything back."""
     from . import ops
-    n, hh, ww = _planes("embed", cover_u8)
+    n, hh, ww = _embed.planes_shape("embed", cover_u8)
     hw = hh * ww
     dev = cover_u8.device
-    h = _height("embed", h)
+    h = stc.check_height("embed: ", h)
     if isinstance(message, torch.Tensor):
         if message.dtype != torch.uint8 or message.dim() != 2 or message.shape[0] != n:
             raise ValueError(f"embed: message must be an ({n}, k) uint8 tensor of 0 / 1 or a payload in bits per pixel")
         msg = message.to(dev).contiguous()
     else:
-        alpha = float(message)
-        if not 0.0 < alpha < ALPHA_MAX:
-            raise ValueError(f"embed: alpha outside (0, log2 3): {message!r}")
+        alpha = float(_embed.alpha_values(float(message), ALPHA_RANGE, who="embed: ")[0])
         msg = None
     k = msg.shape[1] if msg is not None else int(round(alpha * hw))
     if k < 2:
         raise ValueError(f"embed: k={k} message bits; two layers need at least 2")
-    s = stc._seeds("embed", seeds, n, dev)
+    s = _embed.seeds_tensor("embed", seeds, n, dev)
     if msg is None:
         msg = stc.random_message(seeds, k, dev)
     if rho is None:
@@ -129,14 +113,14 @@ def extract(stego_u8: torch.Tensor, layers, *, h: int = 10, seeds, permute: bool
     """The message of every stego image: ((N, max k) uint8 of 0 / 1, zero past an image's k; k (N) int64), both on the device.  layers:
     (N,2) integers [k1, k0] as `embed` returned them; h, seeds, permute and key as `embed` was given them."""
     from . import ops
-    n, hh, ww = _planes("extract", stego_u8)
+    n, hh, ww = _embed.planes_shape("extract", stego_u8, "stego_u8")
     hw = hh * ww
     dev = stego_u8.device
-    h = _height("extract", h)
+    h = stc.check_height("extract: ", h)
     lay = np.asarray(layers.cpu() if isinstance(layers, torch.Tensor) else layers).astype(np.int64)
     if lay.shape != (n, 2) or (lay < 0).any() or (lay > hw).any() or (lay[:, 1] < 1).any():
         raise ValueError(f"extract: layers must be ({n}, 2) integers [k1, k0] with 0 <= k1 <= {hw} and 1 <= k0 <= {hw}")
-    s = stc._seeds("extract", seeds, n, dev)
+    s = _embed.seeds_tensor("extract", seeds, n, dev)
     both = torch.from_numpy(lay.astype(np.int32)).to(dev)
     k1, k0 = both[:, 0].contiguous(), both[:, 1].contiguous()
     cols = _columns_for(h, hw, both.reshape(-1), key, dev)
@@ -149,58 +133,7 @@ def extract(stego_u8: torch.Tensor, layers, *, h: int = 10, seeds, permute: bool
 
 # ---- whole data sets --------------------------------------------------------------------------------------------------------
 
-COLUMNS = ["name", "height", "width", "stego_method", "alpha", "bits_high", "bits_low"]
-
-
-def _payloads(alphas, message) -> typing.List:
-    """The payloads of one call: floats (alpha) or one bytes object"""
-    if (alphas is None) == (message is None):
-        raise ValueError("give either alpha(s) or a message, not both and not neither")
-    if message is not None:
-        if len(bytes(message)) < 1:
-            raise ValueError("the message is empty")
-        return [bytes(message)]
-    out = [float(a) for a in np.atleast_1d(np.asarray(alphas, dtype=np.float64))]
-    if not all(0.0 < a < ALPHA_MAX for a in out):
-        raise ValueError(f"alpha outside (0, log2 3): {alphas!r}")
-    return out
-
-
-def _write_chunk(fnames, kws, *, payloads, stream, out_dir, height, prefetched=None):
-    """One chunk of covers -> their stego images at every payload, written as 8-bit gray PNGs; one list of files.csv rows per cover."""
-    from PIL import Image
-    from . import ops
-    planes = prefetched[0] if prefetched is not None else _embed._prefetch(fnames, kws)[0]
-    cover = torch.from_numpy(np.ascontiguousarray(planes)).to("cuda")
-    n, hh, ww = cover.shape
-    rho = ops.hill_cost_f64(cover)
-    seeds = [_embed.image_seed(f, stream) for f in fnames]
-    rows = [[] for _ in fnames]
-    for p in payloads:
-        if isinstance(p, bytes):
-            bits = stc.bits_from_bytes(p)
-            if bits.size > hh * ww:
-                raise ValueError(f"the message has {bits.size} bits, the images {hh * ww} pixels")
-            msg, a = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(bits, (n, bits.size)))), bits.size / (hh * ww)
-        else:
-            msg, a = p, p
-        try:
-            stego, _, _, _, layers = embed(cover, msg, rho=rho, h=height, seeds=seeds)
-        except ValueError as e:
-            raise ValueError(f"{e} (the batch: {[pathlib.Path(f).name for f in fnames]})") from e
-        stego, layers = stego.cpu().numpy(), layers.cpu().numpy()
-        folder = folder_name("STCT", a)
-        (pathlib.Path(out_dir) / folder).mkdir(parents=True, exist_ok=True)
-        for i, f in enumerate(fnames):
-            name = f"{folder}/{pathlib.Path(f).stem}.png"
-            Image.fromarray(stego[i]).save(pathlib.Path(out_dir) / name)
-            rows[i].append({"name": name, "height": hh, "width": ww, "stego_method": "STCT", "alpha": float(a),
-                            "bits_high": int(layers[i, 0]), "bits_low": int(layers[i, 1])})
-    return rows
-
-
-_write_covers = fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True)(
-    fabrika.shared_kwargs(_write_chunk, ("payloads", "stream", "out_dir", "height"), _embed._prefetch))
+COLUMNS = [*_embed.CSV_COLUMNS, "bits_high", "bits_low"]
 
 
 def write_dataset(data_dir, stego_method: str = "STCT", alpha=None, *, message: typing.Optional[bytes] = None, h: int = 10,
@@ -210,69 +143,39 @@ def write_dataset(data_dir, stego_method: str = "STCT", alpha=None, *, message: 
     same in every image; the folder's alpha is 8 len(message) / (H W), so the covers must share one size).  A folder's files.csv lists
     exactly the files of this call, with each image's layer lengths in `bits_high` and `bits_low`.  An image that cannot carry the
     payload raises ValueError naming its batch."""
-    import pandas as pd
-    data_dir = pathlib.Path(data_dir)
-    method_name(stego_method)
-    payloads = _payloads(alpha, message)
-    h = _height("write_dataset", h)
-    rows = _write_covers(data_dir, split=split, payloads=payloads, stream=int(stream), out_dir=str(data_dir), height=h)
-    folders = []
-    for j in range(len(payloads)):
-        names = {pathlib.Path(r[j]["name"]).parent.name for r in rows}
-        if len(names) != 1:
-            raise ValueError(f"the covers differ in size, so one message gives several payloads: {sorted(names)}")
-        folder = data_dir / names.pop()
-        pd.DataFrame([r[j] for r in rows], columns=COLUMNS).to_csv(folder / "files.csv", index=False)
-        folders.append(folder)
-    return folders
+    from . import ops
+    method = method_name(stego_method)
+    payloads = _embed.payload_list(ALPHA_RANGE, alpha, message, with_message=True)
+    h = stc.check_height("write_dataset: ", h)
+
+    def make(cover, msg, seeds, rho):
+        stego, _, _, _, layers = embed(cover, msg, rho=rho, h=h, seeds=seeds)
+        layers = layers.cpu().numpy()
+        return stego, {"bits_high": [int(v) for v in layers[:, 0]], "bits_low": [int(v) for v in layers[:, 1]]}
+
+    return _embed.write_twins(data_dir, method, payloads, make, prepare=ops.hill_cost_f64, columns=COLUMNS[len(_embed.CSV_COLUMNS):], split=split,
+                              stream=stream)
 
 
 def extract_dataset(data_dir, stego_method: str, alpha: float, out_dir, *, h: int = 10, stream: int = 0,
                     batch_size: int = 32) -> typing.List[pathlib.Path]:
     """Reads the message of every image the folder of (stego_method, alpha) lists in its files.csv, `bits_high` + `bits_low` bits each, and
     writes them, packed by stc.bytes_from_bits, to `out_dir/<stem>.bin`; returns the files.  Images are read in batches of one size."""
-    import pandas as pd
-    from .imread import read_luma_batch
-    data_dir, out_dir = pathlib.Path(data_dir), pathlib.Path(out_dir)
-    table = pd.read_csv(data_dir / folder_name(stego_method, alpha) / "files.csv")
-    names = [str(v) for v in table["name"]]
-    layers = np.stack([table["bits_high"].to_numpy(np.int64), table["bits_low"].to_numpy(np.int64)], axis=1)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    written = []
-    for a in range(0, len(names), int(batch_size)):
-        chunk = names[a:a + int(batch_size)]
-        stego = torch.from_numpy(np.ascontiguousarray(read_luma_batch([data_dir / v for v in chunk]))).to("cuda")
-        got, ks = extract(stego, layers[a:a + len(chunk)], h=h, seeds=[_embed.image_seed(v, stream) for v in chunk])
-        got, ks = got.cpu().numpy(), ks.cpu().numpy()
-        for v, b, k in zip(chunk, got, ks):
-            written.append(out_dir / f"{pathlib.Path(v).stem}.bin")
-            written[-1].write_bytes(stc.bytes_from_bits(b[:int(k)]))
-    return written
+    def read(stego, seeds, rows):
+        layers = np.stack([rows["bits_high"].to_numpy(np.int64), rows["bits_low"].to_numpy(np.int64)], axis=1)
+        got, ks = extract(stego, layers, h=h, seeds=seeds)
+        return [b[:int(k)] for b, k in zip(got.cpu().numpy(), ks.cpu().numpy())]
+
+    return _embed.read_twins(data_dir, folder_name(stego_method, alpha), out_dir, read, stream=stream, batch_size=batch_size)
 
 
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(description="Embed a message in a data set's covers by +-1 changes with a two-layer syndrome-trellis code "
-                                             "over the HILL cost (STCT), and read it back; both on the GPU.")
-    sub = ap.add_subparsers(dest="command", required=True)
-    for name in ("embed", "extract"):
-        p = sub.add_parser(name)
-        p.add_argument("--data", required=True, help="data set directory (images*/files.csv)")
-        p.add_argument("--stego-method", default="STCT", help=" / ".join(METHODS))
-        p.add_argument("--h", type=int, default=10, help="constraint height 1..10")
-        p.add_argument("--stream", type=int, default=0, help="realisation number (embed.image_seed): part of the stego key")
-    p = sub.choices["embed"]
-    what = p.add_mutually_exclusive_group(required=True)
-    what.add_argument("--alphas", type=float, nargs="+", help="payloads in bits per pixel, (0, log2 3): random bits")
-    what.add_argument("--message", help="a file whose bytes every cover carries")
-    p.add_argument("--split", default=None, help="a split CSV of the data set: only its covers")
-    p = sub.choices["extract"]
-    p.add_argument("--alpha", type=float, required=True, help="the payload the folder is named after")
-    p.add_argument("--out", required=True, help="directory for the recovered bytes, <stem>.bin per image")
+    ap, _, _ = stc.cli_parser("Embed a message in a data set's covers by +-1 changes with a two-layer syndrome-trellis code over the HILL cost "
+                              "(STCT), and read it back; both on the GPU.", METHODS, "payloads in bits per pixel, (0, log2 3): random bits",
+                              method_default="STCT")
     ns = ap.parse_args(argv)
     if ns.command == "embed":
-        message = pathlib.Path(ns.message).read_bytes() if ns.message else None
-        for folder in write_dataset(ns.data, ns.stego_method, ns.alphas, message=message, h=ns.h, split=ns.split, stream=ns.stream):
-            print(folder)
+        stc.cli_embed(ns, write_dataset)
     else:
         for f in extract_dataset(ns.data, ns.stego_method, ns.alpha, ns.out, h=ns.h, stream=ns.stream):
             print(f)
