@@ -776,6 +776,32 @@ int wsu_stc_layer_compose(const uint8_t* cover, const double* rho, const uint8_t
                           const uint8_t* ok1, const uint8_t* ok0, uint8_t* stego, long long* changes, double* distortion, uint8_t* ok,
                           void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream);
 
+/* ---- K48: the directional wavelet cost map of S-UNIWARD (Holub, Fridrich, Denemark, "Universal distortion function for steganography in
+ *      an arbitrary domain", EURASIP JIS 2014) and of WOW (Holub, Fridrich, "Designing steganographic distortion using directional
+ *      filters", WIFS 2012); not part of the reference; ws_unet_amd.costs drives it, tests/costs_np.py restates it.  All float64.
+ *        filter:   p[0..15] = the Daubechies-8 orthonormal scaling filter, minimum phase, sum p = sqrt 2 (p[0] = 0.0544158422...; the
+ *                  literals of ws_unet_amd.costs.DB8, derived by tools/db8_taps.py);  l[j] = p[15 - j];  h[j] = (-1)^(j+1) p[j].
+ *        bands:    F_k[u,v] = a_k[u] b_k[v], u down the rows, v along the columns:  (a,b)_1 = (l,h),  (a,b)_2 = (h,l),  (a,b)_3 = (h,h).
+ *        padding:  X~ = the cover as float64 under numpy.pad(mode='symmetric'), the periodic fold of K20 (planes smaller than the pad
+ *                  are defined).  Indices are unpadded coordinates.
+ *        forward:  r_b[y,n]  = sum_{v=0..15} b[v] X~[y, n+8-v]          for b in {l, h},  n in [-8, W+6],  y in [-15, H+14]
+ *                  W_k[m,n]  = sum_{u=0..15} a_k[u] r_bk[m+8-u, n]      m in [-8, H+6]
+ *        g_k:      S-UNIWARD  1 / (|W_k| + sigma), sigma > 0;     WOW  |W_k|
+ *        back:     t_k[m,j]  = sum_v |b_k[v]| g_k[m, j-8+v]             xi_k[i,j] = sum_u |a_k[u]| t_k[i-8+u, j],   i < H, j < W
+ *        merge:    S-UNIWARD  rho = (xi_1 + xi_2) + xi_3;         WOW  rho = (1/xi_1 + 1/xi_2) + 1/xi_3  (a flat neighbourhood has xi = 0,
+ *                  1/0 = +inf);     both, as K20:  rho <= clamp ? rho : clamp  (inf | nan | > clamp -> clamp).
+ *      Every sum starts at +0.0 and adds its taps in ascending order; a product and its addition round separately; the divisions are
+ *      IEEE divisions; no library function is called: the plane equals the numpy restatement bit for bit, and an image's plane does not
+ *      depend on the batch.  rho[i,j] sums |F_k[u,v]| g over exactly the 3 * 256 coefficients that pixel (i,j) enters with weight
+ *      F_k[u,v]: for S-UNIWARD that is the authors' D(X, X +- e_ij) wherever the pixel does not meet its own mirror image in the padding
+ *      (tests/test_costs_host.py).  The published codes' clamps (1e8, 1e10), their pad of 16, sigma = 1 and this alignment are as
+ *      remembered; no run was compared with them.
+ *      x_u8: DEVICE (N,H,W) uint8; rho: DEVICE (N,H,W) float64, 8-byte aligned; H, W >= 1, H*W < 2^32, N <= 65535.  sigma is ignored
+ *      by WOW.  0 < clamp < inf.  Every argument is checked before any HIP call. */
+#define WSU_COST_SUNIWARD 0
+#define WSU_COST_WOW 1
+int wsu_wavelet_cost_f64(const uint8_t* x_u8, double* rho, int kind, double sigma, double clamp, int n, int h, int w, void* stream);
+
 /* ---- K31, K32: the JPEG history of a bitmap (Boehme, "Weighted stego-image steganalysis for JPEG covers", IH 2008; not part of the
  *      reference): which quantisation table an image was compressed with, and the image after a round trip through a table -- the WS
  *      predictor for covers that were a JPEG once (the quantiser rounds the +-1 embedding noise away).  All arithmetic is exact integers:

@@ -149,6 +149,7 @@ SIGNATURES = {
     "wsu_stc_layer_high": (c_int, [_P] * 7 + [c_size_t, c_int, c_int, c_int, _P]),
     "wsu_stc_layer_low": (c_int, [_P] * 7 + [c_int, c_int, c_int, _P]),
     "wsu_stc_layer_compose": (c_int, [_P] * 12 + [c_size_t, c_int, c_int, c_int, _P]),
+    "wsu_wavelet_cost_f64": (c_int, [_P, _P, c_int, c_double, c_double, c_int, c_int, c_int, _P]),
     "wsu_jpeg_energies": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, _P]),
     "wsu_jpeg_predict": (c_int, [_P] * 5 + [c_int] * 3 + [_P]),
     "wsu_ws_meter_beta": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),

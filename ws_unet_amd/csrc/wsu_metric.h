@@ -158,22 +158,24 @@ __device__ __forceinline__ int sym_fold(int j, int n) {
     m = m < 0 ? m + p : m;
     return m < n ? m : p - 1 - m;
 }
-// One 256-thread workgroup stages the (TILE+18)^2 uint8 window of the tile at (r0, c0) -- x padded by 9, 'symmetric' -- into `xs`: LDS row
-// stride TILE + 32, window column wc at wc + 7, so that a tile well inside the image is copied as 16-byte row segments (vec_in: rows and
-// base 16-byte aligned); every other tile reads through the fold.  The caller's barrier follows.
-template <int TILE> __device__ __forceinline__ void hill_stage_window(const uint8_t* __restrict__ img, uint8_t* xs, int r0, int c0,
-                                                                      int h, int w, int vec_in, int tid) {
-    constexpr int X = TILE + 18, XS = TILE + 32, SEGS = XS / 16;
-    if (vec_in && r0 - 9 >= 0 && r0 + TILE + 9 <= h && c0 - 16 >= 0 && c0 + TILE + 16 <= w) {
+// One 256-thread workgroup stages the X x X uint8 window of the tile at (r0, c0) -- x padded 'symmetric', BEFORE rows / columns in front of the
+// tile; K12 and K20: pad 9 on every side, (TILE+18)^2 -- into `xs`: LDS row stride TILE + 32, window column wc at wc + 16 - BEFORE, so that a
+// tile well inside the image is copied as 16-byte row segments (vec_in: rows and base 16-byte aligned); every other tile reads through the
+// fold.  The caller's barrier follows.
+template <int TILE, int BEFORE = 9, int X = TILE + 18> __device__ __forceinline__ void hill_stage_window(const uint8_t* __restrict__ img, uint8_t* xs,
+                                                                                                       int r0, int c0, int h, int w, int vec_in, int tid) {
+    constexpr int XS = TILE + 32, SEGS = XS / 16, OFF = 16 - BEFORE;
+    static_assert(BEFORE <= 16 && X - BEFORE <= TILE + 16, "the window must lie inside the 16-byte segments around the tile");
+    if (vec_in && r0 - BEFORE >= 0 && r0 - BEFORE + X <= h && c0 - 16 >= 0 && c0 + TILE + 16 <= w) {
         for (int i = tid; i < X * SEGS; i += 256) {
             const int wr = i / SEGS, seg = i % SEGS;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(img + (size_t)(r0 - 9 + wr) * w + (c0 - 16 + seg * 16));
+            const u32x4 v = *reinterpret_cast<const u32x4*>(img + (size_t)(r0 - BEFORE + wr) * w + (c0 - 16 + seg * 16));
             *reinterpret_cast<u32x4*>(xs + wr * XS + seg * 16) = v;
         }
     } else {
         for (int i = tid; i < X * X; i += 256) {
             const int wr = i / X, wc = i % X;
-            xs[wr * XS + wc + 7] = img[(size_t)sym_fold(r0 - 9 + wr, h) * w + sym_fold(c0 - 9 + wc, w)];
+            xs[wr * XS + wc + OFF] = img[(size_t)sym_fold(r0 - BEFORE + wr, h) * w + sym_fold(c0 - BEFORE + wc, w)];
         }
     }
 }

@@ -1480,6 +1480,24 @@ def hill_cost_f64(x_u8: torch.Tensor, clamp: float = 1e10) -> torch.Tensor:
     return key
 
 
+WAVELET_COST_KINDS = {"suniward": 0, "wow": 1}                      # WSU_COST_* of include/wsu.h
+WAVELET_COST_CLAMPS = {"suniward": 1e8, "wow": 1e10}
+
+
+def wavelet_cost_f64(x_u8: torch.Tensor, kind: str, sigma: float = 1.0, clamp: Optional[float] = None) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,H,W) fp64 S-UNIWARD (`kind` 'suniward') or WOW ('wow') cost, bit-identical to numpy's float64
+    restatement (wsu_wavelet_cost_f64, K48).  sigma: S-UNIWARD's stabilising constant; clamp: None takes the kind's default (1e8, 1e10)."""
+    lib = _lib.load()
+    n, h, w = _u8_planes(x_u8)
+    if kind not in WAVELET_COST_KINDS:
+        raise ValueError(f"kind must be one of {' / '.join(WAVELET_COST_KINDS)}, got {kind!r}")
+    rho = torch.empty((n, h, w), dtype=torch.float64, device=x_u8.device)
+    check(_launch("wavelet_cost_f64", {"bytes": float(n * h * w * 9)}, lambda: lib.wsu_wavelet_cost_f64(
+        x_u8.data_ptr(), rho.data_ptr(), WAVELET_COST_KINDS[kind], float(sigma), float(WAVELET_COST_CLAMPS[kind] if clamp is None else clamp),
+        n, h, w, _stream())), "wsu_wavelet_cost_f64")
+    return rho
+
+
 def rank_select_f64(key: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
     """key: (N,H,W) fp64, positive and finite; k: (N) int64 ranks on the device -> (N) int64 holding the uint64 pattern of each
     image's key of rank k (0-based, ascending; negative: the pattern 0, below every key), by an exact radix select (K21)."""
