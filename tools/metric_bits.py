@@ -1,4 +1,4 @@
-"""Bit-level record of the metric kernels (K10-K19, filter3x3_valid, lsb_delta_unit, the WS meter) on fixed synthetic inputs.
+"""Bit-level record of the metric kernels (K10-K19, K27, K29, K33, filter3x3_valid, lsb_delta_unit, the WS meter) on fixed synthetic inputs.
 
   python tools/metric_bits.py OUT.json          run every op once and write, per output tensor, the SHA-256 of its bytes; rows whose
                                                 float32 sequence has an inexact product (`may_move`) also keep their values and their
@@ -113,6 +113,32 @@ def main(out_path) -> None:
         ref = ws_ref.filter_infere_single(small[0][..., None], K[name])[None, ..., 0]
         put(f"filter3x3_valid {name}", ops.filter3x3_valid(torch.from_numpy(small).to(dev), K[name]), name == "AVG9", ref)
     put("lsb_delta_unit", ops.lsb_delta_unit(x))
+
+    # K27, K29, K33: integer outputs (none may move), each of the three prediction sources with both weights
+    kernels = np.stack([np.asarray(K[name])[..., 0] for name in ("KB", "AVG", "AVG9")]).astype(F32)
+    m = (h - 2) * (w - 2)
+    assert m > 2048                                              # more than one chunk of K33's fold
+    path_rng = np.random.default_rng(135)
+    path = torch.from_numpy(np.stack([path_rng.permutation(m) for _ in range(n)]).astype(np.int32)).to(dev)
+    for src, kw in (("KB", {"pixel_filter": K["KB"]}), ("per-image", {"pixel_filter": kernels}), ("x_hat", {"x_hat": y, "hat_scale": 255.})):
+        for wgt in (0, 1):
+            kw = dict(kw, mean_filter=K["AVG"], weighted=wgt)
+            tag = f"source={src} weighted={wgt}"
+            for order in ops.ORDERS:
+                for label, t in zip(("k", "t_max", "t_all", "curve"), ops.ws_sequential(x, order=order, return_curve=True, **kw)):
+                    put(f"K27 ws_sequential {tag} order={order} {label}", t)
+            for parts in (1, 4):
+                num, den = (torch.zeros((h - 2, w - 2), dtype=torch.int64, device=dev) for _ in range(2))
+                ops.ws_residual_accumulate(x, num, den, parts=parts, **kw)
+                put(f"K29 ws_residual_accumulate {tag} parts={parts} num", num)
+                put(f"K29 ws_residual_accumulate {tag} parts={parts} den", den)
+            for rate in (1.0, 0.5):
+                terms = ops.ws_ordered_terms(x, flip_rate=rate, **kw)
+                put(f"K33 ws_ordered_terms {tag} flip_rate={rate}", terms)
+                for label, t in zip(("k", "t_max", "t_all"), ops.ws_ordered_fold(terms, path, h, w)):
+                    put(f"K33 ws_ordered_fold {tag} flip_rate={rate} {label}", t)
+                for label, t in zip(("k", "t_max", "t_all"), ops.ws_ordered(x, path, flip_rate=rate, **kw)):
+                    put(f"K33 ws_ordered {tag} flip_rate={rate} {label}", t)
 
     # K12-K14
     cost = ops.hill_cost(x)

@@ -26,28 +26,19 @@ using Taps = Taps3x3<float>;
 // true convolution, 'valid': out(r,c) = sum_{a,b} K[a][b] * v(r+1-a, c+1-b), summed in the order K00 .. K22
 __device__ __forceinline__ float conv9(const Taps& t, const float v[3][3]) { return conv9_f32<true>(t, v); }
 
-__global__ __launch_bounds__(256) void ws_attack_partial_kernel(
-    const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, const float* __restrict__ xbias,
-    Taps mean_taps, Taps pixel_taps, const float* __restrict__ image_filters, int use_pixel_filter, int hat_full, float hat_scale,
-    int weighted, int correct_bias, double* __restrict__ partial, int h, int w) {
+__global__ __launch_bounds__(256) void ws_attack_partial_kernel(const uint8_t* __restrict__ xu8, WsSource src, double* __restrict__ partial,
+                                                                int h, int w) {
     __shared__ double red[3][256];
-    __shared__ float unit[256];                          // u / 255.f of every uint8 value: one IEEE division per thread, not nine per pixel
+    __shared__ float unit[256];                          // u / 255.f of every uint8 value (ws_unit_table)
     const int nn = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
     const uint8_t* img = xu8 + (size_t)nn * h * w;
-    if (image_filters) {                                 // one filter per image, K[a][b] like taps_from_kernel's input (uniform: nn = blockIdx.y)
-#pragma unroll
-        for (int i = 0; i < 9; ++i) pixel_taps.k[8 - i] = image_filters[(size_t)nn * 9 + i];
-    }
-    if (use_pixel_filter) {                              // (uniform over the workgroup)
-        unit[tid] = (float)tid / 255.0f;
-        __syncthreads();
-    }
-    const size_t hbase = hat_base(hat_full, nn, h, w);
+    const Taps taps = ws_source_taps(src, nn);
+    ws_unit_table(src, unit, tid);
+    const size_t hbase = hat_base(src.hat_full, nn, h, w);
     double sw = 0.0, sb = 0.0, sc = 0.0;
     for (int r = 1 + part; r <= h - 2; r += WSA_PARTS) {
         for (int c = 1 + tid; c <= w - 2; c += 256) {
-            const WsTerms t = ws_pixel_terms(img, xhat, xbias, unit, mean_taps, pixel_taps, use_pixel_filter, hat_full, hbase, hat_scale,
-                                             weighted, correct_bias, r, c, w);
+            const WsTerms t = ws_pixel_terms(img, src, taps, unit, hbase, r, c, w);
             const float ws = t.wgt * t.s;
             sw += (double)t.wgt;
             sb += (double)(ws * t.res);
@@ -99,18 +90,16 @@ __global__ __launch_bounds__(256) void filter3x3_valid_kernel(const float* __res
     }
 }
 
-// the two launches behind wsu_ws_attack (one filter, or a prediction) and wsu_ws_attack_taps (image_filters: DEVICE, one filter per image)
-int ws_attack_launch(const uint8_t* x_u8, const float* x_hat, const float* x_bias, const Taps& mt, const Taps& pt, const float* image_filters,
-                     int use_pixel_filter, int hat_full, float hat_scale, int weighted, int correct_bias, float* beta_hat, double* sums,
-                     double* partial, int n, int h, int w, hipStream_t s) {
-    hipLaunchKernelGGL(ws_attack_partial_kernel, dim3(WSA_PARTS, n), dim3(256), 0, s, x_u8, x_hat, x_bias, mt, pt, image_filters,
-                       use_pixel_filter, hat_full, hat_scale, weighted, correct_bias, partial, h, w);
+// the two launches behind wsu_ws_attack (one filter, or a prediction) and wsu_ws_attack_taps (one filter per image)
+int ws_attack_launch(const uint8_t* x_u8, const WsSource& src, float* beta_hat, double* sums, void* workspace, int n, int h, int w, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* partial = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(ws_attack_partial_kernel, dim3(WSA_PARTS, n), dim3(256), 0, s, x_u8, src, partial, h, w);
     int rc = wsu_check_launch("ws_attack_partial_kernel");
     if (rc) return rc;
-    hipLaunchKernelGGL(ws_attack_finish_kernel, dim3(n), dim3(WSA_PARTS), 0, s, partial, beta_hat, sums, correct_bias);
+    hipLaunchKernelGGL(ws_attack_finish_kernel, dim3(n), dim3(WSA_PARTS), 0, s, partial, beta_hat, sums, src.correct_bias);
     return wsu_check_launch("ws_attack_finish_kernel");
 }
-
 }  // namespace
 
 extern "C" {
@@ -121,26 +110,23 @@ int wsu_ws_attack(const uint8_t* x_u8, const float* x_hat, const float* x_bias, 
                   int hat_full, float hat_scale, int weighted, int correct_bias, float* beta_hat, double* sums,
                   void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(x_u8 && beta_hat && workspace, "ws_attack: null pointer");
-    WSU_REQUIRE((x_hat != nullptr) != (pixel_filter != nullptr), "ws_attack: give exactly one of x_hat / pixel_filter");
-    WSU_REQUIRE(weighted >= -1 && weighted <= 1, "ws_attack: weighted=%d outside {-1,0,1}", weighted);
-    WSU_REQUIRE(weighted == 0 || mean_filter, "ws_attack: weighted estimate needs mean_filter");
-    WSU_REQUIRE(!correct_bias || pixel_filter || x_bias, "ws_attack: correct_bias needs x_bias = pixel_estimator(x_bar - x)");
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, "ws_attack: bad shape n=%d h=%d w=%d", n, h, w);
+    WsSource src;
+    int rc = ws_source_make(src, "ws_attack", "the estimate", true, x_hat, x_bias, pixel_filter, nullptr, mean_filter, hat_full, hat_scale,
+                            weighted, correct_bias, n, h, w, 0);                  // (no cap: K11 indexes with size_t and sums in fp64)
+    if (rc) return rc;
     WSU_REQUIRE(workspace_bytes >= wsu_ws_attack_workspace_bytes(n), "ws_attack: workspace too small");
-    const Taps mt = taps_from_kernel(mean_filter), pt = taps_from_kernel(pixel_filter);
-    return ws_attack_launch(x_u8, x_hat, x_bias, mt, pt, nullptr, pixel_filter ? 1 : 0, hat_full, hat_scale, weighted, correct_bias, beta_hat,
-                            sums, static_cast<double*>(workspace), n, h, w, static_cast<hipStream_t>(stream));
+    return ws_attack_launch(x_u8, src, beta_hat, sums, workspace, n, h, w, stream);
 }
 
 int wsu_ws_attack_taps(const uint8_t* x_u8, const float* pixel_filters, const float* mean_filter, int weighted, int correct_bias,
                        float* beta_hat, double* sums, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(x_u8 && pixel_filters && beta_hat && workspace, "ws_attack_taps: null pointer");
-    WSU_REQUIRE(weighted >= -1 && weighted <= 1, "ws_attack_taps: weighted=%d outside {-1,0,1}", weighted);
-    WSU_REQUIRE(weighted == 0 || mean_filter, "ws_attack_taps: weighted estimate needs mean_filter");
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, "ws_attack_taps: bad shape n=%d h=%d w=%d", n, h, w);
+    WsSource src;
+    int rc = ws_source_make(src, "ws_attack_taps", "the estimate", true, nullptr, nullptr, nullptr, pixel_filters, mean_filter, 1, 255.0f,
+                            weighted, correct_bias, n, h, w, 0);
+    if (rc) return rc;
     WSU_REQUIRE(workspace_bytes >= wsu_ws_attack_workspace_bytes(n), "ws_attack_taps: workspace too small");
-    return ws_attack_launch(x_u8, nullptr, nullptr, taps_from_kernel(mean_filter), Taps{}, pixel_filters, 1, 1, 255.0f, weighted, correct_bias,
-                            beta_hat, sums, static_cast<double*>(workspace), n, h, w, static_cast<hipStream_t>(stream));
+    return ws_attack_launch(x_u8, src, beta_hat, sums, workspace, n, h, w, stream);
 }
 
 int wsu_filter3x3_valid_f32(const float* x, const float* filter, float* y, int n, int h, int w, void* stream) {

@@ -23,30 +23,25 @@
 namespace {
 
 constexpr int WSL_FILL = 4096;                           // automatic parts: as many as bring the grid to about this many workgroups (16 waves per SIMD)
-using Taps = Taps3x3<float>;
 
+// (loose parameters, the struct put together inside: as K27's rows kernel, ws_sequential.hip says why; with a WsSource argument and a local
+// copy of the taps this kernel took two more SGPRs and measured 0.1-0.4 us slower than the bound allows, profiles/r35)
 __global__ __launch_bounds__(256) void ws_residual_accumulate_kernel(
-    const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, Taps mean_taps, Taps pixel_taps, const float* __restrict__ image_filters,
-    int use_pixel_filter, int hat_full, float hat_scale, int weighted, long long* __restrict__ num, long long* __restrict__ den, int n, int h,
-    int w) {
-    __shared__ float unit[256];                          // u / 255.f of every uint8 value (K11)
+    const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, Taps3x3<float> mean_taps, Taps3x3<float> pixel_taps,
+    const float* __restrict__ image_filters, int use_pixel_filter, int hat_full, float hat_scale, int weighted, long long* __restrict__ num,
+    long long* __restrict__ den, int n, int h, int w) {
+    __shared__ float unit[256];                          // u / 255.f of every uint8 value (ws_unit_table)
+    const WsSource src{xhat, nullptr, image_filters, mean_taps, pixel_taps, use_pixel_filter, hat_full, hat_scale, weighted, 0};
     const int tid = threadIdx.x;
-    if (use_pixel_filter) {                              // (uniform over the workgroup)
-        unit[tid] = (float)tid / 255.0f;
-        __syncthreads();
-    }
+    ws_unit_table(src, unit, tid);
     const int iw = w - 2;
     const long long m = (long long)(h - 2) * iw, i = (long long)blockIdx.x * 256 + tid;
     if (i >= m) return;
     const int r = (int)(i / iw) + 1, c = (int)(i % iw) + 1;
     long long a = 0, b = 0;
     for (int nn = blockIdx.y; nn < n; nn += gridDim.y) {
-        if (image_filters) {                             // one filter per image
-#pragma unroll
-            for (int j = 0; j < 9; ++j) pixel_taps.k[8 - j] = image_filters[(size_t)nn * 9 + j];
-        }
-        const WsTerms p = ws_pixel_terms(xu8 + (size_t)nn * h * w, xhat, nullptr, unit, mean_taps, pixel_taps, use_pixel_filter, hat_full,
-                                         hat_base(hat_full, nn, h, w), hat_scale, weighted, 0, r, c, w);
+        if (image_filters) pixel_taps = ws_source_taps(src, nn);     // (src keeps the launch's taps; they are not read once there are per-image ones)
+        const WsTerms p = ws_pixel_terms(xu8 + (size_t)nn * h * w, src, pixel_taps, unit, hat_base(hat_full, nn, h, w), r, c, w);
         const float rr = p.s * p.res;
         const float t = p.wgt * rr;
         if (t == t) {                                    // a NaN term adds to neither sum
@@ -71,23 +66,18 @@ int wsu_ws_residual_accumulate(const uint8_t* x_u8, const float* x_hat, const fl
                                const float* mean_filter, int hat_full, float hat_scale, int weighted, int parts, long long* num, long long* den,
                                int n, int h, int w, void* stream) {
     WSU_REQUIRE(x_u8 && num && den, "ws_residual_accumulate: null pointer");
-    WSU_REQUIRE((x_hat != nullptr) + (pixel_filter != nullptr) + (pixel_filters != nullptr) == 1,
-                "ws_residual_accumulate: give exactly one of x_hat / pixel_filter / pixel_filters");
-    WSU_REQUIRE(weighted != -1, "ws_residual_accumulate: weighted=-1 (weights 5 + var) is not defined for the residual means");
-    WSU_REQUIRE(weighted == 0 || weighted == 1, "ws_residual_accumulate: weighted=%d outside {0,1}", weighted);
-    WSU_REQUIRE(weighted == 0 || mean_filter, "ws_residual_accumulate: weighted sums need mean_filter");
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, "ws_residual_accumulate: bad shape n=%d h=%d w=%d", n, h, w);
-    WSU_REQUIRE((long long)(h - 2) * (w - 2) <= (1LL << 31), "ws_residual_accumulate: %lld interior pixels per image exceed 2^31",
-                (long long)(h - 2) * (w - 2));
+    WsSource src;
+    int rc = ws_source_make(src, "ws_residual_accumulate", "the residual means", false, x_hat, nullptr, pixel_filter, pixel_filters, mean_filter,
+                            hat_full, hat_scale, weighted, 0, n, h, w, 31);
+    if (rc) return rc;
     WSU_REQUIRE(parts >= 0 && parts <= 65535, "ws_residual_accumulate: parts=%d outside 0 (automatic) .. 65535", parts);
     WSU_REQUIRE((uintptr_t)num % 8 == 0 && (uintptr_t)den % 8 == 0, "ws_residual_accumulate: accumulators must be 8-byte aligned");
     const long long blocks = ((long long)(h - 2) * (w - 2) + 255) / 256;
     if (parts == 0) parts = (int)(blocks >= WSL_FILL ? 1 : WSL_FILL / blocks);
     if (parts > n) parts = n;
-    const int filtered = x_hat ? 0 : 1;
-    hipLaunchKernelGGL(ws_residual_accumulate_kernel, dim3((unsigned)blocks, parts), dim3(256), 0, static_cast<hipStream_t>(stream), x_u8, x_hat,
-                       taps_from_kernel(mean_filter), taps_from_kernel(pixel_filter), pixel_filters, filtered, filtered ? 1 : hat_full,
-                       filtered ? 255.0f : hat_scale, weighted, num, den, n, h, w);
+    hipLaunchKernelGGL(ws_residual_accumulate_kernel, dim3((unsigned)blocks, parts), dim3(256), 0, static_cast<hipStream_t>(stream), x_u8, src.xhat,
+                       src.mean_taps, src.pixel_taps, src.image_filters, src.use_pixel_filter, src.hat_full, src.hat_scale, src.weighted, num, den,
+                       n, h, w);
     return wsu_check_launch("ws_residual_accumulate_kernel");
 }
 

@@ -16,10 +16,9 @@
 //
 // Kernel A (terms): K27's walk without its reduction: one wave per interior row, lane l computes pixels l, 64 + l, .., so the pixel loads
 //   and the 8-byte stores of the term plane (N,M) are coalesced.  Kernel B (fold): one wave per chunk of 4 x 512 consecutive path
-//   positions.  Per step the wave reads 512 path entries coalesced (lane l: 64 j + l), gathers their terms, and passes them through its own
-//   LDS strip so that lane l folds the eight CONSECUTIVE terms 8 l .. 8 l + 7 serially; one ordered shuffle tree over the 64 triples
-//   finishes the step, lane 0 folds the steps -> one triple per chunk, arg counted from the path's start.  Kernel C (finish): one workgroup
-//   per image, thread t folds a contiguous run of chunks, an ordered tree over the 256 threads finishes.
+//   positions.  Per step (ws_fold_step, wsu_metric.h, K27's) the wave reads 512 path entries coalesced (lane l: 64 j + l) and gathers their
+//   terms; lane 0 folds the steps -> one triple per chunk, arg counted from the path's start.  Kernel C (finish): one workgroup per image,
+//   thread t folds a contiguous run of chunks, an ordered tree over the 256 threads finishes (mp_block_finish).
 // A path entry outside 0..M-1 is never dereferenced: it is compared as unsigned against M and contributes a zero term, as does a
 // position past the path's end.  Integer terms make the result independent of the split and of the batch; no atomics at all.
 // Traffic: A as K27's plus 8 B per pixel written; B 4 B (path) + 8 B (gathered term: the plane of one 512 x 512 image is 2 MB) per pixel.
@@ -29,34 +28,26 @@
 namespace {
 
 constexpr int WSO_PARTS = 64;                           // kernel A: workgroups per image, four rows (waves) each per pass
-constexpr int WSO_PER = 8;                              // consecutive path positions a lane folds serially per step
-constexpr int WSO_STEP = 64 * WSO_PER;                  // path positions per wave step
 constexpr int WSO_STEPS = 4;                            // steps per chunk
-constexpr int WSO_CHUNK = WSO_STEP * WSO_STEPS;         // path positions per wave = per triple of the workspace
-constexpr int WSO_PITCH = WSO_PER + 1;                  // LDS pitch of a lane's run in 8-byte words (K27's: 72 B)
-using Taps = Taps3x3<float>;
+constexpr int WSO_CHUNK = WS_FOLD_STEP * WSO_STEPS;     // path positions per wave = per triple of the workspace
 
+// (loose parameters, the struct put together inside: as K27's rows kernel, ws_sequential.hip says why)
 __global__ __launch_bounds__(256) void ws_ordered_terms_kernel(
-    const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, Taps mean_taps, Taps pixel_taps, const float* __restrict__ image_filters,
-    int use_pixel_filter, int hat_full, float hat_scale, int weighted, float tau, long long* __restrict__ terms, int h, int w) {
-    __shared__ float unit[256];                          // u / 255.f of every uint8 value (K11)
+    const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, Taps3x3<float> mean_taps, Taps3x3<float> pixel_taps,
+    const float* __restrict__ image_filters, int use_pixel_filter, int hat_full, float hat_scale, int weighted, float tau,
+    long long* __restrict__ terms, int h, int w) {
+    __shared__ float unit[256];                          // u / 255.f of every uint8 value (ws_unit_table)
+    const WsSource src{xhat, nullptr, image_filters, mean_taps, pixel_taps, use_pixel_filter, hat_full, hat_scale, weighted, 0};
     const int nn = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint8_t* img = xu8 + (size_t)nn * h * w;
-    if (image_filters) {                                 // one filter per image (uniform: nn = blockIdx.y)
-#pragma unroll
-        for (int i = 0; i < 9; ++i) pixel_taps.k[8 - i] = image_filters[(size_t)nn * 9 + i];
-    }
-    if (use_pixel_filter) {                              // (uniform over the workgroup)
-        unit[tid] = (float)tid / 255.0f;
-        __syncthreads();
-    }
-    const size_t hbase = hat_base(hat_full, nn, h, w);
+    if (image_filters) pixel_taps = ws_source_taps(src, nn);                             // (uniform: nn = blockIdx.y)
+    ws_unit_table(src, unit, tid);
+    const size_t hbase = hat_base(src.hat_full, nn, h, w);
     const int ih = h - 2, iw = w - 2;
     long long* out = terms + (size_t)nn * ih * iw;
     for (int r = 1 + (int)blockIdx.x * 4 + wave; r <= ih; r += WSO_PARTS * 4) {          // (uniform over the wave)
         for (int i = lane; i < iw; i += 64) {
-            const WsTerms p = ws_pixel_terms(img, xhat, nullptr, unit, mean_taps, pixel_taps, use_pixel_filter, hat_full, hbase, hat_scale,
-                                             weighted, 0, r, i + 1, w);
+            const WsTerms p = ws_pixel_terms(img, src, pixel_taps, unit, hbase, r, i + 1, w);
             const float rr = p.s * p.res;
             const float d = rr - tau;
             const float t = p.wgt * d;
@@ -67,7 +58,7 @@ __global__ __launch_bounds__(256) void ws_ordered_terms_kernel(
 
 __global__ __launch_bounds__(256) void ws_ordered_fold_kernel(const long long* __restrict__ terms, const int* __restrict__ path,
                                                               long long* __restrict__ parts, int m, int chunks) {
-    __shared__ long long strip[4][64 * WSO_PITCH];       // per wave: the step's terms, term i at i + i / WSO_PER
+    __shared__ long long strip[4][WS_FOLD_STRIP];        // per wave: the step's terms
     const int nn = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int chunk = (int)blockIdx.x * 4 + wave;
     if (chunk >= chunks) return;                         // (uniform over the wave; no workgroup barrier below)
@@ -75,52 +66,31 @@ __global__ __launch_bounds__(256) void ws_ordered_fold_kernel(const long long* _
     const int* pa = path + (size_t)nn * m;
     long long* st = strip[wave];
     MaxPrefix<int> run{0, 0, chunk * WSO_CHUNK};         // (lane 0's is the chunk's)
-    for (int c0 = chunk * WSO_CHUNK; c0 < (chunk + 1) * WSO_CHUNK && c0 < m; c0 += WSO_STEP) {
-        for (int j = 0; j < WSO_PER; ++j) {
+    for (int c0 = chunk * WSO_CHUNK; c0 < (chunk + 1) * WSO_CHUNK && c0 < m; c0 += WS_FOLD_STEP) {
+        for (int j = 0; j < WS_FOLD_PER; ++j) {
             const int at = 64 * j + lane, i = c0 + at;
             long long v = 0;                             // past the path's end, or no pixel of the plane: 0, which never wins on the right
             if (i < m) {
                 const unsigned p = (unsigned)pa[i];
                 if (p < (unsigned)m) v = q[p];
             }
-            st[at + at / WSO_PER] = v;
+            st[at + at / WS_FOLD_PER] = v;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const int first = c0 + lane * WSO_PER;
-        MaxPrefix<int> e{0, 0, first};
-#pragma unroll
-        for (int j = 0; j < WSO_PER; ++j) {
-            e.sum += st[lane * WSO_PITCH + j];
-            if (e.sum > e.best) { e.best = e.sum; e.arg = first + j + 1; }               // >: among equal maxima the first
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                           // (the next step's writes stay behind these reads)
-        __builtin_amdgcn_wave_barrier();
-        run = mp_combine(run, mp_wave(e));
+        run = mp_combine(run, ws_fold_step(st, lane, c0));
     }
-    if (lane == 0) {
-        long long* o = parts + ((size_t)nn * chunks + chunk) * 3;
-        o[0] = run.sum; o[1] = run.best; o[2] = run.arg;
-    }
+    if (lane == 0) mp_store(parts + ((size_t)nn * chunks + chunk) * 3, run);
 }
 
 __global__ __launch_bounds__(256) void ws_ordered_finish_kernel(const long long* __restrict__ parts, long long* __restrict__ k,
                                                                 long long* __restrict__ t_max, long long* __restrict__ t_all, int chunks) {
-    __shared__ MaxPrefix<long long> wv[4];
     const int nn = blockIdx.x, tid = threadIdx.x;
     const long long* img = parts + (size_t)nn * chunks * 3;
     const int per = (chunks + 255) / 256;                // chunks per thread, contiguous
     const long long p0 = (long long)tid * per;
     const long long p1 = p0 + per < chunks ? p0 + per : chunks;
     MaxPrefix<long long> run{0, 0, p0 * WSO_CHUNK};
-    for (long long p = p0; p < p1; ++p) run = mp_combine(run, MaxPrefix<long long>{img[p * 3], img[p * 3 + 1], img[p * 3 + 2]});
-    run = mp_wave(run);
-    if ((tid & 63) == 0) wv[tid >> 6] = run;
-    __syncthreads();
-    if (tid == 0) {
-        const MaxPrefix<long long> all = mp_combine(mp_combine(wv[0], wv[1]), mp_combine(wv[2], wv[3]));
-        k[nn] = all.arg; t_max[nn] = all.best; t_all[nn] = all.sum;
-    }
+    for (long long p = p0; p < p1; ++p) run = mp_combine(run, mp_load(img + p * 3));
+    mp_block_finish(run, tid, nn, k, t_max, t_all);
 }
 
 long long interior(int h, int w) { return (long long)(h - 2) * (w - 2); }
@@ -128,10 +98,6 @@ long long chunks_of(long long m) { return (m + WSO_CHUNK - 1) / WSO_CHUNK; }
 size_t terms_bytes(int n, long long m) { return (size_t)n * (size_t)m * sizeof(long long); }
 
 }  // namespace
-
-#define WSO_REQUIRE_SHAPE(what)                                                                                        \
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, what ": bad shape n=%d h=%d w=%d", n, h, w);                  \
-    WSU_REQUIRE(interior(h, w) <= (1LL << 27), what ": %lld interior pixels per image exceed 2^27", interior(h, w))
 
 extern "C" {
 
@@ -147,25 +113,21 @@ int wsu_ws_ordered_terms(const uint8_t* x_u8, const float* x_hat, const float* p
                          const float* mean_filter, int hat_full, float hat_scale, int weighted, float tau, long long* terms, int n, int h, int w,
                          void* stream) {
     WSU_REQUIRE(x_u8 && terms, "ws_ordered: null pointer");
-    WSU_REQUIRE((x_hat != nullptr) + (pixel_filter != nullptr) + (pixel_filters != nullptr) == 1,
-                "ws_ordered: give exactly one of x_hat / pixel_filter / pixel_filters");
-    WSU_REQUIRE(weighted != -1, "ws_ordered: weighted=-1 (weights 5 + var) is not defined for the changepoint statistic");
-    WSU_REQUIRE(weighted == 0 || weighted == 1, "ws_ordered: weighted=%d outside {0,1}", weighted);
-    WSU_REQUIRE(weighted == 0 || mean_filter, "ws_ordered: weighted estimate needs mean_filter");
+    WsSource src;
+    int rc = ws_source_make(src, "ws_ordered", "the changepoint statistic", false, x_hat, nullptr, pixel_filter, pixel_filters, mean_filter,
+                            hat_full, hat_scale, weighted, 0, n, h, w, 27);
+    if (rc) return rc;
     WSU_REQUIRE(tau > 0.0f && tau <= 0.5f, "ws_ordered: tau=%g outside (0, 0.5] (tau = flip rate / 2)", (double)tau);
-    WSO_REQUIRE_SHAPE("ws_ordered");
     WSU_REQUIRE((uintptr_t)terms % 8 == 0, "ws_ordered: terms must be 8-byte aligned");
-    const int filtered = x_hat ? 0 : 1;
-    hipLaunchKernelGGL(ws_ordered_terms_kernel, dim3(WSO_PARTS, n), dim3(256), 0, static_cast<hipStream_t>(stream), x_u8, x_hat,
-                       taps_from_kernel(mean_filter), taps_from_kernel(pixel_filter), pixel_filters, filtered, filtered ? 1 : hat_full,
-                       filtered ? 255.0f : hat_scale, weighted, tau, terms, h, w);
+    hipLaunchKernelGGL(ws_ordered_terms_kernel, dim3(WSO_PARTS, n), dim3(256), 0, static_cast<hipStream_t>(stream), x_u8, src.xhat, src.mean_taps,
+                       src.pixel_taps, src.image_filters, src.use_pixel_filter, src.hat_full, src.hat_scale, src.weighted, tau, terms, h, w);
     return wsu_check_launch("ws_ordered_terms_kernel");
 }
 
 int wsu_ws_ordered_fold(const long long* terms, const int* path, long long* k, long long* t_max, long long* t_all, void* workspace,
                         size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(terms && path && k && t_max && t_all && workspace, "ws_ordered_fold: null pointer");
-    WSO_REQUIRE_SHAPE("ws_ordered_fold");
+    WSU_REQUIRE_INTERIOR("ws_ordered_fold", 27);
     WSU_REQUIRE(workspace_bytes >= wsu_ws_ordered_fold_workspace_bytes(n, h, w), "ws_ordered_fold: workspace too small");
     WSU_REQUIRE((uintptr_t)workspace % 8 == 0 && (uintptr_t)terms % 8 == 0 && (uintptr_t)path % 4 == 0,
                 "ws_ordered_fold: terms and workspace must be 8-byte aligned, path 4-byte aligned");

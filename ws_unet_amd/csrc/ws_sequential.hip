@@ -22,13 +22,11 @@
 //   else a.sum + b.best, b.arg -- with arg counted from the start of the whole run, so nothing is shifted.  A single term is
 //   (q, max(q, 0), position + (q > 0)); a term past the row's end is 0, which never wins on the right because best >= sum.
 // Kernel 1: one WAVE per interior row (4 rows per workgroup, 64 workgroups per image striding the rows), 512 consecutive pixels per step:
-//   the loads are coalesced (lane l computes pixels l, 64 + l, ..), the terms cross the wave's own LDS strip so that lane l then folds the
-//   eight CONSECUTIVE terms 8 l .. 8 l + 7 serially (the textbook running maximum), and one ordered shuffle tree over the wave's 64 triples
-//   finishes the step; the steps are folded left to right in lane 0 -> one triple per row (arg relative to the row).  A tree over single
-//   pixels instead costs 2 x K11's time: six dependent steps of five cross-lane moves per pixel.  No workgroup barrier but the one behind
-//   the LDS quotient table: a wave's strip is its own, LDS executes a wave's accesses in order, and a wavefront fence keeps the compiler
-//   from moving a read above the writes of the other lanes.  Kernel 2: one workgroup per image: thread t folds a contiguous run of rows of
-//   the path (read backwards for order 1), an ordered tree over the 256 threads finishes; the curve is the rows' inclusive prefix sum.
+//   ws_fold_step (wsu_metric.h: coalesced loads, the wave's own LDS strip, eight consecutive terms per lane, one ordered shuffle tree; why it
+//   needs fences and no workgroup barrier stands there); the steps are folded left to right in lane 0 -> one triple per row (arg relative to
+//   the row).  The only workgroup barrier is the one behind the LDS quotient table.  Kernel 2: one workgroup per image: thread t folds a
+//   contiguous run of rows of the path (read backwards for order 1), an ordered tree over the 256 threads finishes (mp_block_finish); the
+//   curve is the rows' inclusive prefix sum.
 // Traffic as K11's: 1 B (pixel; the neighbours hit L1 / L2) + 4 B (prediction) per pixel, plus 24 B per row of workspace.  On 512 x 512
 // planes both kernels are bound by the per-pixel arithmetic, not by HBM; this one takes 1.2-1.4 x K11's time (profiles/r23).
 #pragma clang fp contract(off)
@@ -37,62 +35,56 @@
 namespace {
 
 constexpr int WSS_PARTS = 64;                           // kernel 1: workgroups per image, four rows (waves) each per pass
-constexpr int WSS_PER = 8;                              // consecutive path pixels a lane folds serially per step
-constexpr int WSS_STEP = 64 * WSS_PER;                  // pixels of a row per wave step
-constexpr int WSS_PITCH = WSS_PER + 1;                  // LDS pitch of a lane's run in 8-byte words: 72 B, a half-wave's b64 reads hit 32 different bank pairs
-using Taps = Taps3x3<float>;
 
+// Loose parameters and the per-image taps written over `pixel_taps` (K27, K29, K33's terms): with a WsSource ARGUMENT the kernel loaded more
+// of its arguments before the first branch and every stage measured 0.15-0.2 us slower, one outside the bound (profiles/r35).  The struct is
+// put together here instead, so the shared functions serve the kernel all the same, and the device code is the one it had.
 __global__ __launch_bounds__(256) void ws_sequential_rows_kernel(
-    const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, Taps mean_taps, Taps pixel_taps, const float* __restrict__ image_filters,
-    int use_pixel_filter, int hat_full, float hat_scale, int weighted, long long* __restrict__ rows, int h, int w) {
-    __shared__ float unit[256];                          // u / 255.f of every uint8 value (K11)
-    __shared__ long long strip[4][64 * WSS_PITCH];       // per wave: the step's terms, term i at i + i / WSS_PER
+    const uint8_t* __restrict__ xu8, const float* __restrict__ xhat, Taps3x3<float> mean_taps, Taps3x3<float> pixel_taps,
+    const float* __restrict__ image_filters, int use_pixel_filter, int hat_full, float hat_scale, int weighted, long long* __restrict__ rows, int h,
+    int w) {
+    __shared__ float unit[256];                          // u / 255.f of every uint8 value (ws_unit_table)
+    __shared__ long long strip[4][WS_FOLD_STRIP];        // per wave: the step's terms
+    const WsSource src{xhat, nullptr, image_filters, mean_taps, pixel_taps, use_pixel_filter, hat_full, hat_scale, weighted, 0};
     const int nn = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint8_t* img = xu8 + (size_t)nn * h * w;
-    if (image_filters) {                                 // one filter per image (uniform: nn = blockIdx.y)
-#pragma unroll
-        for (int i = 0; i < 9; ++i) pixel_taps.k[8 - i] = image_filters[(size_t)nn * 9 + i];
-    }
-    if (use_pixel_filter) {                              // (uniform over the workgroup)
-        unit[tid] = (float)tid / 255.0f;
-        __syncthreads();
-    }
-    const size_t hbase = hat_base(hat_full, nn, h, w);
+    if (image_filters) pixel_taps = ws_source_taps(src, nn);                             // (uniform: nn = blockIdx.y)
+    ws_unit_table(src, unit, tid);
+    const size_t hbase = hat_base(src.hat_full, nn, h, w);
     const int ih = h - 2, iw = w - 2;
     long long* st = strip[wave];
     for (int r = 1 + (int)blockIdx.x * 4 + wave; r <= ih; r += WSS_PARTS * 4) {          // (uniform over the wave)
         MaxPrefix<int> run{0, 0, 0};                                                     // (lane 0's is the row's)
-        for (int c0 = 0; c0 < iw; c0 += WSS_STEP) {
-            for (int j = 0; j < WSS_PER; ++j) {
+        for (int c0 = 0; c0 < iw; c0 += WS_FOLD_STEP) {
+            for (int j = 0; j < WS_FOLD_PER; ++j) {
                 const int at = 64 * j + lane, i = c0 + at;
                 long long q = 0;                                                         // past the row's end: 0, which never wins on the right
                 if (i < iw) {
-                    const WsTerms p = ws_pixel_terms(img, xhat, nullptr, unit, mean_taps, pixel_taps, use_pixel_filter, hat_full, hbase,
-                                                     hat_scale, weighted, 0, r, i + 1, w);
+                    const WsTerms p = ws_pixel_terms(img, src, pixel_taps, unit, hbase, r, i + 1, w);
                     const float rr = p.s * p.res;
                     const float d = rr - 0.25f;
                     const float t = p.wgt * d;
                     q = ws_seq_term(t);
                 }
-                st[at + at / WSS_PER] = q;
+                st[at + at / WS_FOLD_PER] = q;
             }
+            // ws_fold_step's text, kept here: as a call of it this kernel takes 81 VGPRs instead of 67 and drops from 7 to 5 waves per SIMD
+            // (profiles/r35); the statements are the same and tests/test_gpu_ws_source.py pins that K33, which calls it, agrees.  An edit to
+            // ws_fold_step is made here as well.
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            const int first = c0 + lane * WSS_PER;
+            const int first = c0 + lane * WS_FOLD_PER;
             MaxPrefix<int> e{0, 0, first};
 #pragma unroll
-            for (int j = 0; j < WSS_PER; ++j) {
-                e.sum += st[lane * WSS_PITCH + j];
+            for (int j = 0; j < WS_FOLD_PER; ++j) {
+                e.sum += st[lane * WS_FOLD_PITCH + j];
                 if (e.sum > e.best) { e.best = e.sum; e.arg = first + j + 1; }           // >: among equal maxima the first
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                       // (the next step's writes stay behind these reads)
             __builtin_amdgcn_wave_barrier();
             run = mp_combine(run, mp_wave(e));
         }
-        if (lane == 0) {
-            long long* o = rows + ((size_t)nn * ih + (r - 1)) * 3;
-            o[0] = run.sum; o[1] = run.best; o[2] = run.arg;
-        }
+        if (lane == 0) mp_store(rows + ((size_t)nn * ih + (r - 1)) * 3, run);
     }
 }
 
@@ -100,7 +92,6 @@ __global__ __launch_bounds__(256) void ws_sequential_finish_kernel(const long lo
                                                                    long long* __restrict__ t_max, long long* __restrict__ t_all,
                                                                    long long* __restrict__ curve, int ih, int iw, int order) {
     __shared__ long long seg[256];
-    __shared__ MaxPrefix<long long> wv[4];
     const int nn = blockIdx.x, tid = threadIdx.x;
     const long long* img = rows + (size_t)nn * ih * 3;
     const int per = (ih + 255) / 256;                    // path rows per thread, contiguous
@@ -108,8 +99,7 @@ __global__ __launch_bounds__(256) void ws_sequential_finish_kernel(const long lo
     const long long p1 = p0 + per < ih ? p0 + per : ih;
     MaxPrefix<long long> run{0, 0, p0 * iw};
     for (long long p = p0; p < p1; ++p) {
-        const long long* t = img + (order ? ih - 1 - p : p) * 3;
-        run = mp_combine(run, MaxPrefix<long long>{t[0], t[1], p * iw + t[2]});
+        run = mp_combine(run, mp_load(img + (order ? ih - 1 - p : p) * 3, p * iw));
     }
     if (curve) {                                         // (uniform over the grid)
         seg[tid] = run.sum;
@@ -121,13 +111,7 @@ __global__ __launch_bounds__(256) void ws_sequential_finish_kernel(const long lo
             curve[(size_t)nn * ih + p] = acc;
         }
     }
-    run = mp_wave(run);
-    if ((tid & 63) == 0) wv[tid >> 6] = run;
-    __syncthreads();
-    if (tid == 0) {
-        const MaxPrefix<long long> all = mp_combine(mp_combine(wv[0], wv[1]), mp_combine(wv[2], wv[3]));
-        k[nn] = all.arg; t_max[nn] = all.best; t_all[nn] = all.sum;
-    }
+    mp_block_finish(run, tid, nn, k, t_max, t_all);
 }
 
 }  // namespace
@@ -140,23 +124,17 @@ int wsu_ws_sequential(const uint8_t* x_u8, const float* x_hat, const float* pixe
                       int hat_full, float hat_scale, int weighted, int order, long long* k, long long* t_max, long long* t_all,
                       long long* curve, void* workspace, size_t workspace_bytes, int n, int h, int w, void* stream) {
     WSU_REQUIRE(x_u8 && k && t_max && t_all && workspace, "ws_sequential: null pointer");
-    WSU_REQUIRE((x_hat != nullptr) + (pixel_filter != nullptr) + (pixel_filters != nullptr) == 1,
-                "ws_sequential: give exactly one of x_hat / pixel_filter / pixel_filters");
-    WSU_REQUIRE(weighted != -1, "ws_sequential: weighted=-1 (weights 5 + var) is not defined for the sequential statistic");
-    WSU_REQUIRE(weighted == 0 || weighted == 1, "ws_sequential: weighted=%d outside {0,1}", weighted);
-    WSU_REQUIRE(weighted == 0 || mean_filter, "ws_sequential: weighted estimate needs mean_filter");
+    WsSource src;
+    int rc = ws_source_make(src, "ws_sequential", "the sequential statistic", false, x_hat, nullptr, pixel_filter, pixel_filters, mean_filter,
+                            hat_full, hat_scale, weighted, 0, n, h, w, 27);
+    if (rc) return rc;
     WSU_REQUIRE(order == 0 || order == 1, "ws_sequential: order=%d outside {0 = rows from the top, 1 = rows from the bottom}", order);
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, "ws_sequential: bad shape n=%d h=%d w=%d", n, h, w);
-    WSU_REQUIRE((long long)(h - 2) * (w - 2) <= (1LL << 27), "ws_sequential: %lld interior pixels per image exceed 2^27",
-                (long long)(h - 2) * (w - 2));
     WSU_REQUIRE(workspace_bytes >= wsu_ws_sequential_workspace_bytes(n, h), "ws_sequential: workspace too small");
     WSU_REQUIRE((uintptr_t)workspace % 8 == 0, "ws_sequential: workspace must be 8-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int filtered = x_hat ? 0 : 1;
-    hipLaunchKernelGGL(ws_sequential_rows_kernel, dim3(WSS_PARTS, n), dim3(256), 0, s, x_u8, x_hat, taps_from_kernel(mean_filter),
-                       taps_from_kernel(pixel_filter), pixel_filters, filtered, filtered ? 1 : hat_full, filtered ? 255.0f : hat_scale, weighted,
-                       static_cast<long long*>(workspace), h, w);
-    int rc = wsu_check_launch("ws_sequential_rows_kernel");
+    hipLaunchKernelGGL(ws_sequential_rows_kernel, dim3(WSS_PARTS, n), dim3(256), 0, s, x_u8, src.xhat, src.mean_taps, src.pixel_taps,
+                       src.image_filters, src.use_pixel_filter, src.hat_full, src.hat_scale, src.weighted, static_cast<long long*>(workspace), h, w);
+    rc = wsu_check_launch("ws_sequential_rows_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(ws_sequential_finish_kernel, dim3(n), dim3(256), 0, s, static_cast<const long long*>(workspace), k, t_max, t_all, curve,
                        h - 2, w - 2, order);

@@ -35,6 +35,12 @@ constexpr long long WSU_PATH_PIXELS = 1LL << 31;
 #define WSU_REQUIRE_SHAPE(what, limit, noun)                                                                           \
     WSU_REQUIRE(n > 0 && n <= 65535 && h >= 1 && w >= 1, what ": bad shape n=%d h=%d w=%d", n, h, w);                 \
     WSU_REQUIRE((long long)h * w < (limit), what ": %lld pixels per image exceed the 32-bit " noun, (long long)h * w)
+// ... of an entry that works on the INTERIORS of n planes of h x w pixels (the WS statistics K11, K27, K29, K33): every plane has one, of at
+// most 2^cap_bits pixels (27: sums of 2^36 terms stay inside int64; 31: int32 positions; 0: no cap).  `who` is a run-time string here.
+#define WSU_REQUIRE_INTERIOR(who, cap_bits)                                                                            \
+    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, "%s: bad shape n=%d h=%d w=%d", who, n, h, w);               \
+    WSU_REQUIRE((cap_bits) <= 0 || (long long)(h - 2) * (w - 2) <= (1LL << (cap_bits)), "%s: %lld interior pixels per image exceed 2^%d", who, \
+                (long long)(h - 2) * (w - 2), (int)(cap_bits))
 // a C-linkage helper called across translation units that is no part of include/wsu.h: not exported by libwsu.so
 #define WSU_INTERNAL extern "C" __attribute__((visibility("hidden")))
 // CU count of the current device, queried once per process; 0 after "<who>: cannot query the device" has been set (the caller returns WSU_ERR_HIP)

@@ -1,7 +1,8 @@
 // Device helpers shared by the metric kernels K10-K18, K27, K29, K32 and K33 and the simulators K20, K37, K38 and K45-K47 (pointwise.hip K10 + WS meter,
 // ws_attack.hip, ws_sequential.hip, ws_ordered.hip, ws_locate.hip, jpeg_history.hip, hill.hip, correlation.hip, error_boxes.hip, embed.hip, ternary.hip, stc_layers.hip): the one definition each of a 3x3 predictor's
-// taps, the prediction at a pixel, the float32 residual, the WS statistic's per-pixel terms, the maximum-prefix triple, the HILL cost's input window, the fixed-order
-// block sum, the +-1 sender's exponentials and the radix-select steps.  (The simulators' pixel loop: wsu_embed.h.)
+// taps, the prediction at a pixel, the float32 residual, the WS statistics' prediction source (WsSource: the kernel argument, its host-side
+// maker and checks, the per-image taps, the quotient table) and per-pixel terms, the maximum-prefix triple with its workspace form, block
+// finish and the ordered fold of a wave step, the HILL cost's input window, the fixed-order block sum, the +-1 sender's exponentials and the radix-select steps.  (The simulators' pixel loop: wsu_embed.h.)
 //
 // Rounding policy: these functions restate numpy's float32 / float64 operation sequences with PLAIN operators, one rounding each.  That
 // holds only under `#pragma clang fp contract(off)`, which is per translation unit: every including .hip file sets it BEFORE this
@@ -63,19 +64,49 @@ __device__ __forceinline__ float residual_f32(float x, float y, float scale) {
     return x - xhat;
 }
 
-// ---- the WS statistic's per-pixel terms (K11, K27, K29, K33) -----------------------------------------------------------------------------
+// ---- the WS statistics' prediction source and per-pixel terms (K11, K27, K29, K33) -------------------------------------------------------
+// What a statistic kernel needs to know about its predictor and weights: K11's kernel argument, by value; K27, K29 and K33 put it together
+// from their loose parameters (ws_sequential.hip says why).  Exactly one source is set:
+// `xhat` (a prediction on the device, N full frames or N interiors: hat_full, multiplied by hat_scale), `pixel_taps` (one 3x3 filter,
+// evaluated in the kernel) or `image_filters` (DEVICE, one filter per image, K[a][b] like taps_from_kernel's input); use_pixel_filter says
+// whether it is a filter.  weighted: 0 | 1 | -1 (K11 only); xbias / correct_bias: K11 only.  ws_source_make (below) is the only maker.
+struct WsSource {
+    const float* __restrict__ xhat;
+    const float* __restrict__ xbias;
+    const float* __restrict__ image_filters;
+    Taps3x3<float> mean_taps, pixel_taps;
+    int use_pixel_filter, hat_full;
+    float hat_scale;
+    int weighted, correct_bias;
+};
+// the pixel taps of image nn: the source's own, or row nn of image_filters reversed (uniform where nn is)
+__device__ __forceinline__ Taps3x3<float> ws_source_taps(const WsSource& src, int nn) {
+    Taps3x3<float> t = src.pixel_taps;
+    if (src.image_filters) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) t.k[8 - i] = src.image_filters[(size_t)nn * 9 + i];
+    }
+    return t;
+}
+// One 256-thread workgroup fills unit[u] = u / 255.f for every uint8 value, with its barrier, where the source is a filter (uniform over the
+// workgroup): one IEEE division per thread instead of nine per pixel, the same bits as dividing per pixel.
+__device__ __forceinline__ void ws_unit_table(const WsSource& src, float* unit, int tid) {
+    if (src.use_pixel_filter) {
+        unit[tid] = (float)tid / 255.0f;
+        __syncthreads();
+    }
+}
+
 // At interior pixel (r, c) of the uint8 plane `img` (row stride w), in numpy's float32 operation sequence (src/ws/estimate.py:90-121):
 //   wgt  = 1 (weighted 0) | 1 / (5 + var) (weighted > 0) | 5 + var (weighted < 0),  var = conv(x*x, mean) - conv(x, mean)^2
 //   s    = x - x_bar = +-1
-//   res  = x - x_hat,  x_hat = conv(x / 255., pixel_taps) * 255. (use_pixel_filter; `unit` = the 256 quotients u / 255.f) or
-//          xhat[o] * hat_scale, o = hat_index(...)
+//   res  = x - x_hat,  x_hat = conv(x / 255., taps) * 255. (use_pixel_filter; taps = ws_source_taps, `unit` = ws_unit_table's) or
+//          xhat[o] * hat_scale, o = hat_index(hat_full, hbase, ...), hbase = hat_base(hat_full, nn, h, w)
 //   bias = the predictor applied to x_bar - x (correct_bias only, else 0)
 // Convolutions are true convolutions summed K00 .. K22 (conv9_f32<true>).
 struct WsTerms { float wgt, s, res, bias; };
-__device__ __forceinline__ WsTerms ws_pixel_terms(const uint8_t* __restrict__ img, const float* __restrict__ xhat,
-                                                  const float* __restrict__ xbias, const float* unit, const Taps3x3<float>& mean_taps,
-                                                  const Taps3x3<float>& pixel_taps, int use_pixel_filter, int hat_full, size_t hbase,
-                                                  float hat_scale, int weighted, int correct_bias, int r, int c, int w) {
+__device__ __forceinline__ WsTerms ws_pixel_terms(const uint8_t* __restrict__ img, const WsSource& src, const Taps3x3<float>& taps,
+                                                  const float* unit, size_t hbase, int r, int c, int w) {
     float v[3][3], v2[3][3];
     uint8_t u[3][3];
 #pragma unroll
@@ -88,18 +119,18 @@ __device__ __forceinline__ WsTerms ws_pixel_terms(const uint8_t* __restrict__ im
         }
     WsTerms o;
     o.wgt = 1.0f;
-    if (weighted != 0) {
-        const float mu = conv9_f32<true>(mean_taps, v);
-        const float mu2 = conv9_f32<true>(mean_taps, v2);
+    if (src.weighted != 0) {
+        const float mu = conv9_f32<true>(src.mean_taps, v);
+        const float mu2 = conv9_f32<true>(src.mean_taps, v2);
         const float mu_sq = mu * mu;
         const float var = mu2 - mu_sq;
         const float t = 5.0f + var;
-        o.wgt = weighted > 0 ? 1.0f / t : t;
+        o.wgt = src.weighted > 0 ? 1.0f / t : t;
     }
     const float x = v[1][1];
     o.s = x - (float)(uint8_t)(u[1][1] ^ 1);                                          // x - x_bar = +-1
     o.bias = 0.f;
-    if (use_pixel_filter) {
+    if (src.use_pixel_filter) {
         float q[3][3], qb[3][3];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -108,14 +139,35 @@ __device__ __forceinline__ WsTerms ws_pixel_terms(const uint8_t* __restrict__ im
                 q[i][j] = unit[u[i][j]];                                                // x / 255. (filters/evaluate.py:136-141)
                 qb[i][j] = (u[i][j] & 1) ? -unit[1] : unit[1];                          // (x_bar - x) / 255. = -+1 / 255.
             }
-        o.res = residual_f32(x, conv9_f32<true>(pixel_taps, q), 255.0f);
-        if (correct_bias) o.bias = conv9_f32<true>(pixel_taps, qb) * 255.0f;
+        o.res = residual_f32(x, conv9_f32<true>(taps, q), 255.0f);
+        if (src.correct_bias) o.bias = conv9_f32<true>(taps, qb) * 255.0f;
     } else {
-        const size_t at = hat_index(hat_full, hbase, r, c, w);
-        o.res = residual_f32(x, xhat[at], hat_scale);
-        if (correct_bias) o.bias = xbias[at] * hat_scale;
+        const size_t at = hat_index(src.hat_full, hbase, r, c, w);
+        o.res = residual_f32(x, src.xhat[at], src.hat_scale);
+        if (src.correct_bias) o.bias = src.xbias[at] * src.hat_scale;
     }
     return o;
+}
+
+// The one maker of a WsSource, and the argument checks every statistic entry shares (host; returns WSU_ERR_ARG with "<who>: ..." set).
+// `what` names the statistic in the texts ("the sequential statistic"); attack = K11, the only entry with weights 5 + var (weighted = -1)
+// and a bias correction.  n, h, w: the planes; a plane may have at most 2^cap_bits interior pixels (WSU_REQUIRE_INTERIOR, wsu_device.h; 0: no cap).
+// A filter predicts full frames in pixel units, whatever hat_full / hat_scale say.
+inline int ws_source_make(WsSource& src, const char* who, const char* what, bool attack, const float* x_hat, const float* x_bias,
+                          const float* pixel_filter, const float* pixel_filters, const float* mean_filter, int hat_full, float hat_scale,
+                          int weighted, int correct_bias, int n, int h, int w, int cap_bits) {
+    WSU_REQUIRE((x_hat != nullptr) + (pixel_filter != nullptr) + (pixel_filters != nullptr) == 1,
+                "%s: give exactly one of x_hat / pixel_filter / pixel_filters", who);
+    WSU_REQUIRE(attack || weighted != -1, "%s: weighted=-1 (weights 5 + var) is not defined for %s", who, what);
+    WSU_REQUIRE(weighted >= (attack ? -1 : 0) && weighted <= 1, "%s: weighted=%d outside %s", who, weighted, attack ? "{-1,0,1}" : "{0,1}");
+    WSU_REQUIRE(weighted == 0 || mean_filter, "%s: weighted estimate needs mean_filter", who);
+    WSU_REQUIRE(attack || (!correct_bias && !x_bias), "%s: a bias correction is not defined for %s", who, what);
+    WSU_REQUIRE(!correct_bias || !x_hat || x_bias, "%s: correct_bias needs x_bias = pixel_estimator(x_bar - x)", who);
+    WSU_REQUIRE_INTERIOR(who, cap_bits);
+    const bool filtered = !x_hat;
+    src = WsSource{x_hat, x_bias, pixel_filters, taps_from_kernel(mean_filter), taps_from_kernel(pixel_filter), filtered ? 1 : 0,
+                   filtered ? 1 : hat_full, filtered ? 255.0f : hat_scale, weighted, correct_bias};
+    return 0;
 }
 
 // The fixed-point form of a float32 term t (K27, K29, K33): 0 where t is NaN, else llrint((double)min(max(t, -4096), 4096) * 2^24), round to
@@ -148,6 +200,56 @@ template <typename A> __device__ __forceinline__ MaxPrefix<A> mp_wave(MaxPrefix<
         a = mp_combine(a, b);
     }
     return a;
+}
+
+// One 256-thread workgroup (one image), thread t holding the triple of the t-th contiguous run of the sequence: an ordered tree over each
+// wave, the four waves combined in order, and thread 0 stores k / t_max / t_all of image nn (the tail of K27's and K33's finish kernels).
+__device__ __forceinline__ void mp_block_finish(MaxPrefix<long long> run, int tid, int nn, long long* __restrict__ k,
+                                                long long* __restrict__ t_max, long long* __restrict__ t_all) {
+    __shared__ MaxPrefix<long long> wv[4];
+    run = mp_wave(run);
+    if ((tid & 63) == 0) wv[tid >> 6] = run;
+    __syncthreads();
+    if (tid == 0) {
+        const MaxPrefix<long long> all = mp_combine(mp_combine(wv[0], wv[1]), mp_combine(wv[2], wv[3]));
+        k[nn] = all.arg; t_max[nn] = all.best; t_all[nn] = all.sum;
+    }
+}
+// a triple in the int64 workspace: three consecutive words; `shift` moves a loaded arg to the start of the whole sequence
+template <typename A> __device__ __forceinline__ void mp_store(long long* __restrict__ at, const MaxPrefix<A>& t) {
+    at[0] = t.sum; at[1] = t.best; at[2] = t.arg;
+}
+__device__ __forceinline__ MaxPrefix<long long> mp_load(const long long* __restrict__ at, long long shift = 0) {
+    return MaxPrefix<long long>{at[0], at[1], at[2] + shift};
+}
+
+// ---- the ordered fold of one wave step (K27's rows, K33's chunks) ---------------------------------------------------------------------
+// A wave takes WS_FOLD_STEP consecutive positions of a sequence per step.  Lane l computes (or gathers) the terms at c0 + l, c0 + 64 + l, ..,
+// so the loads are coalesced; the terms cross the wave's own LDS strip so that lane l then folds the WS_FOLD_PER CONSECUTIVE terms
+// 8 l .. 8 l + 7 serially (the textbook running maximum), and one ordered shuffle tree over the wave's 64 triples finishes the step.  (A
+// tree over single terms instead costs 2 x K11's time: six dependent steps of five cross-lane moves per pixel.)  No workgroup barrier: a
+// wave's strip is its own, LDS executes a wave's accesses in order, and a wavefront fence keeps the compiler from moving a read above the
+// writes of the other lanes, or the next step's writes above these reads.
+constexpr int WS_FOLD_PER = 8;                          // consecutive positions a lane folds serially per step
+constexpr int WS_FOLD_STEP = 64 * WS_FOLD_PER;          // positions per wave step
+constexpr int WS_FOLD_PITCH = WS_FOLD_PER + 1;          // LDS pitch of a lane's run in 8-byte words: 72 B, a half-wave's b64 reads hit 32 different bank pairs
+constexpr int WS_FOLD_STRIP = 64 * WS_FOLD_PITCH;       // 8-byte words of a wave's strip: term i of the step at i + i / WS_FOLD_PER
+// Every lane has written its WS_FOLD_PER terms of the step (the term at offset at = 64 j + lane to st[at + at / WS_FOLD_PER]; 0 past the
+// sequence's end, which never wins on the right) to `st`, the wave's strip; c0: the position of the step's first term, counted like the result's arg.  Lane 0's return value is
+// the step's triple.
+__device__ __forceinline__ MaxPrefix<int> ws_fold_step(const long long* st, int lane, int c0) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int first = c0 + lane * WS_FOLD_PER;
+    MaxPrefix<int> e{0, 0, first};
+#pragma unroll
+    for (int j = 0; j < WS_FOLD_PER; ++j) {
+        e.sum += st[lane * WS_FOLD_PITCH + j];
+        if (e.sum > e.best) { e.best = e.sum; e.arg = first + j + 1; }                   // >: among equal maxima the first
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                               // (the next step's writes stay behind these reads)
+    __builtin_amdgcn_wave_barrier();
+    return mp_wave(e);
 }
 
 // ---- the HILL cost's input window (K12 fp32, K20 fp64) -----------------------------------------------------------------------------

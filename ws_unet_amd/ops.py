@@ -998,6 +998,50 @@ def _hat_full(x_hat: torch.Tensor, n: int, h: int, w: int, hat_full: Optional[bo
                      + ("" if hat_full is None else f" (hat_full={bool(hat_full)})"))
 
 
+class _CArguments(tuple):
+    """C arguments that carry the arrays their pointers belong to (`keep`): those live as long as the arguments do."""
+
+
+def _ws_source(who: str, x_u8, x_hat, x_bias, pixel_filter, mean_filter, hat_scale, weighted, what: Optional[str] = None, min_side: int = 0):
+    """The ONE prediction source and the weights of a WS statistic entry (ws_attack, ws_sequential, ws_ordered*, ws_residual_accumulate),
+    checked.  `what` names a statistic that is not defined for weighted=-1 and takes no x_bias (None: K11, which has both); min_side: the
+    smallest plane side the wrapper itself refuses.  Returns ((n, h, w), (x_hat pointer, HOST pixel filter, DEVICE per-image filters, HOST
+    mean filter, hat_full, hat_scale, weighted)): the order in which the C entries take them, as _CArguments that hold the filters' arrays,
+    so they stay alive while the caller holds the arguments, which it does until the launch."""
+    weights = (-1, 0, 1) if what is None else (0, 1)
+    if int(weighted) not in weights:
+        raise ValueError(f"{who}: weighted must be 0 or 1 (weighted=-1 is not defined for {what}), got {weighted}" if what is not None
+                         else f"{who}: weighted={weighted} outside {{-1,0,1}}")
+    per_image = pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3)           # (N,3,3[,1])
+    if (x_hat is None) == (pixel_filter is None) or (per_image and x_bias is not None):
+        raise ValueError(f"{who}: give exactly one of x_hat / pixel_filter")
+    _dev_check(x_hat, x_bias)
+    n, h, w = _u8_planes(x_u8)
+    if h < min_side or w < min_side:
+        raise ValueError(f"{who}: planes of at least {min_side} x {min_side} pixels expected, got {h} x {w}")
+    mt = filter_taps(mean_filter, np.float32, "kernel")
+    pt = pts = None
+    hat_full = 1
+    if x_hat is not None:
+        hat_full = _hat_full(x_hat, n, h, w, None, x_bias)
+    elif per_image:
+        if len(pixel_filter) != n:
+            raise ValueError(f"{who}: {len(pixel_filter)} filters for {n} images")
+        pts = torch.from_numpy(np.stack([filter_taps(f, np.float32, "kernel") for f in pixel_filter])).to(x_u8.device)
+    else:
+        pt = filter_taps(pixel_filter, np.float32, "kernel")
+    host = lambda a: None if a is None else a.ctypes.data
+    source = _CArguments((_ptr(x_hat), host(pt), _ptr(pts), host(mt), hat_full, float(hat_scale), int(weighted)))
+    source.keep = (pt, pts, mt)
+    return (n, h, w), source
+
+
+def _changepoint_outputs(n: int, workspace_bytes: int, dev):
+    """(k, t_max, t_all) int64 (N,) and the int64 workspace of a changepoint entry (K27, K33)."""
+    k, t_max, t_all = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+    return k, t_max, t_all, torch.empty(max(workspace_bytes // 8, 1), dtype=torch.int64, device=dev)
+
+
 def ws_attack(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, x_bias: Optional[torch.Tensor] = None,
               pixel_filter=None, mean_filter=None, hat_scale: float = 255.0, weighted: int = 1, correct_bias: bool = False,
               return_sums: bool = False):
@@ -1006,47 +1050,18 @@ def ws_attack(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, x_bia
     or `pixel_filter` (3,3[,1]) for an in-kernel linear predictor, (N,3,3[,1]) for one per image (wsu_ws_attack_taps).
     Returns beta_hat[N] (and the (N,3) fp64 sums)."""
     lib = _lib.load()
-    _dev_check(x_u8, *[t for t in (x_hat, x_bias) if t is not None])
-    n, h, w = x_u8.shape
-    assert x_u8.dtype == torch.uint8
-    mt = filter_taps(mean_filter, np.float32, "kernel")
+    (n, h, w), source = _ws_source("ws_attack", x_u8, x_hat, x_bias, pixel_filter, mean_filter, hat_scale, weighted)
+    xh, pt, pts, mt, hat_full, scale, wgt = source
     beta = torch.empty(n, dtype=torch.float32, device=x_u8.device)
     sums = torch.empty((n, 3), dtype=torch.float64, device=x_u8.device) if return_sums else None
     ws = torch.empty(lib.wsu_ws_attack_workspace_bytes(n) // 8, dtype=torch.float64, device=x_u8.device)
-    tail = (beta.data_ptr(), sums.data_ptr() if sums is not None else None, ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())
-    if pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3):      # (N,3,3[,1])
-        if x_hat is not None or x_bias is not None:
-            raise ValueError("ws_attack: give exactly one of x_hat / pixel_filter")
-        if len(pixel_filter) != n:
-            raise ValueError(f"ws_attack: {len(pixel_filter)} filters for {n} images")
-        pts = torch.from_numpy(np.stack([filter_taps(k, np.float32, "kernel") for k in pixel_filter])).to(x_u8.device)
-        check(_launch("ws_attack", {}, lambda: lib.wsu_ws_attack_taps(
-            x_u8.data_ptr(), pts.data_ptr(), mt.ctypes.data if mt is not None else None, int(weighted), int(bool(correct_bias)),
-            *tail)), "wsu_ws_attack_taps")
-        return (beta, sums) if return_sums else beta
-    hat_full = _hat_full(x_hat, n, h, w, None, x_bias) if x_hat is not None else 1
-    pt = filter_taps(pixel_filter, np.float32, "kernel")
-    check(_launch("ws_attack", {}, lambda: lib.wsu_ws_attack(
-        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, x_bias.data_ptr() if x_bias is not None else None,
-        pt.ctypes.data if pt is not None else None, mt.ctypes.data if mt is not None else None,
-        hat_full, float(hat_scale), int(weighted), int(bool(correct_bias)), *tail)), "wsu_ws_attack")
-    return (beta, sums) if return_sums else beta
-
-
-def _predictor_pointers(who: str, x_hat, pixel_filter, n: int, h: int, w: int, dev):
-    """(x_hat pointer, HOST filter, DEVICE per-image filters, hat_full) of the ONE prediction source of K27-style entry points; the
-    returned arrays must stay alive until the launch."""
-    pt = pts = None
-    hat_full = 1
-    if pixel_filter is not None and np.ndim(pixel_filter) >= 3 and np.shape(pixel_filter)[1:3] == (3, 3):      # (N,3,3[,1])
-        if len(pixel_filter) != n:
-            raise ValueError(f"{who}: {len(pixel_filter)} filters for {n} images")
-        pts = torch.from_numpy(np.stack([filter_taps(f, np.float32, "kernel") for f in pixel_filter])).to(dev)
-    elif pixel_filter is not None:
-        pt = filter_taps(pixel_filter, np.float32, "kernel")
+    tail = (int(bool(correct_bias)), beta.data_ptr(), _ptr(sums), ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())
+    if pts is not None:
+        check(_launch("ws_attack", {}, lambda: lib.wsu_ws_attack_taps(x_u8.data_ptr(), pts, mt, wgt, *tail)), "wsu_ws_attack_taps")
     else:
-        hat_full = _hat_full(x_hat, n, h, w, None)
-    return pt, pts, hat_full
+        check(_launch("ws_attack", {}, lambda: lib.wsu_ws_attack(x_u8.data_ptr(), xh, _ptr(x_bias), pt, mt, hat_full, scale, wgt, *tail)),
+              "wsu_ws_attack")
+    return (beta, sums) if return_sums else beta
 
 
 ORDERS = ("rows", "rows_up")               # path orders of the sequential statistic and simulator: rows from the top / from the bottom
@@ -1066,25 +1081,15 @@ def ws_sequential(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, p
     in-kernel linear predictor, (N,3,3[,1]) for one per image.  weighted: 0 or 1.  order: 'rows' (the path takes the interior rows from
     the top) or 'rows_up' (from the bottom).  Returns int64 (N,) tensors (k, t_max, t_all[, curve (N,H-2)]): the first maximiser k in
     0..(H-2)(W-2) of the fixed-point cumulative statistic T (2^24 units), T(k), T at the path's end, and T at the end of every row."""
-    if int(weighted) not in (0, 1):
-        raise ValueError(f"ws_sequential: weighted must be 0 or 1 (weighted=-1 is not defined for the sequential statistic), got {weighted}")
-    if (x_hat is None) == (pixel_filter is None):
-        raise ValueError("ws_sequential: give exactly one of x_hat / pixel_filter")
     oid = order_id(order)
     lib = _lib.load()
-    _dev_check(x_u8, *[t for t in (x_hat,) if t is not None])
-    n, h, w = _u8_planes(x_u8)
-    mt = filter_taps(mean_filter, np.float32, "kernel")
-    dev = x_u8.device
-    k, t_max, t_all = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
-    curve = torch.empty((n, h - 2), dtype=torch.int64, device=dev) if return_curve else None
-    ws = torch.empty(max(lib.wsu_ws_sequential_workspace_bytes(n, h) // 8, 1), dtype=torch.int64, device=dev)
-    pt, pts, hat_full = _predictor_pointers("ws_sequential", x_hat, pixel_filter, n, h, w, dev)
+    (n, h, w), source = _ws_source("ws_sequential", x_u8, x_hat, None, pixel_filter, mean_filter, hat_scale, weighted,
+                                         "the sequential statistic")
+    k, t_max, t_all, ws = _changepoint_outputs(n, lib.wsu_ws_sequential_workspace_bytes(n, h), x_u8.device)
+    curve = torch.empty((n, h - 2), dtype=torch.int64, device=x_u8.device) if return_curve else None
     check(_launch("ws_sequential", {"bytes": float(n * h * w * (1 if x_hat is None else 5))}, lambda: lib.wsu_ws_sequential(
-        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
-        pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
-        oid, k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), curve.data_ptr() if curve is not None else None,
-        ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())), "wsu_ws_sequential")
+        x_u8.data_ptr(), *source, oid, k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), _ptr(curve), ws.data_ptr(), ws.numel() * 8, n, h, w,
+        _stream())), "wsu_ws_sequential")
     return (k, t_max, t_all, curve) if return_curve else (k, t_max, t_all)
 
 
@@ -1106,19 +1111,11 @@ def _ordered_path(who: str, path, n: int, m: int, dev) -> None:
         raise ValueError(f"{who}: path lives on {path.device}, the pixels on {dev}")
 
 
-def _ordered_arguments(who: str, x_u8, x_hat, pixel_filter, mean_filter, weighted, flip_rate):
-    """The checked arguments kernel A of K33 takes: ((n, h, w), tau, HOST mean filter, HOST filter, DEVICE per-image filters, hat_full)."""
-    if int(weighted) not in (0, 1):
-        raise ValueError(f"{who}: weighted must be 0 or 1 (weighted=-1 is not defined for the changepoint statistic), got {weighted}")
-    if (x_hat is None) == (pixel_filter is None):
-        raise ValueError(f"{who}: give exactly one of x_hat / pixel_filter")
+def _ordered_arguments(who: str, x_u8, x_hat, pixel_filter, mean_filter, hat_scale, weighted, flip_rate):
+    """The checked arguments kernel A of K33 takes: ((n, h, w), _ws_source's C arguments, tau)."""
     tau = _flip_tau(who, flip_rate)
-    _dev_check(x_u8, x_hat)
-    n, h, w = _u8_planes(x_u8)
-    if h < 3 or w < 3:
-        raise ValueError(f"{who}: planes of at least 3 x 3 pixels expected, got {h} x {w}")
-    mt = filter_taps(mean_filter, np.float32, "kernel")
-    return (n, h, w), tau, mt, *_predictor_pointers(who, x_hat, pixel_filter, n, h, w, x_u8.device)
+    shape, source = _ws_source(who, x_u8, x_hat, None, pixel_filter, mean_filter, hat_scale, weighted, "the changepoint statistic", min_side=3)
+    return shape, source, tau
 
 
 def ws_ordered_terms(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *, pixel_filter=None, mean_filter=None,
@@ -1126,12 +1123,10 @@ def ws_ordered_terms(x_u8: torch.Tensor, x_hat: Optional[torch.Tensor] = None, *
     """Kernel A of K33 alone (wsu_ws_ordered_terms): the fixed-point terms q = ws_seq_term(wgt * (s * res - flip_rate / 2)) of every
     interior pixel, int64 (N, (H-2)(W-2)) in raster order.  Arguments as ws_ordered's."""
     lib = _lib.load()
-    (n, h, w), tau, mt, pt, pts, hat_full = _ordered_arguments("ws_ordered_terms", x_u8, x_hat, pixel_filter, mean_filter, weighted, flip_rate)
+    (n, h, w), source, tau = _ordered_arguments("ws_ordered_terms", x_u8, x_hat, pixel_filter, mean_filter, hat_scale, weighted, flip_rate)
     terms = torch.empty((n, (h - 2) * (w - 2)), dtype=torch.int64, device=x_u8.device)
     check(_launch("ws_ordered_terms", {"bytes": float(n * h * w * (9 if x_hat is None else 13))}, lambda: lib.wsu_ws_ordered_terms(
-        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
-        pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
-        tau, terms.data_ptr(), n, h, w, _stream())), "wsu_ws_ordered_terms")
+        x_u8.data_ptr(), *source, tau, terms.data_ptr(), n, h, w, _stream())), "wsu_ws_ordered_terms")
     return terms
 
 
@@ -1147,8 +1142,7 @@ def ws_ordered_fold(terms: torch.Tensor, path: torch.Tensor, h: int, w: int):
     n, dev = terms.shape[0], terms.device
     _ordered_path(who, path, n, m, dev)
     lib = _lib.load()
-    k, t_max, t_all = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
-    ws = torch.empty(max(lib.wsu_ws_ordered_fold_workspace_bytes(n, h, w) // 8, 1), dtype=torch.int64, device=dev)
+    k, t_max, t_all, ws = _changepoint_outputs(n, lib.wsu_ws_ordered_fold_workspace_bytes(n, h, w), dev)
     check(_launch("ws_ordered_fold", {"bytes": float(n * m * 12)}, lambda: lib.wsu_ws_ordered_fold(
         terms.data_ptr(), path.data_ptr(), k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), ws.data_ptr(), ws.numel() * 8, n, h, w,
         _stream())), "wsu_ws_ordered_fold")
@@ -1166,16 +1160,12 @@ def ws_ordered(x_u8: torch.Tensor, path: torch.Tensor, x_hat: Optional[torch.Ten
     tensors (k, t_max, t_all): the first maximiser k in 0..M of the fixed-point cumulative statistic T (2^24 units) along the path, T(k)
     and T(M).  The change rate is flip_rate * k / M (ws.adaptive.beta)."""
     lib = _lib.load()
-    (n, h, w), tau, mt, pt, pts, hat_full = _ordered_arguments("ws_ordered", x_u8, x_hat, pixel_filter, mean_filter, weighted, flip_rate)
-    dev = x_u8.device
-    _ordered_path("ws_ordered", path, n, (h - 2) * (w - 2), dev)
-    k, t_max, t_all = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
-    ws = torch.empty(max(lib.wsu_ws_ordered_workspace_bytes(n, h, w) // 8, 1), dtype=torch.int64, device=dev)
+    (n, h, w), source, tau = _ordered_arguments("ws_ordered", x_u8, x_hat, pixel_filter, mean_filter, hat_scale, weighted, flip_rate)
+    _ordered_path("ws_ordered", path, n, (h - 2) * (w - 2), x_u8.device)
+    k, t_max, t_all, ws = _changepoint_outputs(n, lib.wsu_ws_ordered_workspace_bytes(n, h, w), x_u8.device)
     check(_launch("ws_ordered", {"bytes": float(n * h * w * (29 if x_hat is None else 33))}, lambda: lib.wsu_ws_ordered(
-        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
-        pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
-        tau, path.data_ptr(), k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), ws.data_ptr(), ws.numel() * 8, n, h, w, _stream())),
-        "wsu_ws_ordered")
+        x_u8.data_ptr(), *source, tau, path.data_ptr(), k.data_ptr(), t_max.data_ptr(), t_all.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+        n, h, w, _stream())), "wsu_ws_ordered")
     return k, t_max, t_all
 
 
@@ -1204,24 +1194,16 @@ def ws_residual_accumulate(x_u8: torch.Tensor, num: torch.Tensor, den: torch.Ten
     int64 (H-2,W-2) on x_u8's device; per interior pixel num gains the images' terms wgt * r in 2^-24 units, den their weights in 2^-32
     units, an image whose term is NaN adds to neither.  parts: workgroups sharing a pixel tile's images (0: chosen from the plane size);
     the sums are exact integers and do not depend on it."""
-    if int(weighted) not in (0, 1):
-        raise ValueError(f"ws_residual_accumulate: weighted must be 0 or 1 (weighted=-1 is not defined for the residual means), got {weighted}")
-    if (x_hat is None) == (pixel_filter is None):
-        raise ValueError("ws_residual_accumulate: give exactly one of x_hat / pixel_filter")
+    who = "ws_residual_accumulate"
     lib = _lib.load()
-    n, h, w = _u8_planes(x_u8)
+    (n, h, w), source = _ws_source(who, x_u8, x_hat, None, pixel_filter, mean_filter, hat_scale, weighted, "the residual means")
     for name, t in (("num", num), ("den", den)):
         if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and tuple(t.shape) == (h - 2, w - 2) and t.is_contiguous()):
-            raise ValueError(f"ws_residual_accumulate: {name} must be a contiguous int64 tensor of shape {(h - 2, w - 2)} for planes of "
+            raise ValueError(f"{who}: {name} must be a contiguous int64 tensor of shape {(h - 2, w - 2)} for planes of "
                              f"{(h, w)}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-    _dev_check(x_u8, num, den, *[t for t in (x_hat,) if t is not None])
-    mt = filter_taps(mean_filter, np.float32, "kernel")
-    pt, pts, hat_full = _predictor_pointers("ws_residual_accumulate", x_hat, pixel_filter, n, h, w, x_u8.device)
-    check(_launch("ws_residual_accumulate", {"bytes": float(n * h * w * (1 if x_hat is None else 5) + 32 * (h - 2) * (w - 2))},
-                  lambda: lib.wsu_ws_residual_accumulate(
-        x_u8.data_ptr(), x_hat.data_ptr() if x_hat is not None else None, pt.ctypes.data if pt is not None else None,
-        pts.data_ptr() if pts is not None else None, mt.ctypes.data if mt is not None else None, hat_full, float(hat_scale), int(weighted),
-        int(parts), num.data_ptr(), den.data_ptr(), n, h, w, _stream())), "wsu_ws_residual_accumulate")
+    _dev_check(num, den)
+    check(_launch(who, {"bytes": float(n * h * w * (1 if x_hat is None else 5) + 32 * (h - 2) * (w - 2))}, lambda: lib.wsu_ws_residual_accumulate(
+        x_u8.data_ptr(), *source, int(parts), num.data_ptr(), den.data_ptr(), n, h, w, _stream())), "wsu_" + who)
 
 
 MAX_KEY_SEARCH_KEYS = 2 ** 31 - 1          # keys one call of ws_key_search takes

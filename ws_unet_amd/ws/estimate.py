@@ -131,12 +131,16 @@ def predictor_arguments(x_u8: torch.Tensor, pixel_estimator, host_planes=None, c
     return kw | ({"x_bias": torch.from_numpy(np.stack(biases)).to(x_u8.device)} if correct_bias else {})
 
 
+def _weights(mean_estimator, weighted) -> dict:
+    """The weights as the keywords the statistic kernels take: the reference's mean estimator as a kernel array, and `weighted`."""
+    return dict(mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted))
+
+
 def _changepoint(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, order, host_planes=None, return_curve=False, pred=None):
     """ops.ws_sequential's (k, t_max, t_all[, curve]) on the device for a batch of planes, with any pixel predictor `_stat` knows
     (pred: its predictor_arguments, where the caller has made them)."""
     pred = predictor_arguments(x_u8, pixel_estimator, host_planes) if pred is None else pred
-    return ops.ws_sequential(x_u8, mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted), order=order,
-                             return_curve=return_curve, **pred)
+    return ops.ws_sequential(x_u8, order=order, return_curve=return_curve, **_weights(mean_estimator, weighted), **pred)
 
 
 def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct_bias, host_planes=None, placement="random",
@@ -151,12 +155,10 @@ def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct
         k = _changepoint(x_u8, pixel_estimator, mean_estimator, weighted, order, pred=pred)[0]
         beta = sequential.beta(k, x_u8.shape[1], x_u8.shape[2], order).to(torch.float32)
     elif placement == "adaptive":                                      # the changepoint along the recomputed cost order
-        k = ops.ws_ordered(x_u8, adaptive.path_for(x_u8, criterion), mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted),
-                           flip_rate=flip_rate, **pred)[0]
+        k = ops.ws_ordered(x_u8, adaptive.path_for(x_u8, criterion), flip_rate=flip_rate, **_weights(mean_estimator, weighted), **pred)[0]
         beta = adaptive.beta(k, x_u8.shape[1], x_u8.shape[2], flip_rate).to(torch.float32)
     else:
-        beta = ops.ws_attack(x_u8, mean_filter=np.asarray(mean_estimator)[..., ::-1], weighted=int(weighted) if abs(int(weighted)) == 1 else 0,
-                             correct_bias=correct_bias, **pred)
+        beta = ops.ws_attack(x_u8, correct_bias=correct_bias, **_weights(mean_estimator, weighted if abs(int(weighted)) == 1 else 0), **pred)
     return jpeg.without_estimate(beta, pred["x_hat"]) if isinstance(pixel_estimator, jpeg.JPEGEstimator) else beta
 
 
