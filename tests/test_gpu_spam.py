@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 COVERS = (6, 7, 8, 9, 10)
 CONFIGS = [(2, 3), (1, 4), (2, 1), (2, 4), (1, 8)]                          # (order, T)
-TILE_ROWS, TILE_COLS = 32, 512                                              # K36's tile (csrc/spam.hip SM_ROWS, SM_COLS)
+TILE_ROWS, TILE_COLS = 32, 512                                              # K36's tile (csrc/wsu_count.h CT_ROWS, CT_COLS)
 SHAPES = [(1, 1, 1), (1, 1, 4), (1, 4, 1), (1, 4, 4), (2, 3, 5), (1, 16, 300), (1, 67, 259), (2, 131, 40), (1, TILE_ROWS + 1, TILE_COLS + 1)]
 
 

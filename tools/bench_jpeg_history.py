@@ -6,7 +6,8 @@
   * the whole predictor (ws.jpeg.JPEGEstimator.planes: K31, the rule, one read-back of the qualities, K32) by the wall clock;
   * for context, from the same process: the forward of an untrained unet_2 (formula weights, the default inference mode) on the same
     batch (unet_run.unet_plane), and the WS statistic on a resident prediction (K11).
-  Each figure is the median of --reps timings between HIP events after warm-up, each over --inner back-to-back calls.  No gate: nothing
+  Each figure is the median of --reps timings between HIP events after warm-up, each over --inner back-to-back calls, with the 10th and
+  90th percentile of those timings.  No gate: nothing
   earlier computes this.  The energies are checked against the numpy restatement (tests/jpeg_np.py) for one image.
 Usage: python tools/bench_jpeg_history.py [--batch 32] [--reps 30] [--inner 5]"""
 import argparse
@@ -41,7 +42,7 @@ tables95, table1 = ops.jpeg_tables(np.arange(1, 96)), ops.jpeg_tables([75])
 tables75 = np.repeat(table1, a.batch, axis=0)
 
 
-def median_ms(fn):
+def sample_ms(fn):
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
@@ -54,18 +55,20 @@ def median_ms(fn):
         e1.record()
         e1.synchronize()
         ms.append(e0.elapsed_time(e1) / a.inner)
-    return float(np.median(ms))
+    return np.asarray(ms)
 
 
-def rates(ms):
-    return {"ms": round(ms, 4), "ms_per_image": round(ms / a.batch, 5), "images_per_s": round(a.batch / ms * 1e3, 1)}
+def rates(samples):
+    ms = float(np.median(samples))
+    return {"ms": round(ms, 4), "p10": round(float(np.percentile(samples, 10)), 4), "p90": round(float(np.percentile(samples, 90)), 4),
+            "ms_per_image": round(ms / a.batch, 5), "images_per_s": round(a.batch / ms * 1e3, 1)}
 
 
 out = {"batch": a.batch, "shape": [512, 512]}
-out["jpeg_energies_95_tables"] = rates(median_ms(lambda: ops.jpeg_energies(x, tables95)))
-out["jpeg_energies_1_table"] = rates(median_ms(lambda: ops.jpeg_energies(x, table1)))
-out["jpeg_predict"] = rates(median_ms(lambda: ops.jpeg_predict(x, tables75)))
-out["jpeg_predict_with_u8"] = rates(median_ms(lambda: ops.jpeg_predict(x, tables75, want_u8=True)))
+out["jpeg_energies_95_tables"] = rates(sample_ms(lambda: ops.jpeg_energies(x, tables95)))
+out["jpeg_energies_1_table"] = rates(sample_ms(lambda: ops.jpeg_energies(x, table1)))
+out["jpeg_predict"] = rates(sample_ms(lambda: ops.jpeg_predict(x, tables75)))
+out["jpeg_predict_with_u8"] = rates(sample_ms(lambda: ops.jpeg_predict(x, tables75, want_u8=True)))
 est = jpeg.JPEGEstimator()
 est.planes(x)
 torch.cuda.synchronize()
@@ -73,14 +76,14 @@ t0 = time.perf_counter()
 for _ in range(a.reps):
     est.planes(x)
 torch.cuda.synchronize()
-out["estimator_planes_wall"] = rates((time.perf_counter() - t0) * 1e3 / a.reps)
+out["estimator_planes_wall"] = rates([(time.perf_counter() - t0) * 1e3 / a.reps])
 
 model = get_model("unet_2", in_channels=1, out_channels=1, channel=[0], drop_rate=None, mode=None)
 model.load_state_dict({k: torch.from_numpy(v) for k, v in formula.formula_state_dict(2, "he").items()})
 model = model.to("cuda")
-out["unet_2_forward"] = rates(median_ms(lambda: unet_plane(model, x)))
+out["unet_2_forward"] = rates(sample_ms(lambda: unet_plane(model, x)))
 hat = ops.jpeg_predict(x, tables75)
-out["ws_attack_on_resident_plane"] = rates(median_ms(lambda: ops.ws_attack(x, hat, hat_scale=1.0, weighted=0)))
+out["ws_attack_on_resident_plane"] = rates(sample_ms(lambda: ops.ws_attack(x, hat, hat_scale=1.0, weighted=0)))
 out["energies_over_unet_forward"] = round(out["jpeg_energies_95_tables"]["ms"] / out["unet_2_forward"]["ms"], 3)
 
 q = jpeg.estimate_quality(x[:5]).cpu().numpy()

@@ -1,7 +1,7 @@
 """Time the moment kernel of the least-squares predictors (ops.ols_moments, K24) on one GPU and print one JSON line.
 
   * the kernel on --batch resident 512x512 planes (the five fixture covers tiled): median of --reps calls between HIP events after
-    warm-up -> ms, images/s and GB/s of pixels read (1 byte per pixel);
+    warm-up -> ms with the 10th and 90th percentile of the samples, images/s and GB/s of pixels read (1 byte per pixel);
   * numpy on the host for the same moments from the same uint8 planes: the float64 design matrix of every image and one BLAS
     `V.T @ V` each (exact: an image's sums stay below 2^53), images spread over --threads threads; checked equal to the kernel's.
 Usage: python tools/bench_ols.py [--batch 32] [--reps 50] [--threads 16]"""
@@ -41,6 +41,7 @@ for _ in range(a.reps):
     e1.record()
     e1.synchronize()
     ms.append(e0.elapsed_time(e1))
+p10, p90 = float(np.percentile(ms, 10)), float(np.percentile(ms, 90))
 ms = float(np.median(ms))
 
 _RING = ops._RING + ((1, 1),)
@@ -58,6 +59,6 @@ with ThreadPoolExecutor(max_workers=a.threads) as pool:
     ref = np.stack(list(pool.map(host_moments, planes)))
     host_ms = (time.perf_counter() - t0) * 1e3
 assert np.array_equal(ref, got.cpu().numpy()), "kernel and numpy moments differ"
-print(json.dumps({"batch": a.batch, "shape": [512, 512], "kernel_ms": round(ms, 4), "images_per_s": round(a.batch / ms * 1e3, 1),
+print(json.dumps({"batch": a.batch, "shape": [512, 512], "kernel_ms": round(ms, 4), "p10": round(p10, 4), "p90": round(p90, 4), "images_per_s": round(a.batch / ms * 1e3, 1),
                   "pixel_GB_per_s": round(planes.size / ms / 1e6, 2), "numpy_ms": round(host_ms, 2), "numpy_threads": a.threads,
                   "numpy_images_per_s": round(a.batch / host_ms * 1e3, 1)}))

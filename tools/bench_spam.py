@@ -6,12 +6,11 @@
     GB/s of pixels read (1 byte per pixel) and the share of the HBM read floor (the N H W bytes at the 8 TB/s of the data sheet);
   * the same counts from a torch composition on the device in the same process (differences of shifted slices, clamp, the bin index,
     one torch.bincount per direction over the whole batch): what a user could do before K36; checked equal, timed the same way;
-  * --ab-lib FILE: the A/B of the register path for the centre bins against all LDS atomics.  FILE is a library built from the same
-    sources with the register path off,
-        hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -DWSU_SPAM_HOT_BINS=0 -shared \
+  * --ab-lib FILE --ab-name NAME: an A/B against another build of the entry point, for instance another commit's
+        hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -shared \
               ws_unet_amd/csrc/wsu_common.hip ws_unet_amd/csrc/spam.hip -o FILE
-    Both arms run in this process, alternating sample by sample, results checked equal first (--ab-name NAME labels any other build of
-    the entry point that is compared this way);
+    Both arms run in this process, alternating sample by sample, results checked equal first (profiles/r29 compared the register path
+    for the centre bins with all LDS atomics this way);
   * --score-repeats R: `spam.score` end to end from PNG files (decode, upload, K36, features, the discriminant) over the five fixture
     covers and their LSBR 0.1 twins, R times after one warm-up pass, by the wall clock -> images/s.
 Usage: python tools/bench_spam.py [--batch 32] [--reps 100] [--inner 50] [--configs 2,3 1,4] [--ab-lib FILE [--ab-name NAME]] [--score-repeats 20]"""

@@ -1,4 +1,5 @@
-"""Bit-level record of the metric kernels (K10-K19, K27, K29, K33, filter3x3_valid, lsb_delta_unit, the WS meter) on fixed synthetic inputs.
+"""Bit-level record of the metric kernels (K10-K19, K27, K29, K33, filter3x3_valid, lsb_delta_unit, the WS meter) on fixed synthetic inputs
+and of the count kernels (K24-K26, K31, K36) on the fixture covers, a constant plane, noise and two ragged shapes.
 
   python tools/metric_bits.py OUT.json          run every op once and write, per output tensor, the SHA-256 of its bytes; rows whose
                                                 float32 sequence has an inexact product (`may_move`) also keep their values and their
@@ -177,6 +178,23 @@ def main(out_path) -> None:
     scores = torch.from_numpy(np.concatenate([rng.random(5000), rng.random(3000) * 0.1, [np.nan, 0.0, 1.0]])).to(dev)
     labels = torch.from_numpy(rng.integers(-1, 2, scores.numel()).astype(np.int8)).to(dev)
     put("K19 roc_counts", ops.roc_counts(scores, labels, [0, 5000, 8000, scores.numel()], roc.TAUS))
+
+    # K24, K25, K26, K36, K31: exact integer tables (none may move) of the five fixture covers, a constant plane, uniform noise and two
+    # ragged shapes (K31 on their largest multiple-of-8 crops)
+    from ws_unet_amd.imread import imread4_u8
+    gold = ROOT / "tests" / "golden"
+    planes = {"covers": np.stack([np.ascontiguousarray(imread4_u8(gold / f"cover_{k}.png")[..., 3]) for k in (6, 7, 8, 9, 10)]),
+              "constant": np.full((1, 512, 512), 77, dtype=np.uint8), "noise": rng.integers(0, 256, (1, 512, 512), dtype=np.uint8),
+              "2x131x40": rng.integers(0, 256, (2, 131, 40), dtype=np.uint8), "1x67x259": rng.integers(0, 256, (1, 67, 259), dtype=np.uint8) // 16}
+    tables95 = ops.jpeg_tables(np.arange(1, 96))
+    for tag, p in planes.items():
+        t = torch.from_numpy(p).to(dev)
+        put(f"K24 ols_moments {tag}", ops.ols_moments(t))
+        put(f"K25 spa_tables {tag}", ops.spa_tables(t))
+        put(f"K26 rs_counts {tag}", ops.rs_counts(t))
+        for order, T in ((2, 3), (1, 4), (1, 8)):
+            put(f"K36 spam_counts order={order} T={T} {tag}", ops.spam_counts(t, order, T))
+        put(f"K31 jpeg_energies {tag}", ops.jpeg_energies(t[:, : p.shape[1] // 8 * 8, : p.shape[2] // 8 * 8].contiguous(), tables95))
 
     torch.cuda.synchronize()
     Path(out_path).write_text("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in rows.items()) + "\n}\n")

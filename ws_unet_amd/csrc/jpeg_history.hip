@@ -19,14 +19,15 @@
 //   t // Q is int(float(t) * (1.f / Q) + 0.002f): float(t) is exact, the product is within 2^-10 of t / Q, and the fractional part of
 //   t / Q is 0 or lies in [1/255, 254/255], so the truncation is the quotient (tests/test_jpeg_host.py walks every t and Q).  A thread
 //   keeps (2 ah + hb, S ah + lo, S) per coefficient, JH_B blocks deep, so that a table's Q and 1 / Q are read from LDS once per JH_B
-//   blocks; a wave's sum per table takes six shuffles, the four waves meet in LDS, and a workgroup adds each table's sum with one 64-bit
-//   vector atomic.  The tables travel as a kernel argument, JH_TCH at a launch (a launch per JH_TCH tables, each repeating the
-//   transform: 64 multiply-adds per thread against ~300 operations per table).
+//   blocks; a table's sum leaves through the wave fold and the flush of the count kernels (wsu_count.h), in 64 bits.  The tables travel
+//   as a kernel argument, JH_TCH at a launch (a launch per JH_TCH tables, each repeating the transform: 64 multiply-adds per thread
+//   against ~300 operations per table).
 // K32 quantises with the image's own table, transforms back through LDS (32-bit first pass) and writes a row of eight pixels per
 //   thread.  An image with use = 0 gets the KB prediction in K11's float32 operation sequence (ws_pixel_terms: conv of u / 255.f, summed
 //   K00 .. K22, times 255.f) on its interior and the pixel itself on its border, so that the statistic of such an image has the bits of
 //   the KB filter's row.
 #pragma clang fp contract(off)
+#include "wsu_count.h"
 #include "wsu_metric.h"
 
 namespace {
@@ -105,12 +106,6 @@ __device__ __forceinline__ void jh_forward(const uint8_t* __restrict__ img, int 
     }
 }
 
-__device__ __forceinline__ unsigned long long jh_wave_sum(unsigned long long s) {             // valid in lane 0
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    return s;
-}
-
 __global__ __launch_bounds__(JH_THREADS) void jpeg_energies_kernel(const uint8_t* __restrict__ xu8, const JhTables tabs, int mt,
                                                                   unsigned long long* __restrict__ energies, int m_total, int h, int w,
                                                                   long long blocks) {
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(JH_THREADS) void jpeg_energies_kernel(const uint8_t
     __shared__ __attribute__((aligned(16))) int qi[JH_TCH * 64];
     __shared__ __attribute__((aligned(16))) float qr[JH_TCH * 64];
     __shared__ int cm[64];
-    __shared__ unsigned long long part[JH_WAVES][JH_TCH];
+    __shared__ unsigned long long part[JH_WAVES * JH_TCH];         // [JH_WAVES][mt]
     const int tid = threadIdx.x, nn = blockIdx.y, u = tid & 7;
     for (int i = tid; i < mt * 64; i += JH_THREADS) {
         const int q = tabs.q[i >> 6][i & 63];
@@ -163,16 +158,10 @@ __global__ __launch_bounds__(JH_THREADS) void jpeg_energies_kernel(const uint8_t
                 const int rp = p[j][v] - __mul24(sg[j][v], __mul24(k, q[v]));
                 e += (unsigned long long)((long long)rp * rp);
             }
-        e = jh_wave_sum(e);
-        if ((tid & 63) == 0) part[tid >> 6][mm] = e;
+        e = wave_sum(e);
+        if ((tid & 63) == 0) part[(tid >> 6) * mt + mm] = e;
     }
-    __syncthreads();
-    if (tid < mt) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int k = 0; k < JH_WAVES; ++k) s += part[k][tid];
-        if (s) atomicAdd(&energies[(size_t)nn * m_total + tid], s);
-    }
+    count_flush<JH_WAVES>(part, mt, energies, (size_t)nn * m_total);
 }
 
 // the KB filter's K[a][b] (filters.NAMED_FILTERS_2D['KB']); symmetric, so K and the taps of the correlation layout are the same numbers

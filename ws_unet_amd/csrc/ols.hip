@@ -9,10 +9,9 @@
 // one column per thread, walking down the rows with a 3x3 register window (three byte loads per pixel).  32-bit accumulators suffice for
 // the WHOLE tile, not only for a thread: a product is at most 255 * 255 = 65 025, and 2^32 / 65 025 = 66 051.3, so a 32-bit sum holds
 // 66 051 products whatever the pixels; a tile has OLS_TR * OLS_TC = 16 384 of them (a thread's own accumulator sees at most OLS_TR = 64).
-// The tile's 45 sums (wave shuffle, then the four waves through LDS) are widened once and added to the image's 64-bit moments with one
-// vector atomic each; the entry point zeroes `moments` on the stream first.
+// The tile's 45 sums leave through the wave fold, the flush and the launch set-up of the count kernels (wsu_count.h).
 // HBM-bound in principle (1 B per pixel); at 45 integer multiply-adds per pixel the VALU is the longer pole.
-#include "wsu_device.h"
+#include "wsu_count.h"
 
 namespace {
 
@@ -49,18 +48,10 @@ __global__ __launch_bounds__(OLS_TC) void ols_moments_kernel(const uint8_t* __re
     }
 #pragma unroll
     for (int m = 0; m < OLS_M; ++m) {
-        uint32_t s = acc[m];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+        const uint32_t s = wave_sum(acc[m]);
         if ((tid & 63) == 0) part[tid >> 6][m] = s;
     }
-    __syncthreads();
-    if (tid < OLS_M) {
-        uint32_t s = 0u;
-#pragma unroll
-        for (int k = 0; k < OLS_TC / 64; ++k) s += part[k][tid];
-        if (s) atomicAdd(&moments[(size_t)nn * OLS_M + tid], (unsigned long long)s);
-    }
+    count_flush<OLS_TC / 64>(&part[0][0], OLS_M, moments, (size_t)nn * OLS_M);
 }
 
 }  // namespace
@@ -68,14 +59,7 @@ __global__ __launch_bounds__(OLS_TC) void ols_moments_kernel(const uint8_t* __re
 extern "C" {
 
 int wsu_ols_moments(const uint8_t* x_u8, unsigned long long* moments, int n, int h, int w, void* stream) {
-    WSU_REQUIRE(x_u8 && moments, "ols_moments: null pointer");
-    WSU_REQUIRE(n > 0 && n <= 65535 && h >= 3 && w >= 3, "ols_moments: bad shape n=%d h=%d w=%d", n, h, w);
-    const long long tiles_r = ((long long)h - 2 + OLS_TR - 1) / OLS_TR, tiles_c = ((long long)w - 2 + OLS_TC - 1) / OLS_TC;
-    WSU_REQUIRE(tiles_r * tiles_c <= 0x7fffffffll, "ols_moments: image of %d x %d has too many tiles", h, w);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(moments, 0, (size_t)n * OLS_M * sizeof(unsigned long long), s) != hipSuccess) return wsu_check_launch("ols_moments memset");
-    hipLaunchKernelGGL(ols_moments_kernel, dim3((unsigned)(tiles_r * tiles_c), n), dim3(OLS_TC), 0, s, x_u8, moments, h, w, (int)tiles_c);
-    return wsu_check_launch("ols_moments_kernel");
+    return count_launch("ols_moments", "ols_moments memset", "ols_moments_kernel", ols_moments_kernel, OLS_TC, 0, x_u8, moments, OLS_M, n, h, w, 1, OLS_TR, OLS_TC, stream);
 }
 
 }  // extern "C"

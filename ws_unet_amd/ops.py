@@ -1276,44 +1276,38 @@ def ws_key_search(num: torch.Tensor, den: torch.Tensor, h: int, w: int, *, keys:
     return snum, sden
 
 
+def _count_entry(entry: str, x_u8: torch.Tensor, tail_shape: Tuple[int, ...], *middle, out: Optional[torch.Tensor] = None, after=()) -> torch.Tensor:
+    """wsu_<entry>(x, *middle, table, n, h, w, *after, stream), the form of every count entry -> the (N, *tail_shape) int64 table of exact
+    sums, which the call zeroes first.  after: what an entry takes behind w (K36's order and T).  out: a tensor of that form to write into;
+    it is NOT validated here, the caller has checked its dtype, shape and device."""
+    n, h, w = _u8_planes(x_u8)
+    if n == 0:
+        raise ValueError(f"{entry}: no images")
+    symbol = "wsu_" + entry
+    fn = getattr(_lib.load(), symbol)
+    table = torch.empty((n, *tail_shape), dtype=torch.int64, device=x_u8.device) if out is None else out
+    check(_launch(entry, {"bytes": float(n * h * w)}, lambda: fn(
+        x_u8.data_ptr(), *middle, table.data_ptr(), n, h, w, *after, _stream())), symbol)
+    return table
+
+
 def ols_moments(x_u8: torch.Tensor) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,45) int64: per image the exact sums of v_i * v_j, i <= j (row-major upper triangle), over the interior
     pixels, v = the eight neighbours in ring order (_RING) and the centre (wsu_ols_moments, K24; ws_unet_amd.ols unpacks and solves)."""
-    lib = _lib.load()
-    n, h, w = _u8_planes(x_u8)
-    if n == 0:
-        raise ValueError("ols_moments: no images")
-    moments = torch.empty((n, 45), dtype=torch.int64, device=x_u8.device)
-    check(_launch("ols_moments", {"bytes": float(n * h * w)}, lambda: lib.wsu_ols_moments(
-        x_u8.data_ptr(), moments.data_ptr(), n, h, w, _stream())), "wsu_ols_moments")
-    return moments
+    return _count_entry("ols_moments", x_u8, (45,))
 
 
 def spa_tables(x_u8: torch.Tensor) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,3,128) int64: per image the sample-pairs table over all horizontally and vertically adjacent pixel pairs
     (u,v), indexed by m = |u-v| >> 1: [0] E, |u-v| even; [1] X, odd with max(u,v) even; [2] Y, odd with max(u,v) odd (wsu_spa_tables, K25;
     ws_unet_amd.ws.structural.spa solves)."""
-    lib = _lib.load()
-    n, h, w = _u8_planes(x_u8)
-    if n == 0:
-        raise ValueError("spa_tables: no images")
-    tables = torch.empty((n, 3, 128), dtype=torch.int64, device=x_u8.device)
-    check(_launch("spa_tables", {"bytes": float(n * h * w)}, lambda: lib.wsu_spa_tables(
-        x_u8.data_ptr(), tables.data_ptr(), n, h, w, _stream())), "wsu_spa_tables")
-    return tables
+    return _count_entry("spa_tables", x_u8, (3, 128))
 
 
 def rs_counts(x_u8: torch.Tensor) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,8) int64: per image R_M, S_M, R_-M, S_-M over the groups of 4 consecutive pixels of every row with the
     mask (0,1,1,0), then the same four on the plane with every LSB flipped (wsu_rs_counts, K26; ws_unet_amd.ws.structural.rs solves)."""
-    lib = _lib.load()
-    n, h, w = _u8_planes(x_u8)
-    if n == 0:
-        raise ValueError("rs_counts: no images")
-    counts = torch.empty((n, 8), dtype=torch.int64, device=x_u8.device)
-    check(_launch("rs_counts", {"bytes": float(n * h * w)}, lambda: lib.wsu_rs_counts(
-        x_u8.data_ptr(), counts.data_ptr(), n, h, w, _stream())), "wsu_rs_counts")
-    return counts
+    return _count_entry("rs_counts", x_u8, (8,))
 
 
 def spam_bins(order: int, T: int) -> int:
@@ -1329,20 +1323,13 @@ def spam_counts(x_u8: torch.Tensor, order: int = 2, T: int = 3, out: Optional[to
     whose order + 2 pixels lie in the image; bin = the differences + T as base-B digits, the first one most significant (wsu_spam_counts,
     K36; ws_unet_amd.spam makes the features).  The defaults are SPAM-686.  `out`: an int64 tensor of that shape to write into (the call
     zeroes it)."""
-    lib = _lib.load()
     bins = spam_bins(order, T)
-    n, h, w = _u8_planes(x_u8)
-    if n == 0:
-        raise ValueError("spam_counts: no images")
-    if out is None:
-        out = torch.empty((n, 4, bins), dtype=torch.int64, device=x_u8.device)
-    else:
+    n = _u8_planes(x_u8)[0]
+    if out is not None and n:
         _dev_check(out)
         if out.dtype != torch.int64 or tuple(out.shape) != (n, 4, bins) or out.device != x_u8.device:
             raise ValueError(f"spam_counts: out must be an int64 tensor of shape {(n, 4, bins)} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
-    check(_launch("spam_counts", {"bytes": float(n * h * w)}, lambda: lib.wsu_spam_counts(
-        x_u8.data_ptr(), out.data_ptr(), n, h, w, int(order), int(T), _stream())), "wsu_spam_counts")
-    return out
+    return _count_entry("spam_counts", x_u8, (4, bins), out=out, after=(int(order), int(T)))
 
 
 # IJG luminance base table (the JPEG standard's Annex K.1), row-major by frequency [u][v]
@@ -1381,12 +1368,8 @@ def jpeg_energies(x_u8: torch.Tensor, tables) -> torch.Tensor:
     """x_u8: (N,H,W) uint8, H and W multiples of 8; tables: HOST integer (M,8,8), entries 1..255 -> int64 (N,M): the residual energy of
     every image's 8x8 DCT coefficients against every table, in 2^-20 units (wsu_jpeg_energies, K31; ws_unet_amd.ws.jpeg reads the
     compression history from it).  Exact integers."""
-    lib = _lib.load()
-    n, h, w, t = _jpeg_args("jpeg_energies", x_u8, tables, None)
-    energies = torch.empty((n, t.shape[0]), dtype=torch.int64, device=x_u8.device)
-    check(_launch("jpeg_energies", {"bytes": float(n * h * w)}, lambda: lib.wsu_jpeg_energies(
-        x_u8.data_ptr(), t.ctypes.data, t.shape[0], energies.data_ptr(), n, h, w, _stream())), "wsu_jpeg_energies")
-    return energies
+    t = _jpeg_args("jpeg_energies", x_u8, tables, None)[3]
+    return _count_entry("jpeg_energies", x_u8, (t.shape[0],), t.ctypes.data, t.shape[0])
 
 
 def jpeg_predict(x_u8: torch.Tensor, tables, use=None, want_u8: bool = False, want_hat: bool = True):
