@@ -507,6 +507,26 @@ int wsu_rs_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h,
  *      integers, the same bits on every run.  n in 1..65535; every argument is checked before any HIP call. */
 int wsu_spam_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, int order, int T, void* stream);
 
+/* ---- K49: the co-occurrence counts of the linear ("spam"-type) submodels of the spatial rich model (SRM; Fridrich, Kodovsky, IEEE TIFS
+ *      7(3), 2012; not part of the reference; only these submodels, no min/max ones; not compared with the authors' extractor).
+ *      x_u8: (N,H,W) DEVICE pixels X[r][c], any H, W >= 1.  All arithmetic is exact integer arithmetic.  Eight residuals per pixel:
+ *        S1   h: X[r][c+1] - X[r][c]                                  v: X[r+1][c] - X[r][c]                      q2 = 2, 4
+ *        S2   h: X[r][c-1] - 2 X[r][c] + X[r][c+1]                    v: the same down a column                   q2 = 4, 6, 8
+ *        S3   h: X[r][c-1] - 3 X[r][c] + 3 X[r][c+1] - X[r][c+2]      v: the same down a column                   q2 = 6, 9, 12
+ *        S3x3 n: [[-1,2,-1],[2,-4,2],[-1,2,-1]] centred on (r,c)                                                  q2 = 8, 12, 16
+ *        S5x5 n: [[-1,2,-2,2,-1],[2,-6,8,-6,2],[-2,8,-12,8,-2],[2,-6,8,-6,2],[-1,2,-2,2,-1]] centred on (r,c)    q2 = 24, 36, 48
+ *      The digit of a residual R at the step q = q2 / 2 is d = sign(R) min((4|R| + q2) / (2 q2), 2) in integer division: R / q rounded
+ *      with halves away from zero, then cut to -2 .. 2.  A table takes one residual at one q and scans it h (the four digits at columns
+ *      c .. c+3 of a row) or v (at rows r .. r+3 of a column); a run counts when every pixel that its four residuals read lies in the image
+ *      (no padding) and adds 1 to bin sum_k (d_k + 2) 5^(3-k), the leftmost or topmost digit the most significant: 625 bins, centre 312.
+ *      The 44 tables in order: for class in S1, S2, S3, S3x3, S5x5; for q ascending; for residual in (h, v) or the one n; for scan in
+ *      (h, v): S1 is 0..7, S2 8..19, S3 20..31, S3x3 32..37, S5x5 38..43.  A table sums to max(H - a, 0) max(W - b, 0) with (a,b) =
+ *        S1: hh (0,4) hv (3,1) vh (1,3) vv (4,0);  S2: (0,5) (3,2) (2,3) (5,0);  S3: (0,6) (3,3) (3,3) (6,0);  S3x3: nh (2,5) nv (5,2);
+ *        S5x5: nh (4,7) nv (7,4).
+ *      counts: DEVICE (N, 44, 625) uint64, zeroed on the stream by this call.  Exact integers, the same bits on every run.  n in
+ *      1..65535; every argument is checked before any HIP call. */
+int wsu_srm_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
+
 /* ---- K12-K14: HILL-cost weighted prediction error (wMAE) of src/filters/evaluate.py:79-115 `get_filter_residuals_cover` and
  *      src/predictor_error.py:19-76 `attack`.  Both reference callers take HILL from a library (conseal.hill._costmap.compute_cost,
  *      stegolab2.hill.compute_rho); here both are the textbook cost, the one pinned by results/prediction/filters.csv:

@@ -1,4 +1,4 @@
-// What the exact count kernels share (ols.hip: K24; structural.hip: K25, K26; spam.hip: K36; jpeg_history.hip: K31): the strip tile and its
+// What the exact count kernels share (ols.hip: K24; structural.hip: K25, K26; spam.hip: K36; srm.hip: K49; jpeg_history.hip: K31): the strip tile and its
 // loaders, the wave fold, the packed counter of the hot bins, a workgroup's flush and the host's launch set-up.  Every output is a table of
 // exact integers that the kernels only ADD to, so the bits depend on no order: the entry point zeroes the table on the stream, a workgroup
 // sums its tile in 32- or 64-bit partials and adds each non-zero sum with one 64-bit vector atomic.
@@ -20,6 +20,14 @@ __device__ __forceinline__ CtStrip ct_strip(int tiles_c, int w, int reach) {
     s.c = (long long)(blockIdx.x % tiles_c) * CT_COLS + (threadIdx.x & (CT_STRIPS - 1)) * 16;
     s.r0 = (long long)(blockIdx.x / tiles_c) * CT_ROWS + (threadIdx.x / CT_STRIPS) * CT_TRT;
     s.rem = (int)min(max((long long)w - s.c, 0ll), (long long)(16 + reach));
+    return s;
+}
+// the same for a kernel whose threads walk TRT rows (K49: 8, a tile of CT_GROUPS * TRT rows): c, r0, and rem capped at 32
+template <int TRT> __device__ __forceinline__ CtStrip ct_strip_rows(int tiles_c, int w) {
+    CtStrip s;
+    s.c = (long long)(blockIdx.x % tiles_c) * CT_COLS + (threadIdx.x & (CT_STRIPS - 1)) * 16;
+    s.r0 = (long long)(blockIdx.x / tiles_c) * (CT_GROUPS * TRT) + (threadIdx.x / CT_STRIPS) * TRT;
+    s.rem = (int)min(max((long long)w - s.c, 0ll), 32ll);
     return s;
 }
 
@@ -108,14 +116,14 @@ template <int FIELDS, int BITS, int UPDATES> struct HotBins {
 
 // The end of every count kernel, by all WAVES * 64 threads of the workgroup: part holds the waves' partial sums [WAVES][k] in LDS (written
 // by plain stores or LDS atomics before the call; the barrier is in here); out[row + b] += the sum over the waves, b < k, one 64-bit vector
-// atomic per non-zero sum.
-template <int WAVES, class T>
+// atomic per non-zero sum.  COPIES: how many partial tables part holds when that is not one per wave (K49: one that its waves share).
+template <int WAVES, class T, int COPIES = WAVES>
 __device__ __forceinline__ void count_flush(const T* __restrict__ part, int k, unsigned long long* __restrict__ out, size_t row) {
     __syncthreads();
     for (int b = threadIdx.x; b < k; b += WAVES * 64) {
         T s = 0;
 #pragma unroll
-        for (int j = 0; j < WAVES; ++j) s += part[j * k + b];
+        for (int j = 0; j < COPIES; ++j) s += part[j * k + b];
         if (s) atomicAdd(&out[row + b], (unsigned long long)s);
     }
 }

@@ -1332,6 +1332,34 @@ def spam_counts(x_u8: torch.Tensor, order: int = 2, T: int = 3, out: Optional[to
     return _count_entry("spam_counts", x_u8, (4, bins), out=out, after=(int(order), int(T)))
 
 
+# The tables of K49 as data.  SRM_Q2: per residual class its quantisation steps as q2 = 2q, ascending.  SRM_REACH: per class and
+# (residual, scan) the (a, b) of the table's total max(H - a, 0) max(W - b, 0).  SRM_TABLES: the 44 tables in the order of the counts,
+# (class, q2, residual, scan, a, b): for class; for q ascending; for residual in (h, v) or the one n; for scan in (h, v).
+SRM_T, SRM_ORDER, SRM_BINS = 2, 4, 625
+SRM_Q2 = {"S1": (2, 4), "S2": (4, 6, 8), "S3": (6, 9, 12), "S3x3": (8, 12, 16), "S5x5": (24, 36, 48)}
+SRM_REACH = {"S1": {("h", "h"): (0, 4), ("h", "v"): (3, 1), ("v", "h"): (1, 3), ("v", "v"): (4, 0)},
+             "S2": {("h", "h"): (0, 5), ("h", "v"): (3, 2), ("v", "h"): (2, 3), ("v", "v"): (5, 0)},
+             "S3": {("h", "h"): (0, 6), ("h", "v"): (3, 3), ("v", "h"): (3, 3), ("v", "v"): (6, 0)},
+             "S3x3": {("n", "h"): (2, 5), ("n", "v"): (5, 2)},
+             "S5x5": {("n", "h"): (4, 7), ("n", "v"): (7, 4)}}
+SRM_TABLES = tuple((cls, q2, res, scan, *ab) for cls, steps in SRM_Q2.items() for q2 in steps for (res, scan), ab in SRM_REACH[cls].items())
+
+
+def srm_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,44,625) int64: per image the co-occurrence counts of the linear submodels of the spatial rich model, table
+    by table as SRM_TABLES lists them: the runs of four digits -2..2 of one linear residual at one quantisation step along a row or down
+    a column, over every run whose pixels all lie in the image; bin = the digits + 2 in base 5, the first one most significant
+    (wsu_srm_counts, K49, which include/wsu.h defines; ws_unet_amd.srm makes the features).  `out`: an int64 tensor of that shape to write
+    into (the call zeroes it)."""
+    n = _u8_planes(x_u8)[0]
+    shape = (n, len(SRM_TABLES), SRM_BINS)
+    if out is not None and n:
+        _dev_check(out)
+        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
+            raise ValueError(f"srm_counts: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
+    return _count_entry("srm_counts", x_u8, shape[1:], out=out)
+
+
 # IJG luminance base table (the JPEG standard's Annex K.1), row-major by frequency [u][v]
 _IJG_LUMINANCE = np.array([
     [16, 11, 10, 16, 24, 40, 51, 61], [12, 12, 14, 19, 26, 58, 60, 55], [14, 13, 16, 24, 40, 57, 69, 56], [14, 17, 22, 29, 51, 87, 80, 62],
