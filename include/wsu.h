@@ -508,7 +508,7 @@ int wsu_rs_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h,
 int wsu_spam_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, int order, int T, void* stream);
 
 /* ---- K49: the co-occurrence counts of the linear ("spam"-type) submodels of the spatial rich model (SRM; Fridrich, Kodovsky, IEEE TIFS
- *      7(3), 2012; not part of the reference; only these submodels, no min/max ones; not compared with the authors' extractor).
+ *      7(3), 2012; not part of the reference; only these submodels, the min/max ones are K50's; not compared with the authors' extractor).
  *      x_u8: (N,H,W) DEVICE pixels X[r][c], any H, W >= 1.  All arithmetic is exact integer arithmetic.  Eight residuals per pixel:
  *        S1   h: X[r][c+1] - X[r][c]                                  v: X[r+1][c] - X[r][c]                      q2 = 2, 4
  *        S2   h: X[r][c-1] - 2 X[r][c] + X[r][c+1]                    v: the same down a column                   q2 = 4, 6, 8
@@ -526,6 +526,32 @@ int wsu_spam_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int 
  *      counts: DEVICE (N, 44, 625) uint64, zeroed on the stream by this call.  Exact integers, the same bits on every run.  n in
  *      1..65535; every argument is checked before any HIP call. */
 int wsu_srm_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
+
+/* ---- K50: the co-occurrence counts of the min/max submodels of the spatial rich model built on the directional first-, second- and
+ *      third-order residuals (the paper's minmax22h/v, minmax24, minmax34h/v of the 1st and 3rd order and minmax21, 41, 32, 24h/v of the
+ *      2nd; stated as remembered, not compared with the authors' extractor; NOT built: the 1st/3rd-order submodels that need diagonal
+ *      residuals (minmax41, 34, 48h/v, 54), the EDGE3x3 and EDGE5x5 classes).  x_u8, the digit d(R, q2), a run (four digits at columns
+ *      c..c+3, scan h, or rows r..r+3, scan v) and its bin are K49's.  The directional residuals at a pixel (r,c):
+ *        S1  q2 = 2, 4       E = X[r][c+1] - X[r][c]   W = X[r][c-1] - X[r][c]   S = X[r+1][c] - X[r][c]   N = X[r-1][c] - X[r][c]
+ *        S2  q2 = 4, 6, 8    h = X[r][c-1] - 2 X[r][c] + X[r][c+1]               v = X[r-1][c] - 2 X[r][c] + X[r+1][c]
+ *                            d = X[r-1][c-1] - 2 X[r][c] + X[r+1][c+1]           m = X[r-1][c+1] - 2 X[r][c] + X[r+1][c-1]
+ *        S3  q2 = 6, 9, 12   E = X[r][c-1] - 3 X[r][c] + 3 X[r][c+1] - X[r][c+2]   W = X[r][c+1] - 3 X[r][c] + 3 X[r][c-1] - X[r][c-2]
+ *                            S = X[r-1][c] - 3 X[r][c] + 3 X[r+1][c] - X[r+2][c]   N = X[r+1][c] - 3 X[r][c] + 3 X[r-1][c] - X[r-2][c]
+ *      A set is a list of residuals of one class taken at the same pixel; its digits are lo = the minimum and hi = the maximum of its
+ *      members' digits (the digit is monotone: the digit of the smallest / largest residual).  The sets in order:
+ *        S1 and S3: WE, NS, WENS, WNE, ESW, SWN, NES          S2: hv, hvdm, hvd, hvm, hd, hm, vd, vm
+ *      One table per (class, q2, set, scan), and TWO updates per run: the run of four lo digits adds 1 at its bin, the run of four hi
+ *      digits adds 1 at the bin of the NEGATED digits, 624 - bin (the rich model's min/max symmetrisation, done at the source).  A run
+ *      counts when every pixel that any member of the set reads at any of its four positions lies in the image (no padding).  With
+ *      (u, dn, l, rt) how far the set's taps reach up, down, left and right, a scan-h table sums to 2 max(H - u - dn, 0) max(W - l - rt - 3, 0)
+ *      and a scan-v table to 2 max(H - u - dn - 3, 0) max(W - l - rt, 0):
+ *        S1: WE (0,0,1,1) NS (1,1,0,0) WENS (1,1,1,1) WNE (1,0,1,1) ESW (0,1,1,1) SWN (1,1,1,0) NES (1,1,0,1);   S2: every set (1,1,1,1);
+ *        S3: WE (0,0,2,2) NS (2,2,0,0) WENS (2,2,2,2) WNE (2,1,2,2) ESW (1,2,2,2) SWN (2,2,2,1) NES (2,2,1,2).
+ *      The 118 tables in order: for class in S1, S2, S3; for q2 ascending; for set as listed; for scan in (h, v): S1 is 0..27, S2 28..75,
+ *      S3 76..117.  counts: DEVICE (N, 118, 625) uint64, zeroed on the stream by this call; an image too small for a table leaves it zero.
+ *      Exact integers, the same bits on every run, independent of the batch split.  n in 1..65535; every argument is checked before any
+ *      HIP call. */
+int wsu_srm_minmax_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
 
 /* ---- K12-K14: HILL-cost weighted prediction error (wMAE) of src/filters/evaluate.py:79-115 `get_filter_residuals_cover` and
  *      src/predictor_error.py:19-76 `attack`.  Both reference callers take HILL from a library (conseal.hill._costmap.compute_cost,

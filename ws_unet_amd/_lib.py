@@ -109,6 +109,7 @@ SIGNATURES = {
     "wsu_rs_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_spam_counts": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "wsu_srm_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "wsu_srm_minmax_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_lsb_delta_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     "wsu_filter3x3_valid_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_hill_cost": (c_int, [_P, _P, c_float, c_int, c_int, c_int, _P]),

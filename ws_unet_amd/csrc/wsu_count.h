@@ -1,7 +1,8 @@
-// What the exact count kernels share (ols.hip: K24; structural.hip: K25, K26; spam.hip: K36; srm.hip: K49; jpeg_history.hip: K31): the strip tile and its
-// loaders, the wave fold, the packed counter of the hot bins, a workgroup's flush and the host's launch set-up.  Every output is a table of
-// exact integers that the kernels only ADD to, so the bits depend on no order: the entry point zeroes the table on the stream, a workgroup
-// sums its tile in 32- or 64-bit partials and adds each non-zero sum with one 64-bit vector atomic.
+// What the exact count kernels share (ols.hip: K24; structural.hip: K25, K26; spam.hip: K36; srm.hip: K49; srm_minmax.hip: K50;
+// jpeg_history.hip: K31): the strip tile and its loaders, the wave fold, the packed counter of the hot bins, a workgroup's flush and the
+// host's launch set-up.  Every output is a table of exact integers that the kernels only ADD to, so the bits depend on no order: the entry
+// point zeroes the table on the stream, a workgroup sums its tile in 32- or 64-bit partials and adds each non-zero sum with one 64-bit
+// vector atomic.
 #pragma once
 #include "wsu_device.h"
 
@@ -22,7 +23,7 @@ __device__ __forceinline__ CtStrip ct_strip(int tiles_c, int w, int reach) {
     s.rem = (int)min(max((long long)w - s.c, 0ll), (long long)(16 + reach));
     return s;
 }
-// the same for a kernel whose threads walk TRT rows (K49: 8, a tile of CT_GROUPS * TRT rows): c, r0, and rem capped at 32
+// the same for a kernel whose threads walk TRT rows (K49, K50: 8, a tile of CT_GROUPS * TRT rows): c, r0, and rem capped at 32
 template <int TRT> __device__ __forceinline__ CtStrip ct_strip_rows(int tiles_c, int w) {
     CtStrip s;
     s.c = (long long)(blockIdx.x % tiles_c) * CT_COLS + (threadIdx.x & (CT_STRIPS - 1)) * 16;
@@ -116,7 +117,7 @@ template <int FIELDS, int BITS, int UPDATES> struct HotBins {
 
 // The end of every count kernel, by all WAVES * 64 threads of the workgroup: part holds the waves' partial sums [WAVES][k] in LDS (written
 // by plain stores or LDS atomics before the call; the barrier is in here); out[row + b] += the sum over the waves, b < k, one 64-bit vector
-// atomic per non-zero sum.  COPIES: how many partial tables part holds when that is not one per wave (K49: one that its waves share).
+// atomic per non-zero sum.  COPIES: how many partial tables part holds when that is not one per wave (K49, K50: one that its waves share).
 template <int WAVES, class T, int COPIES = WAVES>
 __device__ __forceinline__ void count_flush(const T* __restrict__ part, int k, unsigned long long* __restrict__ out, size_t row) {
     __syncthreads();
@@ -132,16 +133,25 @@ __device__ __forceinline__ void count_flush(const T* __restrict__ part, int k, u
 // The set-up of an entry over n planes of h x w pixels whose kernel(x, out, h, w, tiles_c, tail...) takes a tile of tile_r x tile_c pixels
 // of a plane without its `border` outermost rows and columns per workgroup, grid (row tiles x column tiles, n): the argument checks, the
 // table of n x row sums zeroed on the stream (a count kernel only adds), the launch.  The three names as in embed_launch (wsu_embed.h).
+// count_launch_slices: the same with `slices` workgroups per tile and plane (grid z; K50 cuts its tables into slices that a workgroup's LDS
+// holds); count_launch is the one-slice form that every other kernel takes.
 template <class... P, class... A>
-inline int count_launch(const char* who, const char* memset_name, const char* kernel_name, void (*kernel)(P...), int threads, size_t lds,
-                        const uint8_t* x, unsigned long long* out, size_t row, int n, int h, int w, int border, int tile_r, int tile_c,
-                        void* stream, A... tail) {
+inline int count_launch_slices(const char* who, const char* memset_name, const char* kernel_name, void (*kernel)(P...), int threads, size_t lds,
+                               const uint8_t* x, unsigned long long* out, size_t row, int n, int h, int w, int border, int tile_r, int tile_c,
+                               int slices, void* stream, A... tail) {
     WSU_REQUIRE(x && out, "%s: null pointer", who);
     WSU_REQUIRE(n >= 1 && n <= 65535 && h > 2 * border && w > 2 * border, "%s: bad shape n=%d h=%d w=%d", who, n, h, w);
     const long long tr = ((long long)h - 2 * border + tile_r - 1) / tile_r, tc = ((long long)w - 2 * border + tile_c - 1) / tile_c;
     WSU_REQUIRE(tr * tc <= 0x7fffffffll, "%s: image of %d x %d has too many tiles", who, h, w);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (hipMemsetAsync(out, 0, (size_t)n * row * sizeof(unsigned long long), s) != hipSuccess) return wsu_check_launch(memset_name);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(tr * tc), n), dim3(threads), lds, s, x, out, h, w, (int)tc, tail...);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(tr * tc), n, slices), dim3(threads), lds, s, x, out, h, w, (int)tc, tail...);
     return wsu_check_launch(kernel_name);
+}
+template <class... P, class... A>
+inline int count_launch(const char* who, const char* memset_name, const char* kernel_name, void (*kernel)(P...), int threads, size_t lds,
+                        const uint8_t* x, unsigned long long* out, size_t row, int n, int h, int w, int border, int tile_r, int tile_c,
+                        void* stream, A... tail) {
+    return count_launch_slices(who, memset_name, kernel_name, kernel, threads, lds, x, out, row, n, h, w, border, tile_r, tile_c, 1, stream,
+                               tail...);
 }

@@ -1360,6 +1360,34 @@ def srm_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.
     return _count_entry("srm_counts", x_u8, shape[1:], out=out)
 
 
+# The tables of K50 as data.  SRM_MINMAX_Q2: the q2 of its three classes.  SRM_MINMAX_SETS: per class its sets in order, name -> how far the
+# union of the members' taps reaches (up, down, left, right).  SRM_MINMAX_TABLES: the 118 tables in the order of the counts, (class, q2,
+# set, scan, a, b) with the table's total 2 max(H - a, 0) max(W - b, 0): for class; for q ascending; for set; for scan in (h, v).
+SRM_MINMAX_Q2 = {cls: SRM_Q2[cls] for cls in ("S1", "S2", "S3")}
+SRM_MINMAX_SETS = {
+    "S1": {"WE": (0, 0, 1, 1), "NS": (1, 1, 0, 0), "WENS": (1, 1, 1, 1), "WNE": (1, 0, 1, 1), "ESW": (0, 1, 1, 1), "SWN": (1, 1, 1, 0), "NES": (1, 1, 0, 1)},
+    "S2": {name: (1, 1, 1, 1) for name in ("hv", "hvdm", "hvd", "hvm", "hd", "hm", "vd", "vm")},
+    "S3": {"WE": (0, 0, 2, 2), "NS": (2, 2, 0, 0), "WENS": (2, 2, 2, 2), "WNE": (2, 1, 2, 2), "ESW": (1, 2, 2, 2), "SWN": (2, 2, 2, 1), "NES": (2, 2, 1, 2)}}
+SRM_MINMAX_TABLES = tuple((cls, q2, name, scan, u + dn + (3 if scan == "v" else 0), l + rt + (3 if scan == "h" else 0))
+                          for cls, steps in SRM_MINMAX_Q2.items() for q2 in steps for name, (u, dn, l, rt) in SRM_MINMAX_SETS[cls].items()
+                          for scan in "hv")
+
+
+def srm_minmax_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,118,625) int64: per image the co-occurrence counts of the min/max submodels of the spatial rich model on
+    the directional residuals of the first three orders, table by table as SRM_MINMAX_TABLES lists them: per run of four positions
+    along a row or down a column the minimum digits of a set of residuals at their bin and its maximum digits, negated, at theirs, over
+    every run whose taps all lie in the image (wsu_srm_minmax_counts, K50, which include/wsu.h defines; ws_unet_amd.srm.features_minmax
+    makes the features).  `out`: an int64 tensor of that shape to write into (the call zeroes it)."""
+    n = _u8_planes(x_u8)[0]
+    shape = (n, len(SRM_MINMAX_TABLES), SRM_BINS)
+    if out is not None and n:
+        _dev_check(out)
+        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
+            raise ValueError(f"srm_minmax_counts: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
+    return _count_entry("srm_minmax_counts", x_u8, shape[1:], out=out)
+
+
 # IJG luminance base table (the JPEG standard's Annex K.1), row-major by frequency [u][v]
 _IJG_LUMINANCE = np.array([
     [16, 11, 10, 16, 24, 40, 51, 61], [12, 12, 14, 19, 26, 58, 60, 55], [14, 13, 16, 24, 40, 57, 69, 56], [14, 17, 22, 29, 51, 87, 80, 62],

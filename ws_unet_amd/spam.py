@@ -95,6 +95,8 @@ class FLD:
     0.5 as the decision.  The default ridge 0.1 comes from one check on 64 x 64 crops of the five fixture covers (held-out AUC 0.925 at
     0.1, 0.811 at 1e-3 with full-payload LSBR twins); it is not tuned on any real data set."""
 
+    dual = False            # True (srm's larger feature sets): with fewer rows than features and ridge > 0, `fit` solves the n x n dual system
+
     def __init__(self, ridge: float = 0.1, order: int = 2, T: int = 3, normalise: str = "joint"):
         if not ridge >= 0:
             raise ValueError(f"ridge {ridge!r} must not be negative")
@@ -117,6 +119,17 @@ class FLD:
         d = X0.shape[1]
         mu0, mu1 = X0.mean(axis=0), X1.mean(axis=0)
         A0, A1 = X0 - mu0, X1 - mu1
+        if self.dual and len(X0) + len(X1) < d and self.ridge > 0:
+            # fewer rows than features: S = A^T A with A the centred rows over sqrt(n - 2), and by Woodbury
+            # (A^T A + lambda I)^-1 = (I - A^T (A A^T + lambda I)^-1 A) / lambda: an n x n system in place of the d x d one
+            A = np.concatenate([A0, A1]) / np.sqrt(len(X0) + len(X1) - 2.)
+            lam = self.ridge * float(np.einsum("ij,ij->", A, A)) / d             # trace(S) = ||A||_F^2
+            if not lam > 0:
+                raise ValueError("fit: the classes have no within-class variance")
+            delta = mu1 - mu0
+            self.w = (delta - A.T @ np.linalg.solve(A @ A.T + lam * np.eye(len(A)), A @ delta)) / lam
+            self.b = float(self.w @ (mu0 + mu1) / 2.)
+            return self
         S = (A0.T @ A0 + A1.T @ A1) / (len(X0) + len(X1) - 2)
         lam = self.ridge * np.trace(S) / d
         self.w = np.linalg.solve(S + lam * np.eye(d), mu1 - mu0)
