@@ -553,6 +553,18 @@ int wsu_srm_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h
  *      HIP call. */
 int wsu_srm_minmax_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
 
+/* ---- K52: the weighted co-occurrence sums of K49's tables, the integer half of the selection-channel-aware rich model (maxSRM: Denemark,
+ *      Sedighi, Holub, Cogranne, Fridrich, WIFS 2014; not part of the reference; the h and v scans of the linear submodels only, not the
+ *      oblique d2 scan of maxSRMd2 and not the min/max submodels; not compared with the authors' extractor).  x_u8, the residuals, the digit,
+ *      a run, its bin, the condition for a run to count and the order of the 44 tables are K49's, unchanged.  weights_u16: DEVICE uint16
+ *      (N,H,W), any plane of that shape (K51 makes the sender's change probabilities).  The position of a residual is the (r,c) of K49's
+ *      list (the pixel whose coefficient is written at X[r][c]; the centre of S3x3 and S5x5), whatever pixels it reads.  A counted run
+ *      whose four residuals sit at (r, c+k), scan h, or (r+k, c), scan v, k = 0..3, adds  max_k weights[r][c+k]  or  max_k weights[r+k][c]
+ *      to its bin instead of 1.  With weights all 1 the sums are K49's counts.  sums: DEVICE (N, 44, 625) uint64, zeroed on the stream by
+ *      this call.  Exact integers, the same bits on every run and in every batch.  n in 1..65535; every argument is checked before any
+ *      HIP call. */
+int wsu_srm_weighted_counts(const uint8_t* x_u8, const uint16_t* weights_u16, unsigned long long* sums, int n, int h, int w, void* stream);
+
 /* ---- K12-K14: HILL-cost weighted prediction error (wMAE) of src/filters/evaluate.py:79-115 `get_filter_residuals_cover` and
  *      src/predictor_error.py:19-76 `attack`.  Both reference callers take HILL from a library (conseal.hill._costmap.compute_cost,
  *      stegolab2.hill.compute_rho); here both are the textbook cost, the one pinned by results/prediction/filters.csv:
@@ -737,6 +749,12 @@ int wsu_embed_ternary(const uint8_t* cover, const double* rho, const double* lam
 int wsu_lsbm_threshold(double alpha, uint32_t* threshold);
 int wsu_embed_lsbm(const uint8_t* cover, const uint64_t* seeds, const uint32_t* thresholds, uint8_t* stego, long long* changes,
                    int n, int h, int w, void* stream);
+/* K51: the change probability of K38's sender per pixel, as a 16-bit fixed-point weight: with a, e+-, Z as above at lambda =
+ *      lambdas[image] (DEVICE float64 [N], given by the caller: nothing is solved here),  beta = (e+ + e-) / Z  and
+ *      weights[i] = floor(beta * 65536) in float64.  beta <= 2/3, so a weight is at most 43 690 and nothing is clipped; rho = +inf or
+ *      lambda = +inf gives 0; a beta below 2^-16 = 1.5e-5 gives 0.  weights_u16: DEVICE uint16 (N,H,W), the selection channel that K52
+ *      takes.  H * W < 2^32, N <= 65535; every argument is checked before any HIP call. */
+int wsu_change_weights(const uint8_t* x_u8, const double* rho, const double* lambdas, uint16_t* weights_u16, int n, int h, int w, void* stream);
 
 /* ---- K40-K42: binary syndrome-trellis codes (Filler, Judas, Fridrich, IEEE TIFS 6(3), 2011; not part of the reference): a message that is
  *      really carried, embedded with near-minimal additive cost and read back.  Planes, limits and seeds as in K23, but H * W < 2^31.

@@ -110,6 +110,7 @@ SIGNATURES = {
     "wsu_spam_counts": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "wsu_srm_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_srm_minmax_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "wsu_srm_weighted_counts": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_lsb_delta_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     "wsu_filter3x3_valid_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_hill_cost": (c_int, [_P, _P, c_float, c_int, c_int, c_int, _P]),
@@ -138,6 +139,7 @@ SIGNATURES = {
     "wsu_ternary_entropy_workspace_bytes": (c_size_t, [c_int]),
     "wsu_ternary_entropy": (c_int, [_P, _P, _P, c_int, _P, _P, c_size_t, c_int, c_int, c_int, _P]),
     "wsu_embed_ternary": (c_int, [_P] * 6 + [c_int, c_int, c_int, _P]),
+    "wsu_change_weights": (c_int, [_P] * 4 + [c_int, c_int, c_int, _P]),
     "wsu_lsbm_threshold": (c_int, [c_double, _P]),
     "wsu_embed_lsbm": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_philox_words": (c_int, [_P, _P, c_int, c_int, c_int, _P]),

@@ -140,9 +140,48 @@ __global__ __attribute__((amdgpu_num_sgpr(100))) __launch_bounds__(256) void emb
     embed_span(rule, cover + (size_t)nn * hw, stego + (size_t)nn * hw, hw, changes + nn);
 }
 
+// ---- K51: the sender's change probability as a 16-bit weight ---------------------------------------------------------------------------------
+// q = floor((e+ + e-) / Z * 2^16) with K38's a, e+-, Z: beta <= 2/3, so q <= 43 690.  A thread takes four pixels and stores them with one
+// 8-byte store where the plane allows it (pixel index and address both multiples of 4), else pixel by pixel.
+__device__ __forceinline__ uint32_t change_weight(uint8_t x, double lam, double c) {
+    const double a = lam * c;
+    double ep, em;
+    ternary_exp(x, a, ep, em);
+    const double z = (1.0 + ep) + em;
+    const double beta = (ep + em) / z;
+    return (uint32_t)(beta * 65536.0);                                       // floor: not negative
+}
+
+__global__ __launch_bounds__(256) void change_weights_kernel(const uint8_t* __restrict__ x, const double* __restrict__ rho,
+                                                             const double* __restrict__ lambdas, uint16_t* __restrict__ weights, long long hw) {
+    const int nn = blockIdx.y;
+    const double lam = lambdas[nn];
+    const uint8_t* img = x + (size_t)nn * hw;
+    const double* cimg = rho + (size_t)nn * hw;
+    uint16_t* out = weights + (size_t)nn * hw;
+    const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 + 4 <= hw && (reinterpret_cast<uintptr_t>(out + i0) & 7) == 0) {
+        uint32_t q[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[e] = change_weight(img[i0 + e], lam, cimg[i0 + e]);
+        *reinterpret_cast<uint2*>(out + i0) = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
+    } else {
+        for (long long i = i0; i < min(i0 + 4, hw); ++i) out[i] = (uint16_t)change_weight(img[i], lam, cimg[i]);
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int wsu_change_weights(const uint8_t* x_u8, const double* rho, const double* lambdas, uint16_t* weights_u16, int n, int h, int w, void* stream) {
+    WSU_REQUIRE(x_u8 && rho && lambdas && weights_u16, "change_weights: null pointer");
+    WSU_REQUIRE_SHAPE("change_weights", WSU_COUNTER_PIXELS, "counters");
+    const long long hw = (long long)h * w;
+    hipLaunchKernelGGL(change_weights_kernel, dim3((unsigned)((hw + 1023) / 1024), n), dim3(256), 0, static_cast<hipStream_t>(stream), x_u8,
+                       rho, lambdas, weights_u16, hw);
+    return wsu_check_launch("change_weights_kernel");
+}
 
 size_t wsu_ternary_entropy_workspace_bytes(int n) { return n > 0 ? (size_t)n * TE_PARTS * TE_MAXL * sizeof(double) : 0; }
 

@@ -1360,6 +1360,24 @@ def srm_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.
     return _count_entry("srm_counts", x_u8, shape[1:], out=out)
 
 
+def srm_weighted_counts(x_u8: torch.Tensor, weights: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8, weights: (N,H,W) uint16 -> (N,44,625) int64: the tables of srm_counts with every counted run adding the
+    largest of the weights at its four residual positions instead of 1 (wsu_srm_weighted_counts, K52, which include/wsu.h defines: the
+    integer half of the selection-channel-aware features of ws_unet_amd.srm; change_weights makes a sender's weights).  Weights all 1
+    give srm_counts.  `out`: an int64 tensor of that shape to write into (the call zeroes it)."""
+    n = _u8_planes(x_u8)[0]
+    _dev_check(weights)
+    if weights.dtype != torch.uint16 or weights.shape != x_u8.shape or weights.device != x_u8.device:
+        raise ValueError(f"srm_weighted_counts: weights must be uint16 of shape {tuple(x_u8.shape)} on {x_u8.device}, got "
+                         f"{tuple(weights.shape)} {weights.dtype} on {weights.device}")
+    shape = (n, len(SRM_TABLES), SRM_BINS)
+    if out is not None and n:
+        _dev_check(out)
+        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
+            raise ValueError(f"srm_weighted_counts: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
+    return _count_entry("srm_weighted_counts", x_u8, shape[1:], weights.data_ptr(), out=out)
+
+
 # The tables of K50 as data.  SRM_MINMAX_Q2: the q2 of its three classes.  SRM_MINMAX_SETS: per class its sets in order, name -> how far the
 # union of the members' taps reaches (up, down, left, right).  SRM_MINMAX_TABLES: the 118 tables in the order of the counts, (class, q2,
 # set, scan, a, b) with the table's total 2 max(H - a, 0) max(W - b, 0): for class; for q ascending; for set; for scan in (h, v).
@@ -1718,6 +1736,21 @@ def embed_ternary(cover_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tens
     n = _f64_planes(who, cover_u8, rho)[0]
     return _embed_entry(who, cover_u8, 10, rho.data_ptr(), _vector(who, "lambdas", lambdas, n, torch.float64),
                         _vector(who, "seeds", seeds, n, torch.int64))
+
+
+def change_weights(x_u8: torch.Tensor, rho: torch.Tensor, lambdas: torch.Tensor) -> torch.Tensor:
+    """The change probability of embed_ternary's sender per pixel as a 16-bit weight (K51): floor((p+ + p-) * 65536), at most 43 690;
+    0 where rho or lambda is +inf.  rho: (N,H,W) float64; lambdas: (N) float64, given by the caller (ternary_lambda finds a payload's)
+    -> (N,H,W) uint16, the weights of srm_weighted_counts."""
+    who = "change_weights"
+    n, h, w = _f64_planes(who, x_u8, rho)
+    if n == 0:
+        raise ValueError(f"{who}: no images")
+    lam = _vector(who, "lambdas", lambdas, n, torch.float64)
+    weights = torch.empty((n, h, w), dtype=torch.uint16, device=x_u8.device)
+    check(_launch(who, {"bytes": float(n * h * w * 11)}, lambda: _lib.load().wsu_change_weights(
+        x_u8.data_ptr(), rho.data_ptr(), lam, weights.data_ptr(), n, h, w, _stream())), "wsu_change_weights")
+    return weights
 
 
 def lsbm_threshold(alpha: float) -> int:
