@@ -565,6 +565,27 @@ int wsu_srm_minmax_counts(const uint8_t* x_u8, unsigned long long* counts, int n
  *      HIP call. */
 int wsu_srm_weighted_counts(const uint8_t* x_u8, const uint16_t* weights_u16, unsigned long long* sums, int n, int h, int w, void* stream);
 
+/* ---- K53: the bootstrap-weighted scatter matrices of the base learners of the FLD ensemble (Kodovsky, Fridrich, Holub, "Ensemble
+ *      classifiers for steganalysis of digital media", IEEE TIFS 7(2), 2012; not part of the reference; ws_unet_amd.ensemble fits it).
+ *      zt: DEVICE (d, n_rows) float64, FEATURE-major (a feature is one contiguous row), finite.  idx: DEVICE (L, d_sub) int32, every entry
+ *      in [0, d): THE CALLER CHECKS THAT, this entry does not read idx on the host (ops.subspace_gram checks it with one reduction on
+ *      the device); any order, repeats allowed.  weights: DEVICE (L, n_rows) int32 >= 0, the bootstrap multiplicity of row i in learner l.
+ *        G[l][a][b] = sum_i weights[l][i] * zt[idx[l][a]][i] * zt[idx[l][b]][i]         G: DEVICE (L, d_sub, d_sub) float64
+ *      Products and sums are float64 on v_mfma_f64_16x16x4_f64.  The weight is multiplied into the a-operand where it is staged, so a
+ *      term is fl(fl(w z_a) z_b + partial sum): at most one rounding more than a plain product sum, and
+ *      |G - exact| <= (n_rows + 2) 2^-53 sum_i w_i |z_a z_b|.  Only entries with a >= b are computed; each is written at [a][b] and at
+ *      [b][a], so G[l] is symmetric bit for bit.  An entry is accumulated in one accumulator over i ascending in steps of 4: its bits
+ *      depend on n_rows and the data alone, not on L, on the other learners of the launch or on how a caller splits L.  Tails of n_rows
+ *      and d_sub are zero-filled operands: nothing is read outside zt's rows.  Every entry of G is written; nothing needs zeroing.
+ *      L in 1..65535, d_sub in 1..2^20; null pointers and non-positive sizes return -1 before any HIP call. */
+int wsu_subspace_gram_f64(const double* zt, const int32_t* idx, const int32_t* weights, double* G, int n_rows, int d, int d_sub, int L,
+                          void* stream);
+
+/* A register-only loop of v_mfma_f64_16x16x4_f64 (4 independent accumulators per wave, 4 waves per workgroup, `iters` x 4 instructions per
+ * wave, no memory access in the loop): the measured ceiling that tools/bench_ensemble.py quotes K53's rate against, since no FP64
+ * matrix peak is on record.  sink: DEVICE (blocks * 256) float64, written once.  2048 flops per instruction and wave. */
+int wsu_mfma_f64_loop(double* sink, int blocks, int iters, void* stream);
+
 /* ---- K12-K14: HILL-cost weighted prediction error (wMAE) of src/filters/evaluate.py:79-115 `get_filter_residuals_cover` and
  *      src/predictor_error.py:19-76 `attack`.  Both reference callers take HILL from a library (conseal.hill._costmap.compute_cost,
  *      stegolab2.hill.compute_rho); here both are the textbook cost, the one pinned by results/prediction/filters.csv:

@@ -111,6 +111,8 @@ SIGNATURES = {
     "wsu_srm_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_srm_minmax_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_srm_weighted_counts": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "wsu_subspace_gram_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "wsu_mfma_f64_loop": (c_int, [_P, c_int, c_int, _P]),
     "wsu_lsb_delta_unit_f32": (c_int, [_P, _P, c_size_t, _P]),
     "wsu_filter3x3_valid_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_hill_cost": (c_int, [_P, _P, c_float, c_int, c_int, c_int, _P]),

@@ -1378,6 +1378,55 @@ def srm_weighted_counts(x_u8: torch.Tensor, weights: torch.Tensor, out: Optional
     return _count_entry("srm_weighted_counts", x_u8, shape[1:], weights.data_ptr(), out=out)
 
 
+SUBSPACE_GRAM_MAX_BYTES = 1 << 30         # default output budget of one K53 launch: memory, not a tuned number
+SUBSPACE_GRAM_MAX_LEARNERS = 65535        # learners one K53 launch takes (its grid's second dimension)
+SUBSPACE_GRAM_TILE, SUBSPACE_GRAM_KC, SUBSPACE_GRAM_MFMA = 64, 32, 16     # K53's geometry (csrc/ensemble.hip: SG_TILE, SG_KC, the MFMA tile), for tests
+
+
+def subspace_gram(zt: torch.Tensor, idx: torch.Tensor, weights: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  max_bytes: int = SUBSPACE_GRAM_MAX_BYTES) -> torch.Tensor:
+    """zt: (d, n_rows) float64, contiguous, feature-major; idx: (L, d_sub) int32, every entry in [0, d); weights: (L, n_rows) int32 >= 0
+    -> G (L, d_sub, d_sub) float64, G[l, a, b] = sum_i weights[l, i] zt[idx[l, a], i] zt[idx[l, b], i]: the bootstrap-weighted scatter of
+    every base learner of ws_unet_amd.ensemble in float64 on the matrix pipe (wsu_subspace_gram_f64, K53, which include/wsu.h defines).
+    G[l] is symmetric bit for bit.  L is split into launches whose output stays under `max_bytes` (one learner at least); a learner's
+    bits do not depend on the split.  `out`: a float64 tensor of that shape to write into.  ValueError, before anything is launched, for
+    a wrong dtype, shape, device, a tensor that is not contiguous, a negative weight or an index outside [0, d) (one reduction each on
+    the device).  The input must be finite; the callers check that once."""
+    for name, t, dtype, dim in (("zt", zt, torch.float64, 2), ("idx", idx, torch.int32, 2), ("weights", weights, torch.int32, 2)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dim:
+            raise ValueError(f"subspace_gram: {name} must be a {dim}-d {dtype} tensor, got "
+                             f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if not t.is_cuda or t.device != zt.device:
+            raise ValueError(f"subspace_gram: {name} must be on the GPU, on zt's device: got {t.device} (no CPU fallback exists)")
+        if not t.is_contiguous():
+            raise ValueError(f"subspace_gram: {name} must be contiguous" + (" (feature-major: pass Z.T.contiguous())" if name == "zt" else ""))
+    (d, n_rows), (L, d_sub) = zt.shape, idx.shape
+    if min(d, n_rows, L, d_sub) < 1 or tuple(weights.shape) != (L, n_rows):
+        raise ValueError(f"subspace_gram: zt {tuple(zt.shape)}, idx {tuple(idx.shape)}, weights {tuple(weights.shape)}: expected (d, n_rows), "
+                         f"(L, d_sub), (L, n_rows), all sizes positive")
+    if d_sub > 1 << 20:
+        raise ValueError(f"subspace_gram: d_sub={d_sub} above 2^20")
+    if isinstance(max_bytes, bool) or int(max_bytes) != max_bytes or max_bytes < 1:
+        raise ValueError(f"subspace_gram: max_bytes={max_bytes!r} must be a positive integer")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (L, d_sub, d_sub)
+                            or out.device != zt.device or not out.is_contiguous()):
+        raise ValueError(f"subspace_gram: out must be a contiguous float64 tensor of shape {(L, d_sub, d_sub)} on {zt.device}")
+    lo, hi, wmin = (int(v) for v in torch.stack([idx.min(), idx.max(), weights.min()]).tolist())
+    if lo < 0 or hi >= d:
+        raise ValueError(f"subspace_gram: idx holds {lo if lo < 0 else hi}, outside [0, {d}); nothing was launched")
+    if wmin < 0:
+        raise ValueError(f"subspace_gram: weights hold {wmin}: multiplicities must not be negative")
+    G = torch.empty((L, d_sub, d_sub), dtype=torch.float64, device=zt.device) if out is None else out
+    per = max(1, min(SUBSPACE_GRAM_MAX_LEARNERS, int(max_bytes) // (8 * d_sub * d_sub)))
+    fn = _lib.load().wsu_subspace_gram_f64
+    for l0 in range(0, L, per):
+        m = min(per, L - l0)
+        check(_launch("subspace_gram", {"flops": float(m) * n_rows * d_sub * (d_sub + 1)}, lambda: fn(
+            zt.data_ptr(), idx[l0:l0 + m].data_ptr(), weights[l0:l0 + m].data_ptr(), G[l0:l0 + m].data_ptr(), n_rows, d, d_sub, m,
+            _stream())), "wsu_subspace_gram_f64")
+    return G
+
+
 # The tables of K50 as data.  SRM_MINMAX_Q2: the q2 of its three classes.  SRM_MINMAX_SETS: per class its sets in order, name -> how far the
 # union of the members' taps reaches (up, down, left, right).  SRM_MINMAX_TABLES: the 118 tables in the order of the counts, (class, q2,
 # set, scan, a, b) with the table's total 2 max(H - a, 0) max(W - b, 0): for class; for q ascending; for set; for scan in (h, v).

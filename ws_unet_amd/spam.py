@@ -18,7 +18,9 @@ clipped differences of neighbouring pixels along four steps), the host does a fe
     last difference ('transition', the paper's conditional probability; 0 where that total is 0), and averages the tables of the four
     axis steps into the first half of the vector and those of the four diagonal steps into the second: 2 B^(order+1) numbers, 686 at
     order 2, T 3 (SPAM-686), 162 at order 1, T 4;
-  * `FLD` is Fisher's discriminant with a ridge on the pooled within-class covariance, one float64 solve of the feature dimension.
+  * `FLD` is Fisher's discriminant with a ridge on the pooled within-class covariance, one float64 solve of the feature dimension;
+  * `fit --classifier ensemble --learners L --d-sub D [D ...] --seed S` trains the FLD ensemble of ws_unet_amd.ensemble (`Ensemble`, with
+    the tags order, T, normalise) in its place; `load_model` reads either kind of file.  The default stays the FLD.
 
 Not checked: the authors' MATLAB extractor is not at hand.  Clipping differences beyond +-T into the border bins, normalising each
 direction's table by its own total and offering 'transition' as the alternative is the convention of the common SPAM-686 code as
@@ -34,10 +36,11 @@ import typing
 import numpy as np
 import torch
 
-from . import fabrika
+from . import ensemble, fabrika
 
 NORMALISE = ("joint", "transition")
 SIMULATED = ("LSBR", "HILLR", "LSBM", "HILL")                       # the stego methods `simulate=True` makes on the device
+CLASSIFIERS = ("fld", "ensemble")
 CSV_COLUMNS = ["name", "height", "width", "output", "prediction", "stego_method", "alpha"]
 
 
@@ -157,12 +160,42 @@ class FLD:
     @classmethod
     def load(cls, path) -> "FLD":
         with np.load(path, allow_pickle=False) as z:
+            ensemble.refuse_ensemble(z, path, "spam")
             m = cls(float(z["ridge"]), int(z["order"]), int(z["T"]), str(z["normalise"]))
             m.w, m.b = np.array(z["w"], dtype=np.float64), float(z["b"])
             m.stego_methods, m.alphas = [str(s) for s in z["stego_methods"]], [float(a) for a in z["alphas"]]
         if m.w.shape != (2 * bins(m.order, m.T),):
             raise ValueError(f"{path}: {m.w.shape[0]} weights for order {m.order}, T {m.T}")
         return m
+
+
+class Ensemble(ensemble.Ensemble):
+    """ensemble.Ensemble (its fit, votes, output) on the features of this module; the file carries FLD's tags order, T, normalise."""
+
+    def __init__(self, learners: int = 51, d_sub=None, ridge: float = 0.1, seed: int = 0, order: int = 2, T: int = 3, normalise: str = "joint"):
+        super().__init__(learners, d_sub, ridge, seed)
+        if normalise not in NORMALISE:
+            raise ValueError(f"unknown normalise {normalise!r}; choose from {NORMALISE}")
+        bins(order, T)
+        self.order, self.T, self.normalise = int(order), int(T), normalise
+
+    def _tags(self) -> dict:
+        return dict(order=np.int64(self.order), T=np.int64(self.T), normalise=np.array(self.normalise))
+
+    @classmethod
+    def load(cls, path) -> "Ensemble":
+        with np.load(path, allow_pickle=False) as z:
+            cls._require(z, path)
+            m = cls(int(z["learners"]), [int(v) for v in z["d_sub_candidates"]], float(z["ridge"]), int(z["seed"]), int(z["order"]), int(z["T"]),
+                    str(z["normalise"]))._read(z, path)
+        if m.mean.shape != (2 * bins(m.order, m.T),):
+            raise ValueError(f"{path}: {m.mean.shape[0]} features for order {m.order}, T {m.T}")
+        return m
+
+
+def load_model(path):
+    """The model of `fit` at `path`, an FLD or an Ensemble as the file's `classifier` entry says (an FLD file has none)."""
+    return Ensemble.load(path) if ensemble.is_ensemble_file(path) else FLD.load(path)
 
 
 # ---- features of a data set ----------------------------------------------------------------------------------------------------------
@@ -253,17 +286,34 @@ def _sets(a):
     return [(m, al) for m in a.stego_methods for al in a.alphas]
 
 
-def fit(data_dir, stego_methods, alphas, *, split=None, simulate=False, order=2, T=3, normalise="joint", ridge=0.1, **kw) -> FLD:
-    """An FLD on the covers of `data_dir` against its stegos of every listed (method, alpha), pooled into one class."""
+def check_classifier(classifier: str, d_sub) -> str:
+    """'fld' or 'ensemble'; ValueError for another name and for an ensemble without d_sub"""
+    if classifier not in CLASSIFIERS:
+        raise ValueError(f"unknown classifier {classifier!r}; choose from {CLASSIFIERS}")
+    if classifier == "ensemble" and not d_sub:
+        raise ValueError("classifier 'ensemble' needs d_sub (--d-sub D [D ...]): the features of a base learner, or candidates to choose from")
+    return classifier
+
+
+def fit(data_dir, stego_methods, alphas, *, split=None, simulate=False, order=2, T=3, normalise="joint", ridge=0.1, classifier="fld",
+        learners=51, d_sub=None, seed=0, **kw):
+    """An FLD on the covers of `data_dir` against its stegos of every listed (method, alpha), pooled into one class.  classifier='ensemble':
+    an Ensemble(learners, d_sub, ridge, seed) instead, whose bootstrap keeps the rows of one file stem (a cover and its twins) together."""
+    check_classifier(classifier, d_sub)
     opts = dict(split=split, order=order, T=T, normalise=normalise, **kw)
-    _, F0 = extract(data_dir, **opts)
-    F1 = np.concatenate([extract(data_dir, m, al, simulate=simulate, **opts)[1] for m in stego_methods for al in alphas])
-    model = FLD(ridge, order, T, normalise).fit(F0, F1)
+    rows0, F0 = extract(data_dir, **opts)
+    parts = [extract(data_dir, m, al, simulate=simulate, **opts) for m in stego_methods for al in alphas]
+    F1 = np.concatenate([p[1] for p in parts])
+    if classifier == "ensemble":
+        groups = ensemble.stem_groups(rows0["name"], np.concatenate([p[0]["name"].to_numpy(str) for p in parts]))
+        model = Ensemble(learners, d_sub, ridge, seed, order, T, normalise).fit(F0, F1, *groups)
+    else:
+        model = FLD(ridge, order, T, normalise).fit(F0, F1)
     model.stego_methods, model.alphas = [str(m) for m in stego_methods], [float(al) for al in alphas]
     return model
 
 
-def score(data_dir, model: FLD, stego_methods, alphas, *, split=None, simulate=False, **kw):
+def score(data_dir, model, stego_methods, alphas, *, split=None, simulate=False, **kw):
     """The frame of results/detection/b0.csv: the covers (empty stego_method and alpha), then the stegos method by method and alpha by
     alpha; output = model.output of the image's features, prediction = output > 0.5."""
     import pandas as pd
@@ -277,6 +327,23 @@ def score(data_dir, model: FLD, stego_methods, alphas, *, split=None, simulate=F
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------------------------
+
+def add_classifier_options(p) -> None:
+    """the options of `fit` that choose and shape the classifier (shared with ws_unet_amd.srm)"""
+    p.add_argument("--classifier", choices=CLASSIFIERS, default="fld",
+                   help="fld: one ridge-regularised Fisher discriminant (the default); ensemble: the FLD ensemble of ws_unet_amd.ensemble")
+    p.add_argument("--learners", type=int, default=51, help="--classifier ensemble: base learners (odd, so that a vote cannot tie)")
+    p.add_argument("--d-sub", type=int, nargs="+", default=None,
+                   help="--classifier ensemble (required): features per base learner; several values: the one with the least out-of-bag error")
+    p.add_argument("--seed", type=int, default=0, help="--classifier ensemble: the seed of its draws")
+
+
+def classifier_keywords(ap, a) -> dict:
+    """the keywords of `fit` from the parsed options; the parser's error when `ensemble` comes without --d-sub"""
+    if a.classifier == "ensemble" and not a.d_sub:
+        ap.error("--classifier ensemble requires --d-sub D [D ...]")
+    return dict(classifier=a.classifier, learners=a.learners, d_sub=a.d_sub, seed=a.seed) if a.classifier == "ensemble" else {}
+
 
 def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(description="SPAM features and a Fisher linear discriminant: a detector trained in the package, whose "
@@ -302,12 +369,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     p = sub.add_parser("fit", help="train on the covers against every listed (method, alpha), pooled; writes the model .npz")
     common(p, True)
     p.add_argument("--ridge", type=float, default=0.1)
+    add_classifier_options(p)
     p = sub.add_parser("score", help="write detector scores in the schema of results/detection/b0.csv")
     common(p, False)
     p.add_argument("--model", required=True, help="the .npz of `fit`")
     p = sub.add_parser("features", help="write the raw feature matrices as an .npz")
     common(p, True)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    a.classifier_kw = classifier_keywords(ap, a) if a.command == "fit" else {}
+    return a
 
 
 def main(argv=None) -> None:
@@ -315,10 +385,10 @@ def main(argv=None) -> None:
     logging.basicConfig(level=logging.INFO)
     run = dict(split=a.split, simulate=a.simulate, stream=a.stream, batch_size=a.batch_size, progress_on=a.progress)
     if a.command == "fit":
-        model = fit(a.data, a.stego_methods, a.alphas, order=a.order, T=a.T, normalise=a.normalise, ridge=a.ridge, **run)
+        model = fit(a.data, a.stego_methods, a.alphas, order=a.order, T=a.T, normalise=a.normalise, ridge=a.ridge, **a.classifier_kw, **run)
         model.save(a.out)
     elif a.command == "score":
-        score(a.data, FLD.load(a.model), a.stego_methods, a.alphas, **run).to_csv(a.out, index=False)
+        score(a.data, load_model(a.model), a.stego_methods, a.alphas, **run).to_csv(a.out, index=False)
     else:
         opts = dict(order=a.order, T=a.T, normalise=a.normalise, **run)
         rows, F = extract(a.data, **{**opts, "simulate": False})
