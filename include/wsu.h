@@ -529,8 +529,8 @@ int wsu_srm_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h
 
 /* ---- K50: the co-occurrence counts of the min/max submodels of the spatial rich model built on the directional first-, second- and
  *      third-order residuals (the paper's minmax22h/v, minmax24, minmax34h/v of the 1st and 3rd order and minmax21, 41, 32, 24h/v of the
- *      2nd; stated as remembered, not compared with the authors' extractor; NOT built: the 1st/3rd-order submodels that need diagonal
- *      residuals (minmax41, 34, 48h/v, 54), the EDGE3x3 and EDGE5x5 classes).  x_u8, the digit d(R, q2), a run (four digits at columns
+ *      2nd; stated as remembered, not compared with the authors' extractor; the other 1st/3rd-order submodels are K54's and the EDGE3x3 and
+ *      EDGE5x5 classes K55's; by the paper's naming rule the set WENS below is its minmax41 and its minmax24 is K54's).  x_u8, the digit d(R, q2), a run (four digits at columns
  *      c..c+3, scan h, or rows r..r+3, scan v) and its bin are K49's.  The directional residuals at a pixel (r,c):
  *        S1  q2 = 2, 4       E = X[r][c+1] - X[r][c]   W = X[r][c-1] - X[r][c]   S = X[r+1][c] - X[r][c]   N = X[r-1][c] - X[r][c]
  *        S2  q2 = 4, 6, 8    h = X[r][c-1] - 2 X[r][c] + X[r][c+1]               v = X[r-1][c] - 2 X[r][c] + X[r+1][c]
@@ -552,6 +552,43 @@ int wsu_srm_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h
  *      Exact integers, the same bits on every run, independent of the batch split.  n in 1..65535; every argument is checked before any
  *      HIP call. */
 int wsu_srm_minmax_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
+
+/* ---- K54: the co-occurrence counts of the remaining first- and third-order min/max submodels of the spatial rich model, over "fans" of
+ *      the eight directional residuals (stated as remembered, not compared with the authors' extractor; by the rich model's rule
+ *      minmax<number of residuals><symmetry index> the sets below are its minmax24, 34, 48h/v and 54, and K50's set WENS is its minmax41:
+ *      DESIGN.md 4-srmfull has the mapping).  x_u8, the digit d(R, q2), lo / hi, a run, its bin, the two updates per run (the lo digits at
+ *      their bin, the negated hi digits at theirs) and the condition for a run to count are K50's.  The directions counter-clockwise and
+ *      their steps d = (dr, dc):  E (0,1)  NE (-1,1)  N (-1,0)  NW (-1,-1)  W (0,-1)  SW (1,-1)  S (1,0)  SE (1,1);  the residual of a
+ *      direction at the pixel p:
+ *        S1  q2 = 2, 4       X[p+d] - X[p]
+ *        S3  q2 = 6, 9, 12   X[p-d] - 3 X[p] + 3 X[p+d] - X[p+2d]                 (E, W, S, N are K50's)
+ *      The 20 sets in order, named by their members:
+ *        pairs (perpendicular)                    E+N  N+W  W+S  S+E
+ *        3-fans centred on a diagonal             E+NE+N  N+NW+W  W+SW+S  S+SE+E
+ *        4-fans with N or S and both neighbours   E+NE+N+NW  NE+N+NW+W  W+SW+S+SE  SW+S+SE+E          ("vertical")
+ *        4-fans with E or W and both neighbours   N+NW+W+SW  NW+W+SW+S  S+SE+E+NE  SE+E+NE+N          ("horizontal")
+ *        5-fans centred on a diagonal             SE+E+NE+N+NW  NE+N+NW+W+SW  NW+W+SW+S+SE  SW+S+SE+E+NE
+ *      A first-order residual reaches 1 pixel along its direction, a third-order one 2 along it and 1 against it; with (u, dn, l, rt) the
+ *      largest reach of a set's members up, down, left and right, a scan-h table sums to 2 max(H - u - dn, 0) max(W - l - rt - 3, 0) and a
+ *      scan-v table to 2 max(H - u - dn - 3, 0) max(W - l - rt, 0).  The 200 tables in order: for (class, q2) in S1 2, S1 4, S3 6, S3 9,
+ *      S3 12; for set as listed; for scan in (h, v).  counts: DEVICE (N, 200, 625) uint64, zeroed on the stream by this call; an image too
+ *      small for a table leaves it zero.  Exact integers, the same bits on every run, independent of the batch split.  n in 1..65535;
+ *      every argument is checked before any HIP call. */
+int wsu_srm_fan_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
+
+/* ---- K55: the co-occurrence counts of the EDGE3x3 and EDGE5x5 classes of the spatial rich model (stated as remembered, not compared with
+ *      the authors' extractor).  Everything but the residuals and the sets is K50's.  Four residuals per class at a pixel (r,c):
+ *        E3  q2 = 8, 12, 16     U = -X[r-1][c-1] + 2 X[r-1][c] - X[r-1][c+1] + 2 X[r][c-1] - 4 X[r][c] + 2 X[r][c+1]: the top two rows of
+ *                               K49's 3x3 kernel with the centre on its -4
+ *        E5  q2 = 24, 36, 48    U = the top three rows of K49's 5x5 kernel with the centre on its -12 (rows r-2 .. r, columns c-2 .. c+2)
+ *        D = U flipped top to bottom, L = U transposed, R = L mirrored left to right.
+ *      The eleven sets in order: U, D, L, R, UL, UR, DL, DR, UD, LR, UDLR.  A singleton has lo = hi = its digit and takes the same two
+ *      updates: its table is the residual's plain co-occurrence table plus the same with every digit negated.  With k = 1 (E3) or 2 (E5)
+ *      the reach (u, dn, l, rt) is U (k,0,k,k), D (0,k,k,k), L (k,k,k,0), R (k,k,0,k) and (k,k,k,k) for every other set; the sums are K54's.
+ *      The 132 tables in order: for (class, q2) in E3 8, 12, 16, E5 24, 36, 48; for set as listed; for scan in (h, v).  counts: DEVICE
+ *      (N, 132, 625) uint64, zeroed on the stream by this call.  Exact integers, the same bits on every run, independent of the batch
+ *      split.  n in 1..65535; every argument is checked before any HIP call. */
+int wsu_srm_edge_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
 
 /* ---- K52: the weighted co-occurrence sums of K49's tables, the integer half of the selection-channel-aware rich model (maxSRM: Denemark,
  *      Sedighi, Holub, Cogranne, Fridrich, WIFS 2014; not part of the reference; the h and v scans of the linear submodels only, not the

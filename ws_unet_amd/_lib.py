@@ -110,6 +110,8 @@ SIGNATURES = {
     "wsu_spam_counts": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "wsu_srm_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_srm_minmax_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "wsu_srm_fan_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "wsu_srm_edge_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_srm_weighted_counts": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_subspace_gram_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "wsu_mfma_f64_loop": (c_int, [_P, c_int, c_int, _P]),

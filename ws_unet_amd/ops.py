@@ -1455,6 +1455,65 @@ def srm_minmax_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) ->
     return _count_entry("srm_minmax_counts", x_u8, shape[1:], out=out)
 
 
+def _set_tables(q2, sets):
+    """the tables of a min/max count kernel in the order of its counts, (class, q2, set, scan, a, b) with the table's total
+    2 max(H - a, 0) max(W - b, 0): for class; for q2 ascending; for set; for scan in (h, v)"""
+    return tuple((cls, q, name, scan, u + dn + (3 if scan == "v" else 0), l + rt + (3 if scan == "h" else 0))
+                 for cls, steps in q2.items() for q in steps for name, (u, dn, l, rt) in sets[cls].items() for scan in "hv")
+
+
+def _fan_sets(along, against):
+    """name -> (up, down, left, right) of the 20 sets of K54, whose member residuals reach `along` pixels along their direction and
+    `against` against it"""
+    step = {"E": (0, 1), "NE": (-1, 1), "N": (-1, 0), "NW": (-1, -1), "W": (0, -1), "SW": (1, -1), "S": (1, 0), "SE": (1, 1)}
+
+    def side(members, axis, sign):
+        return max(along if step[m][axis] * sign > 0 else against if step[m][axis] * sign < 0 else 0 for m in members)
+    return {name: (side(m, 0, -1), side(m, 0, 1), side(m, 1, -1), side(m, 1, 1)) for name in SRM_FAN_SET_NAMES for m in [name.split("+")]}
+
+
+# The tables of K54 as data, as K50's above.  SRM_FAN_SET_NAMES: the 20 sets in order, named by their members: the perpendicular pairs, the
+# 3-fans, the "vertical" and the "horizontal" 4-fans, the 5-fans.  SRM_FAN_TABLES: the 200 tables.
+SRM_FAN_Q2 = {cls: SRM_Q2[cls] for cls in ("S1", "S3")}
+SRM_FAN_SET_NAMES = ("E+N", "N+W", "W+S", "S+E", "E+NE+N", "N+NW+W", "W+SW+S", "S+SE+E",
+                     "E+NE+N+NW", "NE+N+NW+W", "W+SW+S+SE", "SW+S+SE+E", "N+NW+W+SW", "NW+W+SW+S", "S+SE+E+NE", "SE+E+NE+N",
+                     "SE+E+NE+N+NW", "NE+N+NW+W+SW", "NW+W+SW+S+SE", "SW+S+SE+E+NE")
+SRM_FAN_SETS = {"S1": _fan_sets(1, 0), "S3": _fan_sets(2, 1)}
+SRM_FAN_TABLES = _set_tables(SRM_FAN_Q2, SRM_FAN_SETS)
+# The tables of K55: the classes E3 and E5 at the steps of S3x3 and S5x5, their eleven sets with the reach k = 1 or 2, the 132 tables.
+SRM_EDGE_Q2 = {"E3": SRM_Q2["S3x3"], "E5": SRM_Q2["S5x5"]}
+SRM_EDGE_SETS = {cls: {"U": (k, 0, k, k), "D": (0, k, k, k), "L": (k, k, k, 0), "R": (k, k, 0, k),
+                       **{name: (k, k, k, k) for name in ("UL", "UR", "DL", "DR", "UD", "LR", "UDLR")}} for cls, k in (("E3", 1), ("E5", 2))}
+SRM_EDGE_TABLES = _set_tables(SRM_EDGE_Q2, SRM_EDGE_SETS)
+
+
+def _set_counts(entry: str, tables, x_u8: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    n = _u8_planes(x_u8)[0]
+    shape = (n, len(tables), SRM_BINS)
+    if out is not None and n:
+        _dev_check(out)
+        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
+            raise ValueError(f"{entry}: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
+    return _count_entry(entry, x_u8, shape[1:], out=out)
+
+
+def srm_fan_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,200,625) int64: per image the co-occurrence counts of the first- and third-order min/max submodels of
+    the spatial rich model over perpendicular pairs and 3-, 4- and 5-fans of the eight directional residuals, table by table as
+    SRM_FAN_TABLES lists them; the two updates per run and the condition for a run to count are srm_minmax_counts's
+    (wsu_srm_fan_counts, K54, which include/wsu.h defines; ws_unet_amd.srm.features_fans makes the features).  `out`: an int64 tensor of
+    that shape to write into (the call zeroes it)."""
+    return _set_counts("srm_fan_counts", SRM_FAN_TABLES, x_u8, out)
+
+
+def srm_edge_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,132,625) int64: per image the co-occurrence counts of the EDGE3x3 and EDGE5x5 classes of the spatial rich
+    model, table by table as SRM_EDGE_TABLES lists them: the four half-kernel residuals U, D, L, R and the min/max tables of eleven sets
+    of them, a singleton's table being its plain table plus the negated one (wsu_srm_edge_counts, K55, which include/wsu.h defines;
+    ws_unet_amd.srm.features_edge makes the features).  `out`: an int64 tensor of that shape to write into (the call zeroes it)."""
+    return _set_counts("srm_edge_counts", SRM_EDGE_TABLES, x_u8, out)
+
+
 # IJG luminance base table (the JPEG standard's Annex K.1), row-major by frequency [u][v]
 _IJG_LUMINANCE = np.array([
     [16, 11, 10, 16, 24, 40, 51, 61], [12, 12, 14, 19, 26, 58, 60, 55], [14, 13, 16, 24, 40, 57, 69, 56], [14, 17, 22, 29, 51, 87, 80, 62],
