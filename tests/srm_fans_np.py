@@ -2,10 +2,8 @@
 (ws_unet_amd/srm.py `features_fans`), written from the definition in srm_minmax_np's shape: eight directional residuals per pixel and
 class, a set is a perpendicular pair or a run of adjacent directions, its digits are the minimum and the maximum over its members'
 digits, a table counts the runs of four lo digits and, negated, of four hi digits.  Vectorised over the batch."""
-import numpy as np
-
 import srm_minmax_np as mm_np
-import srm_np
+import srm_sets_np as sets_np
 
 # the eight directions counter-clockwise and their steps (dr, dc)
 DIRECTIONS = {"E": (0, 1), "NE": (-1, 1), "N": (-1, 0), "NW": (-1, -1), "W": (0, -1), "SW": (1, -1), "S": (1, 0), "SE": (1, 1)}
@@ -49,65 +47,35 @@ SUBMODELS = {
 BINS, CENTRE, ORBITS, DIM = 625, 312, 325, 8125
 
 
+_RESIDUALS = {cls: residuals for cls, (_, residuals) in CLASSES.items()}
+_SETS = {cls: SETS for cls in CLASSES}
+
+
 def reach(cls, name):
-    """(up, down, left, right) of the union of the taps of the set's members"""
-    taps = [t for member in SETS[name] for t in CLASSES[cls][1][member]]
-    return (-min(dr for dr, _ in taps), max(dr for dr, _ in taps), -min(dc for _, dc in taps), max(dc for _, dc in taps))
+    return sets_np.reach(_RESIDUALS, _SETS, cls, name)
 
 
 def ab(cls, name, scan):
-    """the (a, b) of the table's total 2 max(h - a, 0) max(w - b, 0)"""
-    u, dn, l, rt = REACH[cls][name]
-    return (u + dn, l + rt + 3) if scan == "h" else (u + dn + 3, l + rt)
+    return sets_np.ab(REACH, cls, name, scan)
 
 
 def totals(h, w):
     """the 200 totals of an h x w image"""
-    return [2 * max(h - a, 0) * max(w - b, 0) for cls, _, name, scan in TABLES for a, b in [ab(cls, name, scan)]]
+    return sets_np.totals(REACH, TABLES, h, w)
 
 
 def members(x, cls, name):
-    """x (N,H,W) int64 -> the member residuals of the set at every pixel at which all the set's taps lie in the image, (M, N, H', W')"""
-    n, h, w = x.shape
-    u, dn, l, rt = reach(cls, name)
-    hh, ww = max(h - u - dn, 0), max(w - l - rt, 0)
-    out = np.zeros((len(SETS[name]), n, hh, ww), dtype=np.int64)
-    if hh and ww:
-        for k, member in enumerate(SETS[name]):
-            for (dr, dc), wt in CLASSES[cls][1][member].items():
-                out[k] += wt * x[:, u + dr:u + dr + hh, l + dc:l + dc + ww]
-    return out
+    return sets_np.members(_RESIDUALS, _SETS, x, cls, name)
 
 
 def counts(x_u8):
     """(N,200,625) int64 of (N,H,W) uint8 planes"""
-    x = np.asarray(x_u8)
-    assert x.dtype == np.uint8 and x.ndim == 3
-    x = x.astype(np.int64)
-    out, cache = [], {}
-    for cls, q2, name, scan in TABLES:
-        if (cls, name) not in cache:
-            cache[cls, name] = members(x, cls, name)
-        D = srm_np.digit(cache[cls, name], q2)
-        lo, hi = np.minimum.reduce(D), np.maximum.reduce(D)
-        out.append(srm_np.table(lo, scan) + srm_np.table(-hi, scan))
-    return np.stack(out, axis=1)
+    return sets_np.counts(_RESIDUALS, _SETS, TABLES, x_u8)
 
 
 def features(c):
     """(N,200,625) counts -> (N,8125) float64: per (class, q2) its five submodels, each the sum of its tables, folded to 325 orbits and
     divided by its own sum"""
-    c = np.asarray(c).astype(np.int64)
-    at = {t: i for i, t in enumerate(TABLES)}
     orb = mm_np.orbits()
-    out = []
-    for cls, (steps, _) in CLASSES.items():
-        for q2 in steps:
-            for tables in SUBMODELS.values():
-                b = sum(c[:, at[cls, q2, name, scan]] for name, scan in tables)
-                f = np.stack([b[:, o].sum(axis=1) for o in orb], axis=1)
-                s = f.sum(axis=1, keepdims=True)
-                if (s == 0).any():
-                    raise ValueError("a submodel without a run")
-                out.append(f.astype(np.float64) / s.astype(np.float64))
-    return np.concatenate(out, axis=1)
+    return sets_np.features(TABLES, {cls: steps for cls, (steps, _) in CLASSES.items()},
+                            {cls: [(summed, orb) for summed in SUBMODELS.values()] for cls in CLASSES}, c)

@@ -1,13 +1,8 @@
 """numpy-only restatement of the counts of the SRM min/max submodels (include/wsu.h K50) and of the features made from them
-(ws_unet_amd/srm.py `features_minmax`), written from the definition: every member residual of a set is a sum of shifted slices over the
-centres at which ALL the set's taps lie in the image, the set's digits are np.minimum.reduce / np.maximum.reduce over its members'
-digits, a table counts the runs of four lo digits and, negated, of four hi digits (srm_np.digit, srm_np.table).  Vectorised over the
-batch."""
+(ws_unet_amd/srm.py `features_minmax`): the data of its three classes; srm_sets_np has the arithmetic, written from the definition."""
 import itertools
 
-import numpy as np
-
-import srm_np
+import srm_sets_np as sets_np
 
 # class -> (its q2 ascending, its residuals: name -> taps {(dr, dc): weight} around the pixel, its sets in order: name -> members)
 _S13 = {"WE": "WE", "NS": "NS", "WENS": "WENS", "WNE": "WNE", "ESW": "ESW", "SWN": "SWN", "NES": "NES"}
@@ -39,49 +34,30 @@ SUBMODELS["S3"] = SUBMODELS["S1"]
 BINS, CENTRE, ORBITS, DIM = 625, 312, 325, 13000
 
 
+_RESIDUALS = {cls: residuals for cls, (_, residuals, _) in CLASSES.items()}
+_SETS = {cls: sets for cls, (_, _, sets) in CLASSES.items()}
+
+
 def reach(cls, name):
-    """(up, down, left, right) of the union of the taps of the set's members"""
-    taps = [t for member in CLASSES[cls][2][name] for t in CLASSES[cls][1][member]]
-    return (-min(dr for dr, _ in taps), max(dr for dr, _ in taps), -min(dc for _, dc in taps), max(dc for _, dc in taps))
+    return sets_np.reach(_RESIDUALS, _SETS, cls, name)
 
 
 def ab(cls, name, scan):
-    """the (a, b) of the table's total 2 max(h - a, 0) max(w - b, 0)"""
-    u, dn, l, rt = REACH[cls][name]
-    return (u + dn, l + rt + 3) if scan == "h" else (u + dn + 3, l + rt)
+    return sets_np.ab(REACH, cls, name, scan)
 
 
 def totals(h, w):
     """the 118 totals of an h x w image"""
-    return [2 * max(h - a, 0) * max(w - b, 0) for cls, _, name, scan in TABLES for a, b in [ab(cls, name, scan)]]
+    return sets_np.totals(REACH, TABLES, h, w)
 
 
 def members(x, cls, name):
-    """x (N,H,W) int64 -> the member residuals of the set at every pixel at which all the set's taps lie in the image, (M, N, H', W')"""
-    n, h, w = x.shape
-    u, dn, l, rt = reach(cls, name)
-    hh, ww = max(h - u - dn, 0), max(w - l - rt, 0)
-    out = np.zeros((len(CLASSES[cls][2][name]), n, hh, ww), dtype=np.int64)
-    if hh and ww:
-        for k, member in enumerate(CLASSES[cls][2][name]):
-            for (dr, dc), wt in CLASSES[cls][1][member].items():
-                out[k] += wt * x[:, u + dr:u + dr + hh, l + dc:l + dc + ww]
-    return out
+    return sets_np.members(_RESIDUALS, _SETS, x, cls, name)
 
 
 def counts(x_u8):
     """(N,118,625) int64 of (N,H,W) uint8 planes"""
-    x = np.asarray(x_u8)
-    assert x.dtype == np.uint8 and x.ndim == 3
-    x = x.astype(np.int64)
-    out, cache = [], {}
-    for cls, q2, name, scan in TABLES:
-        if (cls, name) not in cache:
-            cache[cls, name] = members(x, cls, name)
-        D = srm_np.digit(cache[cls, name], q2)
-        lo, hi = np.minimum.reduce(D), np.maximum.reduce(D)
-        out.append(srm_np.table(lo, scan) + srm_np.table(-hi, scan))
-    return np.stack(out, axis=1)
+    return sets_np.counts(_RESIDUALS, _SETS, TABLES, x_u8)
 
 
 def orbits():
@@ -102,17 +78,6 @@ def orbits():
 def features(c):
     """(N,118,625) counts -> (N,13000) float64: per (class, q2) its five submodels, each the sum of its tables, folded to 325 orbits and
     divided by its own sum"""
-    c = np.asarray(c).astype(np.int64)
-    at = {t: i for i, t in enumerate(TABLES)}
     orb = orbits()
-    out = []
-    for cls, (steps, _, _) in CLASSES.items():
-        for q2 in steps:
-            for tables in SUBMODELS[cls].values():
-                b = sum(c[:, at[cls, q2, name, scan]] for name, scan in tables)
-                f = np.stack([b[:, o].sum(axis=1) for o in orb], axis=1)
-                s = f.sum(axis=1, keepdims=True)
-                if (s == 0).any():
-                    raise ValueError("a submodel without a run")
-                out.append(f.astype(np.float64) / s.astype(np.float64))
-    return np.concatenate(out, axis=1)
+    return sets_np.features(TABLES, {cls: steps for cls, (steps, _, _) in CLASSES.items()},
+                            {cls: [(summed, orb) for summed in SUBMODELS[cls].values()] for cls in CLASSES}, c)

@@ -35,7 +35,7 @@ template <int K> struct EdgeSpec {                      // K = 1: EDGE3x3, 2: ED
                     l += weight(i, j) * px(j, t + i);
                     r += weight(i, j) * px(j, t - i);
                 }
-            P[0][t] = (uint32_t)ss_digit(u, q2) | (uint32_t)ss_digit(d, q2) << 8 | (uint32_t)ss_digit(l, q2) << 16 | (uint32_t)ss_digit(r, q2) << 24;
+            P[0][t] = (uint32_t)run_digit(u, q2) | (uint32_t)run_digit(d, q2) << 8 | (uint32_t)run_digit(l, q2) << 16 | (uint32_t)run_digit(r, q2) << 24;
         }
     }
 };

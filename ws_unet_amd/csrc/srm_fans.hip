@@ -43,7 +43,7 @@ template <int CLS> struct FanSpec {                     // CLS 1: X[p+d] - X[p];
             for (int k = 0; k < 8; ++k) {
                 const int R = CLS == 1 ? px(dr(k), t + dc(k)) - x
                                        : px(-dr(k), t - dc(k)) - 3 * x + 3 * px(dr(k), t + dc(k)) - px(2 * dr(k), t + 2 * dc(k));
-                P[k >> 2][t] |= (uint32_t)ss_digit(R, q2) << (8 * (k & 3));
+                P[k >> 2][t] |= (uint32_t)run_digit(R, q2) << (8 * (k & 3));
             }
         }
     }

@@ -1,19 +1,18 @@
-// What K54 (srm_fans.hip) and K55 (srm_edge.hip) share: a slice of min/max tables over the sets of up to eight member residuals, K50's
-// organisation (srm_minmax.hip has the account of it) with the members' digits in WORDS words per centre instead of one.  A SPEC says
-// what a class is:
+// What K50 (srm_minmax.hip), K54 (srm_fans.hip) and K55 (srm_edge.hip) share: a slice of min/max tables over the sets of up to eight member
+// residuals, in K50's organisation (srm_minmax.hip has the account of it), the members' digits in WORDS words per centre.  The digit and
+// the binning of a row's runs are srm_runs.h's.  A SPEC says what a class is:
 //   UP, S        the rows above / below the centre row that its taps read, and the shift of the 19 centres (columns c - S + t);
 //   WORDS        its members' digits + 2 packed a byte each, member k in byte k % 4 of word k / 4;
 //   members(k)   the members of set k of the class as bits;  reach(member, side)  how far a member's taps reach up, down, left, right;
 //   digits(px, q2, P)  the packed digits of the step, from px(j, col) = pixel (rho + j, c - S + col).
-// A workgroup is K49's and K50's: the strip tile of wsu_count.h, a thread walking SS_TRT rows of its strip in SS_TRT + 3 steps, scan h in
+// A workgroup is K49's: the strip tile of wsu_count.h, a thread walking SS_TRT rows of its strip in SS_TRT + 3 steps, scan h in
 // steps 0 .. SS_TRT-1 and the scan-v run that ENDS in the row in steps 3 .. SS_TRT+2; the tables of the slice in LDS that the four waves
 // add to with LDS atomics, except the centre bins, which get what is left of the thread's counted updates (a closed form of its rows and
 // column masks) after those that HotBins noted as gone elsewhere: a constant plane takes no atomic at all.
 #pragma once
-#include "wsu_count.h"
+#include "srm_runs.h"
 
-constexpr int SS_TRT = 8, SS_STEPS = SS_TRT + 3, SS_ROWS = CT_GROUPS * SS_TRT, SS_DIGITS = 19;
-constexpr int SS_BINS = 625, SS_CENTRE = 312;
+constexpr int SS_TRT = 8, SS_STEPS = SS_TRT + 3, SS_ROWS = CT_GROUPS * SS_TRT, SS_DIGITS = RUN_DIGITS, SS_BINS = RUN_BINS;
 static_assert(2ll * SS_ROWS * CT_COLS < (1ll << 32), "a tile's 32-bit bins must hold every update of the tile");
 using SsHot = HotBins<2, 16, 2 * 16 * SS_TRT>;          // a set's two tables (scan h, scan v) to a register; a thread adds 2 x 16 x SS_TRT to one
 
@@ -27,48 +26,33 @@ template <int SETS> struct SsState {
 // row of the step m, h the image's rows
 struct SsAt { int rem; bool first; long long rho; int h, m; };
 
-__device__ __forceinline__ uint32_t ss_bit(uint32_t mask, int i) { return (uint32_t)((int)(mask << (31 - i)) >> 31); }
-__device__ __forceinline__ uint32_t ss_low_bits(int n) { return (1u << min(max(n, 0), 16)) - 1u; }
-
-// one update of TABLE (of the slice), counted when `counted` is -1 (not 0): outside the centre bin it takes the LDS atomic and is noted
-template <int TABLE, int SETS> __device__ __forceinline__ void ss_count(SsState<SETS>& s, uint32_t bin, uint32_t counted) {
-    if (((bin ^ (uint32_t)SS_CENTRE) & counted) != 0u) {
-        atomicAdd(&s.hist[TABLE * SS_BINS + bin], 1u);
-        s.other[TABLE >> 1].add(TABLE & 1, true);
+// a set's two tables 2 SET (scan h) and 2 SET + 1 (scan v) to run_bins: run i counts where bit i of mh / mv is set; outside the centre
+// bin it takes the LDS atomic and is noted
+template <int SETS> struct SsCounter {
+    SsState<SETS>& s;
+    uint32_t mh, mv;
+    template <int TABLE, int SCAN> __device__ __forceinline__ void count(uint32_t bin, int i) {
+        if (((bin ^ (uint32_t)RUN_CENTRE) & run_bit(SCAN ? mv : mh, i)) != 0u) {
+            atomicAdd(&s.hist[(TABLE + SCAN) * SS_BINS + bin], 1u);
+            s.other[TABLE >> 1].add(SCAN, true);
+        }
     }
-}
+};
 
-// one half of a set at one step: dg, its digits + 2 at the 19 centres.  Table 2 SET: scan h, run i of digits i .. i+3, counted where bit i
-// of mh is set; table 2 SET + 1: scan v, digit i + S (column c + i) under the three above it, where bit i of mv is set
+// one half of a set at one step: dg, its digits + 2 at the 19 centres
 template <int SET, int HALF, int S, int SETS>
 __device__ __forceinline__ void ss_runs(SsState<SETS>& s, const int (&dg)[SS_DIGITS], uint32_t mh, uint32_t mv) {
     asm volatile("" : "+v"(mh), "+v"(mv));            // the masks' bits are tested here, not ahead of the loop in scalar register pairs
-    int pair[SS_DIGITS - 1];
-#pragma unroll
-    for (int t = 0; t < SS_DIGITS - 1; ++t) pair[t] = dg[t] * 5 + dg[t + 1];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) ss_count<2 * SET>(s, (uint32_t)(pair[i] * 25 + pair[i + 2]), ss_bit(mh, i));
-    uint32_t (&above)[4] = s.above[2 * SET + HALF];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        uint32_t now = 0u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = 4 * g + j;
-            const uint32_t bin = ((above[g] >> (8 * j)) & 255u) * 5u + (uint32_t)dg[i + S];
-            ss_count<2 * SET + 1>(s, bin, ss_bit(mv, i));
-            now |= (bin % 125u) << (8 * j);
-        }
-        above[g] = now;
-    }
+    SsCounter<SETS> counter{s, mh, mv};
+    run_bins<2 * SET, S>(counter, dg, s.above[2 * SET + HALF]);
 }
 
 // the columns of a set that reaches l to the left and rt to the right: bit i set where the run of scan h that starts at column c - S + i
 // (and ends three on), or the run of scan v in column c + i, has its taps in the row
 template <int S> __device__ __forceinline__ uint32_t ss_cols_h(const SsAt& at, int l, int rt) {
-    return ss_low_bits(at.rem + S - rt - 3) & ~(at.first ? ss_low_bits(l + S) : 0u);
+    return run_low_bits(at.rem + S - rt - 3) & ~(at.first ? run_low_bits(l + S) : 0u);
 }
-__device__ __forceinline__ uint32_t ss_cols_v(const SsAt& at, int l, int rt) { return ss_low_bits(at.rem - rt) & ~(at.first ? ss_low_bits(l) : 0u); }
+__device__ __forceinline__ uint32_t ss_cols_v(const SsAt& at, int l, int rt) { return run_low_bits(at.rem - rt) & ~(at.first ? run_low_bits(l) : 0u); }
 
 // how far the taps of the members MEMBERS (bits) of SPEC reach on `side` (0 up, 1 down, 2 left, 3 right): the largest over the members
 template <class SPEC> constexpr int ss_reach(int members, int side) {
@@ -122,13 +106,6 @@ template <class SPEC, int MEMBERS> __device__ __forceinline__ uint32_t ss_counte
     return 2u * (uint32_t)(rows_h * __popc(ss_cols_h<SPEC::S>(at, l, rt))) + ((2u * (uint32_t)(rows_v * __popc(ss_cols_v(at, l, rt)))) << 16);
 }
 
-// the digit + 2 of a residual R at the step q2 / 2: sign(R) min((4|R| + q2) / (2 q2), 2) is (4|R| >= q2) + (4|R| >= 3 q2) with the sign
-__device__ __forceinline__ int ss_digit(int R, int q2) {
-    const int mag = 4 * abs(R), sgn = R >> 31;
-    const int m = (mag >= q2 ? 1 : 0) + (mag >= 3 * q2 ? 1 : 0);
-    return (m ^ sgn) - sgn + 2;
-}
-
 // the sets SET0 + K of the class at one step, and their centre bins: the counted updates less those that went elsewhere
 template <class SPEC, int SET0, int SETS, int... K>
 __device__ __forceinline__ void ss_sets(SsState<SETS>& s, uint32_t (&P)[SPEC::WORDS][SS_DIGITS], const SsAt& at, std::integer_sequence<int, K...>) {
@@ -139,7 +116,7 @@ __device__ __forceinline__ void ss_centres(const SsState<SETS>& s, const SsAt& a
     ([&] {
         SsHot centre;
         centre.v = live ? ss_counted<SPEC, SPEC::members(SET0 + K)>(at, r0) - s.other[K].v : 0u;
-        centre.fold(s.hist + 2 * K * SS_BINS + SS_CENTRE, SS_BINS);
+        centre.fold(s.hist + 2 * K * SS_BINS + RUN_CENTRE, SS_BINS);
     }(), ...);
 }
 

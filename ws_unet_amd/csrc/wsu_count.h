@@ -1,6 +1,6 @@
-// What the exact count kernels share (ols.hip: K24; structural.hip: K25, K26; spam.hip: K36; srm.hip: K49; srm_minmax.hip: K50;
-// jpeg_history.hip: K31): the strip tile and its loaders, the wave fold, the packed counter of the hot bins, a workgroup's flush and the
-// host's launch set-up.  Every output is a table of exact integers that the kernels only ADD to, so the bits depend on no order: the entry
+// What the exact count kernels share (ols.hip: K24; structural.hip: K25, K26; spam.hip: K36; jpeg_history.hip: K31; the rich model's five
+// -- srm.hip: K49, srm_weighted.hip: K52, and through srm_sets.h and srm_runs.h srm_minmax.hip: K50, srm_fans.hip: K54, srm_edge.hip: K55):
+// the strip tile and its loaders, the wave fold, the packed counter of the hot bins, a workgroup's flush and the host's launch set-up.  Every output is a table of exact integers that the kernels only ADD to, so the bits depend on no order: the entry
 // point zeroes the table on the stream, a workgroup sums its tile in 32- or 64-bit partials and adds each non-zero sum with one 64-bit
 // vector atomic.
 #pragma once
@@ -23,7 +23,7 @@ __device__ __forceinline__ CtStrip ct_strip(int tiles_c, int w, int reach) {
     s.rem = (int)min(max((long long)w - s.c, 0ll), (long long)(16 + reach));
     return s;
 }
-// the same for a kernel whose threads walk TRT rows (K49, K50: 8, a tile of CT_GROUPS * TRT rows): c, r0, and rem capped at 32
+// the same for a kernel whose threads walk TRT rows (the rich model's: 8, a tile of CT_GROUPS * TRT rows): c, r0, and rem capped at 32
 template <int TRT> __device__ __forceinline__ CtStrip ct_strip_rows(int tiles_c, int w) {
     CtStrip s;
     s.c = (long long)(blockIdx.x % tiles_c) * CT_COLS + (threadIdx.x & (CT_STRIPS - 1)) * 16;

@@ -1345,19 +1345,31 @@ SRM_REACH = {"S1": {("h", "h"): (0, 4), ("h", "v"): (3, 1), ("v", "h"): (1, 3), 
 SRM_TABLES = tuple((cls, q2, res, scan, *ab) for cls, steps in SRM_Q2.items() for q2 in steps for (res, scan), ab in SRM_REACH[cls].items())
 
 
+def _set_counts(entry: str, tables, x_u8: torch.Tensor, out: Optional[torch.Tensor], *middle) -> torch.Tensor:
+    """the count entry `entry` of the SRM, one row of SRM_BINS per table of `tables`, with `out` validated; middle: as _count_entry's"""
+    n = _u8_planes(x_u8)[0]
+    shape = (n, len(tables), SRM_BINS)
+    if out is not None and n:
+        _dev_check(out)
+        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
+            raise ValueError(f"{entry}: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
+    return _count_entry(entry, x_u8, shape[1:], *middle, out=out)
+
+
+def _set_tables(q2, sets):
+    """the tables of a min/max count kernel in the order of its counts, (class, q2, set, scan, a, b) with the table's total
+    2 max(H - a, 0) max(W - b, 0): for class; for q2 ascending; for set; for scan in (h, v)"""
+    return tuple((cls, q, name, scan, u + dn + (3 if scan == "v" else 0), l + rt + (3 if scan == "h" else 0))
+                 for cls, steps in q2.items() for q in steps for name, (u, dn, l, rt) in sets[cls].items() for scan in "hv")
+
+
 def srm_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,44,625) int64: per image the co-occurrence counts of the linear submodels of the spatial rich model, table
     by table as SRM_TABLES lists them: the runs of four digits -2..2 of one linear residual at one quantisation step along a row or down
     a column, over every run whose pixels all lie in the image; bin = the digits + 2 in base 5, the first one most significant
     (wsu_srm_counts, K49, which include/wsu.h defines; ws_unet_amd.srm makes the features).  `out`: an int64 tensor of that shape to write
     into (the call zeroes it)."""
-    n = _u8_planes(x_u8)[0]
-    shape = (n, len(SRM_TABLES), SRM_BINS)
-    if out is not None and n:
-        _dev_check(out)
-        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
-            raise ValueError(f"srm_counts: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
-    return _count_entry("srm_counts", x_u8, shape[1:], out=out)
+    return _set_counts("srm_counts", SRM_TABLES, x_u8, out)
 
 
 def srm_weighted_counts(x_u8: torch.Tensor, weights: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1365,17 +1377,12 @@ def srm_weighted_counts(x_u8: torch.Tensor, weights: torch.Tensor, out: Optional
     largest of the weights at its four residual positions instead of 1 (wsu_srm_weighted_counts, K52, which include/wsu.h defines: the
     integer half of the selection-channel-aware features of ws_unet_amd.srm; change_weights makes a sender's weights).  Weights all 1
     give srm_counts.  `out`: an int64 tensor of that shape to write into (the call zeroes it)."""
-    n = _u8_planes(x_u8)[0]
+    _u8_planes(x_u8)
     _dev_check(weights)
     if weights.dtype != torch.uint16 or weights.shape != x_u8.shape or weights.device != x_u8.device:
         raise ValueError(f"srm_weighted_counts: weights must be uint16 of shape {tuple(x_u8.shape)} on {x_u8.device}, got "
                          f"{tuple(weights.shape)} {weights.dtype} on {weights.device}")
-    shape = (n, len(SRM_TABLES), SRM_BINS)
-    if out is not None and n:
-        _dev_check(out)
-        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
-            raise ValueError(f"srm_weighted_counts: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
-    return _count_entry("srm_weighted_counts", x_u8, shape[1:], weights.data_ptr(), out=out)
+    return _set_counts("srm_weighted_counts", SRM_TABLES, x_u8, out, weights.data_ptr())
 
 
 SUBSPACE_GRAM_MAX_BYTES = 1 << 30         # default output budget of one K53 launch: memory, not a tuned number
@@ -1435,9 +1442,7 @@ SRM_MINMAX_SETS = {
     "S1": {"WE": (0, 0, 1, 1), "NS": (1, 1, 0, 0), "WENS": (1, 1, 1, 1), "WNE": (1, 0, 1, 1), "ESW": (0, 1, 1, 1), "SWN": (1, 1, 1, 0), "NES": (1, 1, 0, 1)},
     "S2": {name: (1, 1, 1, 1) for name in ("hv", "hvdm", "hvd", "hvm", "hd", "hm", "vd", "vm")},
     "S3": {"WE": (0, 0, 2, 2), "NS": (2, 2, 0, 0), "WENS": (2, 2, 2, 2), "WNE": (2, 1, 2, 2), "ESW": (1, 2, 2, 2), "SWN": (2, 2, 2, 1), "NES": (2, 2, 1, 2)}}
-SRM_MINMAX_TABLES = tuple((cls, q2, name, scan, u + dn + (3 if scan == "v" else 0), l + rt + (3 if scan == "h" else 0))
-                          for cls, steps in SRM_MINMAX_Q2.items() for q2 in steps for name, (u, dn, l, rt) in SRM_MINMAX_SETS[cls].items()
-                          for scan in "hv")
+SRM_MINMAX_TABLES = _set_tables(SRM_MINMAX_Q2, SRM_MINMAX_SETS)
 
 
 def srm_minmax_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1446,20 +1451,7 @@ def srm_minmax_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) ->
     along a row or down a column the minimum digits of a set of residuals at their bin and its maximum digits, negated, at theirs, over
     every run whose taps all lie in the image (wsu_srm_minmax_counts, K50, which include/wsu.h defines; ws_unet_amd.srm.features_minmax
     makes the features).  `out`: an int64 tensor of that shape to write into (the call zeroes it)."""
-    n = _u8_planes(x_u8)[0]
-    shape = (n, len(SRM_MINMAX_TABLES), SRM_BINS)
-    if out is not None and n:
-        _dev_check(out)
-        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
-            raise ValueError(f"srm_minmax_counts: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
-    return _count_entry("srm_minmax_counts", x_u8, shape[1:], out=out)
-
-
-def _set_tables(q2, sets):
-    """the tables of a min/max count kernel in the order of its counts, (class, q2, set, scan, a, b) with the table's total
-    2 max(H - a, 0) max(W - b, 0): for class; for q2 ascending; for set; for scan in (h, v)"""
-    return tuple((cls, q, name, scan, u + dn + (3 if scan == "v" else 0), l + rt + (3 if scan == "h" else 0))
-                 for cls, steps in q2.items() for q in steps for name, (u, dn, l, rt) in sets[cls].items() for scan in "hv")
+    return _set_counts("srm_minmax_counts", SRM_MINMAX_TABLES, x_u8, out)
 
 
 def _fan_sets(along, against):
@@ -1485,16 +1477,6 @@ SRM_EDGE_Q2 = {"E3": SRM_Q2["S3x3"], "E5": SRM_Q2["S5x5"]}
 SRM_EDGE_SETS = {cls: {"U": (k, 0, k, k), "D": (0, k, k, k), "L": (k, k, k, 0), "R": (k, k, 0, k),
                        **{name: (k, k, k, k) for name in ("UL", "UR", "DL", "DR", "UD", "LR", "UDLR")}} for cls, k in (("E3", 1), ("E5", 2))}
 SRM_EDGE_TABLES = _set_tables(SRM_EDGE_Q2, SRM_EDGE_SETS)
-
-
-def _set_counts(entry: str, tables, x_u8: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
-    n = _u8_planes(x_u8)[0]
-    shape = (n, len(tables), SRM_BINS)
-    if out is not None and n:
-        _dev_check(out)
-        if out.dtype != torch.int64 or tuple(out.shape) != shape or out.device != x_u8.device:
-            raise ValueError(f"{entry}: out must be an int64 tensor of shape {shape} on {x_u8.device}, got {tuple(out.shape)} {out.dtype}")
-    return _count_entry(entry, x_u8, shape[1:], out=out)
 
 
 def srm_fan_counts(x_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
