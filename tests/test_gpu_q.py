@@ -43,7 +43,8 @@ def _conv3x3_q_ref(x, w, b):
 def _check_q_tensor(tq, ta, what):
     """A planar Q tensor against the e4m3-residual tensor `ta` the same kernel wrote from the same fp32 values: the f16 planes are the same
     bytes; block exponents and the f16 parts' fp4 nibbles are functions of the f16 planes -- exact; the residual nibbles come from the kernel's
-    exact fp32 residual, `ta` carries it rounded to e4m3 -- a few land on the neighbouring grid point."""
+    exact fp32 residual, `ta` carries it rounded to e4m3 -- a few land on the neighbouring grid point.  (The nibble a producer must write
+    for a KNOWN fp32 value is held exactly by tests/test_gpu_q4_terms.py.)"""
     from gpu_util import fp4_codes, q_block_exp
     val, hi, ch, cr, e = planar_q_decode(tq, parts=True)
     raw = ta.detach().contiguous().view(torch.uint8)                                        # (n, chunk, 3, h, w, 16)
