@@ -474,6 +474,27 @@ int wsu_ws_key_search(const long long* num, const long long* den, long long coun
  *      neighbours, X^T y (q = 8) and y^T y (last).  Exact integers (at most 255^2 (H-2)(W-2) each), the same bits on every run. */
 int wsu_ols_moments(const uint8_t* x_u8, unsigned long long* moments, int n, int h, int w, void* stream);
 
+/* ---- K56: moments of the least-squares 5x5 pixel predictor.  x_u8: (N,H,W) DEVICE pixels, H, W >= 5 (else an argument error, checked
+ *      before any HIP call), N <= 65535.  The sums run over every pixel (r,c) with a full 5x5 window, 2 <= r <= H-3, 2 <= c <= W-3.  The 25
+ *      variables: v[0..23] = the 24 neighbours x[r-2+a][c-2+b] in raster order of (a,b), the centre skipped; v[24] = the centre.
+ *      moments: DEVICE (N,325) uint64, zeroed on the stream by this call: moments[i][.] = sum of v_p * v_q, 0 <= p <= q <= 24, row-major
+ *      upper triangle -- K24's layout with 25 variables in place of 9.  Exact integers (at most 255^2 (H-4)(W-4) each), the same bits on
+ *      every run, every batch and every launch split. */
+int wsu_ols_moments5(const uint8_t* x_u8, unsigned long long* moments, int n, int h, int w, void* stream);
+
+/* ---- K57: the 5x5 linear prediction as full frames.  x_u8: (N,H,W) DEVICE pixels, H, W >= 3, N <= 65535.  taps: DEVICE fp32, (N,24) with
+ *      per_image != 0, else (24) for every image; taps[k] weighs v[k] of K56.  x_hat: DEVICE fp32 (N,H,W) in pixel units (hat_scale = 1
+ *      for the WS statistics); x_bias: the same shape, or null.  float32 with plain operators, one rounding each, nothing fused;
+ *      q(u) = (float)u / 255.0f (K11's quotient), qb(u) = (u & 1) ? -q(1) : q(1).  Per pixel:
+ *        frame border (r or c the first or last)       x_hat = 0, x_bias = 0 (no statistic reads them; the plane is fully written)
+ *        ring 1 (r in {1, H-2} or c in {1, W-2})       KB's 3x3 taps as K11 evaluates an in-kernel filter: acc = 0; for j = 8 .. 0:
+ *                                                      acc = acc + kb[j] * q[j]; x_hat = acc * 255.0f (the 5x5 window leaves the image;
+ *                                                      it is not mirrored, which would let a pixel predict itself)
+ *        elsewhere                                     acc = 0; for k = 23 .. 0: acc = acc + taps[k] * q(v[k]); x_hat = acc * 255.0f
+ *      x_bias is the same sequence with qb in place of q.  With KB's taps embedded in the 24, K11 on these planes with hat_scale = 1 has
+ *      the bits of K11 with pixel_filter = KB.  Every argument is checked before any HIP call. */
+int wsu_predict5x5(const uint8_t* x_u8, const float* taps, int per_image, float* x_hat, float* x_bias, int n, int h, int w, void* stream);
+
 /* ---- K25: the trace-set table of Sample Pairs Analysis (Dumitrescu, Wu, Wang 2003).  x_u8: (N,H,W) DEVICE pixels, any H, W >= 1.  The
  *      pairs of an image are all horizontally adjacent (x[r][c], x[r][c+1]) and all vertically adjacent (x[r][c], x[r+1][c]):
  *      H (W-1) + (H-1) W of them.  For a pair (u,v): d = |u - v|, m = d >> 1, hi = max(u,v).  tables: DEVICE (N,3,128) uint64, zeroed on the

@@ -105,6 +105,8 @@ SIGNATURES = {
     "wsu_ws_residual_accumulate": (c_int, [_P] * 5 + [c_int, c_float, c_int, c_int, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_ws_key_search": (c_int, [_P, _P, c_longlong, _P, c_uint64, c_int, c_int, c_uint64, c_int, _P, _P, _P]),
     "wsu_ols_moments": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "wsu_ols_moments5": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "wsu_predict5x5": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
     "wsu_spa_tables": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_rs_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_spam_counts": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -164,14 +164,6 @@ __global__ __launch_bounds__(JH_THREADS) void jpeg_energies_kernel(const uint8_t
     count_flush<JH_WAVES>(part, mt, energies, (size_t)nn * m_total);
 }
 
-// the KB filter's K[a][b] (filters.NAMED_FILTERS_2D['KB']); symmetric, so K and the taps of the correlation layout are the same numbers
-__device__ __forceinline__ Taps3x3<float> jh_kb_taps() {
-    Taps3x3<float> t;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) t.k[i] = i == 4 ? 0.0f : (i & 1) ? 0.5f : -0.25f;
-    return t;
-}
-
 __global__ __launch_bounds__(JH_THREADS) void jpeg_predict_kernel(const uint8_t* __restrict__ xu8, const JhTables tabs, float* __restrict__ xhat,
                                                                  uint8_t* __restrict__ xout, int h, int w, long long blocks) {
     __shared__ __attribute__((aligned(16))) int tl[JH_SLOTS * JH_TS];
@@ -186,7 +178,7 @@ __global__ __launch_bounds__(JH_THREADS) void jpeg_predict_kernel(const uint8_t*
     if (!((tabs.use >> nn) & 1u)) {                      // (uniform over the workgroup) no JPEG history: KB's prediction, the input as the twin
         unit[tid] = (float)tid / 255.0f;
         __syncthreads();
-        const Taps3x3<float> kb = jh_kb_taps();
+        const Taps3x3<float> kb = kb_taps_f32();
 #pragma unroll 1
         for (int j = 0; j < JH_B; ++j) {
             const long long b = b0 + j * (JH_THREADS / 8) + (tid >> 3);

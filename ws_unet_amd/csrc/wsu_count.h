@@ -1,4 +1,4 @@
-// What the exact count kernels share (ols.hip: K24; structural.hip: K25, K26; spam.hip: K36; jpeg_history.hip: K31; the rich model's five
+// What the exact count kernels share (ols.hip: K24; ols5.hip: K56; structural.hip: K25, K26; spam.hip: K36; jpeg_history.hip: K31; the rich model's five
 // -- srm.hip: K49, srm_weighted.hip: K52, and through srm_sets.h and srm_runs.h srm_minmax.hip: K50, srm_fans.hip: K54, srm_edge.hip: K55):
 // the strip tile and its loaders, the wave fold, the packed counter of the hot bins, a workgroup's flush and the host's launch set-up.  Every output is a table of exact integers that the kernels only ADD to, so the bits depend on no order: the entry
 // point zeroes the table on the stream, a workgroup sums its tile in 32- or 64-bit partials and adds each non-zero sum with one 64-bit

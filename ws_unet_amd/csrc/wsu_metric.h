@@ -26,6 +26,15 @@ template <typename T> inline Taps3x3<T> taps_from_kernel(const T* kern) {       
     return t;
 }
 
+// the KB filter's K[a][b] (filters.NAMED_FILTERS_2D['KB']); symmetric, so K and the taps of the correlation layout are the same numbers
+// (K32's and K57's in-kernel KB prediction)
+__device__ __forceinline__ Taps3x3<float> kb_taps_f32() {
+    Taps3x3<float> t;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) t.k[i] = i == 4 ? 0.0f : (i & 1) ? 0.5f : -0.25f;
+    return t;
+}
+
 // The sum order is part of a result's bits: REVERSE = false visits x[r-1][c-1] first (x @ filter, K14 / K16), REVERSE = true visits
 // x[r+1][c+1] first, i.e. K00 .. K22 of scipy's convolve (K11 / K15).  v[i][j] = x[r-1+i][c-1+j].
 template <bool REVERSE> __device__ __forceinline__ float conv9_f32(const Taps3x3<float>& t, const float v[3][3]) {

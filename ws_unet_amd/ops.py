@@ -1297,6 +1297,36 @@ def ols_moments(x_u8: torch.Tensor) -> torch.Tensor:
     return _count_entry("ols_moments", x_u8, (45,))
 
 
+def ols_moments5(x_u8: torch.Tensor) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8, H, W >= 5 -> (N,325) int64: per image the exact sums of v_p * v_q, p <= q (row-major upper triangle), over the
+    pixels with a full 5x5 window, v = the 24 neighbours in raster order and the centre (wsu_ols_moments5, K56; ws_unet_amd.ols5 unpacks
+    and solves)."""
+    return _count_entry("ols_moments5", x_u8, (325,))
+
+
+def predict5x5(x_u8: torch.Tensor, taps: torch.Tensor, want_bias: bool = False):
+    """The 5x5 linear prediction of every image as full frames in pixel units (wsu_predict5x5, K57).  x_u8: (N,H,W) uint8, H, W >= 3;
+    taps: DEVICE float32 (24,) for every image or (N,24) for one row per image, in K56's variable order.  Returns x_hat float32 (N,H,W)
+    -- 0 on the frame border, KB's prediction on the ring inside it, the 24 taps elsewhere -- and with want_bias (x_hat, x_bias), x_bias
+    the predictor applied to x_bar - x: what ws_attack takes as x_hat / x_bias with hat_scale = 1."""
+    n, h, w = _u8_planes(x_u8)
+    if n == 0:
+        raise ValueError("predict5x5: no images")
+    if not (isinstance(taps, torch.Tensor) and taps.dtype == torch.float32 and tuple(taps.shape) in ((24,), (n, 24))):
+        raise ValueError(f"predict5x5: taps must be a float32 tensor of shape (24,) or {(n, 24)}, got "
+                         f"{tuple(taps.shape) if isinstance(taps, torch.Tensor) else type(taps).__name__}"
+                         f"{' ' + str(taps.dtype) if isinstance(taps, torch.Tensor) else ''}")
+    _dev_check(taps)
+    if taps.device != x_u8.device:
+        raise ValueError(f"predict5x5: taps live on {taps.device}, the pixels on {x_u8.device}")
+    lib = _lib.load()
+    x_hat = torch.empty((n, h, w), dtype=torch.float32, device=x_u8.device)
+    x_bias = torch.empty_like(x_hat) if want_bias else None
+    check(_launch("predict5x5", {"bytes": float(n * h * w * (5 + 4 * bool(want_bias)))}, lambda: lib.wsu_predict5x5(
+        x_u8.data_ptr(), taps.data_ptr(), int(taps.dim() == 2), x_hat.data_ptr(), _ptr(x_bias), n, h, w, _stream())), "wsu_predict5x5")
+    return (x_hat, x_bias) if want_bias else x_hat
+
+
 def spa_tables(x_u8: torch.Tensor) -> torch.Tensor:
     """x_u8: (N,H,W) uint8 -> (N,3,128) int64: per image the sample-pairs table over all horizontally and vertically adjacent pixel pairs
     (u,v), indexed by m = |u-v| >> 1: [0] E, |u-v| even; [1] X, odd with max(u,v) even; [2] Y, odd with max(u,v) odd (wsu_spa_tables, K25;

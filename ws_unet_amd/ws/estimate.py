@@ -33,7 +33,7 @@ import typing
 import numpy as np
 import torch
 
-from .. import fabrika, filters, ols, ops
+from .. import fabrika, filters, ols, ols5, ops
 from ..imread import imread4_u8, u8_plane
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import check_unet_geometry, model_device, unet_plane
@@ -103,7 +103,8 @@ def predictor_arguments(x_u8: torch.Tensor, pixel_estimator, host_planes=None, c
     `pixel_filter` for a filters.FilterEstimator (evaluated in the kernel) and an ols.AdaptiveOLSEstimator (moments -> float64 fit on the
     host -> one filter per image); `x_hat` with `hat_scale` for a UNetEstimator (the full-frame output stays on the device, scale 255)
     and for any other callable (the reference's call pattern on `host_planes`, one image at a time; interior layout, scale 1); `x_hat`
-    with scale 1 for a jpeg.JPEGEstimator (history search and round trip on the device, full frames in pixel units).  With
+    with scale 1 for a jpeg.JPEGEstimator (history search and round trip on the device, full frames in pixel units) and for an
+    ols5.Predictor5x5 (moments -> float64 fit on the host -> K57's full frames in pixel units, with its own `x_bias` plane).  With
     correct_bias also `x_bias`, the predictor applied to x_bar - x, where the predictor has one outside the kernel."""
     if isinstance(pixel_estimator, UNetEstimator):
         check_unet_geometry(x_u8.shape[1:], "the UNet estimator")
@@ -116,6 +117,11 @@ def predictor_arguments(x_u8: torch.Tensor, pixel_estimator, host_planes=None, c
     if isinstance(pixel_estimator, jpeg.JPEGEstimator):
         _require_no_bias_correction(pixel_estimator, correct_bias)
         return dict(x_hat=pixel_estimator.planes(x_u8), hat_scale=1.0)
+    if isinstance(pixel_estimator, ols5.Predictor5x5):
+        if not correct_bias:
+            return dict(x_hat=pixel_estimator.planes(x_u8), hat_scale=1.0)
+        x_hat, x_bias = pixel_estimator.planes(x_u8, want_bias=True)
+        return dict(x_hat=x_hat, x_bias=x_bias, hat_scale=1.0)
     if host_planes is None:
         raise ValueError(f"a host predictor ({type(pixel_estimator).__name__}) needs the planes on the host (host_planes)")
     hats, biases = [], []
@@ -241,7 +247,7 @@ def attack_stego(*args, **kw):
 def _native_planes_ok(channels, pixel_estimator, imread, process_image) -> bool:
     """The default gray pipeline (Y plane, built-in predictor) needs no host arrays: native batched decode -> pinned buffer -> device."""
     builtin = isinstance(pixel_estimator, (UNetEstimator, filters.FilterEstimator, ols.AdaptiveOLSEstimator, structural.StructuralEstimator,
-                                           jpeg.JPEGEstimator))
+                                           jpeg.JPEGEstimator, ols5.Predictor5x5))
     plain = process_image is None or getattr(process_image, "plane_selector", None) == (3,)
     return builtin and imread is imread4_u8 and plain and tuple(channels) == (3,)
 
@@ -315,6 +321,8 @@ def run(
         _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
     elif model_name in ols.ADAPTIVE_NAMES:                       # 'OLSa' / 'OLSa2': the least-squares filter of each image under attack
         pixel_estimator = ols.adaptive_estimator(model_name)
+    elif ols5.estimator(model_name) is not None:                 # 'OLSa5x5' / 'OLSa5x5s' and the names of a --kernels5 file: 5x5 least squares
+        pixel_estimator = ols5.estimator(model_name)
     elif model_name in jpeg.NAMES:                               # 'JPEG': each image after a round trip through its own quantisation table
         pixel_estimator = jpeg.estimator(model_name)
         _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
@@ -356,7 +364,7 @@ def parse_args(argv=None):
     ap.add_argument("--stego-methods", nargs="*", default=["LSBR"])
     ap.add_argument("--alphas", nargs="*", type=float, default=[.4, .2, .1])
     ap.add_argument("--filters", nargs="*", default=["AVG", "KB"],
-                    help="named filters, the adaptive 'OLSa' / 'OLSa2', the recompression predictor 'JPEG', and the structural estimators "
+                    help="named filters, the adaptive 'OLSa' / 'OLSa2' and 5x5 'OLSa5x5' / 'OLSa5x5s', the recompression predictor 'JPEG', and the structural estimators "
                          "'SPA' / 'RS' (with --weighted 0)")
     ap.add_argument("--losses", nargs="*", default=["l1", "l1ws"])
     ap.add_argument("--weighted", type=int, default=0)
@@ -371,6 +379,7 @@ def parse_args(argv=None):
                     help="adaptive placement: the probability that a used pixel was flipped (1: HILLR flips every used pixel; 0.5: a real message)")
     ap.add_argument("--out", default=None)
     ols.add_kernels_argument(ap)
+    ols5.add_kernels_argument(ap)
     return ap.parse_args(argv)
 
 
@@ -382,6 +391,7 @@ def main(argv=None) -> None:
     from .. import get_model_name
     a = parse_args(argv)
     ols.register_from_args(a)
+    ols5.register_from_args(a)
     model_dir = pathlib.Path(a.model_dir)
     settings = [(None, .0)] + [(sm, al) for sm in a.stego_methods for al in a.alphas]
     common = dict(demosaic=None, channels=(3,), correct_bias=a.correct_bias, weighted=a.weighted, batched=not a.per_image)

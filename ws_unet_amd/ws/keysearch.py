@@ -25,7 +25,7 @@ import typing
 import numpy as np
 import torch
 
-from .. import ols, ops
+from .. import ols, ols5, ops
 from . import locate
 
 CHUNK_KEYS = 1 << 22                                       # keys per launch when a range is walked
@@ -235,6 +235,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--weighted", type=int, choices=(0, 1), default=1)
     ap.add_argument("--per-image", action="store_true", help="use the per-image iterator instead of the batched one")
     ols.add_kernels_argument(ap)
+    ols5.add_kernels_argument(ap)
     a = ap.parse_args(argv)
     if (a.keys_file is None) == (a.first is None and a.count is None) or (a.keys_file is None and (a.first is None or a.count is None)):
         ap.error("give either --first and --count or --keys-file")
@@ -244,6 +245,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 def main(argv=None) -> None:
     a = parse_args(argv)
     ols.register_from_args(a)
+    ols5.register_from_args(a)
     keys = read_keys_file(a.keys_file) if a.keys_file else None
     res = run(pathlib.Path(a.data), a.stego_method, a.alpha, a.filter, None, (3,), keys=keys, first=a.first, count=a.count,
               search_alpha=a.search_alpha, key=a.key, prefilter_rows=a.prefilter_rows, keep=a.keep, top=a.top, weighted=a.weighted,

@@ -24,7 +24,7 @@ import typing
 import numpy as np
 import torch
 
-from .. import fabrika, filters, ols, ops
+from .. import fabrika, filters, ols, ols5, ops
 from ..imread import imread4_u8
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import model_device
@@ -206,12 +206,14 @@ _ITERATORS = {
 
 
 def pixel_predictor(model_name: str, model_path, channels):
-    """A named filter, 'OLSa' / 'OLSa2', 'JPEG' or a trained UNet run as (pixel predictor, the name its rows carry); the structural estimators
+    """A named filter, 'OLSa' / 'OLSa2', a 5x5 predictor of ols5 ('OLSa5x5' / 'OLSa5x5s', a --kernels5 name), 'JPEG' or a trained UNet run as (pixel predictor, the name its rows carry); the structural estimators
     have no per-pixel prediction and raise."""
     if model_name in structural.NAMES:
         raise ValueError(f"ws.locate needs a pixel predictor; the structural estimators {structural.NAMES} have none")
     if model_name in ols.ADAPTIVE_NAMES:
         return ols.adaptive_estimator(model_name), model_name
+    if ols5.estimator(model_name) is not None:
+        return ols5.estimator(model_name), model_name
     if model_name in jpeg.NAMES:
         return jpeg.estimator(model_name), model_name
     if model_name in estimate.NAMED_FILTERS:
@@ -274,7 +276,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--stego-method", default="LSBRK")
     ap.add_argument("--alpha", type=float, required=True)
-    ap.add_argument("--filters", nargs="*", default=["AVG", "KB"], help="named filters, the adaptive 'OLSa' / 'OLSa2' and the recompression predictor 'JPEG'")
+    ap.add_argument("--filters", nargs="*", default=["AVG", "KB"], help="named filters, the adaptive 'OLSa' / 'OLSa2' and 5x5 'OLSa5x5' / 'OLSa5x5s', and the recompression predictor 'JPEG'")
     ap.add_argument("--model-dir", default=None, help="trained UNets in the reference's layout <dir>/<train method>/<run>/; no UNet rows without it")
     ap.add_argument("--losses", nargs="*", default=["l1ws"], help="UNet runs under --model-dir: 'l1' (the dropout run), 'l1ws' (--train-method)")
     ap.add_argument("--train-method", default="LSBR", help="stego method the l1ws UNet was trained on")
@@ -283,6 +285,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--at", type=int, nargs="*", default=[], help="image counts at which a decision is taken, beside the whole set")
     ap.add_argument("--per-image", action="store_true", help="use the per-image iterator instead of the batched one")
     ols.add_kernels_argument(ap)
+    ols5.add_kernels_argument(ap)
     return ap.parse_args(argv)
 
 
@@ -291,6 +294,7 @@ def main(argv=None) -> None:
     from PIL import Image
     a = parse_args(argv)
     ols.register_from_args(a)
+    ols5.register_from_args(a)
     jobs = [(name, name, None) for name in a.filters]
     if a.model_dir:
         from .. import get_model_name
