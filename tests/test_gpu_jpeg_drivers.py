@@ -110,6 +110,27 @@ def test_raw_covers_fall_back_and_their_rows_are_kbs(datasets):
     assert torch.isnan(none).all()                       # no estimate: `run` drops such rows
 
 
+@pytest.mark.parametrize("name", ["KB", "OLSa2", "OLSa5x5s", "JPEG"])
+def test_the_three_drivers_resolve_a_name_to_one_predictor(datasets, name):
+    """ws.estimate.run, ws.roc.collect_ws_scores and ws.locate.pixel_predictor's estimator (which ws.keysearch uses too) give the same
+    bits for the same files: one name table (ws/predictors.py), one mapping to the kernels' arguments (`device_arguments`)"""
+    _, twin = datasets
+    run = estimate.run(twin, "LSBR", 0.4, name, None, (3,), weighted=0, correct_bias=False, batched=True)
+    assert run["name"].tolist() == [f"{STEGO}/{k}.png" for k in ORDER] and run["model_name"].tolist() == [name] * 5
+    beta = run["beta_hat"].to_numpy(np.float32)
+    res = roc.collect_ws_scores(twin, ["LSBR"], [0.4], (name,))
+    got = res[(res.model_name == name) & (res.stego_method == "LSBR")]
+    assert got["name"].tolist() == run["name"].tolist()
+    np.testing.assert_array_equal(got["beta_hat"].to_numpy(np.float32).view(np.uint32), beta.view(np.uint32))
+    est, label = locate.pixel_predictor(name, None, (3,))
+    assert label == name
+    x = torch.from_numpy(np.stack([_plane(twin / STEGO / f"{k}.png") for k in ORDER])).to(DEV)
+    stat = estimate._stat(x, est, estimate.NAMED_FILTERS["AVG"], 0, False).cpu().numpy()
+    print(f"{name}: beta_hat {beta.tolist()}")
+    assert stat.dtype == np.float32
+    np.testing.assert_array_equal(stat.view(np.uint32), beta.view(np.uint32))
+
+
 def test_filters_jpeg_kb_in_roc_and_locate(datasets, tmp_path):
     _, twin = datasets
     roc.main(["--data", str(twin), "--out-dir", str(tmp_path / "roc"), "--alphas", "0.4", "--filters", "JPEG", "KB"])

@@ -89,6 +89,10 @@ class FilterEstimator:
     def __call__(self, x: np.ndarray) -> np.ndarray:
         return infere_single(x, self.kernel)
 
+    def device_arguments(self, x_u8, correct_bias: bool = False) -> dict:
+        """The statistic kernels' keywords (ws.estimate.predictor_arguments): the taps, evaluated in the kernel."""
+        return dict(pixel_filter=np.asarray(self.kernel)[..., ::-1])
+
 
 def get_filter_estimator(*args, **kw) -> typing.Callable:
     return FilterEstimator(get_coefficients(*args, **kw))

@@ -15,7 +15,7 @@ The 3x3 counterparts and their 8-tap file format are ws_unet_amd.ols; moderated 
     image under attack), 'OLSa5x5s' (5 parameters), and every name loaded from a 5x5 kernels file (`load_kernels`, the drivers'
     --kernels5), which `python -m ws_unet_amd.ols5` writes as {"OLS5x5": [24 floats]} / "OLS5x5s".
 
-A fit is valid iff the matrix of the solved system is positive definite and its condition number is at most 1e12 (ols.COND_MAX);
+A fit is valid iff the matrix of the solved system is positive definite and its condition number is at most 1e12 (lsq.COND_MAX);
 otherwise the taps are KB's, embedded in the 24, and ok is False.
 
 NOT checked: the symmetric pattern is Ker and Boehme's as remembered, and nothing here was compared with their implementation.
@@ -24,19 +24,13 @@ NOT checked: the symmetric pattern is Ker and Boehme's as remembered, and nothin
 """
 from __future__ import annotations
 
-import collections
-import json
-import logging
-import pathlib
-
 import numpy as np
 
-from . import filters
-from .ols import ADAPTIVE_NAMES as _OLS3_NAMES, COND_MAX
-from .planes import load_planes_u8, plane_groups, upload_planes
+from . import filters, lsq
+from .lsq import DatasetFit                                  # (also a name of this module)
+from .ols import ADAPTIVE_NAMES as _OLS3_NAMES
 
 TAPS, VARS, MOMENTS = 24, 25, 325
-_IU = np.triu_indices(VARS)
 # (dr, dc) of tap k: the 5x5 raster without its centre
 OFFSETS = [(a - 2, b - 2) for a in range(5) for b in range(5) if (a, b) != (2, 2)]
 CLASSES = ((0, 1), (1, 1), (0, 2), (1, 2), (2, 2))           # unordered (|dr|,|dc|): the five parameters of the symmetric fit
@@ -58,55 +52,6 @@ def _kb() -> np.ndarray:
     return embed3x3(filters.NAMED_FILTERS_2D["KB"][::-1, ::-1, 0])
 
 
-def unpack(moments):
-    """(325,) or (N,325) integer moments -> (A (...,24,24), b (...,24), yty (...)) float64.  Float64 holds integers up to 2^53 exactly;
-    a larger entry raises."""
-    m = np.asarray(moments)
-    if m.dtype.kind not in "iu" or m.shape[-1] != MOMENTS or m.ndim not in (1, 2):
-        raise ValueError(f"expected integer moments of shape ({MOMENTS},) or (N,{MOMENTS}), got {m.dtype} {m.shape}")
-    if m.size and (m.min() < 0 or m.max() > 2 ** 53):
-        raise OverflowError("a moment outside [0, 2^53] is not exact in float64")
-    full = np.zeros(m.shape[:-1] + (VARS, VARS))
-    full[..., _IU[0], _IU[1]] = m
-    full[..., _IU[1], _IU[0]] = m
-    return full[..., :TAPS, :TAPS], full[..., :TAPS, TAPS], full[..., TAPS, TAPS]
-
-
-def _solve(A, b, symmetric):
-    S = SYMMETRIC if symmetric else None
-    if symmetric:
-        A, b = S.T @ A @ S, S.T @ b
-    try:
-        np.linalg.cholesky(A)
-        if not np.linalg.cond(A) <= COND_MAX:
-            raise np.linalg.LinAlgError
-        k = np.linalg.solve(A, b)
-    except np.linalg.LinAlgError:
-        return _kb(), False
-    if not np.all(np.isfinite(k)):
-        return _kb(), False
-    return (S @ k if symmetric else k), True
-
-
-def fit(moments, symmetric: bool = False):
-    """Least-squares taps of one row of moments -> (taps (24,) float64, ok), or of every row of (N,325) -> ((N,24), ok (N,) bool).
-    numpy.linalg.solve on the normal equations, no intercept.  symmetric=True fits the five class parameters (A and b folded with the
-    24x5 indicator matrix, S^T A S and S^T b) and expands them to 24 taps; validity is then judged on the folded 5x5 system, the one that
-    is solved.  An invalid fit returns KB's taps embedded in the 24 and ok False."""
-    A, b, _ = unpack(moments)
-    if A.ndim == 2:
-        return _solve(A, b, symmetric)
-    res = [_solve(Ai, bi, symmetric) for Ai, bi in zip(A, b)]
-    return np.array([r[0] for r in res]).reshape(len(res), TAPS), np.array([r[1] for r in res], dtype=bool)
-
-
-def residual_mse(moments, taps, count):
-    """Mean squared residual of y - X k over the `count` pixels the moments were summed over: (yty - 2 k.b + k.A.k) / count."""
-    A, b, yty = unpack(moments)
-    k = np.asarray(taps, dtype=np.float64).reshape(TAPS)
-    return (yty - 2. * (b @ k) + k @ A @ k) / count
-
-
 # ---- files and registry -----------------------------------------------------------------------------------------------------------
 
 def register_kernel(name: str, taps) -> None:
@@ -120,29 +65,20 @@ def register_kernel(name: str, taps) -> None:
     KERNELS[name] = k
 
 
-def save_kernels(path, kernels) -> None:
-    """{name: taps} -> JSON {"OLS5x5": [24 floats], ...}; Python's float repr round-trips exactly."""
-    out = {str(name): [float(t) for t in np.asarray(taps, dtype=np.float64).reshape(TAPS)] for name, taps in kernels.items()}
-    path = pathlib.Path(path)
-    path.parent.mkdir(parents=True, exist_ok=True)
-    path.write_text(json.dumps(out, indent=1) + "\n")
+def _show(name, taps) -> str:
+    with np.printoptions(precision=6, suppress=True, linewidth=140):
+        return f"{name} taps (5x5 raster, the centre left out):\n{np.insert(taps, 12, np.nan).reshape(5, 5)}"
 
 
-def load_kernels(path, register: bool = False) -> dict:
-    """The {name: taps (24,) float64} of a save_kernels file; register=True enters every one as a model name."""
-    raw = json.loads(pathlib.Path(path).read_text())
-    if not isinstance(raw, dict):
-        raise ValueError(f"{path}: expected a JSON object of name -> {TAPS} taps")
-    kernels = {}
-    for name, taps in raw.items():
-        k = np.asarray(taps, dtype=np.float64)
-        if k.shape != (TAPS,):
-            raise ValueError(f"{path}: {name!r} has shape {k.shape}, expected {TAPS} taps")
-        kernels[name] = k
-    if register:
-        for name, k in kernels.items():
-            register_kernel(name, k)
-    return kernels
+# the 5x5 window: 24 neighbours and the centre, 325 moments.  lsq.Window has the fit; `fit` returns (taps (24,) float64, ok) and with
+# symmetric=True fits the five class parameters of SYMMETRIC, judged on the folded 5x5 system; an invalid fit returns KB's taps embedded
+# in the 24; load_kernels(register=True) enters a kernel file's {"OLS5x5": [24 taps], ...} as model names (`register_kernel`)
+WINDOW = lsq.Window(vars=VARS, symmetric=SYMMETRIC, kb=_kb, moments_op="ols_moments5", margin=2, register=register_kernel,
+                    size="5x5", label="OLS 5x5", entries=("OLS5x5", "OLS5x5s"), file="kernels5.json",
+                    symmetric_help="five parameters, one per (|dr|,|dc|) class", show=_show)
+unpack, fit, residual_mse = WINDOW.unpack, WINDOW.fit, WINDOW.residual_mse
+save_kernels, load_kernels = WINDOW.save_kernels, WINDOW.load_kernels
+fit_dataset, main = WINDOW.fit_dataset, WINDOW.main
 
 
 def add_kernels_argument(ap) -> None:
@@ -184,12 +120,6 @@ class Predictor5x5:
                 raise ValueError(f"Predictor5x5: {TAPS} finite taps expected, got shape {self.taps.shape}")
         self.fallbacks = 0
 
-    def note(self, ok) -> None:
-        bad = int(np.size(ok) - np.count_nonzero(ok))
-        if bad and not self.fallbacks:
-            logging.warning("OLS 5x5 fit: singular or ill-conditioned normal equations; such images are predicted with KB")
-        self.fallbacks += bad
-
     def image_taps(self, x_u8):
         """(N,H,W) uint8 device planes -> float32 device taps: (24,) fixed, (N,24) fitted per image."""
         import torch
@@ -197,7 +127,7 @@ class Predictor5x5:
         if not self.adaptive:
             return torch.from_numpy(self.taps.astype(np.float32)).to(x_u8.device)
         taps, ok = fit(ops.ols_moments5(x_u8).cpu().numpy(), self.symmetric)
-        self.note(ok)
+        WINDOW.note(self, ok)
         return torch.from_numpy(np.ascontiguousarray(taps, dtype=np.float32)).to(x_u8.device)
 
     def planes(self, x_u8, want_bias: bool = False):
@@ -206,6 +136,13 @@ class Predictor5x5:
             raise ValueError(f"the 5x5 predictor needs (N,H,W) planes of at least 5 x 5 pixels, got {tuple(x_u8.shape)}")
         from . import ops
         return ops.predict5x5(x_u8, self.image_taps(x_u8), want_bias)
+
+    def device_arguments(self, x_u8, correct_bias: bool = False) -> dict:
+        """The statistic kernels' keywords (ws.estimate.predictor_arguments): K57's full frames in pixel units, with their own x_bias."""
+        if not correct_bias:
+            return dict(x_hat=self.planes(x_u8), hat_scale=1.0)
+        x_hat, x_bias = self.planes(x_u8, want_bias=True)
+        return dict(x_hat=x_hat, x_bias=x_bias, hat_scale=1.0)
 
     def __call__(self, x: np.ndarray) -> np.ndarray:
         import torch
@@ -220,58 +157,6 @@ def estimator(model_name: str):
     if model_name in ADAPTIVE_NAMES:
         return Predictor5x5(adaptive=True, symmetric=ADAPTIVE_NAMES[model_name])
     return Predictor5x5(KERNELS[model_name]) if model_name in KERNELS else None
-
-
-# ---- one fit for a data set ----------------------------------------------------------------------------------------------------------
-
-DatasetFit = collections.namedtuple("DatasetFit", "taps ok moments count")
-
-
-def fit_dataset(data_dir, split: str = None, take_num_images: int = None, symmetric: bool = False, batch_size: int = 32) -> DatasetFit:
-    """One fit over the cover images of a data set (fabrika's precovers; `split`, `take_num_images` as everywhere): the batched
-    iterator with the native PNG decode one chunk ahead, one ols_moments5 launch per chunk, the rows summed as int64 on the device and
-    read back once.  -> DatasetFit(taps (24,) float64, ok, moments (325,) int64, count = pixels summed).  Single process."""
-    from . import fabrika, ops
-    total, count = [None], [0]
-
-    def chunk(fnames, kws, prefetched=None):
-        for g, _ in plane_groups(fnames, prefetched):             # (a ragged chunk: image by image)
-            m = ops.ols_moments5(upload_planes(g, "cuda")).sum(dim=0)
-            total[0] = m if total[0] is None else total[0] + m
-            count[0] += g.shape[0] * (g.shape[1] - 4) * (g.shape[2] - 4)
-        return [None] * len(fnames)
-
-    chunk.prefetch = lambda fnames, kws: (load_planes_u8(fnames),)
-    fabrika.precovers(iterator="batched", convert_to=None, ignore_missing=True, batch_size=batch_size)(chunk)(
-        data_dir, split=split, take_num_images=take_num_images)
-    moments = total[0].cpu().numpy()
-    taps, ok = fit(moments, symmetric)
-    return DatasetFit(taps, ok, moments, count[0])
-
-
-def main(argv=None) -> None:
-    import argparse
-    ap = argparse.ArgumentParser(description="fit a least-squares 5x5 pixel predictor on the cover images of a data set")
-    ap.add_argument("--data", required=True, help="dataset root with images*/files.csv (the reference's ../data)")
-    ap.add_argument("--split", default=None, help="split file under --data, e.g. split_tr.csv (default: every cover)")
-    ap.add_argument("--take", type=int, default=None, help="the first N images")
-    ap.add_argument("--symmetric", action="store_true", help="five parameters, one per (|dr|,|dc|) class; the entry is named OLS5x5s")
-    ap.add_argument("--out", required=True, help="kernels5.json; an existing file keeps its other entries")
-    a = ap.parse_args(argv)
-    logging.basicConfig(level=logging.INFO)
-    res = fit_dataset(a.data, split=a.split, take_num_images=a.take, symmetric=a.symmetric)
-    name = "OLS5x5s" if a.symmetric else "OLS5x5"
-    if not res.ok:
-        logging.warning(f"{name}: singular or ill-conditioned normal equations; writing KB's taps")
-    out = pathlib.Path(a.out)
-    kernels = load_kernels(out) if out.exists() else {}
-    kernels[name] = res.taps
-    save_kernels(out, kernels)
-    with np.printoptions(precision=6, suppress=True, linewidth=140):
-        print(f"{name} taps (5x5 raster, the centre left out):\n{np.insert(res.taps, 12, np.nan).reshape(5, 5)}")
-    print(f"{name} residual mse {residual_mse(res.moments, res.taps, res.count):.6f}   "
-          f"KB residual mse {residual_mse(res.moments, _kb(), res.count):.6f}   over {res.count} pixels")
-    print(f"output saved to {out}")
 
 
 if __name__ == "__main__":

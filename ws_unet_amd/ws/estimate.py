@@ -33,11 +33,11 @@ import typing
 import numpy as np
 import torch
 
-from .. import fabrika, filters, ols, ols5, ops
+from .. import fabrika, filters, ops
 from ..imread import imread4_u8, u8_plane
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import check_unet_geometry, model_device, unet_plane
-from . import adaptive, jpeg, sequential, structural
+from . import adaptive, jpeg, predictors, sequential, structural
 
 NAMED_FILTERS = filters.NAMED_FILTERS_2D
 
@@ -52,6 +52,13 @@ class UNetEstimator:
     def __call__(self, x: np.ndarray) -> np.ndarray:
         from ..evaluate import infere_single
         return infere_single(x, model=self.model)
+
+    def device_arguments(self, x_u8: torch.Tensor, correct_bias: bool = False) -> dict:
+        """The statistic kernels' keywords (`predictor_arguments`): the full-frame output stays on the device, scale 255; with
+        correct_bias also the network applied to x_bar - x."""
+        check_unet_geometry(x_u8.shape[1:], "the UNet estimator")
+        y, yb = _unet_planes(self.model, x_u8, correct_bias)
+        return dict(x_hat=y, hat_scale=255.0) | ({"x_bias": yb} if correct_bias else {})
 
     def __reduce__(self):
         # the reference ships its CPU predictor into joblib / loky workers (ws/estimate.py:139); a GPU model must not travel
@@ -99,29 +106,13 @@ def _unet_planes(model, x_u8: torch.Tensor, correct_bias: bool):
 
 
 def predictor_arguments(x_u8: torch.Tensor, pixel_estimator, host_planes=None, correct_bias: bool = False) -> dict:
-    """A pixel predictor as the keywords the statistic kernels take (ops.ws_attack, ops.ws_sequential, ops.ws_residual_accumulate):
-    `pixel_filter` for a filters.FilterEstimator (evaluated in the kernel) and an ols.AdaptiveOLSEstimator (moments -> float64 fit on the
-    host -> one filter per image); `x_hat` with `hat_scale` for a UNetEstimator (the full-frame output stays on the device, scale 255)
-    and for any other callable (the reference's call pattern on `host_planes`, one image at a time; interior layout, scale 1); `x_hat`
-    with scale 1 for a jpeg.JPEGEstimator (history search and round trip on the device, full frames in pixel units) and for an
-    ols5.Predictor5x5 (moments -> float64 fit on the host -> K57's full frames in pixel units, with its own `x_bias` plane).  With
-    correct_bias also `x_bias`, the predictor applied to x_bar - x, where the predictor has one outside the kernel."""
-    if isinstance(pixel_estimator, UNetEstimator):
-        check_unet_geometry(x_u8.shape[1:], "the UNet estimator")
-        y, yb = _unet_planes(pixel_estimator.model, x_u8, correct_bias)
-        return dict(x_hat=y, hat_scale=255.0) | ({"x_bias": yb} if correct_bias else {})
-    if isinstance(pixel_estimator, filters.FilterEstimator):
-        return dict(pixel_filter=np.asarray(pixel_estimator.kernel)[..., ::-1])
-    if isinstance(pixel_estimator, ols.AdaptiveOLSEstimator):
-        return dict(pixel_filter=pixel_estimator.kernels(x_u8)[..., ::-1])
-    if isinstance(pixel_estimator, jpeg.JPEGEstimator):
-        _require_no_bias_correction(pixel_estimator, correct_bias)
-        return dict(x_hat=pixel_estimator.planes(x_u8), hat_scale=1.0)
-    if isinstance(pixel_estimator, ols5.Predictor5x5):
-        if not correct_bias:
-            return dict(x_hat=pixel_estimator.planes(x_u8), hat_scale=1.0)
-        x_hat, x_bias = pixel_estimator.planes(x_u8, want_bias=True)
-        return dict(x_hat=x_hat, x_bias=x_bias, hat_scale=1.0)
+    """A pixel predictor as the keywords the statistic kernels take (ops.ws_attack, ops.ws_sequential, ops.ws_residual_accumulate): what
+    its `device_arguments(x_u8, correct_bias)` returns, if it has that method -- every estimator listed in ws/predictors.py and the
+    UNetEstimator do: `pixel_filter` (evaluated in the kernel), or a full-frame `x_hat` with its `hat_scale` and, with correct_bias, the
+    `x_bias` plane of the predictor applied to x_bar - x.  Any other callable is called on `host_planes` in the reference's call pattern,
+    one image at a time: `x_hat` (and `x_bias`) in interior layout, scale 1."""
+    if hasattr(pixel_estimator, "device_arguments"):
+        return pixel_estimator.device_arguments(x_u8, correct_bias)
     if host_planes is None:
         raise ValueError(f"a host predictor ({type(pixel_estimator).__name__}) needs the planes on the host (host_planes)")
     hats, biases = [], []
@@ -168,16 +159,11 @@ def _stat(x_u8: torch.Tensor, pixel_estimator, mean_estimator, weighted, correct
     return jpeg.without_estimate(beta, pred["x_hat"]) if isinstance(pixel_estimator, jpeg.JPEGEstimator) else beta
 
 
-def _require_no_bias_correction(pixel_estimator, correct_bias) -> None:
-    if correct_bias and isinstance(pixel_estimator, jpeg.JPEGEstimator):
-        raise ValueError("correct_bias=True is not defined for the JPEG predictor: it is not linear, so there is no prediction of x_bar - x")
-
-
 def _check_options(pixel_estimator, weighted, correct_bias, placement="random", order="rows", criterion="hill", flip_rate=1.0) -> None:
     """An option an estimator does not have is the caller's error, not an image without an estimate (`attack` turns a ValueError of
     the statistic into beta_hat = None, as the reference does)."""
     sequential.check_placement(placement, order)
-    _require_no_bias_correction(pixel_estimator, correct_bias)
+    jpeg.require_no_bias_correction(pixel_estimator, correct_bias)
     if placement == "adaptive":
         adaptive.check_options(criterion, flip_rate)
     if placement in ("sequential", "adaptive"):
@@ -246,8 +232,7 @@ def attack_stego(*args, **kw):
 
 def _native_planes_ok(channels, pixel_estimator, imread, process_image) -> bool:
     """The default gray pipeline (Y plane, built-in predictor) needs no host arrays: native batched decode -> pinned buffer -> device."""
-    builtin = isinstance(pixel_estimator, (UNetEstimator, filters.FilterEstimator, ols.AdaptiveOLSEstimator, structural.StructuralEstimator,
-                                           jpeg.JPEGEstimator, ols5.Predictor5x5))
+    builtin = hasattr(pixel_estimator, "device_arguments") or isinstance(pixel_estimator, structural.StructuralEstimator)
     plain = process_image is None or getattr(process_image, "plane_selector", None) == (3,)
     return builtin and imread is imread4_u8 and plain and tuple(channels) == (3,)
 
@@ -298,6 +283,16 @@ attack_cover_batched = fabrika.precovers(iterator="batched", ignore_missing=True
 attack_stego_batched = fabrika.stego_spatial(iterator="batched", ignore_missing=True)(fabrika.shared_kwargs(attack_batch, _ATTACK_KEYS, _prefetch_native))
 
 
+def resolve_predictor(model_name: str, model_path, channels):
+    """A model name as (estimator, the name its rows carry): a name of ws/predictors.py under itself, any other as the trained UNet run
+    `model_name` under `model_path`, whose rows are named 'UNet'."""
+    estimator = predictors.by_name(model_name)
+    if estimator is not None:
+        return estimator, model_name
+    from .. import get_unet_estimator
+    return get_unet_estimator(model_path=model_path, model_name=model_name, channels=channels), "UNet"
+
+
 def run(
     input_dir: pathlib.Path,
     stego_method: str,
@@ -316,22 +311,8 @@ def run(
     process_cover = filters.get_processor_2d(channels=channels)
     placed = (kw.get("placement", "random"), kw.get("order", "rows"), kw.get("criterion", "hill"), kw.get("flip_rate", 1.0))
     _check_options(None, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
-    if model_name in structural.NAMES:
-        pixel_estimator = structural.StructuralEstimator(model_name)
-        _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
-    elif model_name in ols.ADAPTIVE_NAMES:                       # 'OLSa' / 'OLSa2': the least-squares filter of each image under attack
-        pixel_estimator = ols.adaptive_estimator(model_name)
-    elif ols5.estimator(model_name) is not None:                 # 'OLSa5x5' / 'OLSa5x5s' and the names of a --kernels5 file: 5x5 least squares
-        pixel_estimator = ols5.estimator(model_name)
-    elif model_name in jpeg.NAMES:                               # 'JPEG': each image after a round trip through its own quantisation table
-        pixel_estimator = jpeg.estimator(model_name)
-        _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
-    elif model_name in NAMED_FILTERS:
-        pixel_estimator = filters.get_filter_estimator(filter_name=model_name, flatten=False)
-    else:
-        from .. import get_unet_estimator
-        pixel_estimator = get_unet_estimator(model_path=model_path, model_name=model_name, channels=channels)
-        model_name = "UNet"
+    pixel_estimator, model_name = resolve_predictor(model_name, model_path, channels)
+    _check_options(pixel_estimator, kw.get("weighted", 1), kw.get("correct_bias", False), *placed)
     if stego_method:
         fn = attack_stego_batched if batched else attack_stego
         kw_attack = {"stego_method": stego_method, "alpha": alpha}
@@ -364,8 +345,7 @@ def parse_args(argv=None):
     ap.add_argument("--stego-methods", nargs="*", default=["LSBR"])
     ap.add_argument("--alphas", nargs="*", type=float, default=[.4, .2, .1])
     ap.add_argument("--filters", nargs="*", default=["AVG", "KB"],
-                    help="named filters, the adaptive 'OLSa' / 'OLSa2' and 5x5 'OLSa5x5' / 'OLSa5x5s', the recompression predictor 'JPEG', and the structural estimators "
-                         "'SPA' / 'RS' (with --weighted 0)")
+                    help=predictors.filters_help(structural=True) + " (these with --weighted 0)")
     ap.add_argument("--losses", nargs="*", default=["l1", "l1ws"])
     ap.add_argument("--weighted", type=int, default=0)
     ap.add_argument("--correct-bias", action="store_true")
@@ -378,8 +358,7 @@ def parse_args(argv=None):
     ap.add_argument("--flip-rate", type=float, default=1.0,
                     help="adaptive placement: the probability that a used pixel was flipped (1: HILLR flips every used pixel; 0.5: a real message)")
     ap.add_argument("--out", default=None)
-    ols.add_kernels_argument(ap)
-    ols5.add_kernels_argument(ap)
+    predictors.add_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -390,8 +369,7 @@ def main(argv=None) -> None:
     import pandas as pd
     from .. import get_model_name
     a = parse_args(argv)
-    ols.register_from_args(a)
-    ols5.register_from_args(a)
+    predictors.register_from_args(a)
     model_dir = pathlib.Path(a.model_dir)
     settings = [(None, .0)] + [(sm, al) for sm in a.stego_methods for al in a.alphas]
     common = dict(demosaic=None, channels=(3,), correct_bias=a.correct_bias, weighted=a.weighted, batched=not a.per_image)

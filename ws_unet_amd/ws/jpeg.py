@@ -114,11 +114,21 @@ class JPEGEstimator:
             x_hat[torch.from_numpy(~use).to(x_hat.device)] = float("nan")
         return x_hat
 
+    def device_arguments(self, x_u8: torch.Tensor, correct_bias: bool = False) -> dict:
+        """The statistic kernels' keywords (ws.estimate.predictor_arguments): full frames in pixel units; no prediction of x_bar - x."""
+        require_no_bias_correction(self, correct_bias)
+        return dict(x_hat=self.planes(x_u8), hat_scale=1.0)
+
     def __call__(self, x: np.ndarray) -> np.ndarray:
         from ..imread import u8_plane
         plane = u8_plane(np.asarray(x)[..., 0], "the JPEG predictor needs integer pixel values in 0..255")
         hat = self.planes(torch.from_numpy(np.ascontiguousarray(plane))[None].cuda())[0]
         return hat[1:-1, 1:-1].cpu().numpy()[..., None]
+
+
+def require_no_bias_correction(pixel_estimator, correct_bias) -> None:
+    if correct_bias and isinstance(pixel_estimator, JPEGEstimator):
+        raise ValueError("correct_bias=True is not defined for the JPEG predictor: it is not linear, so there is no prediction of x_bar - x")
 
 
 def without_estimate(beta: torch.Tensor, x_hat: torch.Tensor) -> torch.Tensor:

@@ -25,8 +25,8 @@ import typing
 import numpy as np
 import torch
 
-from .. import ols, ols5, ops
-from . import locate
+from .. import ops
+from . import locate, predictors
 
 CHUNK_KEYS = 1 << 22                                       # keys per launch when a range is walked
 NULL_KEYS = 4096                                           # two stages: candidates scanned over the whole frame for the z of the second stage
@@ -223,7 +223,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--out", required=True, help="the table (CSV)")
     ap.add_argument("--stego-method", default="LSBRK")
     ap.add_argument("--alpha", type=float, required=True, help="the payload of the images to read (names their folder)")
-    ap.add_argument("--filter", default="KB", help="the pixel predictor: a named filter, 'OLSa' / 'OLSa2' or 'JPEG'")
+    ap.add_argument("--filter", default="KB", help="one of the " + predictors.filters_help(structural=False))
     ap.add_argument("--first", type=_int, default=None, help="the first key of a range (decimal or 0x)")
     ap.add_argument("--count", type=_int, default=None, help="the number of keys of the range")
     ap.add_argument("--keys-file", default=None, help="candidate keys, one decimal or 0x integer per line")
@@ -234,8 +234,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--key", type=_int, default=None, help="the true key, if known: adds its score and rank")
     ap.add_argument("--weighted", type=int, choices=(0, 1), default=1)
     ap.add_argument("--per-image", action="store_true", help="use the per-image iterator instead of the batched one")
-    ols.add_kernels_argument(ap)
-    ols5.add_kernels_argument(ap)
+    predictors.add_arguments(ap)
     a = ap.parse_args(argv)
     if (a.keys_file is None) == (a.first is None and a.count is None) or (a.keys_file is None and (a.first is None or a.count is None)):
         ap.error("give either --first and --count or --keys-file")
@@ -244,8 +243,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 def main(argv=None) -> None:
     a = parse_args(argv)
-    ols.register_from_args(a)
-    ols5.register_from_args(a)
+    predictors.register_from_args(a)
     keys = read_keys_file(a.keys_file) if a.keys_file else None
     res = run(pathlib.Path(a.data), a.stego_method, a.alpha, a.filter, None, (3,), keys=keys, first=a.first, count=a.count,
               search_alpha=a.search_alpha, key=a.key, prefilter_rows=a.prefilter_rows, keep=a.keep, top=a.top, weighted=a.weighted,

@@ -24,11 +24,11 @@ import typing
 import numpy as np
 import torch
 
-from .. import fabrika, filters, ols, ols5, ops
+from .. import fabrika, filters, ops
 from ..imread import imread4_u8
 from ..planes import decode_pool, load_planes_u8, upload_planes
 from ..unet_run import model_device
-from . import estimate, jpeg, structural
+from . import estimate, predictors, structural
 
 MAX_IMAGES = ops.MAX_LOCATE_IMAGES
 THRESHOLD = 0.25                                           # halfway between the two expectations of the mean
@@ -98,9 +98,9 @@ class ResidualAccumulator:
 
     def add(self, x_u8: torch.Tensor, pixel_estimator, mean_estimator=estimate.NAMED_FILTERS["AVG"], weighted: int = 1,
             host_planes=None) -> "ResidualAccumulator":
-        """Adds the terms of the (N,H,W) uint8 device planes `x_u8` under a pixel predictor of ws.estimate (a filters.FilterEstimator, an
-        ols.AdaptiveOLSEstimator, a UNetEstimator -- its prediction never leaves the device -- or a host callable, which needs
-        `host_planes`).  Nothing waits for the GPU."""
+        """Adds the terms of the (N,H,W) uint8 device planes `x_u8` under a pixel predictor of ws.estimate: an estimator with
+        `device_arguments` (those listed in ws/predictors.py and a UNetEstimator; the prediction never leaves the device), or a host
+        callable, which needs `host_planes` (estimate.predictor_arguments).  Nothing waits for the GPU."""
         if int(weighted) not in (0, 1):
             raise ValueError(f"ResidualAccumulator.add: weighted must be 0 or 1, got {weighted}")
         if isinstance(pixel_estimator, structural.StructuralEstimator) or pixel_estimator is None:
@@ -206,20 +206,11 @@ _ITERATORS = {
 
 
 def pixel_predictor(model_name: str, model_path, channels):
-    """A named filter, 'OLSa' / 'OLSa2', a 5x5 predictor of ols5 ('OLSa5x5' / 'OLSa5x5s', a --kernels5 name), 'JPEG' or a trained UNet run as (pixel predictor, the name its rows carry); the structural estimators
-    have no per-pixel prediction and raise."""
+    """A pixel predictor's name in ws/predictors.py, or a trained UNet run, as (pixel predictor, the name its rows carry)
+    (estimate.resolve_predictor); the structural estimators have no per-pixel prediction and raise."""
     if model_name in structural.NAMES:
         raise ValueError(f"ws.locate needs a pixel predictor; the structural estimators {structural.NAMES} have none")
-    if model_name in ols.ADAPTIVE_NAMES:
-        return ols.adaptive_estimator(model_name), model_name
-    if ols5.estimator(model_name) is not None:
-        return ols5.estimator(model_name), model_name
-    if model_name in jpeg.NAMES:
-        return jpeg.estimator(model_name), model_name
-    if model_name in estimate.NAMED_FILTERS:
-        return filters.get_filter_estimator(filter_name=model_name, flatten=False), model_name
-    from .. import get_unet_estimator
-    return get_unet_estimator(model_path=model_path, model_name=model_name, channels=channels), "UNet"
+    return estimate.resolve_predictor(model_name, model_path, channels)
 
 
 def walk(input_dir, stego_method, alpha, pixel_estimator, channels=(3,), weighted: int = 1, at=(), batched: bool = True,
@@ -276,7 +267,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--stego-method", default="LSBRK")
     ap.add_argument("--alpha", type=float, required=True)
-    ap.add_argument("--filters", nargs="*", default=["AVG", "KB"], help="named filters, the adaptive 'OLSa' / 'OLSa2' and 5x5 'OLSa5x5' / 'OLSa5x5s', and the recompression predictor 'JPEG'")
+    ap.add_argument("--filters", nargs="*", default=["AVG", "KB"], help=predictors.filters_help(structural=False))
     ap.add_argument("--model-dir", default=None, help="trained UNets in the reference's layout <dir>/<train method>/<run>/; no UNet rows without it")
     ap.add_argument("--losses", nargs="*", default=["l1ws"], help="UNet runs under --model-dir: 'l1' (the dropout run), 'l1ws' (--train-method)")
     ap.add_argument("--train-method", default="LSBR", help="stego method the l1ws UNet was trained on")
@@ -284,8 +275,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--key", type=int, default=None, help="the stego key of LSBRK images: adds the confusion counts against its positions")
     ap.add_argument("--at", type=int, nargs="*", default=[], help="image counts at which a decision is taken, beside the whole set")
     ap.add_argument("--per-image", action="store_true", help="use the per-image iterator instead of the batched one")
-    ols.add_kernels_argument(ap)
-    ols5.add_kernels_argument(ap)
+    predictors.add_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -293,8 +283,7 @@ def main(argv=None) -> None:
     import pandas as pd
     from PIL import Image
     a = parse_args(argv)
-    ols.register_from_args(a)
-    ols5.register_from_args(a)
+    predictors.register_from_args(a)
     jobs = [(name, name, None) for name in a.filters]
     if a.model_dir:
         from .. import get_model_name

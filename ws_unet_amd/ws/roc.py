@@ -35,7 +35,7 @@ from .. import filters as filters_lib
 from ..imread import imread4_u8
 from ..planes import load_planes_u8, upload_planes
 from ..unet_run import model_device
-from . import adaptive, jpeg, sequential, structural
+from . import adaptive, predictors, sequential, structural
 
 TAUS = np.linspace(0, 1, 501, endpoint=True)       # ascending; the reference walks them reversed
 AUC_COLUMNS = ["stego_method", "model_name", "auc", "p_e", "tau0", "fpr_tau0", "tpr_tau0", "fpr_50", "tpr_50"]
@@ -214,16 +214,7 @@ def collect_ws_scores(input_dir, stego_methods: typing.Sequence[str] = STEGO_MET
     Other keywords go to the fabrika iterators (take_num_images, split, ...)."""
     import pandas as pd
     from . import estimate
-    from .. import ols, ols5
-    names = list(filters)
-    for name in names:
-        if name not in estimate.NAMED_FILTERS and name not in ols.ADAPTIVE_NAMES and name not in structural.NAMES and name not in jpeg.NAMES \
-                and name not in ols5.names():
-            raise ValueError(f"unknown filter {name!r}; choose from "
-                             f"{sorted(estimate.NAMED_FILTERS) + sorted(ols.ADAPTIVE_NAMES) + ols5.names() + sorted(jpeg.NAMES) + sorted(structural.NAMES)}")
-    preds = [(name, structural.StructuralEstimator(name) if name in structural.NAMES else
-              ols.adaptive_estimator(name) or ols5.estimator(name) or jpeg.estimator(name) or filters_lib.get_filter_estimator(filter_name=name, flatten=False))
-             for name in names]
+    preds = [(name, predictors.require(name)) for name in filters]
     est = estimate.as_unet_estimator(unet, mode)
     if est is not None:
         preds.append(("UNet", est))
@@ -287,7 +278,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--stego-methods", nargs="*", default=list(STEGO_METHODS))
     ap.add_argument("--alphas", nargs="+", type=float, default=list(ALPHAS),
                     help="pooled into one curve per stego method; the LAST one names the output files")
-    ap.add_argument("--filters", nargs="*", default=list(WS_FILTERS), help="named filters of filters.NAMED_FILTERS_2D, 'OLSa' / 'OLSa2', the 5x5 'OLSa5x5' / 'OLSa5x5s', the recompression predictor 'JPEG', and the structural estimators 'SPA' / 'RS'")
+    ap.add_argument("--filters", nargs="*", default=list(WS_FILTERS), help=predictors.filters_help(structural=True))
     ap.add_argument("--scores", nargs=2, action="append", default=[], metavar=("FILE", "NAME"),
                     help="detector scores in the schema of results/detection/b0.csv (the `output` column; covers have an empty "
                          "stego_method) added as model NAME, which must contain 'B0'; repeatable")
@@ -300,10 +291,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--criterion", choices=adaptive.CRITERIA, default="hill", help="adaptive placement: the cost that orders the pixels")
     ap.add_argument("--flip-rate", type=float, default=1.0,
                     help="adaptive placement: the probability that a used pixel was flipped (1: HILLR flips every used pixel; 0.5: a real message)")
-    from .. import ols5
-    from ..ols import add_kernels_argument
-    add_kernels_argument(ap)
-    ols5.add_kernels_argument(ap)
+    predictors.add_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -311,10 +299,7 @@ def main(argv=None) -> None:
     import pandas as pd
     a = parse_args(argv)
     logging.basicConfig(level=logging.INFO)
-    from .. import ols5
-    from ..ols import register_from_args
-    register_from_args(a)
-    ols5.register_from_args(a)
+    predictors.register_from_args(a)
     detectors = [load_scores(path, name, a.stego_methods, a.alphas) for path, name in a.scores]      # input errors before GPU work
     unet = None
     if a.model_dir:
