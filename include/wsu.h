@@ -515,6 +515,29 @@ int wsu_spa_tables(const uint8_t* x_u8, unsigned long long* tables, int n, int h
  *      then the same four on the plane with every LSB flipped (G ^ 1 element-wise in the place of G).  Exact integers. */
 int wsu_rs_counts(const uint8_t* x_u8, unsigned long long* counts, int n, int h, int w, void* stream);
 
+/* ---- K58: the histograms of the segments of a path (the chi-square attack of Westfeld, Pfitzmann, IH 1999, along the file order; not part
+ *      of the reference).  x_u8: (N,H,W) DEVICE pixels, any H, W >= 1 with H W < 2^32.  segments = S in 1..4096.  The path position of pixel
+ *      (r,c) is t = r W + c for order 0 ('rows') and t = (H-1-r) W + c for order 1 ('rows_up'), as in K27 / K28; the pixel belongs to
+ *      segment s = floor(t S / (H W)), the product in 64 bits, so segment s holds the positions ceil(s H W / S) .. ceil((s+1) H W / S) - 1
+ *      (none of them where S > H W leaves it empty).  table: DEVICE (N,S,256) uint64, zeroed on the stream by this call:
+ *        table[i][s][v] = pixels of image i in segment s with the value v.
+ *      S = 1 is the plain histogram; a prefix histogram is a cumulative sum over s, which the caller takes.  Exact integers, the same bits
+ *      on every run.  n in 1..65535; every argument is checked before any HIP call. */
+int wsu_hist_segments(const uint8_t* x_u8, unsigned long long* table, int n, int h, int w, int segments, int order, void* stream);
+
+/* ---- K59: the horizontal adjacency histogram (Ker, IEEE SPL 12(6), 2005; not part of the reference).  x_u8: (N,H,W) DEVICE pixels, any
+ *      H, W >= 1.  table: DEVICE (N,256,256) uint64, zeroed on the stream by this call:
+ *        table[i][u][v] = #{(r,c): c + 1 < W, x[r][c] = u, x[r][c+1] = v},
+ *      H (W - 1) pairs per image; W = 1 gives an all-zero table.  Exact integers, the same bits on every run.  n in 1..65535; every
+ *      argument is checked before any HIP call. */
+int wsu_adjacency_hist(const uint8_t* x_u8, unsigned long long* table, int n, int h, int w, void* stream);
+
+/* ---- K60: the 2 x 2 block mean, rounded down (Ker's calibration image; not part of the reference).  x_u8: (N,H,W) DEVICE pixels, H, W >= 2.
+ *      y_u8: DEVICE (N, H/2, W/2) uint8 in integer division (an odd last row or column is dropped):
+ *        y[i][r][c] = (x[i][2r][2c] + x[i][2r][2c+1] + x[i][2r+1][2c] + x[i][2r+1][2c+1]) >> 2.
+ *      n in 1..65535; every argument is checked before any HIP call. */
+int wsu_downsample2x2(const uint8_t* x_u8, uint8_t* y_u8, int n, int h, int w, void* stream);
+
 /* ---- K36: the co-occurrence counts of the subtractive pixel adjacency matrix (SPAM; Pevny, Bas, Fridrich, IEEE TIFS 5(2), 2010; not part
  *      of the reference).  x_u8: (N,H,W) DEVICE pixels, any H, W >= 1.  order in {1,2}; T in 1..8 at order 1, 1..4 at order 2; B = 2T + 1.
  *      A direction is a step (dr,dc); the four counted ones, in this index order: 0 (0,+1), 1 (+1,0), 2 (+1,+1), 3 (+1,-1).  In integers

@@ -110,6 +110,9 @@ SIGNATURES = {
     "wsu_spa_tables": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_rs_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_spam_counts": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "wsu_hist_segments": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "wsu_adjacency_hist": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "wsu_downsample2x2": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_srm_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_srm_minmax_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wsu_srm_fan_counts": (c_int, [_P, _P, c_int, c_int, c_int, _P]),

@@ -1340,6 +1340,41 @@ def rs_counts(x_u8: torch.Tensor) -> torch.Tensor:
     return _count_entry("rs_counts", x_u8, (8,))
 
 
+HIST_MAX_SEGMENTS = 4096
+
+
+def hist_segments(x_u8: torch.Tensor, segments: int = 1, order="rows") -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,S,256) int64, S = segments in 1..4096: the histogram of every one of S consecutive segments of the path.
+    The path position of pixel (r,c) is t = r W + c for order 'rows' and t = (H-1-r) W + c for 'rows_up' (ORDERS, as in the sequential
+    WS statistic); the pixel belongs to segment floor(t S / (H W)), so segment s holds the positions ceil(s H W / S) ..
+    ceil((s+1) H W / S) - 1 and is empty where S > H W leaves it none.  segments=1 is the plain histogram; a prefix histogram is
+    `.cumsum(1)` (wsu_hist_segments, K58; ws_unet_amd.histogram makes the chi-square curve)."""
+    if isinstance(segments, bool) or int(segments) != segments or not 1 <= segments <= HIST_MAX_SEGMENTS:
+        raise ValueError(f"hist_segments: segments={segments!r} outside 1..{HIST_MAX_SEGMENTS}")
+    return _count_entry("hist_segments", x_u8, (int(segments), 256), after=(int(segments), order_id(order)))
+
+
+def adjacency_hist(x_u8: torch.Tensor) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8 -> (N,256,256) int64: A[u][v] = the number of (r,c) with c + 1 < W, x[r,c] = u and x[r,c+1] = v, the
+    horizontally adjacent pairs only (Ker's adjacency histogram); H (W-1) pairs per image, all zero for W = 1 (wsu_adjacency_hist, K59)."""
+    return _count_entry("adjacency_hist", x_u8, (256, 256))
+
+
+def downsample2x2(x_u8: torch.Tensor) -> torch.Tensor:
+    """x_u8: (N,H,W) uint8, H, W >= 2 -> (N,H//2,W//2) uint8: every output pixel is the sum of its 2 x 2 block divided by 4 and rounded
+    down; an odd last row or column is dropped (wsu_downsample2x2, K60: Ker's calibration image)."""
+    n, h, w = _u8_planes(x_u8)
+    if n == 0:
+        raise ValueError("downsample2x2: no images")
+    if h < 2 or w < 2:
+        raise ValueError(f"downsample2x2: planes of {h} x {w} pixels are too small (H, W >= 2)")
+    lib = _lib.load()
+    y = torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=x_u8.device)
+    check(_launch("downsample2x2", {"bytes": float(n * h * w + y.numel())}, lambda: lib.wsu_downsample2x2(
+        x_u8.data_ptr(), y.data_ptr(), n, h, w, _stream())), "wsu_downsample2x2")
+    return y
+
+
 def spam_bins(order: int, T: int) -> int:
     """B^(order+1), B = 2T + 1: the bins of one direction of the SPAM counts; the (order, T) that K36 takes, else ValueError."""
     if order not in (1, 2) or isinstance(T, bool) or int(T) != T or not 1 <= T <= (8 if order == 1 else 4):

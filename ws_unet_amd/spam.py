@@ -205,21 +205,28 @@ def _prefetch(fnames, kws):
     return (load_planes_u8(fnames),)
 
 
-def _submit(fnames, clean, *, order, T, twin=None, prefetched=None):
-    """Upload the chunk's Y planes once, make their twins when asked (twin = (method, alpha, stream)), queue K36; nothing waits for the GPU."""
-    from . import embed, embed_pm1, ops
+def device_planes(fnames, twin=None, prefetched=None):
+    """The chunk's Y planes on the device, uploaded once: one (x, names) per group of files of one shape.  twin = (method, alpha, stream):
+    their twins instead, made on the device with the seeds embed.image_seed(file, stream) ('HILLR' takes none); a fourth entry is the
+    path order of 'LSBRS'.  Nothing waits for the GPU.  (Shared with ws_unet_amd.histogram.)"""
+    from . import embed, embed_pm1
     from .planes import plane_groups, upload_planes
-    counts = []
     for planes, names in plane_groups(fnames, prefetched):
         x = upload_planes(planes, "cuda")
         if twin is not None:
-            method, alpha, stream = twin
+            method, alpha, stream, *path = twin
+            seeds = [embed.image_seed(f, stream) for f in names]
             if method in embed_pm1.METHODS:
-                x = embed_pm1.simulate(x, method, alpha, [embed.image_seed(f, stream) for f in names])[0]
+                x = embed_pm1.simulate(x, method, alpha, seeds)[0]
             else:
-                x = embed.simulate(x, method, alpha, [embed.image_seed(f, stream) for f in names] if method != "HILLR" else None)[0]
-        counts.append(ops.spam_counts(x, order, T))
-    return clean, counts
+                x = embed.simulate(x, method, alpha, seeds if method != "HILLR" else None, **({"order": path[0]} if path else {}))[0]
+        yield x, names
+
+
+def _submit(fnames, clean, *, order, T, twin=None, prefetched=None):
+    """Upload the chunk's Y planes once, make their twins when asked (twin = (method, alpha, stream)), queue K36; nothing waits for the GPU."""
+    from . import ops
+    return clean, [ops.spam_counts(x, order, T) for x, _ in device_planes(fnames, twin, prefetched)]
 
 
 def _collect(handle):
@@ -241,6 +248,39 @@ def _iterators(batch_size: int):
     return fabrika.precovers(**kw)(_count_chunk), fabrika.stego_spatial(**kw)(_count_chunk)
 
 
+def file_set(covers, stegos, data_dir, stego_method, alpha, simulate, stream, *, simulated=SIMULATED, twin_order=None, **shared):
+    """The rows of one image set from a pair of fabrika iterators over one chunk function: the covers (stego_method None), the files of one
+    stego folder, or with simulate=True the covers again with twin=(method, alpha, stream) for the chunk function and their rows named as
+    the simulator's write_dataset would name the files.  simulated: the methods simulate=True may make; twin_order: the path order of
+    'LSBRS' twins, a fourth entry of `twin`.  (Shared with ws_unet_amd.histogram.)"""
+    from . import embed, embed_pm1
+    if stego_method is None:
+        return covers(data_dir, **shared)
+    if simulate:
+        maker = embed_pm1 if str(stego_method).upper() in embed_pm1.METHODS else embed
+        method = maker.method_name(stego_method)
+        if method not in simulated:
+            raise ValueError(f"simulate=True makes {' / '.join(simulated)} twins only, not {stego_method!r}")
+        path = () if twin_order is None else (twin_order,)
+        folder = maker.folder_name(method, alpha, *path)
+        return [{**r, "name": f"{folder}/{pathlib.Path(r['name']).stem}.png", "stego_method": method, "alpha": float(alpha)}
+                for r in covers(data_dir, twin=(method, float(alpha), int(stream), *path), **shared)]
+    try:
+        return stegos(data_dir, stego_method=stego_method, alpha=alpha, **shared)
+    except KeyError as e:
+        raise ValueError(f"split {shared.get('split')!r} lists no stego rows (no {e.args[0]!r} column): use simulate=True or a split that names them") from e
+
+
+def file_rows(res, drop=()):
+    """the frame name, height, width, stego_method, alpha of the rows `res` without their `drop` entries (covers: NaN in the last two)"""
+    import pandas as pd
+    rows = pd.DataFrame([{k: v for k, v in r.items() if k not in drop} for r in res])
+    for col in ("stego_method", "alpha"):
+        if col not in rows:
+            rows[col] = np.nan
+    return rows[["name", "height", "width", "stego_method", "alpha"]]
+
+
 def extract(data_dir, stego_method: typing.Optional[str] = None, alpha: typing.Optional[float] = None, split: typing.Optional[str] = None,
             order: int = 2, T: int = 3, normalise: str = "joint", simulate: bool = False, stream: int = 0, batch_size: int = 32,
             progress_on: bool = False, **kw):
@@ -250,35 +290,14 @@ def extract(data_dir, stego_method: typing.Optional[str] = None, alpha: typing.O
     files ('LSBR' with embed.image_seed(file, stream), 'HILLR'; 'LSBM' and 'HILL' of embed_pm1 with the same seeds); their rows are named as
     embed.write_dataset / embed_pm1.write_dataset would name the files.
     Other keywords go to the fabrika iterators (take_num_images, shuffle_seed, ...)."""
-    import pandas as pd
-    from . import embed, embed_pm1
     bins(order, T)
     if normalise not in NORMALISE:
         raise ValueError(f"unknown normalise {normalise!r}; choose from {NORMALISE}")
     if (stego_method is None) != (alpha is None):
         raise ValueError("extract: give both stego_method and alpha, or neither (the covers)")
-    covers, stegos = _iterators(batch_size)
     shared = dict(order=order, T=T, split=split, progress_on=progress_on, **kw)
-    if stego_method is None:
-        res = covers(data_dir, **shared)
-    elif simulate:
-        maker = embed_pm1 if str(stego_method).upper() in embed_pm1.METHODS else embed
-        method = maker.method_name(stego_method)
-        if method not in SIMULATED:
-            raise ValueError(f"simulate=True makes {' / '.join(SIMULATED)} twins only, not {stego_method!r}")
-        folder = maker.folder_name(method, alpha)
-        res = [{**r, "name": f"{folder}/{pathlib.Path(r['name']).stem}.png", "stego_method": method, "alpha": float(alpha)}
-               for r in covers(data_dir, twin=(method, float(alpha), int(stream)), **shared)]
-    else:
-        try:
-            res = stegos(data_dir, stego_method=stego_method, alpha=alpha, **shared)
-        except KeyError as e:
-            raise ValueError(f"split {split!r} lists no stego rows (no {e.args[0]!r} column): use simulate=True or a split that names them") from e
-    rows = pd.DataFrame([{k: v for k, v in r.items() if k != "counts"} for r in res])
-    for col in ("stego_method", "alpha"):
-        if col not in rows:
-            rows[col] = np.nan
-    rows = rows[["name", "height", "width", "stego_method", "alpha"]]
+    res = file_set(*_iterators(batch_size), data_dir, stego_method, alpha, simulate, stream, **shared)
+    rows = file_rows(res, ("counts",))
     return rows, features(np.stack([r["counts"] for r in res]), order, T, normalise)
 
 
